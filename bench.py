@@ -5,7 +5,12 @@ One "step" = one pass of the hot path over one batch: every one of the B streams
 advances by one 10 ms frame (480 samples in -> 480 samples out), i.e. B stream-frames.
 Inputs (int16 PCM, the CLI's format) are resident in HBM before the timed region starts.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--streams B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--streams B] [--dump-outputs DIR] [--full]
+
+A plain run measures the headline alone: setup, W warm-up steps, K timed steps, the outputs of the last step when
+--dump-outputs is given, and the result line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).
+Everything else — CPU baseline, parity against the CPU oracle, per-kernel events and rooflines, the other
+configurations, the sustained and paced real-time legs, the detail file — runs with --full.
 
 N > 1: `python bench.py --gpus N` launches its own N ranks through torch.distributed.run (one rank per GPU); when
 the driver launches the ranks itself (WORLD_SIZE/RANK in the environment) the script joins that world instead.
@@ -521,7 +526,7 @@ def drop_in_single_stream(frames=1000):
     import tempfile
     import numpy as np
     from percepnet_amd import synth
-    exe = os.path.join(ROOT, "percepnet_amd", "lib", "percepNet_run_relinked")
+    from oracle.oracle import RELINKED as exe
     if not os.path.exists(exe):
         return None
     from percepnet_amd import weights
@@ -542,7 +547,7 @@ def drop_in_single_stream(frames=1000):
                 best = dt if best is None else min(best, dt)
             times[n] = best
     return {"ms_per_frame": round(1e3 * (times[100 + frames] - times[100]) / frames, 4), "frames": frames,
-            "what": "lib/percepNet_run_relinked (reference main.cpp, untouched) on one stream: wall(1100 frames) - wall(100 frames)",
+            "what": "oracle/_ref/percepNet_run_relinked (reference main.cpp, untouched) on one stream: wall(1100 frames) - wall(100 frames)",
             "wall_s": {str(k): round(v, 3) for k, v in times.items()}}
 
 
@@ -663,6 +668,30 @@ def write_detail(res, path):
         return None
 
 
+DUMP_MAX_STREAMS = 16384    # 16 384 x (480 + 68) x 4 B = 36 MB, inside the 64 MB a dump may take
+DUMP_SEED = 0
+
+
+def dump_sample(B):
+    """Batch slots whose outputs --dump-outputs writes: all of them up to DUMP_MAX_STREAMS, else a fixed seeded sample (sorted)."""
+    import numpy as np
+    if B <= DUMP_MAX_STREAMS:
+        return np.arange(B)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(B, DUMP_MAX_STREAMS, replace=False))
+
+
+def dump_outputs(d, out, gr):
+    """What the last timed step handed its caller — int16 PCM [B, 480] and the g|r rows [B, 68] — as float32 .npy files in d."""
+    import numpy as np
+    import torch
+    idx = dump_sample(out.shape[0])
+    sel = torch.from_numpy(idx).to(out.device)
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "pcm.npy"), out.index_select(0, sel).float().cpu().numpy())
+    np.save(os.path.join(d, "gr.npy"), gr.index_select(0, sel).float().cpu().numpy())
+    np.save(os.path.join(d, "stream_index.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None, help="ranks (one per GPU); default: the launched world, else 1")
@@ -674,10 +703,18 @@ def main():
                          "its largest window; the W warm-up and K timed steps then run on steady-state stream state")
     ap.add_argument("--streams", type=int, default=65536, help="concurrent streams per GPU")
     ap.add_argument("--full", action="store_true",
-                    help="everything round 5's default did (several minutes): the capacity search over the 512-stream grid with a 20 s "
-                         "confirmation run, the split-precision side configuration, the 65 536-distinct-streams leg, the relinked reference CLI, "
-                         "the unpinned CPU pool.  The default run is sized to finish in about a minute")
-    ap.add_argument("--detail-out", default=None, help="where the full record goes (default: gpurun_out/bench_detail.json under the repo)")
+                    help="every measurement besides the headline (a few minutes): the CPU baseline, per-kernel HIP events and rooflines, "
+                         "parity against the CPU oracle, configs[1] / configs[4] and the split-precision side configuration, the "
+                         "65 536-distinct-streams leg, the relinked reference CLI, the sustained loop, the paced real-time capacity search over "
+                         "the 512-stream grid with a 20 s confirmation run, the detail file.  The --no-* options below thin it out.  "
+                         "Without --full a run times the K steps and prints the line, nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (float32): "
+                         "pcm [S, 480] (int16 values) and gr [S, 68] of S streams, their batch slots in stream_index [S] (float64); "
+                         f"S = all streams up to {DUMP_MAX_STREAMS}, else a fixed seeded sample of that many (rank 0 only)")
+    ap.add_argument("--detail-out", default=None,
+                    help="where the full record goes (default with --full: bench_detail.json in the repository root; without --full "
+                         "none is written unless this is given)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true", help="skip per-kernel HIP events")
     ap.add_argument("--no-parity", action="store_true", help="skip the measured max|delta| vs the CPU oracle")
@@ -702,6 +739,9 @@ def main():
     ap.add_argument("--share-gpu", action="store_true",
                     help="testing aid on a 1-GPU box: every rank uses cuda:0 (use with --backend gloo)")
     a = ap.parse_args()
+    if not a.full:
+        # a plain run does what its headline figure needs and nothing else: no per-kernel events in the timed region, no legs after it
+        a.no_cpu_baseline = a.no_profile = a.no_parity = a.no_other_configs = a.no_sustained = a.no_realtime = True
     t_wall0 = time.perf_counter()
     cpu_fn = lambda: cpu_baseline(full=a.full)                 # noqa: E731
 
@@ -762,7 +802,8 @@ def main():
     # synthetic input, resident in HBM: a pool of 64 distinct streams (voiced / bursts+silence /
     # two-tone / loud) tiled over the batch with per-replica sample rotation
     P = min(B, 64)
-    pool_np = synth.synth_batch(P, T, base_seed=synth.BASE_SEED + 7919 * rank)
+    # the same streams either way; worker processes only when the run is long enough for one core to take seconds
+    pool_np = (synth.synth_batch_parallel if T > 200 else synth.synth_batch)(P, T, base_seed=synth.BASE_SEED + 7919 * rank)
     pool = torch.from_numpy(pool_np).to(dev)
     idx = torch.arange(B, device=dev) % P
     rot = (torch.arange(B, device=dev) // P) * 37
@@ -803,10 +844,12 @@ def main():
     rep = sharding.gather_report(dist, B * K, dt, label)      # SUM frames / MAX time; refuses duplicate devices
     fps, dt = rep["fps"], rep["seconds"]
 
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out, gr_buf)
     kt = {} if a.no_profile else ctx.kernel_times()
     checksum = int(out.to(torch.int64).abs().sum().item())     # keeps the result live / sanity
-    periods = read_periods(ctx, B)                              # the periods this run's last frame filtered at (dsp_roofline)
-    silent = read_silent(ctx, B)                                # ... and how many streams it flagged silent (back end: no P read)
+    periods = read_periods(ctx, B) if kt else None              # the periods this run's last frame filtered at (dsp_roofline)
+    silent = read_silent(ctx, B) if kt else None                # ... and how many streams it flagged silent (back end: no P read)
     if os.environ.get("PN_BENCH_DUMP"):                         # debugging aid: last frame's PCM of this rank
         import numpy as _np
         _np.save(os.environ["PN_BENCH_DUMP"], out.cpu().numpy())
@@ -947,7 +990,9 @@ def main():
             res["realtime_streams_p99"] = agg.get("streams_total") if agg.get("all_ranks_met_every_deadline") else None
         res.update(side)
         res["bench_wall_s"] = round(time.perf_counter() - t_wall0, 1)
-        detail = write_detail(res, a.detail_out or os.path.join(ROOT, "gpurun_out", "bench_detail.json"))
+        detail = None
+        if a.full or a.detail_out:
+            detail = write_detail(res, a.detail_out or os.path.join(ROOT, "bench_detail.json"))
         print(compact_line(res, detail and os.path.relpath(detail, ROOT)), flush=True)
     ctx.close()
     model.close()

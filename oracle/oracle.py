@@ -14,6 +14,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ORACLE_SO = os.path.join(HERE, "liboracle.so")
 REF_SO = os.path.join(HERE, "_ref", "libpercepnet_ref.so")
 REF_AVX2_SO = os.path.join(HERE, "_ref", "libpercepnet_ref_avx2.so")   # "best-effort CPU" footnote build, timing only
+RELINKED = os.path.join(HERE, "_ref", "percepNet_run_relinked")          # reference src/main.cpp, untouched, linked against PN_LIB
+PN_LIB = os.path.join(os.path.dirname(HERE), "percepnet_amd", "lib", "libpercepnet_hip.so")
 
 c_f = ctypes.POINTER(ctypes.c_float)
 c_s = ctypes.POINTER(ctypes.c_short)
@@ -25,12 +27,16 @@ def _fp(a):
 
 
 def build(force=False):
-    """Compile the C restatement, and the reference itself when /root/reference is present."""
+    """Compile the C restatement, and the reference itself when /root/reference is present (its CLI relinked against
+    the HIP library too, once that library is built)."""
     if force or not os.path.exists(ORACLE_SO) or os.path.getmtime(ORACLE_SO) < os.path.getmtime(
             os.path.join(HERE, "percepnet_oracle.c")):
         subprocess.check_call(["make", "-s", "-C", HERE, "oracle"])
     if os.path.isdir("/root/reference/src") and (force or not os.path.exists(REF_SO) or not os.path.exists(REF_AVX2_SO)):
         subprocess.check_call(["make", "-s", "-C", HERE, "ref"])
+    if os.path.isdir("/root/reference/src") and os.path.exists(PN_LIB) and (
+            force or not os.path.exists(RELINKED) or os.path.getmtime(RELINKED) < os.path.getmtime(PN_LIB)):
+        subprocess.check_call(["make", "-s", "-C", HERE, "relinked"])
 
 
 class Oracle:

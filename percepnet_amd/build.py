@@ -18,8 +18,6 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libpercepnet_hip.so")
 RUN = os.path.join(LIBDIR, "percepnet_run")
 EXPORT_MAP = os.path.join(CSRC, "libpercepnet_hip.map")    # ld version script: the export list (everything else is local)
-RELINKED = os.path.join(LIBDIR, "percepNet_run_relinked")    # reference src/main.cpp, untouched, linked against LIB
-REFERENCE_SRC = os.environ.get("PERCEPNET_REFERENCE_SRC", "/root/reference/src")
 SOURCES = ["pn_tables.cpp", "pn_model.cpp", "pn_pack.cpp", "pn_dsp_fe.hip", "pn_dsp_fe_g2.hip", "pn_dsp_fe_split_s.hip", "pn_dsp_fe_split_p.hip", "pn_dsp.hip", "pn_nn.hip", "pn_nn_small.hip", "pn_nn_x3.hip", "pn_nn_d.hip", "pn_nn_n48.hip", "pn_targets.hip", "pn_state.hip", "pn_active.hip", "pn_context.cpp",
            "pn_featgen.cpp", "rnnoise_compat.cpp"]
 # percepnet_run.cpp / percepnet_featgen.cpp (the CLIs) are linked separately against the library
@@ -272,16 +270,8 @@ def build(force=False, verbose=True):
             if verbose:
                 print(" ".join(cmd), flush=True)
             subprocess.check_call(cmd)
-    # INTEGRATION.md level 1, built for real: the reference's own UNTOUCHED main.cpp (the percepNet_run CLI) compiled
-    # where it lies and linked against this library instead of the reference's objects.  Only possible where
-    # /root/reference exists (this container); the binary travels to the GPU box like the .so (tests/test_gpu_parity.py).
-    ref_main = os.path.join(REFERENCE_SRC, "main.cpp")
-    if os.path.exists(ref_main) and (force or _stale(RELINKED, [ref_main, LIB])):
-        cmd = ["g++", "-std=c++11", "-O3", "-w", "-I" + REFERENCE_SRC, ref_main, "-o", RELINKED, "-L" + LIBDIR,
-               "-lpercepnet_hip", "-Wl,-rpath,$ORIGIN"]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.check_call(cmd)
+    # INTEGRATION.md level 1 (the reference's untouched main.cpp relinked against this library) is built by oracle/Makefile
+    # `relinked` into oracle/_ref/, with the other binaries made from the reference's sources
     with open(os.path.join(LIBDIR, "BUILD_INFO.txt"), "w") as f:
         f.write(toolchain_info(hipcc) + "\nflags: " + " ".join(FLAGS) + "\n")
         f.write("DSP kernel resources (hipcc -Rpass-analysis=kernel-resource-usage):\n")

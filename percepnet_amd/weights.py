@@ -193,17 +193,24 @@ def default_blob(seed=1234, gain=1.0, cache_dir=None):
     if key in _CACHE:
         return _CACHE[key]
     cache_dir = cache_dir or os.environ.get("PERCEPNET_CACHE", "/tmp/percepnet_amd_cache")
-    os.makedirs(cache_dir, exist_ok=True)
     path = os.path.join(cache_dir, f"pnw1_seed{seed}_gain{gain:g}.bin")
+    blob = None
     if os.path.exists(path):
-        with open(path, "rb") as f:
-            blob = f.read()
-    else:
+        try:
+            with open(path, "rb") as f:
+                blob = f.read()
+        except OSError:
+            blob = None
+    if blob is None:
         blob = pack_blob(modules_to_layers(build_torch_modules(seed), gain))
-        tmp = path + f".{os.getpid()}.tmp"
-        with open(tmp, "wb") as f:
-            f.write(blob)
-        os.replace(tmp, path)
+        try:                                   # the cache is an optimisation: a directory we cannot write is no error
+            os.makedirs(cache_dir, exist_ok=True)
+            tmp = path + f".{os.getpid()}.tmp"
+            with open(tmp, "wb") as f:
+                f.write(blob)
+            os.replace(tmp, path)
+        except OSError:
+            pass
     _CACHE[key] = blob
     return blob
 

@@ -218,6 +218,14 @@ def test_the_printed_line_is_compact_and_complete():
     assert len(line) <= bench.LINE_LIMIT and all(k in json.loads(line) for k in REQUIRED_LINE_KEYS)
 
 
+def test_dump_sample_is_fixed_and_within_the_size_limit():
+    """--dump-outputs writes every stream of a small batch, and of a large one the same seeded sample every time, in 64 MB."""
+    a, b = bench.dump_sample(65536), bench.dump_sample(65536)
+    assert np.array_equal(a, b) and len(a) == bench.DUMP_MAX_STREAMS and (np.diff(a) > 0).all() and 0 <= a[0] and a[-1] < 65536
+    assert len(a) * (480 + 68) * 4 + len(a) * 8 <= 64 * 10**6
+    assert np.array_equal(bench.dump_sample(1000), np.arange(1000))
+
+
 def test_profile_summaries_keep_only_the_steady_state_frames(tmp_path):
     """tools/summarize_prof.py --frames-total W+K --frames-keep K: of every (kernel, grid) only the launches of the last K frames
     count — the first frames of a run from the zero state filter at the degenerate period and move more bytes."""

@@ -17,13 +17,13 @@ LINE_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_ste
 
 
 def _bench(*args):
-    """Runs bench.py; checks the ONE printed line (the driver's record: compact, complete, agreeing with the full record) and returns
+    """Runs bench.py --full; checks the ONE printed line (the driver's record: compact, complete, agreeing with the full record) and returns
     the full record from the detail file the line points at."""
     import tempfile
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     with tempfile.TemporaryDirectory() as d:
         detail = os.path.join(d, "detail.json")
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--detail-out", detail, *args], capture_output=True, text=True,
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--detail-out", detail, *args], capture_output=True, text=True,
                              timeout=900, env=env)
         assert out.returncode == 0, out.stderr[-3000:]
         lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -71,6 +71,40 @@ def test_single_rank_line_has_measured_parity_and_roofline():
     assert r["prime_frames"] == 12 and r["parity"]["pcm_samples_checked"] == 64 * (12 + 9) * 480
     assert r["roofline"]["bound"] == "mfma" and 0 < r["roofline"]["frac"] < 1
     assert abs(r["value"] * 100 - r["frames_per_s"]) < 10
+
+
+def test_plain_run_times_the_steps_and_dumps_the_last_outputs(tmp_path):
+    """Without --full: the line carries the headline (no legs after the timed steps, no detail file), --steps sets the timed
+    steps, and --dump-outputs writes the last timed step's PCM and g|r rows — the same bits from run to run, and the same
+    as the oracle gives for the pool streams in their unrotated slots."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    lines = []
+    for i in range(2):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--streams", "128", "--steps", "7", "--warmup", "2",
+                              "--dump-outputs", str(tmp_path / f"d{i}")], capture_output=True, text=True, timeout=600, env=env)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines.append(json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1]))
+    r = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in r, k
+    assert r["steps"] == 7 and r["warmup"] == 2 and r["ms_per_step"] > 0 and r["higher_is_better"] is True
+    assert abs(r["value"] * 100 - 128 * 7 / (r["ms_per_step"] * 7e-3)) < 1e-2 * r["value"] * 100
+    assert not {"cpu_baseline", "roofline", "dsp_roofline", "sustained", "realtime", "other_configs", "detail"} & set(r)
+    d0, d1 = tmp_path / "d0", tmp_path / "d1"
+    assert sorted(os.listdir(d0)) == ["gr.npy", "pcm.npy", "stream_index.npy"]
+    for name in ("pcm", "gr", "stream_index"):
+        a, b = np.load(d0 / f"{name}.npy"), np.load(d1 / f"{name}.npy")
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+    pcm, gr = np.load(d0 / "pcm.npy"), np.load(d0 / "gr.npy")
+    assert pcm.shape == (128, 480) and gr.shape == (128, 68) and np.array_equal(np.load(d0 / "stream_index.npy"), np.arange(128))
+    assert np.array_equal(pcm, np.round(pcm)) and np.abs(pcm).max() <= 32768 and np.abs(pcm).max() > 0
+    # slots 0..63 carry the 64 pool streams unrotated: the last timed step is frame 12 + 2 + 7 - 1 = 20, its PCM output frame 19
+    from oracle.oracle import Oracle
+    from percepnet_amd import synth, weights
+    ro, rg, _, _ = Oracle(weights.default_blob(1234)).run_batch(synth.synth_batch(64, 21), want_feat=False)
+    assert np.abs(pcm[:64] - ro[:, 19 * 480:20 * 480]).max() <= 1
+    assert np.abs(gr[:64] - rg[:, 20]).max() <= 2e-5
 
 
 def test_paced_real_time_run_through_the_pipelined_host_path():

@@ -617,17 +617,17 @@ def test_rnn_state_roundtrip_and_compute_rnn_symbol(blob, oracle):
 
 def test_relinked_reference_cli(blob, oracle, tmp_path):
     """INTEGRATION.md level 1 for real: the reference's UNTOUCHED src/main.cpp, compiled where it lies and linked
-    against libpercepnet_hip.so (percepnet_amd/build.py -> lib/percepNet_run_relinked), run as `percepNet_run in out`
+    against libpercepnet_hip.so (oracle/Makefile `relinked` -> oracle/_ref/percepNet_run_relinked), run as `percepNet_run in out`
     with the model from PERCEPNET_MODEL: out.pcm and ./feature_test.raw against the oracle."""
     import subprocess
-    from percepnet_amd import build
-    if not os.path.exists(build.RELINKED):
-        pytest.skip("lib/percepNet_run_relinked was not built (needs /root/reference at build time)")
+    from oracle.oracle import RELINKED
+    if not os.path.exists(RELINKED):
+        pytest.skip("oracle/_ref/percepNet_run_relinked was not built (needs the reference's sources at build time)")
     (tmp_path / "m.pnw").write_bytes(blob)
     a = synth.synth_stream(3, 30)
     (tmp_path / "a.pcm").write_bytes(a.tobytes())
     env = dict(os.environ, PERCEPNET_MODEL=str(tmp_path / "m.pnw"))
-    r = subprocess.run([build.RELINKED, "a.pcm", "ao.pcm"], cwd=tmp_path, capture_output=True, text=True, timeout=300, env=env)
+    r = subprocess.run([RELINKED, "a.pcm", "ao.pcm"], cwd=tmp_path, capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr
     assert "INERT" not in r.stderr
     ao = np.fromfile(tmp_path / "ao.pcm", np.int16); tap = np.fromfile(tmp_path / "feature_test.raw", np.float32).reshape(-1, 68)
@@ -635,7 +635,7 @@ def test_relinked_reference_cli(blob, oracle, tmp_path):
     assert ao.size == 29 * 480 and np.abs(ao.astype(np.int32) - ro.astype(np.int32)).max() <= PCM_TOL_LSB
     assert np.abs(ro).max() > 1000
     assert tap.shape == (30, 68) and np.abs(tap - rg).max() <= GR_TOL
-    r = subprocess.run([build.RELINKED, "a.pcm", "as.pcm"], cwd=tmp_path, capture_output=True, text=True, timeout=300,
+    r = subprocess.run([RELINKED, "a.pcm", "as.pcm"], cwd=tmp_path, capture_output=True, text=True, timeout=300,
                        env=dict(env, PERCEPNET_STRICT="1"))
     assert r.returncode == 0 and np.array_equal(np.fromfile(tmp_path / "as.pcm", np.int16), ro)      # bit-exact in STRICT
 

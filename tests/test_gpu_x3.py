@@ -194,7 +194,7 @@ def test_x3_through_the_cli_and_the_rnnoise_entry_points(blob, oracle, tmp_path)
         got = np.fromfile(tmp_path / f"o{i}.pcm", np.int16)
         ref = oracle.run_pcm(x)[0]
         assert got.size == ref.size and np.abs(got.astype(np.int32) - ref.astype(np.int32)).max() <= PCM_TOL_LSB, i
-    exe = os.path.join(os.path.dirname(build.RUN), "percepNet_run_relinked")
+    from oracle.oracle import RELINKED as exe
     if os.path.exists(exe):
         env = dict(os.environ, PERCEPNET_MODEL=str(tmp_path / "m.pnw"), PERCEPNET_X3="1", PERCEPNET_SELFTEST="2")
         r = subprocess.run([exe, "i0.pcm", "r0.pcm"], cwd=tmp_path, env=env, capture_output=True, text=True, timeout=300)

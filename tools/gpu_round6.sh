@@ -20,8 +20,8 @@ if [ "$MODE" = "all" ] || [ "$MODE" = "bench" ]; then
   cp $O/prof_summary/${TAG}_* $R/profiles/ 2>/dev/null
 fi
 if [ "$MODE" != "tests" ]; then
-  T0=$(date +%s); timeout 900 python bench.py --detail-out $O/bench_${TAG}_detail.json > $O/bench_$TAG.json 2> $O/bench_$TAG.err
-  echo "default bench.py wall seconds: $(( $(date +%s) - T0 )); line bytes: $(tail -1 $O/bench_$TAG.json | wc -c)" | tee $O/bench_${TAG}_wall.txt; tail -c 600 $O/bench_$TAG.err
+  T0=$(date +%s); timeout 900 python bench.py --full --detail-out $O/bench_${TAG}_detail.json > $O/bench_$TAG.json 2> $O/bench_$TAG.err
+  echo "bench.py --full wall seconds: $(( $(date +%s) - T0 )); line bytes: $(tail -1 $O/bench_$TAG.json | wc -c)" | tee $O/bench_${TAG}_wall.txt; tail -c 600 $O/bench_$TAG.err
   timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 | tee $O/smoke_$TAG.txt
   tail -1 $O/bench_$TAG.json
 fi
