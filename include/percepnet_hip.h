@@ -190,6 +190,75 @@ int pn_ctx_set_rnn_state_host(pn_ctx *ctx, const float *conv1, const float *conv
 int pn_ctx_get_rnn_state_host(pn_ctx *ctx, float *conv1, float *conv2, float *gru1, float *gru2, float *gru3,
                               float *gru_gb, float *gru_rb);
 
+/* ---- per-stream state records: moving a live stream between slots, contexts, devices, processes ------------------- */
+/* One record holds ALL the state of ONE stream — the DSP half (history, look-ahead, pitch and synthesis memory) and the
+   network half — so that a stream exported from one context and imported into another (any batch size, kernel family,
+   network mode, device, process) continues from exactly that state on the target's kernels: between contexts of one
+   network mode (in PN_NN_MFMA: any of its bit-identical kernel families) the moved stream's outputs are bit for bit those
+   it would have produced in its source context.  The record does not depend on the ring phases of the source: every ring is written in AGE order (oldest
+   entry first) and is scattered at the target's own frame counters.  Scratch (features, silence flags, the comb-filtered
+   spectrum, conv2 output, g|r, dead ring slots) and the operand shadows of the fp16 / split-precision / direct-operand
+   kernels are not state: the target re-derives the shadows of the imported rows from their fp32 values.
+
+   Layout (PN_STREAM_STATE_BYTES = 54 688 bytes, little-endian; every section starts on a 16-byte boundary):
+     header, 64 bytes: uint32 magic PN_STREAM_STATE_MAGIC | uint32 version PN_STREAM_STATE_VERSION | uint32 record bytes |
+                       int32 nn_mode of the source (informational, never checked) | 32-byte pn_model_digest of the model |
+                       16 zero bytes
+     body, fp32 (int32 where noted) words from PN_STREAM_STATE_HEADER_BYTES on, at these word offsets:
+       PN_SS_HIST        11 x 480   the last 11 input frames (the reference's comb_buf minus the frame to come)
+       PN_SS_SPEC         5 x 800   look-ahead spectra of the last 5 frames, bins 0..399 as (re, im) pairs
+       PN_SS_EY           5 x 36    their band energies (34 bands + 2 padding words)
+       PN_SS_CONV1        4 x 128   conv1 FIFO (RNNState layout, nnet_data.h:28-38; the same as pn_ctx_get_rnn_state_host)
+       PN_SS_CONV2        2 x 512   conv2 FIFO
+       PN_SS_GRU          4 x 512   gru1, gru2, gru3, gru_gb states
+       PN_SS_GRU_RB       128       gru_rb state
+       PN_SS_SYNTH        480       synthesis overlap memory
+       PN_SS_TAIL         4         last_gain (fp32) | last_period (int32) | 2 zero words */
+#define PN_STREAM_STATE_MAGIC 0x53534e50u      /* "PNSS" */
+#define PN_STREAM_STATE_VERSION 1
+#define PN_STREAM_STATE_HEADER_BYTES 64
+#define PN_SS_HIST 0
+#define PN_SS_SPEC 5280
+#define PN_SS_EY 9280
+#define PN_SS_CONV1 9460
+#define PN_SS_CONV2 9972
+#define PN_SS_GRU 10996
+#define PN_SS_GRU_RB 13044
+#define PN_SS_SYNTH 13172
+#define PN_SS_TAIL 13652
+#define PN_SS_BODY_WORDS 13656
+#define PN_STREAM_STATE_BYTES (PN_STREAM_STATE_HEADER_BYTES + 4 * PN_SS_BODY_WORDS)
+/* Why a record is refused (pn_stream_state_check's return value, d_status of pn_ctx_import_streams). */
+enum {
+  PN_SS_OK = 0,
+  PN_SS_BAD_MAGIC = -1,
+  PN_SS_BAD_VERSION = -2,
+  PN_SS_BAD_SIZE = -3,      /* a buffer of the wrong size, or a header that names another record size */
+  PN_SS_BAD_MODEL = -4,     /* written under another model (pn_model_digest differs) */
+  PN_SS_BAD_ARG = -5        /* NULL record or model */
+};
+size_t pn_stream_state_bytes(void);            /* PN_STREAM_STATE_BYTES */
+/* Host only, needs no GPU: is `bytes` bytes at `record` one record that a context of `model` accepts?  PN_SS_OK or a
+   PN_SS_BAD_* code (pn_last_error says why).  For callers that receive records from elsewhere. */
+int pn_stream_state_check(const void *record, size_t bytes, const pn_model *model);
+/* Export streams ids[0..n) (host array, in range, duplicates allowed) into records [n][PN_STREAM_STATE_BYTES] at the
+   16-byte aligned DEVICE address d_records.  Asynchronous on the context's stream, ordered like pn_ctx_reset_streams: the
+   records hold the state between the frames submitted before and after the call (on the pipelined host path too); the
+   caller orders its own use of d_records (pn_ctx_synchronize or an event on the context's stream). */
+int pn_ctx_export_streams(pn_ctx *ctx, const int32_t *ids, int n, void *d_records);
+/* Import records [n][PN_STREAM_STATE_BYTES] (16-byte aligned device address) into streams ids[0..n) (host array, DISTINCT
+   ids in range: otherwise -1 and nothing is launched).  Asynchronous and ordered like the export.  Each header is checked
+   on the device against this context's model digest, the version and the size: d_status[i] (device int32 [n], required)
+   receives PN_SS_OK when record i was imported, a PN_SS_BAD_* code when it was refused — a refused record leaves its
+   stream exactly as it was.  The other streams of the context are not touched (their operand shadows neither).  The
+   first frame processed after the import continues the imported streams. */
+int pn_ctx_import_streams(pn_ctx *ctx, const int32_t *ids, int n, const void *d_records, int32_t *d_status);
+/* The same with host records, synchronous (frames in flight on the pipelined host path are completed first).  The host
+   import checks every header BEFORE anything is launched and is all-or-nothing: one bad record (or id) refuses the call
+   and leaves the context untouched. */
+int pn_ctx_export_streams_host(pn_ctx *ctx, const int32_t *ids, int n, void *h_records);
+int pn_ctx_import_streams_host(pn_ctx *ctx, const int32_t *ids, int n, const void *h_records);
+
 /* ---- per-kernel timing (HIP events on the context's stream) ------------------------------- */
 /* When enabled, every launch of the named kernel families is bracketed by events. */
 int pn_ctx_set_profiling(pn_ctx *ctx, int enable);

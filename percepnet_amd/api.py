@@ -14,6 +14,9 @@ LIB_PATH = os.path.join(HERE, "lib", "libpercepnet_hip.so")
 
 NN_MFMA, NN_STRICT, NN_MFMA_F16, NN_MFMA_X3 = 0, 1, 2, 3
 FRAME = 480
+# per-stream state records (include/percepnet_hip.h): size, and the PN_SS_* verdicts of a refused record
+STREAM_STATE_BYTES = 54688
+SS_OK, SS_BAD_MAGIC, SS_BAD_VERSION, SS_BAD_SIZE, SS_BAD_MODEL, SS_BAD_ARG = 0, -1, -2, -3, -4, -5
 
 _vp = ctypes.c_void_p
 _lib = None
@@ -87,6 +90,13 @@ def load_library():
     L.pn_ctx_compute_rnn_host.argtypes = [_vp, _vp, _vp]
     L.pn_ctx_set_rnn_state_host.argtypes = [_vp] * 8
     L.pn_ctx_get_rnn_state_host.argtypes = [_vp] * 8
+    if hasattr(L, "pn_stream_state_bytes"):
+        L.pn_stream_state_bytes.restype = ctypes.c_size_t
+        L.pn_stream_state_bytes.argtypes = []
+        L.pn_stream_state_check.argtypes = [_vp, ctypes.c_size_t, _vp]
+        for name in ("pn_ctx_export_streams", "pn_ctx_export_streams_host", "pn_ctx_import_streams_host"):
+            getattr(L, name).argtypes = [_vp, _vp, ctypes.c_int, _vp]
+        L.pn_ctx_import_streams.argtypes = [_vp, _vp, ctypes.c_int, _vp, _vp]
     L.pn_ctx_debug_copy.restype = ctypes.c_longlong
     L.pn_ctx_debug_copy.argtypes = [_vp, ctypes.c_int, _vp, ctypes.c_longlong]
     L.pn_ctx_set_profiling.argtypes = [_vp, ctypes.c_int]
@@ -283,6 +293,37 @@ class Context:
                 for k, n in self.RNN_STATE_SHAPES]
         self._chk(self.L.pn_ctx_set_rnn_state_host(self.h, *[a.ctypes.data if a is not None else None for a in arrs]))
 
+    # per-stream state records: moving live streams between slots, contexts, devices and processes
+    @staticmethod
+    def _ids(ids):
+        return np.ascontiguousarray(np.asarray(ids, dtype=np.int32).ravel())
+
+    def export_streams(self, ids):
+        """-> uint8 [n, STREAM_STATE_BYTES]: the whole state of the streams `ids` (pn_ctx_export_streams_host)."""
+        a = self._ids(ids)
+        rec = np.empty((a.size, STREAM_STATE_BYTES), np.uint8)
+        self._chk(self.L.pn_ctx_export_streams_host(self.h, a.ctypes.data, int(a.size), rec.ctypes.data))
+        return rec
+
+    def import_streams(self, ids, records):
+        """Records from export_streams (any context of the same model) into the distinct streams `ids`; all or nothing
+        (pn_ctx_import_streams_host)."""
+        a = self._ids(ids)
+        rec = np.ascontiguousarray(records, dtype=np.uint8)
+        if rec.size != a.size * STREAM_STATE_BYTES:
+            raise PercepNetError(f"{rec.size} record bytes for {a.size} streams (a record has {STREAM_STATE_BYTES})")
+        self._chk(self.L.pn_ctx_import_streams_host(self.h, a.ctypes.data, int(a.size), rec.ctypes.data))
+
+    def export_streams_dev(self, ids, d_records):
+        """Device form (async on the context's stream): records [n][STREAM_STATE_BYTES] at device address d_records."""
+        a = self._ids(ids)
+        self._chk(self.L.pn_ctx_export_streams(self.h, a.ctypes.data, int(a.size), d_records))
+
+    def import_streams_dev(self, ids, d_records, d_status):
+        """Device form (async): d_status (device int32 [n]) receives SS_OK or the SS_BAD_* verdict of each record."""
+        a = self._ids(ids)
+        self._chk(self.L.pn_ctx_import_streams(self.h, a.ctypes.data, int(a.size), d_records, d_status))
+
     def debug_copy(self, which, n_floats):
         """Internal device buffer `which` (see pn_ctx_debug_copy in percepnet_hip.h) -> float32[n_floats] (tests/tools)."""
         buf = np.empty(n_floats, np.float32)
@@ -307,6 +348,14 @@ class Context:
             self._chk(self.L.pn_ctx_kernel_time(self.h, name, ctypes.byref(ms), ctypes.byref(n)))
             out[name.decode()] = (ms.value, n.value)
         return out
+
+
+def stream_state_check(record, model):
+    """PN_SS_OK (0) or the PN_SS_BAD_* verdict a context of `model` gives the bytes `record` (host only, no GPU)."""
+    L = load_library()
+    b = np.ascontiguousarray(np.frombuffer(bytes(record), np.uint8)) if not isinstance(record, np.ndarray) else \
+        np.ascontiguousarray(record, dtype=np.uint8)
+    return int(L.pn_stream_state_check(b.ctypes.data if b.size else None, b.size, model.h))
 
 
 class FeatGen:

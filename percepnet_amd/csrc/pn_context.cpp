@@ -419,34 +419,41 @@ static int pipe_drain(pn_ctx *c);
 extern "C" int pn_ctx_reset(pn_ctx *c) { if (!c) return -1; PN_ON_DEVICE(c); if (pipe_drain(c)) return -1; return zero_state(c); }
 // rnnoise_init for a subset of the streams (denoise.cpp:259-280): every row of stream s in every ring slot / ping-pong half
 // of every state buffer goes to zero (pn_state.hip says why that is a fresh stream whatever the ring phases are)
+// ids[0..n) (host) -> c->d_ids through the pinned slot ring, asynchronously on the context's stream (frames may be in flight);
+// the launches that read c->d_ids follow on the same stream.  NULL on failure.  (The caller is on the context's device.)
+static const int *stage_ids(pn_ctx *c, const int32_t *ids, int n) {
+#define SI_CHECK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { pn_set_error("%s failed: %s", #expr, hipGetErrorString(_e)); return NULL; } } while (0)
+  if (c->ids_cap < n) {
+    // (the old, smaller buffers stay in allocs until destroy: kernels of an earlier call may still be reading them)
+    const int cap = n < 1024 ? 1024 : n;
+    int *p = NULL;
+    SI_CHECK(hipMalloc((void **)&p, (size_t)cap * sizeof(int)));
+    c->allocs.push_back(p); c->d_ids = p;
+    for (auto &sl : c->id_slot) {
+      if (sl.ev) SI_CHECK(hipEventSynchronize(sl.ev));
+      if (sl.h) hipHostFree(sl.h);
+      sl.h = NULL;
+      SI_CHECK(hipHostMalloc((void **)&sl.h, (size_t)cap * sizeof(int), hipHostMallocDefault));
+      if (!sl.ev) SI_CHECK(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
+    }
+    c->ids_cap = cap;
+  }
+  pn_ctx::IdSlot &sl = c->id_slot[c->id_calls++ & 3];
+  SI_CHECK(hipEventSynchronize(sl.ev));                 // the copy issued from this slot four calls ago has executed
+  memcpy(sl.h, ids, (size_t)n * sizeof(int));
+  SI_CHECK(hipMemcpyAsync(c->d_ids, sl.h, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  SI_CHECK(hipEventRecord(sl.ev, c->stream));
+  return c->d_ids;
+#undef SI_CHECK
+}
 extern "C" int pn_ctx_reset_streams(pn_ctx *c, const int32_t *ids, int n) {
   if (!c || n < 0 || (n > 0 && !ids)) { pn_set_error("bad argument"); return -1; }
   if (n == 0) return 0;
   for (int i = 0; i < n; i++) if (ids[i] < 0 || ids[i] >= c->B) { pn_set_error("stream id %d out of range [0, %d)", ids[i], c->B); return -1; }
   PN_ON_DEVICE(c);
-  if (c->ids_cap < n) {
-    // (the old, smaller buffers stay in allocs until destroy: kernels of an earlier call may still be reading them)
-    const int cap = n < 1024 ? 1024 : n;
-    int *p = NULL;
-    PN_HIP_CHECK(hipMalloc((void **)&p, (size_t)cap * sizeof(int)));
-    c->allocs.push_back(p); c->d_ids = p;
-    for (auto &sl : c->id_slot) {
-      if (sl.ev) PN_HIP_CHECK(hipEventSynchronize(sl.ev));
-      if (sl.h) hipHostFree(sl.h);
-      sl.h = NULL;
-      PN_HIP_CHECK(hipHostMalloc((void **)&sl.h, (size_t)cap * sizeof(int), hipHostMallocDefault));
-      if (!sl.ev) PN_HIP_CHECK(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
-    }
-    c->ids_cap = cap;
-  }
-  {
-    pn_ctx::IdSlot &sl = c->id_slot[c->id_calls++ & 3];
-    PN_HIP_CHECK(hipEventSynchronize(sl.ev));             // the copy issued from this slot four calls ago has executed
-    memcpy(sl.h, ids, (size_t)n * sizeof(int));
-    PN_HIP_CHECK(hipMemcpyAsync(c->d_ids, sl.h, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    PN_HIP_CHECK(hipEventRecord(sl.ev, c->stream));
-  }
-  hipStream_t st = c->stream; const int *d = c->d_ids;
+  const int *d = stage_ids(c, ids, n);
+  if (!d) return -1;
+  hipStream_t st = c->stream;
   const long long B = c->B, Bp = (long long)c->Bp;
   pn_launch_zero_rows(st, c->hist, PN_HIST_STRIDE, PN_HIST_STRIDE, 1, 0, d, n);
   pn_launch_zero_rows(st, c->synth, PN_FRAME, PN_FRAME, 1, 0, d, n);
@@ -1351,6 +1358,159 @@ extern "C" int pn_ctx_get_rnn_state_host(pn_ctx *c, float *conv1, float *conv2, 
   if (!c) { pn_set_error("NULL argument"); return -1; }
   float *g[4] = {gru1, gru2, gru3, gru_gb};
   return rnn_state_copy(c, false, conv1, conv2, g, gru_rb);
+}
+
+// ---- per-stream state records (pn_stream_state.hip; layout in include/percepnet_hip.h) ------------------------------
+// The header words a context writes (export) and expects (import; word 3, the source's nn_mode, is not compared).
+static void ss_header(uint32_t hdr[16], const unsigned char digest[32], int nn_mode) {
+  memset(hdr, 0, 16 * sizeof(uint32_t));
+  hdr[0] = PN_STREAM_STATE_MAGIC; hdr[1] = PN_STREAM_STATE_VERSION; hdr[2] = PN_STREAM_STATE_BYTES; hdr[3] = (uint32_t)nn_mode;
+  memcpy(&hdr[4], digest, 32);
+}
+static uint32_t ss_le32(const unsigned char *p) { return p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+// host twin of the import kernel's check (pn_stream_state.hip ss_check), same order of verdicts
+static int ss_check_host(const void *record, size_t bytes, const unsigned char digest[32]) {
+  const unsigned char *r = static_cast<const unsigned char *>(record);
+  if (bytes < 16) { pn_set_error("stream-state record of %zu bytes: a record has %d", bytes, PN_STREAM_STATE_BYTES); return PN_SS_BAD_SIZE; }
+  if (ss_le32(r) != PN_STREAM_STATE_MAGIC) { pn_set_error("not a stream-state record (magic 0x%08x)", ss_le32(r)); return PN_SS_BAD_MAGIC; }
+  if (ss_le32(r + 4) != PN_STREAM_STATE_VERSION) { pn_set_error("stream-state record version %u, this library reads %d", ss_le32(r + 4), PN_STREAM_STATE_VERSION); return PN_SS_BAD_VERSION; }
+  if (ss_le32(r + 8) != PN_STREAM_STATE_BYTES || bytes != PN_STREAM_STATE_BYTES) {
+    pn_set_error("stream-state record of %zu bytes (header: %u), a record has %d", bytes, ss_le32(r + 8), PN_STREAM_STATE_BYTES);
+    return PN_SS_BAD_SIZE;
+  }
+  if (memcmp(r + 16, digest, 32)) { pn_set_error("stream-state record written under another model (pn_model_digest differs)"); return PN_SS_BAD_MODEL; }
+  return PN_SS_OK;
+}
+extern "C" size_t pn_stream_state_bytes(void) { return PN_STREAM_STATE_BYTES; }
+extern "C" int pn_stream_state_check(const void *record, size_t bytes, const pn_model *m) {
+  if (!record || !m) { pn_set_error("NULL argument"); return PN_SS_BAD_ARG; }
+  return ss_check_host(record, bytes, m->sha256);
+}
+static const unsigned char *ctx_digest(const pn_ctx *c) { return std::get<0>(c->weights_key).data(); }
+
+// ids in range (and distinct when `distinct`)
+static int ss_ids_check(pn_ctx *c, const int32_t *ids, int n, bool distinct) {
+  std::vector<uint8_t> seen(distinct ? (size_t)c->B : 0, 0);
+  for (int i = 0; i < n; i++) {
+    if (ids[i] < 0 || ids[i] >= c->B) { pn_set_error("stream id %d out of range [0, %d)", ids[i], c->B); return -1; }
+    if (distinct && seen[ids[i]]++) { pn_set_error("stream id %d listed twice", ids[i]); return -1; }
+  }
+  return 0;
+}
+// The sections of a record at the context's CURRENT counters (those of the next frame to run): DSP rings follow t, the
+// network's follow tn (they differ after pn_ctx_compute_rnn_host).  Live entries oldest first from slot `first`.
+static void ss_args(pn_ctx *c, PnStreamStateArgs &a) {
+  memset(&a, 0, sizeof(a));
+  const long long B = c->B, Bp = (long long)c->Bp;
+  const int t12 = (int)((c->t + 1) % 12), t6 = (int)((c->t + 1) % 6), n5 = (int)((c->tn + 1) % 5), n3 = (int)((c->tn + 1) % 3),
+            n2 = (int)(c->tn & 1);
+  int k = 0;
+  auto sec = [&](float *base, long long row_stride, long long slot_stride, int slots, int first, int live, int cols, int off) {
+    a.sec[k++] = PnSsSection{base, row_stride, slot_stride, slots, first, live, cols, off};
+  };
+  sec(c->hist, PN_HIST_STRIDE, PN_FRAME, 12, t12, 11, PN_FRAME, PN_SS_HIST);      // slots back to back inside the row
+  sec(reinterpret_cast<float *>(c->yring), 2 * PN_SPEC_BINS, B * 2 * PN_SPEC_BINS, 6, t6, 5, 2 * PN_SPEC_BINS, PN_SS_SPEC);
+  sec(c->eyring, 36, B * 36, 6, t6, 5, 36, PN_SS_EY);
+  sec(c->c1ring, 128, Bp * 128, 5, n5, 4, 128, PN_SS_CONV1);
+  sec(c->c2ring, 512, Bp * 512, 3, n3, 2, 512, PN_SS_CONV2);
+  for (int g = 0; g < 4; g++) sec(c->gru[g], 512, Bp * 512, 2, n2, 1, 512, PN_SS_GRU + 512 * g);
+  sec(c->rb, 128, Bp * 128, 2, n2, 1, 128, PN_SS_GRU_RB);
+  sec(c->synth, PN_FRAME, 0, 1, 0, 1, PN_FRAME, PN_SS_SYNTH);                      // last: carries the tail
+  a.last_gain = c->last_gain; a.last_period = c->last_period;
+  ss_header(a.hdr, ctx_digest(c), c->nn_mode);
+}
+
+extern "C" int pn_ctx_export_streams(pn_ctx *c, const int32_t *ids, int n, void *d_records) {
+  if (!c || n < 0 || (n > 0 && (!ids || !d_records))) { pn_set_error("bad argument"); return -1; }
+  if (n == 0) return 0;
+  if ((uintptr_t)d_records & 15) { pn_set_error("records must be 16-byte aligned"); return -1; }
+  if (ss_ids_check(c, ids, n, false)) return -1;
+  PN_ON_DEVICE(c);
+  const int *d = stage_ids(c, ids, n);
+  if (!d) return -1;
+  PnStreamStateArgs a;
+  ss_args(c, a);
+  a.ids = d; a.rec = d_records;
+  pn_launch_ss_gather(c->stream, a, n);
+  PN_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int pn_ctx_import_streams(pn_ctx *c, const int32_t *ids, int n, const void *d_records, int32_t *d_status) {
+  if (!c || n < 0 || (n > 0 && (!ids || !d_records || !d_status))) { pn_set_error("bad argument"); return -1; }
+  if (n == 0) return 0;
+  if ((uintptr_t)d_records & 15) { pn_set_error("records must be 16-byte aligned"); return -1; }
+  if (ss_ids_check(c, ids, n, true)) return -1;
+  PN_ON_DEVICE(c);
+  const int *d = stage_ids(c, ids, n);
+  if (!d) return -1;
+  PnStreamStateArgs a;
+  ss_args(c, a);
+  a.ids = d; a.rec = const_cast<void *>(d_records); a.status = d_status;
+  pn_launch_ss_scatter(c->stream, a, n);
+  // operand shadows of the live entries, imported rows only (status 0), in this context's layout: fp16 / hi + lo planes of the
+  // conv FIFOs and the GRU / rb states (shadow-operand modes), fp32 fragments of the GRU / rb states (direct-operand family)
+  const bool x3 = c->nn_mode == PN_NN_MFMA_X3 || c->nn_mode == PN_NN_MFMA_F16;
+  const int np = c->nn_mode == PN_NN_MFMA_X3 ? 2 : 1;
+  const size_t Bp = c->Bp; const int64_t tn = c->tn;
+  int rc = 0;
+  auto resplit = [&](float *slot, int width) {
+    void *S = shadow(c, slot);
+    if (!S) return;                                    // no shadow of this buffer in this mode / family
+    if (x3) rc |= pn_launch_split_x3_rows(c->stream, slot, width, width, S, d, d_status, n, np);
+    else if (c->direct) rc |= pn_launch_split_d_rows(c->stream, slot, width, width, S, d, d_status, n);
+  };
+  for (int j = 0; j < 4; j++) resplit(c->c1ring + (size_t)((tn + 1 + j) % 5) * Bp * 128, 128);
+  for (int j = 0; j < 2; j++) resplit(c->c2ring + (size_t)((tn + 1 + j) % 3) * Bp * 512, 512);
+  for (int g = 0; g < 4; g++) resplit(c->gru[g] + (size_t)(tn & 1) * Bp * 512, 512);
+  resplit(c->rb + (size_t)(tn & 1) * Bp * 128, 128);
+  PN_HIP_CHECK(hipGetLastError());
+  return rc ? -1 : 0;
+}
+
+// Host forms: synchronous, frames in flight on the pipelined path are completed first (like rnn_state_copy).  The records
+// pass through a device buffer of their own size, freed before returning.
+extern "C" int pn_ctx_export_streams_host(pn_ctx *c, const int32_t *ids, int n, void *h_records) {
+  if (!c || n < 0 || (n > 0 && (!ids || !h_records))) { pn_set_error("bad argument"); return -1; }
+  if (n == 0) return 0;
+  if (ss_ids_check(c, ids, n, false)) return -1;
+  PN_ON_DEVICE(c);
+  if (pipe_drain(c)) return -1;
+  const size_t bytes = (size_t)n * PN_STREAM_STATE_BYTES;
+  void *d = NULL;
+  PN_HIP_CHECK(hipMalloc(&d, bytes));
+  int rc = pn_ctx_export_streams(c, ids, n, d);
+  if (!rc && hipMemcpyAsync(h_records, d, bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) { pn_set_error("record copy failed"); rc = -1; }
+  if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) { pn_set_error("export failed"); rc = -1; }
+  hipFree(d);
+  return rc;
+}
+extern "C" int pn_ctx_import_streams_host(pn_ctx *c, const int32_t *ids, int n, const void *h_records) {
+  if (!c || n < 0 || (n > 0 && (!ids || !h_records))) { pn_set_error("bad argument"); return -1; }
+  if (n == 0) return 0;
+  if (ss_ids_check(c, ids, n, true)) return -1;
+  for (int i = 0; i < n; i++)                          // all or nothing: every header before anything is launched
+    if (ss_check_host(static_cast<const char *>(h_records) + (size_t)i * PN_STREAM_STATE_BYTES, PN_STREAM_STATE_BYTES, ctx_digest(c))) {
+      std::string why = pn_last_error();
+      pn_set_error("record %d refused: %s", i, why.c_str());
+      return -1;
+    }
+  PN_ON_DEVICE(c);
+  if (pipe_drain(c)) return -1;
+  const size_t bytes = (size_t)n * PN_STREAM_STATE_BYTES;
+  void *d = NULL;
+  PN_HIP_CHECK(hipMalloc(&d, bytes + (size_t)n * sizeof(int32_t)));
+  int32_t *d_status = reinterpret_cast<int32_t *>(static_cast<char *>(d) + bytes);
+  std::vector<int32_t> status(n, 0);
+  int rc = hipMemcpyAsync(d, h_records, bytes, hipMemcpyHostToDevice, c->stream) == hipSuccess ? 0 : -1;
+  if (rc) pn_set_error("record copy failed");
+  if (!rc) rc = pn_ctx_import_streams(c, ids, n, d, d_status);
+  if (!rc && hipMemcpyAsync(status.data(), d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream) != hipSuccess) { pn_set_error("status copy failed"); rc = -1; }
+  if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) { pn_set_error("import failed"); rc = -1; }
+  hipFree(d);
+  for (int i = 0; i < n && !rc; i++)
+    if (status[i]) { pn_set_error("record %d refused on the device (%d) after passing the host check", i, status[i]); rc = -1; }
+  return rc;
 }
 
 // Debug tap (tests/tools only): copy an internal device buffer to the host.

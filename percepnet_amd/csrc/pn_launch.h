@@ -52,6 +52,25 @@ struct PnActiveArgs {
 void pn_launch_inactive_save(hipStream_t st, const PnActiveArgs &a, int n);
 int pn_launch_spin(hipStream_t st, long long ticks);     // one wave asleep for `ticks` of the 100 MHz wall clock (queue probe)
 void pn_launch_inactive_fixup(hipStream_t st, const PnActiveArgs &a, int n);
+// per-stream state records (pn_stream_state.hip): one section = one ring (or in-place buffer) of the record, its live entries
+// oldest first in slots first, first + 1, ... (mod slots); base + row * row_stride + slot * slot_stride = an entry of `cols`
+// floats (all multiples of 4), stored at body word rec_off of the record
+struct PnSsSection { float *base; long long row_stride, slot_stride; int slots, first, live, cols, rec_off; };
+enum { PN_SS_NSEC = 11 };          // history, spectra, band energies, conv1, conv2, gru1..gru_gb, gru_rb, synth (+ the tail)
+struct PnStreamStateArgs {
+  PnSsSection sec[PN_SS_NSEC];
+  float *last_gain; int *last_period;
+  const int *ids;                  // row of record i (device)
+  void *rec;                       // records [n][PN_STREAM_STATE_BYTES] (device, 16-byte aligned)
+  int *status;                     // scatter: verdict per record (device)
+  uint32_t hdr[16];                // gather: the header to write; scatter: the header to expect (word 3, nn_mode, unchecked)
+};
+void pn_launch_ss_gather(hipStream_t st, const PnStreamStateArgs &a, int n);
+void pn_launch_ss_scatter(hipStream_t st, const PnStreamStateArgs &a, int n);
+// operand shadows of the rows ids[i] whose status[i] == 0 (status may be NULL: every listed row) re-derived from their fp32
+// values: the row-list forms of pn_launch_split_x3 / pn_launch_split_d (same fragment indexing)
+int pn_launch_split_x3_rows(hipStream_t st, const float *src, int ld, int width, void *S, const int *d_ids, const int *d_status, int n, int np);
+int pn_launch_split_d_rows(hipStream_t st, const float *src, int ld, int width, void *S, const int *d_ids, const int *d_status, int n);
 // training-feature path (pn_targets.hip)
 void pn_launch_targets(hipStream_t st, const PnTables *T, int n_pairs, const float *ex_clean, const float *ex_noisy,
                        const float *ey_look_noisy, const float *aux_clean, const float *aux_noisy,

@@ -211,6 +211,14 @@ __global__ __launch_bounds__(NN_THREADS, 4 - RG) void pn_gru_d_kernel(
 
 // ---- fp32 rows -> fragment-order fp32 shadow (the first layer's output; RNN state loaded from the host) -----------
 // one thread per (row, slab pair q): reads 32 bytes (k = 8q .. 8q + 7 of a column tile), writes the kh = 0 and kh = 1 entries
+__device__ __forceinline__ void d_split_row_kg(const float *__restrict__ src, int ld, int width, uint4 *__restrict__ S, size_t row, int kgi) {
+  const fvec4 a = *reinterpret_cast<const fvec4 *>(src + row * ld + 8 * kgi);
+  const fvec4 c = *reinterpret_cast<const fvec4 *>(src + row * ld + 8 * kgi + 4);
+  const fvec4 e = {a.x, a.z, c.x, c.z}, o = {a.y, a.w, c.y, c.w};
+  uint4 *chunk = S + ((row >> 7) * (width >> 5) + (kgi >> 2)) * D_CHUNK;
+  chunk[(2 * (kgi & 3)) * 128 + (row & 127)] = __builtin_bit_cast(uint4, e);
+  chunk[(2 * (kgi & 3) + 1) * 128 + (row & 127)] = __builtin_bit_cast(uint4, o);
+}
 __global__ __launch_bounds__(256) void pn_split_d_kernel(const float *__restrict__ src, int ld, int width, uint4 *__restrict__ S,
                                                          int n_rows_padded) {
   const int kgs = width >> 3;                                    // 8-column groups per row
@@ -218,12 +226,17 @@ __global__ __launch_bounds__(256) void pn_split_d_kernel(const float *__restrict
   const size_t row = idx / kgs;
   const int kgi = (int)(idx - row * kgs);
   if (row >= (size_t)n_rows_padded) return;
-  const fvec4 a = *reinterpret_cast<const fvec4 *>(src + row * ld + 8 * kgi);
-  const fvec4 c = *reinterpret_cast<const fvec4 *>(src + row * ld + 8 * kgi + 4);
-  const fvec4 e = {a.x, a.z, c.x, c.z}, o = {a.y, a.w, c.y, c.w};
-  uint4 *chunk = S + ((row >> 7) * (width >> 5) + (kgi >> 2)) * D_CHUNK;
-  chunk[(2 * (kgi & 3)) * 128 + (row & 127)] = __builtin_bit_cast(uint4, e);
-  chunk[(2 * (kgi & 3) + 1) * 128 + (row & 127)] = __builtin_bit_cast(uint4, o);
+  d_split_row_kg(src, ld, width, S, row, kgi);
+}
+// the same for the rows ids[0..n) only (imported stream states): every other row's shadow stays bit-untouched
+__global__ __launch_bounds__(256) void pn_split_d_rows_kernel(const float *__restrict__ src, int ld, int width, uint4 *__restrict__ S,
+                                                              const int *__restrict__ ids, const int *__restrict__ status, int n) {
+  const int kgs = width >> 3;
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t i = idx / kgs;
+  const int kgi = (int)(idx - i * kgs);
+  if (i >= (size_t)n || (status && status[i])) return;
+  d_split_row_kg(src, ld, width, S, (size_t)ids[i], kgi);
 }
 
 // ---- launchers -----------------------------------------------------------------------------------------------------
@@ -271,5 +284,15 @@ int pn_launch_split_d(hipStream_t st, const float *src, int ld, int width, void 
   }
   const size_t n = (size_t)n_rows_padded * (width >> 3);
   hipLaunchKernelGGL(pn_split_d_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, ld, width, (uint4 *)S, n_rows_padded);
+  return 0;
+}
+int pn_launch_split_d_rows(hipStream_t st, const float *src, int ld, int width, void *S, const int *d_ids, const int *d_status, int n) {
+  if (width < 8 || (width & 7) || ld < width || n < 0 || !src || !S || (n && !d_ids)) {
+    pn_set_error("pn_launch_split_d_rows: width %d (whole groups of 8), row stride %d, %d rows", width, ld, n);
+    return -1;
+  }
+  if (n == 0) return 0;
+  const size_t m = (size_t)n * (width >> 3);
+  hipLaunchKernelGGL(pn_split_d_rows_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, src, ld, width, (uint4 *)S, d_ids, d_status, n);
   return 0;
 }

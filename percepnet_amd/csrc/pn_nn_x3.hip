@@ -804,7 +804,19 @@ __global__ __launch_bounds__(512, 1) void pn_gru_x3p_kernel(
 }
 
 // ---- fp32 rows -> fragment-order hi/lo shadow (the first layer's output; RNN state loaded from the host) ---------
-// one thread per (row, k-group of 8): reads 32 bytes, writes 2 x 16
+// one thread per (row, k-group of 8): reads 32 bytes, writes 2 x 16.  The body is shared with the row-list form below as a
+// statement macro (an inline function moves instructions of the full-batch kernel around: its ISA stays as it was)
+#define X3_SPLIT_ROW_KG(NP_, src, ld, width, S, row, kgi)                                                  \
+  do {                                                                                                     \
+    float f[8];                                                                                            \
+    *reinterpret_cast<float4 *>(&f[0]) = *reinterpret_cast<const float4 *>(src + row * ld + 8 * kgi);      \
+    *reinterpret_cast<float4 *>(&f[4]) = *reinterpret_cast<const float4 *>(src + row * ld + 8 * kgi + 4);  \
+    uint4 hi, lo;                                                                                          \
+    x3_split8(f, hi, lo);                                                                                  \
+    uint4 *chunk = S + ((row >> 7) * (width >> 5) + (kgi >> 2)) * (NP_ * X3_PLANE);                        \
+    chunk[(kgi & 3) * 128 + (row & 127)] = hi;                                                             \
+    if constexpr (NP_ == 2) chunk[X3_PLANE + (kgi & 3) * 128 + (row & 127)] = lo;                          \
+  } while (0)
 template <int NP>
 __global__ __launch_bounds__(256) void pn_split_x3_kernel(const float *__restrict__ src, int ld, int width, uint4 *__restrict__ S,
                                                           int n_rows_padded) {
@@ -813,15 +825,21 @@ __global__ __launch_bounds__(256) void pn_split_x3_kernel(const float *__restric
   const size_t row = idx / kgs;
   const int kgi = (int)(idx - row * kgs);
   if (row >= (size_t)n_rows_padded) return;
-  float f[8];
-  *reinterpret_cast<float4 *>(&f[0]) = *reinterpret_cast<const float4 *>(src + row * ld + 8 * kgi);
-  *reinterpret_cast<float4 *>(&f[4]) = *reinterpret_cast<const float4 *>(src + row * ld + 8 * kgi + 4);
-  uint4 hi, lo;
-  x3_split8(f, hi, lo);
-  uint4 *chunk = S + ((row >> 7) * (width >> 5) + (kgi >> 2)) * (NP * X3_PLANE);
-  chunk[(kgi & 3) * 128 + (row & 127)] = hi;
-  if constexpr (NP == 2) chunk[X3_PLANE + (kgi & 3) * 128 + (row & 127)] = lo;
+  X3_SPLIT_ROW_KG(NP, src, ld, width, S, row, kgi);
 }
+// the same for the rows ids[0..n) only (imported stream states): every other row's shadow stays bit-untouched
+template <int NP>
+__global__ __launch_bounds__(256) void pn_split_x3_rows_kernel(const float *__restrict__ src, int ld, int width, uint4 *__restrict__ S,
+                                                               const int *__restrict__ ids, const int *__restrict__ status, int n) {
+  const int kgs = width >> 3;
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t i = idx / kgs;
+  const int kgi = (int)(idx - i * kgs);
+  if (i >= (size_t)n || (status && status[i])) return;
+  const size_t row = (size_t)ids[i];
+  X3_SPLIT_ROW_KG(NP, src, ld, width, S, row, kgi);
+}
+#undef X3_SPLIT_ROW_KG
 
 // ---- host: weight packing W[K][ncols] -> [CT][ceil(K/32)][k-step 2][plane np][lane 64][8 halfs] ------------------
 static inline int x3_ct_padded(int ncols, int ct_round) {
@@ -950,5 +968,18 @@ int pn_launch_split_x3(hipStream_t st, const float *src, int ld, int width, void
   else
     hipLaunchKernelGGL(pn_split_x3_kernel<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, ld, width, (uint4 *)S,
                        n_rows_padded);
+  return 0;
+}
+int pn_launch_split_x3_rows(hipStream_t st, const float *src, int ld, int width, void *S, const int *d_ids, const int *d_status, int n, int np) {
+  if (width < 8 || (width & 7) || ld < width || n < 0 || (np != 1 && np != 2) || !src || !S || (n && !d_ids)) {
+    pn_set_error("pn_launch_split_x3_rows: width %d (whole groups of 8), row stride %d, %d rows, %d plane(s)", width, ld, n, np);
+    return -1;
+  }
+  if (n == 0) return 0;
+  const size_t m = (size_t)n * (width >> 3);
+  if (np == 2)
+    hipLaunchKernelGGL(pn_split_x3_rows_kernel<2>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, src, ld, width, (uint4 *)S, d_ids, d_status, n);
+  else
+    hipLaunchKernelGGL(pn_split_x3_rows_kernel<1>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, src, ld, width, (uint4 *)S, d_ids, d_status, n);
   return 0;
 }
