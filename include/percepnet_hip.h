@@ -131,6 +131,32 @@ int pn_submit_host_i16_active(pn_ctx *ctx, const int16_t *h_in, int16_t *h_out, 
    place.  Off by default (= rnnoise_process_frame exactly); the tap keeps the network's raw g.
    Takes effect from the next frame. */
 int pn_ctx_set_postfilter(pn_ctx *ctx, int enable);
+/* Per-stream ATTENUATION LIMIT (suppression strength per call).  Stream s has a limit L_s in dB, 0 <= L_s <= +inf, default
+   +inf = off.  The host turns it into lam_s = (float)pow(10.0, -(double)L_s / 20.0) (double, rounded to fp32 once; a factor
+   below FLT_MIN, i.e. L_s > ~758.6 dB, becomes 0 = off, so +inf gives 0 and 0 dB gives 1) and mu_s = 1.0f - lam_s (fp32).
+   In the back end, for every bin k < 400 and both the real and the imaginary part, with a = X_k as analysed (before
+   pitch_filter) and y the value after pitch_filter (non-silent frames) and the gain stage, before the 1/960 scale:
+       lam_s != 0:  y <- (mu_s * y) + (lam_s * a)     (two fp32 products, then the fp32 sum; no FMA)
+   lam_s == 0 runs the unlimited arithmetic exactly.  Bins >= 400 stay exactly 0 (the engine keeps bins 0..399), so 0 dB is a
+   BYPASS: the input band-limited to 20 kHz and delayed like the enhanced signal, by 2880 samples from input frame t to output
+   frame t.  The mix
+   applies to silent frames too (y is then the gained X) and after the optional post-filter; the g|r tap stays the network's
+   raw output, and nothing upstream of the synthesis (features, pitch, network state) depends on the limit.
+   pn_atten_limit_factor: host only, needs no GPU: lam for `db` as above; NaN for db < 0 or NaN.
+   pn_ctx_set_atten_limit: streams ids[0..n) (host array, DISTINCT, in range) get the limits db[0..n) (host array).  An id out of
+   range, a duplicate id or a db that is NaN or negative refuses the call: -1, pn_last_error set, nothing changed or launched.
+   n == 0 is a no-op.  Ordered exactly like pn_ctx_reset_streams: asynchronous on the context's stream, frames submitted before
+   the call use the old values and frames submitted after it the new ones (also on the pipelined host path); the caller may
+   reuse its arrays when the call returns.  While no stream of the context is limited, a frame runs the same back-end kernel
+   as a context that never set a limit.
+   pn_ctx_get_atten_limit: the values as last set, [n_streams] floats (+INFINITY = off).
+   Lifecycle: pn_ctx_reset sets every stream back to off; pn_ctx_reset_streams sets the listed streams back to off (a reset
+   slot is a new call); streams skipped by pn_process_*_active keep their limit (a setting, not per-tick state); stream-state
+   records do not carry it (format, version and size unchanged): an imported stream continues under the target slot's own
+   setting. */
+float pn_atten_limit_factor(float db);
+int pn_ctx_set_atten_limit(pn_ctx *ctx, const int32_t *ids, int n, const float *db);
+int pn_ctx_get_atten_limit(const pn_ctx *ctx, float *h_db);
 /* n_frames consecutive frames per call: in/out are [n_frames][n_streams][480] (frame-major). */
 int pn_process_i16_multi(pn_ctx *ctx, const int16_t *d_in, int16_t *d_out, float *d_gr, int n_frames);
 /* Host-buffer convenience wrappers (H2D, process, D2H, synchronise). */

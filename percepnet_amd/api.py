@@ -97,6 +97,11 @@ def load_library():
         for name in ("pn_ctx_export_streams", "pn_ctx_export_streams_host", "pn_ctx_import_streams_host"):
             getattr(L, name).argtypes = [_vp, _vp, ctypes.c_int, _vp]
         L.pn_ctx_import_streams.argtypes = [_vp, _vp, ctypes.c_int, _vp, _vp]
+    if hasattr(L, "pn_atten_limit_factor"):
+        L.pn_atten_limit_factor.restype = ctypes.c_float
+        L.pn_atten_limit_factor.argtypes = [ctypes.c_float]
+        L.pn_ctx_set_atten_limit.argtypes = [_vp, _vp, ctypes.c_int, _vp]
+        L.pn_ctx_get_atten_limit.argtypes = [_vp, _vp]
     L.pn_ctx_debug_copy.restype = ctypes.c_longlong
     L.pn_ctx_debug_copy.argtypes = [_vp, ctypes.c_int, _vp, ctypes.c_longlong]
     L.pn_ctx_set_profiling.argtypes = [_vp, ctypes.c_int]
@@ -183,6 +188,19 @@ class Context:
     def set_postfilter(self, enable):
         """Optional envelope post-filter on the gains (reference post_filtering, denoise.cpp:216-250)."""
         self._chk(self.L.pn_ctx_set_postfilter(self.h, int(bool(enable))))
+
+    def set_atten_limit(self, ids, db):
+        """Attenuation limit in dB of the distinct streams `ids` (include/percepnet_hip.h pn_ctx_set_atten_limit): `db` is one
+        value for all of them or one per id; 0 = bypass, math.inf = off.  Ordered with the frames like reset_streams."""
+        a = self._ids(ids)
+        v = np.ascontiguousarray(np.broadcast_to(np.asarray(db, dtype=np.float32), a.shape))
+        self._chk(self.L.pn_ctx_set_atten_limit(self.h, a.ctypes.data, int(a.size), v.ctypes.data))
+
+    def atten_limit(self):
+        """-> float32 [n_streams]: the attenuation limits as set, in dB (inf = off)."""
+        out = np.empty(self.n_streams, np.float32)
+        self._chk(self.L.pn_ctx_get_atten_limit(self.h, out.ctypes.data))
+        return out
 
     def device_bytes(self):
         return self.L.pn_ctx_device_bytes(self.h)
@@ -348,6 +366,12 @@ class Context:
             self._chk(self.L.pn_ctx_kernel_time(self.h, name, ctypes.byref(ms), ctypes.byref(n)))
             out[name.decode()] = (ms.value, n.value)
         return out
+
+
+def atten_limit_factor(db):
+    """The mix factor lam = 10^(-db/20) the engine uses for an attenuation limit of `db` dB (pn_atten_limit_factor, host only):
+    1.0 at 0 dB, 0.0 (off) for inf and beyond ~758.6 dB, NaN for a negative or NaN db."""
+    return float(load_library().pn_atten_limit_factor(float(db)))
 
 
 def stream_state_check(record, model):

@@ -4,9 +4,12 @@
 // mono 48 kHz in; (frames-1)*480 samples out (first output frame dropped, main.cpp:37; partial tail frame
 // dropped, main.cpp:32-33); with a single pair ./feature_test.raw gets 68 floats per frame.
 //
-//   percepnet_run [--model model.pnw] [--strict | --x3] [--postfilter] [--slots N] [--device N | --devices 0,1,..|all]
-//                 [--no-numa] [--verbose]
+//   percepnet_run [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--slots N]
+//                 [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
 //                 in0.pcm out0.pcm [in1.pcm out1.pcm ...]
+//
+// --atten-lim DB: every stream takes out at most DB dB of noise (pn_ctx_set_atten_limit; 0 = the input, delayed; default: no
+// limit).  A slot reset clears a stream's limit (a reset slot is a new call), so the limit is set again on every reset slot.
 //
 // --slots N: at most N concurrent streams per device; further pairs wait and take over the slot of a pair that has ended
 // (per-stream re-initialisation on the device, pn_ctx_reset_streams) — a directory of recordings of different lengths goes
@@ -20,6 +23,7 @@
 // --verbose prints the binding).
 #include "../../include/percepnet_hip.h"
 #include "pn_cli_util.h"
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -54,6 +58,7 @@ struct ShardRes {
 // (pn_ctx_reset_streams = rnnoise_destroy + rnnoise_create of the reference, denoise.cpp:252-280,326-331) and the next
 // waiting pair starts there on the following frame, while the other slots keep running.
 static bool g_numa = true, g_verbose = false;
+static float g_atten_lim = INFINITY;                  // --atten-lim: dB for every stream (inf: not set)
 static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, int postfilter, bool tap, int n_slots) {
   const int P = sh->count, B = n_slots > 0 && n_slots < P ? n_slots : P;
   auto fail = [&](int rc, const std::string &msg) { sh->rc = rc; sh->err = msg; };
@@ -69,6 +74,16 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
   pn_ctx *cx = R.cx;
   if (!cx) return fail(3, std::string("pn_ctx_create: ") + pn_last_error());
   if (postfilter) pn_ctx_set_postfilter(cx, 1);
+  auto set_limit = [&](const int32_t *ids, int n) {     // --atten-lim on these slots (after creation and after every slot reset)
+    if (isinf(g_atten_lim) || n == 0) return 0;
+    std::vector<float> db(n, g_atten_lim);
+    return pn_ctx_set_atten_limit(cx, ids, n, db.data());
+  };
+  {
+    std::vector<int32_t> all(B);
+    for (int s = 0; s < B; s++) all[s] = s;
+    if (set_limit(all.data(), B)) return fail(3, std::string("pn_ctx_set_atten_limit: ") + pn_last_error());
+  }
   std::vector<FILE *> &fin = R.fin, &fout = R.fout;
   fin.assign(B, NULL); fout.assign(B, NULL);
   int next_pair = 0;
@@ -129,7 +144,8 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
       else memset(x, 0, PN_FRAME_SIZE * sizeof(int16_t));
     }
     if (n_alive == 0) break;
-    if (!restart.empty() && pn_ctx_reset_streams(cx, restart.data(), (int)restart.size())) return fail(5, pn_last_error());
+    if (!restart.empty() && (pn_ctx_reset_streams(cx, restart.data(), (int)restart.size()) ||
+                             set_limit(restart.data(), (int)restart.size()))) return fail(5, pn_last_error());
     if (pn_submit_host_i16(cx, sl.in, sl.out, sl.gr)) return fail(5, pn_last_error());
     if (t >= 2) flush(slot[(t - 2) % 3]);
   }
@@ -147,6 +163,12 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[ai], "--strict")) nn_mode = PN_NN_STRICT;      // reference-order network, bit-exact to the CPU path
     else if (!strcmp(argv[ai], "--x3")) nn_mode = PN_NN_MFMA_X3;         // split-precision network (same +-1 LSB bound, ~2x the rate)
     else if (!strcmp(argv[ai], "--postfilter")) postfilter = 1;      // optional envelope post-filter (denoise.cpp:216-250)
+    else if (!strcmp(argv[ai], "--atten-lim") && ai + 1 < argc) {   // per-stream attenuation limit in dB (pn_ctx_set_atten_limit)
+      char *end = NULL;
+      const char *v = argv[++ai];
+      g_atten_lim = strtof(v, &end);
+      if (end == v || *end || !(g_atten_lim >= 0.f)) { fprintf(stderr, "--atten-lim: expected a number of dB >= 0 (inf = off), got '%s'\n", v); return 1; }
+    }
     else if (!strcmp(argv[ai], "--no-numa")) g_numa = false;         // leave the host threads' CPU affinity alone
     else if (!strcmp(argv[ai], "--verbose")) g_verbose = true;       // one line per device: its NUMA binding
     else if (!strcmp(argv[ai], "--slots") && ai + 1 < argc) n_slots = atoi(argv[++ai]);   // concurrent streams per device: pairs queue for them
@@ -162,7 +184,7 @@ int main(int argc, char **argv) {
   if (devices.empty()) devices.push_back(0);
   const int nfiles = argc - ai;
   if (nfiles < 2 || (nfiles & 1)) {
-    fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--slots N] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv[0]);
+    fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--slots N] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv[0]);
     return 1;
   }
   const int B = nfiles / 2;

@@ -6,6 +6,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <float.h>
 #include <math.h>
 #include <string.h>
 #include <array>
@@ -91,6 +92,12 @@ struct pn_ctx {
   float2 *yring, *Ps;              // yring: [6][B][400] look-ahead spectra (X of frame t = slot (t+1)%6)
   float *eyring;                   // [6][B][36] look-ahead band energies
   bool postfilter = false;         // optional envelope post-filter in the back end (pn_ctx_set_postfilter)
+  // per-stream attenuation limit (pn_ctx_set_atten_limit): (lam, mu) per stream on the device, allocated by the first set; the
+  // host mirror of the dB values (the getter) and the count of streams with lam != 0 (the launch decision: while it is 0 the
+  // back end is the plain kernel and lam_mu is not read)
+  float2 *lam_mu = NULL;
+  std::vector<float> atten_db;
+  int n_limited = 0;
   bool x3_sat = false;             // PERCEPNET_X3_SATCOUNT=1 (shadow-operand modes): count operand values clamped to the fp16 range
   int dsp_grid_cap = 0;            // > 0 only in the DSP self-test's temporary context: its DSP launches use that many blocks
   bool inject_bad_launch = false;  // pn_ctx_debug_inject_launch_failure (tests): the next frames hand fc a geometry its launcher refuses
@@ -171,6 +178,8 @@ static int zero_state(pn_ctx *c) {
   for (int i = 0; i < 4; i++) PN_HIP_CHECK(hipMemsetAsync(c->gru[i], 0, 2 * Bp * 512 * 4, c->stream));
   PN_HIP_CHECK(hipMemsetAsync(c->rb, 0, 2 * Bp * 128 * 4, c->stream));
   PN_HIP_CHECK(hipMemsetAsync(c->gr, 0, B * 68 * 4, c->stream));
+  if (c->lam_mu) PN_HIP_CHECK(hipMemsetAsync(c->lam_mu, 0, B * sizeof(float2), c->stream));   // every stream back to off
+  c->atten_db.assign(B, INFINITY); c->n_limited = 0;
   if (c->c2outH) {
     const size_t hb = 2 * shadow_halfs_per_element(c);   // shadow bytes per element
     if (c->c1ringH) PN_HIP_CHECK(hipMemsetAsync(c->c1ringH, 0, 5 * Bp * 128 * hb, c->stream));
@@ -421,11 +430,14 @@ extern "C" int pn_ctx_reset(pn_ctx *c) { if (!c) return -1; PN_ON_DEVICE(c); if 
 // of every state buffer goes to zero (pn_state.hip says why that is a fresh stream whatever the ring phases are)
 // ids[0..n) (host) -> c->d_ids through the pinned slot ring, asynchronously on the context's stream (frames may be in flight);
 // the launches that read c->d_ids follow on the same stream.  NULL on failure.  (The caller is on the context's device.)
-static const int *stage_ids(pn_ctx *c, const int32_t *ids, int n) {
+// payload (optional): payload_words more 32-bit words staged in the same copy, at d_ids + stage_payload_offset(n)
+static int stage_payload_offset(int n) { return (n + 3) & ~3; }      // 16-byte aligned
+static const int *stage_ids(pn_ctx *c, const int32_t *ids, int n, const void *payload = NULL, int payload_words = 0) {
+  const int words = payload_words ? stage_payload_offset(n) + payload_words : n;
 #define SI_CHECK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { pn_set_error("%s failed: %s", #expr, hipGetErrorString(_e)); return NULL; } } while (0)
-  if (c->ids_cap < n) {
+  if (c->ids_cap < words) {
     // (the old, smaller buffers stay in allocs until destroy: kernels of an earlier call may still be reading them)
-    const int cap = n < 1024 ? 1024 : n;
+    const int cap = words < 1024 ? 1024 : words;
     int *p = NULL;
     SI_CHECK(hipMalloc((void **)&p, (size_t)cap * sizeof(int)));
     c->allocs.push_back(p); c->d_ids = p;
@@ -441,7 +453,8 @@ static const int *stage_ids(pn_ctx *c, const int32_t *ids, int n) {
   pn_ctx::IdSlot &sl = c->id_slot[c->id_calls++ & 3];
   SI_CHECK(hipEventSynchronize(sl.ev));                 // the copy issued from this slot four calls ago has executed
   memcpy(sl.h, ids, (size_t)n * sizeof(int));
-  SI_CHECK(hipMemcpyAsync(c->d_ids, sl.h, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  if (payload_words) memcpy(sl.h + stage_payload_offset(n), payload, (size_t)payload_words * 4);
+  SI_CHECK(hipMemcpyAsync(c->d_ids, sl.h, (size_t)words * sizeof(int), hipMemcpyHostToDevice, c->stream));
   SI_CHECK(hipEventRecord(sl.ev, c->stream));
   return c->d_ids;
 #undef SI_CHECK
@@ -470,6 +483,7 @@ extern "C" int pn_ctx_reset_streams(pn_ctx *c, const int32_t *ids, int n) {
   for (int i = 0; i < 4; i++) pn_launch_zero_rows(st, c->gru[i], 512, 512, 2, Bp * 512, d, n);
   pn_launch_zero_rows(st, c->rb, 128, 128, 2, Bp * 128, d, n);
   pn_launch_zero_rows(st, c->gr, 68, 68, 1, 0, d, n);
+  if (c->lam_mu) pn_launch_zero_rows(st, c->lam_mu, 2, 2, 1, 0, d, n);   // a reset slot is a new call: attenuation limit off
   if (c->c2outH) {                                         // operand shadows (fp16-operand / split-precision modes, direct-operand GRUs); a NULL one is skipped
     const int np = (int)shadow_halfs_per_element(c);
     pn_launch_zero_shadow_rows(st, c->c1ringH, 128, np, 5, np * Bp * 128, d, n);
@@ -479,6 +493,10 @@ extern "C" int pn_ctx_reset_streams(pn_ctx *c, const int32_t *ids, int n) {
     pn_launch_zero_shadow_rows(st, c->rbH, 128, np, 2, np * Bp * 128, d, n);
   }
   PN_HIP_CHECK(hipGetLastError());
+  for (int i = 0; i < n; i++) {                            // (duplicates allowed: the second sees the stream already off)
+    if (pn_atten_limit_factor(c->atten_db[ids[i]]) != 0.f) c->n_limited--;
+    c->atten_db[ids[i]] = INFINITY;
+  }
   return 0;
 }
 extern "C" int pn_ctx_n_streams(const pn_ctx *c) { return c ? c->B : -1; }
@@ -926,7 +944,8 @@ static int process_dev(pn_ctx *c, const void *d_in, void *d_out, float *d_gr, in
     const size_t slot = (size_t)((c->t + 1) % 6);
     const float2 *Xs = c->yring + slot * c->B * PN_SPEC_BINS;
     const float *Ex = c->postfilter ? c->eyring + slot * c->B * 36 : nullptr;      // Ex(t) = Ey_lookahead(t-5)
-    pn_launch_backend(c->stream, c->tables, c->B, Xs, c->Ps, c->gr, Ex, c->silence, c->synth, d_out, is_i16, c->dsp_grid_cap); }
+    pn_launch_backend(c->stream, c->tables, c->B, Xs, c->Ps, c->gr, Ex, c->silence, c->synth, d_out, is_i16, c->dsp_grid_cap,
+                      c->n_limited > 0 ? c->lam_mu : nullptr); }      // no stream limited: the plain back end
   if (d_gr) PN_HIP_CHECK(hipMemcpyAsync(d_gr, c->gr, (size_t)c->B * 68 * 4, hipMemcpyDeviceToDevice, c->stream));
   PN_HIP_CHECK(hipGetLastError());
   c->t++; c->tn++;
@@ -946,6 +965,46 @@ extern "C" int pn_ctx_debug_inject_launch_failure(pn_ctx *c, int enable) {
 extern "C" int pn_ctx_set_postfilter(pn_ctx *c, int enable) {
   if (!c) { pn_set_error("NULL argument"); return -1; }
   c->postfilter = enable != 0;
+  return 0;
+}
+
+// ---- per-stream attenuation limit ----------------------------------------------------------------------------------------
+// lam = 10^(-L/20) in double, rounded to fp32 once; a factor below FLT_MIN is 0 (off), so no subnormal reaches the device
+extern "C" float pn_atten_limit_factor(float db) {
+  if (!(db >= 0.f)) return NAN;                          // negative or NaN
+  const float lam = (float)pow(10.0, -(double)db / 20.0);
+  return lam < FLT_MIN ? 0.f : lam;
+}
+// ids distinct and in range, every value >= 0 (+inf = off): else -1 before anything is staged or launched.  The (lam, mu) pairs
+// travel with the ids through the pinned slot ring and are scattered on the context's stream, between the frames submitted
+// before and after the call, like pn_ctx_reset_streams.
+extern "C" int pn_ctx_set_atten_limit(pn_ctx *c, const int32_t *ids, int n, const float *db) {
+  if (!c || n < 0 || (n > 0 && (!ids || !db))) { pn_set_error("bad argument"); return -1; }
+  if (n == 0) return 0;
+  if (n > c->B) { pn_set_error("%d stream ids in a context of %d", n, c->B); return -1; }
+  std::vector<uint8_t> seen((size_t)c->B, 0);
+  for (int i = 0; i < n; i++) {
+    if (ids[i] < 0 || ids[i] >= c->B) { pn_set_error("stream id %d out of range [0, %d)", ids[i], c->B); return -1; }
+    if (seen[ids[i]]++) { pn_set_error("stream id %d listed twice", ids[i]); return -1; }
+    if (!(db[i] >= 0.f)) { pn_set_error("attenuation limit %g dB for stream %d: must be >= 0 (+inf = off)", (double)db[i], ids[i]); return -1; }
+  }
+  PN_ON_DEVICE(c);
+  if (!c->lam_mu && dev_alloc(c, (void **)&c->lam_mu, (size_t)c->B * sizeof(float2), true)) return -1;   // zero = every stream off
+  std::vector<float2> lm(n);
+  for (int i = 0; i < n; i++) { const float lam = pn_atten_limit_factor(db[i]); lm[i] = make_float2(lam, 1.0f - lam); }
+  const int *d = stage_ids(c, ids, n, lm.data(), 2 * n);
+  if (!d) return -1;
+  pn_launch_scatter_pairs(c->stream, c->lam_mu, d, reinterpret_cast<const float2 *>(d + stage_payload_offset(n)), n);
+  PN_HIP_CHECK(hipGetLastError());
+  for (int i = 0; i < n; i++) {
+    c->n_limited += (lm[i].x != 0.f) - (pn_atten_limit_factor(c->atten_db[ids[i]]) != 0.f);
+    c->atten_db[ids[i]] = db[i];
+  }
+  return 0;
+}
+extern "C" int pn_ctx_get_atten_limit(const pn_ctx *c, float *h_db) {
+  if (!c || !h_db) { pn_set_error("bad argument"); return -1; }
+  memcpy(h_db, c->atten_db.data(), (size_t)c->B * sizeof(float));
   return 0;
 }
 

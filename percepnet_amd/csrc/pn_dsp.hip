@@ -48,9 +48,14 @@ __device__ __forceinline__ int16_t pn_f2s(float v) {
   return (int16_t)(uint16_t)((uint32_t)t & 0xffffu);
 }
 
+template <typename P, typename... R> __device__ __forceinline__ P pn_first_arg(P p, R...) { return p; }
+
 // PF: optional envelope post-filter (reference post_filtering, denoise.cpp:216-250) on the
 // gains before pitch_filter and the gain stage, where the reference's TEST synthesis has it (743).
-template <typename TOut, bool PF>
+// LamMu: empty = the back end as it always was (same parameter list, same code); one float2 = the per-stream attenuation
+// limit variant (pn_ctx_set_atten_limit), which takes one more argument, lam_mu [n_streams] = (lam, mu), and replaces the
+// gained spectrum y of bins 0..399 by (mu * y) + (lam * X) before the 1/960 scale; rows with lam == 0 run the plain path.
+template <typename TOut, bool PF, typename... LamMu>
 __global__ __launch_bounds__(DSP_THREADS, PN_DSP_WAVES_PER_SIMD) void pn_backend_kernel(
     const PnTables *__restrict__ T, int n_streams,
     const float2 *__restrict__ Xspec, const float2 *__restrict__ Pspec,
@@ -58,7 +63,9 @@ __global__ __launch_bounds__(DSP_THREADS, PN_DSP_WAVES_PER_SIMD) void pn_backend
     const float *__restrict__ ex,          // PF only: [n_streams][36] band energies of Xspec
     const int *__restrict__ silence,
     float *__restrict__ synth_mem,         // [n_streams][480]
-    TOut *__restrict__ out) {              // [n_streams][480]
+    TOut *__restrict__ out,                // [n_streams][480]
+    const LamMu *__restrict__... lam_mu) { // attenuation-limit variant only: [n_streams] (lam, mu)
+  constexpr bool AL = sizeof...(LamMu) != 0;
   __shared__ PnDspShared SH;
   const int tid = threadIdx.x, lane = tid & (LANES - 1), wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   for (int i = tid; i < PN_FRAME; i += DSP_THREADS) SH.win[i] = T->half_window[i];
@@ -71,6 +78,9 @@ __global__ __launch_bounds__(DSP_THREADS, PN_DSP_WAVES_PER_SIMD) void pn_backend
   const int lc = lane < 60 ? lane : 59;
   for (int s = blockIdx.x * WPB + wave; s < n_streams; s += gridDim.x * WPB) {
     const bool sil = silence[s] != 0;
+    float lam = 0.f, mu = 0.f;                              // attenuation-limit variant: one (lam, mu) load per stream, wave-uniform
+    if constexpr (AL) { const float2 lm = pn_first_arg(lam_mu...)[s]; lam = lm.x; mu = lm.y; }
+    const bool mix = AL && lam != 0.f;
     if (lane < PN_NB) {
       const float g = gr[(size_t)s * 68 + lane], r = gr[(size_t)s * 68 + PN_NB + lane];
       W.e[0][lane] = g; W.e[1][lane] = r; W.e[2][lane] = 1 - r;
@@ -142,6 +152,11 @@ __global__ __launch_bounds__(DSP_THREADS, PN_DSP_WAVES_PER_SIMD) void pn_backend
             }
             const float gf = (1 - fr) * W.e[0][b] + fr * W.e[0][b + 1];
             x.x *= gf; x.y *= gf;
+            if constexpr (AL)
+              if (mix) {                                    // dry term: X_k as loaded; separate roundings (-ffp-contract=off)
+                const float2 a = h ? make_float2(xq[it].z, xq[it].w) : make_float2(xq[it].x, xq[it].y);
+                x.x = (mu * x.x) + (lam * a.x); x.y = (mu * x.y) + (lam * a.y);
+              }
             y[h] = make_float2(scale * x.x, scale * x.y);
           }
           Y4[m] = make_float4(y[0].x, y[0].y, y[1].x, y[1].y);
@@ -223,9 +238,27 @@ static inline int pn_dsp_grid(int n_streams, int blocks_per_cu, int grid_cap) {
 
 void pn_launch_backend(hipStream_t st, const PnTables *T, int n_streams, const float2 *Xs, const float2 *Ps,
                        const float *gr, const float *ex_postfilter, const int *silence, float *synth_mem, void *out,
-                       int out_is_i16, int grid_cap) {
+                       int out_is_i16, int grid_cap, const float2 *lam_mu) {
   const int grid = pn_dsp_grid(n_streams, 0, grid_cap);
   const dim3 g(grid), b(DSP_THREADS);
+  if (lam_mu) {                                             // at least one stream of the context has an attenuation limit
+    if (ex_postfilter) {
+      if (out_is_i16)
+        hipLaunchKernelGGL((pn_backend_kernel<int16_t, true, float2>), g, b, 0, st, T, n_streams, Xs, Ps, gr, ex_postfilter, silence,
+                           synth_mem, (int16_t *)out, lam_mu);
+      else
+        hipLaunchKernelGGL((pn_backend_kernel<float, true, float2>), g, b, 0, st, T, n_streams, Xs, Ps, gr, ex_postfilter, silence,
+                           synth_mem, (float *)out, lam_mu);
+    } else {
+      if (out_is_i16)
+        hipLaunchKernelGGL((pn_backend_kernel<int16_t, false, float2>), g, b, 0, st, T, n_streams, Xs, Ps, gr, ex_postfilter, silence,
+                           synth_mem, (int16_t *)out, lam_mu);
+      else
+        hipLaunchKernelGGL((pn_backend_kernel<float, false, float2>), g, b, 0, st, T, n_streams, Xs, Ps, gr, ex_postfilter, silence,
+                           synth_mem, (float *)out, lam_mu);
+    }
+    return;
+  }
   if (ex_postfilter) {
     if (out_is_i16)
       hipLaunchKernelGGL((pn_backend_kernel<int16_t, true>), g, b, 0, st, T, n_streams, Xs, Ps, gr, ex_postfilter, silence,

@@ -37,6 +37,8 @@ void pn_launch_zero_rows(hipStream_t st, void *base, int row_floats, long long r
                          const int *d_ids, int n);
 void pn_launch_zero_shadow_rows(hipStream_t st, void *S, int width, int np, int n_slots, long long slot_stride_halfs,
                                 const int *d_ids, int n);
+// dst[ids[i]] = vals[i] for i < n (distinct ids): the per-stream (lam, mu) pairs of the attenuation limit
+void pn_launch_scatter_pairs(hipStream_t st, float2 *dst, const int *d_ids, const float2 *d_vals, int n);
 // per-call active set (pn_active.hip): the rows ids[0..n) are the streams a call does NOT advance
 struct PnActiveArgs {
   const int *ids;                                    // inactive stream ids (device)
@@ -78,7 +80,8 @@ void pn_launch_targets(hipStream_t st, const PnTables *T, int n_pairs, const flo
 void pn_launch_saturate_i16(hipStream_t st, int n_pairs, const float *in, int16_t *out, long long out_stride);
 void pn_launch_backend(hipStream_t st, const PnTables *T, int n_streams, const float2 *Xs, const float2 *Ps,
                        const float *gr, const float *ex_postfilter /* NULL = off */, const int *silence, float *synth_mem,
-                       void *out, int out_is_i16, int grid_cap);
+                       void *out, int out_is_i16, int grid_cap,
+                       const float2 *lam_mu /* [n_streams] (lam, mu) of the attenuation limit; NULL = no stream limited */);
 size_t pn_packed_floats(int k_alloc, int ncols, int ct_round);
 void pn_pack_weights(const float *W, int K, int k_alloc, int ncols, int ct_round, float *Wp);
 int pn_dense_nt(int N);

@@ -40,3 +40,14 @@ void pn_launch_zero_shadow_rows(hipStream_t st, void *S, int width, int np, int 
   if (n <= 0 || !S) return;
   hipLaunchKernelGGL(pn_zero_shadow_rows_kernel, dim3(n, n_slots), dim3(64), 0, st, (uint4 *)S, width / 32, np, slot_stride_halfs / 8, d_ids);
 }
+
+// per-stream settings (pn_ctx_set_atten_limit): dst[ids[i]] = vals[i], one thread per listed stream (the host refuses duplicates)
+__global__ __launch_bounds__(256) void pn_scatter_pairs_kernel(float2 *__restrict__ dst, const int *__restrict__ ids,
+                                                               const float2 *__restrict__ vals, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[ids[i]] = vals[i];
+}
+void pn_launch_scatter_pairs(hipStream_t st, float2 *dst, const int *d_ids, const float2 *d_vals, int n) {
+  if (n <= 0 || !dst) return;
+  hipLaunchKernelGGL(pn_scatter_pairs_kernel, dim3((n + 255) / 256), dim3(256), 0, st, dst, d_ids, d_vals, n);
+}
