@@ -310,6 +310,11 @@ long long pn_ctx_debug_copy(pn_ctx *ctx, int which, void *dst, long long max_byt
    pn_ctx_debug_inject_launch_failure(ctx, 1) makes every following frame of a non-STRICT context ask the fc layer's
    launcher for a refused geometry. */
 int pn_debug_check_launch(int kind, int n_panels, int width, int n_out);
+/* The kernel families a context of n_streams streams in nn_mode would run under the current environment, without a GPU (every
+   family override is read once, when a context is created: csrc/pn_plan.h).  Writes describe()'s family fields ("nn=" through
+   "frontend=") then " nn_chains=N tile=T share=S" (T: rows per block of the chained kernels; S: the first row of chain 1, 0 with
+   one chain).  Returns the length written, or -1 (pn_last_error()). */
+int pn_debug_plan(int n_streams, int nn_mode, char *buf, size_t n);
 int pn_ctx_debug_inject_launch_failure(pn_ctx *ctx, int enable);
 /* The digest function behind the shared-weights cache key (SHA-256, FIPS 180-4), exposed so that the CPU tests can check it
    against known answers: a model's packed device copy is shared by every context whose model has the same digest. */

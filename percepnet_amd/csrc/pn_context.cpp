@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "pn_launch.h"
+#include "pn_plan.h"
 #include "pn_selftest_golden.h"
 
 extern "C" int pn_device_count(void) { int n = 0; return hipGetDeviceCount(&n) == hipSuccess ? n : 0; }
@@ -27,7 +28,6 @@ enum { KF_FRONTEND, KF_FC, KF_CONV1, KF_CONV2, KF_GRU512, KF_GRU_RB, KF_FC_GB, K
        KF_FE_SPEC_OUT, KF_COUNT };
 static const char *kKernelNames[KF_COUNT] = {"frontend", "fc", "conv1", "conv2", "gru512", "gru_rb", "fc_gb", "fc_rb", "backend",
                                             "fe_spec_in", "fe_pitch", "fe_spec_out"};
-enum { FE_MONO_G4 = 0, FE_MONO_G2 = 1, FE_SPLIT = 2 };
 
 struct DevLayer { float *bias, *w, *rw, *wp, *rwp, *wq; };   // wq: narrow layers of small-batch fp32 contexts (pn_pack_weights_n16)
 
@@ -52,16 +52,10 @@ static std::map<WeightsKey, SharedWeights *> g_weights;
 
 struct pn_ctx {
   int device, B, nn_mode;
-  int x3_rg;                       // split-precision mode: row groups of 32 per wave (1: 128-row blocks, 2: 256-row blocks), fixed at creation from B
-  int small, small_gru;            // network kernel family per layer kind: 1 = small-batch (pn_nn_small.hip), fixed at creation from B
-  int n48;                         // fp32 MFMA mode, batches above the n16 limit: fc_gb on the batch form of the 16x16x4 kernel (pn_nn_n48.hip)
-  int direct;                      // fp32 MFMA mode, large batches: 1 = the direct-operand family (pn_nn_d.hip: A fragments from fp32 shadows,
-                                   // 64 rows per wave when x3_rg == 2); fixed at creation from B, never together with small / small_gru
-  int fe_mode;                     // front end: FE_SPLIT = three phase kernels (pn_dsp_fe_split_*.hip); FE_MONO_G4 / FE_MONO_G2 = the
-                                   // single-launch kernel with four / two streams per wavefront (pn_dsp_fe.hip, pn_dsp_fe_g2.hip)
+  PnPlan plan;                     // the kernel families (pn_plan.h), fixed at creation
   size_t Bp;                       // B rounded up to the largest GEMM M tile (256): row count of every network buffer
   hipStream_t stream; bool own_stream;
-  hipStream_t chain_stream[4] = {nullptr, nullptr, nullptr, nullptr};      // launch_rnn: streams of the row-range chains 1..3 (chain 0 = stream)
+  hipStream_t chain_stream[4] = {nullptr, nullptr, nullptr, nullptr};      // launch_rnn: streams of the row-range chains 1..3 (chain 0 = stream), created with the context
   hipEvent_t chain_fork = nullptr, chain_join[4] = {nullptr, nullptr, nullptr, nullptr};
   char chain_kind[5] = {'-', '-', '-', '-', 0};   // how each chain stream was obtained (n: default priority, probed; h: priority stream)
   int64_t t;                       // frames done: indexes the DSP rings (hist slot t%12, yring/eyring t%6)
@@ -159,7 +153,7 @@ static int upload_w(pn_ctx *c, SharedWeights *w, float **dst, const float *src, 
 
 // operand shadows: 1 half per element (fp16-operand mode) or a hi and a lo plane (split-precision mode)
 // (the fp32 shadows of the direct-operand family are 4 bytes per element, laid out in the same 16-byte slab entries)
-static size_t shadow_halfs_per_element(const pn_ctx *c) { return (c->nn_mode == PN_NN_MFMA_X3 || c->direct) ? 2 : 1; }
+static size_t shadow_halfs_per_element(const pn_ctx *c) { return (c->nn_mode == PN_NN_MFMA_X3 || c->plan.direct) ? 2 : 1; }
 static bool x3_layer(int li) { return li == PN_L_CONV1 || li == PN_L_CONV2 || li == PN_L_GRU_RB || li == PN_L_FC_GB || (li >= PN_L_GRU1 && li < PN_L_GRU1 + 4); }
 static int zero_state(pn_ctx *c) {
   const size_t B = c->B;
@@ -192,35 +186,10 @@ static int zero_state(pn_ctx *c) {
   return 0;
 }
 
-// Front-end kernel family for a batch size.  PERCEPNET_FE=split|mono|g2 overrides (PERCEPNET_FE_G2=1 is the older
-// spelling of g2).
-static int pn_fe_mode_for(int n_streams) {
-  if (const char *e = getenv("PERCEPNET_FE")) {
-    if (!strcmp(e, "split")) return FE_SPLIT;
-    if (!strcmp(e, "mono") || !strcmp(e, "g4")) return FE_MONO_G4;
-    if (!strcmp(e, "g2")) return FE_MONO_G2;
-  }
-  if (const char *e = getenv("PERCEPNET_FE_G2")) return atoi(e) ? FE_MONO_G2 : FE_MONO_G4;
-  (void)n_streams;
-  return FE_SPLIT;      // measured: 0.102 vs 0.124 ms (g2) at 1024 streams, 0.130 vs 0.166 (g4) at 4096, 1.32 vs 2.37 at 65536 (profiles/r03e_*)
-}
-// narrow (34-column) dense layers on 16x16x4 MFMA tiles (pn_dense_n16_kernel) up to this batch size (measured: fc_gb 0.026 vs
-// 0.056 ms at 1024 streams, 0.082 vs 0.101 at 16384, 0.327 vs 0.180 at 65536 where the batch GEMM's operand reuse wins);
-// PERCEPNET_N16_ROWS overrides
-static bool n48_enabled() {             // PERCEPNET_N48=0: fc_gb of large fp32 contexts back on the 32-column batch GEMM
-  const char *e = getenv("PERCEPNET_N48");
-  return !e || atoi(e) != 0;
-}
-static bool n16_rows_ok(int n_streams) {
-  const char *e = getenv("PERCEPNET_N16_ROWS");
-  return n_streams <= (e ? atoi(e) : 20480);
-}
 static int nn_selftest(pn_ctx *c);
 static int dsp_selftest(pn_ctx *c);
-static int nn_chains_of(const pn_ctx *c);
-static int chain_streams_init(pn_ctx *c, int n);
-static pn_ctx *ctx_create(const pn_model *model, int device, int n_streams, int nn_mode, void *hip_stream, bool selftest,
-                          int force_small, int force_small_gru, int force_x3_rg = 0, int force_n16 = -1, int force_direct = -1);
+static int chain_streams_init(pn_ctx *c);
+static pn_ctx *ctx_create(const pn_model *model, int device, int n_streams, int nn_mode, void *hip_stream, bool selftest, const PnPlan *plan);
 
 extern "C" void pn_ctx_destroy(pn_ctx *c) {
   if (!c) return;
@@ -251,12 +220,12 @@ extern "C" void pn_ctx_destroy(pn_ctx *c) {
 }
 
 extern "C" pn_ctx *pn_ctx_create(const pn_model *model, int device, int n_streams, int nn_mode, void *hip_stream) {
-  return ctx_create(model, device, n_streams, nn_mode, hip_stream, true, -1, -1);
+  return ctx_create(model, device, n_streams, nn_mode, hip_stream, true, NULL);
 }
 
 // Biases + weights of `model` on the context's device in the layout `nn_mode` reads: STRICT the nnet_data.h arrays as they
 // are, the MFMA modes re-packed tile orders (pn_pack.cpp, pn_nn_x3.hip).  Returns NULL (pn_set_error) on failure.
-static SharedWeights *build_weights(pn_ctx *c, const pn_model *model, int nn_mode, bool n16, bool n48) {
+static SharedWeights *build_weights(pn_ctx *c, const pn_model *model, int nn_mode, int narrow) {
   SharedWeights *w = new SharedWeights();
   memset(w->L, 0, sizeof(w->L));
   for (int li = 0; li < PN_NLAYERS; li++) {
@@ -289,7 +258,7 @@ static SharedWeights *build_weights(pn_ctx *c, const pn_model *model, int nn_mod
         pn_pack_weights(H.w, K, k_alloc, ncols, ctr, packed.data());
         if (upload_w(c, w, &w->L[li].wp, packed.data(), packed.size())) goto fail_w;
         if (hipStreamSynchronize(c->stream) != hipSuccess) goto fail_w;   // `packed` dies at scope end
-        if ((n16 || (n48 && li == PN_L_FC_GB)) && H.kind == PN_KIND_DENSE && ncols <= 48 && K % 128 == 0) {     // fc_gb, fc_rb (n48: fc_gb only)
+        if ((narrow == 1 || (narrow == 2 && li == PN_L_FC_GB)) && H.kind == PN_KIND_DENSE && ncols <= 48 && K % 128 == 0) {     // fc_gb, fc_rb (n48: fc_gb only)
           std::vector<float> pq(pn_packed_floats_n16(K, ncols));
           pn_pack_weights_n16(H.w, K, ncols, pq.data());
           if (upload_w(c, w, &w->L[li].wq, pq.data(), pq.size())) goto fail_w;
@@ -313,10 +282,9 @@ fail_w:
   return NULL;
 }
 
-// force_small / force_small_gru: -1 = choose the network kernel family from the batch size (the public behaviour);
-// 0 / 1 = the self-test's temporary contexts run the SAME family as the context under test whatever their own size.
-static pn_ctx *ctx_create(const pn_model *model, int device, int n_streams, int nn_mode, void *hip_stream, bool selftest,
-                          int force_small, int force_small_gru, int force_x3_rg, int force_n16, int force_direct) {
+// plan: NULL = pn_plan_for(n_streams, nn_mode) (the public behaviour); the self-tests' temporary contexts run the SAME families
+// as the context under test whatever their own size.
+static pn_ctx *ctx_create(const pn_model *model, int device, int n_streams, int nn_mode, void *hip_stream, bool selftest, const PnPlan *plan) {
   if (!model) { pn_set_error("NULL model"); return NULL; }
   if (n_streams < 1) { pn_set_error("n_streams must be >= 1"); return NULL; }
   if (nn_mode != PN_NN_MFMA && nn_mode != PN_NN_STRICT && nn_mode != PN_NN_MFMA_F16 && nn_mode != PN_NN_MFMA_X3) { pn_set_error("bad nn_mode %d", nn_mode); return NULL; }
@@ -329,9 +297,7 @@ static pn_ctx *ctx_create(const pn_model *model, int device, int n_streams, int 
   DeviceGuard _dg(device);
   if (!_dg.ok) { pn_set_error("hipSetDevice(%d) failed", device); return NULL; }
   pn_ctx *c = new pn_ctx();
-  c->device = device; c->B = n_streams; c->Bp = ((size_t)n_streams + 255) / 256 * 256; c->nn_mode = nn_mode; c->small = force_small >= 0 ? force_small : n_streams <= pn_small_rows(); c->small_gru = force_small_gru >= 0 ? force_small_gru : n_streams <= pn_small_gru_rows(); c->fe_mode = pn_fe_mode_for(n_streams); c->x3_rg = force_x3_rg ? force_x3_rg : pn_x3_rg_for(n_streams);
-  c->direct = (nn_mode == PN_NN_MFMA && !c->small && !c->small_gru) ? (force_direct >= 0 ? force_direct : pn_direct_for(n_streams)) : 0;
-  if (c->direct) c->x3_rg = force_x3_rg ? (force_x3_rg >= 2 ? 2 : 1) : pn_direct_rg_for(n_streams);
+  c->device = device; c->B = n_streams; c->Bp = ((size_t)n_streams + 255) / 256 * 256; c->nn_mode = nn_mode; c->plan = plan ? *plan : pn_plan_for(n_streams, nn_mode);
   c->t = 0; c->tn = 0; c->bytes = 0; c->profiling = false;
   memset(c->fam_ms, 0, sizeof(c->fam_ms)); memset(c->fam_n, 0, sizeof(c->fam_n));
   memset(c->L, 0, sizeof(c->L));
@@ -368,9 +334,9 @@ static pn_ctx *ctx_create(const pn_model *model, int device, int n_streams, int 
   for (int i = 0; i < 4; i++) DEV_ALLOC(c->gru[i], 2 * Bp * 512, false);
   DEV_ALLOC(c->rb, 2 * Bp * 128, false);
   DEV_ALLOC(c->gr, B * 68, false);
-  if (nn_mode == PN_NN_MFMA_F16 || nn_mode == PN_NN_MFMA_X3 || c->direct) {
+  if (nn_mode == PN_NN_MFMA_F16 || nn_mode == PN_NN_MFMA_X3 || c->plan.direct) {
     const size_t hp = shadow_halfs_per_element(c);      // 1: fp16 shadow; 2: hi + lo planes (split precision) / fp32 fragments (direct-operand GRUs)
-    if (!c->direct) {                                   // (the direct-operand family keeps its dense layers on the batch kernels: no shadows of the conv FIFOs)
+    if (!c->plan.direct) {                              // (the direct-operand family keeps its dense layers on the batch kernels: no shadows of the conv FIFOs)
       DEV_ALLOC(c->c1ringH, hp * 5 * Bp * 128, false);
       DEV_ALLOC(c->c2ringH, hp * 3 * Bp * 512, false);
     }
@@ -383,14 +349,9 @@ static pn_ctx *ctx_create(const pn_model *model, int device, int n_streams, int 
   if (zero_state(c)) goto fail;
   for (int li = 0; li < PN_NLAYERS; li++) { c->geom[li] = model->L[li]; c->geom[li].bias = c->geom[li].w = c->geom[li].rw = NULL; }
   {   // the device copy of the weights: shared with every other context of this model content on this device in this mode
-    // narrow layers on the 16x16x4 kernel at small batches in every MFMA mode (in the shadow-operand modes that is fc_rb; fc_gb runs on their own kernels)
-    // force_n16 (the self-tests' temporary contexts): 0 batch GEMM, 1 n16, 2 n48
-    const bool n16 = (nn_mode != PN_NN_STRICT) && (force_n16 >= 0 ? force_n16 == 1 : n16_rows_ok(n_streams));
-    const bool n48 = nn_mode == PN_NN_MFMA && !c->small && !n16 && (force_n16 >= 0 ? force_n16 == 2 : n48_enabled());
-    c->n48 = n48;
     std::array<unsigned char, 32> dig;
     memcpy(dig.data(), model->sha256, 32);
-    c->weights_key = std::make_tuple(dig, model->n_floats, device, nn_mode, n16 ? 1 : (n48 ? 2 : 0));
+    c->weights_key = std::make_tuple(dig, model->n_floats, device, nn_mode, c->plan.narrow);
     std::lock_guard<std::mutex> build_lk(g_weights_build_mu[device & 15]);   // one build per device at a time; the map lock is never held across a build
     SharedWeights *hit = NULL;
     {
@@ -400,7 +361,7 @@ static pn_ctx *ctx_create(const pn_model *model, int device, int n_streams, int 
     }
     if (hit) { c->weights = hit; c->weights_were_cached = true; }
     else {
-      SharedWeights *w = build_weights(c, model, nn_mode, n16, n48);
+      SharedWeights *w = build_weights(c, model, nn_mode, c->plan.narrow);
       if (!w) goto fail;
       w->refs = 1;
       c->weights = w;
@@ -417,7 +378,7 @@ static pn_ctx *ctx_create(const pn_model *model, int device, int n_streams, int 
   if (selftest && nn_mode != PN_NN_STRICT && nn_selftest(c)) goto fail;
   if (selftest && dsp_selftest(c)) goto fail;
   if (c->x3_sat && pn_x3_sat_set(1)) { pn_set_error("cannot enable the operand-saturation counter"); goto fail; }   // after the self-tests: starts at zero
-  if (selftest && nn_chains_of(c) > 1 && chain_streams_init(c, nn_chains_of(c))) goto fail;      // probed now, not inside the first frame
+  if (c->plan.chains > 1 && chain_streams_init(c)) goto fail;      // probed now, not inside a frame
   return c;
 fail:
   pn_ctx_destroy(c);
@@ -509,17 +470,10 @@ extern "C" size_t pn_ctx_device_bytes(const pn_ctx *c) { return c ? c->bytes + (
 extern "C" size_t pn_ctx_weight_bytes(const pn_ctx *c) { return (c && c->weights) ? c->weights->bytes : 0; }
 extern "C" int pn_ctx_describe(const pn_ctx *c, char *buf, size_t n) {
   if (!c || !buf || !n) return -1;
-  const char *nn = c->nn_mode == PN_NN_STRICT ? "strict" : (c->nn_mode == PN_NN_MFMA_F16 ? "mfma_f16" : (c->nn_mode == PN_NN_MFMA_X3 ? "mfma_x3" : "mfma_f32"));
-  const bool x3 = c->nn_mode == PN_NN_MFMA_X3 || c->nn_mode == PN_NN_MFMA_F16;      // shadow-operand kernels (pn_nn_x3.hip)
-  const bool fam = c->nn_mode == PN_NN_MFMA || x3;      // the small-batch family exists for the fp32 MFMA kernels only (in the shadow-operand modes: fc, fc_rb)
-  // rows per wave (conv1, conv2, GRUs, fc_gb); x3_rg 3 = 64 rows with the GRUs on the paired-phase kernel (pn_gru_x3p_kernel)
-  const char *xk = c->nn_mode == PN_NN_MFMA_X3 ? (c->x3_rg >= 2 ? "x3_rows64" : "x3_rows32") : (c->x3_rg >= 2 ? "f16_rows64" : "f16_rows32");
-  const char *xg = c->nn_mode == PN_NN_MFMA_X3 ? (c->x3_rg == 3 ? "x3_rows64_paired" : xk) : (c->x3_rg == 3 ? "f16_rows64_paired" : xk);
-  const char *dk = c->x3_rg >= 2 ? "direct_rows64" : "direct_rows32";      // direct-operand fp32 GRU kernels (pn_nn_d.hip); the dense layers stay "batch"
-  const int w = snprintf(buf, n, "nn=%s dense=%s gru=%s gru_rb=%s narrow=%s frontend=%s weights=%s nn_chains=%d%s%s", nn, x3 ? xk : (fam && c->small ? "small" : "batch"),
-                         x3 ? xg : (c->direct ? dk : (fam && c->small_gru ? "small" : "batch")), x3 ? xg : (c->direct ? dk : (fam && c->small ? "small" : "batch")),
-                         x3 ? (c->L[PN_L_FC_RB].wq ? "fc_gb:x3+fc_rb:n16" : "fc_gb:x3+fc_rb:fp32") : (c->n48 ? "fc_gb:n48+fc_rb:batch" : (c->L[PN_L_FC_GB].wq ? "n16" : (fam && c->small ? "small" : "batch"))), c->fe_mode == FE_SPLIT ? "split" : (c->fe_mode == FE_MONO_G2 ? "g2" : "g4"),
-                         c->weights_were_cached ? "shared" : "own", nn_chains_of(c), nn_chains_of(c) > 1 ? ":" : "", nn_chains_of(c) > 1 ? c->chain_kind + 1 : "");
+  const int f = pn_plan_describe(c->plan, c->nn_mode, buf, n);
+  if (f < 0 || (size_t)f >= n) return -1;
+  const int k = c->plan.chains;
+  const int w = f + snprintf(buf + f, n - f, " weights=%s nn_chains=%d%s%s", c->weights_were_cached ? "shared" : "own", k, k > 1 ? ":" : "", k > 1 ? c->chain_kind + 1 : "");
   if (w < 0 || (size_t)w >= n) return -1;
   if (c->x3_sat) {                                        // debug: operand values clamped to +-65504 so far (device-wide counter)
     DeviceGuard _dg(c->device);
@@ -609,16 +563,17 @@ static PnSegs shadow_segs(pn_ctx *c, const PnSegs &A) {
 // Returns 0, or -1 when a launcher refused its geometry (pn_set_error names it): the refused layer is not launched (later
 // layers of the frame may be — their results are never reported) and the caller fails the frame.
 // The ten layers for the rows [r0, r0 + nrows) of the batch on stream `st`.  Every activation buffer is row-major, so a row range
-// is the same launch with every base pointer moved down by r0 rows.  small / small_gru: the kernel family.  The shadow-operand
+// is the same launch with every base pointer moved down by r0 rows.  The kernel families are c->plan's.  The shadow-operand
 // and STRICT modes always run the whole batch.
-static int launch_rnn_rows(pn_ctx *c, size_t r0, size_t nrows, hipStream_t st, int small, int small_gru) {
+static int launch_rnn_rows(pn_ctx *c, size_t r0, size_t nrows, hipStream_t st) {
   const size_t Bp = c->Bp; const int strict = c->nn_mode == PN_NN_STRICT; const int64_t t = c->tn;
   const int B = (int)nrows;
   // x3: the layers that run on the fp16 matrix cores from operand shadows — split precision (hi + lo planes) or fp16 operands (hi only)
   const bool x3 = c->nn_mode == PN_NN_MFMA_X3 || c->nn_mode == PN_NN_MFMA_F16;
   const int np = c->nn_mode == PN_NN_MFMA_X3 ? 2 : 1;
-  const bool dm = c->direct != 0;   // the GRU steps take their activations straight from fragment-order fp32 shadows (pn_nn_d.hip): written by conv2
-                                    // (batch kernel, second output) and by the GRU steps themselves; every dense layer stays on the batch kernels
+  const int small = c->plan.small, small_gru = c->plan.small_gru, rg = c->plan.rg;
+  const bool dm = c->plan.direct != 0;   // the GRU steps take their activations straight from fragment-order fp32 shadows (pn_nn_d.hip): written by conv2
+                                         // (batch kernel, second output) and by the GRU steps themselves; every dense layer stays on the batch kernels
   const float *tab = c->tansig;
   int rc = 0;
   const int cur = (int)(t & 1), nxt = cur ^ 1;
@@ -636,12 +591,12 @@ static int launch_rnn_rows(pn_ctx *c, size_t r0, size_t nrows, hipStream_t st, i
   { MaybeScope sc(c, KF_CONV1, st);   // causal conv as dense over [4 previous fc outputs | current] (nnet.cpp:182-200)
     PnSegs A; memset(&A, 0, sizeof(A)); A.n = 5;
     for (int j = 0; j < 5; j++) { A.p[j] = c->c1ring + (size_t)((t + 1 + j) % 5) * Bp * 128 + r0 * 128; A.ld[j] = 128; A.width[j] = 128; }
-    if (x3) rc |= pn_launch_dense_x3(st, shadow_segs(c, A), c->L[PN_L_CONV1].wp, c->L[PN_L_CONV1].bias, 512, c->geom[PN_L_CONV1].act, tab, c2new, 512, shadow(c, c2new), 16, B, c->x3_rg, np);
+    if (x3) rc |= pn_launch_dense_x3(st, shadow_segs(c, A), c->L[PN_L_CONV1].wp, c->L[PN_L_CONV1].bias, 512, c->geom[PN_L_CONV1].act, tab, c2new, 512, shadow(c, c2new), 16, B, rg, np);
     else rc |= pn_launch_dense(st, strict, A, c->L[PN_L_CONV1].w, c->L[PN_L_CONV1].wp, c->L[PN_L_CONV1].bias, 512, c->geom[PN_L_CONV1].act, tab, c2new, 512, B, small); }
   { MaybeScope sc(c, KF_CONV2, st);
     PnSegs A; memset(&A, 0, sizeof(A)); A.n = 3;
     for (int j = 0; j < 3; j++) { A.p[j] = c->c2ring + (size_t)((t + 1 + j) % 3) * Bp * 512 + r0 * 512; A.ld[j] = 512; A.width[j] = 512; }
-    if (x3) rc |= pn_launch_dense_x3(st, shadow_segs(c, A), c->L[PN_L_CONV2].wp, c->L[PN_L_CONV2].bias, 512, c->geom[PN_L_CONV2].act, tab, c2out, 512, c->c2outH, 16, B, c->x3_rg, np);
+    if (x3) rc |= pn_launch_dense_x3(st, shadow_segs(c, A), c->L[PN_L_CONV2].wp, c->L[PN_L_CONV2].bias, 512, c->geom[PN_L_CONV2].act, tab, c2out, 512, c->c2outH, 16, B, rg, np);
     else if (dm) rc |= pn_launch_dense(st, 0, A, NULL, c->L[PN_L_CONV2].wp, c->L[PN_L_CONV2].bias, 512, c->geom[PN_L_CONV2].act, tab, c2out, 512, B, 0, shadow(c, c2out), 16);   // + the shadow the GRUs read
     else rc |= pn_launch_dense(st, strict, A, c->L[PN_L_CONV2].w, c->L[PN_L_CONV2].wp, c->L[PN_L_CONV2].bias, 512, c->geom[PN_L_CONV2].act, tab, c2out, 512, B, small); }
   const float *x = c2out;
@@ -650,8 +605,8 @@ static int launch_rnn_rows(pn_ctx *c, size_t r0, size_t nrows, hipStream_t st, i
     const int li = PN_L_GRU1 + i;
     float *ho = c->gru[i] + (size_t)cur * Bp * 512 + r0 * 512, *hn = c->gru[i] + (size_t)nxt * Bp * 512 + r0 * 512;
     PnSegs X = seg1(x, 512, 512);
-    if (x3) rc |= pn_launch_gru_x3(st, shadow_segs(c, X), ho, shadow(c, ho), c->L[li].wp, c->L[li].rwp, c->L[li].bias, 512, c->geom[li].act, tab, hn, shadow(c, hn), B, c->x3_rg, np);
-    else if (dm) rc |= pn_launch_gru_d(st, shadow_segs(c, X), ho, shadow(c, ho), c->L[li].wp, c->L[li].rwp, c->L[li].bias, 512, c->geom[li].act, tab, hn, shadow(c, hn), B, c->x3_rg);
+    if (x3) rc |= pn_launch_gru_x3(st, shadow_segs(c, X), ho, shadow(c, ho), c->L[li].wp, c->L[li].rwp, c->L[li].bias, 512, c->geom[li].act, tab, hn, shadow(c, hn), B, rg, np);
+    else if (dm) rc |= pn_launch_gru_d(st, shadow_segs(c, X), ho, shadow(c, ho), c->L[li].wp, c->L[li].rwp, c->L[li].bias, 512, c->geom[li].act, tab, hn, shadow(c, hn), B, rg);
     else rc |= pn_launch_gru(st, strict, X, ho, c->L[li].w, c->L[li].rw, c->L[li].wp, c->L[li].rwp, c->L[li].bias, 512, c->geom[li].act, tab, hn, B, small_gru);
     x = hn;
   }
@@ -662,20 +617,20 @@ static int launch_rnn_rows(pn_ctx *c, size_t r0, size_t nrows, hipStream_t st, i
     PnSegs X; memset(&X, 0, sizeof(X)); X.n = 2;
     X.p[0] = g3; X.ld[0] = 512; X.width[0] = 512; X.p[1] = c2out; X.ld[1] = 512; X.width[1] = 512;
     const int li = PN_L_GRU_RB;
-    if (x3) rc |= pn_launch_gru_x3(st, shadow_segs(c, X), rbo, shadow(c, rbo), c->L[li].wp, c->L[li].rwp, c->L[li].bias, 128, c->geom[li].act, tab, rbn, shadow(c, rbn), B, c->x3_rg, np);
-    else if (dm) rc |= pn_launch_gru_d(st, shadow_segs(c, X), rbo, shadow(c, rbo), c->L[li].wp, c->L[li].rwp, c->L[li].bias, 128, c->geom[li].act, tab, rbn, shadow(c, rbn), B, c->x3_rg);
+    if (x3) rc |= pn_launch_gru_x3(st, shadow_segs(c, X), rbo, shadow(c, rbo), c->L[li].wp, c->L[li].rwp, c->L[li].bias, 128, c->geom[li].act, tab, rbn, shadow(c, rbn), B, rg, np);
+    else if (dm) rc |= pn_launch_gru_d(st, shadow_segs(c, X), rbo, shadow(c, rbo), c->L[li].wp, c->L[li].rwp, c->L[li].bias, 128, c->geom[li].act, tab, rbn, shadow(c, rbn), B, rg);
     else rc |= pn_launch_gru(st, strict, X, rbo, c->L[li].w, c->L[li].rw, c->L[li].wp, c->L[li].rwp, c->L[li].bias, 128, c->geom[li].act, tab, rbn, B, small); }   // gru_rb (1024->128) crosses over with the dense layers
   { MaybeScope sc(c, KF_FC_GB, st);    // input = [conv2 out | gru1 | gru2 | gru3 | gru_gb] (rnn.cpp:72-77)
     PnSegs A; memset(&A, 0, sizeof(A)); A.n = 5;
     const float *ps[5] = {c2out, g1, g2, g3, gb};
     for (int j = 0; j < 5; j++) { A.p[j] = ps[j]; A.ld[j] = 512; A.width[j] = 512; }
-    if (x3) rc |= pn_launch_dense_x3(st, shadow_segs(c, A), c->L[PN_L_FC_GB].wp, c->L[PN_L_FC_GB].bias, 34, c->geom[PN_L_FC_GB].act, tab, gr, 68, NULL, 0, B, c->x3_rg, np);
-    else if (c->n48) rc |= pn_launch_dense_n48(st, A, c->L[PN_L_FC_GB].wq, c->L[PN_L_FC_GB].bias, 34, c->geom[PN_L_FC_GB].act, tab, gr, 68, B);
-    else if (c->L[PN_L_FC_GB].wq) rc |= pn_launch_dense_n16(st, A, c->L[PN_L_FC_GB].wq, c->L[PN_L_FC_GB].bias, 34, c->geom[PN_L_FC_GB].act, tab, gr, 68, B);
+    if (x3) rc |= pn_launch_dense_x3(st, shadow_segs(c, A), c->L[PN_L_FC_GB].wp, c->L[PN_L_FC_GB].bias, 34, c->geom[PN_L_FC_GB].act, tab, gr, 68, NULL, 0, B, rg, np);
+    else if (c->plan.narrow == 2) rc |= pn_launch_dense_n48(st, A, c->L[PN_L_FC_GB].wq, c->L[PN_L_FC_GB].bias, 34, c->geom[PN_L_FC_GB].act, tab, gr, 68, B);
+    else if (c->plan.narrow == 1) rc |= pn_launch_dense_n16(st, A, c->L[PN_L_FC_GB].wq, c->L[PN_L_FC_GB].bias, 34, c->geom[PN_L_FC_GB].act, tab, gr, 68, B);
     else rc |= pn_launch_dense(st, strict, A, c->L[PN_L_FC_GB].w, c->L[PN_L_FC_GB].wp, c->L[PN_L_FC_GB].bias, 34, c->geom[PN_L_FC_GB].act, tab, gr, 68, B, small); }
   { MaybeScope sc(c, KF_FC_RB, st);
     PnSegs A = seg1(rbn, 128, 128);
-    if (c->L[PN_L_FC_RB].wq) rc |= pn_launch_dense_n16(st, A, c->L[PN_L_FC_RB].wq, c->L[PN_L_FC_RB].bias, 34, c->geom[PN_L_FC_RB].act, tab, gr + 34, 68, B);
+    if (c->plan.narrow == 1) rc |= pn_launch_dense_n16(st, A, c->L[PN_L_FC_RB].wq, c->L[PN_L_FC_RB].bias, 34, c->geom[PN_L_FC_RB].act, tab, gr + 34, 68, B);
     else rc |= pn_launch_dense(st, strict, A, c->L[PN_L_FC_RB].w, c->L[PN_L_FC_RB].wp, c->L[PN_L_FC_RB].bias, 34, c->geom[PN_L_FC_RB].act, tab, gr + 34, 68, B, small); }
   return rc ? -1 : 0;
 }
@@ -687,30 +642,11 @@ static int launch_rnn_rows(pn_ctx *c, size_t r0, size_t nrows, hipStream_t st, i
 // ramp and drain of ten launches idle.  No layer mixes rows, so the batch is cut into PN_NN_CHAINS row ranges (multiples of 128
 // rows) whose ten layers are independent chains of the SAME kernels on streams of their own: while one chain drains a layer the
 // blocks of another fill the slots.  One fork (the features are ready) and one join (before the back end) per frame; results
-// are bit-identical by construction (the same launches over sub-ranges of the rows).  Measured (profiles/r06_row_chains.log).
+// are bit-identical by construction (the same launches over sub-ranges of the rows).  The chain count and the shares are
+// pn_plan.h's (measured: profiles/r06_row_chains.log).
 // The first attempts — the rows past the last whole round on the small-batch kernels, in the same stream or beside the body —
 // cost 2-3x the tail's share: a small block holds a block slot for a single latency-bound MFMA chain, and any slot taken from
 // an exactly fitting body pushes that layer into an extra round.
-#define PN_MAX_CHAINS 4
-static int nn_chains_of(const pn_ctx *c) {
-  if (c->nn_mode != PN_NN_MFMA || c->small || c->small_gru) return 1;
-  const char *e = getenv("PN_NN_CHAINS");
-  // default: two chains unless the batch fits EVERY layer's rounds exactly — a multiple of 32 768 streams (8 rounds of the 512-wide
-  // layers, 2 of the 128-wide GRU) whose 128-row tile count also fits the 34-wide layers' single column block (<= 512 tiles or a
-  // multiple of 512): 32 768, 65 536, 131 072, ...  Measured (profiles/r06_row_chains.log): two chains win 0.6-2 % at 20 480, 49 152,
-  // 61 440, 69 632 and every size off the 4096-stream grid, and change nothing at 32 768 / 65 536 (+-0.03 ms) — where a second compute
-  // stream would only be one more hardware queue for the pipelined host path's copy streams to stay clear of (HIP has four by default)
-  const size_t mt = ((size_t)c->B + 127) / 128;
-  // (second session of round 6: with the direct-operand GRU kernels — 256-row blocks, 8 instead of 16 rounds per 512-wide layer at
-  // 65 536 streams, longer drains — two chains win at the exact fits from 65 536 streams too: 9.02 / 9.03 / 9.07 -> 8.93 / 8.99 / 8.96 ms
-  // per frame at 65 536, 17.99 -> 17.85 at 131 072, even at 32 768; profiles/r06_direct_operand_gru.log H)
-  const bool exact = (c->B % 32768 == 0) && (mt <= 512 || mt % 512 == 0) && !(c->direct && c->B >= 65536);
-  int n = e ? atoi(e) : ((c->B > 16384 && !exact) ? 2 : 1);
-  if (n < 1) n = 1;
-  if (n > PN_MAX_CHAINS) n = PN_MAX_CHAINS;
-  while (n > 1 && (size_t)c->B < (size_t)n * 4096) n--;      // a chain of fewer than 4096 rows is the small-batch regime: not worth a stream
-  return n;
-}
 // Every extra chain's stream must have a HARDWARE queue of its own: HIP multiplexes the streams of one priority over a few queues,
 // and on a queue shared with the context's stream a chain runs in front of the others instead of beside them.  Same remedy as for
 // the copy streams of the pipelined host path: default-priority streams PROBED against the streams they must not share a queue
@@ -724,36 +660,43 @@ static std::vector<hipStream_t> busy_streams(const pn_ctx *c) {
   if (c->pipe.d2h) v.push_back(c->pipe.d2h);
   return v;
 }
-static int chain_streams_init(pn_ctx *c, int n) {
+static int chain_streams_init(pn_ctx *c) {
   int lo = 0, hi = 0;
   PN_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-  for (int k = 1; k < n; k++) {
-    if (c->chain_stream[k]) continue;
+  for (int k = 1; k < c->plan.chains; k++) {
     if (pipe_make_stream(c, &c->chain_stream[k], 'a', hi, 'h', busy_streams(c), &c->chain_kind[k])) return -1;
     PN_HIP_CHECK(hipEventCreateWithFlags(&c->chain_join[k], hipEventDisableTiming));
   }
-  if (!c->chain_fork) PN_HIP_CHECK(hipEventCreateWithFlags(&c->chain_fork, hipEventDisableTiming));
+  PN_HIP_CHECK(hipEventCreateWithFlags(&c->chain_fork, hipEventDisableTiming));
   return 0;
 }
+// hipSuccess, or the error recorded as the frame's (pn_set_error) unless an earlier one already is
+static bool chain_ok(hipError_t e, const char *what, int &rc) {
+  if (e == hipSuccess) return true;
+  if (!rc) pn_set_error("%s failed: %s", what, hipGetErrorString(e));
+  rc = -1;
+  return false;
+}
 static int launch_rnn(pn_ctx *c) {
-  const int n = nn_chains_of(c);
-  if (n <= 1) return launch_rnn_rows(c, 0, c->B, c->stream, c->small, c->small_gru);
-  if (chain_streams_init(c, n)) return -1;
-  // row ranges: equal shares rounded up to whole 128-row tiles; the last chain takes what is left
-  const size_t tile = c->direct ? 128 * (size_t)c->x3_rg : 128;            // rows per block of the family's kernels
-  const size_t B = c->B, share = ((B + n - 1) / n + tile - 1) / tile * tile;
+  const int n = c->plan.chains;
+  if (n <= 1) return launch_rnn_rows(c, 0, c->B, c->stream);
+  const size_t B = c->B, share = pn_plan_share(c->plan, B);
   PN_HIP_CHECK(hipEventRecord(c->chain_fork, c->stream));                 // the front end's features (and last frame's state) are in place
+  // Once forked, every chain that started is joined back into the context's stream whatever fails after it (a refused launch,
+  // a HIP error): nothing stays unordered.  No chain starts after a failure; the first error is the one returned.
   int rc = 0;
-  for (int k = n - 1; k >= 0; k--) {                                      // the context's own stream last: the others are already queued
+  bool started[PN_MAX_CHAINS] = {};
+  for (int k = n - 1; k >= 0 && !rc; k--) {                               // the context's own stream last: the others are already queued
     const size_t r0 = share * k, nr = r0 >= B ? 0 : (B - r0 < share ? B - r0 : share);
     if (!nr) continue;
     hipStream_t st = k ? c->chain_stream[k] : c->stream;
-    if (k) PN_HIP_CHECK(hipStreamWaitEvent(st, c->chain_fork, 0));
-    rc |= launch_rnn_rows(c, r0, nr, st, c->small, c->small_gru);
-    if (k) PN_HIP_CHECK(hipEventRecord(c->chain_join[k], st));             // also after a refused launch: nothing stays unordered
+    if (k && !(started[k] = chain_ok(hipStreamWaitEvent(st, c->chain_fork, 0), "hipStreamWaitEvent(chain, fork)", rc))) break;
+    if (launch_rnn_rows(c, r0, nr, st)) rc = -1;
   }
-  for (int k = 1; k < n; k++) PN_HIP_CHECK(hipStreamWaitEvent(c->stream, c->chain_join[k], 0));
-  return rc ? -1 : 0;
+  for (int k = 1; k < n; k++)
+    if (started[k] && chain_ok(hipEventRecord(c->chain_join[k], c->chain_stream[k]), "hipEventRecord(join)", rc))
+      chain_ok(hipStreamWaitEvent(c->stream, c->chain_join[k], 0), "hipStreamWaitEvent(stream, join)", rc);
+  return rc;
 }
 
 // Known-answer self-test of the MFMA network kernels (PERCEPNET_SELFTEST=0 skips it).
@@ -768,7 +711,7 @@ static int launch_rnn(pn_ctx *c) {
 // differs by more than 2e-5 (fp32 operands) / 4e-3 (fp16 operands, whose rounding the x3 weights amplify).  The verdict is cached for
 // the process; a self-test that cannot allocate its ~70 MB of temporaries is reported as SKIPPED, not as a failure.
 static std::mutex g_selftest_mu;
-static std::map<std::tuple<int, int, int, int, int, int>, int> g_selftest_done;     // key -> 0 passed, 1 skipped
+static std::map<std::tuple<int, int, int, int, int, int, int>, int> g_selftest_done;     // key -> 0 passed, 1 skipped
 
 pn_model *pn_model_from_sources(const struct PnLayerSrc *src);
 static pn_model *selftest_model() {
@@ -800,8 +743,8 @@ static pn_model *selftest_model() {
 static int nn_selftest(pn_ctx *c) {
   const char *env = getenv("PERCEPNET_SELFTEST");
   if (env && !atoi(env)) return 0;
-  const int n16 = c->n48 ? 2 : (c->L[PN_L_FC_RB].wq != NULL);   // narrow layers: 1 = the 16x16x4 kernel (small batches; fc_rb in every MFMA mode, fc_gb in the fp32 one), 2 = fc_gb on its batch form, 0 = the batch GEMM
-  const auto key = std::make_tuple(c->device, c->nn_mode, c->small, c->small_gru, (c->nn_mode == PN_NN_MFMA_X3 || c->nn_mode == PN_NN_MFMA_F16) ? c->x3_rg : (c->direct ? 10 + c->x3_rg : 0), n16);
+  const PnPlan &p = c->plan;      // the kernel-selecting fields; the front end and the chains select no network kernel
+  const auto key = std::make_tuple(c->device, c->nn_mode, p.small, p.small_gru, p.direct, p.rg, p.narrow);
   std::lock_guard<std::mutex> lk(g_selftest_mu);
   if (g_selftest_done.count(key)) return 0;
   const int rows = 192;
@@ -811,9 +754,11 @@ static int nn_selftest(pn_ctx *c) {
   std::vector<float> feat((size_t)rows * PN_NFEAT), gr[2][2];
   int rc = m ? 0 : -1;
   bool oom = false;
+  PnPlan plan[2] = {p, pn_plan_for(rows, PN_NN_STRICT)};
+  plan[0].chains = 1;                                    // (192 rows are one chain)
   for (int pass = 0; pass < 2 && !rc; pass++) {          // pass 0: the kernel family under test; pass 1: STRICT kernels
     g_last_alloc_oom = false;
-    cx[pass] = ctx_create(m, c->device, rows, pass ? PN_NN_STRICT : c->nn_mode, NULL, false, c->small, c->small_gru, c->x3_rg, n16, pass ? 0 : c->direct);
+    cx[pass] = ctx_create(m, c->device, rows, pass ? PN_NN_STRICT : c->nn_mode, NULL, false, &plan[pass]);
     if (!cx[pass]) { rc = -1; oom = g_last_alloc_oom; break; }
     unsigned x = 12345u;
     for (int step = 0; step < 2 && !rc; step++) {
@@ -837,12 +782,12 @@ static int nn_selftest(pn_ctx *c) {
     }
   if (env && atoi(env) >= 2)
     fprintf(stderr, "percepnet_hip: network self-test device %d nn_mode %d dense=%s gru=%s: worst |delta g,r| %g (tolerance %g) at row %d output %d\n",
-            c->device, c->nn_mode, c->small ? "small" : "batch", c->small_gru ? "small" : "batch", (double)worst, (double)tol, wrow, wcol);
+            c->device, c->nn_mode, p.small ? "small" : "batch", p.small_gru ? "small" : "batch", (double)worst, (double)tol, wrow, wcol);
   if (!(worst <= tol)) {
     pn_set_error("network self-test FAILED (nn_mode %d, dense=%s gru=%s): the MFMA kernels differ from the reference-order kernels by %g "
                  "(> %g) at row %d (row %% 32 = %d), output %d on the built-in weight set — the build's instruction schedule is "
-                 "not the validated one (DESIGN.md 4.3); refusing to run", c->nn_mode, c->small ? "small" : "batch",
-                 c->small_gru ? "small" : "batch", (double)worst, (double)tol, wrow, wrow % 32, wcol);
+                 "not the validated one (DESIGN.md 4.3); refusing to run", c->nn_mode, p.small ? "small" : "batch",
+                 p.small_gru ? "small" : "batch", (double)worst, (double)tol, wrow, wrow % 32, wcol);
     return -1;
   }
   g_selftest_done[key] = 0;
@@ -877,7 +822,7 @@ static int dsp_selftest(pn_ctx *c) {
   const char *env = getenv("PERCEPNET_SELFTEST");
   if (env && !atoi(env)) return 0;
   static std::map<std::pair<int, int>, int> done;
-  const auto key = std::make_pair(c->device, c->fe_mode);
+  const auto key = std::make_pair(c->device, c->plan.fe);
   std::lock_guard<std::mutex> lk(g_selftest_mu);
   if (done.count(key)) return 0;
   const int Bt = 40;
@@ -885,7 +830,9 @@ static int dsp_selftest(pn_ctx *c) {
   selftest_pcm(pcm);
   pn_model *m = selftest_model();
   g_last_alloc_oom = false;
-  pn_ctx *t = m ? ctx_create(m, c->device, Bt, PN_NN_MFMA, NULL, false, -1, -1) : NULL;
+  PnPlan plan = pn_plan_for(Bt, PN_NN_MFMA);
+  plan.fe = c->plan.fe;
+  pn_ctx *t = m ? ctx_create(m, c->device, Bt, PN_NN_MFMA, NULL, false, &plan) : NULL;
   if (!t) {
     const bool oom = g_last_alloc_oom;
     pn_model_free(m);
@@ -911,11 +858,11 @@ static int dsp_selftest(pn_ctx *c) {
       }
   }
   pn_ctx_destroy(t); pn_model_free(m);
-  if (env && atoi(env) >= 2) fprintf(stderr, "percepnet_hip: DSP self-test device %d front end %d: %s\n", c->device, c->fe_mode, rc ? msg.c_str() : "70 features + 14 silence flags bit-equal to the CPU oracle, 40 streams identical");
+  if (env && atoi(env) >= 2) fprintf(stderr, "percepnet_hip: DSP self-test device %d front end %d: %s\n", c->device, c->plan.fe, rc ? msg.c_str() : "70 features + 14 silence flags bit-equal to the CPU oracle, 40 streams identical");
   if (rc == -1) { pn_set_error("DSP self-test could not run: %s", msg.c_str()); return -1; }
   if (rc) {
     pn_set_error("DSP self-test FAILED (front end %s): %s does not match the CPU reference's known answer — this build of the DSP "
-                 "kernels is not bit-exact (DESIGN.md 4.4); refusing to run", c->fe_mode == FE_SPLIT ? "split" : (c->fe_mode == FE_MONO_G2 ? "g2" : "g4"), msg.c_str());
+                 "kernels is not bit-exact (DESIGN.md 4.4); refusing to run", c->plan.fe == FE_SPLIT ? "split" : (c->plan.fe == FE_MONO_G2 ? "g2" : "g4"), msg.c_str());
     return -1;
   }
   done[key] = 0;
@@ -925,7 +872,7 @@ static int dsp_selftest(pn_ctx *c) {
 static int process_dev(pn_ctx *c, const void *d_in, void *d_out, float *d_gr, int is_i16) {
   if (!c || !d_in || !d_out) { pn_set_error("NULL argument"); return -1; }
   PN_ON_DEVICE(c);
-  if (c->fe_mode == FE_SPLIT) {
+  if (c->plan.fe == FE_SPLIT) {
     { Scope sc(c, KF_FE_SPEC_IN);
       pn_launch_fe_spec_in(c->stream, c->tables, c->B, c->t, d_in, is_i16, PN_FRAME, 1.f / 32768.f, c->hist, c->yring, c->eyring, c->dsp_grid_cap); }
     { Scope sc(c, KF_FE_PITCH);
@@ -935,7 +882,7 @@ static int process_dev(pn_ctx *c, const void *d_in, void *d_out, float *d_gr, in
                             c->silence, nullptr, c->dsp_grid_cap); }
   } else {
     Scope sc(c, KF_FRONTEND);
-    (c->fe_mode == FE_MONO_G2 ? pn_launch_frontend_g2 : pn_launch_frontend)(c->stream, c->tables, c->B, c->t, d_in, is_i16, PN_FRAME, 1.f / 32768.f,
+    (c->plan.fe == FE_MONO_G2 ? pn_launch_frontend_g2 : pn_launch_frontend)(c->stream, c->tables, c->B, c->t, d_in, is_i16, PN_FRAME, 1.f / 32768.f,
         c->hist, c->yring, c->eyring, c->Ps, c->feat, c->silence, c->last_period, c->last_gain, nullptr, c->dsp_grid_cap);
   }
   if (launch_rnn(c)) return -1;                        // a refused launch fails the frame (pn_last_error says which layer)
@@ -1390,7 +1337,7 @@ static int rnn_state_copy(pn_ctx *c, bool to_device, float *conv1, float *conv2,
   auto resplit = [&](float *dev, int width) {
     if (x3) split_rc |= pn_launch_split_x3(c->stream, dev, width, width, shadow(c, dev), (int)Bp, 2);
     if (f16) split_rc |= pn_launch_split_x3(c->stream, dev, width, width, shadow(c, dev), (int)Bp, 1);
-    if (c->direct && to_device && shadow(c, dev)) split_rc |= pn_launch_split_d(c->stream, dev, width, width, shadow(c, dev), (int)Bp);   // (GRU states; the conv FIFOs have no shadow there)
+    if (c->plan.direct && to_device && shadow(c, dev)) split_rc |= pn_launch_split_d(c->stream, dev, width, width, shadow(c, dev), (int)Bp);   // (GRU states; the conv FIFOs have no shadow there)
   };
   if (conv1) for (int j = 0; j < 4; j++) {
     float *d = c->c1ring + (size_t)((t + 1 + j) % 5) * Bp * 128;
@@ -1517,7 +1464,7 @@ extern "C" int pn_ctx_import_streams(pn_ctx *c, const int32_t *ids, int n, const
     void *S = shadow(c, slot);
     if (!S) return;                                    // no shadow of this buffer in this mode / family
     if (x3) rc |= pn_launch_split_x3_rows(c->stream, slot, width, width, S, d, d_status, n, np);
-    else if (c->direct) rc |= pn_launch_split_d_rows(c->stream, slot, width, width, S, d, d_status, n);
+    else if (c->plan.direct) rc |= pn_launch_split_d_rows(c->stream, slot, width, width, S, d, d_status, n);
   };
   for (int j = 0; j < 4; j++) resplit(c->c1ring + (size_t)((tn + 1 + j) % 5) * Bp * 128, 128);
   for (int j = 0; j < 2; j++) resplit(c->c2ring + (size_t)((tn + 1 + j) % 3) * Bp * 512, 512);

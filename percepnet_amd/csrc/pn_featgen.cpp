@@ -5,6 +5,7 @@
 // and — when the caller wants the TEST build's test_output.pcm — the inference back-end kernel on the
 // noisy spectrum with the ideal gains, through the speech state's synthesis memory (744-757).
 #include "pn_launch.h"
+#include "pn_plan.h"
 #include "../../include/percepnet_hip.h"
 #include <stdlib.h>
 #include <string.h>
@@ -17,6 +18,7 @@ struct FgSide {                 // one DenoiseState's worth of DSP state per str
 
 struct pn_featgen {
   int device, B; int64_t t; size_t bytes;
+  int fe;                       // front end (pn_plan.h): the single-launch kernel for FE_MONO_G4, else the phase-split one
   hipStream_t stream; bool own_stream;
   PnTables *tables;
   FgSide clean, noisy;
@@ -65,7 +67,7 @@ extern "C" pn_featgen *pn_featgen_create(int device, int n_pairs, void *hip_stre
   DeviceGuard _dg(device);
   if (!_dg.ok) { pn_set_error("hipSetDevice(%d) failed", device); return NULL; }
   pn_featgen *c = new pn_featgen();
-  c->device = device; c->B = n_pairs; c->t = 0; c->bytes = 0;
+  c->device = device; c->B = n_pairs; c->t = 0; c->bytes = 0; c->fe = pn_plan_for(n_pairs, PN_NN_MFMA).fe;
   if (hip_stream) { c->stream = (hipStream_t)hip_stream; c->own_stream = false; }
   else {
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { pn_set_error("hipStreamCreate failed"); delete c; return NULL; }
@@ -122,9 +124,8 @@ static int fg_frame(pn_featgen *c, const int16_t *sp, const int16_t *no, long lo
   const size_t B = c->B;
   // train() analyses the noisy frame first (730) and the speech frame second (731); the two states are
   // independent, so the order of the launches is immaterial
-  // the phase-split front end (three launches per analysed signal) unless PERCEPNET_FE=mono asks for the single-launch kernel
-  static const bool mono = getenv("PERCEPNET_FE") && (!strcmp(getenv("PERCEPNET_FE"), "mono") || !strcmp(getenv("PERCEPNET_FE"), "g4"));
-  auto fe = mono ? pn_launch_frontend : pn_launch_frontend_split;
+  // the phase-split front end (three launches per analysed signal) unless the plan asks for the single-launch kernel
+  auto fe = c->fe == FE_MONO_G4 ? pn_launch_frontend : pn_launch_frontend_split;
   fe(c->stream, c->tables, c->B, c->t, no, 1, in_stride, 1.f, c->noisy.hist, c->noisy.yring, c->noisy.eyring, c->noisy.Ps,
      c->noisy.feat, c->noisy.silence, c->noisy.last_period, c->noisy.last_gain, c->noisy.aux, 0);
   fe(c->stream, c->tables, c->B, c->t, sp, 1, in_stride, 1.f, c->clean.hist, c->clean.yring, c->clean.eyring, c->clean.Ps,

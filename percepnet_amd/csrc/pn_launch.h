@@ -95,7 +95,6 @@ int pn_launch_dense_x3(hipStream_t st, const PnSegs &A, const void *Wp, const fl
 int pn_launch_gru_x3(hipStream_t st, const PnSegs &X, const float *h_old, const void *h_oldS, const void *Wp,
                       const void *Up, const float *b, int N, int act, const float *tansig, float *h_new, void *h_newS,
                       int n_rows, int rg, int np);
-int pn_x3_rg_for(int n_rows);
 int pn_x3_sat_set(int enable);          // debug counter of operand values clamped to +-65504 (current device): reset + switch
 long long pn_x3_sat_read();             // ... and its value, or -1
 int pn_launch_split_x3(hipStream_t st, const float *src, int ld, int width, void *S, int n_rows_padded, int np);
@@ -106,8 +105,6 @@ int pn_launch_gru_d(hipStream_t st, const PnSegs &X, const float *h_old, const v
                     const float *Up, const float *b, int N, int act, const float *tansig, float *h_new, void *h_newS,
                     int n_rows, int rg);
 int pn_launch_split_d(hipStream_t st, const float *src, int ld, int width, void *S, int n_rows);
-int pn_direct_for(int n_rows);          // 1: a PN_NN_MFMA context of this many streams runs the direct-operand family (PERCEPNET_NN_DIRECT overrides)
-int pn_direct_rg_for(int n_rows);       // its rows per wave / 32 (PERCEPNET_NN_DIRECT_RG overrides)
 // narrow layers (N <= 48) of small-batch contexts: 16x16x4 MFMA tiles, one wave per (16 rows, 16 columns) (pn_nn_small.hip)
 size_t pn_packed_floats_n16(int K, int ncols);
 void pn_pack_weights_n16(const float *W, int K, int ncols, float *Wq);
@@ -120,9 +117,6 @@ int pn_launch_dense_n48(hipStream_t st, const PnSegs &A, const float *Wq, const 
 // the frame (launch_rnn -> pn_process_*), it must never report a frame whose layer outputs are stale.
 // pn_check_dense_geometry / pn_check_gru_geometry (pn_launch_check.h) are the HIP-free predicates behind the refusals.
 // small: 1 = the small-batch kernel family (pn_nn_small.hip), 0 = the batch-GEMM kernels; ignored when strict.
-// pn_small_rows(): the batch size up to which a context picks the small family (PERCEPNET_SMALL_ROWS, default 4096).
-int pn_small_rows();
-int pn_small_gru_rows();
 // outS (optional, batch kernels only): fragment-order fp32 shadow of `out`, a buffer nts_out column tiles wide (pn_nn_common.h)
 int pn_launch_dense(hipStream_t st, int strict, const PnSegs &A, const float *W, const float *Wp, const float *bias,
                      int N, int act, const float *tansig, float *out, int ldo, int n_rows, int small, void *outS = nullptr, int nts_out = 0);

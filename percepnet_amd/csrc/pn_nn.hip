@@ -579,20 +579,8 @@ __global__ __launch_bounds__(NN_THREADS, 2) void pn_dense_mfma_ps_kernel(
 }
 
 // ---- launchers -----------------------------------------------------------------------------------
-// Batches of at most this many streams run the small-batch kernel family (pn_nn_small.hip: one 32x32 tile and one
-// accumulator chain per wave, 3-4x more blocks), larger ones the batch-GEMM kernels above.  Same numerics either way.
-// Measured crossovers (profiles/r02f_small_batch_study.txt): the dense/conv kernels win up to 4096 streams, the
-// gate-per-wave GRU up to ~1500.  PERCEPNET_SMALL_ROWS / PERCEPNET_SMALL_GRU_ROWS override them (0 = never).
-int pn_small_rows() {                     // read at every context creation (tests switch families through it)
-  const char *e = getenv("PERCEPNET_SMALL_ROWS");
-  return e ? atoi(e) : 4096;
-}
-int pn_small_gru_rows() {
-  const char *e = getenv("PERCEPNET_SMALL_GRU_ROWS");
-  if (e) return atoi(e);
-  const int d = pn_small_rows();
-  return d < 1536 ? d : 1536;
-}
+// small: the small-batch kernel family (pn_nn_small.hip: one 32x32 tile and one accumulator chain per wave, 3-4x more
+// blocks), else the batch-GEMM kernels above.  Same numerics either way; which one a context runs is pn_plan.h's choice.
 int pn_launch_dense_small(hipStream_t st, const PnSegs &A, const float *Wp, const float *bias, int N, int act,
                           const float *tansig, float *out, int ldo, int n_rows, int ct_padded);
 int pn_launch_gru_small(hipStream_t st, const PnSegs &X, const float *h_old, const float *Wp, const float *Up,

@@ -240,24 +240,7 @@ __global__ __launch_bounds__(256) void pn_split_d_rows_kernel(const float *__res
 }
 
 // ---- launchers -----------------------------------------------------------------------------------------------------
-// Which PN_NN_MFMA contexts run their GRU steps here (read at every context creation; tests switch it between contexts):
-// PERCEPNET_NN_DIRECT=0|1 overrides the batch-size rule.  Measured against the batch family, same box, default chain rule
-// (profiles/r06_direct_operand_gru.log): frame time -0.6 % at 24 576 streams, -1.1 % at 32 768, -1.2 % at 61 440 / 66 560, -1.4 % at
-// 69 632 (the 512 -> 512 step at 65 536: 1.552 -> 1.523 ms), even at 16 384, +1.4 % at 8192 (too few blocks per launch).
-#ifndef PN_DIRECT_ROWS
-#define PN_DIRECT_ROWS 24576
-#endif
-int pn_direct_for(int n_rows) {
-  const char *e = getenv("PERCEPNET_NN_DIRECT");
-  if (e) return atoi(e) ? 1 : 0;
-  return n_rows >= PN_DIRECT_ROWS;
-}
-int pn_direct_rg_for(int n_rows) {
-  const char *e = getenv("PERCEPNET_NN_DIRECT_RG");
-  const int env = e ? atoi(e) : 0;
-  if (env == 1 || env == 2) return env;
-  return n_rows >= 32768 ? 2 : 1;
-}
+// (which PN_NN_MFMA contexts run their GRU steps here, and at how many rows per wave: pn_plan.h)
 // X panels / h_oldS / h_newS: the uint4* fragment-order fp32 shadows; Wp / Up: the fp32 packed tiles of pn_pack_weights.
 // rg: row groups of 32 per wave (2: 256-row blocks, two per CU; 1: 128-row blocks, three)
 int pn_launch_gru_d(hipStream_t st, const PnSegs &X, const float *h_old, const void *h_oldS, const float *Wp,

@@ -872,18 +872,8 @@ int pn_pack_weights_x3(const float *W, int K, int k_alloc, int ncols, int ct_rou
 
 int pn_dense_x3_nt(int N) { return N >= 128 ? 4 : 2; }
 
-// rows per wave: 2 row groups of 32 (256-row blocks, two per CU: fewest operand bytes per MFMA, best when the grid fills
-// the chip several times over) or 1 (128-row blocks, three per CU: twice the blocks, shorter chains — measured 0.45 vs 0.60 ms
-// per frame at 1024 streams, 0.60 vs 0.68 at 4096, equal at 16 384, 0.60 vs 0.585 per GRU step at 65 536).  The context
-// fixes the choice at creation (and its self-test runs the same instantiation); PERCEPNET_X3_RG=1|2 overrides.
-int pn_x3_rg_for(int n_rows) {
-  const char *e = getenv("PERCEPNET_X3_RG");           // read at every context creation (tests switch it between contexts)
-  const int env = e ? atoi(e) : 0;
-  if (env >= 1 && env <= 3) return env;
-  // 3 = 64 rows per wave with the GRUs on the paired-phase kernel (pn_gru_x3p_kernel): opt-in only — measured at parity
-  // with the one-tile-per-block kernel (0.305 vs 0.291 ms fp16 operands, 0.57 vs 0.59 ms split precision)
-  return n_rows >= 32768 ? 2 : 1;
-}
+// rows per wave (rg): 2 row groups of 32 (256-row blocks, two per CU) or 1 (128-row blocks, three per CU); 3 = 64 rows with the
+// GRUs on the paired-phase kernel.  The context fixes the choice at creation (pn_plan.h) and its self-test runs the same instantiation.
 
 // A: panels carry the uint4* shadows of equally wide buffers (width = logical columns, a multiple of 32);
 // out (fp32, optional) / outS (shadow of a buffer nts_out column tiles wide, optional)

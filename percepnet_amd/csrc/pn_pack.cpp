@@ -62,3 +62,16 @@ extern "C" PN_EXPORT int pn_debug_check_launch(int kind, int n_panels, int width
     default: pn_set_error("pn_debug_check_launch: unknown kind %d", kind); return -1;
   }
 }
+
+// ---- the kernel families of a context without a GPU (include/percepnet_hip.h: pn_debug_plan) -------------------------------
+#include "pn_plan.h"
+extern "C" PN_EXPORT int pn_debug_plan(int n_streams, int nn_mode, char *buf, size_t n) {
+  if (!buf || !n || n_streams < 1) { pn_set_error("pn_debug_plan: bad argument"); return -1; }
+  if (nn_mode != PN_NN_MFMA && nn_mode != PN_NN_STRICT && nn_mode != PN_NN_MFMA_F16 && nn_mode != PN_NN_MFMA_X3) { pn_set_error("bad nn_mode %d", nn_mode); return -1; }
+  const PnPlan p = pn_plan_for(n_streams, nn_mode);
+  const int f = pn_plan_describe(p, nn_mode, buf, n);
+  if (f < 0 || (size_t)f >= n) { pn_set_error("pn_debug_plan: buffer too small"); return -1; }
+  const int w = snprintf(buf + f, n - f, " nn_chains=%d tile=%zu share=%zu", p.chains, pn_plan_tile(p), pn_plan_share(p, (size_t)n_streams));
+  if (w < 0 || (size_t)(f + w) >= n) { pn_set_error("pn_debug_plan: buffer too small"); return -1; }
+  return f + w;
+}

@@ -13,13 +13,12 @@ import pytest
 
 from percepnet_amd import api, synth
 from tests import backend_model as bm
+from tests import families
 
 pytestmark = pytest.mark.gpu
 MODES = {"strict": api.NN_STRICT, "mfma": api.NN_MFMA, "x3": api.NN_MFMA_X3, "f16": api.NN_MFMA_F16}
 LIMITS = [math.inf, 0.0, 1.5, 6.0, 12.0, 24.0, 60.0, 1000.0]
 DELAY = 2880          # output frame t vs input frame t; 2400 between the CLI's input and output files
-FAMILY_ENV = ("PERCEPNET_SMALL_ROWS", "PERCEPNET_SMALL_GRU_ROWS", "PERCEPNET_NN_DIRECT", "PERCEPNET_NN_DIRECT_RG",
-              "PERCEPNET_X3_RG", "PERCEPNET_N16_ROWS", "PERCEPNET_N48", "PN_NN_CHAINS", "PERCEPNET_FE", "PERCEPNET_FE_G2")
 
 
 @pytest.fixture(scope="module")
@@ -31,7 +30,7 @@ def model(blob):
 
 @pytest.fixture(autouse=True)
 def default_families(monkeypatch):
-    for k in FAMILY_ENV:
+    for k in families.FAMILY_ENV:
         monkeypatch.delenv(k, raising=False)
 
 

@@ -74,7 +74,7 @@ def test_direct_family_is_bit_identical_to_the_batch_family(model, oracle, monke
 def test_direct_family_as_row_range_chains(model, monkeypatch):
     """8192 + 300 streams as one, two and three (capped to two) row-range chains, 64 rows per wave: the chains' shares are whole
     256-row blocks (4352 + 4140) and a block past a chain's last row stores nothing (neither rows nor shadow entries: they are the
-    other chain's) — bit-identical to the batch family on one stream."""
+    other chain's) — bit-identical to the batch family on one stream.  PN_NN_CHAINS changed after creation changes nothing."""
     B, T = 8192 + 300, 5
     pool = synth.synth_batch(64, T)
     pcm = pool[np.arange(B) % 64].copy()
@@ -86,8 +86,13 @@ def test_direct_family_as_row_range_chains(model, monkeypatch):
     for chains in (1, 2, 3):
         ctx = _ctx(monkeypatch, model, B, True, rg=2, chains=chains)
         assert ctx.describe()["nn_chains"].split(":")[0] == str(min(chains, 2)), ctx.describe()
+        monkeypatch.setenv("PN_NN_CHAINS", "2" if chains == 1 else "1")       # read once, at creation: the context keeps its chains
+        assert ctx.describe()["nn_chains"].split(":")[0] == str(min(chains, 2)), ctx.describe()
+        ctx.set_profiling(True)
         o, g = ctx.run_pcm(pcm)
         r = ctx.compute_rnn(feat)
+        assert ctx.kernel_times()["fc"][1] == (T + 1) * min(chains, 2), ctx.kernel_times()["fc"]      # one fc launch per chain per step
+        assert ctx.describe()["nn_chains"].split(":")[0] == str(min(chains, 2)), ctx.describe()
         ctx.close()
         assert np.array_equal(ref[0], o), chains
         assert np.array_equal(ref[1].view(np.uint32), g.view(np.uint32)), chains

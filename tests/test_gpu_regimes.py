@@ -1,15 +1,15 @@
 """Row independence at every default kernel-family boundary, checked on EVERY row with distinct inputs (-m gpu).
 
-The batch size picks the network kernels (pn_context.cpp ctx_create / nn_chains_of; pn_small_rows, pn_small_gru_rows,
-pn_direct_for, pn_direct_rg_for, pn_x3_rg_for, n16_rows_ok, n48_enabled), and every non-STRICT mode promises that a
-stream's PCM, g|r, features and silence flag depend, bit for bit, only on that stream's own input.  The large-batch
-tests elsewhere fill their batches with copies of 16 or 64 streams, so a kernel that hands row r the result of row
-r +- 16 k (a lane or fragment permutation, a wrong 128-row chunk of a 256-row block, a chain's r0 off by a block) still
-passes them.  Here no two rows carry the same input: row r carries pool stream r % 256 rotated inside each frame by an
+The batch size picks the network kernels, once, when the context is created (percepnet_amd/csrc/pn_plan.h: pn_plan_for,
+the only reader of the family overrides), and every non-STRICT mode promises that a stream's PCM, g|r, features and
+silence flag depend, bit for bit, only on that stream's own input.  The large-batch tests elsewhere fill their batches
+with copies of 16 or 64 streams, so a kernel that hands row r the result of row r +- 16 k (a lane or fragment
+permutation, a wrong 128-row chunk of a 256-row block, a chain's r0 off by a block) still passes them.  Here no two rows carry the same input: row r carries pool stream r % 256 rotated inside each frame by an
 amount that never repeats for rows sharing a pool stream, and 256 slots — the tile, chain and last-block boundaries
 among them — carry the pool streams unrotated for the oracle anchor.
 
-  * test_every_row_of_a_regime_*: describe() against the regime map REGIMES; 14 frames (every ring and both GRU halves
+  * test_every_row_of_a_regime_*: describe() against the regime map REGIMES (tests/families.py) and against pn_debug_plan
+    (the plan computed without a GPU, as tests/test_plan_host.py checks it); 14 frames (every ring and both GRU halves
     wrap); every row bit-identical to a 1024-stream context of the same nn_mode fed the same rows chunk by chunk (the
     family that test_gpu_longrun checks against the oracle for every stream); the unrotated slots against the oracle.
   * test_lifecycle_at_chained_and_direct_sizes: per-stream reset and the active set (pn_state.hip, pn_active.hip) on
@@ -21,6 +21,8 @@ import numpy as np
 import pytest
 
 from percepnet_amd import api, synth
+from tests import families
+from tests.families import REGIMES, chain_share, rows_per_block
 
 P = 256                 # distinct pool streams
 T_ROWS = 14             # frames of the every-row check: the 12-slot history ring and the 6-slot look-ahead ring wrap
@@ -28,51 +30,8 @@ T_LIFE, T_RESET = 30, 13
 REF_ROWS = 1024         # the reference context
 PCM_TOL_LSB = 1
 GR_TOL = 2e-5
-FAMILY_ENV = ("PERCEPNET_SMALL_ROWS", "PERCEPNET_SMALL_GRU_ROWS", "PERCEPNET_NN_DIRECT", "PERCEPNET_NN_DIRECT_RG",
-              "PERCEPNET_X3_RG", "PERCEPNET_N16_ROWS", "PERCEPNET_N48", "PN_NN_CHAINS", "PERCEPNET_FE",
-              "PERCEPNET_FE_G2")
 MODES = {"mfma": api.NN_MFMA, "x3": api.NN_MFMA_X3, "f16": api.NN_MFMA_F16}
-N48 = "fc_gb:n48+fc_rb:batch"
-
-
-def _r(dense, gru, gru_rb, narrow, chains, share=None):
-    return dict(dense=dense, gru=gru, gru_rb=gru_rb, narrow=narrow, chains=chains, share=share)
-
-
-# The regime map with default settings: (mode, B) -> the families ctx_create picks.  Moving a threshold moves a row of
-# this table; move the sizes with it so that each boundary keeps a size on both sides.
-REGIMES = {
-    ("mfma", 1536): _r("small", "small", "small", "n16", 1),
-    ("mfma", 1537): _r("small", "batch", "small", "n16", 1),
-    ("mfma", 4096): _r("small", "batch", "small", "n16", 1),
-    ("mfma", 4097): _r("batch", "batch", "batch", "n16", 1),
-    ("mfma", 16384): _r("batch", "batch", "batch", "n16", 1),
-    ("mfma", 16385): _r("batch", "batch", "batch", "n16", 2, 8320),
-    ("mfma", 20480): _r("batch", "batch", "batch", "n16", 2, 10240),
-    ("mfma", 20481): _r("batch", "batch", "batch", N48, 2, 10368),
-    ("mfma", 24575): _r("batch", "batch", "batch", N48, 2, 12288),
-    ("mfma", 24576): _r("batch", "direct_rows32", "direct_rows32", N48, 2, 12288),
-    ("mfma", 32767): _r("batch", "direct_rows32", "direct_rows32", N48, 2, 16384),
-    ("mfma", 32768): _r("batch", "direct_rows64", "direct_rows64", N48, 1),          # an exact fit: one chain
-    ("mfma", 65536): _r("batch", "direct_rows64", "direct_rows64", N48, 2, 32768),
-    ("mfma", 65836): _r("batch", "direct_rows64", "direct_rows64", N48, 2, 33024),
-}
-for _m in ("x3", "f16"):
-    for _B, _k, _rb in ((20480, "rows32", "n16"), (20481, "rows32", "fp32"), (32767, "rows32", "fp32"),
-                        (32768, "rows64", "fp32"), (32897, "rows64", "fp32")):
-        _f = f"{_m}_{_k}"
-        REGIMES[(_m, _B)] = _r(_f, _f, _f, f"fc_gb:x3+fc_rb:{_rb}", 1)
 NN_NAME = {"mfma": "mfma_f32", "x3": "mfma_x3", "f16": "mfma_f16"}
-
-
-def rows_per_block(reg):
-    """Rows per block of the family's chained kernels (launch_rnn's `tile`): 128, or 256 for the direct family at 64 rows per wave."""
-    return 256 if reg["gru"] == "direct_rows64" else 128
-
-
-def chain_share(B, chains, tile):
-    """launch_rnn: equal shares rounded up to whole `tile` rows; the last chain takes what is left."""
-    return ((B + chains - 1) // chains + tile - 1) // tile * tile
 
 
 def boundary_rows(B, share=None):
@@ -142,7 +101,7 @@ def pool(oracle):
 
 @pytest.fixture
 def default_families(monkeypatch):
-    for k in FAMILY_ENV:
+    for k in families.FAMILY_ENV:
         monkeypatch.delenv(k, raising=False)
 
 
@@ -168,6 +127,9 @@ def _check_describe(ctx, mode, B, reg):
     want = {k: reg[k] for k in got}
     assert d["nn"] == NN_NAME[mode] and d["frontend"] == "split", d
     assert got == want, f"{mode} at B={B} now lands in {got}, the regime map says {want}: move the sizes with the threshold"
+    plan = families.debug_plan(api.load_library(), B, MODES[mode])        # the host-only plan is what the context runs
+    assert {k: d[k] for k in ("nn", "dense", "gru", "gru_rb", "narrow", "frontend")} == {k: plan[k] for k in ("nn", "dense", "gru", "gru_rb", "narrow", "frontend")}, (d, plan)
+    assert d["nn_chains"].split(":")[0] == plan["nn_chains"], (d, plan)
 
 
 def _where(B, r, share):

@@ -10,11 +10,10 @@ import numpy as np
 import pytest
 
 from percepnet_amd import api, synth, weights
+from tests import families
 
 pytestmark = pytest.mark.gpu
 MODES = {"strict": api.NN_STRICT, "mfma": api.NN_MFMA, "x3": api.NN_MFMA_X3, "f16": api.NN_MFMA_F16}
-FAMILY_ENV = ("PERCEPNET_SMALL_ROWS", "PERCEPNET_SMALL_GRU_ROWS", "PERCEPNET_NN_DIRECT", "PERCEPNET_NN_DIRECT_RG",
-              "PERCEPNET_X3_RG", "PERCEPNET_N16_ROWS", "PERCEPNET_N48", "PN_NN_CHAINS", "PERCEPNET_FE", "PERCEPNET_FE_G2")
 
 
 @pytest.fixture(scope="module")
@@ -26,7 +25,7 @@ def model(blob):
 
 @pytest.fixture
 def default_families(monkeypatch):
-    for k in FAMILY_ENV:
+    for k in families.FAMILY_ENV:
         monkeypatch.delenv(k, raising=False)
 
 
