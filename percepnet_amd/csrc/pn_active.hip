@@ -2,14 +2,13 @@
 //
 // In the reference a stream's state moves only when ITS rnnoise_process_frame is called (denoise.cpp:508-547,
 // rnnoise.h:60); a batched context moves all B streams in lock-step and indexes every ring by its own global counter
-// (history slot t % 12, look-ahead rings t % 6, conv FIFOs tn % 5 / tn % 3, GRU halves tn & 1).  A stream whose packet is
-// late must keep ALL of its state and produce no output for that tick.
+// (pn_state_layout.h lists the buffers, their geometry and their class).  A stream whose packet is late must keep ALL of its
+// state and produce no output for that tick.
 //
 // How, without touching a hot kernel: every per-tick write of the frame kernels lands either
-//   (a) in the ring slot that holds the OLDEST, already dead entry (history frame t-12, look-ahead spectrum t-6, fc
-//       output t-5, conv1 output t-3), or in the ping-pong half the next step does not read,
-//   (b) in scratch that the next frame recomputes before reading (features, silence, Ps, c2out, g|r), or
-//   (c) in place: the synthesis overlap memory, last_period, last_gain — and the caller's output rows.
+//   (a) RING: in the ring slot that holds the OLDEST, already dead entry, or in the ping-pong half the next step does not read,
+//   (b) SCRATCH: in what the next frame recomputes before reading, or
+//   (c) INPLACE: in the state itself — and in the caller's output rows.
 // So the frame runs for all rows as always (a skipped row computes on whatever its input row holds; nothing of it
 // survives), bracketed by two small launches over the INACTIVE rows only:
 //   before  save (c) — 4.1 KB per skipped stream;
@@ -76,27 +75,16 @@ __global__ __launch_bounds__(256) void pn_inactive_fixup_kernel(PnActiveArgs a) 
     if (tid == 0) { a.last_period[s] = a.save_period[i]; a.last_gain[s] = a.save_gain[i]; }
   }
   if (a.restore_only) return;
-  // (a) rings: t / tn are the counters of the tick that has just run
-  const int t12 = (int)(a.t % 12), t6 = (int)(a.t % 6), n5 = (int)(a.tn % 5), n3 = (int)(a.tn % 3), n2 = (int)(a.tn & 1);
-  {   // history: frames t-1 .. t-11 (slots t-1 .. t-11 mod 12) one slot up; slots sit back to back inside the row
-    float4 *h = reinterpret_cast<float4 *>(a.hist + (size_t)s * PN_HIST_STRIDE);
-    pn_shift_ring(h, PN_FRAME / 4, PN_FRAME / 4, 12, (t12 + 11) % 12, 11, tid, 256);
-    // the mirror of the ring's first 8 samples (unaligned comb-tap loads): columns 0 and 1 of slot 0, moved by threads 0 and 1
-    if (tid < 2) h[PN_HIST / 4 + tid] = h[tid];
-  }
-  pn_shift_ring(reinterpret_cast<float4 *>(a.yring + (size_t)s * PN_SPEC_BINS), (long long)a.B * PN_SPEC_BINS / 2, PN_SPEC_BINS / 2, 6, (t6 + 5) % 6, 5, tid, 256);
-  pn_shift_ring(reinterpret_cast<float4 *>(a.eyring + (size_t)s * 36), (long long)a.B * 9, 9, 6, (t6 + 5) % 6, 5, tid, 256);
-  pn_shift_ring(reinterpret_cast<float4 *>(a.c1ring + (size_t)s * 128), a.Bp * 32, 32, 5, (n5 + 4) % 5, 4, tid, 256);
-  pn_shift_ring(reinterpret_cast<float4 *>(a.c2ring + (size_t)s * 512), a.Bp * 128, 128, 3, (n3 + 2) % 3, 2, tid, 256);
-  // ping-pong pairs: the live state is in half tn & 1 (the half this tick read); the next tick reads the other one
-  for (int g = 0; g < 4; g++) pn_shift_ring(reinterpret_cast<float4 *>(a.gru[g] + (size_t)s * 512), a.Bp * 128, 128, 2, n2, 1, tid, 256);
-  pn_shift_ring(reinterpret_cast<float4 *>(a.rb + (size_t)s * 128), a.Bp * 32, 32, 2, n2, 1, tid, 256);
-  // operand shadows of the fp16-operand / split-precision modes
-  if (a.np) {
-    pn_shift_shadow(a.c1ringH, a.np * a.Bp * 128 / 8, 4, a.np, s, 5, (n5 + 4) % 5, 4, tid, 256);
-    pn_shift_shadow(a.c2ringH, a.np * a.Bp * 512 / 8, 16, a.np, s, 3, (n3 + 2) % 3, 2, tid, 256);
-    for (int g = 0; g < 4; g++) pn_shift_shadow(a.gruH[g], a.np * a.Bp * 512 / 8, 16, a.np, s, 2, n2, 1, tid, 256);
-    pn_shift_shadow(a.rbH, a.np * a.Bp * 128 / 8, 4, a.np, s, 2, n2, 1, tid, 256);
+  // (a) every ring section's live entries first .. first + live - 1 (at the counters of the tick that has just run) one slot up
+  for (int k = 0; k < PN_SS_NSEC; k++) {
+    const PnSsSection S = a.sec[k];
+    if (S.slots < 2) continue;
+    const int newest = S.first + S.live - 1 < S.slots ? S.first + S.live - 1 : S.first + S.live - 1 - S.slots;
+    float4 *row = reinterpret_cast<float4 *>(S.base + (size_t)s * S.row_stride);
+    pn_shift_ring(row, S.slot_stride / 4, S.cols / 4, S.slots, newest, S.live, tid, 256);
+    // history: the mirror of the ring's first 8 samples (unaligned comb-tap loads): columns 0 and 1 of slot 0, moved by threads 0 and 1
+    if (k == 0 && tid < 2) row[PN_HIST / 4 + tid] = row[tid];
+    pn_shift_shadow(S.shadow, S.slot_stride * S.np / 8, S.cols / 32, S.np, s, S.slots, newest, S.live, tid, 256);
   }
 }
 

@@ -58,33 +58,31 @@ struct pn_ctx {
   hipStream_t chain_stream[4] = {nullptr, nullptr, nullptr, nullptr};      // launch_rnn: streams of the row-range chains 1..3 (chain 0 = stream), created with the context
   hipEvent_t chain_fork = nullptr, chain_join[4] = {nullptr, nullptr, nullptr, nullptr};
   char chain_kind[5] = {'-', '-', '-', '-', 0};   // how each chain stream was obtained (n: default priority, probed; h: priority stream)
-  int64_t t;                       // frames done: indexes the DSP rings (hist slot t%12, yring/eyring t%6)
-  int64_t tn;                      // network steps done: indexes the conv rings (tn%5, tn%3) and the GRU ping-pong (tn&1).
+  int64_t t;                       // frames done: the counter of the DSP rings (pn_state_layout.h)
+  int64_t tn;                      // network steps done: the counter of the conv FIFOs and the GRU pairs.
                                    // == t unless pn_ctx_compute_rnn_host advanced the network on its own (rnn.cpp:42 is
                                    // callable on an RNNState without a DenoiseState in the reference too)
   size_t bytes;
   PnLayerHost geom[PN_NLAYERS];
   DevLayer L[PN_NLAYERS];           // = weights->L (pointers into the shared copy)
   SharedWeights *weights = NULL; WeightsKey weights_key; bool weights_were_cached = false;
-  // pn_ctx_reset_streams: stream ids on the device, and a ring of pinned host copies (the H2D copy runs when the stream gets
-  // to it — frames may be in flight — so its source must outlive the call; slot k is reused once its copy has executed)
-  int *d_ids = NULL; int ids_cap = 0;
-  struct IdSlot { int *h = NULL; hipEvent_t ev = nullptr; } id_slot[4];
-  unsigned id_calls = 0;
-  // pn_process_*_active: inactive-row list on the device (+ its ring of pinned host copies) and the save area of the
+  // a list of stream ids on the device, and a ring of pinned host copies (the H2D copy runs when the stream gets to it —
+  // frames may be in flight — so its source must outlive the call; slot k is reused once its copy has executed)
+  struct IdRing { int *d = NULL; int cap = 0; unsigned calls = 0; struct { int *h = NULL; hipEvent_t ev = nullptr; } slot[4]; };
+  IdRing ids;                      // pn_ctx_reset_streams, pn_ctx_set_atten_limit, stream-state export / import
+  // pn_process_*_active: the inactive rows (a ring of its own: a reset's list may still be in flight) and the save area of the
   // in-place state of those rows, grown on demand
   struct Active {
-    int *d_ids = NULL; int cap = 0;
-    pn_ctx::IdSlot slot[4]; unsigned calls = 0;
+    IdRing ids;
     float *save_synth = NULL, *save_gr = NULL, *save_gain = NULL; uint32_t *save_out = NULL; int *save_period = NULL;
     std::vector<uint8_t> mark; std::vector<int32_t> inactive;
   } act;
   PnTables *tables; float *tansig;
-  float *hist, *synth, *last_gain, *feat, *c1ring, *c2ring, *c2out, *gru[4], *rb, *gr, *io_in, *io_out;
-  // fp16-operand variant only: shadow copies (2 bytes per element, same indexing) of the buffers the GEMMs read
-  uint16_t *c1ringH, *c2ringH, *c2outH, *gruH[4], *rbH;
-  float2 *yring, *Ps;              // yring: [6][B][400] look-ahead spectra (X of frame t = slot (t+1)%6)
-  float *eyring;                   // [6][B][36] look-ahead band energies
+  // the per-stream state: pn_kState (pn_state_layout.h) resolved for this context's size, mode and plan.  sh: the operand shadow
+  // (same element index, shadow_halfs_per_element halfs per element), NULL where the mode / family keeps none
+  struct StateBuf { float *p; uint16_t *sh; size_t words; long long slot_stride; } st[PN_ST_COUNT] = {};
+  float *hist, *eyring, *synth, *last_gain, *feat, *gr, *io_in, *io_out;      // aliases of st[].p that the frame path reads
+  float2 *yring, *Ps;
   bool postfilter = false;         // optional envelope post-filter in the back end (pn_ctx_set_postfilter)
   // per-stream attenuation limit (pn_ctx_set_atten_limit): (lam, mu) per stream on the device, allocated by the first set; the
   // host mirror of the dB values (the getter) and the count of streams with lam != 0 (the launch decision: while it is 0 the
@@ -95,7 +93,7 @@ struct pn_ctx {
   bool x3_sat = false;             // PERCEPNET_X3_SATCOUNT=1 (shadow-operand modes): count operand values clamped to the fp16 range
   int dsp_grid_cap = 0;            // > 0 only in the DSP self-test's temporary context: its DSP launches use that many blocks
   bool inject_bad_launch = false;  // pn_ctx_debug_inject_launch_failure (tests): the next frames hand fc a geometry its launcher refuses
-  int *last_period, *silence;
+  int *last_period, *silence;      // (aliases too)
   std::vector<void *> allocs;
   bool profiling;
   struct Ev { int fam; hipEvent_t a, b; };
@@ -155,35 +153,32 @@ static int upload_w(pn_ctx *c, SharedWeights *w, float **dst, const float *src, 
 // (the fp32 shadows of the direct-operand family are 4 bytes per element, laid out in the same 16-byte slab entries)
 static size_t shadow_halfs_per_element(const pn_ctx *c) { return (c->nn_mode == PN_NN_MFMA_X3 || c->plan.direct) ? 2 : 1; }
 static bool x3_layer(int li) { return li == PN_L_CONV1 || li == PN_L_CONV2 || li == PN_L_GRU_RB || li == PN_L_FC_GB || (li >= PN_L_GRU1 && li < PN_L_GRU1 + 4); }
+// "fresh context", pn_ctx_reset and "every stream reset" are one statement: every word of every entry and shadow is zero
 static int zero_state(pn_ctx *c) {
-  const size_t B = c->B;
-  PN_HIP_CHECK(hipMemsetAsync(c->hist, 0, B * PN_HIST_STRIDE * 4, c->stream));
-  PN_HIP_CHECK(hipMemsetAsync(c->synth, 0, B * PN_FRAME * 4, c->stream));
-  PN_HIP_CHECK(hipMemsetAsync(c->yring, 0, 6 * B * PN_SPEC_BINS * sizeof(float2), c->stream));
-  PN_HIP_CHECK(hipMemsetAsync(c->eyring, 0, 6 * B * 36 * 4, c->stream));
-  PN_HIP_CHECK(hipMemsetAsync(c->last_gain, 0, B * 4, c->stream));
-  PN_HIP_CHECK(hipMemsetAsync(c->last_period, 0, B * 4, c->stream));
-  PN_HIP_CHECK(hipMemsetAsync(c->silence, 0, B * 4, c->stream));
-  const size_t Bp = c->Bp;
-  PN_HIP_CHECK(hipMemsetAsync(c->feat, 0, Bp * PN_FEAT_STRIDE * 4, c->stream));
-  PN_HIP_CHECK(hipMemsetAsync(c->c1ring, 0, 5 * Bp * 128 * 4, c->stream));
-  PN_HIP_CHECK(hipMemsetAsync(c->c2ring, 0, 3 * Bp * 512 * 4, c->stream));
-  PN_HIP_CHECK(hipMemsetAsync(c->c2out, 0, Bp * 512 * 4, c->stream));
-  for (int i = 0; i < 4; i++) PN_HIP_CHECK(hipMemsetAsync(c->gru[i], 0, 2 * Bp * 512 * 4, c->stream));
-  PN_HIP_CHECK(hipMemsetAsync(c->rb, 0, 2 * Bp * 128 * 4, c->stream));
-  PN_HIP_CHECK(hipMemsetAsync(c->gr, 0, B * 68 * 4, c->stream));
-  if (c->lam_mu) PN_HIP_CHECK(hipMemsetAsync(c->lam_mu, 0, B * sizeof(float2), c->stream));   // every stream back to off
-  c->atten_db.assign(B, INFINITY); c->n_limited = 0;
-  if (c->c2outH) {
-    const size_t hb = 2 * shadow_halfs_per_element(c);   // shadow bytes per element
-    if (c->c1ringH) PN_HIP_CHECK(hipMemsetAsync(c->c1ringH, 0, 5 * Bp * 128 * hb, c->stream));
-    if (c->c2ringH) PN_HIP_CHECK(hipMemsetAsync(c->c2ringH, 0, 3 * Bp * 512 * hb, c->stream));
-    PN_HIP_CHECK(hipMemsetAsync(c->c2outH, 0, Bp * 512 * hb, c->stream));
-    for (int i = 0; i < 4; i++) PN_HIP_CHECK(hipMemsetAsync(c->gruH[i], 0, 2 * Bp * 512 * hb, c->stream));
-    PN_HIP_CHECK(hipMemsetAsync(c->rbH, 0, 2 * Bp * 128 * hb, c->stream));
+  for (const pn_ctx::StateBuf &b : c->st) {
+    PN_HIP_CHECK(hipMemsetAsync(b.p, 0, b.words * 4, c->stream));
+    if (b.sh) PN_HIP_CHECK(hipMemsetAsync(b.sh, 0, b.words * 2 * shadow_halfs_per_element(c), c->stream));
   }
+  if (c->lam_mu) PN_HIP_CHECK(hipMemsetAsync(c->lam_mu, 0, (size_t)c->B * sizeof(float2), c->stream));   // every stream back to off
+  c->atten_db.assign(c->B, INFINITY); c->n_limited = 0;
   c->t = 0; c->tn = 0;
   return 0;
+}
+// entry e of the state: its j-th live entry, oldest first, before the step with the context's counters runs (j == live: the slot
+// that step writes), from row r0 on
+static float *state_at(const pn_ctx *c, int e, int j, size_t r0 = 0) {
+  const PnStateEntry &L = pn_kState[e];
+  const int slot = j < L.live ? (pn_state_first(L, c->t, c->tn) + j) % L.slots : pn_state_write(L, c->t, c->tn);
+  return c->st[e].p + slot * c->st[e].slot_stride + r0 * L.row_words;
+}
+// The record sections (= the rings the active-set fix-up shifts, and synth) at the context's CURRENT counters, those of the next
+// frame to run: DSP rings follow t, the network's follow tn (they differ after pn_ctx_compute_rnn_host)
+static void state_sections(const pn_ctx *c, PnSsSection sec[PN_SS_NSEC]) {
+  for (int e = 0; e < PN_ST_COUNT; e++) {
+    const PnStateEntry &L = pn_kState[e]; const pn_ctx::StateBuf &b = c->st[e];
+    if (L.rec_off >= 0) sec[pn_state_section(e)] = PnSsSection{b.p, (uint4 *)b.sh, L.row_words, b.slot_stride, L.slots, pn_state_first(L, c->t, c->tn), L.live, L.cols, L.rec_off,
+                         b.sh ? (int)shadow_halfs_per_element(c) : 0};
+  }
 }
 
 static int nn_selftest(pn_ctx *c);
@@ -205,8 +200,8 @@ extern "C" void pn_ctx_destroy(pn_ctx *c) {
   for (auto &e : c->events) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
   for (hipEvent_t e : c->event_pool) hipEventDestroy(e);
   for (void *p : c->allocs) hipFree(p);
-  for (auto &sl : c->id_slot) { if (sl.h) hipHostFree(sl.h); if (sl.ev) hipEventDestroy(sl.ev); }
-  for (auto &sl : c->act.slot) { if (sl.h) hipHostFree(sl.h); if (sl.ev) hipEventDestroy(sl.ev); }
+  for (pn_ctx::IdRing *r : {&c->ids, &c->act.ids})
+    for (auto &sl : r->slot) { if (sl.h) hipHostFree(sl.h); if (sl.ev) hipEventDestroy(sl.ev); }
   if (c->weights) {
     std::lock_guard<std::mutex> lk(g_weights_mu);
     if (--c->weights->refs == 0) {
@@ -301,7 +296,6 @@ static pn_ctx *ctx_create(const pn_model *model, int device, int n_streams, int 
   c->t = 0; c->tn = 0; c->bytes = 0; c->profiling = false;
   memset(c->fam_ms, 0, sizeof(c->fam_ms)); memset(c->fam_n, 0, sizeof(c->fam_n));
   memset(c->L, 0, sizeof(c->L));
-  c->c1ringH = c->c2ringH = c->c2outH = c->rbH = NULL; memset(c->gruH, 0, sizeof(c->gruH));
 
   if (hip_stream) { c->stream = (hipStream_t)hip_stream; c->own_stream = false; }
   else {
@@ -319,31 +313,20 @@ static pn_ctx *ctx_create(const pn_model *model, int device, int n_streams, int 
     delete ht;
     if (rc) goto fail;
   }
-  DEV_ALLOC(c->hist, B * PN_HIST_STRIDE, false);
-  DEV_ALLOC(c->synth, B * PN_FRAME, false);
-  DEV_ALLOC(c->last_gain, B, false);
-  DEV_ALLOC(c->last_period, B, false);
-  DEV_ALLOC(c->silence, B, false);
-  DEV_ALLOC(c->yring, 6 * B * PN_SPEC_BINS, false);
-  DEV_ALLOC(c->eyring, 6 * B * 36, false);
-  DEV_ALLOC(c->Ps, B * PN_SPEC_BINS, true);
-  DEV_ALLOC(c->feat, Bp * PN_FEAT_STRIDE, false);
-  DEV_ALLOC(c->c1ring, 5 * Bp * 128, false);
-  DEV_ALLOC(c->c2ring, 3 * Bp * 512, false);
-  DEV_ALLOC(c->c2out, Bp * 512, false);
-  for (int i = 0; i < 4; i++) DEV_ALLOC(c->gru[i], 2 * Bp * 512, false);
-  DEV_ALLOC(c->rb, 2 * Bp * 128, false);
-  DEV_ALLOC(c->gr, B * 68, false);
-  if (nn_mode == PN_NN_MFMA_F16 || nn_mode == PN_NN_MFMA_X3 || c->plan.direct) {
-    const size_t hp = shadow_halfs_per_element(c);      // 1: fp16 shadow; 2: hi + lo planes (split precision) / fp32 fragments (direct-operand GRUs)
-    if (!c->plan.direct) {                              // (the direct-operand family keeps its dense layers on the batch kernels: no shadows of the conv FIFOs)
-      DEV_ALLOC(c->c1ringH, hp * 5 * Bp * 128, false);
-      DEV_ALLOC(c->c2ringH, hp * 3 * Bp * 512, false);
-    }
-    DEV_ALLOC(c->c2outH, hp * Bp * 512, false);
-    for (int i = 0; i < 4; i++) DEV_ALLOC(c->gruH[i], hp * 2 * Bp * 512, false);
-    DEV_ALLOC(c->rbH, hp * 2 * Bp * 128, false);
+  for (int e = 0; e < PN_ST_COUNT; e++) {
+    const PnStateEntry &L = pn_kState[e]; pn_ctx::StateBuf &b = c->st[e];
+    const size_t rows = L.padded ? Bp : B;
+    b.slot_stride = L.in_row ? L.cols : (long long)(rows * L.row_words);
+    b.words = (L.in_row ? 1 : L.slots) * rows * L.row_words;
+    DEV_ALLOC(b.p, b.words, false);
   }
+  // operand shadows: of the shadow-operand modes (1 half per element: fp16 operands; hi + lo planes: split precision), and of the
+  // direct-operand family (fp32 fragments), which keeps its dense layers on the batch kernels: no shadows of the conv FIFOs
+  for (int e = 0; e < PN_ST_COUNT; e++)
+    if (pn_kState[e].shadow != PN_SH_NONE && (nn_mode == PN_NN_MFMA_F16 || nn_mode == PN_NN_MFMA_X3 || (c->plan.direct && pn_kState[e].shadow == PN_SH_MODES_DIRECT)))
+      DEV_ALLOC(c->st[e].sh, shadow_halfs_per_element(c) * c->st[e].words, false);
+  c->hist = c->st[PN_ST_HIST].p; c->synth = c->st[PN_ST_SYNTH].p; c->last_gain = c->st[PN_ST_LAST_GAIN].p; c->feat = c->st[PN_ST_FEAT].p; c->gr = c->st[PN_ST_GR].p;
+  c->eyring = c->st[PN_ST_EYRING].p; c->yring = (float2 *)c->st[PN_ST_YRING].p; c->Ps = (float2 *)c->st[PN_ST_PS].p; c->last_period = (int *)c->st[PN_ST_LAST_PERIOD].p; c->silence = (int *)c->st[PN_ST_SILENCE].p;
   DEV_ALLOC(c->io_in, B * PN_FRAME, false);
   DEV_ALLOC(c->io_out, B * PN_FRAME, false);
   if (zero_state(c)) goto fail;
@@ -387,39 +370,42 @@ fail:
 
 static int pipe_drain(pn_ctx *c);
 extern "C" int pn_ctx_reset(pn_ctx *c) { if (!c) return -1; PN_ON_DEVICE(c); if (pipe_drain(c)) return -1; return zero_state(c); }
-// rnnoise_init for a subset of the streams (denoise.cpp:259-280): every row of stream s in every ring slot / ping-pong half
-// of every state buffer goes to zero (pn_state.hip says why that is a fresh stream whatever the ring phases are)
-// ids[0..n) (host) -> c->d_ids through the pinned slot ring, asynchronously on the context's stream (frames may be in flight);
-// the launches that read c->d_ids follow on the same stream.  NULL on failure.  (The caller is on the context's device.)
-// payload (optional): payload_words more 32-bit words staged in the same copy, at d_ids + stage_payload_offset(n)
+// The pinned id ring, for both of its users.  (The caller is on the context's device.)
 static int stage_payload_offset(int n) { return (n + 3) & ~3; }      // 16-byte aligned
-static const int *stage_ids(pn_ctx *c, const int32_t *ids, int n, const void *payload = NULL, int payload_words = 0) {
-  const int words = payload_words ? stage_payload_offset(n) + payload_words : n;
-#define SI_CHECK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { pn_set_error("%s failed: %s", #expr, hipGetErrorString(_e)); return NULL; } } while (0)
-  if (c->ids_cap < words) {
-    // (the old, smaller buffers stay in allocs until destroy: kernels of an earlier call may still be reading them)
-    const int cap = words < 1024 ? 1024 : words;
-    int *p = NULL;
-    SI_CHECK(hipMalloc((void **)&p, (size_t)cap * sizeof(int)));
-    c->allocs.push_back(p); c->d_ids = p;
-    for (auto &sl : c->id_slot) {
-      if (sl.ev) SI_CHECK(hipEventSynchronize(sl.ev));
-      if (sl.h) hipHostFree(sl.h);
-      sl.h = NULL;
-      SI_CHECK(hipHostMalloc((void **)&sl.h, (size_t)cap * sizeof(int), hipHostMallocDefault));
-      if (!sl.ev) SI_CHECK(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
-    }
-    c->ids_cap = cap;
+// room for `cap` ints in ring r (the old, smaller buffers stay in allocs until destroy: kernels of an earlier call may still be reading them)
+static int id_ring_reserve(pn_ctx *c, pn_ctx::IdRing &r, int cap) {
+  if (r.cap >= cap) return 0;
+  if (dev_alloc(c, (void **)&r.d, (size_t)cap * sizeof(int), false)) return -1;
+  for (auto &sl : r.slot) {
+    if (sl.ev) PN_HIP_CHECK(hipEventSynchronize(sl.ev));
+    if (sl.h) hipHostFree(sl.h);
+    sl.h = NULL;
+    PN_HIP_CHECK(hipHostMalloc((void **)&sl.h, (size_t)cap * sizeof(int), hipHostMallocDefault));
+    if (!sl.ev) PN_HIP_CHECK(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
   }
-  pn_ctx::IdSlot &sl = c->id_slot[c->id_calls++ & 3];
-  SI_CHECK(hipEventSynchronize(sl.ev));                 // the copy issued from this slot four calls ago has executed
+  r.cap = cap;
+  return 0;
+}
+// ids[0..n) (+ the payload) -> r.d through the next pinned slot, asynchronously on the context's stream; r holds `words` ints
+static int id_ring_stage(pn_ctx *c, pn_ctx::IdRing &r, const int32_t *ids, int n, const void *payload, int payload_words, int words) {
+  auto &sl = r.slot[r.calls++ & 3];
+  PN_HIP_CHECK(hipEventSynchronize(sl.ev));                 // the copy issued from this slot four calls ago has executed
   memcpy(sl.h, ids, (size_t)n * sizeof(int));
   if (payload_words) memcpy(sl.h + stage_payload_offset(n), payload, (size_t)payload_words * 4);
-  SI_CHECK(hipMemcpyAsync(c->d_ids, sl.h, (size_t)words * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  SI_CHECK(hipEventRecord(sl.ev, c->stream));
-  return c->d_ids;
-#undef SI_CHECK
+  PN_HIP_CHECK(hipMemcpyAsync(r.d, sl.h, (size_t)words * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  PN_HIP_CHECK(hipEventRecord(sl.ev, c->stream));
+  return 0;
 }
+// ids[0..n) (host) -> c->ids.d, asynchronously on the context's stream (frames may be in flight); the launches that read it follow
+// on the same stream.  NULL on failure.  payload (optional): payload_words more 32-bit words staged in the same copy, at
+// c->ids.d + stage_payload_offset(n)
+static const int *stage_ids(pn_ctx *c, const int32_t *ids, int n, const void *payload = NULL, int payload_words = 0) {
+  const int words = payload_words ? stage_payload_offset(n) + payload_words : n;
+  if (id_ring_reserve(c, c->ids, words < 1024 ? 1024 : words) || id_ring_stage(c, c->ids, ids, n, payload, payload_words, words)) return NULL;
+  return c->ids.d;
+}
+// rnnoise_init for a subset of the streams (denoise.cpp:259-280): every row of stream s in every ring slot / ping-pong half
+// of every state buffer goes to zero (pn_state.hip says why that is a fresh stream whatever the ring phases are)
 extern "C" int pn_ctx_reset_streams(pn_ctx *c, const int32_t *ids, int n) {
   if (!c || n < 0 || (n > 0 && !ids)) { pn_set_error("bad argument"); return -1; }
   if (n == 0) return 0;
@@ -427,32 +413,14 @@ extern "C" int pn_ctx_reset_streams(pn_ctx *c, const int32_t *ids, int n) {
   PN_ON_DEVICE(c);
   const int *d = stage_ids(c, ids, n);
   if (!d) return -1;
-  hipStream_t st = c->stream;
-  const long long B = c->B, Bp = (long long)c->Bp;
-  pn_launch_zero_rows(st, c->hist, PN_HIST_STRIDE, PN_HIST_STRIDE, 1, 0, d, n);
-  pn_launch_zero_rows(st, c->synth, PN_FRAME, PN_FRAME, 1, 0, d, n);
-  pn_launch_zero_rows(st, c->yring, 2 * PN_SPEC_BINS, 2 * PN_SPEC_BINS, 6, B * 2 * PN_SPEC_BINS, d, n);
-  pn_launch_zero_rows(st, c->eyring, 36, 36, 6, B * 36, d, n);
-  pn_launch_zero_rows(st, c->Ps, 2 * PN_SPEC_BINS, 2 * PN_SPEC_BINS, 1, 0, d, n);
-  pn_launch_zero_rows(st, c->last_gain, 1, 1, 1, 0, d, n);
-  pn_launch_zero_rows(st, c->last_period, 1, 1, 1, 0, d, n);
-  pn_launch_zero_rows(st, c->silence, 1, 1, 1, 0, d, n);
-  pn_launch_zero_rows(st, c->feat, PN_FEAT_STRIDE, PN_FEAT_STRIDE, 1, 0, d, n);
-  pn_launch_zero_rows(st, c->c1ring, 128, 128, 5, Bp * 128, d, n);
-  pn_launch_zero_rows(st, c->c2ring, 512, 512, 3, Bp * 512, d, n);
-  pn_launch_zero_rows(st, c->c2out, 512, 512, 1, 0, d, n);
-  for (int i = 0; i < 4; i++) pn_launch_zero_rows(st, c->gru[i], 512, 512, 2, Bp * 512, d, n);
-  pn_launch_zero_rows(st, c->rb, 128, 128, 2, Bp * 128, d, n);
-  pn_launch_zero_rows(st, c->gr, 68, 68, 1, 0, d, n);
-  if (c->lam_mu) pn_launch_zero_rows(st, c->lam_mu, 2, 2, 1, 0, d, n);   // a reset slot is a new call: attenuation limit off
-  if (c->c2outH) {                                         // operand shadows (fp16-operand / split-precision modes, direct-operand GRUs); a NULL one is skipped
-    const int np = (int)shadow_halfs_per_element(c);
-    pn_launch_zero_shadow_rows(st, c->c1ringH, 128, np, 5, np * Bp * 128, d, n);
-    pn_launch_zero_shadow_rows(st, c->c2ringH, 512, np, 3, np * Bp * 512, d, n);
-    pn_launch_zero_shadow_rows(st, c->c2outH, 512, np, 1, 0, d, n);
-    for (int i = 0; i < 4; i++) pn_launch_zero_shadow_rows(st, c->gruH[i], 512, np, 2, np * Bp * 512, d, n);
-    pn_launch_zero_shadow_rows(st, c->rbH, 128, np, 2, np * Bp * 128, d, n);
+  const int np = (int)shadow_halfs_per_element(c);
+  for (int e = 0; e < PN_ST_COUNT; e++) {                    // the rows in every slot of every entry, and of its shadow (a NULL one is skipped)
+    const PnStateEntry &L = pn_kState[e]; const pn_ctx::StateBuf &b = c->st[e];
+    const int outer = L.in_row ? 1 : L.slots;
+    pn_launch_zero_rows(c->stream, b.p, L.row_words, L.row_words, outer, b.slot_stride, d, n);
+    pn_launch_zero_shadow_rows(c->stream, b.sh, L.cols, np, outer, np * b.slot_stride, d, n);
   }
+  if (c->lam_mu) pn_launch_zero_rows(c->stream, c->lam_mu, 2, 2, 1, 0, d, n);   // a reset slot is a new call: attenuation limit off
   PN_HIP_CHECK(hipGetLastError());
   for (int i = 0; i < n; i++) {                            // (duplicates allowed: the second sees the stream already off)
     if (pn_atten_limit_factor(c->atten_db[ids[i]]) != 0.f) c->n_limited--;
@@ -546,12 +514,7 @@ static PnSegs seg1(const float *p, int ld, int width) { PnSegs s; memset(&s, 0, 
 // compute_rnn (rnn.cpp:42-81) for all streams; features in c->feat, result in c->gr
 // fp16 shadow of an fp32 activation pointer (same element index in the twin buffer)
 static uint16_t *shadow(pn_ctx *c, const float *p) {
-  const size_t Bp = c->Bp;
-  struct { const float *f; uint16_t *h; size_t n; } m[8] = {
-      {c->c1ring, c->c1ringH, 5 * Bp * 128}, {c->c2ring, c->c2ringH, 3 * Bp * 512}, {c->c2out, c->c2outH, Bp * 512},
-      {c->gru[0], c->gruH[0], 2 * Bp * 512}, {c->gru[1], c->gruH[1], 2 * Bp * 512}, {c->gru[2], c->gruH[2], 2 * Bp * 512},
-      {c->gru[3], c->gruH[3], 2 * Bp * 512}, {c->rb, c->rbH, 2 * Bp * 128}};
-  for (auto &e : m) if (p >= e.f && p < e.f + e.n) return e.h ? e.h + shadow_halfs_per_element(c) * (size_t)(p - e.f) : NULL;
+  for (const pn_ctx::StateBuf &b : c->st) if (b.sh && p >= b.p && p < b.p + b.words) return b.sh + shadow_halfs_per_element(c) * (size_t)(p - b.p);
   return NULL;
 }
 static PnSegs shadow_segs(pn_ctx *c, const PnSegs &A) {
@@ -566,7 +529,7 @@ static PnSegs shadow_segs(pn_ctx *c, const PnSegs &A) {
 // is the same launch with every base pointer moved down by r0 rows.  The kernel families are c->plan's.  The shadow-operand
 // and STRICT modes always run the whole batch.
 static int launch_rnn_rows(pn_ctx *c, size_t r0, size_t nrows, hipStream_t st) {
-  const size_t Bp = c->Bp; const int strict = c->nn_mode == PN_NN_STRICT; const int64_t t = c->tn;
+  const size_t Bp = c->Bp; const int strict = c->nn_mode == PN_NN_STRICT;
   const int B = (int)nrows;
   // x3: the layers that run on the fp16 matrix cores from operand shadows — split precision (hi + lo planes) or fp16 operands (hi only)
   const bool x3 = c->nn_mode == PN_NN_MFMA_X3 || c->nn_mode == PN_NN_MFMA_F16;
@@ -576,13 +539,12 @@ static int launch_rnn_rows(pn_ctx *c, size_t r0, size_t nrows, hipStream_t st) {
                                          // (batch kernel, second output) and by the GRU steps themselves; every dense layer stays on the batch kernels
   const float *tab = c->tansig;
   int rc = 0;
-  const int cur = (int)(t & 1), nxt = cur ^ 1;
   // every chain's launches are bracketed on the stream they go to (pn_ctx_kernel_times averages over all launches of a family;
   // with N chains the launches of one family overlap in time: bench.py prices the CONCURRENT launches together)
   struct MaybeScope { Scope s; MaybeScope(pn_ctx *c_, int fam, hipStream_t st_) : s(c_, fam, st_) {} };
-  float *c1new = c->c1ring + (size_t)(t % 5) * Bp * 128 + r0 * 128;
-  float *c2new = c->c2ring + (size_t)(t % 3) * Bp * 512 + r0 * 512;
-  float *c2out = c->c2out + r0 * 512, *gr = c->gr + r0 * 68;
+  // conv FIFOs: panels 0 .. ks - 2 are the live entries, oldest first, panel ks - 1 the slot this step writes; GRU pairs: 0 read, 1 written
+  float *c1new = state_at(c, PN_ST_C1RING, 4, r0), *c2new = state_at(c, PN_ST_C2RING, 2, r0);
+  float *c2out = state_at(c, PN_ST_C2OUT, 0, r0), *gr = c->gr + r0 * 68;
   { MaybeScope sc(c, KF_FC, st);
     PnSegs A = seg1(c->feat + r0 * PN_FEAT_STRIDE, PN_FEAT_STRIDE, strict ? PN_NFEAT : PN_FEAT_STRIDE);   // cols 70..127 are zero
     if (c->inject_bad_launch && !strict) A.width[0] = 96;   // test hook: three K-tiles, which every MFMA dense launcher refuses
@@ -590,29 +552,28 @@ static int launch_rnn_rows(pn_ctx *c, size_t r0, size_t nrows, hipStream_t st) {
     if (x3) rc |= pn_launch_split_x3(st, c1new, 128, 128, shadow(c, c1new), (int)Bp, np); }   // fc runs in fp32 (70 inputs); its output enters the shadow-operand layers
   { MaybeScope sc(c, KF_CONV1, st);   // causal conv as dense over [4 previous fc outputs | current] (nnet.cpp:182-200)
     PnSegs A; memset(&A, 0, sizeof(A)); A.n = 5;
-    for (int j = 0; j < 5; j++) { A.p[j] = c->c1ring + (size_t)((t + 1 + j) % 5) * Bp * 128 + r0 * 128; A.ld[j] = 128; A.width[j] = 128; }
+    for (int j = 0; j < 5; j++) { A.p[j] = state_at(c, PN_ST_C1RING, j, r0); A.ld[j] = 128; A.width[j] = 128; }
     if (x3) rc |= pn_launch_dense_x3(st, shadow_segs(c, A), c->L[PN_L_CONV1].wp, c->L[PN_L_CONV1].bias, 512, c->geom[PN_L_CONV1].act, tab, c2new, 512, shadow(c, c2new), 16, B, rg, np);
     else rc |= pn_launch_dense(st, strict, A, c->L[PN_L_CONV1].w, c->L[PN_L_CONV1].wp, c->L[PN_L_CONV1].bias, 512, c->geom[PN_L_CONV1].act, tab, c2new, 512, B, small); }
   { MaybeScope sc(c, KF_CONV2, st);
     PnSegs A; memset(&A, 0, sizeof(A)); A.n = 3;
-    for (int j = 0; j < 3; j++) { A.p[j] = c->c2ring + (size_t)((t + 1 + j) % 3) * Bp * 512 + r0 * 512; A.ld[j] = 512; A.width[j] = 512; }
-    if (x3) rc |= pn_launch_dense_x3(st, shadow_segs(c, A), c->L[PN_L_CONV2].wp, c->L[PN_L_CONV2].bias, 512, c->geom[PN_L_CONV2].act, tab, c2out, 512, c->c2outH, 16, B, rg, np);
+    for (int j = 0; j < 3; j++) { A.p[j] = state_at(c, PN_ST_C2RING, j, r0); A.ld[j] = 512; A.width[j] = 512; }
+    if (x3) rc |= pn_launch_dense_x3(st, shadow_segs(c, A), c->L[PN_L_CONV2].wp, c->L[PN_L_CONV2].bias, 512, c->geom[PN_L_CONV2].act, tab, c2out, 512, shadow(c, c2out), 16, B, rg, np);
     else if (dm) rc |= pn_launch_dense(st, 0, A, NULL, c->L[PN_L_CONV2].wp, c->L[PN_L_CONV2].bias, 512, c->geom[PN_L_CONV2].act, tab, c2out, 512, B, 0, shadow(c, c2out), 16);   // + the shadow the GRUs read
     else rc |= pn_launch_dense(st, strict, A, c->L[PN_L_CONV2].w, c->L[PN_L_CONV2].wp, c->L[PN_L_CONV2].bias, 512, c->geom[PN_L_CONV2].act, tab, c2out, 512, B, small); }
   const float *x = c2out;
   for (int i = 0; i < 4 && !rc; i++) {    // gru1 -> gru2 -> gru3 -> gru_gb, each fed the UPDATED state of its predecessor
     MaybeScope sc(c, KF_GRU512, st);
     const int li = PN_L_GRU1 + i;
-    float *ho = c->gru[i] + (size_t)cur * Bp * 512 + r0 * 512, *hn = c->gru[i] + (size_t)nxt * Bp * 512 + r0 * 512;
+    float *ho = state_at(c, PN_ST_GRU1 + i, 0, r0), *hn = state_at(c, PN_ST_GRU1 + i, 1, r0);
     PnSegs X = seg1(x, 512, 512);
     if (x3) rc |= pn_launch_gru_x3(st, shadow_segs(c, X), ho, shadow(c, ho), c->L[li].wp, c->L[li].rwp, c->L[li].bias, 512, c->geom[li].act, tab, hn, shadow(c, hn), B, rg, np);
     else if (dm) rc |= pn_launch_gru_d(st, shadow_segs(c, X), ho, shadow(c, ho), c->L[li].wp, c->L[li].rwp, c->L[li].bias, 512, c->geom[li].act, tab, hn, shadow(c, hn), B, rg);
     else rc |= pn_launch_gru(st, strict, X, ho, c->L[li].w, c->L[li].rw, c->L[li].wp, c->L[li].rwp, c->L[li].bias, 512, c->geom[li].act, tab, hn, B, small_gru);
     x = hn;
   }
-  const float *g1 = c->gru[0] + (size_t)nxt * Bp * 512 + r0 * 512, *g2 = c->gru[1] + (size_t)nxt * Bp * 512 + r0 * 512,
-              *g3 = c->gru[2] + (size_t)nxt * Bp * 512 + r0 * 512, *gb = c->gru[3] + (size_t)nxt * Bp * 512 + r0 * 512;
-  float *rbo = c->rb + (size_t)cur * Bp * 128 + r0 * 128, *rbn = c->rb + (size_t)nxt * Bp * 128 + r0 * 128;
+  const float *g1 = state_at(c, PN_ST_GRU1, 1, r0), *g2 = state_at(c, PN_ST_GRU2, 1, r0), *g3 = state_at(c, PN_ST_GRU3, 1, r0), *gb = state_at(c, PN_ST_GRU_GB, 1, r0);
+  float *rbo = state_at(c, PN_ST_RB, 0, r0), *rbn = state_at(c, PN_ST_RB, 1, r0);
   { MaybeScope sc(c, KF_GRU_RB, st);   // input = [gru3 | conv2 out] (rnn.cpp:67-69)
     PnSegs X; memset(&X, 0, sizeof(X)); X.n = 2;
     X.p[0] = g3; X.ld[0] = 512; X.width[0] = 512; X.p[1] = c2out; X.ld[1] = 512; X.width[1] = 512;
@@ -887,10 +848,9 @@ static int process_dev(pn_ctx *c, const void *d_in, void *d_out, float *d_gr, in
   }
   if (launch_rnn(c)) return -1;                        // a refused launch fails the frame (pn_last_error says which layer)
   { Scope sc(c, KF_BACKEND);
-    // X(t) == the look-ahead spectrum of frame t-5 (pn_dsp_fe.hip): ring slot (t+1)%6
-    const size_t slot = (size_t)((c->t + 1) % 6);
-    const float2 *Xs = c->yring + slot * c->B * PN_SPEC_BINS;
-    const float *Ex = c->postfilter ? c->eyring + slot * c->B * 36 : nullptr;      // Ex(t) = Ey_lookahead(t-5)
+    // X(t) == the look-ahead spectrum of frame t-5 (pn_dsp_fe.hip): the oldest live entry of the ring
+    const float2 *Xs = (const float2 *)state_at(c, PN_ST_YRING, 0);
+    const float *Ex = c->postfilter ? state_at(c, PN_ST_EYRING, 0) : nullptr;      // Ex(t) = Ey_lookahead(t-5)
     pn_launch_backend(c->stream, c->tables, c->B, Xs, c->Ps, c->gr, Ex, c->silence, c->synth, d_out, is_i16, c->dsp_grid_cap,
                       c->n_limited > 0 ? c->lam_mu : nullptr); }      // no stream limited: the plain back end
   if (d_gr) PN_HIP_CHECK(hipMemcpyAsync(d_gr, c->gr, (size_t)c->B * 68 * 4, hipMemcpyDeviceToDevice, c->stream));
@@ -993,37 +953,19 @@ static int process_active(pn_ctx *c, const void *d_in, void *d_out, float *d_gr,
   for (int s = 0; s < B; s++) if (!A.mark[s]) A.inactive.push_back(s);
   const int ni = (int)A.inactive.size();
   PN_ON_DEVICE(c);
-  if (A.cap < ni) {
-    // (the old, smaller buffers stay in allocs until destroy: kernels of an earlier call may still be using them)
+  if (A.ids.cap < ni) {
     int cap = 1024; while (cap < ni) cap *= 2; if (cap > B) cap = B;
-    if (dev_alloc(c, (void **)&A.d_ids, (size_t)cap * 4, false) || dev_alloc(c, (void **)&A.save_synth, (size_t)cap * PN_FRAME * 4, false) ||
+    if (dev_alloc(c, (void **)&A.save_synth, (size_t)cap * PN_FRAME * 4, false) ||
         dev_alloc(c, (void **)&A.save_out, (size_t)cap * PN_FRAME * 4, false) || dev_alloc(c, (void **)&A.save_gr, (size_t)cap * 68 * 4, false) ||
-        dev_alloc(c, (void **)&A.save_period, (size_t)cap * 4, false) || dev_alloc(c, (void **)&A.save_gain, (size_t)cap * 4, false)) return -1;
-    for (auto &sl : A.slot) {
-      if (sl.ev) PN_HIP_CHECK(hipEventSynchronize(sl.ev));
-      if (sl.h) hipHostFree(sl.h);
-      sl.h = NULL;
-      PN_HIP_CHECK(hipHostMalloc((void **)&sl.h, (size_t)cap * sizeof(int), hipHostMallocDefault));
-      if (!sl.ev) PN_HIP_CHECK(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
-    }
-    A.cap = cap;
+        dev_alloc(c, (void **)&A.save_period, (size_t)cap * 4, false) || dev_alloc(c, (void **)&A.save_gain, (size_t)cap * 4, false) ||
+        id_ring_reserve(c, A.ids, cap)) return -1;
   }
-  {
-    pn_ctx::IdSlot &sl = A.slot[A.calls++ & 3];
-    PN_HIP_CHECK(hipEventSynchronize(sl.ev));             // the copy issued from this slot four calls ago has executed
-    memcpy(sl.h, A.inactive.data(), (size_t)ni * sizeof(int));
-    PN_HIP_CHECK(hipMemcpyAsync(A.d_ids, sl.h, (size_t)ni * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    PN_HIP_CHECK(hipEventRecord(sl.ev, c->stream));
-  }
+  if (id_ring_stage(c, A.ids, A.inactive.data(), ni, NULL, 0, ni)) return -1;
   PnActiveArgs a; memset(&a, 0, sizeof(a));
-  a.ids = A.d_ids; a.synth = c->synth; a.last_period = c->last_period; a.last_gain = c->last_gain;
+  a.ids = A.ids.d; a.synth = c->synth; a.last_period = c->last_period; a.last_gain = c->last_gain;
   a.out = d_out; a.out_row_words = is_i16 ? PN_FRAME / 2 : PN_FRAME; a.d_gr = d_gr;
   a.save_synth = A.save_synth; a.save_out = A.save_out; a.save_gr = A.save_gr; a.save_period = A.save_period; a.save_gain = A.save_gain;
-  a.hist = c->hist; a.yring = c->yring; a.eyring = c->eyring; a.c1ring = c->c1ring; a.c2ring = c->c2ring; a.rb = c->rb;
-  for (int i = 0; i < 4; i++) { a.gru[i] = c->gru[i]; a.gruH[i] = (uint4 *)c->gruH[i]; }
-  a.c1ringH = (uint4 *)c->c1ringH; a.c2ringH = (uint4 *)c->c2ringH; a.rbH = (uint4 *)c->rbH;
-  a.np = c->c2outH ? (int)shadow_halfs_per_element(c) : 0;     // (a NULL shadow is skipped)
-  a.B = B; a.Bp = (long long)c->Bp; a.t = c->t; a.tn = c->tn;
+  state_sections(c, a.sec);                             // at the counters the frame below runs with
   pn_launch_inactive_save(c->stream, a, ni);
   if (process_dev(c, d_in, d_out, d_gr, is_i16)) {
     // a refused launch: the frame did not complete and the counters did not advance, but the front end may already have
@@ -1033,7 +975,7 @@ static int process_active(pn_ctx *c, const void *d_in, void *d_out, float *d_gr,
     pn_launch_inactive_fixup(c->stream, a, ni);
     return -1;
   }
-  pn_launch_inactive_fixup(c->stream, a, ni);           // a.t / a.tn: the counters the frame above ran with
+  pn_launch_inactive_fixup(c->stream, a, ni);
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -1318,52 +1260,46 @@ extern "C" int pn_ctx_compute_rnn_host(pn_ctx *c, const float *h_feat, float *h_
 }
 
 // ---- network state <-> host arrays in the reference's RNNState layout (nnet_data.h:28-38) ---------------------------
-// The conv FIFOs are rings here: the ks-1 previous layer inputs, oldest first, live in slots (tn+1+j) % ks, j = 0..ks-2
-// (launch_rnn reads panels (tn+1+j) % ks for j = 0..ks-1, the last one being the slot the current step writes).
-// The GRU states are ping-pong pairs: buffer tn & 1 holds the state the next step reads.
-static int rnn_state_copy(pn_ctx *c, bool to_device, float *conv1, float *conv2, float *const gru[4], float *rb) {
+// The same walk as a record section: an entry's live slots, oldest first (the ks-1 previous layer inputs of a conv FIFO, the
+// half of a GRU pair that the next step reads), one host row = live * cols floats.  host[i]: the i-th ring of the network
+// (conv1, conv2, gru1..gru_gb, gru_rb, in table order), or NULL.
+enum { PN_ST_NNET = 7 };
+static int rnn_state_copy(pn_ctx *c, bool to_device, float *const host[PN_ST_NNET]) {
   PN_ON_DEVICE(c);
   if (pipe_drain(c)) return -1;
   // fp16-operand and split-precision modes: the fp32 buffers are complete (every layer stores fp32 next to its operand
   // shadow), so a store reads them as in the fp32 modes and a load re-derives the shadows from the loaded fp32 values
   const bool x3 = c->nn_mode == PN_NN_MFMA_X3 && to_device, f16 = c->nn_mode == PN_NN_MFMA_F16 && to_device;
-  const size_t B = c->B, Bp = c->Bp; const int64_t t = c->tn;
-  const hipMemcpyKind kind = to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
-  auto cp2d = [&](float *host, size_t hpitch, float *dev, size_t dpitch, size_t width) -> hipError_t {
-    return to_device ? hipMemcpy2DAsync(dev, dpitch * 4, host, hpitch * 4, width * 4, B, kind, c->stream)
-                     : hipMemcpy2DAsync(host, hpitch * 4, dev, dpitch * 4, width * 4, B, kind, c->stream);
-  };
+  const size_t B = c->B; const int Bp = (int)c->Bp;
   int split_rc = 0;
-  auto resplit = [&](float *dev, int width) {
-    if (x3) split_rc |= pn_launch_split_x3(c->stream, dev, width, width, shadow(c, dev), (int)Bp, 2);
-    if (f16) split_rc |= pn_launch_split_x3(c->stream, dev, width, width, shadow(c, dev), (int)Bp, 1);
-    if (c->plan.direct && to_device && shadow(c, dev)) split_rc |= pn_launch_split_d(c->stream, dev, width, width, shadow(c, dev), (int)Bp);   // (GRU states; the conv FIFOs have no shadow there)
-  };
-  if (conv1) for (int j = 0; j < 4; j++) {
-    float *d = c->c1ring + (size_t)((t + 1 + j) % 5) * Bp * 128;
-    PN_HIP_CHECK(cp2d(conv1 + j * 128, 4 * 128, d, 128, 128)); resplit(d, 128);
+  for (int e = PN_ST_C1RING, i = 0; e <= PN_ST_RB; e++) {
+    const PnStateEntry &L = pn_kState[e];
+    if (L.cls != PN_CLS_RING) continue;
+    float *const hrow = host[i++];
+    const size_t hp = (size_t)L.live * L.cols * 4, dp = (size_t)L.row_words * 4, w = (size_t)L.cols * 4;
+    for (int j = 0; hrow && j < L.live; j++) {
+      float *d = state_at(c, e, j), *h = hrow + j * L.cols;
+      PN_HIP_CHECK(to_device ? hipMemcpy2DAsync(d, dp, h, hp, w, B, hipMemcpyHostToDevice, c->stream)
+                             : hipMemcpy2DAsync(h, hp, d, dp, w, B, hipMemcpyDeviceToHost, c->stream));
+      if (x3) split_rc |= pn_launch_split_x3(c->stream, d, L.cols, L.cols, shadow(c, d), Bp, 2);
+      if (f16) split_rc |= pn_launch_split_x3(c->stream, d, L.cols, L.cols, shadow(c, d), Bp, 1);
+      if (c->plan.direct && to_device && shadow(c, d)) split_rc |= pn_launch_split_d(c->stream, d, L.cols, L.cols, shadow(c, d), Bp);   // (GRU states; the conv FIFOs have no shadow there)
+    }
   }
-  if (conv2) for (int j = 0; j < 2; j++) {
-    float *d = c->c2ring + (size_t)((t + 1 + j) % 3) * Bp * 512;
-    PN_HIP_CHECK(cp2d(conv2 + j * 512, 2 * 512, d, 512, 512)); resplit(d, 512);
-  }
-  for (int i = 0; i < 4; i++)
-    if (gru[i]) { float *d = c->gru[i] + (size_t)(t & 1) * Bp * 512; PN_HIP_CHECK(cp2d(gru[i], 512, d, 512, 512)); resplit(d, 512); }
-  if (rb) { float *d = c->rb + (size_t)(t & 1) * Bp * 128; PN_HIP_CHECK(cp2d(rb, 128, d, 128, 128)); resplit(d, 128); }
   PN_HIP_CHECK(hipStreamSynchronize(c->stream));
   return split_rc ? -1 : 0;                  // a refused shadow-operand split (pn_launch_split_x3) fails the call, like any refused launch
 }
 extern "C" int pn_ctx_set_rnn_state_host(pn_ctx *c, const float *conv1, const float *conv2, const float *gru1, const float *gru2,
                                          const float *gru3, const float *gru_gb, const float *gru_rb) {
   if (!c) { pn_set_error("NULL argument"); return -1; }
-  float *g[4] = {(float *)gru1, (float *)gru2, (float *)gru3, (float *)gru_gb};
-  return rnn_state_copy(c, true, (float *)conv1, (float *)conv2, g, (float *)gru_rb);
+  float *h[PN_ST_NNET] = {(float *)conv1, (float *)conv2, (float *)gru1, (float *)gru2, (float *)gru3, (float *)gru_gb, (float *)gru_rb};
+  return rnn_state_copy(c, true, h);
 }
 extern "C" int pn_ctx_get_rnn_state_host(pn_ctx *c, float *conv1, float *conv2, float *gru1, float *gru2, float *gru3,
                                          float *gru_gb, float *gru_rb) {
   if (!c) { pn_set_error("NULL argument"); return -1; }
-  float *g[4] = {gru1, gru2, gru3, gru_gb};
-  return rnn_state_copy(c, false, conv1, conv2, g, gru_rb);
+  float *h[PN_ST_NNET] = {conv1, conv2, gru1, gru2, gru3, gru_gb, gru_rb};
+  return rnn_state_copy(c, false, h);
 }
 
 // ---- per-stream state records (pn_stream_state.hip; layout in include/percepnet_hip.h) ------------------------------
@@ -1403,25 +1339,9 @@ static int ss_ids_check(pn_ctx *c, const int32_t *ids, int n, bool distinct) {
   }
   return 0;
 }
-// The sections of a record at the context's CURRENT counters (those of the next frame to run): DSP rings follow t, the
-// network's follow tn (they differ after pn_ctx_compute_rnn_host).  Live entries oldest first from slot `first`.
 static void ss_args(pn_ctx *c, PnStreamStateArgs &a) {
   memset(&a, 0, sizeof(a));
-  const long long B = c->B, Bp = (long long)c->Bp;
-  const int t12 = (int)((c->t + 1) % 12), t6 = (int)((c->t + 1) % 6), n5 = (int)((c->tn + 1) % 5), n3 = (int)((c->tn + 1) % 3),
-            n2 = (int)(c->tn & 1);
-  int k = 0;
-  auto sec = [&](float *base, long long row_stride, long long slot_stride, int slots, int first, int live, int cols, int off) {
-    a.sec[k++] = PnSsSection{base, row_stride, slot_stride, slots, first, live, cols, off};
-  };
-  sec(c->hist, PN_HIST_STRIDE, PN_FRAME, 12, t12, 11, PN_FRAME, PN_SS_HIST);      // slots back to back inside the row
-  sec(reinterpret_cast<float *>(c->yring), 2 * PN_SPEC_BINS, B * 2 * PN_SPEC_BINS, 6, t6, 5, 2 * PN_SPEC_BINS, PN_SS_SPEC);
-  sec(c->eyring, 36, B * 36, 6, t6, 5, 36, PN_SS_EY);
-  sec(c->c1ring, 128, Bp * 128, 5, n5, 4, 128, PN_SS_CONV1);
-  sec(c->c2ring, 512, Bp * 512, 3, n3, 2, 512, PN_SS_CONV2);
-  for (int g = 0; g < 4; g++) sec(c->gru[g], 512, Bp * 512, 2, n2, 1, 512, PN_SS_GRU + 512 * g);
-  sec(c->rb, 128, Bp * 128, 2, n2, 1, 128, PN_SS_GRU_RB);
-  sec(c->synth, PN_FRAME, 0, 1, 0, 1, PN_FRAME, PN_SS_SYNTH);                      // last: carries the tail
+  state_sections(c, a.sec);
   a.last_gain = c->last_gain; a.last_period = c->last_period;
   ss_header(a.hdr, ctx_digest(c), c->nn_mode);
 }
@@ -1458,18 +1378,15 @@ extern "C" int pn_ctx_import_streams(pn_ctx *c, const int32_t *ids, int n, const
   // conv FIFOs and the GRU / rb states (shadow-operand modes), fp32 fragments of the GRU / rb states (direct-operand family)
   const bool x3 = c->nn_mode == PN_NN_MFMA_X3 || c->nn_mode == PN_NN_MFMA_F16;
   const int np = c->nn_mode == PN_NN_MFMA_X3 ? 2 : 1;
-  const size_t Bp = c->Bp; const int64_t tn = c->tn;
   int rc = 0;
-  auto resplit = [&](float *slot, int width) {
-    void *S = shadow(c, slot);
-    if (!S) return;                                    // no shadow of this buffer in this mode / family
-    if (x3) rc |= pn_launch_split_x3_rows(c->stream, slot, width, width, S, d, d_status, n, np);
-    else if (c->plan.direct) rc |= pn_launch_split_d_rows(c->stream, slot, width, width, S, d, d_status, n);
-  };
-  for (int j = 0; j < 4; j++) resplit(c->c1ring + (size_t)((tn + 1 + j) % 5) * Bp * 128, 128);
-  for (int j = 0; j < 2; j++) resplit(c->c2ring + (size_t)((tn + 1 + j) % 3) * Bp * 512, 512);
-  for (int g = 0; g < 4; g++) resplit(c->gru[g] + (size_t)(tn & 1) * Bp * 512, 512);
-  resplit(c->rb + (size_t)(tn & 1) * Bp * 128, 128);
+  for (int e = PN_ST_C1RING; e <= PN_ST_RB; e++)
+    for (int j = 0; pn_kState[e].cls == PN_CLS_RING && j < pn_kState[e].live; j++) {
+      float *slot = state_at(c, e, j); void *S = shadow(c, slot);
+      const int width = pn_kState[e].cols;
+      if (!S) continue;                                  // no shadow of this buffer in this mode / family
+      if (x3) rc |= pn_launch_split_x3_rows(c->stream, slot, width, width, S, d, d_status, n, np);
+      else if (c->plan.direct) rc |= pn_launch_split_d_rows(c->stream, slot, width, width, S, d, d_status, n);
+    }
   PN_HIP_CHECK(hipGetLastError());
   return rc ? -1 : 0;
 }
@@ -1525,22 +1442,10 @@ extern "C" int pn_ctx_import_streams_host(pn_ctx *c, const int32_t *ids, int n, 
 //        12 history ring, 13 last_period int32 [B].  Returns the byte count.
 extern "C" long long pn_ctx_debug_copy(pn_ctx *c, int which, void *dst, long long max_bytes) {
   if (!c || !dst) return -1;
-  const size_t B = c->B, Bp = c->Bp;
-  const void *src = NULL; size_t n = 0;
-  switch (which) {
-    case 0: src = c->feat; n = Bp * PN_FEAT_STRIDE * 4; break;
-    case 1: src = c->c1ring; n = 5 * Bp * 128 * 4; break;
-    case 2: src = c->c2ring; n = 3 * Bp * 512 * 4; break;
-    case 3: src = c->c2out; n = Bp * 512 * 4; break;
-    case 4: case 5: case 6: case 7: src = c->gru[which - 4]; n = 2 * Bp * 512 * 4; break;
-    case 8: src = c->rb; n = 2 * Bp * 128 * 4; break;
-    case 9: src = c->gr; n = B * 68 * 4; break;
-    case 10: src = c->yring; n = 6 * B * PN_SPEC_BINS * sizeof(float2); break;     // look-ahead spectra ring [6][B][400]
-    case 11: src = c->Ps; n = B * PN_SPEC_BINS * sizeof(float2); break;            // comb-filtered spectrum [B][400]
-    case 12: src = c->hist; n = B * PN_HIST_STRIDE * 4; break;                     // history ring
-    case 13: src = c->last_period; n = B * 4; break;                               // pitch period of the last frame, int32 [B]
-    default: pn_set_error("bad debug buffer id"); return -1;
-  }
+  static const int entry[14] = {PN_ST_FEAT, PN_ST_C1RING, PN_ST_C2RING, PN_ST_C2OUT, PN_ST_GRU1, PN_ST_GRU2, PN_ST_GRU3, PN_ST_GRU_GB, PN_ST_RB,
+                                PN_ST_GR, PN_ST_YRING, PN_ST_PS, PN_ST_HIST, PN_ST_LAST_PERIOD};
+  if (which < 0 || which >= 14) { pn_set_error("bad debug buffer id"); return -1; }
+  const void *src = c->st[entry[which]].p; const size_t n = c->st[entry[which]].words * 4;
   if ((long long)n > max_bytes) { pn_set_error("debug buffer needs %zu bytes", n); return -1; }
   PN_ON_DEVICE(c);
   if (hipStreamSynchronize(c->stream) != hipSuccess) return -1;

@@ -1,6 +1,7 @@
 // Kernel launchers shared by the host files (pn_context.cpp, pn_featgen.cpp).
 #pragma once
 #include "pn_common.h"
+#include "pn_state_layout.h"
 
 // grid_cap (last argument of every DSP launcher): test hook of the create-time DSP self-test (pn_context.cpp: dsp_selftest).
 // When > 0 the launcher caps its grid at this many blocks, so that a 40-stream batch walks several grid-stride rounds of ONE
@@ -39,26 +40,25 @@ void pn_launch_zero_shadow_rows(hipStream_t st, void *S, int width, int np, int 
                                 const int *d_ids, int n);
 // dst[ids[i]] = vals[i] for i < n (distinct ids): the per-stream (lam, mu) pairs of the attenuation limit
 void pn_launch_scatter_pairs(hipStream_t st, float2 *dst, const int *d_ids, const float2 *d_vals, int n);
+// One section of a context's per-stream state at given counters (pn_context.cpp state_sections, from pn_state_layout.h): a
+// ring or an in-place buffer, its live entries oldest first in slots first, first + 1, ... (mod slots); base + row * row_stride
+// + slot * slot_stride = an entry of `cols` floats (all multiples of 4), stored at body word rec_off of a stream-state record.
+// shadow: the entry's fragment-order operand shadow of np planes (pn_nn_x3.hip), slot for slot; NULL = none
+struct PnSsSection { float *base; uint4 *shadow; long long row_stride, slot_stride; int slots, first, live, cols, rec_off, np; };
 // per-call active set (pn_active.hip): the rows ids[0..n) are the streams a call does NOT advance
 struct PnActiveArgs {
   const int *ids;                                    // inactive stream ids (device)
   float *synth; int *last_period; float *last_gain;  // in-place state
   void *out; int out_row_words; float *d_gr;         // the caller's output rows (480 int16 = 240 words, or 480 floats); d_gr may be NULL
   float *save_synth; uint32_t *save_out; float *save_gr; int *save_period; float *save_gain;   // save area, row i = ids[i]
-  float *hist; float2 *yring; float *eyring, *c1ring, *c2ring, *gru[4], *rb;
-  uint4 *c1ringH, *c2ringH, *gruH[4], *rbH; int np;  // operand shadows (np = 0: none)
-  long long B, Bp, t, tn;                            // t / tn: the counters of the tick the fix-up follows
+  PnSsSection sec[PN_SS_NSEC];                       // the rings at the counters of the tick the fix-up follows
   int restore_only;                                  // the frame FAILED (a refused launch): put the in-place state and the caller's rows of the
                                                      // skipped streams back, shift nothing (the context's counters did not advance)
 };
 void pn_launch_inactive_save(hipStream_t st, const PnActiveArgs &a, int n);
 int pn_launch_spin(hipStream_t st, long long ticks);     // one wave asleep for `ticks` of the 100 MHz wall clock (queue probe)
 void pn_launch_inactive_fixup(hipStream_t st, const PnActiveArgs &a, int n);
-// per-stream state records (pn_stream_state.hip): one section = one ring (or in-place buffer) of the record, its live entries
-// oldest first in slots first, first + 1, ... (mod slots); base + row * row_stride + slot * slot_stride = an entry of `cols`
-// floats (all multiples of 4), stored at body word rec_off of the record
-struct PnSsSection { float *base; long long row_stride, slot_stride; int slots, first, live, cols, rec_off; };
-enum { PN_SS_NSEC = 11 };          // history, spectra, band energies, conv1, conv2, gru1..gru_gb, gru_rb, synth (+ the tail)
+// per-stream state records (pn_stream_state.hip): the sections at the context's current counters
 struct PnStreamStateArgs {
   PnSsSection sec[PN_SS_NSEC];
   float *last_gain; int *last_period;

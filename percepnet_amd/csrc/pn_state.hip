@@ -1,10 +1,10 @@
 // Per-stream lifecycle of a batched context (round-3 verdict item 4): what rnnoise_init does for ONE DenoiseState
 // (reference denoise.cpp:259-280: memset of the struct, calloc of the RNN state) for a chosen subset of the B streams of a
 // context, on the device, while the other streams keep running.  Every per-stream buffer of a context is a ring or a
-// ping-pong pair indexed by the context's GLOBAL frame counter (hist slot t % 12, look-ahead rings t % 6, conv rings
-// tn % 5 / tn % 3, GRU buffers tn & 1); a fresh stream is all-zero in every slot, so zeroing the rows of stream s in every
-// slot puts that stream at its own frame 0 whatever the phase of the rings is (the look-ahead spectrum of an all-zero
-// window is zero, its band energies are zero: the same values a fresh context holds).
+// ping-pong pair indexed by the context's GLOBAL counters (pn_state_layout.h); a fresh stream is all-zero in every slot, so
+// zeroing the rows of stream s in every slot of every entry puts that stream at its own frame 0 whatever the phase of the
+// rings is (the look-ahead spectrum of an all-zero window is zero, its band energies are zero: the same values a fresh
+// context holds).
 #include "pn_common.h"
 
 // rows ids[0..n) of a [n_slots][n_rows][row_floats] array (slot stride in floats): one block per (row, slot), float4 stores

@@ -1,23 +1,15 @@
 // Per-stream state records (include/percepnet_hip.h, "per-stream state records"): gather the whole state of chosen streams
 // into phase-free records, and scatter records into chosen streams of another context at ITS phase.
 //
-// Every per-stream buffer is a ring or a ping-pong pair indexed by the context's global counters (pn_active.hip lists them and
-// how many entries of each are live): history slot t % 12 (11 live), look-ahead spectra and band energies t % 6 (5 live), conv1
-// FIFO tn % 5 (4 live), conv2 FIFO tn % 3 (2 live), GRU / rb halves tn & 1 (1 live); synth, last_gain, last_period in place.
-// Before the frame with counters (t, tn) runs, the live entries sit, oldest first, in slots first, first + 1, ... (mod slots)
-// with first = (t + 1) % 12, (t + 1) % 6, (tn + 1) % 5, (tn + 1) % 3, tn & 1 — the host computes `first` per section, the
-// kernels only walk it.  The dead slots of an imported row keep what they held: the frame kernels overwrite them before
-// they read them (pn_active.hip class (a)).  Operand shadows are re-derived afterwards for the imported rows only, by the
-// row-list forms of the split kernels (pn_launch_split_x3_rows, pn_launch_split_d_rows).
+// Every per-stream buffer is a ring or a ping-pong pair indexed by the context's global counters, or in place
+// (pn_state_layout.h: the table, the phases, and the check that the record offsets follow from the geometry).  Before the
+// frame with counters (t, tn) runs, the live entries of a section sit, oldest first, in slots first, first + 1, ... (mod
+// slots) — the host computes `first` per section, the kernels only walk it.  The dead slots of an imported row keep what they
+// held: the frame kernels overwrite them before they read them.  Operand shadows are re-derived afterwards for the imported
+// rows only, by the row-list forms of the split kernels (pn_launch_split_x3_rows, pn_launch_split_d_rows).
 #include "pn_common.h"
 #include "pn_launch.h"
 #include "../../include/percepnet_hip.h"
-
-static_assert(PN_STREAM_STATE_BYTES % 16 == 0 && PN_STREAM_STATE_HEADER_BYTES % 16 == 0, "records stay float4-aligned");
-static_assert(PN_SS_SPEC == PN_SS_HIST + 11 * PN_FRAME && PN_SS_EY == PN_SS_SPEC + 5 * 2 * PN_SPEC_BINS &&
-              PN_SS_CONV1 == PN_SS_EY + 5 * 36 && PN_SS_CONV2 == PN_SS_CONV1 + 4 * 128 && PN_SS_GRU == PN_SS_CONV2 + 2 * 512 &&
-              PN_SS_GRU_RB == PN_SS_GRU + 4 * 512 && PN_SS_SYNTH == PN_SS_GRU_RB + 128 && PN_SS_TAIL == PN_SS_SYNTH + PN_FRAME &&
-              PN_SS_BODY_WORDS == PN_SS_TAIL + 4, "record layout (percepnet_hip.h) and ring geometry agree");
 
 #define SS_THREADS 256
 

@@ -1,11 +1,13 @@
 // CPU-only sanitizer harness (tests/test_hardening.py builds it with g++ -fsanitize=address,undefined -DPN_NO_HIP): the
 // HIP-free host pieces of libpercepnet_hip — the PNW1 / RNNModel parsers (pn_model.cpp), the table builder (pn_tables.cpp),
 // the weight packers (pn_pack.cpp) and the CLI helpers (pn_cli_util.h) — driven with valid, truncated, oversized and
-// corrupted inputs.  Any out-of-bounds access, overflow or leak-free violation aborts; the process prints "ok" and exits 0.
+// corrupted inputs; and the table of a context's per-stream state (pn_state_layout.h): record offsets, ring phases, classes.
+// Any out-of-bounds access, overflow or leak-free violation aborts; the process prints "ok" and exits 0.
 #include "../../percepnet_amd/csrc/pn_model.cpp"
 #include "../../percepnet_amd/csrc/pn_pack.cpp"
 #include "../../percepnet_amd/csrc/pn_tables.cpp"
 #include "../../percepnet_amd/csrc/pn_cli_util.h"
+#include "../../percepnet_amd/csrc/pn_state_layout.h"
 #include <stdio.h>
 #include <string>
 #include <vector>
@@ -23,6 +25,39 @@ int main(int argc, char **argv) {
 
   // tables
   { PnTables *t = new PnTables(); CHECK(pn_build_tables(t) == 0); CHECK(t->border[PN_NB - 1] == PN_SPEC_BINS); CHECK(t->tansig[200] > 0.999f); delete t; }
+
+  // the state table.  Records: every entry with a record offset starts at its public PN_SS_* constant, the sections are
+  // contiguous in offset order, and with the four tail words they fill the body
+  { const int want[PN_SS_NSEC] = {PN_SS_HIST, PN_SS_SPEC, PN_SS_EY, PN_SS_CONV1, PN_SS_CONV2, PN_SS_GRU, PN_SS_GRU + 512, PN_SS_GRU + 1024,
+                                  PN_SS_GRU + 1536, PN_SS_GRU_RB, PN_SS_SYNTH};
+    int off = 0, nrec = 0;
+    for (int k = 0; k < PN_SS_NSEC; k++)                     // section k = the entry with the k-th smallest offset
+      for (int e = 0; e < PN_ST_COUNT; e++) {
+        const PnStateEntry &L = pn_kState[e];
+        if (pn_state_section(e) != k) continue;
+        CHECK(L.rec_off == want[k]); CHECK(L.rec_off == off);
+        off += L.live * L.cols; nrec++;
+      }
+    for (int e = 0; e < PN_ST_COUNT; e++) CHECK((pn_kState[e].rec_off >= 0) == (pn_state_section(e) >= 0));
+    CHECK(nrec == PN_SS_NSEC); CHECK(off == PN_SS_TAIL); CHECK(off + 4 == PN_SS_BODY_WORDS); CHECK(PN_SS_BODY_WORDS == 13656); }
+  // classes agree with the geometry; and the ring phases the active-set fix-up and the records both rest on: the slot a frame
+  // writes is not live, after the frame `first` has advanced by one and the slot written is the newest live one
+  for (int e = 0; e < PN_ST_COUNT; e++) {
+    const PnStateEntry &L = pn_kState[e];
+    CHECK(L.slots >= 1 && L.cols >= 1 && L.row_words >= (L.in_row ? L.slots : 1) * L.cols);
+    if (L.cls == PN_CLS_RING) { CHECK(L.slots >= 2 && L.live == L.slots - 1); CHECK(L.counter == PN_CNT_T || L.counter == PN_CNT_TN); }
+    else { CHECK(L.cls == PN_CLS_INPLACE || L.cls == PN_CLS_SCRATCH); CHECK(L.slots == 1 && L.live == 1 && L.counter == PN_CNT_NONE); }
+    if (L.shadow != PN_SH_NONE) CHECK(L.padded && L.cols % 32 == 0 && L.cols == L.row_words);      // fragment-order shadows: whole column tiles of Bp rows
+    if (L.cls != PN_CLS_RING) continue;
+    for (int64_t t = 0; t < 24; t++)
+      for (int64_t tn : {t, t + 1, t + 7}) {
+        const int first = pn_state_first(L, t, tn), wr = pn_state_write(L, t, tn);
+        CHECK(first >= 0 && first < L.slots && wr >= 0 && wr < L.slots);
+        for (int j = 0; j < L.live; j++) CHECK((first + j) % L.slots != wr);
+        CHECK(pn_state_first(L, t + 1, tn + 1) == (first + 1) % L.slots);
+        CHECK((pn_state_first(L, t + 1, tn + 1) + L.live - 1) % L.slots == wr);
+      }
+  }
 
   // CLI helpers
   { std::vector<int> d;

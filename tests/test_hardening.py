@@ -42,7 +42,8 @@ def test_nothing_but_the_c_abi_and_the_reference_names_is_exported(lib):
 def test_host_pieces_under_address_and_undefined_behaviour_sanitizers(blob, tmp_path):
     """tests/c/host_sanitize.cpp = pn_model.cpp + pn_pack.cpp + pn_tables.cpp + pn_cli_util.h built WITHOUT HIP by plain g++
     with -fsanitize=address,undefined, then fed the valid container, every truncation around the headers, absurd
-    dimensions in every header field, random byte flips, wrong RNNModel geometries, and exactly-sized packer outputs."""
+    dimensions in every header field, random byte flips, wrong RNNModel geometries, and exactly-sized packer outputs.  It also
+    checks the table of the per-stream state (pn_state_layout.h): record offsets, ring phases and classes."""
     if not shutil.which("g++"):
         pytest.skip("g++ not available")
     exe = tmp_path / "host_sanitize"
