@@ -77,9 +77,11 @@ struct pn_model {
 #endif
 void pn_set_error(const char *fmt, ...);
 
-// pn_model.cpp: the fixed topology and the size of a layer's arrays in the nnet_data.h layout
+// the fixed topology, and (pn_model.cpp) the size of a layer's arrays in the nnet_data.h layout
 struct PnGeom { int kind, nin, nn, ks; };
-extern const PnGeom pn_kGeom[];
+static constexpr PnGeom pn_kGeom[PN_NLAYERS] = {
+  {PN_KIND_DENSE, 70, 128, 1}, {PN_KIND_CONV1D, 128, 512, 5}, {PN_KIND_CONV1D, 512, 512, 3}, {PN_KIND_GRU, 512, 512, 1}, {PN_KIND_GRU, 512, 512, 1},
+  {PN_KIND_GRU, 512, 512, 1}, {PN_KIND_GRU, 512, 512, 1}, {PN_KIND_GRU, 1024, 128, 1}, {PN_KIND_DENSE, 2560, 34, 1}, {PN_KIND_DENSE, 128, 34, 1}};
 size_t pn_layer_floats(int kind, int nin, int nn, int ks, size_t *nb, size_t *nw, size_t *nr);
 // pn_pack.cpp: host-side re-packing of the weight matrices for the fp32 MFMA kernels
 size_t pn_packed_floats(int k_alloc, int ncols, int ct_round);

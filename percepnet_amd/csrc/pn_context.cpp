@@ -1,119 +1,24 @@
 // Host side of libpercepnet_hip: models, batched contexts, the per-frame launch sequence and the
 // C-ABI declared in include/percepnet_hip.h.  Mirrors the reference's frame engine
 // (rnnoise_create/init/process_frame, denoise.cpp:252-280,508-547) for B streams in lock-step.
-#include "pn_common.h"
-#include "../../include/percepnet_hip.h"
-#include <stdarg.h>
+#include "pn_context.h"
 #include <stdio.h>
-#include <stdlib.h>
 #include <float.h>
 #include <math.h>
-#include <string.h>
-#include <array>
 #include <map>
 #include <mutex>
-#include <new>
 #include <string>
-#include <tuple>
-#include <vector>
 
-#include "pn_launch.h"
-#include "pn_plan.h"
 #include "pn_selftest_golden.h"
 
 extern "C" int pn_device_count(void) { int n = 0; return hipGetDeviceCount(&n) == hipSuccess ? n : 0; }
 
 // ---- contexts -----------------------------------------------------------------------------------------
-enum { KF_FRONTEND, KF_FC, KF_CONV1, KF_CONV2, KF_GRU512, KF_GRU_RB, KF_FC_GB, KF_FC_RB, KF_BACKEND, KF_FE_SPEC_IN, KF_FE_PITCH,
-       KF_FE_SPEC_OUT, KF_COUNT };
 static const char *kKernelNames[KF_COUNT] = {"frontend", "fc", "conv1", "conv2", "gru512", "gru_rb", "fc_gb", "fc_rb", "backend",
                                             "fe_spec_in", "fe_pitch", "fe_spec_out"};
 
-struct DevLayer { float *bias, *w, *rw, *wp, *rwp, *wq; };   // wq: narrow layers of small-batch fp32 contexts (pn_pack_weights_n16)
-
-// Device copy of a model's biases and (re-packed) weights, shared by every context of one (model content, device, network
-// mode, narrow-layer packing): the reference binds all its states to ONE static model (denoise.cpp:49-51,267: a borrowed
-// pointer, zero copies); here N contexts — N legacy rnnoise_create handles, the shards of a CLI run, a service that opens
-// and closes contexts — share one 32 MB upload and one re-pack instead of N.  Reference-counted, freed with its last user.
-struct SharedWeights {
-  int refs = 0;
-  DevLayer L[PN_NLAYERS];
-  std::vector<void *> allocs;
-  size_t bytes = 0;
-};
-// SHA-256 of the model content (pn_model_from_sources: arrays + activations + reset_after), array length, device, nn_mode, narrow
-// layers packed for the n16 kernel.  The digest IS the identity: no host copy of the model is kept and nothing is compared byte for
-// byte on a hit (round 5 kept 32 MB per entry and memcmp'ed it under the build lock).
-typedef std::tuple<std::array<unsigned char, 32>, size_t, int, int, int> WeightsKey;
-static std::mutex g_weights_mu;                              // guards g_weights and every refs counter
-static std::mutex g_weights_build_mu[16];                    // per device (mod 16): uploads and re-packs of DIFFERENT devices run
-                                                             // side by side (percepnet_run --devices creates its contexts from one thread per device)
-static std::map<WeightsKey, SharedWeights *> g_weights;
-
-struct pn_ctx {
-  int device, B, nn_mode;
-  PnPlan plan;                     // the kernel families (pn_plan.h), fixed at creation
-  size_t Bp;                       // B rounded up to the largest GEMM M tile (256): row count of every network buffer
-  hipStream_t stream; bool own_stream;
-  hipStream_t chain_stream[4] = {nullptr, nullptr, nullptr, nullptr};      // launch_rnn: streams of the row-range chains 1..3 (chain 0 = stream), created with the context
-  hipEvent_t chain_fork = nullptr, chain_join[4] = {nullptr, nullptr, nullptr, nullptr};
-  char chain_kind[5] = {'-', '-', '-', '-', 0};   // how each chain stream was obtained (n: default priority, probed; h: priority stream)
-  int64_t t;                       // frames done: the counter of the DSP rings (pn_state_layout.h)
-  int64_t tn;                      // network steps done: the counter of the conv FIFOs and the GRU pairs.
-                                   // == t unless pn_ctx_compute_rnn_host advanced the network on its own (rnn.cpp:42 is
-                                   // callable on an RNNState without a DenoiseState in the reference too)
-  size_t bytes;
-  PnLayerHost geom[PN_NLAYERS];
-  DevLayer L[PN_NLAYERS];           // = weights->L (pointers into the shared copy)
-  SharedWeights *weights = NULL; WeightsKey weights_key; bool weights_were_cached = false;
-  // a list of stream ids on the device, and a ring of pinned host copies (the H2D copy runs when the stream gets to it —
-  // frames may be in flight — so its source must outlive the call; slot k is reused once its copy has executed)
-  struct IdRing { int *d = NULL; int cap = 0; unsigned calls = 0; struct { int *h = NULL; hipEvent_t ev = nullptr; } slot[4]; };
-  IdRing ids;                      // pn_ctx_reset_streams, pn_ctx_set_atten_limit, stream-state export / import
-  // pn_process_*_active: the inactive rows (a ring of its own: a reset's list may still be in flight) and the save area of the
-  // in-place state of those rows, grown on demand
-  struct Active {
-    IdRing ids;
-    float *save_synth = NULL, *save_gr = NULL, *save_gain = NULL; uint32_t *save_out = NULL; int *save_period = NULL;
-    std::vector<uint8_t> mark; std::vector<int32_t> inactive;
-  } act;
-  PnTables *tables; float *tansig;
-  // the per-stream state: pn_kState (pn_state_layout.h) resolved for this context's size, mode and plan.  sh: the operand shadow
-  // (same element index, shadow_halfs_per_element halfs per element), NULL where the mode / family keeps none
-  struct StateBuf { float *p; uint16_t *sh; size_t words; long long slot_stride; } st[PN_ST_COUNT] = {};
-  float *hist, *eyring, *synth, *last_gain, *feat, *gr, *io_in, *io_out;      // aliases of st[].p that the frame path reads
-  float2 *yring, *Ps;
-  bool postfilter = false;         // optional envelope post-filter in the back end (pn_ctx_set_postfilter)
-  // per-stream attenuation limit (pn_ctx_set_atten_limit): (lam, mu) per stream on the device, allocated by the first set; the
-  // host mirror of the dB values (the getter) and the count of streams with lam != 0 (the launch decision: while it is 0 the
-  // back end is the plain kernel and lam_mu is not read)
-  float2 *lam_mu = NULL;
-  std::vector<float> atten_db;
-  int n_limited = 0;
-  bool x3_sat = false;             // PERCEPNET_X3_SATCOUNT=1 (shadow-operand modes): count operand values clamped to the fp16 range
-  int dsp_grid_cap = 0;            // > 0 only in the DSP self-test's temporary context: its DSP launches use that many blocks
-  bool inject_bad_launch = false;  // pn_ctx_debug_inject_launch_failure (tests): the next frames hand fc a geometry its launcher refuses
-  int *last_period, *silence;      // (aliases too)
-  std::vector<void *> allocs;
-  bool profiling;
-  struct Ev { int fam; hipEvent_t a, b; };
-  std::vector<Ev> events;
-  std::vector<hipEvent_t> event_pool;   // recycled timing events: no hipEventCreate/Destroy inside a timed region
-  double fam_ms[KF_COUNT]; int64_t fam_n[KF_COUNT];
-  // pipelined host-buffer path (pn_submit_host_*): created on first use
-  struct Pipe {
-    bool init = false;
-    hipStream_t h2d = nullptr, d2h = nullptr;
-    hipEvent_t in_ready[2] = {nullptr, nullptr}, done[2] = {nullptr, nullptr}, delivered[2] = {nullptr, nullptr};
-    void *in[2] = {nullptr, nullptr}, *out[2] = {nullptr, nullptr};
-    float *gr[2] = {nullptr, nullptr};
-    int64_t submitted = 0;
-    char kind[3] = {'?', '?', 0};             // how each copy stream was obtained: n (default priority, probed) / h / l (priority stream)
-  } pipe;
-};
-
 static thread_local bool g_last_alloc_oom = false;     // the last dev_alloc failure on this thread was hipErrorOutOfMemory
-static int dev_alloc_into(std::vector<void *> &allocs, size_t &total, hipStream_t stream, void **p, size_t bytes, bool zero) {
+int dev_alloc_into(std::vector<void *> &allocs, size_t &total, hipStream_t stream, void **p, size_t bytes, bool zero) {
   // PERCEPNET_GUARD=1 (debugging aid): every buffer is followed by 1 MB of 0xFF (NaN as fp32 and as fp16), so that a
   // read past the end of a buffer shows up as NaN in the outputs instead of as run-to-run noise
   static const bool guard = getenv("PERCEPNET_GUARD") != NULL;
@@ -137,22 +42,6 @@ static int dev_alloc(pn_ctx *c, void **p, size_t bytes, bool zero) { return dev_
 #define DEV_ALLOC(ptr, count, zero) \
   do { if (dev_alloc(c, (void **)&(ptr), sizeof(*(ptr)) * (size_t)(count), zero)) goto fail; } while (0)
 
-static int upload(pn_ctx *c, float **dst, const float *src, size_t n) {
-  if (dev_alloc(c, (void **)dst, n * sizeof(float), false)) return -1;
-  PN_HIP_CHECK(hipMemcpyAsync(*dst, src, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  return 0;
-}
-// the same into the shared weight copy under construction (uploads run on the creating context's stream)
-static int upload_w(pn_ctx *c, SharedWeights *w, float **dst, const float *src, size_t n) {
-  if (dev_alloc_into(w->allocs, w->bytes, c->stream, (void **)dst, n * sizeof(float), false)) return -1;
-  PN_HIP_CHECK(hipMemcpyAsync(*dst, src, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  return 0;
-}
-
-// operand shadows: 1 half per element (fp16-operand mode) or a hi and a lo plane (split-precision mode)
-// (the fp32 shadows of the direct-operand family are 4 bytes per element, laid out in the same 16-byte slab entries)
-static size_t shadow_halfs_per_element(const pn_ctx *c) { return (c->nn_mode == PN_NN_MFMA_X3 || c->plan.direct) ? 2 : 1; }
-static bool x3_layer(int li) { return li == PN_L_CONV1 || li == PN_L_CONV2 || li == PN_L_GRU_RB || li == PN_L_FC_GB || (li >= PN_L_GRU1 && li < PN_L_GRU1 + 4); }
 // "fresh context", pn_ctx_reset and "every stream reset" are one statement: every word of every entry and shadow is zero
 static int zero_state(pn_ctx *c) {
   for (const pn_ctx::StateBuf &b : c->st) {
@@ -163,13 +52,6 @@ static int zero_state(pn_ctx *c) {
   c->atten_db.assign(c->B, INFINITY); c->n_limited = 0;
   c->t = 0; c->tn = 0;
   return 0;
-}
-// entry e of the state: its j-th live entry, oldest first, before the step with the context's counters runs (j == live: the slot
-// that step writes), from row r0 on
-static float *state_at(const pn_ctx *c, int e, int j, size_t r0 = 0) {
-  const PnStateEntry &L = pn_kState[e];
-  const int slot = j < L.live ? (pn_state_first(L, c->t, c->tn) + j) % L.slots : pn_state_write(L, c->t, c->tn);
-  return c->st[e].p + slot * c->st[e].slot_stride + r0 * L.row_words;
 }
 // The record sections (= the rings the active-set fix-up shifts, and synth) at the context's CURRENT counters, those of the next
 // frame to run: DSP rings follow t, the network's follow tn (they differ after pn_ctx_compute_rnn_host)
@@ -183,7 +65,6 @@ static void state_sections(const pn_ctx *c, PnSsSection sec[PN_SS_NSEC]) {
 
 static int nn_selftest(pn_ctx *c);
 static int dsp_selftest(pn_ctx *c);
-static int chain_streams_init(pn_ctx *c);
 static pn_ctx *ctx_create(const pn_model *model, int device, int n_streams, int nn_mode, void *hip_stream, bool selftest, const PnPlan *plan);
 
 extern "C" void pn_ctx_destroy(pn_ctx *c) {
@@ -202,79 +83,13 @@ extern "C" void pn_ctx_destroy(pn_ctx *c) {
   for (void *p : c->allocs) hipFree(p);
   for (pn_ctx::IdRing *r : {&c->ids, &c->act.ids})
     for (auto &sl : r->slot) { if (sl.h) hipHostFree(sl.h); if (sl.ev) hipEventDestroy(sl.ev); }
-  if (c->weights) {
-    std::lock_guard<std::mutex> lk(g_weights_mu);
-    if (--c->weights->refs == 0) {
-      for (void *p : c->weights->allocs) hipFree(p);
-      g_weights.erase(c->weights_key);
-      delete c->weights;
-    }
-  }
+  weights_release(c);
   if (c->own_stream) hipStreamDestroy(c->stream);
   delete c;
 }
 
 extern "C" pn_ctx *pn_ctx_create(const pn_model *model, int device, int n_streams, int nn_mode, void *hip_stream) {
   return ctx_create(model, device, n_streams, nn_mode, hip_stream, true, NULL);
-}
-
-// Biases + weights of `model` on the context's device in the layout `nn_mode` reads: STRICT the nnet_data.h arrays as they
-// are, the MFMA modes re-packed tile orders (pn_pack.cpp, pn_nn_x3.hip).  Returns NULL (pn_set_error) on failure.
-static SharedWeights *build_weights(pn_ctx *c, const pn_model *model, int nn_mode, int narrow) {
-  SharedWeights *w = new SharedWeights();
-  memset(w->L, 0, sizeof(w->L));
-  for (int li = 0; li < PN_NLAYERS; li++) {
-    const PnLayerHost &H = model->L[li];
-    size_t nb, nw, nr;
-    pn_layer_floats(H.kind, H.nin, H.nn, H.ks, &nb, &nw, &nr);
-    if (upload_w(c, w, &w->L[li].bias, H.bias, nb)) goto fail_w;
-    if (nn_mode == PN_NN_STRICT) {
-      if (upload_w(c, w, &w->L[li].w, H.w, nw)) goto fail_w;
-      if (nr && upload_w(c, w, &w->L[li].rw, H.rw, nr)) goto fail_w;
-    } else {
-      const int K = H.nin * H.ks, ncols = H.nn * (H.kind == PN_KIND_GRU ? 3 : 1);
-      const int k_alloc = (li == PN_L_FC) ? PN_FEAT_STRIDE : K;   // fc sweeps the zero-padded feature panel
-      const int ctr = H.kind == PN_KIND_GRU ? 1 : pn_dense_nt(H.nn);
-      if ((nn_mode == PN_NN_MFMA_X3 || nn_mode == PN_NN_MFMA_F16) && x3_layer(li)) {   // conv1, conv2, the GRUs and fc_gb; fc and fc_rb (K = 70 / 128) stay fp32 below
-        const int np = nn_mode == PN_NN_MFMA_X3 ? 2 : 1;         // operand planes: hi + lo (split precision) or hi only (fp16 operands)
-        const int ctx3 = H.kind == PN_KIND_GRU ? 1 : pn_dense_x3_nt(H.nn);
-        std::vector<uint16_t> packed(pn_packed_halfs_x3(K, ncols, ctx3, np));
-        if (pn_pack_weights_x3(H.w, K, K, ncols, ctx3, np, packed.data())) { pn_set_error("layer %d has a weight outside the fp16 range: the fp16-operand and split-precision modes cannot represent it", li); goto fail_w; }
-        if (upload_w(c, w, &w->L[li].wp, (const float *)packed.data(), packed.size() / 2)) goto fail_w;
-        if (hipStreamSynchronize(c->stream) != hipSuccess) goto fail_w;   // `packed` dies at scope end
-        if (nr) {
-          std::vector<uint16_t> rp(pn_packed_halfs_x3(H.nn, ncols, 1, np));
-          if (pn_pack_weights_x3(H.rw, H.nn, H.nn, ncols, 1, np, rp.data())) { pn_set_error("layer %d has a recurrent weight outside the fp16 range", li); goto fail_w; }
-          if (upload_w(c, w, &w->L[li].rwp, (const float *)rp.data(), rp.size() / 2)) goto fail_w;
-          if (hipStreamSynchronize(c->stream) != hipSuccess) goto fail_w;
-        }
-      } else {
-        std::vector<float> packed(pn_packed_floats(k_alloc, ncols, ctr));
-        pn_pack_weights(H.w, K, k_alloc, ncols, ctr, packed.data());
-        if (upload_w(c, w, &w->L[li].wp, packed.data(), packed.size())) goto fail_w;
-        if (hipStreamSynchronize(c->stream) != hipSuccess) goto fail_w;   // `packed` dies at scope end
-        if ((narrow == 1 || (narrow == 2 && li == PN_L_FC_GB)) && H.kind == PN_KIND_DENSE && ncols <= 48 && K % 128 == 0) {     // fc_gb, fc_rb (n48: fc_gb only)
-          std::vector<float> pq(pn_packed_floats_n16(K, ncols));
-          pn_pack_weights_n16(H.w, K, ncols, pq.data());
-          if (upload_w(c, w, &w->L[li].wq, pq.data(), pq.size())) goto fail_w;
-          if (hipStreamSynchronize(c->stream) != hipSuccess) goto fail_w;
-        }
-        if (nr) {
-          std::vector<float> rp(pn_packed_floats(H.nn, ncols, 1));
-          pn_pack_weights(H.rw, H.nn, H.nn, ncols, 1, rp.data());
-          if (upload_w(c, w, &w->L[li].rwp, rp.data(), rp.size())) goto fail_w;
-          if (hipStreamSynchronize(c->stream) != hipSuccess) goto fail_w;
-        }
-      }
-    }
-  }
-  if (hipStreamSynchronize(c->stream) != hipSuccess) { pn_set_error("weight upload failed"); goto fail_w; }
-  return w;
-fail_w:
-  hipStreamSynchronize(c->stream);
-  for (void *p : w->allocs) hipFree(p);
-  delete w;
-  return NULL;
 }
 
 // plan: NULL = pn_plan_for(n_streams, nn_mode) (the public behaviour); the self-tests' temporary contexts run the SAME families
@@ -308,7 +123,8 @@ static pn_ctx *ctx_create(const pn_model *model, int device, int n_streams, int 
     int rc = pn_build_tables(ht);
     if (!rc) rc = dev_alloc(c, (void **)&c->tables, sizeof(PnTables), false);
     if (!rc && hipMemcpyAsync(c->tables, ht, sizeof(PnTables), hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = -1;
-    if (!rc) rc = upload(c, &c->tansig, ht->tansig, 208);
+    if (!rc) rc = dev_alloc(c, (void **)&c->tansig, sizeof(ht->tansig), false);
+    if (!rc && hipMemcpyAsync(c->tansig, ht->tansig, sizeof(ht->tansig), hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = -1;
     hipStreamSynchronize(c->stream);
     delete ht;
     if (rc) goto fail;
@@ -323,36 +139,14 @@ static pn_ctx *ctx_create(const pn_model *model, int device, int n_streams, int 
   // operand shadows: of the shadow-operand modes (1 half per element: fp16 operands; hi + lo planes: split precision), and of the
   // direct-operand family (fp32 fragments), which keeps its dense layers on the batch kernels: no shadows of the conv FIFOs
   for (int e = 0; e < PN_ST_COUNT; e++)
-    if (pn_kState[e].shadow != PN_SH_NONE && (nn_mode == PN_NN_MFMA_F16 || nn_mode == PN_NN_MFMA_X3 || (c->plan.direct && pn_kState[e].shadow == PN_SH_MODES_DIRECT)))
-      DEV_ALLOC(c->st[e].sh, shadow_halfs_per_element(c) * c->st[e].words, false);
+    if (pn_state_shadowed(e, c->plan, nn_mode)) DEV_ALLOC(c->st[e].sh, shadow_halfs_per_element(c) * c->st[e].words, false);
   c->hist = c->st[PN_ST_HIST].p; c->synth = c->st[PN_ST_SYNTH].p; c->last_gain = c->st[PN_ST_LAST_GAIN].p; c->feat = c->st[PN_ST_FEAT].p; c->gr = c->st[PN_ST_GR].p;
   c->eyring = c->st[PN_ST_EYRING].p; c->yring = (float2 *)c->st[PN_ST_YRING].p; c->Ps = (float2 *)c->st[PN_ST_PS].p; c->last_period = (int *)c->st[PN_ST_LAST_PERIOD].p; c->silence = (int *)c->st[PN_ST_SILENCE].p;
   DEV_ALLOC(c->io_in, B * PN_FRAME, false);
   DEV_ALLOC(c->io_out, B * PN_FRAME, false);
   if (zero_state(c)) goto fail;
   for (int li = 0; li < PN_NLAYERS; li++) { c->geom[li] = model->L[li]; c->geom[li].bias = c->geom[li].w = c->geom[li].rw = NULL; }
-  {   // the device copy of the weights: shared with every other context of this model content on this device in this mode
-    std::array<unsigned char, 32> dig;
-    memcpy(dig.data(), model->sha256, 32);
-    c->weights_key = std::make_tuple(dig, model->n_floats, device, nn_mode, c->plan.narrow);
-    std::lock_guard<std::mutex> build_lk(g_weights_build_mu[device & 15]);   // one build per device at a time; the map lock is never held across a build
-    SharedWeights *hit = NULL;
-    {
-      std::lock_guard<std::mutex> lk(g_weights_mu);
-      auto it = g_weights.find(c->weights_key);
-      if (it != g_weights.end()) { hit = it->second; hit->refs++; }
-    }
-    if (hit) { c->weights = hit; c->weights_were_cached = true; }
-    else {
-      SharedWeights *w = build_weights(c, model, nn_mode, c->plan.narrow);
-      if (!w) goto fail;
-      w->refs = 1;
-      c->weights = w;
-      std::lock_guard<std::mutex> lk(g_weights_mu);
-      g_weights[c->weights_key] = w;
-    }
-    memcpy(c->L, c->weights->L, sizeof(c->L));
-  }
+  if (weights_acquire(c, model)) goto fail;
   if (hipStreamSynchronize(c->stream) != hipSuccess) { pn_set_error("initial upload failed"); goto fail; }
   if (selftest && (nn_mode == PN_NN_MFMA_X3 || nn_mode == PN_NN_MFMA_F16)) {       // (not for the self-tests' temporary contexts)
     const char *e = getenv("PERCEPNET_X3_SATCOUNT");
@@ -432,10 +226,10 @@ extern "C" int pn_ctx_n_streams(const pn_ctx *c) { return c ? c->B : -1; }
 extern "C" int64_t pn_ctx_frames_done(const pn_ctx *c) { return c ? c->t : -1; }
 // state (+ tables) of this context, plus the weights if this context created their device copy (a context that found them
 // in the cache adds nothing: the copy is shared)
-extern "C" size_t pn_ctx_device_bytes(const pn_ctx *c) { return c ? c->bytes + ((c->weights && !c->weights_were_cached) ? c->weights->bytes : 0) : 0; }
+extern "C" size_t pn_ctx_device_bytes(const pn_ctx *c) { return c ? c->bytes + ((c->weights && !c->weights_were_cached) ? c->weight_bytes : 0) : 0; }
 // bytes of the packed weight copy this context reads, whoever created it: a process's footprint is the sum of
 // pn_ctx_device_bytes over its contexts plus every DISTINCT shared copy that no live context reports as its own
-extern "C" size_t pn_ctx_weight_bytes(const pn_ctx *c) { return (c && c->weights) ? c->weights->bytes : 0; }
+extern "C" size_t pn_ctx_weight_bytes(const pn_ctx *c) { return (c && c->weights) ? c->weight_bytes : 0; }
 extern "C" int pn_ctx_describe(const pn_ctx *c, char *buf, size_t n) {
   if (!c || !buf || !n) return -1;
   const int f = pn_plan_describe(c->plan, c->nn_mode, buf, n);
@@ -453,22 +247,6 @@ extern "C" int pn_ctx_describe(const pn_ctx *c, char *buf, size_t n) {
 }
 extern "C" int pn_ctx_synchronize(pn_ctx *c) { if (!c) return -1; PN_ON_DEVICE(c); PN_HIP_CHECK(hipStreamSynchronize(c->stream)); return 0; }
 
-// ---- profiling ------------------------------------------------------------------------------------------
-struct Scope {
-  pn_ctx *c; int fam; hipEvent_t a, b; bool on; hipStream_t st;      // st: the stream the bracketed launches go to (a row-range chain's own)
-  Scope(pn_ctx *c_, int fam_, hipStream_t st_ = nullptr) : c(c_), fam(fam_), on(c_->profiling), st(st_ ? st_ : c_->stream) {
-    if (on) {
-      auto take = [&](hipEvent_t &e) { if (c->event_pool.empty()) hipEventCreate(&e); else { e = c->event_pool.back(); c->event_pool.pop_back(); } };
-      take(a); take(b); hipEventRecord(a, st);
-    }
-  }
-  ~Scope() {
-    if (on) { hipEventRecord(b, st); c->events.push_back({fam, a, b}); }
-    // debugging aid: PERCEPNET_SYNC_EACH=<bit mask over kernel families, -1 = all>: host sync after those launches
-    static const long sync_mask = getenv("PERCEPNET_SYNC_EACH") ? strtol(getenv("PERCEPNET_SYNC_EACH"), NULL, 0) : 0;
-    if (sync_mask & (1L << fam)) hipStreamSynchronize(st);
-  }
-};
 
 static int flush_events(pn_ctx *c) {
   PN_HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -508,157 +286,6 @@ extern "C" int pn_ctx_reset_profile(pn_ctx *c) {
   return 0;
 }
 
-// ---- the per-frame launch sequence -----------------------------------------------------------------------
-static PnSegs seg1(const float *p, int ld, int width) { PnSegs s; memset(&s, 0, sizeof(s)); s.p[0] = p; s.ld[0] = ld; s.width[0] = width; s.n = 1; return s; }
-
-// compute_rnn (rnn.cpp:42-81) for all streams; features in c->feat, result in c->gr
-// fp16 shadow of an fp32 activation pointer (same element index in the twin buffer)
-static uint16_t *shadow(pn_ctx *c, const float *p) {
-  for (const pn_ctx::StateBuf &b : c->st) if (b.sh && p >= b.p && p < b.p + b.words) return b.sh + shadow_halfs_per_element(c) * (size_t)(p - b.p);
-  return NULL;
-}
-static PnSegs shadow_segs(pn_ctx *c, const PnSegs &A) {
-  PnSegs H = A;
-  for (int j = 0; j < A.n; j++) H.p[j] = reinterpret_cast<const float *>(shadow(c, A.p[j]));
-  return H;
-}
-
-// Returns 0, or -1 when a launcher refused its geometry (pn_set_error names it): the refused layer is not launched (later
-// layers of the frame may be — their results are never reported) and the caller fails the frame.
-// The ten layers for the rows [r0, r0 + nrows) of the batch on stream `st`.  Every activation buffer is row-major, so a row range
-// is the same launch with every base pointer moved down by r0 rows.  The kernel families are c->plan's.  The shadow-operand
-// and STRICT modes always run the whole batch.
-static int launch_rnn_rows(pn_ctx *c, size_t r0, size_t nrows, hipStream_t st) {
-  const size_t Bp = c->Bp; const int strict = c->nn_mode == PN_NN_STRICT;
-  const int B = (int)nrows;
-  // x3: the layers that run on the fp16 matrix cores from operand shadows — split precision (hi + lo planes) or fp16 operands (hi only)
-  const bool x3 = c->nn_mode == PN_NN_MFMA_X3 || c->nn_mode == PN_NN_MFMA_F16;
-  const int np = c->nn_mode == PN_NN_MFMA_X3 ? 2 : 1;
-  const int small = c->plan.small, small_gru = c->plan.small_gru, rg = c->plan.rg;
-  const bool dm = c->plan.direct != 0;   // the GRU steps take their activations straight from fragment-order fp32 shadows (pn_nn_d.hip): written by conv2
-                                         // (batch kernel, second output) and by the GRU steps themselves; every dense layer stays on the batch kernels
-  const float *tab = c->tansig;
-  int rc = 0;
-  // every chain's launches are bracketed on the stream they go to (pn_ctx_kernel_times averages over all launches of a family;
-  // with N chains the launches of one family overlap in time: bench.py prices the CONCURRENT launches together)
-  struct MaybeScope { Scope s; MaybeScope(pn_ctx *c_, int fam, hipStream_t st_) : s(c_, fam, st_) {} };
-  // conv FIFOs: panels 0 .. ks - 2 are the live entries, oldest first, panel ks - 1 the slot this step writes; GRU pairs: 0 read, 1 written
-  float *c1new = state_at(c, PN_ST_C1RING, 4, r0), *c2new = state_at(c, PN_ST_C2RING, 2, r0);
-  float *c2out = state_at(c, PN_ST_C2OUT, 0, r0), *gr = c->gr + r0 * 68;
-  { MaybeScope sc(c, KF_FC, st);
-    PnSegs A = seg1(c->feat + r0 * PN_FEAT_STRIDE, PN_FEAT_STRIDE, strict ? PN_NFEAT : PN_FEAT_STRIDE);   // cols 70..127 are zero
-    if (c->inject_bad_launch && !strict) A.width[0] = 96;   // test hook: three K-tiles, which every MFMA dense launcher refuses
-    rc |= pn_launch_dense(st, strict, A, c->L[PN_L_FC].w, c->L[PN_L_FC].wp, c->L[PN_L_FC].bias, 128, c->geom[PN_L_FC].act, tab, c1new, 128, B, small);
-    if (x3) rc |= pn_launch_split_x3(st, c1new, 128, 128, shadow(c, c1new), (int)Bp, np); }   // fc runs in fp32 (70 inputs); its output enters the shadow-operand layers
-  { MaybeScope sc(c, KF_CONV1, st);   // causal conv as dense over [4 previous fc outputs | current] (nnet.cpp:182-200)
-    PnSegs A; memset(&A, 0, sizeof(A)); A.n = 5;
-    for (int j = 0; j < 5; j++) { A.p[j] = state_at(c, PN_ST_C1RING, j, r0); A.ld[j] = 128; A.width[j] = 128; }
-    if (x3) rc |= pn_launch_dense_x3(st, shadow_segs(c, A), c->L[PN_L_CONV1].wp, c->L[PN_L_CONV1].bias, 512, c->geom[PN_L_CONV1].act, tab, c2new, 512, shadow(c, c2new), 16, B, rg, np);
-    else rc |= pn_launch_dense(st, strict, A, c->L[PN_L_CONV1].w, c->L[PN_L_CONV1].wp, c->L[PN_L_CONV1].bias, 512, c->geom[PN_L_CONV1].act, tab, c2new, 512, B, small); }
-  { MaybeScope sc(c, KF_CONV2, st);
-    PnSegs A; memset(&A, 0, sizeof(A)); A.n = 3;
-    for (int j = 0; j < 3; j++) { A.p[j] = state_at(c, PN_ST_C2RING, j, r0); A.ld[j] = 512; A.width[j] = 512; }
-    if (x3) rc |= pn_launch_dense_x3(st, shadow_segs(c, A), c->L[PN_L_CONV2].wp, c->L[PN_L_CONV2].bias, 512, c->geom[PN_L_CONV2].act, tab, c2out, 512, shadow(c, c2out), 16, B, rg, np);
-    else if (dm) rc |= pn_launch_dense(st, 0, A, NULL, c->L[PN_L_CONV2].wp, c->L[PN_L_CONV2].bias, 512, c->geom[PN_L_CONV2].act, tab, c2out, 512, B, 0, shadow(c, c2out), 16);   // + the shadow the GRUs read
-    else rc |= pn_launch_dense(st, strict, A, c->L[PN_L_CONV2].w, c->L[PN_L_CONV2].wp, c->L[PN_L_CONV2].bias, 512, c->geom[PN_L_CONV2].act, tab, c2out, 512, B, small); }
-  const float *x = c2out;
-  for (int i = 0; i < 4 && !rc; i++) {    // gru1 -> gru2 -> gru3 -> gru_gb, each fed the UPDATED state of its predecessor
-    MaybeScope sc(c, KF_GRU512, st);
-    const int li = PN_L_GRU1 + i;
-    float *ho = state_at(c, PN_ST_GRU1 + i, 0, r0), *hn = state_at(c, PN_ST_GRU1 + i, 1, r0);
-    PnSegs X = seg1(x, 512, 512);
-    if (x3) rc |= pn_launch_gru_x3(st, shadow_segs(c, X), ho, shadow(c, ho), c->L[li].wp, c->L[li].rwp, c->L[li].bias, 512, c->geom[li].act, tab, hn, shadow(c, hn), B, rg, np);
-    else if (dm) rc |= pn_launch_gru_d(st, shadow_segs(c, X), ho, shadow(c, ho), c->L[li].wp, c->L[li].rwp, c->L[li].bias, 512, c->geom[li].act, tab, hn, shadow(c, hn), B, rg);
-    else rc |= pn_launch_gru(st, strict, X, ho, c->L[li].w, c->L[li].rw, c->L[li].wp, c->L[li].rwp, c->L[li].bias, 512, c->geom[li].act, tab, hn, B, small_gru);
-    x = hn;
-  }
-  const float *g1 = state_at(c, PN_ST_GRU1, 1, r0), *g2 = state_at(c, PN_ST_GRU2, 1, r0), *g3 = state_at(c, PN_ST_GRU3, 1, r0), *gb = state_at(c, PN_ST_GRU_GB, 1, r0);
-  float *rbo = state_at(c, PN_ST_RB, 0, r0), *rbn = state_at(c, PN_ST_RB, 1, r0);
-  { MaybeScope sc(c, KF_GRU_RB, st);   // input = [gru3 | conv2 out] (rnn.cpp:67-69)
-    PnSegs X; memset(&X, 0, sizeof(X)); X.n = 2;
-    X.p[0] = g3; X.ld[0] = 512; X.width[0] = 512; X.p[1] = c2out; X.ld[1] = 512; X.width[1] = 512;
-    const int li = PN_L_GRU_RB;
-    if (x3) rc |= pn_launch_gru_x3(st, shadow_segs(c, X), rbo, shadow(c, rbo), c->L[li].wp, c->L[li].rwp, c->L[li].bias, 128, c->geom[li].act, tab, rbn, shadow(c, rbn), B, rg, np);
-    else if (dm) rc |= pn_launch_gru_d(st, shadow_segs(c, X), rbo, shadow(c, rbo), c->L[li].wp, c->L[li].rwp, c->L[li].bias, 128, c->geom[li].act, tab, rbn, shadow(c, rbn), B, rg);
-    else rc |= pn_launch_gru(st, strict, X, rbo, c->L[li].w, c->L[li].rw, c->L[li].wp, c->L[li].rwp, c->L[li].bias, 128, c->geom[li].act, tab, rbn, B, small); }   // gru_rb (1024->128) crosses over with the dense layers
-  { MaybeScope sc(c, KF_FC_GB, st);    // input = [conv2 out | gru1 | gru2 | gru3 | gru_gb] (rnn.cpp:72-77)
-    PnSegs A; memset(&A, 0, sizeof(A)); A.n = 5;
-    const float *ps[5] = {c2out, g1, g2, g3, gb};
-    for (int j = 0; j < 5; j++) { A.p[j] = ps[j]; A.ld[j] = 512; A.width[j] = 512; }
-    if (x3) rc |= pn_launch_dense_x3(st, shadow_segs(c, A), c->L[PN_L_FC_GB].wp, c->L[PN_L_FC_GB].bias, 34, c->geom[PN_L_FC_GB].act, tab, gr, 68, NULL, 0, B, rg, np);
-    else if (c->plan.narrow == 2) rc |= pn_launch_dense_n48(st, A, c->L[PN_L_FC_GB].wq, c->L[PN_L_FC_GB].bias, 34, c->geom[PN_L_FC_GB].act, tab, gr, 68, B);
-    else if (c->plan.narrow == 1) rc |= pn_launch_dense_n16(st, A, c->L[PN_L_FC_GB].wq, c->L[PN_L_FC_GB].bias, 34, c->geom[PN_L_FC_GB].act, tab, gr, 68, B);
-    else rc |= pn_launch_dense(st, strict, A, c->L[PN_L_FC_GB].w, c->L[PN_L_FC_GB].wp, c->L[PN_L_FC_GB].bias, 34, c->geom[PN_L_FC_GB].act, tab, gr, 68, B, small); }
-  { MaybeScope sc(c, KF_FC_RB, st);
-    PnSegs A = seg1(rbn, 128, 128);
-    if (c->plan.narrow == 1) rc |= pn_launch_dense_n16(st, A, c->L[PN_L_FC_RB].wq, c->L[PN_L_FC_RB].bias, 34, c->geom[PN_L_FC_RB].act, tab, gr + 34, 68, B);
-    else rc |= pn_launch_dense(st, strict, A, c->L[PN_L_FC_RB].w, c->L[PN_L_FC_RB].wp, c->L[PN_L_FC_RB].bias, 34, c->geom[PN_L_FC_RB].act, tab, gr + 34, 68, B, small); }
-  return rc ? -1 : 0;
-}
-
-// compute_rnn for the whole batch.  Large fp32 MFMA contexts run it as ROW-RANGE CHAINS (round 6, round-5 verdict item 3).
-// The batch-GEMM kernels run in rounds of 512 co-resident blocks (two per CU) — 4096 rows of a 512-wide layer, 65 536 rows of a
-// 34-wide one — and on ONE in-order stream every layer pays whole rounds: 65 536 streams = 16 rounds per 512-wide layer, 66 048 = 17
-// (+0.45 ms per frame; the reference has no such step, its cost is per stream: nnet.cpp:120-180), and even an exact fit leaves the
-// ramp and drain of ten launches idle.  No layer mixes rows, so the batch is cut into PN_NN_CHAINS row ranges (multiples of 128
-// rows) whose ten layers are independent chains of the SAME kernels on streams of their own: while one chain drains a layer the
-// blocks of another fill the slots.  One fork (the features are ready) and one join (before the back end) per frame; results
-// are bit-identical by construction (the same launches over sub-ranges of the rows).  The chain count and the shares are
-// pn_plan.h's (measured: profiles/r06_row_chains.log).
-// The first attempts — the rows past the last whole round on the small-batch kernels, in the same stream or beside the body —
-// cost 2-3x the tail's share: a small block holds a block slot for a single latency-bound MFMA chain, and any slot taken from
-// an exactly fitting body pushes that layer into an extra round.
-// Every extra chain's stream must have a HARDWARE queue of its own: HIP multiplexes the streams of one priority over a few queues,
-// and on a queue shared with the context's stream a chain runs in front of the others instead of beside them.  Same remedy as for
-// the copy streams of the pipelined host path: default-priority streams PROBED against the streams they must not share a queue
-// with, a high-priority one as the fallback (pipe_make_stream).
-static int pipe_make_stream(pn_ctx *c, hipStream_t *out, char how, int prio, char fallback, const std::vector<hipStream_t> &others, char *kind);
-// every stream of this context that carries kernels or copies of a frame: a new one must share a hardware queue with none of them
-static std::vector<hipStream_t> busy_streams(const pn_ctx *c) {
-  std::vector<hipStream_t> v{c->stream};
-  for (int k = 1; k < 4; k++) if (c->chain_stream[k]) v.push_back(c->chain_stream[k]);
-  if (c->pipe.h2d) v.push_back(c->pipe.h2d);
-  if (c->pipe.d2h) v.push_back(c->pipe.d2h);
-  return v;
-}
-static int chain_streams_init(pn_ctx *c) {
-  int lo = 0, hi = 0;
-  PN_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-  for (int k = 1; k < c->plan.chains; k++) {
-    if (pipe_make_stream(c, &c->chain_stream[k], 'a', hi, 'h', busy_streams(c), &c->chain_kind[k])) return -1;
-    PN_HIP_CHECK(hipEventCreateWithFlags(&c->chain_join[k], hipEventDisableTiming));
-  }
-  PN_HIP_CHECK(hipEventCreateWithFlags(&c->chain_fork, hipEventDisableTiming));
-  return 0;
-}
-// hipSuccess, or the error recorded as the frame's (pn_set_error) unless an earlier one already is
-static bool chain_ok(hipError_t e, const char *what, int &rc) {
-  if (e == hipSuccess) return true;
-  if (!rc) pn_set_error("%s failed: %s", what, hipGetErrorString(e));
-  rc = -1;
-  return false;
-}
-static int launch_rnn(pn_ctx *c) {
-  const int n = c->plan.chains;
-  if (n <= 1) return launch_rnn_rows(c, 0, c->B, c->stream);
-  const size_t B = c->B, share = pn_plan_share(c->plan, B);
-  PN_HIP_CHECK(hipEventRecord(c->chain_fork, c->stream));                 // the front end's features (and last frame's state) are in place
-  // Once forked, every chain that started is joined back into the context's stream whatever fails after it (a refused launch,
-  // a HIP error): nothing stays unordered.  No chain starts after a failure; the first error is the one returned.
-  int rc = 0;
-  bool started[PN_MAX_CHAINS] = {};
-  for (int k = n - 1; k >= 0 && !rc; k--) {                               // the context's own stream last: the others are already queued
-    const size_t r0 = share * k, nr = r0 >= B ? 0 : (B - r0 < share ? B - r0 : share);
-    if (!nr) continue;
-    hipStream_t st = k ? c->chain_stream[k] : c->stream;
-    if (k && !(started[k] = chain_ok(hipStreamWaitEvent(st, c->chain_fork, 0), "hipStreamWaitEvent(chain, fork)", rc))) break;
-    if (launch_rnn_rows(c, r0, nr, st)) rc = -1;
-  }
-  for (int k = 1; k < n; k++)
-    if (started[k] && chain_ok(hipEventRecord(c->chain_join[k], c->chain_stream[k]), "hipEventRecord(join)", rc))
-      chain_ok(hipStreamWaitEvent(c->stream, c->chain_join[k], 0), "hipStreamWaitEvent(stream, join)", rc);
-  return rc;
-}
 
 // Known-answer self-test of the MFMA network kernels (PERCEPNET_SELFTEST=0 skips it).
 // The MFMA paths (fp32 and fp16 operands) depend on the compiler's wait-state insertion and on pinned instruction
@@ -754,7 +381,6 @@ static int nn_selftest(pn_ctx *c) {
   g_selftest_done[key] = 0;
   return 0;
 }
-
 
 // Known-answer self-test of the DSP kernels, the counterpart of nn_selftest (PERCEPNET_SELFTEST=0 skips both).
 // The first context of every (device, front-end family) in a process runs a fixed integer-generated waveform
@@ -1024,7 +650,7 @@ static int pipe_streams_share(pn_ctx *c, hipStream_t busy, hipStream_t cand, voi
 // One copy stream.  how: 'n' default priority unprobed, 'h' / 'l' a priority stream, 'a' (the default) a default-priority
 // stream that shares its queue with none of `others` — up to 6 candidates (the rejected ones stay alive until the end, so
 // that the runtime's least-used-queue choice moves on), else the priority stream `fallback`.
-static int pipe_make_stream(pn_ctx *c, hipStream_t *out, char how, int prio, char fallback, const std::vector<hipStream_t> &others, char *kind) {
+int pipe_make_stream(pn_ctx *c, hipStream_t *out, char how, int prio, char fallback, const std::vector<hipStream_t> &others, char *kind) {
   if (how == 'h' || how == 'l') {
     int lo = 0, hi = 0;
     PN_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
@@ -1123,8 +749,6 @@ static int pipe_drain(pn_ctx *c) {
   return 0;
 }
 
-static int process_active(pn_ctx *c, const void *d_in, void *d_out, float *d_gr, int is_i16, const int32_t *ids, int n);
-static int active_check(pn_ctx *c, const int32_t *ids, int n);
 // ids != NULL or n >= 0 with active = true: only the listed streams advance (pn_submit_host_*_active)
 static int submit_host(pn_ctx *c, const void *h_in, void *h_out, float *h_gr, int is_i16, bool active = false, const int32_t *ids = NULL, int n = 0) {
   if (!c || !h_in || !h_out) { pn_set_error("NULL argument"); return -1; }
@@ -1267,10 +891,9 @@ enum { PN_ST_NNET = 7 };
 static int rnn_state_copy(pn_ctx *c, bool to_device, float *const host[PN_ST_NNET]) {
   PN_ON_DEVICE(c);
   if (pipe_drain(c)) return -1;
-  // fp16-operand and split-precision modes: the fp32 buffers are complete (every layer stores fp32 next to its operand
-  // shadow), so a store reads them as in the fp32 modes and a load re-derives the shadows from the loaded fp32 values
-  const bool x3 = c->nn_mode == PN_NN_MFMA_X3 && to_device, f16 = c->nn_mode == PN_NN_MFMA_F16 && to_device;
-  const size_t B = c->B; const int Bp = (int)c->Bp;
+  // fp16-operand, split-precision and direct-operand contexts: the fp32 buffers are complete (every layer stores fp32 next to its
+  // operand shadow), so a store reads them as in the plain fp32 mode and a load re-derives the shadows from the loaded fp32 values
+  const size_t B = c->B;
   int split_rc = 0;
   for (int e = PN_ST_C1RING, i = 0; e <= PN_ST_RB; e++) {
     const PnStateEntry &L = pn_kState[e];
@@ -1281,9 +904,7 @@ static int rnn_state_copy(pn_ctx *c, bool to_device, float *const host[PN_ST_NNE
       float *d = state_at(c, e, j), *h = hrow + j * L.cols;
       PN_HIP_CHECK(to_device ? hipMemcpy2DAsync(d, dp, h, hp, w, B, hipMemcpyHostToDevice, c->stream)
                              : hipMemcpy2DAsync(h, hp, d, dp, w, B, hipMemcpyDeviceToHost, c->stream));
-      if (x3) split_rc |= pn_launch_split_x3(c->stream, d, L.cols, L.cols, shadow(c, d), Bp, 2);
-      if (f16) split_rc |= pn_launch_split_x3(c->stream, d, L.cols, L.cols, shadow(c, d), Bp, 1);
-      if (c->plan.direct && to_device && shadow(c, d)) split_rc |= pn_launch_split_d(c->stream, d, L.cols, L.cols, shadow(c, d), Bp);   // (GRU states; the conv FIFOs have no shadow there)
+      if (to_device) split_rc |= reshadow(c, c->stream, e, d);
     }
   }
   PN_HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -1376,17 +997,9 @@ extern "C" int pn_ctx_import_streams(pn_ctx *c, const int32_t *ids, int n, const
   pn_launch_ss_scatter(c->stream, a, n);
   // operand shadows of the live entries, imported rows only (status 0), in this context's layout: fp16 / hi + lo planes of the
   // conv FIFOs and the GRU / rb states (shadow-operand modes), fp32 fragments of the GRU / rb states (direct-operand family)
-  const bool x3 = c->nn_mode == PN_NN_MFMA_X3 || c->nn_mode == PN_NN_MFMA_F16;
-  const int np = c->nn_mode == PN_NN_MFMA_X3 ? 2 : 1;
   int rc = 0;
   for (int e = PN_ST_C1RING; e <= PN_ST_RB; e++)
-    for (int j = 0; pn_kState[e].cls == PN_CLS_RING && j < pn_kState[e].live; j++) {
-      float *slot = state_at(c, e, j); void *S = shadow(c, slot);
-      const int width = pn_kState[e].cols;
-      if (!S) continue;                                  // no shadow of this buffer in this mode / family
-      if (x3) rc |= pn_launch_split_x3_rows(c->stream, slot, width, width, S, d, d_status, n, np);
-      else if (c->plan.direct) rc |= pn_launch_split_d_rows(c->stream, slot, width, width, S, d, d_status, n);
-    }
+    for (int j = 0; pn_kState[e].cls == PN_CLS_RING && j < pn_kState[e].live; j++) rc |= reshadow(c, c->stream, e, state_at(c, e, j), d, d_status, n);
   PN_HIP_CHECK(hipGetLastError());
   return rc ? -1 : 0;
 }

@@ -1,7 +1,7 @@
-// Kernel launchers shared by the host files (pn_context.cpp, pn_featgen.cpp).
+// Kernel launchers shared by the host files (pn_context.cpp, pn_network.cpp, pn_featgen.cpp).
 #pragma once
 #include "pn_common.h"
-#include "pn_state_layout.h"
+#include "pn_network.h"       // PnSegs, and through it pn_state_layout.h
 
 // grid_cap (last argument of every DSP launcher): test hook of the create-time DSP self-test (pn_context.cpp: dsp_selftest).
 // When > 0 the launcher caps its grid at this many blocks, so that a 40-stream batch walks several grid-stride rounds of ONE
@@ -9,7 +9,6 @@
 // the temporary self-test context only (pn_ctx::dsp_grid_cap): no other context, thread or device ever sees it.  0 = off.
 
 // ---- kernels / helpers implemented in pn_dsp.hip and pn_nn.hip -----------------------------------
-struct PnSegs { const float *p[5]; int ld[5]; int width[5]; int n; };
 // in: stream s's 480 samples at in + s*in_stride; i16_scale: 1/32768 (CLI, main.cpp:34) or 1 (training binary,
 // denoise.cpp:41,697); aux: optional [n_streams][PN_AUX_STRIDE] side outputs for the training-feature path
 void pn_launch_frontend(hipStream_t st, const PnTables *T, int n_streams, int64_t frame, const void *in,
@@ -82,9 +81,6 @@ void pn_launch_backend(hipStream_t st, const PnTables *T, int n_streams, const f
                        const float *gr, const float *ex_postfilter /* NULL = off */, const int *silence, float *synth_mem,
                        void *out, int out_is_i16, int grid_cap,
                        const float2 *lam_mu /* [n_streams] (lam, mu) of the attenuation limit; NULL = no stream limited */);
-size_t pn_packed_floats(int k_alloc, int ncols, int ct_round);
-void pn_pack_weights(const float *W, int K, int k_alloc, int ncols, int ct_round, float *Wp);
-int pn_dense_nt(int N);
 // split-precision variant (pn_nn_x3.hip): operands as fp16 hi/lo planes in fragment order; panels of A / h_oldS / outS /
 // h_newS are the uint4* shadows (carried as float* in PnSegs), width = logical columns (multiple of 32)
 size_t pn_packed_halfs_x3(int k_alloc, int ncols, int ct_round, int np /* planes: 2 = hi+lo (split precision), 1 = fp16 operands */);
@@ -106,8 +102,6 @@ int pn_launch_gru_d(hipStream_t st, const PnSegs &X, const float *h_old, const v
                     int n_rows, int rg);
 int pn_launch_split_d(hipStream_t st, const float *src, int ld, int width, void *S, int n_rows);
 // narrow layers (N <= 48) of small-batch contexts: 16x16x4 MFMA tiles, one wave per (16 rows, 16 columns) (pn_nn_small.hip)
-size_t pn_packed_floats_n16(int K, int ncols);
-void pn_pack_weights_n16(const float *W, int K, int ncols, float *Wq);
 int pn_launch_dense_n16(hipStream_t st, const PnSegs &A, const float *Wq, const float *bias, int N, int act,
                          const float *tansig, float *out, int ldo, int n_rows);
 // the batch form for large batches (pn_nn_n48.hip): 128-row blocks x 48 columns of 16x16x4 tiles, the same packed weights Wq

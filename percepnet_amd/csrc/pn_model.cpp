@@ -18,11 +18,6 @@ extern "C" const char *pn_last_error(void) { return g_err; }
 extern "C" const char *pn_version(void) { return "percepnet_hip 0.2 (gfx950)"; }
 
 // ---- models -------------------------------------------------------------------------------------------
-const PnGeom pn_kGeom[PN_NLAYERS] = {
-  {PN_KIND_DENSE, 70, 128, 1}, {PN_KIND_CONV1D, 128, 512, 5}, {PN_KIND_CONV1D, 512, 512, 3},
-  {PN_KIND_GRU, 512, 512, 1}, {PN_KIND_GRU, 512, 512, 1}, {PN_KIND_GRU, 512, 512, 1}, {PN_KIND_GRU, 512, 512, 1},
-  {PN_KIND_GRU, 1024, 128, 1}, {PN_KIND_DENSE, 2560, 34, 1}, {PN_KIND_DENSE, 128, 34, 1}};
-
 size_t pn_layer_floats(int kind, int nin, int nn, int ks, size_t *nb, size_t *nw, size_t *nr) {
   *nb = kind == PN_KIND_GRU ? 6 * (size_t)nn : (size_t)nn;
   *nw = (size_t)nin * ks * nn * (kind == PN_KIND_GRU ? 3 : 1);
@@ -41,7 +36,7 @@ static int check_geometry(int li, int kind, int nin, int nn, int ks) {
 
 
 
-// ---- SHA-256 (FIPS 180-4) of a model's content: the key of the per-device cache of packed weights (pn_context.cpp).  A strong
+// ---- SHA-256 (FIPS 180-4) of a model's content: the key of the per-device cache of packed weights (pn_network.cpp).  A strong
 // digest, computed ONCE per model, instead of two 64-bit hashes plus a retained 32 MB host copy that every cache hit was compared
 // against byte for byte under the build lock (advisor, round 5): a PNW1 file cannot be crafted to share another model's entry.
 namespace {

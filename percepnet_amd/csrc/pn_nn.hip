@@ -600,7 +600,7 @@ int pn_launch_dense(hipStream_t st, int strict, const PnSegs &A, const float *W,
   const int tps = (A.width[0] + 31) / 32, KT = tps * A.n;   // equal-width panels
   const int NT = pn_dense_nt(N);
   // the half-tile pipeline consumes K-tiles in pairs: every layer of the PercepNet topology (the only geometry a
-  // context accepts, pn_context.cpp:check_geometry) has an even number of them (4, 20, 48, 80, 4)
+  // context accepts, pn_model.cpp:check_geometry) has an even number of them (4, 20, 48, 80, 4)
   if (pn_check_dense_geometry("pn_launch_dense", A.n, A.width, 0)) return -1;
   const int n_cblocks = pn_ct_padded(N, NT) / NT;
   const int n_mtiles = (n_rows + BM - 1) / BM;

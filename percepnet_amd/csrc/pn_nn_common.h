@@ -2,19 +2,12 @@
 #pragma once
 #include "pn_launch_check.h"
 #include "pn_common.h"
+#include "pn_network.h"       // PnSegs
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 #define BM 128            // streams per block tile
 #define NN_THREADS 256
-
-struct PnSegs {           // A operand = concatenation along K of up to 5 row-major panels
-  const float *p[5];
-  int ld[5];              // row stride (floats)
-  int width[5];           // valid columns; the MFMA path requires every panel to be readable (and
-                          // zero) up to the next multiple of 32 and all panels to be equally wide
-  int n;
-};
 
 enum { ACT_LINEAR = 0, ACT_SIGMOID = 1, ACT_TANH = 2, ACT_RELU = 3 };
 

@@ -64,7 +64,7 @@ extern "C" PN_EXPORT int pn_debug_check_launch(int kind, int n_panels, int width
 }
 
 // ---- the kernel families of a context without a GPU (include/percepnet_hip.h: pn_debug_plan) -------------------------------
-#include "pn_plan.h"
+#include "pn_network.h"
 extern "C" PN_EXPORT int pn_debug_plan(int n_streams, int nn_mode, char *buf, size_t n) {
   if (!buf || !n || n_streams < 1) { pn_set_error("pn_debug_plan: bad argument"); return -1; }
   if (nn_mode != PN_NN_MFMA && nn_mode != PN_NN_STRICT && nn_mode != PN_NN_MFMA_F16 && nn_mode != PN_NN_MFMA_X3) { pn_set_error("bad nn_mode %d", nn_mode); return -1; }

@@ -2,7 +2,6 @@
 // regime map can be checked without a GPU (pn_debug_plan, tests/test_plan_host.py).  pn_plan_for is the only reader of the
 // family overrides; a context keeps the plan it was created with whatever the environment does afterwards.
 #pragma once
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include "../../include/percepnet_hip.h"
@@ -92,20 +91,4 @@ static inline size_t pn_plan_tile(const PnPlan &p) { return p.direct ? 128 * (si
 static inline size_t pn_plan_share(const PnPlan &p, size_t n_streams) {
   const size_t k = p.chains, tile = pn_plan_tile(p);
   return k > 1 ? ((n_streams + k - 1) / k + tile - 1) / tile * tile : 0;
-}
-
-// The family part of pn_ctx_describe, "nn=... frontend=...": snprintf's result
-static inline int pn_plan_describe(const PnPlan &p, int nn_mode, char *buf, size_t n) {
-  const char *nn = nn_mode == PN_NN_STRICT ? "strict" : (nn_mode == PN_NN_MFMA_F16 ? "mfma_f16" : (nn_mode == PN_NN_MFMA_X3 ? "mfma_x3" : "mfma_f32"));
-  const bool x3 = nn_mode == PN_NN_MFMA_X3 || nn_mode == PN_NN_MFMA_F16;      // shadow-operand kernels (pn_nn_x3.hip)
-  const bool fam = nn_mode == PN_NN_MFMA || x3;      // the small-batch family exists for the fp32 MFMA kernels only (in the shadow-operand modes: fc, fc_rb)
-  // rows per wave (conv1, conv2, GRUs, fc_gb); rg 3 = 64 rows with the GRUs on the paired-phase kernel (pn_gru_x3p_kernel)
-  const char *xk = nn_mode == PN_NN_MFMA_X3 ? (p.rg >= 2 ? "x3_rows64" : "x3_rows32") : (p.rg >= 2 ? "f16_rows64" : "f16_rows32");
-  const char *xg = nn_mode == PN_NN_MFMA_X3 ? (p.rg == 3 ? "x3_rows64_paired" : xk) : (p.rg == 3 ? "f16_rows64_paired" : xk);
-  const char *dk = p.rg >= 2 ? "direct_rows64" : "direct_rows32";      // direct-operand fp32 GRU kernels (pn_nn_d.hip); the dense layers stay "batch"
-  const char *dense = fam && p.small ? "small" : "batch";
-  return snprintf(buf, n, "nn=%s dense=%s gru=%s gru_rb=%s narrow=%s frontend=%s", nn, x3 ? xk : dense,
-                  x3 ? xg : (p.direct ? dk : (fam && p.small_gru ? "small" : "batch")), x3 ? xg : (p.direct ? dk : dense),
-                  x3 ? (p.narrow == 1 ? "fc_gb:x3+fc_rb:n16" : "fc_gb:x3+fc_rb:fp32") : (p.narrow == 2 ? "fc_gb:n48+fc_rb:batch" : (p.narrow == 1 ? "n16" : dense)),
-                  p.fe == FE_SPLIT ? "split" : (p.fe == FE_MONO_G2 ? "g2" : "g4"));
 }

@@ -1,13 +1,14 @@
 // CPU-only sanitizer harness (tests/test_hardening.py builds it with g++ -fsanitize=address,undefined -DPN_NO_HIP): the
 // HIP-free host pieces of libpercepnet_hip — the PNW1 / RNNModel parsers (pn_model.cpp), the table builder (pn_tables.cpp),
 // the weight packers (pn_pack.cpp) and the CLI helpers (pn_cli_util.h) — driven with valid, truncated, oversized and
-// corrupted inputs; and the table of a context's per-stream state (pn_state_layout.h): record offsets, ring phases, classes.
+// corrupted inputs; the table of a context's per-stream state (pn_state_layout.h): record offsets, ring phases, classes; and the
+// table of the network's layers (pn_network.h): kernel, weight format, shadows and launch geometry of every layer under every plan.
 // Any out-of-bounds access, overflow or leak-free violation aborts; the process prints "ok" and exits 0.
 #include "../../percepnet_amd/csrc/pn_model.cpp"
 #include "../../percepnet_amd/csrc/pn_pack.cpp"
 #include "../../percepnet_amd/csrc/pn_tables.cpp"
 #include "../../percepnet_amd/csrc/pn_cli_util.h"
-#include "../../percepnet_amd/csrc/pn_state_layout.h"
+#include "../../percepnet_amd/csrc/pn_network.h"
 #include <stdio.h>
 #include <string>
 #include <vector>
@@ -58,6 +59,49 @@ int main(int argc, char **argv) {
         CHECK((pn_state_first(L, t + 1, tn + 1) + L.live - 1) % L.slots == wr);
       }
   }
+
+  // the network table.  Every plan pn_plan_for can return — small and small_gru freely; narrow 1 outside STRICT, 2 in fp32 MFMA off
+  // the small dense family; direct in fp32 MFMA off both small families; rg 1|2 with direct, 1|2|3 in the shadow-operand modes,
+  // else 0 — in every mode: each layer's kernel is legal for the layer, reads the weight format the shared copy of (mode, narrow)
+  // holds, finds every shadow it reads or writes allocated, and is handed panels its launcher accepts
+  { int n_plans = 0;
+    for (int mode : {PN_NN_MFMA, PN_NN_STRICT, PN_NN_MFMA_F16, PN_NN_MFMA_X3})
+      for (int bits = 0; bits < 2 * 2 * 3 * 2 * 4; bits++) {
+        PnPlan p = {FE_SPLIT, bits & 1, bits >> 1 & 1, bits / 4 % 3, bits / 12 & 1, bits / 24, 1};
+        const bool f32 = mode == PN_NN_MFMA, x3 = pn_mode_x3(mode);
+        if ((p.narrow == 1 && mode == PN_NN_STRICT) || (p.narrow == 2 && !(f32 && !p.small)) || (p.direct && !(f32 && !p.small && !p.small_gru))) continue;
+        if (p.direct ? (p.rg < 1 || p.rg > 2) : (x3 ? p.rg < 1 : p.rg != 0)) continue;
+        n_plans++;
+        for (int li = 0; li < PN_NLAYERS; li++) {
+          const PnNetLayer &R = pn_kNet[li];
+          const int k = pn_layer_kernel(p, mode, li), N = pn_kGeom[li].nn;
+          const bool gru = pn_kGeom[li].kind == PN_KIND_GRU;
+          // (a) legal for the layer's type and the mode
+          CHECK((k == PN_K_STRICT) == (mode == PN_NN_STRICT)); if (k == PN_K_X3) CHECK(x3);
+          if (k == PN_K_N16 || k == PN_K_N48) CHECK(pn_layer_narrow(li) && N == PN_NB);
+          if (k == PN_K_DIRECT || k == PN_K_BATCH_SH) CHECK(f32 && gru == (k == PN_K_DIRECT));
+          // (b) the weights the kind reads are the ones built for (mode, narrow)
+          CHECK(pn_kernel_weight_format(k) == pn_layer_weight_format(mode, p.narrow, li));
+          // (c) shadows read (panels, GRU state) and written (the output; the gains that leave an x3 network have none) exist
+          int width[5];
+          for (int j = 0; j < R.n_in; j++) {
+            width[j] = pn_kState[R.in[j].entry].cols;
+            if (pn_kernel_reads_shadows(k)) CHECK(pn_state_shadowed(R.in[j].entry, p, mode));
+          }
+          if (pn_kernel_reads_shadows(k) && gru) CHECK(pn_state_shadowed(R.state, p, mode));
+          if (pn_kernel_writes_shadow(k) && !(k == PN_K_X3 && R.out.entry == PN_ST_GR)) CHECK(pn_state_shadowed(R.out.entry, p, mode));
+          // (d) the launcher's own predicate takes the panels
+          switch (k) {
+            case PN_K_STRICT: break;                   // any geometry
+            case PN_K_X3: CHECK((gru ? pn_check_gru_geometry("x3", R.n_in, width, N) : pn_check_dense_geometry("x3", R.n_in, width, 1)) == 0); break;
+            case PN_K_DIRECT: CHECK(pn_check_gru_geometry("direct", R.n_in, width, N) == 0); break;
+            case PN_K_N16: CHECK(pn_check_n16_geometry("n16", R.n_in, width, 8) == 0); break;
+            case PN_K_N48: CHECK(pn_check_dense_geometry("n48", R.n_in, width, 1) == 0); break;
+            default: if (!gru) CHECK(pn_check_dense_geometry("fp32", R.n_in, width, 0) == 0);      // (the fp32 GRU launchers refuse nothing)
+          }
+        }
+      }
+    CHECK(n_plans == 4 + 2 * 24 + 16); }      // STRICT; fp16 operands, split precision; fp32 MFMA (6 direct, 4 small, 6 batch)
 
   // CLI helpers
   { std::vector<int> d;

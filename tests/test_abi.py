@@ -56,7 +56,7 @@ def test_model_parsing_and_error_paths_without_gpu(lib, blob):
 
 
 def test_model_digest_is_sha256_of_the_content(lib, blob):
-    """The shared-weights cache (pn_context.cpp) is keyed by SHA-256 of the model content — a strong digest instead of round 5's two
+    """The shared-weights cache (pn_network.cpp) is keyed by SHA-256 of the model content — a strong digest instead of round 5's two
     64-bit hashes + retained host copy.  Known answers for the hash itself, and the model digest recomputed with hashlib from the
     PNW1 container: array bytes in layer order, then (activation, reset_after) of every layer."""
     import hashlib
@@ -147,7 +147,7 @@ def test_launch_geometry_refusals_without_gpu(lib):
     import ctypes
     lib.pn_debug_check_launch.argtypes = [ctypes.c_int] * 4
     lib.pn_last_error.restype = ctypes.c_char_p
-    # (kind, panels, width, n_out) of the layers as pn_context.cpp launches them
+    # (kind, panels, width, n_out) of the layers as pn_network.cpp launches them
     topology = [(0, 1, 128, 128), (0, 5, 128, 512), (0, 3, 512, 512), (0, 5, 512, 34), (0, 1, 128, 34),
                 (1, 5, 128, 512), (1, 3, 512, 512), (1, 5, 512, 34), (2, 1, 512, 512), (2, 2, 512, 128),
                 (3, 5, 512, 34), (3, 1, 128, 34)]

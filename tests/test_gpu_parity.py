@@ -84,7 +84,7 @@ def test_hip_path_straight_against_the_compiled_reference(model, blob):
 def test_row_range_chains_bit_identical(model, oracle, monkeypatch):
     """Round-5 verdict item 3: on one in-order stream every layer of the batch GEMMs pays whole rounds of 512 co-resident blocks
     (65 536 streams = 16 rounds, 66 048 = 17).  Large fp32 contexts now run the network as row-range chains on streams of their own
-    (pn_context.cpp launch_rnn; default 2 chains above 16 384 streams).  8192 + 300 streams, forced to 1, 2 and 3 chains (ragged
+    (pn_network.cpp launch_rnn; default 2 chains above 16 384 streams).  8192 + 300 streams, forced to 1, 2 and 3 chains (ragged
     last range: 8492 = 4352 + 4140 = 2944 + 2944 + 2604 rows): bit-identical PCM and g,r for every stream, also through the
     network-only entry point, and the last rows still follow the oracle."""
     B, T = 8192 + 300, 5
