@@ -2,6 +2,8 @@
 #pragma once
 #ifndef PN_NO_HIP                 // PN_NO_HIP: the HIP-free host pieces (pn_model.cpp, pn_pack.cpp, pn_tables.cpp) built alone, e.g.
 #include <hip/hip_runtime.h>      // by the sanitizer harness tests/c/host_sanitize.cpp with plain g++
+#else
+struct float2 { float x, y; };    // (the HIP-free tables only name pointers to it)
 #endif
 #include <stdint.h>
 #include <stddef.h>

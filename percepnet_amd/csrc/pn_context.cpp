@@ -14,8 +14,6 @@
 extern "C" int pn_device_count(void) { int n = 0; return hipGetDeviceCount(&n) == hipSuccess ? n : 0; }
 
 // ---- contexts -----------------------------------------------------------------------------------------
-static const char *kKernelNames[KF_COUNT] = {"frontend", "fc", "conv1", "conv2", "gru512", "gru_rb", "fc_gb", "fc_rb", "backend",
-                                            "fe_spec_in", "fe_pitch", "fe_spec_out"};
 
 static thread_local bool g_last_alloc_oom = false;     // the last dev_alloc failure on this thread was hipErrorOutOfMemory
 int dev_alloc_into(std::vector<void *> &allocs, size_t &total, hipStream_t stream, void **p, size_t bytes, bool zero) {
@@ -41,6 +39,22 @@ int dev_alloc_into(std::vector<void *> &allocs, size_t &total, hipStream_t strea
 static int dev_alloc(pn_ctx *c, void **p, size_t bytes, bool zero) { return dev_alloc_into(c->allocs, c->bytes, c->stream, p, bytes, zero); }
 #define DEV_ALLOC(ptr, count, zero) \
   do { if (dev_alloc(c, (void **)&(ptr), sizeof(*(ptr)) * (size_t)(count), zero)) goto fail; } while (0)
+int tables_upload(std::vector<void *> &allocs, size_t &total, hipStream_t stream, PnTables **tables, float **tansig) {
+  PnTables *ht = new PnTables();
+  hipError_t e = hipSuccess;
+  int rc = pn_build_tables(ht);                          // these two set the error themselves
+  if (!rc) rc = dev_alloc_into(allocs, total, stream, (void **)tables, sizeof(PnTables), false);
+  if (!rc) e = hipMemcpyAsync(*tables, ht, sizeof(PnTables), hipMemcpyHostToDevice, stream);
+  if (!rc && e == hipSuccess && tansig) {
+    rc = dev_alloc_into(allocs, total, stream, (void **)tansig, sizeof(ht->tansig), false);
+    if (!rc) e = hipMemcpyAsync(*tansig, ht->tansig, sizeof(ht->tansig), hipMemcpyHostToDevice, stream);
+  }
+  const hipError_t es = hipStreamSynchronize(stream);    // always: ht must outlive the copies
+  if (e == hipSuccess) e = es;
+  if (!rc && e != hipSuccess) { pn_set_error("table upload failed: %s", hipGetErrorString(e)); rc = -1; }
+  delete ht;
+  return rc;
+}
 
 // "fresh context", pn_ctx_reset and "every stream reset" are one statement: every word of every entry and shadow is zero
 static int zero_state(pn_ctx *c) {
@@ -118,30 +132,20 @@ static pn_ctx *ctx_create(const pn_model *model, int device, int n_streams, int 
     c->own_stream = true;
   }
   const size_t B = n_streams, Bp = c->Bp;
-  {
-    PnTables *ht = new PnTables();
-    int rc = pn_build_tables(ht);
-    if (!rc) rc = dev_alloc(c, (void **)&c->tables, sizeof(PnTables), false);
-    if (!rc && hipMemcpyAsync(c->tables, ht, sizeof(PnTables), hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = -1;
-    if (!rc) rc = dev_alloc(c, (void **)&c->tansig, sizeof(ht->tansig), false);
-    if (!rc && hipMemcpyAsync(c->tansig, ht->tansig, sizeof(ht->tansig), hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = -1;
-    hipStreamSynchronize(c->stream);
-    delete ht;
-    if (rc) goto fail;
-  }
+  float *base[PN_ST_COUNT];
+  if (tables_upload(c->allocs, c->bytes, c->stream, &c->tables, &c->tansig)) goto fail;
   for (int e = 0; e < PN_ST_COUNT; e++) {
-    const PnStateEntry &L = pn_kState[e]; pn_ctx::StateBuf &b = c->st[e];
-    const size_t rows = L.padded ? Bp : B;
-    b.slot_stride = L.in_row ? L.cols : (long long)(rows * L.row_words);
-    b.words = (L.in_row ? 1 : L.slots) * rows * L.row_words;
+    pn_ctx::StateBuf &b = c->st[e];
+    const PnStateSize z = pn_state_size(pn_kState[e], pn_kState[e].padded ? Bp : B);
+    b.words = z.words; b.slot_stride = z.slot_stride;
     DEV_ALLOC(b.p, b.words, false);
+    base[e] = b.p;
   }
+  c->side = pn_dsp_side(base, nullptr, B);
   // operand shadows: of the shadow-operand modes (1 half per element: fp16 operands; hi + lo planes: split precision), and of the
   // direct-operand family (fp32 fragments), which keeps its dense layers on the batch kernels: no shadows of the conv FIFOs
   for (int e = 0; e < PN_ST_COUNT; e++)
     if (pn_state_shadowed(e, c->plan, nn_mode)) DEV_ALLOC(c->st[e].sh, shadow_halfs_per_element(c) * c->st[e].words, false);
-  c->hist = c->st[PN_ST_HIST].p; c->synth = c->st[PN_ST_SYNTH].p; c->last_gain = c->st[PN_ST_LAST_GAIN].p; c->feat = c->st[PN_ST_FEAT].p; c->gr = c->st[PN_ST_GR].p;
-  c->eyring = c->st[PN_ST_EYRING].p; c->yring = (float2 *)c->st[PN_ST_YRING].p; c->Ps = (float2 *)c->st[PN_ST_PS].p; c->last_period = (int *)c->st[PN_ST_LAST_PERIOD].p; c->silence = (int *)c->st[PN_ST_SILENCE].p;
   DEV_ALLOC(c->io_in, B * PN_FRAME, false);
   DEV_ALLOC(c->io_out, B * PN_FRAME, false);
   if (zero_state(c)) goto fail;
@@ -270,12 +274,12 @@ extern "C" int pn_ctx_set_profiling(pn_ctx *c, int enable) {
   return 0;
 }
 extern "C" int pn_kernel_count(void) { return KF_COUNT; }
-extern "C" const char *pn_kernel_name(int i) { return (i >= 0 && i < KF_COUNT) ? kKernelNames[i] : NULL; }
+extern "C" const char *pn_kernel_name(int i) { return (i >= 0 && i < KF_COUNT) ? pn_kFamilyName[i] : NULL; }
 extern "C" int pn_ctx_kernel_time(pn_ctx *c, const char *name, double *total_ms, int64_t *launches) {
   if (!c || !name) return -1;
   if (flush_events(c)) return -1;
   for (int i = 0; i < KF_COUNT; i++)
-    if (!strcmp(name, kKernelNames[i])) { if (total_ms) *total_ms = c->fam_ms[i]; if (launches) *launches = c->fam_n[i]; return 0; }
+    if (!strcmp(name, pn_kFamilyName[i])) { if (total_ms) *total_ms = c->fam_ms[i]; if (launches) *launches = c->fam_n[i]; return 0; }
   pn_set_error("unknown kernel family '%s'", name);
   return -1;
 }
@@ -449,37 +453,38 @@ static int dsp_selftest(pn_ctx *c) {
   if (rc == -1) { pn_set_error("DSP self-test could not run: %s", msg.c_str()); return -1; }
   if (rc) {
     pn_set_error("DSP self-test FAILED (front end %s): %s does not match the CPU reference's known answer — this build of the DSP "
-                 "kernels is not bit-exact (DESIGN.md 4.4); refusing to run", c->plan.fe == FE_SPLIT ? "split" : (c->plan.fe == FE_MONO_G2 ? "g2" : "g4"), msg.c_str());
+                 "kernels is not bit-exact (DESIGN.md 4.4); refusing to run", pn_kFe[c->plan.fe].name, msg.c_str());
     return -1;
   }
   done[key] = 0;
   return 0;
 }
 
+// launch k of front-end family fe: row fe of this table is row fe of pn_kFe, its launchers in the order of that row's fam[]
+void pn_launch_fe(hipStream_t st, const PnTables *T, int n_streams, int fe, int k, const PnDspSide &s, const PnDspSlots &sl, const PnDspIn &in, int grid_cap) {
+  static PnFeLaunch *const launch[][3] = {{pn_launch_frontend}, {pn_launch_frontend_g2}, {pn_launch_fe_spec_in, pn_launch_fe_pitch, pn_launch_fe_spec_out}};
+  static_assert(sizeof(launch) / sizeof(launch[0]) == sizeof(pn_kFe) / sizeof(pn_kFe[0]) && sizeof(launch[0]) / sizeof(launch[0][0]) == sizeof(pn_kFe[0].fam) / sizeof(int),
+                "one row of launchers per front-end family of pn_kFe");
+  launch[fe][k](st, T, n_streams, s, sl, in, grid_cap);
+}
+
 static int process_dev(pn_ctx *c, const void *d_in, void *d_out, float *d_gr, int is_i16) {
   if (!c || !d_in || !d_out) { pn_set_error("NULL argument"); return -1; }
   PN_ON_DEVICE(c);
-  if (c->plan.fe == FE_SPLIT) {
-    { Scope sc(c, KF_FE_SPEC_IN);
-      pn_launch_fe_spec_in(c->stream, c->tables, c->B, c->t, d_in, is_i16, PN_FRAME, 1.f / 32768.f, c->hist, c->yring, c->eyring, c->dsp_grid_cap); }
-    { Scope sc(c, KF_FE_PITCH);
-      pn_launch_fe_pitch(c->stream, c->B, c->t, c->hist, c->feat, c->last_period, c->last_gain, nullptr, c->dsp_grid_cap); }
-    { Scope sc(c, KF_FE_SPEC_OUT);
-      pn_launch_fe_spec_out(c->stream, c->tables, c->B, c->t, c->hist, c->yring, c->eyring, c->last_period, c->Ps, c->feat,
-                            c->silence, nullptr, c->dsp_grid_cap); }
-  } else {
-    Scope sc(c, KF_FRONTEND);
-    (c->plan.fe == FE_MONO_G2 ? pn_launch_frontend_g2 : pn_launch_frontend)(c->stream, c->tables, c->B, c->t, d_in, is_i16, PN_FRAME, 1.f / 32768.f,
-        c->hist, c->yring, c->eyring, c->Ps, c->feat, c->silence, c->last_period, c->last_gain, nullptr, c->dsp_grid_cap);
+  const PnDspSide &s = c->side;
+  const PnDspSlots k = pn_dsp_slots(c->t);
+  const PnDspIn in = {d_in, is_i16, PN_FRAME, 1.f / 32768.f};
+  float *const gr = c->st[PN_ST_GR].p;
+  for (int i = 0; i < pn_kFe[c->plan.fe].n; i++) {
+    Scope sc(c, pn_kFe[c->plan.fe].fam[i]);
+    pn_launch_fe(c->stream, c->tables, c->B, c->plan.fe, i, s, k, in, c->dsp_grid_cap);
   }
   if (launch_rnn(c)) return -1;                        // a refused launch fails the frame (pn_last_error says which layer)
   { Scope sc(c, KF_BACKEND);
-    // X(t) == the look-ahead spectrum of frame t-5 (pn_dsp_fe.hip): the oldest live entry of the ring
-    const float2 *Xs = (const float2 *)state_at(c, PN_ST_YRING, 0);
-    const float *Ex = c->postfilter ? state_at(c, PN_ST_EYRING, 0) : nullptr;      // Ex(t) = Ey_lookahead(t-5)
-    pn_launch_backend(c->stream, c->tables, c->B, Xs, c->Ps, c->gr, Ex, c->silence, c->synth, d_out, is_i16, c->dsp_grid_cap,
-                      c->n_limited > 0 ? c->lam_mu : nullptr); }      // no stream limited: the plain back end
-  if (d_gr) PN_HIP_CHECK(hipMemcpyAsync(d_gr, c->gr, (size_t)c->B * 68 * 4, hipMemcpyDeviceToDevice, c->stream));
+    // X(t), and Ex(t) for the post-filter: the oldest live look-ahead slot
+    pn_launch_backend(c->stream, c->tables, c->B, pn_dsp_spec(s, k.slot_r), s.Ps, gr, c->postfilter ? pn_dsp_bands(s, k.slot_r) : nullptr, s.silence,
+                      c->st[PN_ST_SYNTH].p, d_out, is_i16, c->dsp_grid_cap, c->n_limited > 0 ? c->lam_mu : nullptr); }      // no stream limited: the plain back end
+  if (d_gr) PN_HIP_CHECK(hipMemcpyAsync(d_gr, gr, (size_t)c->B * 68 * 4, hipMemcpyDeviceToDevice, c->stream));
   PN_HIP_CHECK(hipGetLastError());
   c->t++; c->tn++;
   if (c->events.size() >= 4096 && flush_events(c)) return -1;   // profiling left on: bound the pending events
@@ -588,7 +593,7 @@ static int process_active(pn_ctx *c, const void *d_in, void *d_out, float *d_gr,
   }
   if (id_ring_stage(c, A.ids, A.inactive.data(), ni, NULL, 0, ni)) return -1;
   PnActiveArgs a; memset(&a, 0, sizeof(a));
-  a.ids = A.ids.d; a.synth = c->synth; a.last_period = c->last_period; a.last_gain = c->last_gain;
+  a.ids = A.ids.d; a.synth = c->st[PN_ST_SYNTH].p; a.last_period = c->side.last_period; a.last_gain = c->side.last_gain;
   a.out = d_out; a.out_row_words = is_i16 ? PN_FRAME / 2 : PN_FRAME; a.d_gr = d_gr;
   a.save_synth = A.save_synth; a.save_out = A.save_out; a.save_gr = A.save_gr; a.save_period = A.save_period; a.save_gain = A.save_gain;
   state_sections(c, a.sec);                             // at the counters the frame below runs with
@@ -616,7 +621,7 @@ static int process_host(pn_ctx *c, const void *h_in, void *h_out, float *h_gr, i
   PN_HIP_CHECK(hipMemcpyAsync(c->io_in, h_in, nbytes, hipMemcpyHostToDevice, c->stream));
   if (process_dev(c, c->io_in, c->io_out, NULL, is_i16)) return -1;
   PN_HIP_CHECK(hipMemcpyAsync(h_out, c->io_out, nbytes, hipMemcpyDeviceToHost, c->stream));
-  if (h_gr) PN_HIP_CHECK(hipMemcpyAsync(h_gr, c->gr, (size_t)c->B * 68 * 4, hipMemcpyDeviceToHost, c->stream));
+  if (h_gr) PN_HIP_CHECK(hipMemcpyAsync(h_gr, c->st[PN_ST_GR].p, (size_t)c->B * 68 * 4, hipMemcpyDeviceToHost, c->stream));
   PN_HIP_CHECK(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -853,8 +858,8 @@ extern "C" int pn_ctx_read_features(pn_ctx *c, float *h_feat, int32_t *h_silence
   if (!c) return -1;
   PN_ON_DEVICE(c);
   if (h_feat)
-    PN_HIP_CHECK(hipMemcpy2DAsync(h_feat, PN_NFEAT * 4, c->feat, PN_FEAT_STRIDE * 4, PN_NFEAT * 4, c->B, hipMemcpyDeviceToHost, c->stream));
-  if (h_silence) PN_HIP_CHECK(hipMemcpyAsync(h_silence, c->silence, (size_t)c->B * 4, hipMemcpyDeviceToHost, c->stream));
+    PN_HIP_CHECK(hipMemcpy2DAsync(h_feat, PN_NFEAT * 4, c->side.feat, PN_FEAT_STRIDE * 4, PN_NFEAT * 4, c->B, hipMemcpyDeviceToHost, c->stream));
+  if (h_silence) PN_HIP_CHECK(hipMemcpyAsync(h_silence, c->side.silence, (size_t)c->B * 4, hipMemcpyDeviceToHost, c->stream));
   PN_HIP_CHECK(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -865,8 +870,8 @@ extern "C" int pn_ctx_read_features_dev(pn_ctx *c, float *d_feat, int32_t *d_sil
   if (!c) return -1;
   PN_ON_DEVICE(c);
   if (d_feat)
-    PN_HIP_CHECK(hipMemcpy2DAsync(d_feat, PN_NFEAT * 4, c->feat, PN_FEAT_STRIDE * 4, PN_NFEAT * 4, c->B, hipMemcpyDeviceToDevice, c->stream));
-  if (d_silence) PN_HIP_CHECK(hipMemcpyAsync(d_silence, c->silence, (size_t)c->B * 4, hipMemcpyDeviceToDevice, c->stream));
+    PN_HIP_CHECK(hipMemcpy2DAsync(d_feat, PN_NFEAT * 4, c->side.feat, PN_FEAT_STRIDE * 4, PN_NFEAT * 4, c->B, hipMemcpyDeviceToDevice, c->stream));
+  if (d_silence) PN_HIP_CHECK(hipMemcpyAsync(d_silence, c->side.silence, (size_t)c->B * 4, hipMemcpyDeviceToDevice, c->stream));
   return 0;
 }
 
@@ -874,9 +879,9 @@ extern "C" int pn_ctx_compute_rnn_host(pn_ctx *c, const float *h_feat, float *h_
   if (!c || !h_feat || !h_gr) { pn_set_error("NULL argument"); return -1; }
   PN_ON_DEVICE(c);
   if (pipe_drain(c)) return -1;                      // frames in flight on the pipelined path own feat/gr
-  PN_HIP_CHECK(hipMemcpy2DAsync(c->feat, PN_FEAT_STRIDE * 4, h_feat, PN_NFEAT * 4, PN_NFEAT * 4, c->B, hipMemcpyHostToDevice, c->stream));
+  PN_HIP_CHECK(hipMemcpy2DAsync(c->side.feat, PN_FEAT_STRIDE * 4, h_feat, PN_NFEAT * 4, PN_NFEAT * 4, c->B, hipMemcpyHostToDevice, c->stream));
   if (launch_rnn(c)) return -1;
-  PN_HIP_CHECK(hipMemcpyAsync(h_gr, c->gr, (size_t)c->B * 68 * 4, hipMemcpyDeviceToHost, c->stream));
+  PN_HIP_CHECK(hipMemcpyAsync(h_gr, c->st[PN_ST_GR].p, (size_t)c->B * 68 * 4, hipMemcpyDeviceToHost, c->stream));
   PN_HIP_CHECK(hipStreamSynchronize(c->stream));
   PN_HIP_CHECK(hipGetLastError());
   c->tn++;                                           // only the network's rings advance; the DSP rings keep their frame
@@ -963,7 +968,7 @@ static int ss_ids_check(pn_ctx *c, const int32_t *ids, int n, bool distinct) {
 static void ss_args(pn_ctx *c, PnStreamStateArgs &a) {
   memset(&a, 0, sizeof(a));
   state_sections(c, a.sec);
-  a.last_gain = c->last_gain; a.last_period = c->last_period;
+  a.last_gain = c->side.last_gain; a.last_period = c->side.last_period;
   ss_header(a.hdr, ctx_digest(c), c->nn_mode);
 }
 

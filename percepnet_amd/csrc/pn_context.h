@@ -1,14 +1,11 @@
 // Private to the host side of libpercepnet_hip: a batched context and the few helpers its two files share — pn_context.cpp
 // (lifecycle, frame path, active set, host pipeline, state I/O, self-tests) and pn_network.cpp (shared weights, the ten-layer
-// launch loop, row-range chains).
+// launch loop, row-range chains).  The training-feature generator (pn_featgen.cpp) shares the allocator and the table upload.
 #pragma once
 #include <array>
 #include <tuple>
 #include <vector>
-#include "pn_launch.h"       // pn_common.h, pn_network.h (plan, state table), the public header
-
-enum { KF_FRONTEND, KF_FC, KF_CONV1, KF_CONV2, KF_GRU512, KF_GRU_RB, KF_FC_GB, KF_FC_RB, KF_BACKEND, KF_FE_SPEC_IN, KF_FE_PITCH,
-       KF_FE_SPEC_OUT, KF_COUNT };
+#include "pn_launch.h"       // pn_common.h, pn_network.h (plan, state table, DSP side, kernel families), the public header
 
 struct DevLayer { float *bias, *w, *rw, *wp, *rwp, *wq; };   // wq: narrow layers of small-batch fp32 contexts (pn_pack_weights_n16)
 struct SharedWeights;             // pn_network.cpp
@@ -48,8 +45,8 @@ struct pn_ctx {
   // the per-stream state: pn_kState (pn_state_layout.h) resolved for this context's size, mode and plan.  sh: the operand shadow
   // (same element index, shadow_halfs_per_element halfs per element), NULL where the mode / family keeps none
   struct StateBuf { float *p; uint16_t *sh; size_t words; long long slot_stride; } st[PN_ST_COUNT] = {};
-  float *hist, *eyring, *synth, *last_gain, *feat, *gr, *io_in, *io_out;      // aliases of st[].p that the frame path reads
-  float2 *yring, *Ps;
+  PnDspSide side;                  // the front end's entries of st[] (pn_dsp_layout.h), resolved once; no aux rows
+  float *io_in, *io_out;           // staging rows of the host-buffer paths
   bool postfilter = false;         // optional envelope post-filter in the back end (pn_ctx_set_postfilter)
   // per-stream attenuation limit (pn_ctx_set_atten_limit): (lam, mu) per stream on the device, allocated by the first set; the
   // host mirror of the dB values (the getter) and the count of streams with lam != 0 (the launch decision: while it is 0 the
@@ -60,7 +57,6 @@ struct pn_ctx {
   bool x3_sat = false;             // PERCEPNET_X3_SATCOUNT=1 (shadow-operand modes): count operand values clamped to the fp16 range
   int dsp_grid_cap = 0;            // > 0 only in the DSP self-test's temporary context: its DSP launches use that many blocks
   bool inject_bad_launch = false;  // pn_ctx_debug_inject_launch_failure (tests): the next frames hand fc a geometry its launcher refuses
-  int *last_period, *silence;      // (aliases too)
   std::vector<void *> allocs;
   bool profiling;
   struct Ev { int fam; hipEvent_t a, b; };
@@ -81,12 +77,14 @@ struct pn_ctx {
 
 // ---- pn_context.cpp ---------------------------------------------------------------------------------------------------------
 int dev_alloc_into(std::vector<void *> &allocs, size_t &total, hipStream_t stream, void **p, size_t bytes, bool zero);
+// the shared tables built on the host and copied to a new device buffer (synchronous); tansig (optional): the activation table alone
+int tables_upload(std::vector<void *> &allocs, size_t &total, hipStream_t stream, PnTables **tables, float **tansig);
 int pipe_make_stream(pn_ctx *c, hipStream_t *out, char how, int prio, char fallback, const std::vector<hipStream_t> &others, char *kind);
 // ---- pn_network.cpp ---------------------------------------------------------------------------------------------------------
 int weights_acquire(pn_ctx *c, const pn_model *model);     // c->weights, c->L: the shared device copy for c's key, built by its first user
 void weights_release(pn_ctx *c);                           // ... freed with its last one
 int chain_streams_init(pn_ctx *c);
-int launch_rnn(pn_ctx *c);                                 // compute_rnn (rnn.cpp:42-81) for all streams; features in c->feat, result in c->gr
+int launch_rnn(pn_ctx *c);                                 // compute_rnn (rnn.cpp:42-81) for all streams; features in st[PN_ST_FEAT], result in st[PN_ST_GR]
 // the operand shadow of entry e at p (a pointer into the entry) re-derived from its fp32 values, in this context's mode and
 // family: the whole batch, or the rows ids[i] with status[i] == 0 (status may be NULL).  Launches nothing where e keeps no shadow.
 int reshadow(pn_ctx *c, hipStream_t st, int e, const float *p, const int *d_ids = NULL, const int *d_status = NULL, int n = 0);

@@ -236,42 +236,26 @@ static inline int pn_dsp_grid(int n_streams, int blocks_per_cu, int grid_cap) {
   return need < cap ? need : cap;
 }
 
+// one instantiation: LamMu = float2 passes lam_mu on, none drops it
+template <typename TOut, bool PF, typename... LamMu>
+static void backend_launch(hipStream_t st, int grid, const PnTables *T, int n_streams, const float2 *Xs, const float2 *Ps, const float *gr,
+                           const float *ex, const int *silence, float *synth_mem, void *out, const float2 *lam_mu) {
+  if constexpr (sizeof...(LamMu) != 0)
+    hipLaunchKernelGGL((pn_backend_kernel<TOut, PF, LamMu...>), dim3(grid), dim3(DSP_THREADS), 0, st, T, n_streams, Xs, Ps, gr, ex, silence, synth_mem,
+                       (TOut *)out, lam_mu);
+  else
+    hipLaunchKernelGGL((pn_backend_kernel<TOut, PF>), dim3(grid), dim3(DSP_THREADS), 0, st, T, n_streams, Xs, Ps, gr, ex, silence, synth_mem, (TOut *)out);
+}
 void pn_launch_backend(hipStream_t st, const PnTables *T, int n_streams, const float2 *Xs, const float2 *Ps,
                        const float *gr, const float *ex_postfilter, const int *silence, float *synth_mem, void *out,
                        int out_is_i16, int grid_cap, const float2 *lam_mu) {
-  const int grid = pn_dsp_grid(n_streams, 0, grid_cap);
-  const dim3 g(grid), b(DSP_THREADS);
-  if (lam_mu) {                                             // at least one stream of the context has an attenuation limit
-    if (ex_postfilter) {
-      if (out_is_i16)
-        hipLaunchKernelGGL((pn_backend_kernel<int16_t, true, float2>), g, b, 0, st, T, n_streams, Xs, Ps, gr, ex_postfilter, silence,
-                           synth_mem, (int16_t *)out, lam_mu);
-      else
-        hipLaunchKernelGGL((pn_backend_kernel<float, true, float2>), g, b, 0, st, T, n_streams, Xs, Ps, gr, ex_postfilter, silence,
-                           synth_mem, (float *)out, lam_mu);
-    } else {
-      if (out_is_i16)
-        hipLaunchKernelGGL((pn_backend_kernel<int16_t, false, float2>), g, b, 0, st, T, n_streams, Xs, Ps, gr, ex_postfilter, silence,
-                           synth_mem, (int16_t *)out, lam_mu);
-      else
-        hipLaunchKernelGGL((pn_backend_kernel<float, false, float2>), g, b, 0, st, T, n_streams, Xs, Ps, gr, ex_postfilter, silence,
-                           synth_mem, (float *)out, lam_mu);
-    }
-    return;
-  }
-  if (ex_postfilter) {
-    if (out_is_i16)
-      hipLaunchKernelGGL((pn_backend_kernel<int16_t, true>), g, b, 0, st, T, n_streams, Xs, Ps, gr, ex_postfilter, silence,
-                         synth_mem, (int16_t *)out);
-    else
-      hipLaunchKernelGGL((pn_backend_kernel<float, true>), g, b, 0, st, T, n_streams, Xs, Ps, gr, ex_postfilter, silence,
-                         synth_mem, (float *)out);
-  } else {
-    if (out_is_i16)
-      hipLaunchKernelGGL((pn_backend_kernel<int16_t, false>), g, b, 0, st, T, n_streams, Xs, Ps, gr, ex_postfilter, silence,
-                         synth_mem, (int16_t *)out);
-    else
-      hipLaunchKernelGGL((pn_backend_kernel<float, false>), g, b, 0, st, T, n_streams, Xs, Ps, gr, ex_postfilter, silence,
-                         synth_mem, (float *)out);
-  }
+  // The eight instantiations.  Each index is 0 where the feature is ON: the kernels are emitted into the code object in the order
+  // this initialiser names them, and that order (limited, post-filter, int16 first) is the one the object has always had.
+  static constexpr decltype(&backend_launch<float, false>) launch[2][2][2] = {
+      {{backend_launch<int16_t, true, float2>, backend_launch<float, true, float2>},     // a stream limited: post-filter    (int16, float)
+       {backend_launch<int16_t, false, float2>, backend_launch<float, false, float2>}},  //                   no post-filter
+      {{backend_launch<int16_t, true>, backend_launch<float, true>},                     // none limited:     post-filter
+       {backend_launch<int16_t, false>, backend_launch<float, false>}}};                 //                   no post-filter
+  const int limited_off = !lam_mu, pf_off = !ex_postfilter, i16_off = !out_is_i16;
+  launch[limited_off][pf_off][i16_off](st, pn_dsp_grid(n_streams, 0, grid_cap), T, n_streams, Xs, Ps, gr, ex_postfilter, silence, synth_mem, out, lam_mu);
 }

@@ -555,21 +555,17 @@ __global__ __launch_bounds__(FE_THREADS, PN_FE_WAVES_PER_SIMD) void pn_frontend_
 }
 
 // ---- launcher ---------------------------------------------------------------------------------
-void pn_launch_frontend(hipStream_t st, const PnTables *T, int n_streams, int64_t frame, const void *in,
-                        int in_is_i16, long long in_stride, float i16_scale, float *hist, float2 *yring, float *eyring,
-                        float2 *Ps, float *feat, int *silence, int *last_period, float *last_gain, float *aux, int grid_cap) {
+void pn_launch_frontend(hipStream_t st, const PnTables *T, int n_streams, const PnDspSide &s, const PnDspSlots &k, const PnDspIn &in, int grid_cap) {
   const int need = (n_streams + FE_SPB - 1) / FE_SPB;
   const int cap = 256 * (16 / FE_SPB);                 // LDS-resident blocks on 256 CUs
   int grid = need < cap ? need : cap;                  // grid-stride
   if (grid_cap > 0 && grid > grid_cap) grid = grid_cap;
-  const int frame_t = (int)(frame % PN_HIST_FRAMES);
-  const int slot_w = (int)(frame % 6), slot_r = (int)((frame + 1) % 6);
-  if (in_is_i16)
-    hipLaunchKernelGGL(pn_frontend_kernel<int16_t>, dim3(grid), dim3(FE_THREADS), 0, st, T, n_streams, frame_t,
-                       slot_w, slot_r, (const int16_t *)in, in_stride, i16_scale, hist, yring, eyring, Ps, feat, silence,
-                       last_period, last_gain, aux);
+  if (in.is_i16)
+    hipLaunchKernelGGL(pn_frontend_kernel<int16_t>, dim3(grid), dim3(FE_THREADS), 0, st, T, n_streams, k.frame_t, k.slot_w, k.slot_r,
+                       (const int16_t *)in.p, in.stride, in.i16_scale, s.hist, s.yring, s.eyring, s.Ps, s.feat, s.silence, s.last_period,
+                       s.last_gain, s.aux);
   else
-    hipLaunchKernelGGL(pn_frontend_kernel<float>, dim3(grid), dim3(FE_THREADS), 0, st, T, n_streams, frame_t, slot_w,
-                       slot_r, (const float *)in, in_stride, i16_scale, hist, yring, eyring, Ps, feat, silence, last_period,
-                       last_gain, aux);
+    hipLaunchKernelGGL(pn_frontend_kernel<float>, dim3(grid), dim3(FE_THREADS), 0, st, T, n_streams, k.frame_t, k.slot_w, k.slot_r,
+                       (const float *)in.p, in.stride, in.i16_scale, s.hist, s.yring, s.eyring, s.Ps, s.feat, s.silence, s.last_period,
+                       s.last_gain, s.aux);
 }

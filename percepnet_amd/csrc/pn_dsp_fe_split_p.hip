@@ -881,14 +881,13 @@ __global__ __launch_bounds__(FP_THREADS, 2) void pn_fe_pitch_kernel(
   }
 }
 
-void pn_launch_fe_pitch(hipStream_t st, int n_streams, int64_t frame, const float *hist, float *feat, int *last_period,
-                        float *last_gain, float *aux, int grid_cap) {
+void pn_launch_fe_pitch(hipStream_t st, const PnTables *, int n_streams, const PnDspSide &s, const PnDspSlots &k, const PnDspIn &, int grid_cap) {
   const int need = (n_streams + FP_SPB - 1) / FP_SPB;
   const int cap = 256 * 2;                               // two LDS-resident blocks on each of 256 CUs
   int grid = need < cap ? need : cap;
   if (grid_cap > 0 && grid > grid_cap) grid = grid_cap;
   static const int stagger = getenv("PERCEPNET_FP_STAGGER") ? atoi(getenv("PERCEPNET_FP_STAGGER")) : 0;
   // only worth it when a block walks several stream groups (the delay is paid once per launch)
-  hipLaunchKernelGGL(pn_fe_pitch_kernel, dim3(grid), dim3(FP_THREADS), 0, st, n_streams, (int)(frame % PN_HIST_FRAMES), hist,
-                     feat, last_period, last_gain, aux, need >= 4 * cap ? stagger : 0);
+  hipLaunchKernelGGL(pn_fe_pitch_kernel, dim3(grid), dim3(FP_THREADS), 0, st, n_streams, k.frame_t, s.hist, s.feat, s.last_period,
+                     s.last_gain, s.aux, need >= 4 * cap ? stagger : 0);
 }

@@ -1,51 +1,29 @@
 // Host side of the batched training-feature generator: the reference's
 // `percepNet <speech> <noisy> <count> <output>` binary (train(), denoise.cpp:603-787) for n_pairs
 // (speech, noisy) file pairs advanced in lock-step on one GPU.  Per frame: the inference path's
-// front-end kernel once over the speech streams and once over the noisy streams, the target kernel,
+// front end once over the speech streams and once over the noisy streams, the target kernel,
 // and — when the caller wants the TEST build's test_output.pcm — the inference back-end kernel on the
 // noisy spectrum with the ideal gains, through the speech state's synthesis memory (744-757).
-#include "pn_launch.h"
-#include "pn_plan.h"
-#include "../../include/percepnet_hip.h"
+// The two DenoiseStates are two DSP sides (pn_dsp_layout.h): the front end's entries of the state table, sized for n_pairs rows
+// each, allocated, zeroed and reset by the walk a context makes, and run by the plan's front-end family like a context's.
+#include "pn_context.h"      // the launchers, the DSP side, dev_alloc_into, tables_upload
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
 
-struct FgSide {                 // one DenoiseState's worth of DSP state per stream (no network state)
-  float *hist; float2 *yring; float *eyring; float2 *Ps; float *feat; int *silence; int *last_period;
-  float *last_gain; float *aux;
-};
-
 struct pn_featgen {
   int device, B; int64_t t; size_t bytes;
-  int fe;                       // front end (pn_plan.h): the single-launch kernel for FE_MONO_G4, else the phase-split one
+  int fe;                       // front-end family (pn_plan.h)
   hipStream_t stream; bool own_stream;
   PnTables *tables;
-  FgSide clean, noisy;
+  float *st[2][PN_ST_COUNT];    // the side entries of the speech (0) and the noisy (1) state, NULL elsewhere
+  PnDspSide clean, noisy;
   float *synth;                 // st->synthesis_mem of the speech state (frame_synthesis(st, ...), 753)
   float *gr, *tmp_out;          // [B][68], [B][480] for the TEST synthesis
   std::vector<void *> allocs;
 };
 
-static int fg_alloc(pn_featgen *c, void **p, size_t bytes) {
-  PN_HIP_CHECK(hipMalloc(p, bytes));
-  c->allocs.push_back(*p); c->bytes += bytes;
-  PN_HIP_CHECK(hipMemsetAsync(*p, 0, bytes, c->stream));
-  return 0;
-}
-#define FG_ALLOC(ptr, count) \
-  do { if (fg_alloc(c, (void **)&(ptr), sizeof(*(ptr)) * (size_t)(count))) goto fail; } while (0)
-
-static int fg_zero_side(pn_featgen *c, FgSide &s) {
-  const size_t B = c->B;
-  PN_HIP_CHECK(hipMemsetAsync(s.hist, 0, B * PN_HIST_STRIDE * 4, c->stream));
-  PN_HIP_CHECK(hipMemsetAsync(s.yring, 0, 6 * B * PN_SPEC_BINS * sizeof(float2), c->stream));
-  PN_HIP_CHECK(hipMemsetAsync(s.eyring, 0, 6 * B * 36 * 4, c->stream));
-  PN_HIP_CHECK(hipMemsetAsync(s.last_gain, 0, B * 4, c->stream));
-  PN_HIP_CHECK(hipMemsetAsync(s.last_period, 0, B * 4, c->stream));
-  PN_HIP_CHECK(hipMemsetAsync(s.silence, 0, B * 4, c->stream));
-  return 0;
-}
+static int fg_alloc(pn_featgen *c, float **p, size_t words) { return dev_alloc_into(c->allocs, c->bytes, c->stream, (void **)p, words * 4, true); }
 
 extern "C" void pn_featgen_destroy(pn_featgen *c) {
   if (!c) return;
@@ -73,43 +51,31 @@ extern "C" pn_featgen *pn_featgen_create(int device, int n_pairs, void *hip_stre
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { pn_set_error("hipStreamCreate failed"); delete c; return NULL; }
     c->own_stream = true;
   }
-  {
-    const size_t B = n_pairs;
-    PnTables *ht = (PnTables *)malloc(sizeof(PnTables));
-    if (!ht) { pn_set_error("out of host memory"); goto fail; }
-    if (pn_build_tables(ht) || fg_alloc(c, (void **)&c->tables, sizeof(PnTables))) { free(ht); goto fail; }
-    hipError_t e = hipMemcpyAsync(c->tables, ht, sizeof(PnTables), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    free(ht);
-    if (e != hipSuccess) { pn_set_error("table upload failed: %s", hipGetErrorString(e)); goto fail; }
-    FgSide *sides[2] = {&c->clean, &c->noisy};
-    for (FgSide *s : sides) {
-      FG_ALLOC(s->hist, B * PN_HIST_STRIDE);
-      FG_ALLOC(s->yring, 6 * B * PN_SPEC_BINS);
-      FG_ALLOC(s->eyring, 6 * B * 36);
-      FG_ALLOC(s->Ps, B * PN_SPEC_BINS);
-      FG_ALLOC(s->feat, B * PN_FEAT_STRIDE);
-      FG_ALLOC(s->silence, B);
-      FG_ALLOC(s->last_period, B);
-      FG_ALLOC(s->last_gain, B);
-      FG_ALLOC(s->aux, B * PN_AUX_STRIDE);
-    }
-    FG_ALLOC(c->synth, B * PN_FRAME);
-    FG_ALLOC(c->gr, B * 68);
-    FG_ALLOC(c->tmp_out, B * PN_FRAME);
-    if (hipStreamSynchronize(c->stream) != hipSuccess) { pn_set_error("featgen init failed"); goto fail; }
+  const size_t B = n_pairs;
+  if (tables_upload(c->allocs, c->bytes, c->stream, &c->tables, NULL)) goto fail;
+  for (int side = 0; side < 2; side++) {
+    float *aux;
+    for (int e : pn_kSideEntries)                             // B rows for every entry: no GEMM reads them
+      if (fg_alloc(c, &c->st[side][e], pn_state_size(pn_kState[e], B).words)) goto fail;
+    if (fg_alloc(c, &aux, B * PN_AUX_STRIDE)) goto fail;
+    (side ? c->noisy : c->clean) = pn_dsp_side(c->st[side], aux, B);
   }
+  if (fg_alloc(c, &c->synth, pn_state_size(pn_kState[PN_ST_SYNTH], B).words) || fg_alloc(c, &c->gr, pn_state_size(pn_kState[PN_ST_GR], B).words) ||
+      fg_alloc(c, &c->tmp_out, B * PN_FRAME)) goto fail;
+  if (hipStreamSynchronize(c->stream) != hipSuccess) { pn_set_error("featgen init failed"); goto fail; }
   return c;
 fail:
   pn_featgen_destroy(c);
   return NULL;
 }
 
+// as pn_ctx_reset: every word of every entry is zero
 extern "C" int pn_featgen_reset(pn_featgen *c) {
   if (!c) return -1;
   PN_ON_DEVICE(c);
-  if (fg_zero_side(c, c->clean) || fg_zero_side(c, c->noisy)) return -1;
-  PN_HIP_CHECK(hipMemsetAsync(c->synth, 0, (size_t)c->B * PN_FRAME * 4, c->stream));
+  for (int side = 0; side < 2; side++)
+    for (int e : pn_kSideEntries) PN_HIP_CHECK(hipMemsetAsync(c->st[side][e], 0, pn_state_size(pn_kState[e], c->B).words * 4, c->stream));
+  PN_HIP_CHECK(hipMemsetAsync(c->synth, 0, pn_state_size(pn_kState[PN_ST_SYNTH], c->B).words * 4, c->stream));
   c->t = 0;
   return 0;
 }
@@ -120,21 +86,17 @@ extern "C" int pn_featgen_synchronize(pn_featgen *c) { if (!c) return -1; PN_HIP
 
 static int fg_frame(pn_featgen *c, const int16_t *sp, const int16_t *no, long long in_stride, float *rec,
                     long long rec_stride, int16_t *pcm, long long pcm_stride) {
-  const int slot_w = (int)(c->t % 6), slot_r = (int)((c->t + 1) % 6);
-  const size_t B = c->B;
+  const PnDspSlots k = pn_dsp_slots(c->t);
   // train() analyses the noisy frame first (730) and the speech frame second (731); the two states are
   // independent, so the order of the launches is immaterial
-  // the phase-split front end (three launches per analysed signal) unless the plan asks for the single-launch kernel
-  auto fe = c->fe == FE_MONO_G4 ? pn_launch_frontend : pn_launch_frontend_split;
-  fe(c->stream, c->tables, c->B, c->t, no, 1, in_stride, 1.f, c->noisy.hist, c->noisy.yring, c->noisy.eyring, c->noisy.Ps,
-     c->noisy.feat, c->noisy.silence, c->noisy.last_period, c->noisy.last_gain, c->noisy.aux, 0);
-  fe(c->stream, c->tables, c->B, c->t, sp, 1, in_stride, 1.f, c->clean.hist, c->clean.yring, c->clean.eyring, c->clean.Ps,
-     c->clean.feat, c->clean.silence, c->clean.last_period, c->clean.last_gain, c->clean.aux, 0);
-  pn_launch_targets(c->stream, c->tables, c->B, c->clean.eyring + (size_t)slot_r * B * 36,
-                    c->noisy.eyring + (size_t)slot_r * B * 36, c->noisy.eyring + (size_t)slot_w * B * 36, c->clean.aux,
-                    c->noisy.aux, c->noisy.last_period, rec, rec_stride, c->gr);
+  const PnDspSide *side[2] = {&c->noisy, &c->clean};
+  const PnDspIn in[2] = {{no, 1, in_stride, 1.f}, {sp, 1, in_stride, 1.f}};
+  for (int s = 0; s < 2; s++)
+    for (int i = 0; i < pn_kFe[c->fe].n; i++) pn_launch_fe(c->stream, c->tables, c->B, c->fe, i, *side[s], k, in[s], 0);
+  pn_launch_targets(c->stream, c->tables, c->B, pn_dsp_bands(c->clean, k.slot_r), pn_dsp_bands(c->noisy, k.slot_r), pn_dsp_bands(c->noisy, k.slot_w),
+                    c->clean.aux, c->noisy.aux, c->noisy.last_period, rec, rec_stride, c->gr);
   // the synthesis memory must advance every frame whether or not the caller keeps the PCM (753)
-  pn_launch_backend(c->stream, c->tables, c->B, c->noisy.yring + (size_t)slot_r * B * PN_SPEC_BINS, c->noisy.Ps, c->gr,
+  pn_launch_backend(c->stream, c->tables, c->B, pn_dsp_spec(c->noisy, k.slot_r), c->noisy.Ps, c->gr,
                     nullptr /* the targets kernel already post-filtered g (743) */, c->noisy.silence, c->synth, c->tmp_out, 0, 0,
                     nullptr /* no attenuation limit */);
   if (pcm) pn_launch_saturate_i16(c->stream, c->B, c->tmp_out, pcm, pcm_stride);

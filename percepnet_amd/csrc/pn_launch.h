@@ -1,37 +1,22 @@
-// Kernel launchers shared by the host files (pn_context.cpp, pn_network.cpp, pn_featgen.cpp).
+// Kernel launchers shared by the host files (pn_context.cpp, pn_network.cpp, pn_featgen.cpp).  The DSP ones take the
+// descriptions of pn_dsp_layout.h (a side, the slots of a frame, its input), the network ones the panels of pn_network.h.
 #pragma once
 #include "pn_common.h"
-#include "pn_network.h"       // PnSegs, and through it pn_state_layout.h
+#include "pn_network.h"       // PnSegs, and through it pn_dsp_layout.h and pn_state_layout.h
 
-// grid_cap (last argument of every DSP launcher): test hook of the create-time DSP self-test (pn_context.cpp: dsp_selftest).
-// When > 0 the launcher caps its grid at this many blocks, so that a 40-stream batch walks several grid-stride rounds of ONE
-// block (the regime in which a mis-scheduled persistent loop once corrupted later rounds).  It is state of
-// the temporary self-test context only (pn_ctx::dsp_grid_cap): no other context, thread or device ever sees it.  0 = off.
-
-// ---- kernels / helpers implemented in pn_dsp.hip and pn_nn.hip -----------------------------------
-// in: stream s's 480 samples at in + s*in_stride; i16_scale: 1/32768 (CLI, main.cpp:34) or 1 (training binary,
-// denoise.cpp:41,697); aux: optional [n_streams][PN_AUX_STRIDE] side outputs for the training-feature path
-void pn_launch_frontend(hipStream_t st, const PnTables *T, int n_streams, int64_t frame, const void *in,
-                        int in_is_i16, long long in_stride, float i16_scale, float *hist, float2 *yring, float *eyring,
-                        float2 *Ps, float *feat, int *silence, int *last_period, float *last_gain, float *aux, int grid_cap);
-// the same kernel instantiated with two streams per wavefront (pn_dsp_fe_g2.hip): lower latency per stream, lower
-// throughput — used by small-batch contexts
-void pn_launch_frontend_g2(hipStream_t st, const PnTables *T, int n_streams, int64_t frame, const void *in,
-                           int in_is_i16, long long in_stride, float i16_scale, float *hist, float2 *yring, float *eyring,
-                           float2 *Ps, float *feat, int *silence, int *last_period, float *last_gain, float *aux, int grid_cap);
-// the phase-split front end (pn_dsp_fe_split_s.hip, pn_dsp_fe_split_p.hip): three launches with their own lane mapping
-// and register / LDS budget; spec_in and pitch are independent of each other, spec_out needs both.  Same results, bit
-// for bit, as pn_launch_frontend.
-void pn_launch_fe_spec_in(hipStream_t st, const PnTables *T, int n_streams, int64_t frame, const void *in, int in_is_i16,
-                          long long in_stride, float i16_scale, float *hist, float2 *yring, float *eyring, int grid_cap);
-void pn_launch_fe_pitch(hipStream_t st, int n_streams, int64_t frame, const float *hist, float *feat, int *last_period,
-                        float *last_gain, float *aux, int grid_cap);
-void pn_launch_fe_spec_out(hipStream_t st, const PnTables *T, int n_streams, int64_t frame, const float *hist,
-                           const float2 *yring, const float *eyring, const int *last_period, float2 *Ps, float *feat,
-                           int *silence, float *aux, int grid_cap);
-void pn_launch_frontend_split(hipStream_t st, const PnTables *T, int n_streams, int64_t frame, const void *in, int in_is_i16,
-                              long long in_stride, float i16_scale, float *hist, float2 *yring, float *eyring, float2 *Ps,
-                              float *feat, int *silence, int *last_period, float *last_gain, float *aux, int grid_cap);
+// ---- the DSP launchers (pn_dsp_fe*.hip, pn_dsp.hip) ------------------------------------------------------------------------
+// A front-end launch takes a side, the frame's slots and the frame's input (pn_dsp_layout.h); a launch that needs no tables or
+// no input ignores them, so that all five have one signature.  pn_launch_fe (pn_context.cpp) is launch k of family fe: a context
+// and the feature generator both loop over pn_kFe[fe]'s launches.
+// grid_cap: test hook of the create-time DSP self-test (pn_context.cpp: dsp_selftest).  When > 0 the launcher caps its grid at
+// this many blocks, so that a 40-stream batch walks several grid-stride rounds of ONE block (the regime in which a mis-scheduled
+// persistent loop once corrupted later rounds).  It is state of the temporary self-test context only
+// (pn_ctx::dsp_grid_cap): no other context, thread or device ever sees it.  0 = off.
+typedef void PnFeLaunch(hipStream_t st, const PnTables *T, int n_streams, const PnDspSide &s, const PnDspSlots &k, const PnDspIn &in, int grid_cap);
+PnFeLaunch pn_launch_frontend;        // four streams per wavefront (pn_dsp_fe.hip)
+PnFeLaunch pn_launch_frontend_g2;     // the same kernel with two (pn_dsp_fe_g2.hip): lower latency per stream, lower throughput
+PnFeLaunch pn_launch_fe_spec_in, pn_launch_fe_pitch, pn_launch_fe_spec_out;   // the phase kernels, each with its own lane mapping and register / LDS budget
+void pn_launch_fe(hipStream_t st, const PnTables *T, int n_streams, int fe, int k, const PnDspSide &s, const PnDspSlots &sl, const PnDspIn &in, int grid_cap);
 // per-stream re-initialisation (pn_state.hip): rows ids[] of a [n_slots][rows][row_floats] array / of a fragment-order shadow
 void pn_launch_zero_rows(hipStream_t st, void *base, int row_floats, long long row_stride, int n_slots, long long slot_stride,
                          const int *d_ids, int n);
@@ -77,6 +62,8 @@ void pn_launch_targets(hipStream_t st, const PnTables *T, int n_pairs, const flo
                        const float *ey_look_noisy, const float *aux_clean, const float *aux_noisy,
                        const int *period_noisy, float *records, long long rec_stride, float *gr);
 void pn_launch_saturate_i16(hipStream_t st, int n_pairs, const float *in, int16_t *out, long long out_stride);
+// the back end takes its operands one by one: the feature generator mixes sides (Xs, Ps, silence of the noisy side; the speech
+// state's synthesis memory).  Xs / ex_postfilter: pn_dsp_spec / pn_dsp_bands of a side at the frame's slot_r
 void pn_launch_backend(hipStream_t st, const PnTables *T, int n_streams, const float2 *Xs, const float2 *Ps,
                        const float *gr, const float *ex_postfilter /* NULL = off */, const int *silence, float *synth_mem,
                        void *out, int out_is_i16, int grid_cap,

@@ -4,10 +4,6 @@
 #include <map>
 #include <mutex>
 
-static_assert(pn_kNet[PN_L_FC].fam == KF_FC && pn_kNet[PN_L_CONV1].fam == KF_CONV1 && pn_kNet[PN_L_CONV2].fam == KF_CONV2 &&
-              pn_kNet[PN_L_GRU1].fam == KF_GRU512 && pn_kNet[PN_L_GRU_GB].fam == KF_GRU512 && pn_kNet[PN_L_GRU_RB].fam == KF_GRU_RB &&
-              pn_kNet[PN_L_FC_GB].fam == KF_FC_GB && pn_kNet[PN_L_FC_RB].fam == KF_FC_RB, "pn_kNet's profiling families are the KF_* indices");
-
 // Device copy of a model's biases and (re-packed) weights, shared by every context of one (model content, device, network
 // mode, narrow-layer packing): the reference binds all its states to ONE static model (denoise.cpp:49-51,267: a borrowed
 // pointer, zero copies); here N contexts — N legacy rnnoise_create handles, the shards of a CLI run, a service that opens

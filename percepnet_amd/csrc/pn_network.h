@@ -4,8 +4,7 @@
 // shadows it goes through: the launch loop and the weight upload (pn_network.cpp), the shadow allocation (pn_context.cpp) and
 // pn_plan_describe all ask here.  A new kernel variant is one new kind and one arm of pn_layer_kernel.
 #pragma once
-#include "pn_plan.h"
-#include "pn_state_layout.h"
+#include "pn_dsp_layout.h"    // the profiling families, and through it pn_plan.h and pn_state_layout.h
 
 // The A operand of a layer = the concatenation along K of n <= 5 row-major panels: base, row stride (floats) and valid columns of
 // each; the MFMA path requires every panel to be readable (and zero) up to the next multiple of 32 and all panels to be equally wide
@@ -20,21 +19,21 @@ struct PnNetLayer {
   int n_in; PnRef in[5];   // input panels, in K order; each as wide as its entry (fc: PN_FEAT_STRIDE, PN_NFEAT of them valid)
   PnRef out; int out_col;  // output: pn_kGeom[].nn columns from out_col on; the leading dimension is the entry's row width
   int state;               // GRU: the entry of its recurrent state (read: live slot 0; written: out), else -1
-  int fam;                 // profiling family the launch is bracketed under (a KF_* of pn_context.h)
+  int fam;                 // profiling family the launch is bracketed under (KF_*, pn_dsp_layout.h)
 };
 static constexpr PnNetLayer pn_kNet[PN_NLAYERS] = {
-    {1, {{PN_ST_FEAT, 0}}, pn_ref_new(PN_ST_C1RING), 0, -1, 1},                                             // fc
+    {1, {{PN_ST_FEAT, 0}}, pn_ref_new(PN_ST_C1RING), 0, -1, KF_FC},                                                   // fc
     {5, {{PN_ST_C1RING, 0}, {PN_ST_C1RING, 1}, {PN_ST_C1RING, 2}, {PN_ST_C1RING, 3}, pn_ref_new(PN_ST_C1RING)},
-     pn_ref_new(PN_ST_C2RING), 0, -1, 2},                                                                   // conv1: [4 previous fc outputs | current] (nnet.cpp:182-200)
-    {3, {{PN_ST_C2RING, 0}, {PN_ST_C2RING, 1}, pn_ref_new(PN_ST_C2RING)}, {PN_ST_C2OUT, 0}, 0, -1, 3},      // conv2
-    {1, {{PN_ST_C2OUT, 0}}, pn_ref_new(PN_ST_GRU1), 0, PN_ST_GRU1, 4},                                      // gru1
-    {1, {pn_ref_new(PN_ST_GRU1)}, pn_ref_new(PN_ST_GRU2), 0, PN_ST_GRU2, 4},                                // gru2: the UPDATED state of gru1
-    {1, {pn_ref_new(PN_ST_GRU2)}, pn_ref_new(PN_ST_GRU3), 0, PN_ST_GRU3, 4},                                // gru3
-    {1, {pn_ref_new(PN_ST_GRU3)}, pn_ref_new(PN_ST_GRU_GB), 0, PN_ST_GRU_GB, 4},                            // gru_gb
-    {2, {pn_ref_new(PN_ST_GRU3), {PN_ST_C2OUT, 0}}, pn_ref_new(PN_ST_RB), 0, PN_ST_RB, 5},                  // gru_rb (rnn.cpp:67-69)
+     pn_ref_new(PN_ST_C2RING), 0, -1, KF_CONV1},                                                                      // conv1: [4 previous fc outputs | current] (nnet.cpp:182-200)
+    {3, {{PN_ST_C2RING, 0}, {PN_ST_C2RING, 1}, pn_ref_new(PN_ST_C2RING)}, {PN_ST_C2OUT, 0}, 0, -1, KF_CONV2},         // conv2
+    {1, {{PN_ST_C2OUT, 0}}, pn_ref_new(PN_ST_GRU1), 0, PN_ST_GRU1, KF_GRU512},                                        // gru1
+    {1, {pn_ref_new(PN_ST_GRU1)}, pn_ref_new(PN_ST_GRU2), 0, PN_ST_GRU2, KF_GRU512},                                  // gru2: the UPDATED state of gru1
+    {1, {pn_ref_new(PN_ST_GRU2)}, pn_ref_new(PN_ST_GRU3), 0, PN_ST_GRU3, KF_GRU512},                                  // gru3
+    {1, {pn_ref_new(PN_ST_GRU3)}, pn_ref_new(PN_ST_GRU_GB), 0, PN_ST_GRU_GB, KF_GRU512},                              // gru_gb
+    {2, {pn_ref_new(PN_ST_GRU3), {PN_ST_C2OUT, 0}}, pn_ref_new(PN_ST_RB), 0, PN_ST_RB, KF_GRU_RB},                    // gru_rb (rnn.cpp:67-69)
     {5, {{PN_ST_C2OUT, 0}, pn_ref_new(PN_ST_GRU1), pn_ref_new(PN_ST_GRU2), pn_ref_new(PN_ST_GRU3), pn_ref_new(PN_ST_GRU_GB)},
-     {PN_ST_GR, 0}, 0, -1, 6},                                                                              // fc_gb (rnn.cpp:72-77)
-    {1, {pn_ref_new(PN_ST_RB)}, {PN_ST_GR, 0}, PN_NB, -1, 7},                                               // fc_rb
+     {PN_ST_GR, 0}, 0, -1, KF_FC_GB},                                                                                 // fc_gb (rnn.cpp:72-77)
+    {1, {pn_ref_new(PN_ST_RB)}, {PN_ST_GR, 0}, PN_NB, -1, KF_FC_RB},                                                  // fc_rb
 };
 constexpr int pn_net_k(int li) { return pn_kNet[li].n_in * pn_kState[pn_kNet[li].in[0].entry].cols; }   // columns the layer's K sweep covers
 // the table and the topology agree: equally wide panels that add up to the layer's inputs (fc: the zero-padded feature panel),
@@ -114,5 +113,5 @@ static inline int pn_plan_describe(const PnPlan &p, int nn_mode, char *buf, size
   if (gb == rb) snprintf(narrow, sizeof(narrow), "%s", name(PN_L_FC_GB));
   else snprintf(narrow, sizeof(narrow), "fc_gb:%s+fc_rb:%s", gb == PN_K_X3 ? "x3" : name(PN_L_FC_GB), gb == PN_K_X3 && rb != PN_K_N16 ? "fp32" : name(PN_L_FC_RB));
   return snprintf(buf, n, "nn=%s dense=%s gru=%s gru_rb=%s narrow=%s frontend=%s", nn, name(PN_L_CONV1), name(PN_L_GRU1), name(PN_L_GRU_RB), narrow,
-                  p.fe == FE_SPLIT ? "split" : (p.fe == FE_MONO_G2 ? "g2" : "g4"));
+                  pn_kFe[p.fe].name);
 }

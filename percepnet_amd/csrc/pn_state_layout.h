@@ -2,6 +2,8 @@
 // ring phases are checked without a GPU (tests/c/host_sanitize.cpp).  Every per-stream device buffer of pn_ctx is one entry of
 // pn_kState; allocation, zeroing, per-stream reset, the active-set fix-up, the stream-state records, the host state copies and
 // the debug taps all walk this table (pn_context.cpp resolves it once per context).  A new state buffer is one new entry.
+// The DSP entries are also the buffers of a front-end side (pn_dsp_layout.h), which the training-feature generator
+// (pn_featgen.cpp) allocates, zeroes and resets by the same walk with pn_state_size.
 //
 // All buffers are 4-byte words (float2 / int buffers are described in words).  An entry is `slots` slots of `cols` words per
 // row, `live` of which hold state between two frames; the slots lie one batch apart ([slots][rows][row_words]) or, for the
@@ -51,6 +53,13 @@ static constexpr PnStateEntry pn_kState[PN_ST_COUNT] = {
     {1, 128,                  2,  1, 128,              0, PN_CNT_TN,   PN_CLS_RING,    PN_SH_MODES_DIRECT, PN_SS_GRU_RB},  // rb
     {0, 68,                   1,  1, 68,               0, PN_CNT_NONE, PN_CLS_SCRATCH, PN_SH_NONE,         -1},            // gr
 };
+
+// An entry sized for `rows` rows: its words, and the distance between two of its slots.  A context passes B or Bp as `padded`
+// says; the feature generator, whose rows no GEMM reads, B for every entry.
+struct PnStateSize { size_t words; long long slot_stride; };
+constexpr PnStateSize pn_state_size(const PnStateEntry &e, size_t rows) {
+  return PnStateSize{(e.in_row ? 1 : e.slots) * rows * e.row_words, e.in_row ? e.cols : (long long)(rows * e.row_words)};
+}
 
 // The ring phases — the only place that spells them.  Before the frame with counters (t, tn) runs, an entry's live slots are
 // first, first + 1, ... first + live - 1 (mod slots), oldest first; the frame writes the one slot that is not live, which

@@ -1,7 +1,8 @@
 // CPU-only sanitizer harness (tests/test_hardening.py builds it with g++ -fsanitize=address,undefined -DPN_NO_HIP): the
 // HIP-free host pieces of libpercepnet_hip — the PNW1 / RNNModel parsers (pn_model.cpp), the table builder (pn_tables.cpp),
 // the weight packers (pn_pack.cpp) and the CLI helpers (pn_cli_util.h) — driven with valid, truncated, oversized and
-// corrupted inputs; the table of a context's per-stream state (pn_state_layout.h): record offsets, ring phases, classes; and the
+// corrupted inputs; the table of a context's per-stream state (pn_state_layout.h): record offsets, ring phases, classes; the DSP
+// half of a frame (pn_dsp_layout.h): slots, side entries, front-end families, profiling families; and the
 // table of the network's layers (pn_network.h): kernel, weight format, shadows and launch geometry of every layer under every plan.
 // Any out-of-bounds access, overflow or leak-free violation aborts; the process prints "ok" and exits 0.
 #include "../../percepnet_amd/csrc/pn_model.cpp"
@@ -59,6 +60,54 @@ int main(int argc, char **argv) {
         CHECK((pn_state_first(L, t + 1, tn + 1) + L.live - 1) % L.slots == wr);
       }
   }
+
+  // the DSP half of a frame.  The slots a launcher is handed are the phases the kernels were written against, and what the
+  // back end reads at slot_r is where state_at (pn_context.h) puts the oldest live entry (j = 0) of a context's yring / eyring:
+  // p + (first + j) % slots * slot_stride, with the stride a context keeps in st[] (pn_state_size of B rows)
+  { float y[1], ey[1], *base[PN_ST_COUNT] = {};
+    base[PN_ST_YRING] = y; base[PN_ST_EYRING] = ey;
+    const size_t B = 19;
+    const PnDspSide s = pn_dsp_side(base, NULL, B);
+    for (int64_t t = 0; t < 48; t++) {
+      const PnDspSlots k = pn_dsp_slots(t);
+      CHECK(k.frame_t == t % 12 && k.slot_w == t % 6 && k.slot_r == (t + 1) % 6);
+      CHECK((const float *)pn_dsp_spec(s, k.slot_r) == y + (t % 6 + 1 + 0) % 6 * (long long)(B * 2 * PN_SPEC_BINS));
+      CHECK(pn_dsp_bands(s, k.slot_r) == ey + (t % 6 + 1 + 0) % 6 * (long long)(B * 36));
+    } }
+  // a side is exactly the table's non-network entries other than synth (the back end's), none of them shadowed
+  { int n = 0;
+    for (int e = 0; e < PN_ST_COUNT; e++) {
+      bool in_side = false;
+      for (int f : pn_kSideEntries) in_side = in_side || f == e;
+      CHECK(in_side == (e < PN_ST_C1RING && e != PN_ST_SYNTH));
+      if (in_side) { n++; CHECK(pn_kState[e].shadow == PN_SH_NONE); }
+    }
+    CHECK(n == 8 && sizeof(pn_kSideEntries) / sizeof(int) == 8);
+    float buf[PN_ST_COUNT], *base[PN_ST_COUNT];
+    for (int e = 0; e < PN_ST_COUNT; e++) base[e] = &buf[e];
+    const PnDspSide s = pn_dsp_side(base, NULL, 19);
+    CHECK(s.hist == base[PN_ST_HIST] && s.last_gain == base[PN_ST_LAST_GAIN] && (float *)s.last_period == base[PN_ST_LAST_PERIOD] && (float *)s.silence == base[PN_ST_SILENCE]);
+    CHECK((float *)s.yring == base[PN_ST_YRING] && s.eyring == base[PN_ST_EYRING] && (float *)s.Ps == base[PN_ST_PS] && s.feat == base[PN_ST_FEAT] && !s.aux && s.rows == 19);
+    CHECK((const float *)pn_dsp_spec(s, 2) == base[PN_ST_YRING] + 2 * pn_state_size(pn_kState[PN_ST_YRING], 19).slot_stride);
+    CHECK(pn_dsp_bands(s, 5) == base[PN_ST_EYRING] + 5 * pn_state_size(pn_kState[PN_ST_EYRING], 19).slot_stride);
+    // sizes: one side of a feature-generator pair is 47 148 bytes with its aux row
+    size_t words = PN_AUX_STRIDE;
+    for (int e : pn_kSideEntries) words += pn_state_size(pn_kState[e], 1).words;
+    CHECK(words * 4 == 47148);
+    CHECK(pn_state_size(pn_kState[PN_ST_HIST], 7).words == 7 * PN_HIST_STRIDE && pn_state_size(pn_kState[PN_ST_HIST], 7).slot_stride == PN_FRAME);
+    CHECK(pn_state_size(pn_kState[PN_ST_C1RING], 256).words == 5 * 256 * 128 && pn_state_size(pn_kState[PN_ST_C1RING], 256).slot_stride == 256 * 128); }
+  // the front-end families and the profiling families
+  { CHECK(sizeof(pn_kFe) / sizeof(pn_kFe[0]) == 3);
+    CHECK(pn_kFe[FE_MONO_G4].n == 1 && pn_kFe[FE_MONO_G2].n == 1 && pn_kFe[FE_SPLIT].n == 3);
+    CHECK(pn_kFe[FE_MONO_G4].fam[0] == KF_FRONTEND && pn_kFe[FE_MONO_G2].fam[0] == KF_FRONTEND);
+    CHECK(pn_kFe[FE_SPLIT].fam[0] == KF_FE_SPEC_IN && pn_kFe[FE_SPLIT].fam[1] == KF_FE_PITCH && pn_kFe[FE_SPLIT].fam[2] == KF_FE_SPEC_OUT);
+    CHECK(!strcmp(pn_kFe[FE_MONO_G4].name, "g4") && !strcmp(pn_kFe[FE_MONO_G2].name, "g2") && !strcmp(pn_kFe[FE_SPLIT].name, "split"));
+    const char *want[] = {"frontend", "fc", "conv1", "conv2", "gru512", "gru_rb", "fc_gb", "fc_rb", "backend", "fe_spec_in", "fe_pitch", "fe_spec_out"};
+    CHECK(KF_COUNT == 12 && sizeof(pn_kFamilyName) / sizeof(pn_kFamilyName[0]) == 12);
+    for (int i = 0; i < 12; i++) CHECK(!strcmp(pn_kFamilyName[i], want[i]));
+    CHECK(!strcmp(pn_kFamilyName[KF_FRONTEND], "frontend") && !strcmp(pn_kFamilyName[KF_GRU512], "gru512") && !strcmp(pn_kFamilyName[KF_BACKEND], "backend") && !strcmp(pn_kFamilyName[KF_FE_SPEC_OUT], "fe_spec_out"));
+    const int fam[PN_NLAYERS] = {KF_FC, KF_CONV1, KF_CONV2, KF_GRU512, KF_GRU512, KF_GRU512, KF_GRU512, KF_GRU_RB, KF_FC_GB, KF_FC_RB};
+    for (int li = 0; li < PN_NLAYERS; li++) CHECK(pn_kNet[li].fam == fam[li]); }
 
   // the network table.  Every plan pn_plan_for can return — small and small_gru freely; narrow 1 outside STRICT, 2 in fp32 MFMA off
   // the small dense family; direct in fp32 MFMA off both small families; rg 1|2 with direct, 1|2|3 in the shadow-operand modes,

@@ -55,6 +55,33 @@ def test_featgen_matches_oracle(oracle):
     fg.close()
 
 
+def test_featgen_front_end_families_agree_bit_for_bit(oracle):
+    """The generator runs the front-end family of its plan, like a context: PERCEPNET_FE=split|mono|g2 at creation.  19 pairs
+    (a ragged second block of the 16-streams-per-block g4 kernel, a partial group of the g2 and pitch kernels; silence pairs
+    3, 7, 11) x 14 frames (a wrap of the 12-slot history ring and of the 6-slot spectrum ring).  split against the oracle;
+    mono and g2 against split bit for bit, records (the target kernel is the same, so its inputs — both sides' band energies,
+    side outputs and periods — were equal) and PCM.  A pair costs 98 408 device bytes whatever the family."""
+    B, T = 19, 14
+    sp, no = synth.synth_pairs(B, T)
+    res = {}
+    for fam in ("split", "mono", "g2"):
+        os.environ["PERCEPNET_FE"] = fam
+        try:
+            fg = api.FeatGen(B)
+        finally:
+            del os.environ["PERCEPNET_FE"]
+        res[fam] = fg.run(sp, no)
+        fg.close()
+    orec, opcm = _oracle_pairs(oracle, sp, no)
+    _check(res["split"][0], res["split"][1], orec, opcm)
+    for fam in ("mono", "g2"):
+        assert np.array_equal(res[fam][0].view(np.uint32), res["split"][0].view(np.uint32)), fam
+        assert np.array_equal(res[fam][1], res["split"][1]), fam
+    a, b = api.FeatGen(B), api.FeatGen(1)
+    assert a.device_bytes() - b.device_bytes() == 18 * 98408
+    a.close(); b.close()
+
+
 def test_featgen_golden_records_of_compiled_reference(golden_dir):
     g = np.load(os.path.join(golden_dir, "featgen_golden.npz"))
     sp = np.stack([g["speech_0"], g["speech_2"], g["speech_3"]]); no = np.stack([g["noisy_0"], g["noisy_2"], g["noisy_3"]])
