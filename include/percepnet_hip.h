@@ -102,7 +102,8 @@ int pn_ctx_describe(const pn_ctx *ctx, char *buf, size_t buf_bytes);
    stream.  in: [n_streams][480]; out: [n_streams][480]; gr (optional, may be NULL):
    [n_streams][68] = g[34] | r[34], the reference's feature_test.raw tap (denoise.cpp:533-534).
    f32 = the rnnoise_process_frame sample convention (nominal [-1,1));
-   i16 = the CLI convention (main.cpp:34,36): in/32768.f, out = trunc(x*32768) wrapped to 16 bit.
+   i16 = the CLI convention (main.cpp:34,36): in/32768.f, out = trunc(x*32768) wrapped to 16 bit
+   (saturated instead after pn_ctx_set_output_saturate).
    in and out may alias.
    Ordering is the caller's: the launches only see what is complete on the context's stream.  A
    context created with hip_stream = NULL runs on its own NON-BLOCKING stream, which does not
@@ -157,6 +158,44 @@ int pn_ctx_set_postfilter(pn_ctx *ctx, int enable);
 float pn_atten_limit_factor(float db);
 int pn_ctx_set_atten_limit(pn_ctx *ctx, const int32_t *ids, int n, const float *db);
 int pn_ctx_get_atten_limit(const pn_ctx *ctx, float *h_db);
+/* Per-stream FRAME REPORT and SATURATING int16 output: one more kernel after the back end (csrc/pn_outstage.hip), launched only
+   while one of the two is on; with both off (the default) a frame launches exactly what it always did.
+   pn_ctx_set_report(ctx, 1): every following frame also leaves one record per stream on the device, PN_REPORT_WORDS = 8
+   little-endian 32-bit words, [n_streams][8]:
+     0  f32  in_peak       max |x| over the 480 input samples this output frame is about: the stream's input frame 6 frames
+                           (2880 samples, the engine's delay: INTEGRATION.md §2) back, in the float convention (int16 / 32768),
+                           read from the history ring; 0 for the first 6 frames of a stream after a reset
+     1  f32  in_energy     sum of x * x over those samples
+     2  f32  out_peak      max |o| over the 480 output samples o before any cast (a NaN sample is ignored here)
+     3  f32  out_energy    sum of o * o
+     4  f32  gain_mean     (sum of g_b) / 34 over the network's raw g (the first 34 words of the g|r tap)
+     5  i32  pitch_period  the period this frame's comb filter used (pn_ctx_debug_copy's buffer 13)
+     6  i32  out_clipped   output samples whose t = o * 32768 (fp32) lies outside the open interval (-32769, 32768), i.e. that do
+                           not fit an int16 after truncation; NaN counts.  Computed for the float entry points too
+     7  u32  flags         bit 0: the frame's silence flag; the other bits are 0
+   The sums are fp32 in one fixed order, so a stream's record does not depend on the batch size, its slot or the kernel family.
+   pn_ctx_set_output_saturate(ctx, 1): the int16 entry points cast t = o * 32768 as  t >= 32768 -> 32767,  t <= -32769 -> -32768,
+   NaN -> 0, otherwise trunc(t), instead of the reference CLI's wrap to the low 16 bits (main.cpp:36), which turns a sample
+   that lands on +32768 into -32768.  A sample in range is cast exactly as before.  Float outputs are never altered (with only
+   this setting on, a float frame launches nothing more).
+   Both are context-wide settings like pn_ctx_set_postfilter: they take effect from the next frame submitted and survive
+   pn_ctx_reset, pn_ctx_reset_streams and imports; the device buffers they need are allocated inside these two calls, never inside
+   a frame.  While the stage is on, the int16 entry points run the back end's float kernel into a context-owned buffer and the
+   stage casts it: the same fp32 arithmetic, so wrap-mode PCM is bit for bit what the fused cast gives.  The stage is profiled
+   under the "backend" family, which then counts two launches per frame.
+   pn_ctx_read_report: the last frame's records to h_report [n_streams][8] words (synchronising, like pn_ctx_read_features);
+   pn_ctx_read_report_dev: the same into a device buffer, asynchronous on the context's stream.  Both return -1 while the report
+   is off.  Rows of streams skipped by pn_process_*_active are unspecified for that tick; a listed stream's input figures follow
+   its own received frames.  After pn_process_i16_multi the records are the last frame's.
+   pn_host_next_report: the next pn_submit_host_* call (any of the four) also delivers ITS frame's records to h_report
+   [n_streams][8] words, copied on the device-to-host stream with h_out and under h_out's lifetime rule.  One-shot; NULL cancels a
+   pending request; -1 while the report is off. */
+#define PN_REPORT_WORDS 8
+int pn_ctx_set_report(pn_ctx *ctx, int enable);
+int pn_ctx_set_output_saturate(pn_ctx *ctx, int enable);
+int pn_ctx_read_report(pn_ctx *ctx, void *h_report);
+int pn_ctx_read_report_dev(pn_ctx *ctx, void *d_report);
+int pn_host_next_report(pn_ctx *ctx, void *h_report);
 /* n_frames consecutive frames per call: in/out are [n_frames][n_streams][480] (frame-major). */
 int pn_process_i16_multi(pn_ctx *ctx, const int16_t *d_in, int16_t *d_out, float *d_gr, int n_frames);
 /* Host-buffer convenience wrappers (H2D, process, D2H, synchronise). */

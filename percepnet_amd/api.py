@@ -17,6 +17,10 @@ FRAME = 480
 # per-stream state records (include/percepnet_hip.h): size, and the PN_SS_* verdicts of a refused record
 STREAM_STATE_BYTES = 54688
 SS_OK, SS_BAD_MAGIC, SS_BAD_VERSION, SS_BAD_SIZE, SS_BAD_MODEL, SS_BAD_ARG = 0, -1, -2, -3, -4, -5
+# per-stream frame report (include/percepnet_hip.h pn_ctx_set_report): one record of PN_REPORT_WORDS 32-bit words per stream
+REPORT_WORDS = 8
+REPORT_DTYPE = np.dtype([("in_peak", "<f4"), ("in_energy", "<f4"), ("out_peak", "<f4"), ("out_energy", "<f4"), ("gain_mean", "<f4"),
+                         ("pitch_period", "<i4"), ("out_clipped", "<i4"), ("flags", "<u4")])
 
 _vp = ctypes.c_void_p
 _lib = None
@@ -102,6 +106,11 @@ def load_library():
         L.pn_atten_limit_factor.argtypes = [ctypes.c_float]
         L.pn_ctx_set_atten_limit.argtypes = [_vp, _vp, ctypes.c_int, _vp]
         L.pn_ctx_get_atten_limit.argtypes = [_vp, _vp]
+    if hasattr(L, "pn_ctx_set_report"):
+        for name in ("pn_ctx_set_report", "pn_ctx_set_output_saturate"):
+            getattr(L, name).argtypes = [_vp, ctypes.c_int]
+        for name in ("pn_ctx_read_report", "pn_ctx_read_report_dev", "pn_host_next_report"):
+            getattr(L, name).argtypes = [_vp, _vp]
     L.pn_ctx_debug_copy.restype = ctypes.c_longlong
     L.pn_ctx_debug_copy.argtypes = [_vp, ctypes.c_int, _vp, ctypes.c_longlong]
     L.pn_ctx_set_profiling.argtypes = [_vp, ctypes.c_int]
@@ -196,6 +205,24 @@ class Context:
         v = np.ascontiguousarray(np.broadcast_to(np.asarray(db, dtype=np.float32), a.shape))
         self._chk(self.L.pn_ctx_set_atten_limit(self.h, a.ctypes.data, int(a.size), v.ctypes.data))
 
+    def set_report(self, on):
+        """Per-stream frame report from the next frame on (include/percepnet_hip.h pn_ctx_set_report): read_report()."""
+        self._chk(self.L.pn_ctx_set_report(self.h, int(bool(on))))
+
+    def set_output_saturate(self, on):
+        """int16 outputs saturate at the ends of the range instead of wrapping (pn_ctx_set_output_saturate)."""
+        self._chk(self.L.pn_ctx_set_output_saturate(self.h, int(bool(on))))
+
+    def read_report(self):
+        """-> REPORT_DTYPE [n_streams]: the last frame's records (synchronising; raises while the report is off)."""
+        rep = np.empty(self.n_streams, REPORT_DTYPE)
+        self._chk(self.L.pn_ctx_read_report(self.h, rep.ctypes.data))
+        return rep
+
+    def read_report_dev(self, d_report):
+        """Device-pointer twin of read_report (async on the context's stream): [n_streams][REPORT_WORDS] 32-bit words."""
+        self._chk(self.L.pn_ctx_read_report_dev(self.h, d_report))
+
     def atten_limit(self):
         """-> float32 [n_streams]: the attenuation limits as set, in dB (inf = off)."""
         out = np.empty(self.n_streams, np.float32)
@@ -236,11 +263,16 @@ class Context:
         self._chk(self.L.pn_ctx_debug_inject_launch_failure(self.h, int(bool(enable))))
 
     # pipelined host-buffer entry points (raw host pointers; the buffers should be pinned and must outlive delivery)
-    def submit_host_i16(self, h_in, h_out, h_gr=None):
+    # h_report (optional): this frame's report records go there too, [n_streams][REPORT_WORDS] words, under h_out's lifetime rule
+    def submit_host_i16(self, h_in, h_out, h_gr=None, h_report=None):
+        if h_report is not None:
+            self._chk(self.L.pn_host_next_report(self.h, h_report))
         self._chk(self.L.pn_submit_host_i16(self.h, h_in, h_out, h_gr))
 
-    def submit_host_i16_active(self, h_in, h_out, h_gr, ids):
+    def submit_host_i16_active(self, h_in, h_out, h_gr, ids, h_report=None):
         a = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).ravel())
+        if h_report is not None:
+            self._chk(self.L.pn_host_next_report(self.h, h_report))
         self._chk(self.L.pn_submit_host_i16_active(self.h, h_in, h_out, h_gr, a.ctypes.data, int(a.size)))
 
     def pipe_streams(self):

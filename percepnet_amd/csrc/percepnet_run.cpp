@@ -4,12 +4,18 @@
 // mono 48 kHz in; (frames-1)*480 samples out (first output frame dropped, main.cpp:37; partial tail frame
 // dropped, main.cpp:32-33); with a single pair ./feature_test.raw gets 68 floats per frame.
 //
-//   percepnet_run [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--slots N]
+//   percepnet_run [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N]
 //                 [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
 //                 in0.pcm out0.pcm [in1.pcm out1.pcm ...]
 //
 // --atten-lim DB: every stream takes out at most DB dB of noise (pn_ctx_set_atten_limit; 0 = the input, delayed; default: no
 // limit).  A slot reset clears a stream's limit (a reset slot is a new call), so the limit is set again on every reset slot.
+//
+// --saturate: the int16 output saturates at +-full scale instead of wrapping like main.cpp:36 (pn_ctx_set_output_saturate).
+// --report: one line per pair on stdout when its output file is complete (pn_ctx_set_report): the frames written, how many of
+// their samples left the int16 range, the largest |sample| before the cast, and 10 log10(output energy / input energy) over
+// those frames (the input delayed like the output).  Both are settings of the context: a slot reset leaves them on, so unlike
+// --atten-lim they need no setting again on a reused slot; the per-pair sums start over with every pair.
 //
 // --slots N: at most N concurrent streams per device; further pairs wait and take over the slot of a pair that has ended
 // (per-stream re-initialisation on the device, pn_ctx_reset_streams) — a directory of recordings of different lengths goes
@@ -42,9 +48,10 @@ struct ShardRes {
   FILE *ftap = NULL;
   // one of three rotating pinned buffer sets; file[s] = the output file the frame of slot s belongs to (NULL: slot idle),
   // skip[s] = that frame is the pair's first output frame, which main.cpp:37 drops
-  struct Slot { int16_t *in = NULL, *out = NULL; float *gr = NULL; std::vector<FILE *> file; std::vector<char> skip, last; } slot[3];
+  // (--report) rep: the frame's report records, pair[s]: the pair the frame of slot s belongs to
+  struct Slot { int16_t *in = NULL, *out = NULL; float *gr = NULL; uint32_t *rep = NULL; std::vector<FILE *> file; std::vector<char> skip, last; std::vector<int> pair; } slot[3];
   ~ShardRes() {
-    for (auto &sl : slot) { pn_host_free(sl.in); pn_host_free(sl.out); pn_host_free(sl.gr); }
+    for (auto &sl : slot) { pn_host_free(sl.in); pn_host_free(sl.out); pn_host_free(sl.gr); pn_host_free(sl.rep); }
     for (FILE *f : fin) if (f) fclose(f);
     for (FILE *f : fout) if (f) fclose(f);
     if (ftap) fclose(ftap);
@@ -59,6 +66,9 @@ struct ShardRes {
 // waiting pair starts there on the following frame, while the other slots keep running.
 static bool g_numa = true, g_verbose = false;
 static float g_atten_lim = INFINITY;                  // --atten-lim: dB for every stream (inf: not set)
+static bool g_saturate = false, g_report = false;     // --saturate, --report
+// --report: what a pair's written frames add up to (one report record = PN_REPORT_WORDS words, include/percepnet_hip.h)
+struct PairStat { long frames = 0; long long clipped = 0; float peak = 0.f; double e_in = 0, e_out = 0; };
 static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, int postfilter, bool tap, int n_slots) {
   const int P = sh->count, B = n_slots > 0 && n_slots < P ? n_slots : P;
   auto fail = [&](int rc, const std::string &msg) { sh->rc = rc; sh->err = msg; };
@@ -74,6 +84,7 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
   pn_ctx *cx = R.cx;
   if (!cx) return fail(3, std::string("pn_ctx_create: ") + pn_last_error());
   if (postfilter) pn_ctx_set_postfilter(cx, 1);
+  if ((g_saturate && pn_ctx_set_output_saturate(cx, 1)) || (g_report && pn_ctx_set_report(cx, 1))) return fail(3, pn_last_error());
   auto set_limit = [&](const int32_t *ids, int n) {     // --atten-lim on these slots (after creation and after every slot reset)
     if (isinf(g_atten_lim) || n == 0) return 0;
     std::vector<float> db(n, g_atten_lim);
@@ -87,9 +98,11 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
   std::vector<FILE *> &fin = R.fin, &fout = R.fout;
   fin.assign(B, NULL); fout.assign(B, NULL);
   int next_pair = 0;
+  std::vector<int> cur_pair(B, 0);
+  std::vector<PairStat> stat(g_report ? P : 0);
   auto open_pair = [&](int s) -> bool {                 // the next waiting pair starts playing in slot s
     const char *pi = paths[2 * (sh->first + next_pair)], *po = paths[2 * (sh->first + next_pair) + 1];
-    next_pair++;
+    cur_pair[s] = next_pair++;
     fin[s] = fopen(pi, "rb"); fout[s] = fopen(po, "wb");
     if (!fin[s] || !fout[s]) { fail(4, std::string("cannot open ") + pi + " / " + po); return false; }
     return true;
@@ -106,8 +119,9 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
     sl.in = (int16_t *)pn_host_alloc((size_t)B * PN_FRAME_SIZE * sizeof(int16_t));
     sl.out = (int16_t *)pn_host_alloc((size_t)B * PN_FRAME_SIZE * sizeof(int16_t));
     sl.gr = (float *)pn_host_alloc((size_t)B * 68 * sizeof(float));
-    if (!sl.in || !sl.out || !sl.gr) return fail(5, pn_last_error());
-    sl.file.assign(B, NULL); sl.skip.assign(B, 0); sl.last.assign(B, 0);
+    if (g_report) sl.rep = (uint32_t *)pn_host_alloc((size_t)B * PN_REPORT_WORDS * sizeof(uint32_t));
+    if (!sl.in || !sl.out || !sl.gr || (g_report && !sl.rep)) return fail(5, pn_last_error());
+    sl.file.assign(B, NULL); sl.skip.assign(B, 0); sl.last.assign(B, 0); sl.pair.assign(B, 0);
   }
   std::vector<char> first(B, 1);
   auto flush = [&](Slot &sl) {                       // main.cpp:36-38 for every stream that supplied this frame
@@ -115,6 +129,21 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
       if (!sl.file[s]) continue;
       if (ftap) fwrite(&sl.gr[(size_t)s * 68], sizeof(float), 68, ftap);
       if (!sl.skip[s]) fwrite(&sl.out[(size_t)s * PN_FRAME_SIZE], sizeof(int16_t), PN_FRAME_SIZE, sl.file[s]);
+      if (g_report) {
+        PairStat &ps = stat[sl.pair[s]];
+        if (!sl.skip[s]) {
+          const uint32_t *w = sl.rep + (size_t)s * PN_REPORT_WORDS;
+          float f[4];
+          memcpy(f, w, sizeof(f));                    // in_peak, in_energy, out_peak, out_energy
+          ps.frames++; ps.clipped += (int32_t)w[6]; ps.e_in += f[1]; ps.e_out += f[3];
+          if (f[2] > ps.peak) ps.peak = f[2];
+        }
+        if (sl.last[s]) {
+          char level[32] = "n/a";
+          if (ps.e_in > 0 && ps.e_out > 0) snprintf(level, sizeof(level), "%.2f dB", 10 * log10(ps.e_out / ps.e_in));
+          printf("%s: frames %ld clipped %lld peak %.6f level %s\n", paths[2 * (sh->first + sl.pair[s]) + 1], ps.frames, ps.clipped, (double)ps.peak, level);
+        }
+      }
       if (sl.last[s]) { fclose(sl.file[s]); }        // the pair's last frame has been written: its output file is complete
     }
   };
@@ -140,12 +169,13 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
         }
         if (!fin[s]) n_alive--;
       }
-      if (fin[s]) { sl.file[s] = fout[s]; sl.skip[s] = first[s]; first[s] = 0; }
+      if (fin[s]) { sl.file[s] = fout[s]; sl.skip[s] = first[s]; first[s] = 0; sl.pair[s] = cur_pair[s]; }
       else memset(x, 0, PN_FRAME_SIZE * sizeof(int16_t));
     }
     if (n_alive == 0) break;
     if (!restart.empty() && (pn_ctx_reset_streams(cx, restart.data(), (int)restart.size()) ||
                              set_limit(restart.data(), (int)restart.size()))) return fail(5, pn_last_error());
+    if (g_report && pn_host_next_report(cx, sl.rep)) return fail(5, pn_last_error());
     if (pn_submit_host_i16(cx, sl.in, sl.out, sl.gr)) return fail(5, pn_last_error());
     if (t >= 2) flush(slot[(t - 2) % 3]);
   }
@@ -169,6 +199,8 @@ int main(int argc, char **argv) {
       g_atten_lim = strtof(v, &end);
       if (end == v || *end || !(g_atten_lim >= 0.f)) { fprintf(stderr, "--atten-lim: expected a number of dB >= 0 (inf = off), got '%s'\n", v); return 1; }
     }
+    else if (!strcmp(argv[ai], "--saturate")) g_saturate = true;     // int16 output saturates instead of wrapping (pn_ctx_set_output_saturate)
+    else if (!strcmp(argv[ai], "--report")) g_report = true;         // one line of levels and clipping per pair (pn_ctx_set_report)
     else if (!strcmp(argv[ai], "--no-numa")) g_numa = false;         // leave the host threads' CPU affinity alone
     else if (!strcmp(argv[ai], "--verbose")) g_verbose = true;       // one line per device: its NUMA binding
     else if (!strcmp(argv[ai], "--slots") && ai + 1 < argc) n_slots = atoi(argv[++ai]);   // concurrent streams per device: pairs queue for them
@@ -184,7 +216,7 @@ int main(int argc, char **argv) {
   if (devices.empty()) devices.push_back(0);
   const int nfiles = argc - ai;
   if (nfiles < 2 || (nfiles & 1)) {
-    fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--slots N] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv[0]);
+    fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv[0]);
     return 1;
   }
   const int B = nfiles / 2;

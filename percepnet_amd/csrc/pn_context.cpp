@@ -480,10 +480,20 @@ static int process_dev(pn_ctx *c, const void *d_in, void *d_out, float *d_gr, in
     pn_launch_fe(c->stream, c->tables, c->B, c->plan.fe, i, s, k, in, c->dsp_grid_cap);
   }
   if (launch_rnn(c)) return -1;                        // a refused launch fails the frame (pn_last_error says which layer)
+  // the output stage runs while it has something to do: a report to write, or int16 rows to saturate.  It then owns the int16
+  // cast: the back end's float kernel writes the context's own rows and the stage casts them into the caller's
+  const bool stage = c->report_on || (c->saturate && is_i16), staged_cast = stage && is_i16;
   { Scope sc(c, KF_BACKEND);
     // X(t), and Ex(t) for the post-filter: the oldest live look-ahead slot
     pn_launch_backend(c->stream, c->tables, c->B, pn_dsp_spec(s, k.slot_r), s.Ps, gr, c->postfilter ? pn_dsp_bands(s, k.slot_r) : nullptr, s.silence,
-                      c->st[PN_ST_SYNTH].p, d_out, is_i16, c->dsp_grid_cap, c->n_limited > 0 ? c->lam_mu : nullptr); }      // no stream limited: the plain back end
+                      c->st[PN_ST_SYNTH].p, staged_cast ? (void *)c->stage_o : d_out, staged_cast ? 0 : is_i16, c->dsp_grid_cap,
+                      c->n_limited > 0 ? c->lam_mu : nullptr); }      // no stream limited: the plain back end
+  if (stage) {
+    Scope sc(c, KF_BACKEND);
+    // the input frame this output frame is about: frame t - 6 of the history ring (the engine's delay)
+    pn_launch_outstage(c->stream, c->B, staged_cast ? c->stage_o : (const float *)d_out, s, (k.frame_t + 6) % PN_HIST_FRAMES, gr,
+                       is_i16 ? (int16_t *)d_out : nullptr, c->saturate, c->report_on ? c->report : nullptr);
+  }
   if (d_gr) PN_HIP_CHECK(hipMemcpyAsync(d_gr, gr, (size_t)c->B * 68 * 4, hipMemcpyDeviceToDevice, c->stream));
   PN_HIP_CHECK(hipGetLastError());
   c->t++; c->tn++;
@@ -503,6 +513,50 @@ extern "C" int pn_ctx_debug_inject_launch_failure(pn_ctx *c, int enable) {
 extern "C" int pn_ctx_set_postfilter(pn_ctx *c, int enable) {
   if (!c) { pn_set_error("NULL argument"); return -1; }
   c->postfilter = enable != 0;
+  return 0;
+}
+
+// ---- per-stream frame report, saturating int16 output (pn_outstage.hip) ---------------------------------------------------
+// Context-wide settings; what the stage needs is allocated here, never inside a frame (the lam_mu pattern).
+static int stage_buffers(pn_ctx *c, bool report) {
+  if (!c->stage_o && dev_alloc(c, (void **)&c->stage_o, (size_t)c->B * PN_FRAME * sizeof(float), false)) return -1;
+  if (report && !c->report && dev_alloc(c, (void **)&c->report, (size_t)c->B * PN_REPORT_WORDS * 4, true)) return -1;
+  return 0;
+}
+extern "C" int pn_ctx_set_report(pn_ctx *c, int enable) {
+  if (!c) { pn_set_error("NULL argument"); return -1; }
+  if (enable) { PN_ON_DEVICE(c); if (stage_buffers(c, true)) return -1; }
+  else c->next_report = NULL;                            // a pending pn_host_next_report goes with it
+  c->report_on = enable != 0;
+  return 0;
+}
+extern "C" int pn_ctx_set_output_saturate(pn_ctx *c, int enable) {
+  if (!c) { pn_set_error("NULL argument"); return -1; }
+  if (enable) { PN_ON_DEVICE(c); if (stage_buffers(c, false)) return -1; }
+  c->saturate = enable != 0;
+  return 0;
+}
+static int report_copy(pn_ctx *c, void *dst, hipMemcpyKind kind) {
+  if (!c || !dst) { pn_set_error("NULL argument"); return -1; }
+  if (!c->report_on) { pn_set_error("the frame report is off (pn_ctx_set_report)"); return -1; }
+  PN_ON_DEVICE(c);
+  PN_HIP_CHECK(hipMemcpyAsync(dst, c->report, (size_t)c->B * PN_REPORT_WORDS * 4, kind, c->stream));
+  if (kind == hipMemcpyDeviceToHost) PN_HIP_CHECK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+extern "C" int pn_ctx_read_report(pn_ctx *c, void *h_report) { return report_copy(c, h_report, hipMemcpyDeviceToHost); }
+extern "C" int pn_ctx_read_report_dev(pn_ctx *c, void *d_report) { return report_copy(c, d_report, hipMemcpyDeviceToDevice); }
+// The next pn_submit_host_* call copies its frame's records into its pipeline slot on the context's stream and from there to
+// h_report on the device-to-host stream, behind h_out.  (NULL cancels; the slot copies are allocated here.)
+extern "C" int pn_host_next_report(pn_ctx *c, void *h_report) {
+  if (!c) { pn_set_error("NULL argument"); return -1; }
+  if (!c->report_on) { pn_set_error("the frame report is off (pn_ctx_set_report)"); return -1; }
+  if (h_report) {
+    PN_ON_DEVICE(c);
+    for (int k = 0; k < 2; k++)
+      if (!c->pipe.report[k] && dev_alloc(c, (void **)&c->pipe.report[k], (size_t)c->B * PN_REPORT_WORDS * 4, false)) return -1;
+  }
+  c->next_report = h_report;
   return 0;
 }
 
@@ -762,6 +816,8 @@ static int submit_host(pn_ctx *c, const void *h_in, void *h_out, float *h_gr, in
   if (pipe_init(c)) return -1;
   pn_ctx::Pipe &P = c->pipe;
   const int k = (int)(P.submitted & 1);
+  void *const h_report = c->next_report;                     // pn_host_next_report: this call's, whatever becomes of it
+  c->next_report = NULL;
   if (P.submitted >= 2) PN_HIP_CHECK(hipEventSynchronize(P.delivered[k]));     // frame submitted-2 delivered: slot k is free
   const size_t nbytes = (size_t)c->B * PN_FRAME * (is_i16 ? 2 : 4);
   PN_HIP_CHECK(hipMemcpyAsync(P.in[k], h_in, nbytes, hipMemcpyHostToDevice, P.h2d));
@@ -769,10 +825,13 @@ static int submit_host(pn_ctx *c, const void *h_in, void *h_out, float *h_gr, in
   PN_HIP_CHECK(hipStreamWaitEvent(c->stream, P.in_ready[k], 0));
   if (active ? process_active(c, P.in[k], P.out[k], h_gr ? P.gr[k] : NULL, is_i16, ids, n)
              : process_dev(c, P.in[k], P.out[k], h_gr ? P.gr[k] : NULL, is_i16)) return -1;
+  const size_t report_bytes = (size_t)c->B * PN_REPORT_WORDS * 4;
+  if (h_report) PN_HIP_CHECK(hipMemcpyAsync(P.report[k], c->report, report_bytes, hipMemcpyDeviceToDevice, c->stream));   // the next frame rewrites c->report
   PN_HIP_CHECK(hipEventRecord(P.done[k], c->stream));
   PN_HIP_CHECK(hipStreamWaitEvent(P.d2h, P.done[k], 0));
   PN_HIP_CHECK(hipMemcpyAsync(h_out, P.out[k], nbytes, hipMemcpyDeviceToHost, P.d2h));
   if (h_gr) PN_HIP_CHECK(hipMemcpyAsync(h_gr, P.gr[k], (size_t)c->B * 68 * 4, hipMemcpyDeviceToHost, P.d2h));
+  if (h_report) PN_HIP_CHECK(hipMemcpyAsync(h_report, P.report[k], report_bytes, hipMemcpyDeviceToHost, P.d2h));
   PN_HIP_CHECK(hipEventRecord(P.delivered[k], P.d2h));
   P.submitted++;
   return 0;

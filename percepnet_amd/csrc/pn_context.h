@@ -54,7 +54,13 @@ struct pn_ctx {
   float2 *lam_mu = NULL;
   std::vector<float> atten_db;
   int n_limited = 0;
-  bool x3_sat = false;             // PERCEPNET_X3_SATCOUNT=1 (shadow-operand modes): count operand values clamped to the fp16 range
+  // the output stage (pn_outstage.hip; pn_ctx_set_report, pn_ctx_set_output_saturate): launched after the back end while either
+  // setting is on.  stage_o: [B][480] fp32 rows the back end's float kernel writes for an int16 entry point; report: [B][8] words.
+  // Both are allocated by the two setters.  next_report: pn_host_next_report's pending host destination (one-shot)
+  bool report_on = false, saturate = false;
+  float *stage_o = NULL; uint32_t *report = NULL;
+  void *next_report = NULL;
+  bool x3_sat = false;            // PERCEPNET_X3_SATCOUNT=1 (shadow-operand modes): count operand values clamped to the fp16 range
   int dsp_grid_cap = 0;            // > 0 only in the DSP self-test's temporary context: its DSP launches use that many blocks
   bool inject_bad_launch = false;  // pn_ctx_debug_inject_launch_failure (tests): the next frames hand fc a geometry its launcher refuses
   std::vector<void *> allocs;
@@ -70,6 +76,7 @@ struct pn_ctx {
     hipEvent_t in_ready[2] = {nullptr, nullptr}, done[2] = {nullptr, nullptr}, delivered[2] = {nullptr, nullptr};
     void *in[2] = {nullptr, nullptr}, *out[2] = {nullptr, nullptr};
     float *gr[2] = {nullptr, nullptr};
+    uint32_t *report[2] = {nullptr, nullptr};   // per-slot copy of the frame's report records (pn_host_next_report allocates them)
     int64_t submitted = 0;
     char kind[3] = {'?', '?', 0};             // how each copy stream was obtained: n (default priority, probed) / h / l (priority stream)
   } pipe;

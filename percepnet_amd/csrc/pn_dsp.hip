@@ -16,6 +16,7 @@
 // PCM cast write straight to HBM.
 #include "pn_fft960.h"
 #include "pn_launch.h"
+#include "pn_pcm.h"           // pn_f2s: the CLI's float -> int16 cast
 
 #define LANES 64
 #ifndef PN_DSP_WPB
@@ -40,13 +41,6 @@ struct PnDspShared {
   uint8_t band[PN_SPEC_BINS];
   PnDspWaveLds w[WPB];
 };
-
-// float -> int16 as the reference CLI's x86-64 build does it (main.cpp:36): truncate toward zero
-// to int32 (cvttss2si; NaN / out of range -> 0x80000000), keep the low 16 bits.
-__device__ __forceinline__ int16_t pn_f2s(float v) {
-  const int32_t t = (fabsf(v) < 2147483648.f) ? (int32_t)v : (int32_t)0x80000000;
-  return (int16_t)(uint16_t)((uint32_t)t & 0xffffu);
-}
 
 template <typename P, typename... R> __device__ __forceinline__ P pn_first_arg(P p, R...) { return p; }
 

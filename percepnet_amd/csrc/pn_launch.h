@@ -68,6 +68,12 @@ void pn_launch_backend(hipStream_t st, const PnTables *T, int n_streams, const f
                        const float *gr, const float *ex_postfilter /* NULL = off */, const int *silence, float *synth_mem,
                        void *out, int out_is_i16, int grid_cap,
                        const float2 *lam_mu /* [n_streams] (lam, mu) of the attenuation limit; NULL = no stream limited */);
+// the output stage (pn_outstage.hip), after the back end while the frame report or the saturating cast is on: o [n_streams][480]
+// are the frame's fp32 output samples; pcm (NULL: a float entry point) receives their int16 cast, wrapping like the back end's
+// fused one or saturating; report (NULL: off) [n_streams][PN_REPORT_WORDS] the records, whose input figures come from slot
+// hist_slot of the side's history ring.  One wavefront per stream, no grid cap.
+void pn_launch_outstage(hipStream_t st, int n_streams, const float *o, const PnDspSide &s, int hist_slot, const float *gr,
+                        int16_t *pcm, int saturate, void *report);
 // split-precision variant (pn_nn_x3.hip): operands as fp16 hi/lo planes in fragment order; panels of A / h_oldS / outS /
 // h_newS are the uint4* shadows (carried as float* in PnSegs), width = logical columns (multiple of 32)
 size_t pn_packed_halfs_x3(int k_alloc, int ncols, int ct_round, int np /* planes: 2 = hi+lo (split precision), 1 = fp16 operands */);
