@@ -89,7 +89,6 @@ size_t pn_layer_floats(int kind, int nin, int nn, int ks, size_t *nb, size_t *nw
 size_t pn_packed_floats(int k_alloc, int ncols, int ct_round);
 void pn_pack_weights(const float *W, int K, int k_alloc, int ncols, int ct_round, float *Wp);
 int pn_ct_padded(int ncols, int ct_round);
-int pn_dense_nt(int N);
 size_t pn_packed_floats_n16(int K, int ncols);
 void pn_pack_weights_n16(const float *W, int K, int ncols, float *Wq);
 

@@ -7,7 +7,6 @@
 #include <vector>
 #include "pn_launch.h"       // pn_common.h, pn_network.h (plan, state table, DSP side, kernel families), the public header
 
-struct DevLayer { float *bias, *w, *rw, *wp, *rwp, *wq; };   // wq: narrow layers of small-batch fp32 contexts (pn_pack_weights_n16)
 struct SharedWeights;             // pn_network.cpp
 // SHA-256 of the model content (pn_model_from_sources: arrays + activations + reset_after), array length, device, nn_mode, narrow
 // layers packed for the n16 kernel.  The digest IS the identity: no host copy of the model is kept and nothing is compared byte for

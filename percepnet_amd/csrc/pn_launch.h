@@ -1,5 +1,6 @@
 // Kernel launchers shared by the host files (pn_context.cpp, pn_network.cpp, pn_featgen.cpp).  The DSP ones take the
-// descriptions of pn_dsp_layout.h (a side, the slots of a frame, its input), the network ones the panels of pn_network.h.
+// descriptions of pn_dsp_layout.h (a side, the slots of a frame, its input), the network ones one record of a layer's launch
+// (PnLayerLaunch, below) and begin with the rule of their kernel kind (pn_network.h).
 #pragma once
 #include "pn_common.h"
 #include "pn_network.h"       // PnSegs, and through it pn_dsp_layout.h and pn_state_layout.h
@@ -74,40 +75,36 @@ void pn_launch_backend(hipStream_t st, const PnTables *T, int n_streams, const f
 // hist_slot of the side's history ring.  One wavefront per stream, no grid cap.
 void pn_launch_outstage(hipStream_t st, int n_streams, const float *o, const PnDspSide &s, int hist_slot, const float *gr,
                         int16_t *pcm, int saturate, void *report);
-// split-precision variant (pn_nn_x3.hip): operands as fp16 hi/lo planes in fragment order; panels of A / h_oldS / outS /
-// h_newS are the uint4* shadows (carried as float* in PnSegs), width = logical columns (multiple of 32)
+// ---- the network launchers (pn_nn*.hip) -----------------------------------------------------------------------------------------
+// Device pointers of a layer's biases and weights in the formats of pn_network.h: raw (w, rw), packed fp32 or fp16 planes (wp,
+// rwp), the 16x16x4 packing of a narrow layer (wq)
+struct DevLayer { float *bias, *w, *rw, *wp, *rwp, *wq; };
+// One launch of one layer over n_rows rows, as launch_rnn_rows (pn_network.cpp) assembles it; every launcher takes this record
+// and reads the fields its kernel has a use for.
+struct PnLayerLaunch {
+  PnSegs A, S;                       // input panels: fp32 rows, and their fragment-order operand shadows (uint4* carried as float*; NULL
+                                     // where the entry keeps none) for the kinds that read those (pn_kernel_reads_shadows)
+  const float *bias;
+  const void *w, *rw;                // input / recurrent weights in the format of the kind (pn_kernel_weight_format)
+  int N, act; const float *tansig;   // neurons, activation, the activation table
+  float *out; int ldo;               // output rows (a GRU: the new state, ldo = N)
+  void *outS; int nts_out;           // shadow of the output, a buffer nts_out column tiles wide; NULL: the kind writes none
+  const float *h_old; const void *h_oldS;   // GRU: the state it reads and that state's shadow; NULL for dense layers
+  int n_rows, rg, np;                // rg: row groups of 32 per wave (pn_plan.h; 3 = 2 with the GRUs on the paired-phase kernel); np: weight planes
+};
+// A launcher begins with the rule of its kind (pn_kernel_geometry_ok, pn_network.h) and returns 0, or -1 (pn_set_error) WITHOUT
+// launching when it refuses the geometry: the caller fails the frame (launch_rnn -> pn_process_*), it must never report a frame
+// whose layer outputs are stale.  One launcher per (kind, dense | GRU); pn_launch_dense also serves batch_sh: handed outS it runs
+// the kernel that writes it.  The table kind -> launchers is pn_network.cpp's.
+typedef int PnLayerLauncher(hipStream_t, const PnLayerLaunch &);
+PnLayerLauncher pn_launch_dense_strict, pn_launch_gru_strict, pn_launch_dense, pn_launch_gru;         // pn_nn.hip
+PnLayerLauncher pn_launch_dense_small, pn_launch_gru_small, pn_launch_dense_n16, pn_launch_dense_n48; // pn_nn_small.hip, pn_nn_n48.hip
+PnLayerLauncher pn_launch_dense_x3, pn_launch_gru_x3, pn_launch_gru_d;   // pn_nn_x3.hip, pn_nn_d.hip (bit-identical to pn_launch_gru)
+// split-precision packing (pn_nn_x3.hip): fp16 hi / lo planes in fragment order
 size_t pn_packed_halfs_x3(int k_alloc, int ncols, int ct_round, int np /* planes: 2 = hi+lo (split precision), 1 = fp16 operands */);
 int pn_pack_weights_x3(const float *W, int K, int k_alloc, int ncols, int ct_round, int np, void *Wp);   // -1: weight outside fp16 range
-int pn_dense_x3_nt(int N);
-int pn_launch_dense_x3(hipStream_t st, const PnSegs &A, const void *Wp, const float *bias, int N, int act,
-                        const float *tansig, float *out, int ldo, void *outS, int nts_out, int n_rows, int rg /* row groups of 32 per wave: 1 | 2 */, int np);
-int pn_launch_gru_x3(hipStream_t st, const PnSegs &X, const float *h_old, const void *h_oldS, const void *Wp,
-                      const void *Up, const float *b, int N, int act, const float *tansig, float *h_new, void *h_newS,
-                      int n_rows, int rg, int np);
 int pn_x3_sat_set(int enable);          // debug counter of operand values clamped to +-65504 (current device): reset + switch
 long long pn_x3_sat_read();             // ... and its value, or -1
+// operand shadows re-derived from fp32 rows: fp16 planes (pn_nn_x3.hip), fp32 fragments of the direct-operand family (pn_nn_d.hip)
 int pn_launch_split_x3(hipStream_t st, const float *src, int ld, int width, void *S, int n_rows_padded, int np);
-// direct-operand fp32 GRU kernels (pn_nn_d.hip): the large-batch GRU steps of nn_mode PN_NN_MFMA.  X panels / h_oldS / h_newS are the
-// uint4* fragment-order fp32 shadows (carried as float* in PnSegs), Wp / Up the fp32 packed tiles of pn_pack_weights; bit-identical
-// to pn_launch_gru.  rg: row groups of 32 per wave (1 | 2)
-int pn_launch_gru_d(hipStream_t st, const PnSegs &X, const float *h_old, const void *h_oldS, const float *Wp,
-                    const float *Up, const float *b, int N, int act, const float *tansig, float *h_new, void *h_newS,
-                    int n_rows, int rg);
 int pn_launch_split_d(hipStream_t st, const float *src, int ld, int width, void *S, int n_rows);
-// narrow layers (N <= 48) of small-batch contexts: 16x16x4 MFMA tiles, one wave per (16 rows, 16 columns) (pn_nn_small.hip)
-int pn_launch_dense_n16(hipStream_t st, const PnSegs &A, const float *Wq, const float *bias, int N, int act,
-                         const float *tansig, float *out, int ldo, int n_rows);
-// the batch form for large batches (pn_nn_n48.hip): 128-row blocks x 48 columns of 16x16x4 tiles, the same packed weights Wq
-int pn_launch_dense_n48(hipStream_t st, const PnSegs &A, const float *Wq, const float *bias, int N, int act,
-                        const float *tansig, float *out, int ldo, int n_rows);
-// The network launchers return 0, or -1 (pn_set_error) WITHOUT launching when they refuse a geometry: the caller fails
-// the frame (launch_rnn -> pn_process_*), it must never report a frame whose layer outputs are stale.
-// pn_check_dense_geometry / pn_check_gru_geometry (pn_launch_check.h) are the HIP-free predicates behind the refusals.
-// small: 1 = the small-batch kernel family (pn_nn_small.hip), 0 = the batch-GEMM kernels; ignored when strict.
-// outS (optional, batch kernels only): fragment-order fp32 shadow of `out`, a buffer nts_out column tiles wide (pn_nn_common.h)
-int pn_launch_dense(hipStream_t st, int strict, const PnSegs &A, const float *W, const float *Wp, const float *bias,
-                     int N, int act, const float *tansig, float *out, int ldo, int n_rows, int small, void *outS = nullptr, int nts_out = 0);
-int pn_launch_gru(hipStream_t st, int strict, const PnSegs &X, const float *h_old, const float *W, const float *U,
-                   const float *Wp, const float *Up, const float *b, int N, int act, const float *tansig,
-                   float *h_new, int n_rows, int small);
-

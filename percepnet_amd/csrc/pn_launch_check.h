@@ -1,9 +1,14 @@
-// Geometry predicates of the network launchers (pn_nn.hip, pn_nn_small.hip, pn_nn_x3.hip) — HIP-free, so that the
-// refusals can be exercised without a GPU (pn_debug_check_launch, tests/test_abi.py).  A launcher that refuses returns -1
-// with pn_set_error and launches nothing; launch_rnn / pn_process_* fail the frame (round-4 verdict item 8: a refused
-// launch used to return silently and the frame completed with stale layer outputs).
+// Geometry predicates of the network launchers (pn_nn*.hip) — HIP-free, so that the refusals can be exercised without a
+// GPU (pn_debug_check_launch, tests/test_abi.py; tests/c/host_sanitize.cpp).  These are the building blocks; which of
+// them a kernel kind's launcher applies, with which parameters, is pn_kernel_geometry_ok (pn_network.h), the one rule
+// that the launchers, the debug entry point and the harness all call.  A launcher that refuses returns -1 with
+// pn_set_error and launches nothing; launch_rnn / pn_process_* fail the frame (round-4 verdict item 8: a refused launch
+// used to return silently and the frame completed with stale layer outputs).
 #pragma once
 void pn_set_error(const char *fmt, ...);
+
+#define N16_DEPTH 8       // 16-k groups per register set of pn_dense_n16_kernel (pn_nn_small.hip): its K loop runs whole sets
+#define PN_N48_COLS 48    // output columns of a block of pn_dense_n48_kernel (pn_nn_n48.hip), which runs one block per row tile
 
 // dense / conv1d layers: the K range is n_panels panels of EQUAL width, swept as 32-column tiles that the software
 // pipelines consume in PAIRS (the prefetch clamps to the last tile: an odd count would accumulate it twice).
@@ -21,6 +26,13 @@ static inline int pn_check_dense_geometry(const char *who, int n_panels, const i
 static inline int pn_check_gru_geometry(const char *who, int n_panels, const int *width, int N) {
   if (pn_check_dense_geometry(who, n_panels, width, 1)) return -1;
   if (N < 32 || (N & 31) || ((N / 32) & 1)) { pn_set_error("%s: %d neurons (need an even number of 32-column tiles)", who, N); return -1; }
+  return 0;
+}
+// GRU layers of the fp32 small-batch kernel: input and recurrent K-tiles alternate between two register sets as ONE sequence
+static inline int pn_check_gru_small_geometry(const char *who, int n_panels, const int *width, int N) {
+  for (int j = 1; j < n_panels; j++) if (width[j] != width[0]) { pn_set_error("%s: unequal panel widths", who); return -1; }
+  const int KTx = (width[0] + 31) / 32 * n_panels;
+  if ((N & 31) || ((KTx + N / 32) & 1)) { pn_set_error("%s: %d input + %d recurrent K-tiles (the sum must be even, N whole tiles)", who, KTx, N / 32); return -1; }
   return 0;
 }
 // narrow layers on 16x16x4 tiles: k-groups of 16 in bursts of `depth`, power-of-two groups per panel

@@ -38,7 +38,7 @@ static SharedWeights *build_weights(pn_ctx *c, const pn_model *model, int nn_mod
     const int K = H.nin * H.ks, ncols = H.nn * (gru ? 3 : 1);
     // a packed array: its host copy dies with this scope, so the copy has executed when this returns
     auto put = [&](float **dst, const void *src, size_t n_floats) { return upload_w(c, w, dst, (const float *)src, n_floats) || hipStreamSynchronize(c->stream) != hipSuccess; };
-    // one matrix (k rows, k_alloc swept; ctr: column-tile rounding of the kernel family) in the tile order of the layer's format
+    // one matrix (k rows, k_alloc swept; ctr: column-tile rounding of the layer's kernel) in the tile order of the layer's format
     auto pack = [&](float **dst, const float *W, int k, int k_alloc, int ctr, const char *what) {
       if (fmt != PN_WF_X3) {
         std::vector<float> f(pn_packed_floats(k_alloc, ncols, ctr));
@@ -54,7 +54,7 @@ static SharedWeights *build_weights(pn_ctx *c, const pn_model *model, int nn_mod
       if (upload_w(c, w, &D.w, H.w, nw) || (nr && upload_w(c, w, &D.rw, H.rw, nr))) goto fail_w;
       continue;
     }
-    if (pack(&D.wp, H.w, K, pn_net_k(li), gru ? 1 : (fmt == PN_WF_X3 ? pn_dense_x3_nt(H.nn) : pn_dense_nt(H.nn)), "")) goto fail_w;   // (fc sweeps the zero-padded feature panel)
+    if (pack(&D.wp, H.w, K, pn_net_k(li), pn_layer_ct_round(nn_mode, narrow, li), "")) goto fail_w;   // (fc sweeps the zero-padded feature panel)
     if (fmt == PN_WF_F32_N16) {
       std::vector<float> pq(pn_packed_floats_n16(K, ncols));
       pn_pack_weights_n16(H.w, K, ncols, pq.data());
@@ -101,6 +101,17 @@ void weights_release(pn_ctx *c) {
 }
 
 // ---- the per-frame launch sequence -----------------------------------------------------------------------
+// the launchers of a kernel kind (pn_network.h: pn_kKernelRule names the same forms)
+static constexpr struct { PnLayerLauncher *dense, *gru; } kLaunchers[] = {
+    {pn_launch_dense_strict, pn_launch_gru_strict}, {pn_launch_dense, pn_launch_gru}, {pn_launch_dense, NULL}, {pn_launch_dense_small, pn_launch_gru_small},
+    {pn_launch_dense_n16, NULL}, {pn_launch_dense_n48, NULL}, {pn_launch_dense_x3, pn_launch_gru_x3}, {NULL, pn_launch_gru_d}};
+constexpr bool launchers_match_rules() {
+  for (int k = 0; k < PN_K_COUNT; k++)
+    if ((kLaunchers[k].dense != nullptr) != (pn_kKernelRule[k].dense != nullptr) || (kLaunchers[k].gru != nullptr) != (pn_kKernelRule[k].gru != nullptr)) return false;
+  return true;
+}
+static_assert(sizeof(kLaunchers) / sizeof(kLaunchers[0]) == PN_K_COUNT && launchers_match_rules(), "one launcher per form of every kernel kind (pn_kKernelRule)");
+
 int reshadow(pn_ctx *c, hipStream_t st, int e, const float *p, const int *d_ids, const int *d_status, int n) {
   void *S = shadow_at(c, e, p); const int w = pn_kState[e].cols, np = pn_weight_planes(c->nn_mode);
   if (!S) return 0;
@@ -114,17 +125,17 @@ int reshadow(pn_ctx *c, hipStream_t st, int e, const float *p, const int *d_ids,
 // is the same launch with every base pointer moved down by r0 rows.  Wiring, kernel and shadows of each layer are pn_network.h's,
 // under c->plan.  The shadow-operand and STRICT modes always run the whole batch.
 static int launch_rnn_rows(pn_ctx *c, size_t r0, size_t nrows, hipStream_t st) {
-  const int strict = c->nn_mode == PN_NN_STRICT, B = (int)nrows, rg = c->plan.rg, np = pn_weight_planes(c->nn_mode);
-  const float *tab = c->tansig;
+  const bool strict = c->nn_mode == PN_NN_STRICT;
   int rc = 0;
   for (int li = 0; li < PN_NLAYERS; li++) {
     const PnNetLayer &R = pn_kNet[li]; const DevLayer &W = c->L[li];
-    const int k = pn_layer_kernel(c->plan, c->nn_mode, li), N = pn_kGeom[li].nn, act = c->geom[li].act; const bool gru = R.state >= 0;
+    const int k = pn_layer_kernel(c->plan, c->nn_mode, li), fmt = pn_kernel_weight_format(k); const bool gru = R.state >= 0;
     if (rc && R.fam == KF_GRU512) continue;   // gru1 -> gru2 -> gru3 -> gru_gb, each fed the UPDATED state of its predecessor: the sequence stops at a refusal
     // every chain's launches are bracketed on the stream they go to (pn_ctx_kernel_times averages over all launches of a family;
     // with N chains the launches of one family overlap in time: bench.py prices the CONCURRENT launches together)
     Scope sc(c, R.fam, st);
-    PnSegs A = {}, S = {}; A.n = S.n = R.n_in;         // the input panels, and their operand shadows for the kernels that read those
+    PnLayerLaunch L = {};
+    PnSegs &A = L.A, &S = L.S; A.n = S.n = R.n_in;     // the input panels, and their operand shadows for the kernels that read those
     for (int j = 0; j < R.n_in; j++) {
       const int e = R.in[j].entry;
       A.p[j] = state_at(c, e, R.in[j].j, r0); A.ld[j] = S.ld[j] = pn_kState[e].row_words; A.width[j] = S.width[j] = pn_kState[e].cols;
@@ -132,24 +143,19 @@ static int launch_rnn_rows(pn_ctx *c, size_t r0, size_t nrows, hipStream_t st) {
     }
     if (li == PN_L_FC && strict) A.width[0] = pn_kGeom[li].nin;               // (the MFMA kernels sweep the zero-padded panel: cols 70..127 are zero)
     if (li == PN_L_FC && c->inject_bad_launch && !strict) A.width[0] = 96;     // test hook: three K-tiles, which every MFMA dense launcher refuses
-    float *out = state_at(c, R.out.entry, R.out.j, r0) + R.out_col; const int ldo = pn_kState[R.out.entry].row_words;
-    void *outS = pn_kernel_writes_shadow(k) ? shadow_at(c, R.out.entry, out) : NULL;     // (fc_gb's output keeps none)
-    const int nts = outS ? pn_kState[R.out.entry].cols / 32 : 0;                         // column tiles of the output's shadow
-    const float *ho = gru ? state_at(c, R.state, 0, r0) : NULL;                          // GRU pairs: live half read, the other written
-    switch (k) {
-      case PN_K_X3:
-        rc |= gru ? pn_launch_gru_x3(st, S, ho, shadow_at(c, R.state, ho), W.wp, W.rwp, W.bias, N, act, tab, out, outS, B, rg, np)
-                  : pn_launch_dense_x3(st, S, W.wp, W.bias, N, act, tab, out, ldo, outS, nts, B, rg, np);
-        break;
-      case PN_K_DIRECT: rc |= pn_launch_gru_d(st, S, ho, shadow_at(c, R.state, ho), W.wp, W.rwp, W.bias, N, act, tab, out, outS, B, rg); break;
-      case PN_K_N16: case PN_K_N48: rc |= (k == PN_K_N16 ? pn_launch_dense_n16 : pn_launch_dense_n48)(st, A, W.wq, W.bias, N, act, tab, out, ldo, B); break;
-      default:       // strict, batch (conv2 under the direct family: + the shadow the GRUs read), small
-        rc |= gru ? pn_launch_gru(st, strict, A, ho, W.w, W.rw, W.wp, W.rwp, W.bias, N, act, tab, out, B, k == PN_K_SMALL)
-                  : pn_launch_dense(st, strict, A, W.w, W.wp, W.bias, N, act, tab, out, ldo, B, k == PN_K_SMALL, outS, nts);
-    }
+    L.bias = W.bias;
+    L.w = fmt == PN_WF_RAW ? W.w : (fmt == PN_WF_F32_N16 ? W.wq : W.wp); L.rw = fmt == PN_WF_RAW ? W.rw : W.rwp;
+    L.N = pn_kGeom[li].nn; L.act = c->geom[li].act; L.tansig = c->tansig;
+    L.out = state_at(c, R.out.entry, R.out.j, r0) + R.out_col; L.ldo = pn_kState[R.out.entry].row_words;
+    L.outS = pn_kernel_writes_shadow(k) ? shadow_at(c, R.out.entry, L.out) : NULL;       // (fc_gb's output keeps none)
+    L.nts_out = L.outS ? pn_kState[R.out.entry].cols / 32 : 0;                           // column tiles of the output's shadow
+    if (gru) { L.h_old = state_at(c, R.state, 0, r0); L.h_oldS = shadow_at(c, R.state, L.h_old); }   // GRU pairs: live half read, the other written
+    L.n_rows = (int)nrows; L.rg = c->plan.rg; L.np = pn_weight_planes(c->nn_mode);
+    PnLayerLauncher *launch = gru ? kLaunchers[k].gru : kLaunchers[k].dense;
+    rc |= launch ? launch(st, L) : pn_kernel_geometry_ok(k, gru, A.n, A.width, L.N);   // (no such form: the rule's refusal says so)
     // an output whose entry keeps a shadow that the kernel does not write: fc in the shadow-operand modes runs in fp32 (70 inputs),
     // its output enters the shadow-operand layers
-    if (!pn_kernel_writes_shadow(k)) rc |= reshadow(c, st, R.out.entry, out);
+    if (!pn_kernel_writes_shadow(k)) rc |= reshadow(c, st, R.out.entry, L.out);
   }
   return rc ? -1 : 0;
 }

@@ -1,10 +1,13 @@
 // The ten layers of the gain network, described once — HIP-free (builds with -DPN_NO_HIP), checked on the CPU by
 // tests/c/host_sanitize.cpp.  What each layer reads and writes (pn_kNet, in terms of pn_state_layout.h's entries), which kernel
-// runs it under a plan (pn_layer_kernel), which packed weights that kernel reads (pn_layer_weight_format) and which operand
-// shadows it goes through: the launch loop and the weight upload (pn_network.cpp), the shadow allocation (pn_context.cpp) and
-// pn_plan_describe all ask here.  A new kernel variant is one new kind and one arm of pn_layer_kernel.
+// runs it under a plan (pn_layer_kernel), which packed weights that kernel reads (pn_layer_weight_format), which operand
+// shadows it goes through, and what a kernel kind needs in order to be launched (pn_kKernelRule: the launcher of its dense and
+// of its GRU form, the geometry that launcher refuses, the column-tile rounding of its packed weights): the launch loop and the
+// weight upload (pn_network.cpp), the launchers (pn_nn*.hip), the shadow allocation (pn_context.cpp), pn_debug_check_launch and
+// pn_plan_describe all ask here.  A new kernel variant is one new kind, one arm of pn_layer_kernel, one rule row and one launcher.
 #pragma once
 #include "pn_dsp_layout.h"    // the profiling families, and through it pn_plan.h and pn_state_layout.h
+#include "pn_launch_check.h"  // the geometry predicates the rules are made of
 
 // The A operand of a layer = the concatenation along K of n <= 5 row-major panels: base, row stride (floats) and valid columns of
 // each; the MFMA path requires every panel to be readable (and zero) up to the next multiple of 32 and all panels to be equally wide
@@ -59,7 +62,7 @@ static_assert(pn_net_ok(), "layer wiring (pn_kNet), topology (pn_kGeom) and stat
 // fragment-order shadow of its output (pn_dense_mfma_ps_kernel); small: small-batch family (pn_nn_small.hip); n16 / n48: 16x16x4
 // tiles for the 34-wide layers, one wave per tile (pn_nn_small.hip) / batch form (pn_nn_n48.hip); x3: fp16 matrix cores from operand
 // shadows, split precision or fp16 operands (pn_nn_x3.hip); direct: fp32 GRU step from fragment-order fp32 shadows (pn_nn_d.hip)
-enum { PN_K_STRICT, PN_K_BATCH, PN_K_BATCH_SH, PN_K_SMALL, PN_K_N16, PN_K_N48, PN_K_X3, PN_K_DIRECT };
+enum { PN_K_STRICT, PN_K_BATCH, PN_K_BATCH_SH, PN_K_SMALL, PN_K_N16, PN_K_N48, PN_K_X3, PN_K_DIRECT, PN_K_COUNT };
 constexpr bool pn_mode_x3(int nn_mode) { return nn_mode == PN_NN_MFMA_X3 || nn_mode == PN_NN_MFMA_F16; }   // shadow-operand modes
 constexpr bool pn_layer_narrow(int li) { return pn_kGeom[li].kind == PN_KIND_DENSE && pn_kGeom[li].nn <= 48; }   // fc_gb, fc_rb
 // The only place that spells the precedence.  The exceptions: in the shadow-operand modes fc (70 inputs) and fc_rb (K = 128) stay
@@ -93,6 +96,42 @@ constexpr int pn_weight_planes(int nn_mode) { return nn_mode == PN_NN_MFMA_X3 ? 
 // layer's kernel reads under that narrow setting.  No other plan field may change it (host_sanitize.cpp checks every plan).
 constexpr int pn_layer_weight_format(int nn_mode, int narrow, int li) {
   return pn_kernel_weight_format(pn_layer_kernel(PnPlan{0, 0, 0, narrow, 0, 0, 1}, nn_mode, li));
+}
+
+// ---- what a kind needs to be launched -------------------------------------------------------------------------------------------
+// The launcher of a kind's dense / conv form and of its GRU form, by the name its refusals carry; NULL: the kind has no such form.
+// pn_network.cpp's table of the launchers themselves is static_asserted against this one.
+struct PnKernelRule { const char *dense, *gru; };
+static constexpr PnKernelRule pn_kKernelRule[PN_K_COUNT] = {
+    {"pn_launch_dense_strict", "pn_launch_gru_strict"},   // strict
+    {"pn_launch_dense", "pn_launch_gru"},                 // batch
+    {"pn_launch_dense", NULL},                            // batch_sh: the batch launcher, handed the shadow of its output
+    {"pn_launch_dense_small", "pn_launch_gru_small"},     // small
+    {"pn_launch_dense_n16", NULL},                        // n16
+    {"pn_launch_dense_n48", NULL},                        // n48
+    {"pn_launch_dense_x3", "pn_launch_gru_x3"},           // x3
+    {NULL, "pn_launch_gru_d"},                            // direct
+};
+constexpr const char *pn_kernel_launcher(int k, bool gru) { return gru ? pn_kKernelRule[k].gru : pn_kKernelRule[k].dense; }
+// Column-tile rounding of the kind's packed input weights (pn_pack_weights / pn_pack_weights_x3: column tiles per block of the
+// kernel that reads them): what the upload packs with and the launcher sizes its grid by.  A GRU's gates are whole tiles.
+constexpr int pn_kernel_ct_round(int k, bool gru, int N) { return gru ? 1 : ((k == PN_K_X3 ? N >= 128 : N % 128 == 0) ? 4 : 2); }
+constexpr int pn_layer_ct_round(int nn_mode, int narrow, int li) {      // ... of layer li in the shared copy of (nn_mode, narrow)
+  return pn_kernel_ct_round(pn_layer_kernel(PnPlan{0, 0, 0, narrow, 0, 0, 1}, nn_mode, li), pn_kGeom[li].kind == PN_KIND_GRU, pn_kGeom[li].nn);
+}
+// 0, or -1 (pn_set_error names the launcher) where the launcher of (k, gru) refuses n_panels input panels of width[] columns
+// and N neurons.  Every launcher begins with this call; pn_debug_check_launch and the harness make the same one.
+static inline int pn_kernel_geometry_ok(int k, bool gru, int n_panels, const int *width, int N) {
+  const char *who = k >= 0 && k < PN_K_COUNT ? pn_kernel_launcher(k, gru) : NULL;
+  if (!who) { pn_set_error("kernel kind %d has no %s launcher", k, gru ? "GRU" : "dense"); return -1; }
+  if (k == PN_K_STRICT || (gru && k == PN_K_BATCH)) return 0;       // strict: one lane per output, any geometry; the fp32 batch GRU launcher checks nothing
+  if (k == PN_K_N16) return pn_check_n16_geometry(who, n_panels, width, N16_DEPTH);
+  if (gru) return k == PN_K_SMALL ? pn_check_gru_small_geometry(who, n_panels, width, N) : pn_check_gru_geometry(who, n_panels, width, N);   // : x3, direct
+  const bool fp32 = k == PN_K_BATCH || k == PN_K_BATCH_SH || k == PN_K_SMALL;      // zero-fill a ragged last tile; n48 and x3 read whole tiles
+  if (pn_check_dense_geometry(who, n_panels, width, !fp32)) return -1;
+  if (k == PN_K_BATCH_SH && pn_kernel_ct_round(k, gru, N) != 4) { pn_set_error("%s: a shadow output needs whole 128-column blocks", who); return -1; }
+  if (k == PN_K_N48 && (N < 1 || N > PN_N48_COLS)) { pn_set_error("%s: %d output columns (1..%d)", who, N, PN_N48_COLS); return -1; }
+  return 0;
 }
 
 // ---- describe -------------------------------------------------------------------------------------------------------------------

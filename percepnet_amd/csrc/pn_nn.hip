@@ -579,61 +579,47 @@ __global__ __launch_bounds__(NN_THREADS, 2) void pn_dense_mfma_ps_kernel(
 }
 
 // ---- launchers -----------------------------------------------------------------------------------
-// small: the small-batch kernel family (pn_nn_small.hip: one 32x32 tile and one accumulator chain per wave, 3-4x more
-// blocks), else the batch-GEMM kernels above.  Same numerics either way; which one a context runs is pn_plan.h's choice.
-int pn_launch_dense_small(hipStream_t st, const PnSegs &A, const float *Wp, const float *bias, int N, int act,
-                          const float *tansig, float *out, int ldo, int n_rows, int ct_padded);
-int pn_launch_gru_small(hipStream_t st, const PnSegs &X, const float *h_old, const float *Wp, const float *Up,
-                        const float *b, int N, int act, const float *tansig, float *h_new, int n_rows);
-int pn_launch_dense(hipStream_t st, int strict, const PnSegs &A, const float *W, const float *Wp, const float *bias,
-                     int N, int act, const float *tansig, float *out, int ldo, int n_rows, int small, void *outS, int nts_out) {
-  // outS: fragment-order fp32 shadow of `out` (a buffer nts_out column tiles wide) for the direct-operand GRU kernels — batch kernels only
-  if (outS && (strict || small)) { pn_set_error("pn_launch_dense: a shadow output needs the batch-GEMM kernels"); return -1; }
-  if (strict) {
-    const int nbx = (N + 63) / 64;
-    hipLaunchKernelGGL(pn_dense_strict_kernel, dim3((unsigned)nbx * (unsigned)n_rows), dim3(64), 0, st, A, W, bias, N, act, tansig, out, ldo, nbx);
-    return 0;
-  }
-  if (small) {
-    return pn_launch_dense_small(st, A, Wp, bias, N, act, tansig, out, ldo, n_rows, pn_ct_padded(N, pn_dense_nt(N)));
-  }
-  const int tps = (A.width[0] + 31) / 32, KT = tps * A.n;   // equal-width panels
-  const int NT = pn_dense_nt(N);
-  // the half-tile pipeline consumes K-tiles in pairs: every layer of the PercepNet topology (the only geometry a
-  // context accepts, pn_model.cpp:check_geometry) has an even number of them (4, 20, 48, 80, 4)
-  if (pn_check_dense_geometry("pn_launch_dense", A.n, A.width, 0)) return -1;
-  const int n_cblocks = pn_ct_padded(N, NT) / NT;
-  const int n_mtiles = (n_rows + BM - 1) / BM;
-  const int grid = 8 * ((n_mtiles + 7) / 8) * n_cblocks;
-  if (outS) {
-    if (NT != 4) { pn_set_error("pn_launch_dense: a shadow output needs whole 128-column blocks"); return -1; }
-    hipLaunchKernelGGL(pn_dense_mfma_ps_kernel<4>, dim3(grid), dim3(NN_THREADS), 0, st, A, Wp, bias, N, KT, tps, act,
-                       tansig, out, ldo, n_rows, n_mtiles, n_cblocks, (uint4 *)outS, nts_out);
-  } else if (NT == 4)
-    hipLaunchKernelGGL(pn_dense_mfma_p_kernel<4>, dim3(grid), dim3(NN_THREADS), 0, st, A, Wp, bias, N, KT, tps, act,
-                       tansig, out, ldo, n_rows, n_mtiles, n_cblocks);
-  else
-    hipLaunchKernelGGL(pn_dense_mfma_p_kernel<2>, dim3(grid), dim3(NN_THREADS), 0, st, A, Wp, bias, N, KT, tps, act,
-                       tansig, out, ldo, n_rows, n_mtiles, n_cblocks);
+// strict: one lane per output.  batch: the batch-GEMM kernels above; the small-batch family (pn_nn_small.hip: one 32x32 tile and
+// one accumulator chain per wave, 3-4x more blocks) has the same numerics; which one a context runs is pn_plan.h's choice.
+int pn_launch_dense_strict(hipStream_t st, const PnLayerLaunch &L) {
+  const int nbx = (L.N + 63) / 64;
+  hipLaunchKernelGGL(pn_dense_strict_kernel, dim3((unsigned)nbx * (unsigned)L.n_rows), dim3(64), 0, st, L.A, (const float *)L.w, L.bias, L.N,
+                     L.act, L.tansig, L.out, L.ldo, nbx);
   return 0;
 }
-
-int pn_launch_gru(hipStream_t st, int strict, const PnSegs &X, const float *h_old, const float *W, const float *U,
-                   const float *Wp, const float *Up, const float *b, int N, int act, const float *tansig,
-                   float *h_new, int n_rows, int small) {
-  if (strict) {
-    const int nbx = (N + 63) / 64;
-    hipLaunchKernelGGL(pn_gru_strict_kernel, dim3((unsigned)nbx * (unsigned)n_rows), dim3(64), 0, st, X, h_old, W, U, b, N, act, tansig, h_new, nbx);
-    return 0;
-  }
-  if (small) {
-    return pn_launch_gru_small(st, X, h_old, Wp, Up, b, N, act, tansig, h_new, n_rows);
-  }
-  const int tps = (X.width[0] + 31) / 32, KTx = tps * X.n;   // equal-width panels
-  const int NTn = N / 32;
-  const int n_mtiles = (n_rows + BM - 1) / BM;
-  const int grid = 8 * ((n_mtiles + 7) / 8) * NTn;
-  hipLaunchKernelGGL(pn_gru_mfma_p_kernel, dim3(grid), dim3(NN_THREADS), 0, st, X, h_old, Wp, Up, b, N, KTx, tps, act,
-                       tansig, h_new, n_rows, n_mtiles);
+int pn_launch_gru_strict(hipStream_t st, const PnLayerLaunch &L) {
+  const int nbx = (L.N + 63) / 64;
+  hipLaunchKernelGGL(pn_gru_strict_kernel, dim3((unsigned)nbx * (unsigned)L.n_rows), dim3(64), 0, st, L.A, L.h_old, (const float *)L.w,
+                     (const float *)L.rw, L.bias, L.N, L.act, L.tansig, L.out, nbx);
+  return 0;
+}
+// outS: fragment-order fp32 shadow of `out` for the direct-operand GRU kernels (batch_sh)
+int pn_launch_dense(hipStream_t st, const PnLayerLaunch &L) {
+  // the half-tile pipeline consumes K-tiles in pairs: every layer of the PercepNet topology (the only geometry a
+  // context accepts, pn_model.cpp:check_geometry) has an even number of them (4, 20, 48, 80, 4)
+  if (pn_kernel_geometry_ok(L.outS ? PN_K_BATCH_SH : PN_K_BATCH, false, L.A.n, L.A.width, L.N)) return -1;
+  const int tps = (L.A.width[0] + 31) / 32, KT = tps * L.A.n;   // equal-width panels
+  const int NT = pn_kernel_ct_round(PN_K_BATCH, false, L.N), n_cblocks = pn_ct_padded(L.N, NT) / NT;
+  const int n_mtiles = (L.n_rows + BM - 1) / BM;
+  const int grid = 8 * ((n_mtiles + 7) / 8) * n_cblocks;
+  const float *Wp = (const float *)L.w;
+  if (L.outS)
+    hipLaunchKernelGGL(pn_dense_mfma_ps_kernel<4>, dim3(grid), dim3(NN_THREADS), 0, st, L.A, Wp, L.bias, L.N, KT, tps, L.act,
+                       L.tansig, L.out, L.ldo, L.n_rows, n_mtiles, n_cblocks, (uint4 *)L.outS, L.nts_out);
+  else if (NT == 4)
+    hipLaunchKernelGGL(pn_dense_mfma_p_kernel<4>, dim3(grid), dim3(NN_THREADS), 0, st, L.A, Wp, L.bias, L.N, KT, tps, L.act,
+                       L.tansig, L.out, L.ldo, L.n_rows, n_mtiles, n_cblocks);
+  else
+    hipLaunchKernelGGL(pn_dense_mfma_p_kernel<2>, dim3(grid), dim3(NN_THREADS), 0, st, L.A, Wp, L.bias, L.N, KT, tps, L.act,
+                       L.tansig, L.out, L.ldo, L.n_rows, n_mtiles, n_cblocks);
+  return 0;
+}
+int pn_launch_gru(hipStream_t st, const PnLayerLaunch &L) {
+  if (pn_kernel_geometry_ok(PN_K_BATCH, true, L.A.n, L.A.width, L.N)) return -1;
+  const int tps = (L.A.width[0] + 31) / 32, KTx = tps * L.A.n;   // equal-width panels
+  const int n_mtiles = (L.n_rows + BM - 1) / BM;
+  const int grid = 8 * ((n_mtiles + 7) / 8) * (L.N / 32);
+  hipLaunchKernelGGL(pn_gru_mfma_p_kernel, dim3(grid), dim3(NN_THREADS), 0, st, L.A, L.h_old, (const float *)L.w, (const float *)L.rw,
+                     L.bias, L.N, KTx, tps, L.act, L.tansig, L.out, L.n_rows, n_mtiles);
   return 0;
 }

@@ -241,20 +241,17 @@ __global__ __launch_bounds__(256) void pn_split_d_rows_kernel(const float *__res
 
 // ---- launchers -----------------------------------------------------------------------------------------------------
 // (which PN_NN_MFMA contexts run their GRU steps here, and at how many rows per wave: pn_plan.h)
-// X panels / h_oldS / h_newS: the uint4* fragment-order fp32 shadows; Wp / Up: the fp32 packed tiles of pn_pack_weights.
+// L.S / h_oldS / outS: the uint4* fragment-order fp32 shadows; w / rw: the fp32 packed tiles of pn_pack_weights.
 // rg: row groups of 32 per wave (2: 256-row blocks, two per CU; 1: 128-row blocks, three)
-int pn_launch_gru_d(hipStream_t st, const PnSegs &X, const float *h_old, const void *h_oldS, const float *Wp,
-                    const float *Up, const float *b, int N, int act, const float *tansig, float *h_new, void *h_newS,
-                    int n_rows, int rg) {
-  const int tps = X.width[0] / 32, KTx = tps * X.n;
-  const int NTn = N / 32;
-  if (pn_check_gru_geometry("pn_launch_gru_d", X.n, X.width, N)) return -1;   // k-tiles are consumed in pairs (x: 16 / 32, h: 16 / 4)
-  const int n_mtiles = (n_rows + 128 * rg - 1) / (128 * rg);
-  const int grid = 8 * ((n_mtiles + 7) / 8) * NTn;
-#define DG_LAUNCH(RG_)                                                                                             \
-  hipLaunchKernelGGL((pn_gru_d_kernel<RG_>), dim3(grid), dim3(NN_THREADS), 0, st, X, h_old, (const uint4 *)h_oldS, Wp, Up, \
-                     b, N, KTx, tps, act, tansig, h_new, (uint4 *)h_newS, n_rows, n_mtiles)
-  if (rg == 2) DG_LAUNCH(2); else DG_LAUNCH(1);
+int pn_launch_gru_d(hipStream_t st, const PnLayerLaunch &L) {
+  if (pn_kernel_geometry_ok(PN_K_DIRECT, true, L.S.n, L.S.width, L.N)) return -1;   // k-tiles are consumed in pairs (x: 16 / 32, h: 16 / 4)
+  const int tps = L.S.width[0] / 32, KTx = tps * L.S.n;
+  const int n_mtiles = (L.n_rows + 128 * L.rg - 1) / (128 * L.rg);
+  const int grid = 8 * ((n_mtiles + 7) / 8) * (L.N / 32);
+#define DG_LAUNCH(RG_)                                                                                                       \
+  hipLaunchKernelGGL((pn_gru_d_kernel<RG_>), dim3(grid), dim3(NN_THREADS), 0, st, L.S, L.h_old, (const uint4 *)L.h_oldS, (const float *)L.w, \
+                     (const float *)L.rw, L.bias, L.N, KTx, tps, L.act, L.tansig, L.out, (uint4 *)L.outS, L.n_rows, n_mtiles)
+  if (L.rg == 2) DG_LAUNCH(2); else DG_LAUNCH(1);
 #undef DG_LAUNCH
   return 0;
 }

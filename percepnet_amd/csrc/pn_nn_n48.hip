@@ -136,13 +136,13 @@ __global__ __launch_bounds__(NN_THREADS) void pn_dense_n48_kernel(
 
 // Wq: pn_pack_weights_n16 (16-column tiles x 16-k groups x 64 lanes x 4).  N <= 48; panels of equal width, whole 32-column
 // tiles, an even number of them in total (the K loop consumes tiles in pairs and clamps its prefetch to the last one)
-int pn_launch_dense_n48(hipStream_t st, const PnSegs &A, const float *Wq, const float *bias, int N, int act,
-                        const float *tansig, float *out, int ldo, int n_rows) {
-  if (pn_check_dense_geometry("pn_launch_dense_n48", A.n, A.width, 1)) return -1;
-  if (N < 1 || N > 16 * Q_CT) { pn_set_error("pn_launch_dense_n48: %d output columns (1..%d)", N, 16 * Q_CT); return -1; }
-  const int tps = A.width[0] / 32, KT = tps * A.n;
+static_assert(16 * Q_CT == PN_N48_COLS, "the rule of the n48 kind (pn_network.h) and the kernel's block agree");
+int pn_launch_dense_n48(hipStream_t st, const PnLayerLaunch &L) {
+  if (pn_kernel_geometry_ok(PN_K_N48, false, L.A.n, L.A.width, L.N)) return -1;
+  const int tps = L.A.width[0] / 32, KT = tps * L.A.n;
   constexpr int Q_BM = 64 * PN_N48_RGW;
-  const int n_mt = (n_rows + Q_BM - 1) / Q_BM;
-  hipLaunchKernelGGL(pn_dense_n48_kernel<PN_N48_RGW>, dim3(n_mt), dim3(NN_THREADS), 0, st, A, Wq, bias, N, KT, tps, act, tansig, out, ldo, n_rows);
+  const int n_mt = (L.n_rows + Q_BM - 1) / Q_BM;
+  hipLaunchKernelGGL(pn_dense_n48_kernel<PN_N48_RGW>, dim3(n_mt), dim3(NN_THREADS), 0, st, L.A, (const float *)L.w, L.bias, L.N, KT, tps, L.act,
+                     L.tansig, L.out, L.ldo, L.n_rows);
   return 0;
 }

@@ -219,7 +219,6 @@ __global__ __launch_bounds__(192) void pn_gru_small_kernel(
 //     ds_read_b32 per four MFMAs);
 //   * eight 16-k groups of both operands in flight (the chain is paced by L2 latency, not bandwidth).
 // Chain order = bias, then k ascending: identical to the other kernel families and to sgemv_accum (nnet.cpp:59-72).
-#define N16_DEPTH 8
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(64, 1) void pn_dense_n16_kernel(        // (64, 1): one wave per block, up to 512 registers — no spills
     PnSegs A, const float *__restrict__ Wq, const float *__restrict__ bias, int N, int KG, int lg_gps, int act,
@@ -290,36 +289,31 @@ __global__ __launch_bounds__(64, 1) void pn_dense_n16_kernel(        // (64, 1):
   }
 }
 
-int pn_launch_dense_n16(hipStream_t st, const PnSegs &A, const float *Wq, const float *bias, int N, int act,
-                        const float *tansig, float *out, int ldo, int n_rows) {
-  if (pn_check_n16_geometry("pn_launch_dense_n16", A.n, A.width, N16_DEPTH)) return -1;
-  const int gps = A.width[0] / 16, KG = gps * A.n;      // equal-width panels, widths multiples of 16 (128, 512)
-  const int n_mt = (n_rows + 15) / 16, n_ct = (N + 15) / 16;
+int pn_launch_dense_n16(hipStream_t st, const PnLayerLaunch &L) {
+  if (pn_kernel_geometry_ok(PN_K_N16, false, L.A.n, L.A.width, L.N)) return -1;
+  const int gps = L.A.width[0] / 16, KG = gps * L.A.n;      // equal-width panels, widths multiples of 16 (128, 512)
+  const int n_mt = (L.n_rows + 15) / 16, n_ct = (L.N + 15) / 16;
   int lg = 0;
   while ((1 << lg) < gps) lg++;
-  hipLaunchKernelGGL(pn_dense_n16_kernel, dim3(n_mt * n_ct), dim3(64), 0, st, A, Wq, bias, N, KG, lg, act, tansig, out, ldo,
-                     n_rows, n_ct);
+  hipLaunchKernelGGL(pn_dense_n16_kernel, dim3(n_mt * n_ct), dim3(64), 0, st, L.A, (const float *)L.w, L.bias, L.N, KG, lg, L.act, L.tansig,
+                     L.out, L.ldo, L.n_rows, n_ct);
   return 0;
 }
 
-// ---- launchers (called from pn_launch_dense / pn_launch_gru when the batch is small) -------------------------------
-int pn_launch_dense_small(hipStream_t st, const PnSegs &A, const float *Wp, const float *bias, int N, int act,
-                          const float *tansig, float *out, int ldo, int n_rows, int ct_padded) {
-  if (pn_check_dense_geometry("pn_launch_dense_small", A.n, A.width, 0)) return -1;   // K-tiles alternate between two register sets
-  const int tps = (A.width[0] + 31) / 32, KT = tps * A.n;   // equal-width panels
-  const int n_mt = (n_rows + SBM - 1) / SBM, ct_total = (N + 31) / 32, n_cblocks = (ct_total + 3) / 4;
-  (void)ct_padded;
-  hipLaunchKernelGGL(pn_dense_small_kernel, dim3(n_mt * n_cblocks), dim3(256), 0, st, A, Wp, bias, N, KT, tps, act, tansig,
-                     out, ldo, n_rows, n_cblocks, ct_total);
+// ---- launchers of the small-batch family ---------------------------------------------------------------------------
+int pn_launch_dense_small(hipStream_t st, const PnLayerLaunch &L) {
+  if (pn_kernel_geometry_ok(PN_K_SMALL, false, L.A.n, L.A.width, L.N)) return -1;   // K-tiles alternate between two register sets
+  const int tps = (L.A.width[0] + 31) / 32, KT = tps * L.A.n;   // equal-width panels
+  const int n_mt = (L.n_rows + SBM - 1) / SBM, ct_total = (L.N + 31) / 32, n_cblocks = (ct_total + 3) / 4;
+  hipLaunchKernelGGL(pn_dense_small_kernel, dim3(n_mt * n_cblocks), dim3(256), 0, st, L.A, (const float *)L.w, L.bias, L.N, KT, tps, L.act,
+                     L.tansig, L.out, L.ldo, L.n_rows, n_cblocks, ct_total);
   return 0;
 }
-int pn_launch_gru_small(hipStream_t st, const PnSegs &X, const float *h_old, const float *Wp, const float *Up,
-                        const float *b, int N, int act, const float *tansig, float *h_new, int n_rows) {
-  const int tps = (X.width[0] + 31) / 32, KTx = tps * X.n;
-  for (int j = 1; j < X.n; j++) if (X.width[j] != X.width[0]) { pn_set_error("pn_launch_gru_small: unequal panel widths"); return -1; }
-  if ((N & 31) || ((KTx + N / 32) & 1)) { pn_set_error("pn_launch_gru_small: %d input + %d recurrent K-tiles (the sum must be even, N whole tiles)", KTx, N / 32); return -1; }
-  const int n_mt = (n_rows + SBM - 1) / SBM;
-  hipLaunchKernelGGL(pn_gru_small_kernel, dim3(n_mt * (N / 32)), dim3(192), 0, st, X, h_old, Wp, Up, b, N, KTx, tps, act,
-                     tansig, h_new, n_rows);
+int pn_launch_gru_small(hipStream_t st, const PnLayerLaunch &L) {
+  if (pn_kernel_geometry_ok(PN_K_SMALL, true, L.A.n, L.A.width, L.N)) return -1;
+  const int tps = (L.A.width[0] + 31) / 32, KTx = tps * L.A.n;
+  const int n_mt = (L.n_rows + SBM - 1) / SBM;
+  hipLaunchKernelGGL(pn_gru_small_kernel, dim3(n_mt * (L.N / 32)), dim3(192), 0, st, L.A, L.h_old, (const float *)L.w, (const float *)L.rw,
+                     L.bias, L.N, KTx, tps, L.act, L.tansig, L.out, L.n_rows);
   return 0;
 }

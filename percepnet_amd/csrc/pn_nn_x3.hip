@@ -842,17 +842,13 @@ __global__ __launch_bounds__(256) void pn_split_x3_rows_kernel(const float *__re
 #undef X3_SPLIT_ROW_KG
 
 // ---- host: weight packing W[K][ncols] -> [CT][ceil(K/32)][k-step 2][plane np][lane 64][8 halfs] ------------------
-static inline int x3_ct_padded(int ncols, int ct_round) {
-  const int CT = (ncols + 31) / 32;
-  return ((CT + ct_round - 1) / ct_round) * ct_round;
-}
 size_t pn_packed_halfs_x3(int k_alloc, int ncols, int ct_round, int np) {
-  return (size_t)x3_ct_padded(ncols, ct_round) * ((k_alloc + 31) / 32) * 1024 * np;
+  return (size_t)pn_ct_padded(ncols, ct_round) * ((k_alloc + 31) / 32) * 1024 * np;
 }
 // returns 0, or -1 if a weight is outside the fp16 range (the mode cannot represent it)
 int pn_pack_weights_x3(const float *W, int K, int k_alloc, int ncols, int ct_round, int np, void *out) {
   _Float16 *Wp = (_Float16 *)out;
-  const int CT = x3_ct_padded(ncols, ct_round), KT = (k_alloc + 31) / 32;
+  const int CT = pn_ct_padded(ncols, ct_round), KT = (k_alloc + 31) / 32;
   for (int ct = 0; ct < CT; ct++)
     for (int kt = 0; kt < KT; kt++) {
       _Float16 *tile = Wp + ((size_t)ct * KT + kt) * 1024 * np;
@@ -870,29 +866,26 @@ int pn_pack_weights_x3(const float *W, int K, int k_alloc, int ncols, int ct_rou
   return 0;
 }
 
-int pn_dense_x3_nt(int N) { return N >= 128 ? 4 : 2; }
-
 // rows per wave (rg): 2 row groups of 32 (256-row blocks, two per CU) or 1 (128-row blocks, three per CU); 3 = 64 rows with the
 // GRUs on the paired-phase kernel.  The context fixes the choice at creation (pn_plan.h) and its self-test runs the same instantiation.
 
-// A: panels carry the uint4* shadows of equally wide buffers (width = logical columns, a multiple of 32);
+// L.S: panels carry the uint4* shadows of equally wide buffers (width = logical columns, a multiple of 32);
 // out (fp32, optional) / outS (shadow of a buffer nts_out column tiles wide, optional)
-int pn_launch_dense_x3(hipStream_t st, const PnSegs &A, const void *Wp, const float *bias, int N, int act,
-                        const float *tansig, float *out, int ldo, void *outS, int nts_out, int n_rows, int rg, int np) {
-  if (rg == 3) rg = 2;                 // the paired-phase form exists for the GRUs only
-  const int tps = A.width[0] / 32, KT = tps * A.n;
+int pn_launch_dense_x3(hipStream_t st, const PnLayerLaunch &L) {
   // the K loop consumes k-tiles in pairs and clamps its prefetch to the last tile: an odd count would accumulate that
   // tile twice; panels must be whole 32-column tiles of equal width (every layer of the fixed topology is: 20 / 48 / 80)
-  if (pn_check_dense_geometry("pn_launch_dense_x3", A.n, A.width, 1)) return -1;
-  const int NT = pn_dense_x3_nt(N);
-  const int n_mtiles = (n_rows + 128 * rg - 1) / (128 * rg);
-  const int n_cblocks = x3_ct_padded(N, NT) / NT;
+  if (pn_kernel_geometry_ok(PN_K_X3, false, L.S.n, L.S.width, L.N)) return -1;
+  const int rg = L.rg == 3 ? 2 : L.rg;                 // the paired-phase form exists for the GRUs only
+  const int tps = L.S.width[0] / 32, KT = tps * L.S.n;
+  const int NT = pn_kernel_ct_round(PN_K_X3, false, L.N);
+  const int n_mtiles = (L.n_rows + 128 * rg - 1) / (128 * rg);
+  const int n_cblocks = pn_ct_padded(L.N, NT) / NT;
   const int grid = 8 * ((n_mtiles + 7) / 8) * n_cblocks;
-#define XD_LAUNCH(NT_) do { if (np == 2) { if (rg == 2) XD_LAUNCH2(2, 2, NT_); else XD_LAUNCH2(1, 2, NT_); } \
+#define XD_LAUNCH(NT_) do { if (L.np == 2) { if (rg == 2) XD_LAUNCH2(2, 2, NT_); else XD_LAUNCH2(1, 2, NT_); } \
                             else { if (rg == 2) XD_LAUNCH2(2, 1, NT_); else XD_LAUNCH2(1, 1, NT_); } } while (0)
 #define XD_LAUNCH2(RG_, NP_, NT_)                                                                                \
-  hipLaunchKernelGGL((pn_dense_x3_kernel<RG_, NP_, NT_>), dim3(grid), dim3(NN_THREADS), 0, st, A, (const uint4 *)Wp, bias, N, \
-                     KT, tps, act, tansig, out, ldo, (uint4 *)outS, nts_out, n_rows, n_mtiles, n_cblocks)
+  hipLaunchKernelGGL((pn_dense_x3_kernel<RG_, NP_, NT_>), dim3(grid), dim3(NN_THREADS), 0, st, L.S, (const uint4 *)L.w, L.bias, L.N, \
+                     KT, tps, L.act, L.tansig, L.out, L.ldo, (uint4 *)L.outS, L.nts_out, L.n_rows, n_mtiles, n_cblocks)
   if (NT == 4) XD_LAUNCH(4); else XD_LAUNCH(2);
 #undef XD_LAUNCH
 #undef XD_LAUNCH2
@@ -912,34 +905,32 @@ static int x3_cu_count() {
   return cus[dev];
 }
 
-int pn_launch_gru_x3(hipStream_t st, const PnSegs &X, const float *h_old, const void *h_oldS, const void *Wp,
-                      const void *Up, const float *b, int N, int act, const float *tansig, float *h_new, void *h_newS,
-                      int n_rows, int rg, int np) {
-  const int tps = X.width[0] / 32, KTx = tps * X.n;
-  const int NTn = N / 32;
-  if (pn_check_gru_geometry("pn_launch_gru_x3", X.n, X.width, N)) return -1;   // k-tiles are consumed in pairs (x: 16 / 32, h: 16 / 4)
+int pn_launch_gru_x3(hipStream_t st, const PnLayerLaunch &L) {
+  if (pn_kernel_geometry_ok(PN_K_X3, true, L.S.n, L.S.width, L.N)) return -1;   // k-tiles are consumed in pairs (x: 16 / 32, h: 16 / 4)
+  const int tps = L.S.width[0] / 32, KTx = tps * L.S.n;
+  const int NTn = L.N / 32;
   // rg 3: paired-phase kernel (one 8-wave block per CU, K loop of one wave group beside the epilogue of the other); it
   // is written for the tanh candidate and instantiated for the two GRU geometries of the network (512 -> 512 and
   // 1024 -> 128); anything else runs on the 64-rows-per-wave kernel
-  if (rg == 3 && act == ACT_TANH && ((KTx == 16 && NTn == 16) || (KTx == 32 && NTn == 4))) {
-    const int n_mtiles = (n_rows + 255) / 256;
+  if (L.rg == 3 && L.act == ACT_TANH && ((KTx == 16 && NTn == 16) || (KTx == 32 && NTn == 4))) {
+    const int n_mtiles = (L.n_rows + 255) / 256;
     const int grid = 8 * (x3_cu_count() / 8);
 #define XP_LAUNCH(NP_, KTX_, NTN_)                                                                                  \
-    hipLaunchKernelGGL((pn_gru_x3p_kernel<NP_, KTX_, NTN_>), dim3(grid), dim3(512), 0, st, X, h_old, (const uint4 *)h_oldS, \
-                       (const uint4 *)Wp, (const uint4 *)Up, b, tps, tansig, h_new, (uint4 *)h_newS, n_rows, n_mtiles)
-    if (NTn == 16) { if (np == 2) XP_LAUNCH(2, 16, 16); else XP_LAUNCH(1, 16, 16); }
-    else { if (np == 2) XP_LAUNCH(2, 32, 4); else XP_LAUNCH(1, 32, 4); }
+    hipLaunchKernelGGL((pn_gru_x3p_kernel<NP_, KTX_, NTN_>), dim3(grid), dim3(512), 0, st, L.S, L.h_old, (const uint4 *)L.h_oldS, \
+                       (const uint4 *)L.w, (const uint4 *)L.rw, L.bias, tps, L.tansig, L.out, (uint4 *)L.outS, L.n_rows, n_mtiles)
+    if (NTn == 16) { if (L.np == 2) XP_LAUNCH(2, 16, 16); else XP_LAUNCH(1, 16, 16); }
+    else { if (L.np == 2) XP_LAUNCH(2, 32, 4); else XP_LAUNCH(1, 32, 4); }
 #undef XP_LAUNCH
     return 0;
   }
-  if (rg == 3) rg = 2;
-  const int n_mtiles = (n_rows + 128 * rg - 1) / (128 * rg);
+  const int rg = L.rg == 3 ? 2 : L.rg;
+  const int n_mtiles = (L.n_rows + 128 * rg - 1) / (128 * rg);
   const int grid = 8 * ((n_mtiles + 7) / 8) * NTn;
 #define XG_LAUNCH(RG_, NP_)                                                                                           \
-  hipLaunchKernelGGL((pn_gru_x3_kernel<RG_, NP_>), dim3(grid), dim3(NN_THREADS), 0, st, X, h_old, (const uint4 *)h_oldS,  \
-                     (const uint4 *)Wp, (const uint4 *)Up, b, N, KTx, tps, act, tansig, h_new, (uint4 *)h_newS, n_rows,   \
+  hipLaunchKernelGGL((pn_gru_x3_kernel<RG_, NP_>), dim3(grid), dim3(NN_THREADS), 0, st, L.S, L.h_old, (const uint4 *)L.h_oldS,  \
+                     (const uint4 *)L.w, (const uint4 *)L.rw, L.bias, L.N, KTx, tps, L.act, L.tansig, L.out, (uint4 *)L.outS, L.n_rows,   \
                      n_mtiles)
-  if (np == 2) { if (rg == 2) XG_LAUNCH(2, 2); else XG_LAUNCH(1, 2); }
+  if (L.np == 2) { if (rg == 2) XG_LAUNCH(2, 2); else XG_LAUNCH(1, 2); }
   else { if (rg == 2) XG_LAUNCH(2, 1); else XG_LAUNCH(1, 1); }
 #undef XG_LAUNCH
   return 0;

@@ -32,8 +32,6 @@ void pn_pack_weights(const float *W, int K, int k_alloc, int ncols, int ct_round
         }
     }
 }
-int pn_dense_nt(int N) { return (N % 128 == 0) ? 4 : 2; }
-
 
 // weights of a narrow layer for pn_dense_n16_kernel: Wq[ct][t][lane][e] = W[k = 16t + 4e + (lane >> 4)][col = 16 ct + (lane & 15)]
 size_t pn_packed_floats_n16(int K, int ncols) { return (size_t)((ncols + 15) / 16) * ((K + 15) / 16) * 256; }
@@ -49,22 +47,18 @@ void pn_pack_weights_n16(const float *W, int K, int ncols, float *Wq) {
 }
 
 // ---- launch-geometry predicates without a GPU (include/percepnet_hip.h: pn_debug_check_launch) ----------------------------
-#include "pn_launch_check.h"
-// kind: 0 dense on the fp32 MFMA kernels (batch and small-batch), 1 dense on the shadow-operand kernels, 2 GRU on the
-// shadow-operand kernels (n_out neurons), 3 narrow dense on 16x16x4 tiles.  n_panels panels of `width` columns each.
+#include "pn_network.h"
+// The launcher's own rule (pn_kernel_geometry_ok) behind each public number.  kind: 0 dense on the fp32 MFMA kernels (batch and
+// small-batch), 1 dense on the shadow-operand kernels, 2 GRU on the shadow-operand kernels (n_out neurons), 3 narrow dense on
+// 16x16x4 tiles.  n_panels panels of `width` columns each.
 extern "C" PN_EXPORT int pn_debug_check_launch(int kind, int n_panels, int width, int n_out) {
   int w[5] = {width, width, width, width, width};
-  switch (kind) {
-    case 0: return pn_check_dense_geometry("pn_launch_dense", n_panels, w, 0);
-    case 1: return pn_check_dense_geometry("pn_launch_dense_x3", n_panels, w, 1);
-    case 2: return pn_check_gru_geometry("pn_launch_gru_x3", n_panels, w, n_out);
-    case 3: return pn_check_n16_geometry("pn_launch_dense_n16", n_panels, w, 8);
-    default: pn_set_error("pn_debug_check_launch: unknown kind %d", kind); return -1;
-  }
+  static const struct { int k; bool gru; } rule[4] = {{PN_K_BATCH, false}, {PN_K_X3, false}, {PN_K_X3, true}, {PN_K_N16, false}};
+  if (kind < 0 || kind > 3) { pn_set_error("pn_debug_check_launch: unknown kind %d", kind); return -1; }
+  return pn_kernel_geometry_ok(rule[kind].k, rule[kind].gru, n_panels, w, n_out);
 }
 
 // ---- the kernel families of a context without a GPU (include/percepnet_hip.h: pn_debug_plan) -------------------------------
-#include "pn_network.h"
 extern "C" PN_EXPORT int pn_debug_plan(int n_streams, int nn_mode, char *buf, size_t n) {
   if (!buf || !n || n_streams < 1) { pn_set_error("pn_debug_plan: bad argument"); return -1; }
   if (nn_mode != PN_NN_MFMA && nn_mode != PN_NN_STRICT && nn_mode != PN_NN_MFMA_F16 && nn_mode != PN_NN_MFMA_X3) { pn_set_error("bad nn_mode %d", nn_mode); return -1; }

@@ -112,7 +112,8 @@ int main(int argc, char **argv) {
   // the network table.  Every plan pn_plan_for can return — small and small_gru freely; narrow 1 outside STRICT, 2 in fp32 MFMA off
   // the small dense family; direct in fp32 MFMA off both small families; rg 1|2 with direct, 1|2|3 in the shadow-operand modes,
   // else 0 — in every mode: each layer's kernel is legal for the layer, reads the weight format the shared copy of (mode, narrow)
-  // holds, finds every shadow it reads or writes allocated, and is handed panels its launcher accepts
+  // holds, packed with the column-tile rounding its launcher sizes its grid by, finds every shadow it reads or writes allocated, has a
+// launcher for the layer's type, and is handed panels that launcher's rule (pn_kernel_geometry_ok, the launchers' own first call) accepts
   { int n_plans = 0;
     for (int mode : {PN_NN_MFMA, PN_NN_STRICT, PN_NN_MFMA_F16, PN_NN_MFMA_X3})
       for (int bits = 0; bits < 2 * 2 * 3 * 2 * 4; bits++) {
@@ -131,6 +132,7 @@ int main(int argc, char **argv) {
           if (k == PN_K_DIRECT || k == PN_K_BATCH_SH) CHECK(f32 && gru == (k == PN_K_DIRECT));
           // (b) the weights the kind reads are the ones built for (mode, narrow)
           CHECK(pn_kernel_weight_format(k) == pn_layer_weight_format(mode, p.narrow, li));
+          CHECK(pn_kernel_ct_round(k, gru, N) == pn_layer_ct_round(mode, p.narrow, li));      // ... and so is their column-tile rounding
           // (c) shadows read (panels, GRU state) and written (the output; the gains that leave an x3 network have none) exist
           int width[5];
           for (int j = 0; j < R.n_in; j++) {
@@ -139,18 +141,22 @@ int main(int argc, char **argv) {
           }
           if (pn_kernel_reads_shadows(k) && gru) CHECK(pn_state_shadowed(R.state, p, mode));
           if (pn_kernel_writes_shadow(k) && !(k == PN_K_X3 && R.out.entry == PN_ST_GR)) CHECK(pn_state_shadowed(R.out.entry, p, mode));
-          // (d) the launcher's own predicate takes the panels
-          switch (k) {
-            case PN_K_STRICT: break;                   // any geometry
-            case PN_K_X3: CHECK((gru ? pn_check_gru_geometry("x3", R.n_in, width, N) : pn_check_dense_geometry("x3", R.n_in, width, 1)) == 0); break;
-            case PN_K_DIRECT: CHECK(pn_check_gru_geometry("direct", R.n_in, width, N) == 0); break;
-            case PN_K_N16: CHECK(pn_check_n16_geometry("n16", R.n_in, width, 8) == 0); break;
-            case PN_K_N48: CHECK(pn_check_dense_geometry("n48", R.n_in, width, 1) == 0); break;
-            default: if (!gru) CHECK(pn_check_dense_geometry("fp32", R.n_in, width, 0) == 0);      // (the fp32 GRU launchers refuse nothing)
-          }
+          // (d) the kind has a launcher for the layer's type (pn_network.cpp static_asserts its table of launchers against these
+          // names), and that launcher's rule takes the panels
+          CHECK(k >= 0 && k < PN_K_COUNT && pn_kernel_launcher(k, gru) != NULL);
+          CHECK(pn_kernel_geometry_ok(k, gru, R.n_in, width, N) == 0);
         }
       }
-    CHECK(n_plans == 4 + 2 * 24 + 16); }      // STRICT; fp16 operands, split precision; fp32 MFMA (6 direct, 4 small, 6 batch)
+    CHECK(n_plans == 4 + 2 * 24 + 16);
+    // the rule is not vacuous: what each launcher is documented to refuse, it refuses (and a form that does not exist)
+    const int w96[1] = {96}, w128[1] = {128}, w64[1] = {64};
+    for (int k : {PN_K_BATCH, PN_K_BATCH_SH, PN_K_SMALL, PN_K_N48, PN_K_X3}) CHECK(pn_kernel_geometry_ok(k, false, 1, w96, 128) == -1);   // three K-tiles
+    CHECK(pn_kernel_geometry_ok(PN_K_STRICT, false, 1, w96, 128) == 0);
+    CHECK(pn_kernel_geometry_ok(PN_K_BATCH_SH, false, 1, w128, 34) == -1 && pn_kernel_geometry_ok(PN_K_BATCH, false, 1, w128, 34) == 0);
+    CHECK(pn_kernel_geometry_ok(PN_K_N16, false, 1, w64, 34) == -1 && pn_kernel_geometry_ok(PN_K_N48, false, 1, w128, 49) == -1);
+    CHECK(pn_kernel_geometry_ok(PN_K_X3, true, 1, w128, 96) == -1 && pn_kernel_geometry_ok(PN_K_DIRECT, true, 1, w128, 96) == -1);
+    CHECK(pn_kernel_geometry_ok(PN_K_SMALL, true, 1, w96, 128) == -1 && pn_kernel_geometry_ok(PN_K_BATCH, true, 1, w96, 128) == 0);
+    CHECK(pn_kernel_geometry_ok(PN_K_DIRECT, false, 1, w128, 128) == -1 && pn_kernel_geometry_ok(PN_K_N16, true, 1, w128, 128) == -1); }      // STRICT; fp16 operands, split precision; fp32 MFMA (6 direct, 4 small, 6 batch)
 
   // CLI helpers
   { std::vector<int> d;
@@ -227,7 +233,7 @@ int main(int argc, char **argv) {
   for (int li = 0; li < PN_NLAYERS; li++) {
     const PnLayerHost &H = m->L[li];
     const int K = H.nin * H.ks, ncols = H.nn * (H.kind == PN_KIND_GRU ? 3 : 1), k_alloc = li == PN_L_FC ? PN_FEAT_STRIDE : K;
-    const int ctr = H.kind == PN_KIND_GRU ? 1 : pn_dense_nt(H.nn);
+    const int ctr = pn_layer_ct_round(PN_NN_MFMA, 0, li);
     std::vector<float> wp(pn_packed_floats(k_alloc, ncols, ctr));
     pn_pack_weights(H.w, K, k_alloc, ncols, ctr, wp.data());
     if (H.rw) { std::vector<float> rp(pn_packed_floats(H.nn, ncols, 1)); pn_pack_weights(H.rw, H.nn, H.nn, ncols, 1, rp.data()); }
