@@ -12,6 +12,7 @@
  *  (2) The batched interface the GPU needs: one context = B independent 48 kHz streams advanced
  *      in lock-step, one 10 ms frame (480 samples) per stream per call.  Plain pointers and
  *      sizes only; device pointers are raw HIP device addresses (e.g. torch's data_ptr()).
+ *      8, 16 and 24 kHz streams go through a pn_rate beside the context (the rate converter, below).
  *
  * All functions are thread-compatible per context; one context belongs to one HIP device.
  * Errors: functions returning int give 0 on success, <0 on failure; pn_last_error() returns a
@@ -300,7 +301,8 @@ enum {
   PN_SS_BAD_VERSION = -2,
   PN_SS_BAD_SIZE = -3,      /* a buffer of the wrong size, or a header that names another record size */
   PN_SS_BAD_MODEL = -4,     /* written under another model (pn_model_digest differs) */
-  PN_SS_BAD_ARG = -5        /* NULL record or model */
+  PN_SS_BAD_ARG = -5,       /* NULL record or model */
+  PN_SS_BAD_RATE = -6       /* pn_rate_state_check: written by a converter of another rate, or a rate no converter has */
 };
 size_t pn_stream_state_bytes(void);            /* PN_STREAM_STATE_BYTES */
 /* Host only, needs no GPU: is `bytes` bytes at `record` one record that a context of `model` accepts?  PN_SS_OK or a
@@ -391,6 +393,91 @@ int pn_featgen_process_host_i16_files(pn_featgen *fg, const int16_t *h_speech, c
 int pn_featgen_run_files(int device, int n_jobs, const char *const *speech_paths, const char *const *noisy_paths,
                          const int *counts, const char *const *out_paths, const char *const *test_out_paths,
                          const char *const *test_in_paths);
+
+/* ---- batched rate converter: 8, 16 and 24 kHz streams through a 48 kHz context ------------------------------------------- */
+/* The engine runs at 48 kHz; a pn_rate is an object BESIDE a context (like pn_featgen: it adds nothing to the context's state)
+   that converts all of the context's streams from ONE low rate up to 48 kHz in front of a frame and back down behind it, on the
+   GPU (csrc/pn_rate.hip).  rate_hz is 8000, 16000 or 24000 — L = 48000 / rate_hz = 6, 3, 2; any other rate is refused.  A caller
+   with mixed rates uses one context (and converter) per rate: packed weights are shared between contexts of one model, device and
+   mode, so this costs state memory only.  A frame is still 10 ms: n = 480 / L = 80 | 160 | 240 samples per stream.
+
+   Arithmetic (fixed, so that a float32 model reproduces it bit for bit: tests/rate_model.py).  T = PN_RATE_TAPS = 16, D = T * L.
+   Prototype filter, k = -D..D:  h[k] = sinc(k / L) * I0(8 * sqrt(1 - (k / D)^2)) / I0(8)  (a Kaiser-windowed sinc, beta = 8),
+   computed in double for k >= 0, mirrored, h[0] = 1 and h[jL] = 0 (j != 0) exactly, rounded to fp32 once; the down-converter's taps
+   are g[k] = (float)(h_double[k] / L).
+     up    y[Lq + p] = sum_m x[m] * h[L(q - T - m) + p]:  phase p = 0 is the copy y[Lq] = x[q - T] (the input's bits), phases
+           1..L-1 sum over the 32 samples x[q - 2T + 1 .. q].  Per-stream state: the last 32 low-rate input samples.
+     down  z[m] = sum_{i = Lm - 2D + 1}^{Lm - 1} g[Lm - D - i] * o[i].  Per-stream state: the last 2D 48 kHz samples (192 | 96 | 64).
+   Every sum runs oldest sample first from acc = 0.0f as acc = acc + c * x, product and sum separately rounded (no FMA), so a
+   stream's output does not depend on the batch size, its slot or the block it ran in.
+   Delay from an input sample to the same sample in the output, in low-rate samples: 2880 / L + 2T
+
+       rate_hz    L    n     delay (samples)   delay (ms)   state record (bytes)
+        8000      6    80        512              64           912
+       16000      3   160        992              62           528
+       24000      2   240       1472              61.33        400
+
+   The engine runs in float between the two conversions; int16 exists only at the edges: input (float)v / 32768, output
+   trunc(z * 32768) wrapped to 16 bit, or saturated while pn_ctx_set_output_saturate is on.  The frame report (pn_ctx_set_report)
+   stays that of the 48 kHz signal inside the engine: 480 samples per frame, the engine's own 2880-sample delay, levels before the
+   down-conversion.
+   NOT provided: the pipelined pn_submit_host_* path, device-side record export / import, per-stream rates inside one context,
+   other rates, profiling families of the two kernels.
+
+   Host only, needing no GPU:
+   pn_rate_frame_samples: n, -1 for a refused rate.  pn_rate_delay_samples: the table above, -1.  pn_rate_taps: the fp32 table,
+   2D + 1 values for k = -D..D (down == 0: h; otherwise g), into taps[0..cap); returns the count, -1 for a refused rate or
+   cap < 2D + 1.  pn_rate_state_bytes: the record size, 0 for a refused rate.  pn_rate_state_check: is `bytes` bytes at `record`
+   one state record of a converter of rate_hz?  PN_SS_OK or a PN_SS_BAD_* code (pn_last_error says why).
+   State record (little-endian): 16-byte header — uint32 magic PN_RATE_STATE_MAGIC | uint32 version PN_RATE_STATE_VERSION |
+   uint32 record bytes | int32 rate_hz — then the 32 fp32 words of the up-converter's tail and the 2D words of the
+   down-converter's, each oldest sample first. */
+#define PN_RATE_TAPS 16
+#define PN_RATE_STATE_MAGIC 0x53524e50u        /* "PNRS" */
+#define PN_RATE_STATE_VERSION 1
+#define PN_RATE_STATE_HEADER_BYTES 16
+typedef struct pn_rate pn_rate;
+int pn_rate_frame_samples(int rate_hz);
+int pn_rate_delay_samples(int rate_hz);
+int pn_rate_taps(int rate_hz, int down, float *taps, int cap);
+size_t pn_rate_state_bytes(int rate_hz);
+int pn_rate_state_check(const void *record, size_t bytes, int rate_hz);
+/* A converter for every stream of ctx.  It BORROWS ctx — its device, n_streams and HIP stream — and owns its state, its tap
+   tables and the 48 kHz rows between the conversions: destroy the converter before ctx.  State starts all-zero.  Everything
+   below runs on the context's stream, so it is ordered against pn_process_*, pn_ctx_reset_streams and the rest like they are
+   against each other.  Id lists are host arrays under the context's rules (in range and, where streams advance or are imported,
+   distinct; otherwise -1 and nothing is launched); the caller may reuse them when the call returns. */
+pn_rate *pn_rate_create(pn_ctx *ctx, int rate_hz);
+void pn_rate_destroy(pn_rate *r);
+int pn_rate_reset(pn_rate *r);                       /* zero every stream's tails */
+/* The converter's half of a slot reset, asynchronous like pn_ctx_reset_streams (duplicates allowed): a caller whose slot starts a
+   new call calls both. */
+int pn_rate_reset_streams(pn_rate *r, const int32_t *ids, int n);
+/* The two kernels on their own, device buffers (16-byte aligned), asynchronous.  d_in [n_streams][n] -> d_out48 [n_streams][480],
+   and d_in48 [n_streams][480] -> d_out [n_streams][n].  ids == NULL: every stream; otherwise only the n_ids listed rows are
+   read, written and advanced — an unlisted stream's tails and output row are not touched. */
+int pn_rate_up_f32(pn_rate *r, const float *d_in, float *d_out48, const int32_t *ids, int n_ids);
+int pn_rate_up_i16(pn_rate *r, const int16_t *d_in, float *d_out48, const int32_t *ids, int n_ids);
+int pn_rate_down_f32(pn_rate *r, const float *d_in48, float *d_out, const int32_t *ids, int n_ids);
+int pn_rate_down_i16(pn_rate *r, const float *d_in48, int16_t *d_out, const int32_t *ids, int n_ids);
+/* One whole frame of every stream: up, pn_process_f32 on converter-owned 48 kHz rows, down.  d_in, d_out [n_streams][n] at the
+   low rate; d_gr (optional) [n_streams][68] as for pn_process_*.  When the frame fails inside pn_process_f32 the call returns -1
+   with the context's error kept: reset the context AND the converter before reuse.
+   _active: only the n listed streams advance (pn_process_f32_active in the middle); the converter has no save and restore —
+   its kernels simply run over the listed rows.  _host: host buffers, synchronous (H2D, frame, D2H, synchronise), like
+   pn_process_host_*; frames in flight on the context's pipelined host path are completed first. */
+int pn_rate_process_f32(pn_rate *r, const float *d_in, float *d_out, float *d_gr);
+int pn_rate_process_i16(pn_rate *r, const int16_t *d_in, int16_t *d_out, float *d_gr);
+int pn_rate_process_f32_active(pn_rate *r, const float *d_in, float *d_out, float *d_gr, const int32_t *ids, int n);
+int pn_rate_process_i16_active(pn_rate *r, const int16_t *d_in, int16_t *d_out, float *d_gr, const int32_t *ids, int n);
+int pn_rate_process_host_f32(pn_rate *r, const float *h_in, float *h_out, float *h_gr);
+int pn_rate_process_host_i16(pn_rate *r, const int16_t *h_in, int16_t *h_out, float *h_gr);
+/* State records of streams ids[0..n) to / from host memory [n][pn_rate_state_bytes(rate)], synchronous.  The import checks every
+   header before anything is launched and is all-or-nothing (distinct ids): a record of another rate, or any other bad record or
+   id, refuses the call and leaves the converter untouched.  With pn_ctx_export_streams_host / pn_ctx_import_streams_host this
+   moves a narrowband stream between slots, contexts, devices and processes bit for bit. */
+int pn_rate_export_streams_host(pn_rate *r, const int32_t *ids, int n, void *h_records);
+int pn_rate_import_streams_host(pn_rate *r, const int32_t *ids, int n, const void *h_records);
 
 const char *pn_last_error(void);
 const char *pn_version(void);

@@ -17,6 +17,10 @@ FRAME = 480
 # per-stream state records (include/percepnet_hip.h): size, and the PN_SS_* verdicts of a refused record
 STREAM_STATE_BYTES = 54688
 SS_OK, SS_BAD_MAGIC, SS_BAD_VERSION, SS_BAD_SIZE, SS_BAD_MODEL, SS_BAD_ARG = 0, -1, -2, -3, -4, -5
+SS_BAD_RATE = -6          # pn_rate_state_check: a record of another rate
+# batched rate converter (include/percepnet_hip.h pn_rate): the rates it takes, taps per phase
+RATES = (8000, 16000, 24000)
+RATE_TAPS = 16
 # per-stream frame report (include/percepnet_hip.h pn_ctx_set_report): one record of PN_REPORT_WORDS 32-bit words per stream
 REPORT_WORDS = 8
 REPORT_DTYPE = np.dtype([("in_peak", "<f4"), ("in_energy", "<f4"), ("out_peak", "<f4"), ("out_energy", "<f4"), ("gain_mean", "<f4"),
@@ -111,6 +115,27 @@ def load_library():
             getattr(L, name).argtypes = [_vp, ctypes.c_int]
         for name in ("pn_ctx_read_report", "pn_ctx_read_report_dev", "pn_host_next_report"):
             getattr(L, name).argtypes = [_vp, _vp]
+    if hasattr(L, "pn_rate_create"):
+        for name in ("pn_rate_frame_samples", "pn_rate_delay_samples"):
+            getattr(L, name).argtypes = [ctypes.c_int]
+        L.pn_rate_taps.argtypes = [ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int]
+        L.pn_rate_state_bytes.restype = ctypes.c_size_t
+        L.pn_rate_state_bytes.argtypes = [ctypes.c_int]
+        L.pn_rate_state_check.argtypes = [_vp, ctypes.c_size_t, ctypes.c_int]
+        L.pn_rate_create.restype = _vp
+        L.pn_rate_create.argtypes = [_vp, ctypes.c_int]
+        L.pn_rate_destroy.argtypes = [_vp]
+        L.pn_rate_destroy.restype = None
+        L.pn_rate_reset.argtypes = [_vp]
+        L.pn_rate_reset_streams.argtypes = [_vp, _vp, ctypes.c_int]
+        for name in ("pn_rate_up_f32", "pn_rate_up_i16", "pn_rate_down_f32", "pn_rate_down_i16"):
+            getattr(L, name).argtypes = [_vp, _vp, _vp, _vp, ctypes.c_int]
+        for name in ("pn_rate_process_f32", "pn_rate_process_i16", "pn_rate_process_host_f32", "pn_rate_process_host_i16"):
+            getattr(L, name).argtypes = [_vp, _vp, _vp, _vp]
+        for name in ("pn_rate_process_f32_active", "pn_rate_process_i16_active"):
+            getattr(L, name).argtypes = [_vp, _vp, _vp, _vp, _vp, ctypes.c_int]
+        for name in ("pn_rate_export_streams_host", "pn_rate_import_streams_host"):
+            getattr(L, name).argtypes = [_vp, _vp, ctypes.c_int, _vp]
     L.pn_ctx_debug_copy.restype = ctypes.c_longlong
     L.pn_ctx_debug_copy.argtypes = [_vp, ctypes.c_int, _vp, ctypes.c_longlong]
     L.pn_ctx_set_profiling.argtypes = [_vp, ctypes.c_int]
@@ -412,6 +437,161 @@ def stream_state_check(record, model):
     b = np.ascontiguousarray(np.frombuffer(bytes(record), np.uint8)) if not isinstance(record, np.ndarray) else \
         np.ascontiguousarray(record, dtype=np.uint8)
     return int(L.pn_stream_state_check(b.ctypes.data if b.size else None, b.size, model.h))
+
+
+def rate_frame_samples(rate_hz):
+    """Samples per 10 ms frame at rate_hz: 80 | 160 | 240; -1 for a rate no converter takes (pn_rate_frame_samples, host only)."""
+    return int(load_library().pn_rate_frame_samples(int(rate_hz)))
+
+
+def rate_delay_samples(rate_hz):
+    """Input-to-output delay of a converted stream in samples at rate_hz: 512 | 992 | 1472; -1 for a refused rate (host only)."""
+    return int(load_library().pn_rate_delay_samples(int(rate_hz)))
+
+
+def rate_taps(rate_hz, down=False):
+    """The converter's fp32 taps for k = -D..D, D = 16 * 48000 / rate_hz: h (up) or g = h / L (down) (pn_rate_taps, host only)."""
+    L = load_library()
+    n = rate_frame_samples(rate_hz)
+    if n < 0:
+        raise PercepNetError(_err(L))
+    t = np.empty(2 * RATE_TAPS * (FRAME // n) + 1, np.float32)
+    if L.pn_rate_taps(int(rate_hz), int(bool(down)), t.ctypes.data, int(t.size)) != t.size:
+        raise PercepNetError(_err(L))
+    return t
+
+
+def rate_state_bytes(rate_hz):
+    """Bytes of one converter state record at rate_hz: 912 | 528 | 400; 0 for a refused rate (host only)."""
+    return int(load_library().pn_rate_state_bytes(int(rate_hz)))
+
+
+def rate_state_check(record, rate_hz):
+    """PN_SS_OK (0) or the PN_SS_BAD_* verdict a converter of rate_hz gives the bytes `record` (host only, no GPU)."""
+    L = load_library()
+    b = np.ascontiguousarray(np.frombuffer(bytes(record), np.uint8)) if not isinstance(record, np.ndarray) else \
+        np.ascontiguousarray(record, dtype=np.uint8)
+    return int(L.pn_rate_state_check(b.ctypes.data if b.size else None, b.size, int(rate_hz)))
+
+
+class RateConverter:
+    """8, 16 or 24 kHz streams through a 48 kHz Context (pn_rate): a converter beside `ctx` for all of its streams at ONE rate.
+    It borrows the context (device, n_streams, HIP stream): close the converter before the context."""
+
+    def __init__(self, ctx, rate_hz):
+        self.L = ctx.L
+        self.ctx = ctx
+        self.rate = int(rate_hz)
+        self.n_streams = ctx.n_streams
+        self.h = self.L.pn_rate_create(ctx.h, self.rate)
+        if not self.h:
+            raise PercepNetError(_err(self.L))
+        self.frame = rate_frame_samples(self.rate)
+        self.state_bytes = rate_state_bytes(self.rate)
+
+    def close(self):
+        if self.h:
+            if self.ctx.h:                      # (a context closed first has taken the device buffers' stream with it)
+                self.L.pn_rate_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise PercepNetError(_err(self.L))
+
+    @staticmethod
+    def _ids(ids):
+        if ids is None:
+            return None, 0
+        a = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).ravel())
+        return a, int(a.size)
+
+    def reset(self):
+        self._chk(self.L.pn_rate_reset(self.h))
+
+    def reset_streams(self, ids):
+        """The converter's half of a slot reset (pn_rate_reset_streams): call Context.reset_streams for the same slots."""
+        a, n = self._ids(ids)
+        self._chk(self.L.pn_rate_reset_streams(self.h, a.ctypes.data, n))
+
+    # the two kernels on their own: device pointers (ints); ids None = every stream
+    def _kernel(self, name, d_in, d_out, ids):
+        a, n = self._ids(ids)
+        self._chk(getattr(self.L, name)(self.h, d_in, d_out, a.ctypes.data if a is not None else None, n))
+
+    def up_f32_dev(self, d_in, d_out48, ids=None):
+        self._kernel("pn_rate_up_f32", d_in, d_out48, ids)
+
+    def up_i16_dev(self, d_in, d_out48, ids=None):
+        self._kernel("pn_rate_up_i16", d_in, d_out48, ids)
+
+    def down_f32_dev(self, d_in48, d_out, ids=None):
+        self._kernel("pn_rate_down_f32", d_in48, d_out, ids)
+
+    def down_i16_dev(self, d_in48, d_out, ids=None):
+        self._kernel("pn_rate_down_i16", d_in48, d_out, ids)
+
+    # one whole frame, device pointers: [n_streams][frame] in and out at the low rate, d_gr [n_streams][68] or None
+    def process_f32_dev(self, d_in, d_out, d_gr=None, ids=None):
+        if ids is None:
+            self._chk(self.L.pn_rate_process_f32(self.h, d_in, d_out, d_gr))
+        else:
+            a, n = self._ids(ids)
+            self._chk(self.L.pn_rate_process_f32_active(self.h, d_in, d_out, d_gr, a.ctypes.data, n))
+
+    def process_i16_dev(self, d_in, d_out, d_gr=None, ids=None):
+        if ids is None:
+            self._chk(self.L.pn_rate_process_i16(self.h, d_in, d_out, d_gr))
+        else:
+            a, n = self._ids(ids)
+            self._chk(self.L.pn_rate_process_i16_active(self.h, d_in, d_out, d_gr, a.ctypes.data, n))
+
+    # host numpy entry points (synchronous)
+    def _host(self, name, frame, dtype, want_gr):
+        frame = np.ascontiguousarray(frame, dtype=dtype).reshape(self.n_streams, self.frame)
+        out = np.empty_like(frame)
+        gr = np.empty((self.n_streams, 68), np.float32) if want_gr else None
+        self._chk(getattr(self.L, name)(self.h, frame.ctypes.data, out.ctypes.data, gr.ctypes.data if want_gr else None))
+        return out, gr
+
+    def process_f32(self, frame, want_gr=True):
+        return self._host("pn_rate_process_host_f32", frame, np.float32, want_gr)
+
+    def process_i16(self, frame, want_gr=True):
+        return self._host("pn_rate_process_host_i16", frame, np.int16, want_gr)
+
+    def run_pcm(self, pcm):
+        """percepnet_run --rate semantics for a batch: pcm int16 [B, n_frames * frame] -> out int16 [B, (n_frames - 1) * frame]
+        (the first output frame dropped, like Context.run_pcm)."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.int16).reshape(self.n_streams, -1)
+        f, n = self.frame, pcm.shape[1] // self.frame
+        out = np.zeros((self.n_streams, max(n - 1, 0) * f), np.int16)
+        for t in range(n):
+            o, _ = self.process_i16(pcm[:, t * f:(t + 1) * f], want_gr=False)
+            if t > 0:
+                out[:, (t - 1) * f:t * f] = o
+        return out
+
+    def export_streams(self, ids):
+        """-> uint8 [n, state_bytes]: the converter's state of the streams `ids` (pn_rate_export_streams_host)."""
+        a, n = self._ids(ids)
+        rec = np.empty((n, self.state_bytes), np.uint8)
+        self._chk(self.L.pn_rate_export_streams_host(self.h, a.ctypes.data, n, rec.ctypes.data))
+        return rec
+
+    def import_streams(self, ids, records):
+        """Records from export_streams of a converter of the same rate into the distinct streams `ids`; all or nothing."""
+        a, n = self._ids(ids)
+        rec = np.ascontiguousarray(records, dtype=np.uint8)
+        if rec.size != n * self.state_bytes:
+            raise PercepNetError(f"{rec.size} record bytes for {n} streams (a record at {self.rate} Hz has {self.state_bytes})")
+        self._chk(self.L.pn_rate_import_streams_host(self.h, a.ctypes.data, n, rec.ctypes.data))
 
 
 class FeatGen:

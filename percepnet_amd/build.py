@@ -19,7 +19,7 @@ LIB = os.path.join(LIBDIR, "libpercepnet_hip.so")
 RUN = os.path.join(LIBDIR, "percepnet_run")
 EXPORT_MAP = os.path.join(CSRC, "libpercepnet_hip.map")    # ld version script: the export list (everything else is local)
 SOURCES = ["pn_tables.cpp", "pn_model.cpp", "pn_pack.cpp", "pn_dsp_fe.hip", "pn_dsp_fe_g2.hip", "pn_dsp_fe_split_s.hip", "pn_dsp_fe_split_p.hip", "pn_dsp.hip", "pn_outstage.hip", "pn_nn.hip", "pn_nn_small.hip", "pn_nn_x3.hip", "pn_nn_d.hip", "pn_nn_n48.hip", "pn_targets.hip", "pn_state.hip", "pn_active.hip", "pn_stream_state.hip", "pn_context.cpp", "pn_network.cpp",
-           "pn_featgen.cpp", "rnnoise_compat.cpp"]
+           "pn_featgen.cpp", "pn_rate.hip", "pn_rate.cpp", "rnnoise_compat.cpp"]
 # percepnet_run.cpp / percepnet_featgen.cpp (the CLIs) are linked separately against the library
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden",
          "-Wall", "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unused-value", "-Wno-unused-result"]
@@ -185,6 +185,12 @@ def toolchain_info(hipcc):
     return out.strip()
 
 
+def _obj(dirname, src):
+    """Object file of a source: its stem, or stem_host for the .cpp of a (kernel file, host file) pair that share one (pn_rate)."""
+    stem, ext = src.rsplit(".", 1)
+    return os.path.join(dirname, stem + ("_host" if ext == "cpp" and stem + ".hip" in SOURCES else "") + ".o")
+
+
 def _stale(target, deps):
     if not os.path.exists(target):
         return True
@@ -202,9 +208,9 @@ def build_variant(name, defines, verbose=False, only=None):
     objs = []
     for src in SOURCES:
         if only is not None and src not in only:
-            objs.append(os.path.join(LIBDIR, src.rsplit(".", 1)[0] + ".o"))
+            objs.append(_obj(LIBDIR, src))
             continue
-        o = os.path.join(vdir, src.rsplit(".", 1)[0] + ".o")
+        o = _obj(vdir, src)
         cmd = [hipcc] + FLAGS + EXTRA_FLAGS.get(src, []) + list(defines) + (["-x", "hip"] if src.endswith(".cpp") else []) + \
               ["-c", os.path.join(CSRC, src), "-o", o]
         if verbose:
@@ -226,7 +232,7 @@ def build(force=False, verbose=True):
     resources = {}
     for src in SOURCES:
         s = os.path.join(CSRC, src)
-        o = os.path.join(LIBDIR, src.rsplit(".", 1)[0] + ".o")
+        o = _obj(LIBDIR, src)
         rlog = o + ".resources.txt"
         if force or _stale(o, deps) or (src in RESOURCE_SOURCES and not os.path.exists(rlog)):
             cmd = [hipcc] + FLAGS + EXTRA_FLAGS.get(src, []) + (["-x", "hip"] if src.endswith(".cpp") else []) + ["-c", s, "-o", o]

@@ -5,8 +5,15 @@
 // dropped, main.cpp:32-33); with a single pair ./feature_test.raw gets 68 floats per frame.
 //
 //   percepnet_run [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N]
-//                 [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
+//                 [--rate 8000|16000|24000] [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
 //                 in0.pcm out0.pcm [in1.pcm out1.pcm ...]
+//
+// --rate R: the files are raw int16 at R Hz instead of 48 kHz, in frames of n = 480 * R / 48000 samples (80 | 160 | 240): a rate
+// converter beside each context (pn_rate) takes every frame up to 48 kHz in front of the engine and back down behind it.  The
+// per-stream contract is unchanged: (frames-1)*n samples out, first output frame and partial tail dropped.  The frames go through
+// the synchronous pn_rate_process_host_i16 (the converter has no pipelined path), --report reads each frame's records after
+// it (pn_ctx_read_report) — its figures stay those of the 48 kHz signal inside the engine — and the converter's slots are reset
+// with the context's.  Without --rate nothing of this runs.
 //
 // --atten-lim DB: every stream takes out at most DB dB of noise (pn_ctx_set_atten_limit; 0 = the input, delayed; default: no
 // limit).  A slot reset clears a stream's limit (a reset slot is a new call), so the limit is set again on every reset slot.
@@ -44,6 +51,7 @@ struct Shard { int device, first, count, rc; std::string err; };
 // Everything a shard holds; released on every exit path of run_shard.
 struct ShardRes {
   pn_ctx *cx = NULL;
+  pn_rate *rt = NULL;                   // --rate: the converter beside cx (destroyed before it)
   std::vector<FILE *> fin, fout;        // per SLOT: the pair currently playing there
   FILE *ftap = NULL;
   // one of three rotating pinned buffer sets; file[s] = the output file the frame of slot s belongs to (NULL: slot idle),
@@ -55,6 +63,7 @@ struct ShardRes {
     for (FILE *f : fin) if (f) fclose(f);
     for (FILE *f : fout) if (f) fclose(f);
     if (ftap) fclose(ftap);
+    pn_rate_destroy(rt);
     pn_ctx_destroy(cx);
   }
 };
@@ -67,10 +76,12 @@ struct ShardRes {
 static bool g_numa = true, g_verbose = false;
 static float g_atten_lim = INFINITY;                  // --atten-lim: dB for every stream (inf: not set)
 static bool g_saturate = false, g_report = false;     // --saturate, --report
+static int g_rate = 0;                                // --rate: the files' sample rate (0: 48 kHz, no converter)
 // --report: what a pair's written frames add up to (one report record = PN_REPORT_WORDS words, include/percepnet_hip.h)
 struct PairStat { long frames = 0; long long clipped = 0; float peak = 0.f; double e_in = 0, e_out = 0; };
 static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, int postfilter, bool tap, int n_slots) {
   const int P = sh->count, B = n_slots > 0 && n_slots < P ? n_slots : P;
+  const size_t FS = g_rate ? (size_t)pn_rate_frame_samples(g_rate) : PN_FRAME_SIZE;     // samples per frame in the files
   auto fail = [&](int rc, const std::string &msg) { sh->rc = rc; sh->err = msg; };
   ShardRes R;
   // this thread owns the device from here on: run on the CPUs of the GPU's NUMA node BEFORE the context and the pinned
@@ -83,6 +94,8 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
   R.cx = pn_ctx_create(m, sh->device, B, nn_mode, NULL);
   pn_ctx *cx = R.cx;
   if (!cx) return fail(3, std::string("pn_ctx_create: ") + pn_last_error());
+  if (g_rate && !(R.rt = pn_rate_create(cx, g_rate))) return fail(3, std::string("pn_rate_create: ") + pn_last_error());
+  pn_rate *rt = R.rt;
   if (postfilter) pn_ctx_set_postfilter(cx, 1);
   if ((g_saturate && pn_ctx_set_output_saturate(cx, 1)) || (g_report && pn_ctx_set_report(cx, 1))) return fail(3, pn_last_error());
   auto set_limit = [&](const int32_t *ids, int n) {     // --atten-lim on these slots (after creation and after every slot reset)
@@ -116,8 +129,8 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
   Slot *slot = R.slot;
   for (int k = 0; k < 3; k++) {
     Slot &sl = slot[k];
-    sl.in = (int16_t *)pn_host_alloc((size_t)B * PN_FRAME_SIZE * sizeof(int16_t));
-    sl.out = (int16_t *)pn_host_alloc((size_t)B * PN_FRAME_SIZE * sizeof(int16_t));
+    sl.in = (int16_t *)pn_host_alloc((size_t)B * FS * sizeof(int16_t));
+    sl.out = (int16_t *)pn_host_alloc((size_t)B * FS * sizeof(int16_t));
     sl.gr = (float *)pn_host_alloc((size_t)B * 68 * sizeof(float));
     if (g_report) sl.rep = (uint32_t *)pn_host_alloc((size_t)B * PN_REPORT_WORDS * sizeof(uint32_t));
     if (!sl.in || !sl.out || !sl.gr || (g_report && !sl.rep)) return fail(5, pn_last_error());
@@ -128,7 +141,7 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
     for (int s = 0; s < B; s++) {
       if (!sl.file[s]) continue;
       if (ftap) fwrite(&sl.gr[(size_t)s * 68], sizeof(float), 68, ftap);
-      if (!sl.skip[s]) fwrite(&sl.out[(size_t)s * PN_FRAME_SIZE], sizeof(int16_t), PN_FRAME_SIZE, sl.file[s]);
+      if (!sl.skip[s]) fwrite(&sl.out[(size_t)s * FS], sizeof(int16_t), FS, sl.file[s]);
       if (g_report) {
         PairStat &ps = stat[sl.pair[s]];
         if (!sl.skip[s]) {
@@ -154,9 +167,9 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
     Slot &sl = slot[t % 3];
     restart.clear();
     for (int s = 0; s < B; s++) {
-      int16_t *x = sl.in + (size_t)s * PN_FRAME_SIZE;
+      int16_t *x = sl.in + (size_t)s * FS;
       sl.file[s] = NULL; sl.skip[s] = 0; sl.last[s] = 0;
-      if (fin[s] && fread(x, sizeof(int16_t), PN_FRAME_SIZE, fin[s]) != PN_FRAME_SIZE) {
+      if (fin[s] && fread(x, sizeof(int16_t), FS, fin[s]) != FS) {
         // this pair is finished (partial tail dropped, main.cpp:32-33): mark the frame it supplied last as its final one
         fclose(fin[s]); fin[s] = NULL;
         Slot &prev = slot[(t + 2) % 3];                // = frame t - 1
@@ -164,19 +177,25 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
         fout[s] = NULL;
         while (next_pair < P) {                        // the slot starts over with the next waiting pair, from this frame on
           if (!open_pair(s)) return;
-          if (fread(x, sizeof(int16_t), PN_FRAME_SIZE, fin[s]) == PN_FRAME_SIZE) { restart.push_back(s); first[s] = 1; break; }
+          if (fread(x, sizeof(int16_t), FS, fin[s]) == FS) { restart.push_back(s); first[s] = 1; break; }
           fclose(fin[s]); fin[s] = NULL; fclose(fout[s]); fout[s] = NULL;       // shorter than one frame: an empty output, next pair
         }
         if (!fin[s]) n_alive--;
       }
       if (fin[s]) { sl.file[s] = fout[s]; sl.skip[s] = first[s]; first[s] = 0; sl.pair[s] = cur_pair[s]; }
-      else memset(x, 0, PN_FRAME_SIZE * sizeof(int16_t));
+      else memset(x, 0, FS * sizeof(int16_t));
     }
     if (n_alive == 0) break;
     if (!restart.empty() && (pn_ctx_reset_streams(cx, restart.data(), (int)restart.size()) ||
+                             (rt && pn_rate_reset_streams(rt, restart.data(), (int)restart.size())) ||
                              set_limit(restart.data(), (int)restart.size()))) return fail(5, pn_last_error());
-    if (g_report && pn_host_next_report(cx, sl.rep)) return fail(5, pn_last_error());
-    if (pn_submit_host_i16(cx, sl.in, sl.out, sl.gr)) return fail(5, pn_last_error());
+    if (rt) {                                          // --rate: one synchronous frame, then its report records
+      if (pn_rate_process_host_i16(rt, sl.in, sl.out, sl.gr)) return fail(5, pn_last_error());
+      if (g_report && pn_ctx_read_report(cx, sl.rep)) return fail(5, pn_last_error());
+    } else {
+      if (g_report && pn_host_next_report(cx, sl.rep)) return fail(5, pn_last_error());
+      if (pn_submit_host_i16(cx, sl.in, sl.out, sl.gr)) return fail(5, pn_last_error());
+    }
     if (t >= 2) flush(slot[(t - 2) % 3]);
   }
   if (pn_host_wait(cx)) return fail(5, pn_last_error());
@@ -201,6 +220,10 @@ int main(int argc, char **argv) {
     }
     else if (!strcmp(argv[ai], "--saturate")) g_saturate = true;     // int16 output saturates instead of wrapping (pn_ctx_set_output_saturate)
     else if (!strcmp(argv[ai], "--report")) g_report = true;         // one line of levels and clipping per pair (pn_ctx_set_report)
+    else if (!strcmp(argv[ai], "--rate") && ai + 1 < argc) {        // the files' sample rate: a rate converter beside each context (pn_rate)
+      g_rate = atoi(argv[++ai]);
+      if (pn_rate_frame_samples(g_rate) < 0) { fprintf(stderr, "--rate: expected 8000, 16000 or 24000, got '%s'\n", argv[ai]); return 1; }
+    }
     else if (!strcmp(argv[ai], "--no-numa")) g_numa = false;         // leave the host threads' CPU affinity alone
     else if (!strcmp(argv[ai], "--verbose")) g_verbose = true;       // one line per device: its NUMA binding
     else if (!strcmp(argv[ai], "--slots") && ai + 1 < argc) n_slots = atoi(argv[++ai]);   // concurrent streams per device: pairs queue for them
@@ -216,7 +239,7 @@ int main(int argc, char **argv) {
   if (devices.empty()) devices.push_back(0);
   const int nfiles = argc - ai;
   if (nfiles < 2 || (nfiles & 1)) {
-    fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv[0]);
+    fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N] [--rate 8000|16000|24000] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv[0]);
     return 1;
   }
   const int B = nfiles / 2;

@@ -197,7 +197,7 @@ static int id_ring_stage(pn_ctx *c, pn_ctx::IdRing &r, const int32_t *ids, int n
 // ids[0..n) (host) -> c->ids.d, asynchronously on the context's stream (frames may be in flight); the launches that read it follow
 // on the same stream.  NULL on failure.  payload (optional): payload_words more 32-bit words staged in the same copy, at
 // c->ids.d + stage_payload_offset(n)
-static const int *stage_ids(pn_ctx *c, const int32_t *ids, int n, const void *payload = NULL, int payload_words = 0) {
+const int *stage_ids(pn_ctx *c, const int32_t *ids, int n, const void *payload, int payload_words) {
   const int words = payload_words ? stage_payload_offset(n) + payload_words : n;
   if (id_ring_reserve(c, c->ids, words < 1024 ? 1024 : words) || id_ring_stage(c, c->ids, ids, n, payload, payload_words, words)) return NULL;
   return c->ids.d;

@@ -85,6 +85,9 @@ struct pn_ctx {
 int dev_alloc_into(std::vector<void *> &allocs, size_t &total, hipStream_t stream, void **p, size_t bytes, bool zero);
 // the shared tables built on the host and copied to a new device buffer (synchronous); tansig (optional): the activation table alone
 int tables_upload(std::vector<void *> &allocs, size_t &total, hipStream_t stream, PnTables **tables, float **tansig);
+// ids[0..n) (host) -> the context's id ring on the device, asynchronously on the context's stream; NULL on failure.  For the
+// objects beside a context that take id lists under its rules (pn_rate.cpp)
+const int *stage_ids(pn_ctx *c, const int32_t *ids, int n, const void *payload = NULL, int payload_words = 0);
 int pipe_make_stream(pn_ctx *c, hipStream_t *out, char how, int prio, char fallback, const std::vector<hipStream_t> &others, char *kind);
 // ---- pn_network.cpp ---------------------------------------------------------------------------------------------------------
 int weights_acquire(pn_ctx *c, const pn_model *model);     // c->weights, c->L: the shared device copy for c's key, built by its first user

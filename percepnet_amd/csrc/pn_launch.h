@@ -75,6 +75,13 @@ void pn_launch_backend(hipStream_t st, const PnTables *T, int n_streams, const f
 // hist_slot of the side's history ring.  One wavefront per stream, no grid cap.
 void pn_launch_outstage(hipStream_t st, int n_streams, const float *o, const PnDspSide &s, int hist_slot, const float *gr,
                         int16_t *pcm, int saturate, void *report);
+// the rate converter (pn_rate.hip; factor = 48000 / rate = 6 | 3 | 2, arithmetic in pn_rate_design.h): one wavefront per row, rows d_ids[0..n_rows) or,
+// with d_ids == NULL, streams 0..n_rows.  up: in [.][480 / factor] float or int16 -> out48 [.][480], tail [.][32]; down: in48 [.][480] ->
+// out [.][480 / factor] float or int16 (wrapping or saturating cast), tail [.][2 * 16 * factor]; taps: the 2 * 16 * factor + 1 fp32 taps on the
+// device.  -1 (pn_set_error) without launching for another L.  records: state record i <-> the tails of stream d_ids[i]
+int pn_launch_rate_up(hipStream_t st, int factor, int is_i16, int n_rows, const int *d_ids, const void *in, float *out48, float *tail, const float *taps);
+int pn_launch_rate_down(hipStream_t st, int factor, int is_i16, int n_rows, const int *d_ids, const float *in48, void *out, int saturate, float *tail, const float *taps);
+void pn_launch_rate_records(hipStream_t st, int factor, int rate_hz, const int *d_ids, int n, float *tail_up, float *tail_down, void *rec, int scatter);
 // ---- the network launchers (pn_nn*.hip) -----------------------------------------------------------------------------------------
 // Device pointers of a layer's biases and weights in the formats of pn_network.h: raw (w, rw), packed fp32 or fp16 planes (wp,
 // rwp), the 16x16x4 packing of a narrow layer (wq)

@@ -22,13 +22,6 @@
 #define OS_OWNERS (PN_FRAME / 8)   // lanes that own samples
 static_assert(PN_FRAME % 8 == 0 && OS_OWNERS <= OS_LANES && PN_HIST_STRIDE % 4 == 0 && PN_REPORT_WORDS == 8, "eight samples per lane, 16-byte aligned rows");
 
-// the saturating cast of t = o * 32768: NaN -> 0, else trunc(t) clamped to the int16 range
-__device__ __forceinline__ int16_t pn_f2s_sat(float t) {
-  if (t >= 32768.f) return 32767;
-  if (t <= -32769.f) return -32768;
-  return t == t ? (int16_t)(int32_t)t : (int16_t)0;
-}
-
 __device__ __forceinline__ float os_wave_sum(float v) {
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m);

@@ -1,0 +1,253 @@
+// Host side of the batched rate converter (include/percepnet_hip.h "batched rate converter"): an object BESIDE a context, built
+// like the feature generator — it borrows the context's device, batch size and HIP stream, and owns everything else: the two
+// tap tables on the device, the per-stream tails of the two kernels (pn_rate.hip), the 48 kHz rows between the conversions and
+// the staging rows of the host-buffer path.  Nothing of it lives in pn_ctx, its state table or its records.  Every launch goes
+// to the context's stream, so a converter call is ordered against the context's calls like they are against each other.
+#include "pn_context.h"      // the context it borrows, the launchers, dev_alloc_into, stage_ids
+#include "pn_rate_design.h"
+#include <string>
+#include <vector>
+
+struct pn_rate {
+  pn_ctx *c;                    // borrowed: device, B, stream, the id ring, the saturate setting
+  int rate, L, n, td;           // rate_hz, 48000 / rate, samples per frame, 2D
+  size_t bytes;
+  float *taps_up, *taps_down;   // [2D + 1] h, g
+  float *tail_up, *tail_down;   // [B][32], [B][2D]: the state
+  float *x48, *y48;             // [B][480]: the engine's input and output rows of a whole frame
+  void *io_in, *io_out;         // [B][n] 4-byte words: staging rows of the host-buffer path
+  float *io_gr;                 // [B][68]
+  std::vector<void *> allocs;
+};
+
+// ---- host only ---------------------------------------------------------------------------------------------------------------
+extern "C" int pn_rate_frame_samples(int rate_hz) {
+  const int L = pn_rate_factor(rate_hz);
+  if (!L) { pn_set_error("rate %d Hz: a converter takes 8000, 16000 or 24000", rate_hz); return -1; }
+  return PN_FRAME / L;
+}
+extern "C" int pn_rate_delay_samples(int rate_hz) {
+  const int L = pn_rate_factor(rate_hz);
+  if (!L) { pn_set_error("rate %d Hz: a converter takes 8000, 16000 or 24000", rate_hz); return -1; }
+  return 6 * PN_FRAME / L + 2 * PN_RATE_TAPS;          // the engine's 2880 samples at the low rate, T up and T down
+}
+extern "C" int pn_rate_taps(int rate_hz, int down, float *taps, int cap) {
+  const int L = pn_rate_factor(rate_hz);
+  if (!L) { pn_set_error("rate %d Hz: a converter takes 8000, 16000 or 24000", rate_hz); return -1; }
+  return pn_rate_design(L, down, taps, cap);
+}
+extern "C" size_t pn_rate_state_bytes(int rate_hz) {
+  const int L = pn_rate_factor(rate_hz);
+  if (!L) { pn_set_error("rate %d Hz: a converter takes 8000, 16000 or 24000", rate_hz); return 0; }
+  return 4 * pn_rate_record_words(L);
+}
+extern "C" int pn_rate_state_check(const void *record, size_t bytes, int rate_hz) { return pn_rate_record_check(record, bytes, rate_hz); }
+
+// ---- lifecycle ---------------------------------------------------------------------------------------------------------------
+extern "C" void pn_rate_destroy(pn_rate *r) {
+  if (!r) return;
+  DeviceGuard _dg(r->c->device);
+  hipStreamSynchronize(r->c->stream);
+  for (void *p : r->allocs) hipFree(p);
+  delete r;
+}
+
+extern "C" pn_rate *pn_rate_create(pn_ctx *c, int rate_hz) {
+  if (!c) { pn_set_error("NULL argument"); return NULL; }
+  const int L = pn_rate_factor(rate_hz);
+  if (!L) { pn_set_error("rate %d Hz: a converter takes 8000, 16000 or 24000", rate_hz); return NULL; }
+  DeviceGuard _dg(c->device);
+  if (!_dg.ok) { pn_set_error("hipSetDevice(%d) failed", c->device); return NULL; }
+  pn_rate *r = new pn_rate();
+  r->c = c; r->rate = rate_hz; r->L = L; r->n = PN_FRAME / L; r->td = pn_rate_down_tail(L); r->bytes = 0;
+  const size_t B = (size_t)c->B, nt = (size_t)r->td + 1;
+  float h[2][PN_RATE_MAX_TAPS];
+  auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
+  if (pn_rate_design(L, 0, h[0], PN_RATE_MAX_TAPS) < 0 || pn_rate_design(L, 1, h[1], PN_RATE_MAX_TAPS) < 0) goto fail;
+  if (alloc((void **)&r->taps_up, nt * 4, false) || alloc((void **)&r->taps_down, nt * 4, false) ||
+      alloc((void **)&r->tail_up, B * PN_RATE_UP_TAIL * 4, true) || alloc((void **)&r->tail_down, B * r->td * 4, true) ||
+      alloc((void **)&r->x48, B * PN_FRAME * 4, true) || alloc((void **)&r->y48, B * PN_FRAME * 4, true) ||
+      alloc(&r->io_in, B * r->n * 4, false) || alloc(&r->io_out, B * r->n * 4, false) || alloc((void **)&r->io_gr, B * 68 * 4, false)) goto fail;
+  // (synchronous copies: h is on this stack)
+  if (hipMemcpyAsync(r->taps_up, h[0], nt * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipMemcpyAsync(r->taps_down, h[1], nt * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipGetLastError(); pn_set_error("rate converter init failed"); goto fail; }
+  return r;
+fail:
+  pn_rate_destroy(r);
+  return NULL;
+}
+
+extern "C" int pn_rate_reset(pn_rate *r) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  PN_ON_DEVICE(r->c);
+  PN_HIP_CHECK(hipMemsetAsync(r->tail_up, 0, (size_t)r->c->B * PN_RATE_UP_TAIL * 4, r->c->stream));
+  PN_HIP_CHECK(hipMemsetAsync(r->tail_down, 0, (size_t)r->c->B * r->td * 4, r->c->stream));
+  return 0;
+}
+
+// the context's rules for an id list: in range, and distinct where the streams advance or are written
+static int rate_ids_check(const pn_rate *r, const int32_t *ids, int n, bool distinct) {
+  const int B = r->c->B;
+  if (n < 0 || (n > 0 && !ids)) { pn_set_error("bad argument"); return -1; }
+  if (distinct && n > B) { pn_set_error("%d streams listed for a context of %d", n, B); return -1; }
+  std::vector<uint8_t> seen(distinct ? (size_t)B : 0, 0);
+  for (int i = 0; i < n; i++) {
+    if (ids[i] < 0 || ids[i] >= B) { pn_set_error("stream id %d out of range [0, %d)", ids[i], B); return -1; }
+    if (distinct && seen[ids[i]]++) { pn_set_error("stream id %d listed twice", ids[i]); return -1; }
+  }
+  return 0;
+}
+
+extern "C" int pn_rate_reset_streams(pn_rate *r, const int32_t *ids, int n) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (rate_ids_check(r, ids, n, false)) return -1;
+  if (n == 0) return 0;
+  PN_ON_DEVICE(r->c);
+  const int *d = stage_ids(r->c, ids, n);
+  if (!d) return -1;
+  pn_launch_zero_rows(r->c->stream, r->tail_up, PN_RATE_UP_TAIL, PN_RATE_UP_TAIL, 1, 0, d, n);
+  pn_launch_zero_rows(r->c->stream, r->tail_down, r->td, r->td, 1, 0, d, n);
+  PN_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// ---- the two kernels -----------------------------------------------------------------------------------------------------------
+// The rows of one call: every stream (ids == NULL), or the listed ones staged ONCE through the context's id ring; both kernels of a
+// whole frame read the same staged list.
+struct RateRows { const int *d_ids; int n; };
+static int rate_rows(pn_rate *r, const int32_t *ids, int n, RateRows *rows) {
+  rows->d_ids = NULL; rows->n = r->c->B;
+  if (!ids) return 0;
+  if (rate_ids_check(r, ids, n, true)) return -1;
+  rows->n = n;
+  if (n > 0 && !(rows->d_ids = stage_ids(r->c, ids, n))) return -1;
+  return 0;
+}
+static int rate_aligned(const void *a, const void *b) {
+  if (!a || !b) { pn_set_error("NULL argument"); return -1; }
+  if (((uintptr_t)a | (uintptr_t)b) & 15) { pn_set_error("rate converter rows must be 16-byte aligned"); return -1; }
+  return 0;
+}
+static int rate_up(pn_rate *r, const void *d_in, int is_i16, float *d_out48, const RateRows &rows) {
+  if (pn_launch_rate_up(r->c->stream, r->L, is_i16, rows.n, rows.d_ids, d_in, d_out48, r->tail_up, r->taps_up)) return -1;
+  PN_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+static int rate_down(pn_rate *r, const float *d_in48, void *d_out, int is_i16, const RateRows &rows) {
+  if (pn_launch_rate_down(r->c->stream, r->L, is_i16, rows.n, rows.d_ids, d_in48, d_out, r->c->saturate ? 1 : 0, r->tail_down, r->taps_down)) return -1;
+  PN_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+static int rate_up_call(pn_rate *r, const void *d_in, int is_i16, float *d_out48, const int32_t *ids, int n) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (rate_aligned(d_in, d_out48)) return -1;
+  PN_ON_DEVICE(r->c);
+  RateRows rows;
+  if (rate_rows(r, ids, n, &rows)) return -1;
+  return rate_up(r, d_in, is_i16, d_out48, rows);
+}
+static int rate_down_call(pn_rate *r, const float *d_in48, void *d_out, int is_i16, const int32_t *ids, int n) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (rate_aligned(d_in48, d_out)) return -1;
+  PN_ON_DEVICE(r->c);
+  RateRows rows;
+  if (rate_rows(r, ids, n, &rows)) return -1;
+  return rate_down(r, d_in48, d_out, is_i16, rows);
+}
+extern "C" int pn_rate_up_f32(pn_rate *r, const float *d_in, float *d_out48, const int32_t *ids, int n_ids) { return rate_up_call(r, d_in, 0, d_out48, ids, n_ids); }
+extern "C" int pn_rate_up_i16(pn_rate *r, const int16_t *d_in, float *d_out48, const int32_t *ids, int n_ids) { return rate_up_call(r, d_in, 1, d_out48, ids, n_ids); }
+extern "C" int pn_rate_down_f32(pn_rate *r, const float *d_in48, float *d_out, const int32_t *ids, int n_ids) { return rate_down_call(r, d_in48, d_out, 0, ids, n_ids); }
+extern "C" int pn_rate_down_i16(pn_rate *r, const float *d_in48, int16_t *d_out, const int32_t *ids, int n_ids) { return rate_down_call(r, d_in48, d_out, 1, ids, n_ids); }
+
+// ---- one whole frame -----------------------------------------------------------------------------------------------------------
+// up into x48, the engine's float frame from x48 into y48 (all streams, or the listed ones through the context's own active
+// set), down from y48.  A frame the engine refuses returns -1 with its error kept; the up kernel has then advanced its tails
+// and the down kernel has not, which is why the header asks for a reset of both objects before reuse.
+static int rate_process(pn_rate *r, const void *d_in, void *d_out, float *d_gr, int is_i16, bool active, const int32_t *ids, int n) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (rate_aligned(d_in, d_out)) return -1;
+  pn_ctx *c = r->c;
+  PN_ON_DEVICE(c);
+  RateRows rows = {NULL, c->B};
+  if (active) {                                      // (an empty list is legal, as for pn_process_*_active: nobody advances)
+    if (rate_ids_check(r, ids, n, true)) return -1;
+    rows.n = n;
+    if (n > 0 && !(rows.d_ids = stage_ids(c, ids, n))) return -1;
+  }
+  if (rate_up(r, d_in, is_i16, r->x48, rows)) return -1;
+  if (active ? pn_process_f32_active(c, r->x48, r->y48, d_gr, ids, n) : pn_process_f32(c, r->x48, r->y48, d_gr)) return -1;
+  return rate_down(r, r->y48, d_out, is_i16, rows);
+}
+extern "C" int pn_rate_process_f32(pn_rate *r, const float *d_in, float *d_out, float *d_gr) { return rate_process(r, d_in, d_out, d_gr, 0, false, NULL, 0); }
+extern "C" int pn_rate_process_i16(pn_rate *r, const int16_t *d_in, int16_t *d_out, float *d_gr) { return rate_process(r, d_in, d_out, d_gr, 1, false, NULL, 0); }
+extern "C" int pn_rate_process_f32_active(pn_rate *r, const float *d_in, float *d_out, float *d_gr, const int32_t *ids, int n) { return rate_process(r, d_in, d_out, d_gr, 0, true, ids, n); }
+extern "C" int pn_rate_process_i16_active(pn_rate *r, const int16_t *d_in, int16_t *d_out, float *d_gr, const int32_t *ids, int n) { return rate_process(r, d_in, d_out, d_gr, 1, true, ids, n); }
+
+static int rate_process_host(pn_rate *r, const void *h_in, void *h_out, float *h_gr, int is_i16) {
+  if (!r || !h_in || !h_out) { pn_set_error("NULL argument"); return -1; }
+  pn_ctx *c = r->c;
+  PN_ON_DEVICE(c);
+  if (pn_host_wait(c)) return -1;                    // frames in flight on the context's pipelined path complete first
+  const size_t nbytes = (size_t)c->B * r->n * (is_i16 ? 2 : 4);
+  PN_HIP_CHECK(hipMemcpyAsync(r->io_in, h_in, nbytes, hipMemcpyHostToDevice, c->stream));
+  if (rate_process(r, r->io_in, r->io_out, h_gr ? r->io_gr : NULL, is_i16, false, NULL, 0)) return -1;
+  PN_HIP_CHECK(hipMemcpyAsync(h_out, r->io_out, nbytes, hipMemcpyDeviceToHost, c->stream));
+  if (h_gr) PN_HIP_CHECK(hipMemcpyAsync(h_gr, r->io_gr, (size_t)c->B * 68 * 4, hipMemcpyDeviceToHost, c->stream));
+  PN_HIP_CHECK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+extern "C" int pn_rate_process_host_f32(pn_rate *r, const float *h_in, float *h_out, float *h_gr) { return rate_process_host(r, h_in, h_out, h_gr, 0); }
+extern "C" int pn_rate_process_host_i16(pn_rate *r, const int16_t *h_in, int16_t *h_out, float *h_gr) { return rate_process_host(r, h_in, h_out, h_gr, 1); }
+
+// ---- state records -----------------------------------------------------------------------------------------------------------
+// Host forms only: synchronous, through a device buffer of the records' size that is freed before returning (like the host
+// forms of the context's stream-state records).
+extern "C" int pn_rate_export_streams_host(pn_rate *r, const int32_t *ids, int n, void *h_records) {
+  if (!r || n < 0 || (n > 0 && (!ids || !h_records))) { pn_set_error("bad argument"); return -1; }
+  if (n == 0) return 0;
+  if (rate_ids_check(r, ids, n, false)) return -1;
+  pn_ctx *c = r->c;
+  PN_ON_DEVICE(c);
+  if (pn_host_wait(c)) return -1;
+  const size_t bytes = (size_t)n * 4 * pn_rate_record_words(r->L);
+  const int *d_ids = stage_ids(c, ids, n);
+  if (!d_ids) return -1;
+  void *d = NULL;
+  PN_HIP_CHECK(hipMalloc(&d, bytes));
+  int rc = 0;
+  pn_launch_rate_records(c->stream, r->L, r->rate, d_ids, n, r->tail_up, r->tail_down, d, 0);
+  if (hipGetLastError() != hipSuccess) { pn_set_error("record gather launch failed"); rc = -1; }
+  if (!rc && hipMemcpyAsync(h_records, d, bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) { pn_set_error("record copy failed"); rc = -1; }
+  if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) { pn_set_error("export failed"); rc = -1; }
+  hipFree(d);
+  return rc;
+}
+extern "C" int pn_rate_import_streams_host(pn_rate *r, const int32_t *ids, int n, const void *h_records) {
+  if (!r || n < 0 || (n > 0 && (!ids || !h_records))) { pn_set_error("bad argument"); return -1; }
+  if (n == 0) return 0;
+  if (rate_ids_check(r, ids, n, true)) return -1;
+  const size_t rec_bytes = 4 * pn_rate_record_words(r->L), bytes = (size_t)n * rec_bytes;
+  for (int i = 0; i < n; i++)                          // all or nothing: every header before anything is launched
+    if (pn_rate_record_check(static_cast<const char *>(h_records) + (size_t)i * rec_bytes, rec_bytes, r->rate)) {
+      std::string why = pn_last_error();
+      pn_set_error("record %d refused: %s", i, why.c_str());
+      return -1;
+    }
+  pn_ctx *c = r->c;
+  PN_ON_DEVICE(c);
+  if (pn_host_wait(c)) return -1;
+  const int *d_ids = stage_ids(c, ids, n);
+  if (!d_ids) return -1;
+  void *d = NULL;
+  PN_HIP_CHECK(hipMalloc(&d, bytes));
+  int rc = hipMemcpyAsync(d, h_records, bytes, hipMemcpyHostToDevice, c->stream) == hipSuccess ? 0 : -1;
+  if (rc) pn_set_error("record copy failed");
+  if (!rc) {
+    pn_launch_rate_records(c->stream, r->L, r->rate, d_ids, n, r->tail_up, r->tail_down, d, 1);
+    if (hipGetLastError() != hipSuccess) { pn_set_error("record scatter launch failed"); rc = -1; }
+  }
+  if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) { pn_set_error("import failed"); rc = -1; }
+  hipFree(d);
+  return rc;
+}

@@ -1,0 +1,180 @@
+// The two kernels of the batched rate converter for gfx950 (include/percepnet_hip.h "batched rate converter"; host side
+// pn_rate.cpp; arithmetic and tap design pn_rate_design.h): L = 6 | 3 | 2 takes 8 | 16 | 24 kHz rows of n = 480 / L samples up to
+// the engine's 48 kHz rows in front of a frame and back down behind it.  T = 16 taps per phase, D = T * L.
+//
+// One wavefront (64 lanes) per stream, four streams per block, like the output stage.  A wave stages its row behind the stream's
+// tail in LDS — up: 32 + n low-rate samples, down: 2D + 480 samples at 48 kHz — with 16-byte loads, the block stages the 2D + 1
+// taps, and then lane l owns the low-rate sample indices l, l + 64, ...:
+//   up    index q: the window x[q - 31 .. q] goes to registers once; phase 0 stores x[q - 16] (a copy: the input's bits), phases
+//         p = 1..L-1 each run sum_i h[L(15 - i) + p] * x[q - 31 + i], i ascending = oldest sample first.  The tap address is the
+//         same in every lane (an LDS broadcast), the window addresses are consecutive.
+//   down  index m: sum_j g[D - 1 - j] * o[Lm - 2D + 1 + j], j = 0..2D-2 ascending = oldest first (g[+-D] = 0 is not visited).
+// acc starts at 0.0f and every step is acc = acc + c * x with the product and the sum rounded separately (-ffp-contract=off, like
+// the DSP kernels), in one order that depends on nothing but the stream's own samples: no atomics, no cross-lane sums, so a
+// stream's output is the same in every batch size, slot and block, and numpy float32 reproduces it (tests/rate_model.py).
+// The results pass through LDS once more so that the rows leave with 16-byte coalesced stores (every row here is a multiple of
+// 16 bytes), and the wave then writes the stream's new tail in place — the last 32 staged low-rate samples / the last 2D staged
+// 48 kHz samples — after all of its reads of the old one.
+// ids (optional): the rows to run, one per wave; the grid covers only those.  An unlisted stream is neither read nor written,
+// which is the converter's whole active-set story: nothing to save, nothing to restore.
+// Memory-bound by design.  Per stream and frame — up: n samples + 128 B of tail in, 1920 B out, 32 n (L - 1) multiply-adds
+// (12 800 | 10 240 | 7 680); down: 1920 B + 8 D bytes of tail in, n samples out, n (2D - 1) multiply-adds (15 280 | 15 200 | 15 120).
+#include "pn_launch.h"
+#include "pn_pcm.h"
+#include "pn_rate_design.h"
+
+#define RT_LANES 64
+#define RT_WPB 4                     // wavefronts (= streams) per block
+#define RT_T PN_RATE_TAPS
+#define RT_UT PN_RATE_UP_TAIL        // 32
+static_assert(RT_UT == 2 * RT_T && RT_UT % 4 == 0 && PN_FRAME % (8 * PN_RATE_MAX_L) == 0, "tails and rows are whole 16-byte groups");
+
+template <int L, bool I16>
+__global__ __launch_bounds__(RT_LANES * RT_WPB) void pn_rate_up_kernel(
+    int n_rows, const int *__restrict__ ids,   // rows to run; ids == NULL: row w is stream w
+    const void *__restrict__ in,               // [n_streams][N] float or int16
+    float *__restrict__ out48,                 // [n_streams][480]
+    float *__restrict__ tail,                  // [n_streams][32], read then rewritten
+    const float *__restrict__ taps) {          // h[-D..D]
+  constexpr int N = PN_FRAME / L, D = RT_T * L, NT = 2 * D + 1;
+  static_assert(N % 8 == 0 && N / 4 <= RT_LANES, "one 16-byte load per lane covers a row");
+  __shared__ float s_taps[NT];
+  __shared__ __align__(16) float s_buf[RT_WPB][RT_UT + N];
+  __shared__ __align__(16) float s_out[RT_WPB][PN_FRAME];
+  const int lane = threadIdx.x & (RT_LANES - 1), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (int i = threadIdx.x; i < NT; i += RT_LANES * RT_WPB) s_taps[i] = taps[i];
+  const int w = blockIdx.x * RT_WPB + wave;
+  const bool live = w < n_rows;                // (no early return: the block meets at its barriers)
+  const size_t s = live ? (size_t)(ids ? ids[w] : w) : 0;
+  float *buf = s_buf[wave], *o = s_out[wave];
+  if (live) {
+    if (lane < RT_UT / 4) reinterpret_cast<float4 *>(buf)[lane] = reinterpret_cast<const float4 *>(tail + s * RT_UT)[lane];
+    if constexpr (I16) {
+      if (lane < N / 8) {
+        union { uint4 q; int16_t h[8]; } u;
+        u.q = reinterpret_cast<const uint4 *>(static_cast<const int16_t *>(in) + s * N)[lane];
+        float4 *d = reinterpret_cast<float4 *>(buf + RT_UT) + 2 * lane;
+        d[0] = make_float4((float)u.h[0] / 32768.f, (float)u.h[1] / 32768.f, (float)u.h[2] / 32768.f, (float)u.h[3] / 32768.f);
+        d[1] = make_float4((float)u.h[4] / 32768.f, (float)u.h[5] / 32768.f, (float)u.h[6] / 32768.f, (float)u.h[7] / 32768.f);
+      }
+    } else {
+      if (lane < N / 4) reinterpret_cast<float4 *>(buf + RT_UT)[lane] = reinterpret_cast<const float4 *>(static_cast<const float *>(in) + s * N)[lane];
+    }
+  }
+  __syncthreads();
+  if (live) {
+    for (int q = lane; q < N; q += RT_LANES) {
+      float x[RT_UT];                          // x[i] = sample q - 31 + i
+#pragma unroll
+      for (int i = 0; i < RT_UT; i++) x[i] = buf[q + 1 + i];
+      o[L * q] = x[RT_T - 1];                  // phase 0: sample q - T
+#pragma unroll 1                        // (unrolled, L = 6 keeps all 160 taps in registers: 256 VGPRs)
+      for (int p = 1; p < L; p++) {
+        float acc = 0.0f;
+#pragma unroll
+        for (int i = 0; i < RT_UT; i++) acc = acc + s_taps[D + L * (RT_T - 1 - i) + p] * x[i];
+        o[L * q + p] = acc;
+      }
+    }
+  }
+  __syncthreads();
+  if (live) {
+    float4 *dst = reinterpret_cast<float4 *>(out48 + s * PN_FRAME);
+    for (int i = lane; i < PN_FRAME / 4; i += RT_LANES) dst[i] = reinterpret_cast<const float4 *>(o)[i];
+    if (lane < RT_UT / 4) reinterpret_cast<float4 *>(tail + s * RT_UT)[lane] = reinterpret_cast<const float4 *>(buf + N)[lane];
+  }
+}
+
+template <int L, bool I16>
+__global__ __launch_bounds__(RT_LANES * RT_WPB) void pn_rate_down_kernel(
+    int n_rows, const int *__restrict__ ids,
+    const float *__restrict__ in48,            // [n_streams][480]
+    void *__restrict__ out,                    // [n_streams][N] float or int16
+    int saturate,                              // int16 only: the saturating cast instead of the wrap
+    float *__restrict__ tail,                  // [n_streams][2D], read then rewritten
+    const float *__restrict__ taps) {          // g[-D..D]
+  constexpr int N = PN_FRAME / L, D = RT_T * L, TD = 2 * D, NT = 2 * D + 1;
+  static_assert(TD % 4 == 0 && TD / 4 <= RT_LANES && N % 8 == 0 && N / 4 <= RT_LANES, "one 16-byte access per lane covers a tail and an output row");
+  __shared__ float s_taps[NT];
+  __shared__ __align__(16) float s_buf[RT_WPB][TD + PN_FRAME];
+  __shared__ __align__(16) float s_out[RT_WPB][N];
+  const int lane = threadIdx.x & (RT_LANES - 1), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (int i = threadIdx.x; i < NT; i += RT_LANES * RT_WPB) s_taps[i] = taps[i];
+  const int w = blockIdx.x * RT_WPB + wave;
+  const bool live = w < n_rows;
+  const size_t s = live ? (size_t)(ids ? ids[w] : w) : 0;
+  float *buf = s_buf[wave], *z = s_out[wave];
+  if (live) {
+    if (lane < TD / 4) reinterpret_cast<float4 *>(buf)[lane] = reinterpret_cast<const float4 *>(tail + s * TD)[lane];
+    const float4 *src = reinterpret_cast<const float4 *>(in48 + s * PN_FRAME);
+    for (int i = lane; i < PN_FRAME / 4; i += RT_LANES) reinterpret_cast<float4 *>(buf + TD)[i] = src[i];
+  }
+  __syncthreads();
+  if (live) {
+    for (int m = lane; m < N; m += RT_LANES) {
+      const float *x = buf + L * m + 1;        // x[j] = 48 kHz sample Lm - 2D + 1 + j
+      float acc = 0.0f;
+#pragma unroll 8
+      for (int j = 0; j < TD - 1; j++) acc = acc + s_taps[TD - 1 - j] * x[j];
+      z[m] = acc;
+    }
+  }
+  __syncthreads();
+  if (live) {
+    if constexpr (I16) {
+      if (lane < N / 8) {
+        const float4 a = reinterpret_cast<const float4 *>(z)[2 * lane], b = reinterpret_cast<const float4 *>(z)[2 * lane + 1];
+        const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+        union { int16_t h[8]; uint4 q; } p;
+#pragma unroll
+        for (int i = 0; i < 8; i++) { const float t = v[i] * 32768; p.h[i] = saturate ? pn_f2s_sat(t) : pn_f2s(t); }
+        reinterpret_cast<uint4 *>(static_cast<int16_t *>(out) + s * N)[lane] = p.q;
+      }
+    } else {
+      if (lane < N / 4) reinterpret_cast<float4 *>(static_cast<float *>(out) + s * N)[lane] = reinterpret_cast<const float4 *>(z)[lane];
+    }
+    if (lane < TD / 4) reinterpret_cast<float4 *>(tail + s * TD)[lane] = reinterpret_cast<const float4 *>(buf + PN_FRAME)[lane];
+  }
+}
+
+// State records (include/percepnet_hip.h): record i <-> the two tails of stream ids[i]; one block per record.  gather writes the
+// header too; scatter trusts it (the host import has checked every header before anything is launched).
+__global__ __launch_bounds__(64) void pn_rate_records_kernel(const int *__restrict__ ids, float *__restrict__ tail_up, float *__restrict__ tail_down,
+                                                             int td, uint32_t *__restrict__ rec, int rec_words, uint4 hdr, int scatter) {
+  const size_t s = (size_t)ids[blockIdx.x];
+  uint32_t *r = rec + (size_t)blockIdx.x * rec_words;
+  if (!scatter && threadIdx.x == 0) *reinterpret_cast<uint4 *>(r) = hdr;
+  float *body = reinterpret_cast<float *>(r + PN_RATE_STATE_HEADER_BYTES / 4);
+  for (int i = threadIdx.x; i < RT_UT + td; i += blockDim.x) {
+    float *p = i < RT_UT ? tail_up + s * RT_UT + i : tail_down + s * td + (i - RT_UT);
+    if (scatter) *p = body[i]; else body[i] = *p;
+  }
+}
+
+#define RT_DISPATCH(kernel, ...)                                                                                     \
+  do {                                                                                                               \
+    const dim3 grid((n_rows + RT_WPB - 1) / RT_WPB), block(RT_LANES * RT_WPB);                                         \
+    if (L == 6) { if (is_i16) hipLaunchKernelGGL(HIP_KERNEL_NAME(kernel<6, true>), grid, block, 0, st, __VA_ARGS__); else hipLaunchKernelGGL(HIP_KERNEL_NAME(kernel<6, false>), grid, block, 0, st, __VA_ARGS__); } \
+    else if (L == 3) { if (is_i16) hipLaunchKernelGGL(HIP_KERNEL_NAME(kernel<3, true>), grid, block, 0, st, __VA_ARGS__); else hipLaunchKernelGGL(HIP_KERNEL_NAME(kernel<3, false>), grid, block, 0, st, __VA_ARGS__); } \
+    else { if (is_i16) hipLaunchKernelGGL(HIP_KERNEL_NAME(kernel<2, true>), grid, block, 0, st, __VA_ARGS__); else hipLaunchKernelGGL(HIP_KERNEL_NAME(kernel<2, false>), grid, block, 0, st, __VA_ARGS__); } \
+  } while (0)
+
+int pn_launch_rate_up(hipStream_t st, int L, int is_i16, int n_rows, const int *d_ids, const void *in, float *out48, float *tail, const float *taps) {
+  if (L != 2 && L != 3 && L != 6) { pn_set_error("pn_launch_rate_up: no kernel for L = %d", L); return -1; }
+  if (n_rows <= 0) return 0;
+  RT_DISPATCH(pn_rate_up_kernel, n_rows, d_ids, in, out48, tail, taps);
+  return 0;
+}
+int pn_launch_rate_down(hipStream_t st, int L, int is_i16, int n_rows, const int *d_ids, const float *in48, void *out, int saturate, float *tail, const float *taps) {
+  if (L != 2 && L != 3 && L != 6) { pn_set_error("pn_launch_rate_down: no kernel for L = %d", L); return -1; }
+  if (n_rows <= 0) return 0;
+  RT_DISPATCH(pn_rate_down_kernel, n_rows, d_ids, in48, out, saturate, tail, taps);
+  return 0;
+}
+void pn_launch_rate_records(hipStream_t st, int L, int rate_hz, const int *d_ids, int n, float *tail_up, float *tail_down, void *rec, int scatter) {
+  if (n <= 0) return;
+  uint32_t h[4];
+  pn_rate_record_header(h, rate_hz);
+  hipLaunchKernelGGL(pn_rate_records_kernel, dim3(n), dim3(64), 0, st, d_ids, tail_up, tail_down, pn_rate_down_tail(L), (uint32_t *)rec,
+                     (int)pn_rate_record_words(L), make_uint4(h[0], h[1], h[2], h[3]), scatter);
+}

@@ -1,0 +1,79 @@
+// The rate converter's arithmetic that needs no GPU, described once — HIP-free (builds with -DPN_NO_HIP), checked on the CPU by
+// tests/c/rate_sanitize.cpp under the sanitizers and by tests/test_rate_host.py through the C-ABI (include/percepnet_hip.h says
+// what the numbers mean): the three rates and their sizes, the prototype filter, and the per-stream state record.
+// The filter is computed like the tables of pn_tables.cpp: in double, each value narrowed to float once.
+//   h[k] = sinc(k / L) * I0(beta * sqrt(1 - (k / D)^2)) / I0(beta),  k = -D..D,  D = T * L,  beta = 8
+// for k >= 0 and mirrored, so the table is symmetric bit for bit; h[0] = 1 and h[jL] = 0 are set, not computed (sin(pi j) is not
+// 0 in double), which is what makes phase 0 of the up-conversion a copy.  The down-converter's taps are (float)(h_double[k] / L).
+#pragma once
+#include "pn_common.h"
+#include "../../include/percepnet_hip.h"
+#include <math.h>
+#include <string.h>
+
+#define PN_RATE_BETA 8.0
+#define PN_RATE_UP_TAIL (2 * PN_RATE_TAPS)      // low-rate samples an up-converted stream carries: x[q - 2T + 1 .. q] is 32 wide
+#define PN_RATE_MAX_L 6
+#define PN_RATE_MAX_TAPS (2 * PN_RATE_TAPS * PN_RATE_MAX_L + 1)
+
+// L = 48000 / rate_hz for the three rates a converter takes, 0 for every other
+static inline int pn_rate_factor(int rate_hz) { return rate_hz == 8000 ? 6 : rate_hz == 16000 ? 3 : rate_hz == 24000 ? 2 : 0; }
+static inline int pn_rate_down_tail(int L) { return 2 * PN_RATE_TAPS * L; }                       // 48 kHz samples a down-converted stream carries: 2D
+static inline size_t pn_rate_record_words(int L) { return PN_RATE_STATE_HEADER_BYTES / 4 + PN_RATE_UP_TAIL + (size_t)pn_rate_down_tail(L); }
+
+// modified Bessel function of the first kind, order 0: sum_k ((x / 2)^k / k!)^2, terms are positive and fall monotonically
+// once k > x / 2, so stopping below 1e-20 of the sum leaves a relative error far under double's
+static inline double pn_rate_i0(double x) {
+  double sum = 1.0, term = 1.0;
+  const double q = 0.25 * x * x;
+  for (int k = 1; k < 500; k++) {
+    term *= q / ((double)k * (double)k);
+    sum += term;
+    if (term < 1e-20 * sum) break;
+  }
+  return sum;
+}
+
+// taps[k + D], k = -D..D: h (down == 0) or g = h / L (down != 0) for L in {2, 3, 6}.  Returns 2D + 1, or -1 (another L, cap too small).
+static inline int pn_rate_design(int L, int down, float *taps, int cap) {
+  if (L != 2 && L != 3 && L != 6) { pn_set_error("rate converter: no design for L = %d", L); return -1; }
+  const int D = PN_RATE_TAPS * L, n = 2 * D + 1;
+  if (!taps || cap < n) { pn_set_error("rate converter: %d taps need room for %d, got %d", n, n, taps ? cap : 0); return -1; }
+  const double pi = 3.14159265358979323846264338327, i0b = pn_rate_i0(PN_RATE_BETA);
+  for (int k = 0; k <= D; k++) {
+    double h;
+    if (k == 0) h = 1.0;
+    else if (k % L == 0) h = 0.0;
+    else {
+      const double t = (double)k / L, r = (double)k / D;
+      h = sin(pi * t) / (pi * t) * pn_rate_i0(PN_RATE_BETA * sqrt(1.0 - r * r)) / i0b;
+    }
+    const float v = down ? (float)(h / L) : (float)h;
+    taps[D + k] = v; taps[D - k] = v;
+  }
+  return n;
+}
+
+static inline void pn_rate_record_header(uint32_t hdr[4], int rate_hz) {
+  hdr[0] = PN_RATE_STATE_MAGIC; hdr[1] = PN_RATE_STATE_VERSION;
+  hdr[2] = (uint32_t)(4 * pn_rate_record_words(pn_rate_factor(rate_hz))); hdr[3] = (uint32_t)rate_hz;
+}
+static inline uint32_t pn_rate_le32(const unsigned char *p) { return p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+// is `bytes` bytes at `record` one state record of a converter of rate_hz?  Reads the 16 header bytes only, and only when
+// they are there.  Same order of verdicts as the stream-state check (pn_context.cpp ss_check_host), then the rate.
+static inline int pn_rate_record_check(const void *record, size_t bytes, int rate_hz) {
+  const int L = pn_rate_factor(rate_hz);
+  if (!record) { pn_set_error("NULL argument"); return PN_SS_BAD_ARG; }
+  if (!L) { pn_set_error("rate %d Hz: a converter takes 8000, 16000 or 24000", rate_hz); return PN_SS_BAD_RATE; }
+  const size_t want = 4 * pn_rate_record_words(L);
+  const unsigned char *r = static_cast<const unsigned char *>(record);
+  if (bytes < PN_RATE_STATE_HEADER_BYTES) { pn_set_error("rate-state record of %zu bytes: a record at %d Hz has %zu", bytes, rate_hz, want); return PN_SS_BAD_SIZE; }
+  if (pn_rate_le32(r) != PN_RATE_STATE_MAGIC) { pn_set_error("not a rate-state record (magic 0x%08x)", pn_rate_le32(r)); return PN_SS_BAD_MAGIC; }
+  if (pn_rate_le32(r + 4) != PN_RATE_STATE_VERSION) { pn_set_error("rate-state record version %u, this library reads %d", pn_rate_le32(r + 4), PN_RATE_STATE_VERSION); return PN_SS_BAD_VERSION; }
+  if ((int32_t)pn_rate_le32(r + 12) != rate_hz) { pn_set_error("rate-state record written at %d Hz, this converter runs at %d", (int32_t)pn_rate_le32(r + 12), rate_hz); return PN_SS_BAD_RATE; }
+  if (pn_rate_le32(r + 8) != want || bytes != want) {
+    pn_set_error("rate-state record of %zu bytes (header: %u), a record at %d Hz has %zu", bytes, pn_rate_le32(r + 8), rate_hz, want);
+    return PN_SS_BAD_SIZE;
+  }
+  return PN_SS_OK;
+}
