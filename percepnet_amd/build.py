@@ -18,7 +18,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libpercepnet_hip.so")
 RUN = os.path.join(LIBDIR, "percepnet_run")
 EXPORT_MAP = os.path.join(CSRC, "libpercepnet_hip.map")    # ld version script: the export list (everything else is local)
-SOURCES = ["pn_tables.cpp", "pn_model.cpp", "pn_pack.cpp", "pn_dsp_fe.hip", "pn_dsp_fe_g2.hip", "pn_dsp_fe_split_s.hip", "pn_dsp_fe_split_p.hip", "pn_dsp.hip", "pn_outstage.hip", "pn_nn.hip", "pn_nn_small.hip", "pn_nn_x3.hip", "pn_nn_d.hip", "pn_nn_n48.hip", "pn_targets.hip", "pn_state.hip", "pn_active.hip", "pn_stream_state.hip", "pn_context.cpp", "pn_network.cpp",
+SOURCES = ["pn_tables.cpp", "pn_model.cpp", "pn_pack.cpp", "pn_dsp_fe.hip", "pn_dsp_fe_g2.hip", "pn_dsp_fe_split_s.hip", "pn_dsp_fe_split_p.hip", "pn_dsp.hip", "pn_outstage.hip", "pn_nn.hip", "pn_nn_small.hip", "pn_nn_x3.hip", "pn_nn_d.hip", "pn_nn_n48.hip", "pn_targets.hip", "pn_state.hip", "pn_active.hip", "pn_stream_state.hip", "pn_context.cpp", "pn_selftest.cpp", "pn_host_pipe.cpp", "pn_stream_state.cpp", "pn_network.cpp",
            "pn_featgen.cpp", "pn_rate.hip", "pn_rate.cpp", "rnnoise_compat.cpp"]
 # percepnet_run.cpp / percepnet_featgen.cpp (the CLIs) are linked separately against the library
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden",
@@ -186,7 +186,7 @@ def toolchain_info(hipcc):
 
 
 def _obj(dirname, src):
-    """Object file of a source: its stem, or stem_host for the .cpp of a (kernel file, host file) pair that share one (pn_rate)."""
+    """Object file of a source: its stem, or stem_host for the .cpp of a (kernel file, host file) pair that share one (pn_rate, pn_stream_state)."""
     stem, ext = src.rsplit(".", 1)
     return os.path.join(dirname, stem + ("_host" if ext == "cpp" and stem + ".hip" in SOURCES else "") + ".o")
 

@@ -95,7 +95,7 @@ void pn_launch_inactive_fixup(hipStream_t st, const PnActiveArgs &a, int n) {
   if (n > 0) hipLaunchKernelGGL(pn_inactive_fixup_kernel, dim3(n), dim3(256), 0, st, a);
 }
 
-// ---- a kernel that only passes time (pipe_init's queue probe, pn_context.cpp) --------------------------------------
+// ---- a kernel that only passes time (pipe_init's queue probe, pn_host_pipe.cpp) --------------------------------------
 // One wave that sleeps until `ticks` of the 100 MHz wall clock have gone by.
 __global__ void pn_spin_kernel(long long ticks) {
   const long long t0 = wall_clock64();

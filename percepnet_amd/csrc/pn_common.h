@@ -97,7 +97,9 @@ void pn_pack_weights_n16(const float *W, int K, int ncols, float *Wq);
 // hand in torch data_ptr()s from a thread whose current device torch manages).
 struct DeviceGuard {
   int prev = -1; bool ok = true;
-  explicit DeviceGuard(int dev) {
+  DeviceGuard() {}                                      // entered later (open_device)
+  explicit DeviceGuard(int dev) { enter(dev); }
+  void enter(int dev) {
     if (hipGetDevice(&prev) != hipSuccess) prev = -1;
     if (prev != dev && hipSetDevice(dev) != hipSuccess) ok = false;
     if (prev == dev) prev = -1;                       // nothing to restore

@@ -1,10 +1,14 @@
-// Private to the host side of libpercepnet_hip: a batched context and the few helpers its two files share — pn_context.cpp
-// (lifecycle, frame path, active set, host pipeline, state I/O, self-tests) and pn_network.cpp (shared weights, the ten-layer
-// launch loop, row-range chains).  The training-feature generator (pn_featgen.cpp) shares the allocator and the table upload.
+// Private to the host side of libpercepnet_hip: a batched context and the few helpers its files share — pn_context.cpp (lifecycle,
+// settings, the frame's launch sequence, active set), pn_selftest.cpp (the create-time self-tests), pn_host_pipe.cpp (pipelined
+// host-buffer path, host-thread helpers), pn_stream_state.cpp (RNN-state and stream-state I/O) and pn_network.cpp (shared weights,
+// the ten-layer launch loop, row-range chains).  The training-feature generator (pn_featgen.cpp) shares the allocator, the table
+// upload and the device preamble; the rate converter (pn_rate.cpp) the id ring and the host form of a record transfer.
 #pragma once
 #include <array>
+#include <functional>
 #include <tuple>
 #include <vector>
+#include "pn_host_rules.h"   // the id-list rule, the record-header rule
 #include "pn_launch.h"       // pn_common.h, pn_network.h (plan, state table, DSP side, kernel families), the public header
 
 struct SharedWeights;             // pn_network.cpp
@@ -82,13 +86,38 @@ struct pn_ctx {
 };
 
 // ---- pn_context.cpp ---------------------------------------------------------------------------------------------------------
+// device count and range, then the guard (entered, the caller's to hold), then the stream: the caller's own, or a new non-blocking
+// one (*own_stream).  What pn_ctx_create and pn_featgen_create do before they allocate anything; -1 with the error set.
+int open_device(int device, void *hip_stream, DeviceGuard &guard, hipStream_t *stream, bool *own_stream);
+// plan: NULL = pn_plan_for(n_streams, nn_mode) (the public behaviour); the self-tests' temporary contexts run the SAME families
+// as the context under test whatever their own size.
+pn_ctx *ctx_create(const pn_model *model, int device, int n_streams, int nn_mode, void *hip_stream, bool selftest, const PnPlan *plan);
 int dev_alloc_into(std::vector<void *> &allocs, size_t &total, hipStream_t stream, void **p, size_t bytes, bool zero);
+static inline int dev_alloc(pn_ctx *c, void **p, size_t bytes, bool zero) { return dev_alloc_into(c->allocs, c->bytes, c->stream, p, bytes, zero); }
+bool &last_alloc_oom();      // this thread's last dev_alloc_into failure was hipErrorOutOfMemory (the self-tests: skipped, not failed)
 // the shared tables built on the host and copied to a new device buffer (synchronous); tansig (optional): the activation table alone
 int tables_upload(std::vector<void *> &allocs, size_t &total, hipStream_t stream, PnTables **tables, float **tansig);
 // ids[0..n) (host) -> the context's id ring on the device, asynchronously on the context's stream; NULL on failure.  For the
 // objects beside a context that take id lists under its rules (pn_rate.cpp)
 const int *stage_ids(pn_ctx *c, const int32_t *ids, int n, const void *payload = NULL, int payload_words = 0);
+// one frame for every stream / for the listed ones (device rows); active_check: the list's verdict alone, leaves c->act.mark
+int process_dev(pn_ctx *c, const void *d_in, void *d_out, float *d_gr, int is_i16);
+int active_check(pn_ctx *c, const int32_t *ids, int n);
+int process_active(pn_ctx *c, const void *d_in, void *d_out, float *d_gr, int is_i16, const int32_t *ids, int n);
+// ---- pn_selftest.cpp --------------------------------------------------------------------------------------------------------
+int nn_selftest(pn_ctx *c);
+int dsp_selftest(pn_ctx *c);
+// ---- pn_host_pipe.cpp -------------------------------------------------------------------------------------------------------
 int pipe_make_stream(pn_ctx *c, hipStream_t *out, char how, int prio, char fallback, const std::vector<hipStream_t> &others, char *kind);
+int pipe_drain(pn_ctx *c);       // frames in flight on the pipelined path complete (the caller is on the context's device)
+void pipe_destroy(pn_ctx *c);    // the pipeline's streams and events, whole or partly built; its device buffers stay with the context
+// ---- pn_stream_state.cpp ----------------------------------------------------------------------------------------------------
+// The synchronous host form of a record transfer, for the context's records and for those of the objects beside it (pn_rate.cpp):
+// frames in flight on the pipelined path complete first; the records pass through a device buffer of their own size (+ extra_bytes
+// behind them, copied to h_extra after the launch: the context's import keeps its status words there) that is freed on every path.
+// import: h_records -> device before launch(d_records); else device -> h_records after it.  launch returns 0, or -1 with the error set.
+int host_records_sync(pn_ctx *c, bool import, void *h_records, size_t bytes, const std::function<int(void *d_records)> &launch,
+                      void *h_extra = NULL, size_t extra_bytes = 0);
 // ---- pn_network.cpp ---------------------------------------------------------------------------------------------------------
 int weights_acquire(pn_ctx *c, const pn_model *model);     // c->weights, c->L: the shared device copy for c's key, built by its first user
 void weights_release(pn_ctx *c);                           // ... freed with its last one
@@ -109,6 +138,15 @@ static inline float *state_at(const pn_ctx *c, int e, int j, size_t r0 = 0) {
   const PnStateEntry &L = pn_kState[e];
   const int slot = j < L.live ? (pn_state_first(L, c->t, c->tn) + j) % L.slots : pn_state_write(L, c->t, c->tn);
   return c->st[e].p + slot * c->st[e].slot_stride + r0 * L.row_words;
+}
+// The record sections (= the rings the active-set fix-up shifts, and synth) at the context's CURRENT counters, those of the next
+// frame to run: DSP rings follow t, the network's follow tn (they differ after pn_ctx_compute_rnn_host)
+static inline void state_sections(const pn_ctx *c, PnSsSection sec[PN_SS_NSEC]) {
+  for (int e = 0; e < PN_ST_COUNT; e++) {
+    const PnStateEntry &L = pn_kState[e]; const pn_ctx::StateBuf &b = c->st[e];
+    if (L.rec_off >= 0) sec[pn_state_section(e)] = PnSsSection{b.p, (uint4 *)b.sh, L.row_words, b.slot_stride, L.slots, pn_state_first(L, c->t, c->tn), L.live, L.cols, L.rec_off,
+                         b.sh ? (int)shadow_halfs_per_element(c) : 0};
+  }
 }
 // every stream of this context that carries kernels or copies of a frame: a new one must share a hardware queue with none of them
 static inline std::vector<hipStream_t> busy_streams(const pn_ctx *c) {

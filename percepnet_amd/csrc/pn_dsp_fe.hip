@@ -173,9 +173,6 @@ __global__ __launch_bounds__(FE_THREADS, PN_FE_WAVES_PER_SIMD) void pn_frontend_
       PN_WAVE_SYNC();
       FE_MARK(3);
 
-#if defined(PN_FE_ABL) && PN_FE_ABL == 1
-      continue;   // timing ablation (tools/kernel_times.py): history write + look-ahead FFT + band energies only
-#endif
       // -- pitch_downsample (pitch.cpp:148-216) of pitch_buf == comb_buf[1632,3360) ----------------
       // outputs 2m, 2m+1 need x[4m-1 .. 4m+3]
       {
@@ -266,9 +263,6 @@ __global__ __launch_bounds__(FE_THREADS, PN_FE_WAVES_PER_SIMD) void pn_frontend_
       PN_WAVE_SYNC();
 
       FE_MARK(6);   // FIR
-#if defined(PN_FE_ABL) && PN_FE_ABL == 2
-      continue;   // timing ablation: + downsample, autocorr, LPC, FIR
-#endif
       // -- pitch_search (pitch.cpp:283-386): x_lp = pbuf+384, y = pbuf, len 960, max_pitch 588 ----
       // coarse: x_lp4[j] = pbuf[384+2j] (240, group-uniform operand, read straight from pbuf),
       // y_lp4[j] = pbuf[2j] (387, copied out contiguously); lane owns lags l + L*c, c < NCH
@@ -340,9 +334,6 @@ __global__ __launch_bounds__(FE_THREADS, PN_FE_WAVES_PER_SIMD) void pn_frontend_
       PN_WAVE_SYNC();
 
       FE_MARK(10);  // find_best_pitch fine + interp
-#if defined(PN_FE_ABL) && PN_FE_ABL == 3
-      continue;   // timing ablation: + pitch_search
-#endif
       // -- remove_doubling (pitch.cpp:424-527): maxperiod 384, minperiod 30, N 480, x = pbuf+384 -----
       float pg;
       {
@@ -455,9 +446,6 @@ __global__ __launch_bounds__(FE_THREADS, PN_FE_WAVES_PER_SIMD) void pn_frontend_
       PN_WAVE_SYNC();
 
       FE_MARK(13);  // decisions + final 3 chains
-#if defined(PN_FE_ABL) && PN_FE_ABL == 4
-      continue;   // timing ablation: + remove_doubling
-#endif
       // -- comb filter (denoise.cpp:416-422) + window + FFT -> P, Ep, Exp -------------------------
       {
         // each lane filters 4 consecutive samples per step: one (unaligned) dwordx4 load per tap instead of four

@@ -6,7 +6,7 @@
 // noisy spectrum with the ideal gains, through the speech state's synthesis memory (744-757).
 // The two DenoiseStates are two DSP sides (pn_dsp_layout.h): the front end's entries of the state table, sized for n_pairs rows
 // each, allocated, zeroed and reset by the walk a context makes, and run by the plan's front-end family like a context's.
-#include "pn_context.h"      // the launchers, the DSP side, dev_alloc_into, tables_upload
+#include "pn_context.h"      // the launchers, the DSP side, open_device, dev_alloc_into, tables_upload
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
@@ -36,21 +36,11 @@ extern "C" void pn_featgen_destroy(pn_featgen *c) {
 
 extern "C" pn_featgen *pn_featgen_create(int device, int n_pairs, void *hip_stream) {
   if (n_pairs < 1) { pn_set_error("n_pairs must be >= 1"); return NULL; }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    pn_set_error("no HIP device available (this library has no CPU fallback)");
-    return NULL;
-  }
-  if (device < 0 || device >= ndev) { pn_set_error("device %d out of range (%d devices)", device, ndev); return NULL; }
-  DeviceGuard _dg(device);
-  if (!_dg.ok) { pn_set_error("hipSetDevice(%d) failed", device); return NULL; }
+  DeviceGuard _dg; hipStream_t stream; bool own_stream;
+  if (open_device(device, hip_stream, _dg, &stream, &own_stream)) return NULL;
   pn_featgen *c = new pn_featgen();
   c->device = device; c->B = n_pairs; c->t = 0; c->bytes = 0; c->fe = pn_plan_for(n_pairs, PN_NN_MFMA).fe;
-  if (hip_stream) { c->stream = (hipStream_t)hip_stream; c->own_stream = false; }
-  else {
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { pn_set_error("hipStreamCreate failed"); delete c; return NULL; }
-    c->own_stream = true;
-  }
+  c->stream = stream; c->own_stream = own_stream;
   const size_t B = n_pairs;
   if (tables_upload(c->allocs, c->bytes, c->stream, &c->tables, NULL)) goto fail;
   for (int side = 0; side < 2; side++) {

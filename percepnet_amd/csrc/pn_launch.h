@@ -1,4 +1,4 @@
-// Kernel launchers shared by the host files (pn_context.cpp, pn_network.cpp, pn_featgen.cpp).  The DSP ones take the
+// Kernel launchers shared by the host files (pn_context.cpp and the units split from it, pn_network.cpp, pn_featgen.cpp, pn_rate.cpp).  The DSP ones take the
 // descriptions of pn_dsp_layout.h (a side, the slots of a frame, its input), the network ones one record of a layer's launch
 // (PnLayerLaunch, below) and begin with the rule of their kernel kind (pn_network.h).
 #pragma once
@@ -9,7 +9,7 @@
 // A front-end launch takes a side, the frame's slots and the frame's input (pn_dsp_layout.h); a launch that needs no tables or
 // no input ignores them, so that all five have one signature.  pn_launch_fe (pn_context.cpp) is launch k of family fe: a context
 // and the feature generator both loop over pn_kFe[fe]'s launches.
-// grid_cap: test hook of the create-time DSP self-test (pn_context.cpp: dsp_selftest).  When > 0 the launcher caps its grid at
+// grid_cap: test hook of the create-time DSP self-test (pn_selftest.cpp: dsp_selftest).  When > 0 the launcher caps its grid at
 // this many blocks, so that a 40-stream batch walks several grid-stride rounds of ONE block (the regime in which a mis-scheduled
 // persistent loop once corrupted later rounds).  It is state of the temporary self-test context only
 // (pn_ctx::dsp_grid_cap): no other context, thread or device ever sees it.  0 = off.
@@ -25,7 +25,7 @@ void pn_launch_zero_shadow_rows(hipStream_t st, void *S, int width, int np, int 
                                 const int *d_ids, int n);
 // dst[ids[i]] = vals[i] for i < n (distinct ids): the per-stream (lam, mu) pairs of the attenuation limit
 void pn_launch_scatter_pairs(hipStream_t st, float2 *dst, const int *d_ids, const float2 *d_vals, int n);
-// One section of a context's per-stream state at given counters (pn_context.cpp state_sections, from pn_state_layout.h): a
+// One section of a context's per-stream state at given counters (pn_context.h state_sections, from pn_state_layout.h): a
 // ring or an in-place buffer, its live entries oldest first in slots first, first + 1, ... (mod slots); base + row * row_stride
 // + slot * slot_stride = an entry of `cols` floats (all multiples of 4), stored at body word rec_off of a stream-state record.
 // shadow: the entry's fragment-order operand shadow of np planes (pn_nn_x3.hip), slot for slot; NULL = none

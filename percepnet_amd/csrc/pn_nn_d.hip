@@ -25,19 +25,8 @@
 #include "pn_nn_common.h"
 #include <stdlib.h>
 
-// Timing ablations (tools only; results WRONG): 1 no A refills, 2 no weight staging, 4 no K-loop barriers, 8 no gating epilogue,
-// 16 no weight-fragment reads
-#ifndef PN_D_ABL
-#define PN_D_ABL 0
-#endif
 #ifndef PN_D_REFILL_IDLE
 #define PN_D_REFILL_IDLE 1              // 64-row waves: a tile's activation loads go to the register set the current tile does not read
-#endif
-
-#if PN_D_ABL & 4
-#define D_SYNC() __builtin_amdgcn_sched_barrier(0)
-#else
-#define D_SYNC() __syncthreads()
 #endif
 
 #define D_CHUNK PN_SHADOW_CHUNK
@@ -83,11 +72,7 @@ __device__ __forceinline__ void d_tile(DA<RG> &a, DA<RG> &fill, const fvec4 (*Bs
   for (int i = 0; i < 4 * NT; i++) {
     const int q = i / NT, t = i % NT;
     fvec4 &cur = (i & 1) ? f1 : f0, &nxt = (i & 1) ? f0 : f1;
-#if !(PN_D_ABL & 16)
     if (i + 1 < 4 * NT) nxt = Bs[(i + 1) % NT][((i + 1) / NT) * 64 + lane];
-#else
-    nxt = cur;
-#endif
     __builtin_amdgcn_sched_barrier(0);                   // keep the read ahead of the MFMAs it overlaps (the scheduler sinks it)
 #pragma unroll
     for (int c = 0; c < 4; c++)
@@ -95,12 +80,10 @@ __device__ __forceinline__ void d_tile(DA<RG> &a, DA<RG> &fill, const fvec4 (*Bs
       for (int rg = 0; rg < RG; rg++)
         acc[rg][IDX[t]] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.v[q][rg][c], cur[c], acc[rg][IDX[t]], 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
-#if !(PN_D_ABL & 1)
     if (t == NT - 1) {
       d_load_A<RG>(fill, pf, lb, q);
       __builtin_amdgcn_sched_barrier(0);
     }
-#endif
     mid(i);
   }
 }
@@ -162,10 +145,10 @@ __global__ __launch_bounds__(NN_THREADS, 4 - RG) void pn_gru_d_kernel(
   constexpr bool IDLE = PN_D_REFILL_IDLE && RG == 2;
 #define DG_FILL(cur, other) (IDLE ? other : cur)
 #define DG_PAIR(g, I2)                                                                                             \
-    { DG_APTR(pa); d_tile<RG, 3, 0, 1, I2, 0>(qa, DG_FILL(qa, qb), S.B[0], pa, lb, lane, acc, [&](int i) { if (!(PN_D_ABL & 2)) { if (i == 1) DG_BSTASH(1); if (i == 3) DG_BLOAD((g) + 2); } }); } \
-    D_SYNC();                                                                                                      \
-    { DG_APTR(pb); d_tile<RG, 3, 0, 1, I2, 0>(qb, DG_FILL(qb, qa), S.B[1], pb, lb, lane, acc, [&](int i) { if (!(PN_D_ABL & 2)) { if (i == 1) DG_BSTASH(0); if (i == 3) DG_BLOAD((g) + 3); } }); } \
-    D_SYNC()
+    { DG_APTR(pa); d_tile<RG, 3, 0, 1, I2, 0>(qa, DG_FILL(qa, qb), S.B[0], pa, lb, lane, acc, [&](int i) { if (i == 1) DG_BSTASH(1); if (i == 3) DG_BLOAD((g) + 2); }); } \
+    __syncthreads();                                                                                               \
+    { DG_APTR(pb); d_tile<RG, 3, 0, 1, I2, 0>(qb, DG_FILL(qb, qa), S.B[1], pb, lb, lane, acc, [&](int i) { if (i == 1) DG_BSTASH(0); if (i == 3) DG_BLOAD((g) + 3); }); } \
+    __syncthreads()
   DA<RG> qa, qb;
   fvec4 rb[3];
   { DG_APTR(p0); _Pragma("unroll") for (int q = 0; q < 4; q++) d_load_A<RG>(qa, p0, lb, q); }
@@ -199,11 +182,7 @@ __global__ __launch_bounds__(NN_THREADS, 4 - RG) void pn_gru_d_kernel(
     for (int rg = 0; rg < RG; rg++) {
       const int grow0 = mt * XMB + 32 * RG * wave + 32 * rg;
       float v[16];
-#if PN_D_ABL & 8
-      _Pragma("unroll") for (int i = 0; i < 16; i++) v[i] = acc[rg][0][i] + acc[rg][1][i] + acc[rg][2][i] + acc[rg][3][i] + ho[rg][i] + bh;
-#else
       pn_gru_gate16(acc[rg][0], acc[rg][1], acc[rg][2], acc[rg][3], ho[rg], bh, act, S.tansig, v);
-#endif
       pn_store_tile_frag(T, v, h_new, N, nt * 32, N, grow0, n_rows, Sx, srow + 32 * rg, lane);
     }
   }

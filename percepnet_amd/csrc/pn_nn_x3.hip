@@ -137,12 +137,10 @@ __device__ __forceinline__ void x3_tile(X3A<RG> &qa, X3A<RG> &qb, const uint4 (*
     __builtin_amdgcn_sched_barrier(0);                   // keep the read ahead of the MFMAs it overlaps (the scheduler sinks it)
     x3_mma6<RG, NP>(s ? qb : qa, cur, acc, IDX[t]);
     __builtin_amdgcn_sched_barrier(0);
-#if !(defined(PN_XP_ABL) && (PN_XP_ABL & 4))   // timing ablation (results wrong): no A refills
     if (t == NT - 1) {
       x3_load_A<RG, NP>(s ? qb : qa, pf, s);
       __builtin_amdgcn_sched_barrier(0);
     }
-#endif
   }
 }
 
@@ -570,15 +568,11 @@ __global__ __launch_bounds__(512, 1) void pn_gru_x3p_kernel(
   // put tiles 0, 1, 2 into its ring; interval s >= 1 adds tile s + 2 to slot (s + 2) % 3 — free since barrier s - 1 — from
   // register set (s + 2) % XP_BD, loaded XP_BD intervals earlier (tiles 3 .. 2 + XP_BD: at interval 0), and refills the set
   // with tile s + 2 + XP_BD.
-#if defined(PN_XP_ABL) && (PN_XP_ABL & 8)       // timing ablation (results wrong): no weight staging during K phases
-#define XP_STAGE(s_) do { } while (0)
-#else
 #define XP_STAGE(s_) do {                                                                                        \
     if ((s_) >= 1 && (s_) + 2 < TT) XP_BSTASHP(grp ^ 1, ((s_) + 2) % 3, pb[((s_) + 2) % XP_BD]);                 \
     if ((s_) == 0) { _Pragma("unroll") for (int j_ = 0; j_ < XP_BD; j_++) if (3 + j_ < TT) XP_BLOADP(pb[(3 + j_) % XP_BD], pWz, pUz, 3 + j_); } \
     else if ((s_) + 2 + XP_BD < TT) XP_BLOADP(pb[((s_) + 2) % XP_BD], pWz, pUz, (s_) + 2 + XP_BD);               \
   } while (0)
-#endif
   // z-gate weight bases of the partner group's tile with walk index it_
 #define XP_PARTNER(it_) do {                                                                                     \
     int w_ = (slot ^ 1) + (it_) * NS; w_ = w_ < Wx ? w_ : Wx - 1;                                                \
@@ -589,9 +583,6 @@ __global__ __launch_bounds__(512, 1) void pn_gru_x3p_kernel(
   // stay in flight across it
 #define XP_KBAR() do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0xC07F | (((XP_D - 1) * NP) << 8)); \
     __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#if defined(PN_XP_ABL) && (PN_XP_ABL & 2)       // timing ablation (results wrong): the K phase is only its barriers
-#define XP_PAIR(g, I2) XP_KBAR(); XP_KBAR()
-#else
   // two k-tiles: tile g from ring slot s0 with the A registers q0/q1 (refilled from pfA = tile g + 2), tile g + 1 from s1
   // with q2/q3 (pfB); each tile's hook advances the A cursor for the other tile's next pointer
 #define XP_PAIR(g, I2)                                                                                           \
@@ -602,7 +593,6 @@ __global__ __launch_bounds__(512, 1) void pn_gru_x3p_kernel(
         [&]() { }, [&]() { XP_APTR(pn_); pfA = pn_; });                                                           \
     XP_KBAR();                                                                                                   \
     { const int s_ = s0; s0 = s2; s2 = s1; s1 = s_; }
-#endif
   // prologue of the tile with walk index it_: coordinates, the first two A tiles and the first weight tile in flight ...
 #define XP_PRO0(it_) do {                                                                                        \
     int w_ = slot + (it_) * NS; w_ = w_ < Wx ? w_ : Wx - 1;    /* past the end: a valid tile, loaded and never used */ \
@@ -708,7 +698,6 @@ __global__ __launch_bounds__(512, 1) void pn_gru_x3p_kernel(
       for (int s = 0; s < TT; s++) {
         XP_STAGE(s);
         int n_reads = 0;                                       // table reads issued in this step for the next one
-#if !(defined(PN_XP_ABL) && (PN_XP_ABL & 1))       // timing ablation (results wrong): no gating arithmetic
 #pragma unroll
         for (int v = 0; v < 32; v++) {
           if (((3 * v) >> 2) + 2 != s) continue;
@@ -744,7 +733,6 @@ __global__ __launch_bounds__(512, 1) void pn_gru_x3p_kernel(
           x3_pin(za[v].x); x3_pin(za[v].sb); x3_pin(ra[v].x); x3_pin(ra[v].sb);
           n_reads += 2;
         }
-#endif
         if (s == 22) XP_PRO0(it + 1);
         if (s == 26 || s == 28) {
           const int rg = (s - 26) >> 1;

@@ -3,7 +3,7 @@
 // tap tables on the device, the per-stream tails of the two kernels (pn_rate.hip), the 48 kHz rows between the conversions and
 // the staging rows of the host-buffer path.  Nothing of it lives in pn_ctx, its state table or its records.  Every launch goes
 // to the context's stream, so a converter call is ordered against the context's calls like they are against each other.
-#include "pn_context.h"      // the context it borrows, the launchers, dev_alloc_into, stage_ids
+#include "pn_context.h"      // the context it borrows, the launchers, dev_alloc_into, stage_ids, the id rule, host_records_sync
 #include "pn_rate_design.h"
 #include <string>
 #include <vector>
@@ -86,22 +86,9 @@ extern "C" int pn_rate_reset(pn_rate *r) {
   return 0;
 }
 
-// the context's rules for an id list: in range, and distinct where the streams advance or are written
-static int rate_ids_check(const pn_rate *r, const int32_t *ids, int n, bool distinct) {
-  const int B = r->c->B;
-  if (n < 0 || (n > 0 && !ids)) { pn_set_error("bad argument"); return -1; }
-  if (distinct && n > B) { pn_set_error("%d streams listed for a context of %d", n, B); return -1; }
-  std::vector<uint8_t> seen(distinct ? (size_t)B : 0, 0);
-  for (int i = 0; i < n; i++) {
-    if (ids[i] < 0 || ids[i] >= B) { pn_set_error("stream id %d out of range [0, %d)", ids[i], B); return -1; }
-    if (distinct && seen[ids[i]]++) { pn_set_error("stream id %d listed twice", ids[i]); return -1; }
-  }
-  return 0;
-}
-
 extern "C" int pn_rate_reset_streams(pn_rate *r, const int32_t *ids, int n) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
-  if (rate_ids_check(r, ids, n, false)) return -1;
+  if (pn_ids_check(r->c->B, ids, n, false)) return -1;
   if (n == 0) return 0;
   PN_ON_DEVICE(r->c);
   const int *d = stage_ids(r->c, ids, n);
@@ -119,7 +106,7 @@ struct RateRows { const int *d_ids; int n; };
 static int rate_rows(pn_rate *r, const int32_t *ids, int n, RateRows *rows) {
   rows->d_ids = NULL; rows->n = r->c->B;
   if (!ids) return 0;
-  if (rate_ids_check(r, ids, n, true)) return -1;
+  if (pn_ids_check(r->c->B, ids, n, true)) return -1;
   rows->n = n;
   if (n > 0 && !(rows->d_ids = stage_ids(r->c, ids, n))) return -1;
   return 0;
@@ -171,7 +158,7 @@ static int rate_process(pn_rate *r, const void *d_in, void *d_out, float *d_gr, 
   PN_ON_DEVICE(c);
   RateRows rows = {NULL, c->B};
   if (active) {                                      // (an empty list is legal, as for pn_process_*_active: nobody advances)
-    if (rate_ids_check(r, ids, n, true)) return -1;
+    if (pn_ids_check(r->c->B, ids, n, true)) return -1;
     rows.n = n;
     if (n > 0 && !(rows.d_ids = stage_ids(c, ids, n))) return -1;
   }
@@ -201,53 +188,27 @@ extern "C" int pn_rate_process_host_f32(pn_rate *r, const float *h_in, float *h_
 extern "C" int pn_rate_process_host_i16(pn_rate *r, const int16_t *h_in, int16_t *h_out, float *h_gr) { return rate_process_host(r, h_in, h_out, h_gr, 1); }
 
 // ---- state records -----------------------------------------------------------------------------------------------------------
-// Host forms only: synchronous, through a device buffer of the records' size that is freed before returning (like the host
-// forms of the context's stream-state records).
+// Host forms only: synchronous, through the context's host form of a record transfer (host_records_sync).
+static int rate_records_host(pn_rate *r, bool import, const int32_t *ids, int n, void *h_records) {
+  pn_ctx *c = r->c;
+  return host_records_sync(c, import, h_records, (size_t)n * 4 * pn_rate_record_words(r->L), [&](void *d) {
+    const int *d_ids = stage_ids(c, ids, n);
+    if (!d_ids) return -1;
+    pn_launch_rate_records(c->stream, r->L, r->rate, d_ids, n, r->tail_up, r->tail_down, d, import ? 1 : 0);
+    if (hipGetLastError() != hipSuccess) { pn_set_error(import ? "record scatter launch failed" : "record gather launch failed"); return -1; }
+    return 0;
+  });
+}
 extern "C" int pn_rate_export_streams_host(pn_rate *r, const int32_t *ids, int n, void *h_records) {
   if (!r || n < 0 || (n > 0 && (!ids || !h_records))) { pn_set_error("bad argument"); return -1; }
   if (n == 0) return 0;
-  if (rate_ids_check(r, ids, n, false)) return -1;
-  pn_ctx *c = r->c;
-  PN_ON_DEVICE(c);
-  if (pn_host_wait(c)) return -1;
-  const size_t bytes = (size_t)n * 4 * pn_rate_record_words(r->L);
-  const int *d_ids = stage_ids(c, ids, n);
-  if (!d_ids) return -1;
-  void *d = NULL;
-  PN_HIP_CHECK(hipMalloc(&d, bytes));
-  int rc = 0;
-  pn_launch_rate_records(c->stream, r->L, r->rate, d_ids, n, r->tail_up, r->tail_down, d, 0);
-  if (hipGetLastError() != hipSuccess) { pn_set_error("record gather launch failed"); rc = -1; }
-  if (!rc && hipMemcpyAsync(h_records, d, bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) { pn_set_error("record copy failed"); rc = -1; }
-  if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) { pn_set_error("export failed"); rc = -1; }
-  hipFree(d);
-  return rc;
+  if (pn_ids_check(r->c->B, ids, n, false)) return -1;
+  return rate_records_host(r, false, ids, n, h_records);
 }
 extern "C" int pn_rate_import_streams_host(pn_rate *r, const int32_t *ids, int n, const void *h_records) {
   if (!r || n < 0 || (n > 0 && (!ids || !h_records))) { pn_set_error("bad argument"); return -1; }
   if (n == 0) return 0;
-  if (rate_ids_check(r, ids, n, true)) return -1;
-  const size_t rec_bytes = 4 * pn_rate_record_words(r->L), bytes = (size_t)n * rec_bytes;
-  for (int i = 0; i < n; i++)                          // all or nothing: every header before anything is launched
-    if (pn_rate_record_check(static_cast<const char *>(h_records) + (size_t)i * rec_bytes, rec_bytes, r->rate)) {
-      std::string why = pn_last_error();
-      pn_set_error("record %d refused: %s", i, why.c_str());
-      return -1;
-    }
-  pn_ctx *c = r->c;
-  PN_ON_DEVICE(c);
-  if (pn_host_wait(c)) return -1;
-  const int *d_ids = stage_ids(c, ids, n);
-  if (!d_ids) return -1;
-  void *d = NULL;
-  PN_HIP_CHECK(hipMalloc(&d, bytes));
-  int rc = hipMemcpyAsync(d, h_records, bytes, hipMemcpyHostToDevice, c->stream) == hipSuccess ? 0 : -1;
-  if (rc) pn_set_error("record copy failed");
-  if (!rc) {
-    pn_launch_rate_records(c->stream, r->L, r->rate, d_ids, n, r->tail_up, r->tail_down, d, 1);
-    if (hipGetLastError() != hipSuccess) { pn_set_error("record scatter launch failed"); rc = -1; }
-  }
-  if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) { pn_set_error("import failed"); rc = -1; }
-  hipFree(d);
-  return rc;
+  if (pn_ids_check(r->c->B, ids, n, true)) return -1;
+  if (pn_records_check(h_records, n, 4 * pn_rate_record_words(r->L), [&](const void *rec, size_t b) { return pn_rate_record_check(rec, b, r->rate); })) return -1;
+  return rate_records_host(r, true, ids, n, const_cast<void *>(h_records));
 }

@@ -6,10 +6,8 @@
 // for k >= 0 and mirrored, so the table is symmetric bit for bit; h[0] = 1 and h[jL] = 0 are set, not computed (sin(pi j) is not
 // 0 in double), which is what makes phase 0 of the up-conversion a copy.  The down-converter's taps are (float)(h_double[k] / L).
 #pragma once
-#include "pn_common.h"
-#include "../../include/percepnet_hip.h"
+#include "pn_host_rules.h"   // pn_le32, pn_record_header_check
 #include <math.h>
-#include <string.h>
 
 #define PN_RATE_BETA 8.0
 #define PN_RATE_UP_TAIL (2 * PN_RATE_TAPS)      // low-rate samples an up-converted stream carries: x[q - 2T + 1 .. q] is 32 wide
@@ -58,21 +56,20 @@ static inline void pn_rate_record_header(uint32_t hdr[4], int rate_hz) {
   hdr[0] = PN_RATE_STATE_MAGIC; hdr[1] = PN_RATE_STATE_VERSION;
   hdr[2] = (uint32_t)(4 * pn_rate_record_words(pn_rate_factor(rate_hz))); hdr[3] = (uint32_t)rate_hz;
 }
-static inline uint32_t pn_rate_le32(const unsigned char *p) { return p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
 // is `bytes` bytes at `record` one state record of a converter of rate_hz?  Reads the 16 header bytes only, and only when
-// they are there.  Same order of verdicts as the stream-state check (pn_context.cpp ss_check_host), then the rate.
+// they are there.  The verdicts every record shares (pn_host_rules.h pn_record_header_check), then the rate, then the size.
 static inline int pn_rate_record_check(const void *record, size_t bytes, int rate_hz) {
   const int L = pn_rate_factor(rate_hz);
   if (!record) { pn_set_error("NULL argument"); return PN_SS_BAD_ARG; }
   if (!L) { pn_set_error("rate %d Hz: a converter takes 8000, 16000 or 24000", rate_hz); return PN_SS_BAD_RATE; }
   const size_t want = 4 * pn_rate_record_words(L);
   const unsigned char *r = static_cast<const unsigned char *>(record);
-  if (bytes < PN_RATE_STATE_HEADER_BYTES) { pn_set_error("rate-state record of %zu bytes: a record at %d Hz has %zu", bytes, rate_hz, want); return PN_SS_BAD_SIZE; }
-  if (pn_rate_le32(r) != PN_RATE_STATE_MAGIC) { pn_set_error("not a rate-state record (magic 0x%08x)", pn_rate_le32(r)); return PN_SS_BAD_MAGIC; }
-  if (pn_rate_le32(r + 4) != PN_RATE_STATE_VERSION) { pn_set_error("rate-state record version %u, this library reads %d", pn_rate_le32(r + 4), PN_RATE_STATE_VERSION); return PN_SS_BAD_VERSION; }
-  if ((int32_t)pn_rate_le32(r + 12) != rate_hz) { pn_set_error("rate-state record written at %d Hz, this converter runs at %d", (int32_t)pn_rate_le32(r + 12), rate_hz); return PN_SS_BAD_RATE; }
-  if (pn_rate_le32(r + 8) != want || bytes != want) {
-    pn_set_error("rate-state record of %zu bytes (header: %u), a record at %d Hz has %zu", bytes, pn_rate_le32(r + 8), rate_hz, want);
+  const int v = pn_record_header_check(r, bytes, PN_RATE_STATE_MAGIC, PN_RATE_STATE_VERSION, "rate-state");
+  if (v == PN_SS_BAD_SIZE) pn_set_error("rate-state record of %zu bytes: a record at %d Hz has %zu", bytes, rate_hz, want);
+  if (v) return v;
+  if ((int32_t)pn_le32(r + 12) != rate_hz) { pn_set_error("rate-state record written at %d Hz, this converter runs at %d", (int32_t)pn_le32(r + 12), rate_hz); return PN_SS_BAD_RATE; }
+  if (pn_le32(r + 8) != want || bytes != want) {
+    pn_set_error("rate-state record of %zu bytes (header: %u), a record at %d Hz has %zu", bytes, pn_le32(r + 8), rate_hz, want);
     return PN_SS_BAD_SIZE;
   }
   return PN_SS_OK;

@@ -8,7 +8,7 @@
 //
 // One DenoiseState = a batch-of-one context.  That is correct but launch-bound (15 kernel
 // launches and two PCIe hops per 10 ms frame); throughput lives in the batched pn_* API.  N handles of one model share
-// ONE DEVICE copy of the weights (pn_context.cpp: SharedWeights, found by the model's SHA-256).  Host side (round 6): a handle
+// ONE DEVICE copy of the weights (pn_network.cpp: SharedWeights, found by the model's SHA-256).  Host side (round 6): a handle
 // keeps NO copy of the model.  The host pn_model a context is created from comes from
 //   * the OwnedModel behind an RNNModel that rnnoise_model_from_file returned (the arrays ARE that pn_model's: zero copies);
 //   * one process-wide pn_model of the link-time percepnet_model_orig (immutable .rodata) / of the PERCEPNET_MODEL file

@@ -3,13 +3,15 @@
 // the weight packers (pn_pack.cpp) and the CLI helpers (pn_cli_util.h) — driven with valid, truncated, oversized and
 // corrupted inputs; the table of a context's per-stream state (pn_state_layout.h): record offsets, ring phases, classes; the DSP
 // half of a frame (pn_dsp_layout.h): slots, side entries, front-end families, profiling families; and the
-// table of the network's layers (pn_network.h): kernel, weight format, shadows and launch geometry of every layer under every plan.
+// table of the network's layers (pn_network.h): kernel, weight format, shadows and launch geometry of every layer under every plan;
+// and the host rules of the C-ABI (pn_host_rules.h): id lists in exactly-sized heap arrays, the header verdicts of a stream-state record.
 // Any out-of-bounds access, overflow or leak-free violation aborts; the process prints "ok" and exits 0.
 #include "../../percepnet_amd/csrc/pn_model.cpp"
 #include "../../percepnet_amd/csrc/pn_pack.cpp"
 #include "../../percepnet_amd/csrc/pn_tables.cpp"
 #include "../../percepnet_amd/csrc/pn_cli_util.h"
 #include "../../percepnet_amd/csrc/pn_network.h"
+#include "../../percepnet_amd/csrc/pn_host_rules.h"
 #include <stdio.h>
 #include <string>
 #include <vector>
@@ -157,6 +159,92 @@ int main(int argc, char **argv) {
     CHECK(pn_kernel_geometry_ok(PN_K_X3, true, 1, w128, 96) == -1 && pn_kernel_geometry_ok(PN_K_DIRECT, true, 1, w128, 96) == -1);
     CHECK(pn_kernel_geometry_ok(PN_K_SMALL, true, 1, w96, 128) == -1 && pn_kernel_geometry_ok(PN_K_BATCH, true, 1, w96, 128) == 0);
     CHECK(pn_kernel_geometry_ok(PN_K_DIRECT, false, 1, w128, 128) == -1 && pn_kernel_geometry_ok(PN_K_N16, true, 1, w128, 128) == -1); }      // STRICT; fp16 operands, split precision; fp32 MFMA (6 direct, 4 small, 6 batch)
+
+  // the id-list rule.  Every list is a heap array of exactly n ids, so that a read past ids[n - 1] aborts
+  for (int B : {1, 5}) {
+    typedef std::vector<int32_t> Ids;
+    std::vector<uint8_t> mark(3, 7);                           // wrong size, stale content: the rule resizes and clears it
+    auto ok = [&](const Ids &v, bool distinct, std::vector<uint8_t> *m = NULL) { return pn_ids_check(B, v.empty() ? NULL : v.data(), (int)v.size(), distinct, m) == 0; };
+    auto says = [&](const std::string &want) { return std::string(pn_last_error()) == want; };
+    const std::string range = " out of range [0, " + std::to_string(B) + ")";
+    for (bool distinct : {false, true}) {
+      CHECK(ok(Ids(), distinct));                              // empty list, with and without a pointer
+      { Ids one(1, 0); CHECK(pn_ids_check(B, one.data(), 0, distinct) == 0); }
+      CHECK(pn_ids_check(B, NULL, 1, distinct) == -1 && says("bad argument"));
+      { Ids one(1, 0); CHECK(pn_ids_check(B, one.data(), -1, distinct) == -1 && says("bad argument")); }
+      CHECK(pn_ids_check(B, NULL, -1, distinct) == -1 && says("bad argument"));
+      for (int bad : {-1, B})                                  // out of range at the first and at the last position of a list of B
+        for (int pos : {0, B - 1}) {
+          Ids v(B); for (int i = 0; i < B; i++) v[i] = i;
+          v[pos] = bad;
+          CHECK(!ok(v, distinct) && says("stream id " + std::to_string(bad) + range));
+        }
+      Ids perm(B); for (int i = 0; i < B; i++) perm[i] = (2 * i + 1) % B;      // (2 is coprime to 1 and 5)
+      CHECK(ok(perm, distinct, &mark));
+      if (distinct) { CHECK(mark.size() == (size_t)B); for (int i = 0; i < B; i++) CHECK(mark[i] == 1); }
+      else CHECK(mark.size() == 3 && mark[0] == 7);            // not distinct: the marks are not the rule's business
+    }
+    { Ids dup(2, B - 1);                                       // a duplicate: legal where the streams are only reset or read
+      CHECK(ok(dup, false));
+      if (B >= 2) CHECK(!ok(dup, true) && says("stream id " + std::to_string(B - 1) + " listed twice"));
+      Ids over(B + 1, 0);                                      // a distinct list longer than B is refused by its count ...
+      CHECK(!ok(over, true) && says(std::to_string(B + 1) + " stream ids in a context of " + std::to_string(B)));
+      CHECK(ok(over, false));                                  // ... a list that may repeat is not
+      over[B] = B; CHECK(!ok(over, true) && says(std::to_string(B + 1) + " stream ids in a context of " + std::to_string(B)));   // count before ids
+      if (B >= 3) { Ids v = {1, 1, B}; CHECK(!ok(v, true) && says("stream id 1 listed twice")); }      // list order: the duplicate comes first
+      if (B >= 3) { Ids v = {B, 1, 1}; CHECK(!ok(v, true) && says("stream id " + std::to_string(B) + range)); } }
+    if (B == 5) {                                              // the marks are exactly the listed set, and a shorter list leaves none behind
+      Ids a = {4, 0, 2}, b = {3};
+      CHECK(ok(a, true, &mark)); CHECK(mark == std::vector<uint8_t>({1, 0, 1, 0, 1}));
+      CHECK(ok(b, true, &mark)); CHECK(mark == std::vector<uint8_t>({0, 0, 0, 1, 0}));
+      CHECK(ok(Ids(), true, &mark)); CHECK(mark == std::vector<uint8_t>(5, 0));
+    }
+  }
+
+  // the record-header rule, for the stream-state record: a valid header, every length that cannot hold one, and every single-byte
+  // corruption of bytes 0..47 against the verdict of its field in the documented order (magic, version, size, model)
+  { unsigned char digest[32];
+    for (int i = 0; i < 32; i++) digest[i] = (unsigned char)(37 * i + 11);
+    uint32_t hdr[16];
+    ss_header(hdr, digest, PN_NN_MFMA_X3);
+    CHECK(hdr[0] == PN_STREAM_STATE_MAGIC && hdr[1] == PN_STREAM_STATE_VERSION && hdr[2] == PN_STREAM_STATE_BYTES && hdr[3] == (uint32_t)PN_NN_MFMA_X3);
+    std::vector<unsigned char> rec(PN_STREAM_STATE_BYTES, 0);
+    memcpy(rec.data(), hdr, sizeof(hdr));
+    CHECK(rec[0] == 'P' && rec[1] == 'N' && rec[2] == 'S' && rec[3] == 'S');
+    CHECK(ss_check_host(rec.data(), rec.size(), digest) == PN_SS_OK);
+    for (size_t len = 0; len < 16; len++) {                    // exact-size heap copies: a read past the end aborts
+      std::vector<unsigned char> t(rec.begin(), rec.begin() + len);
+      CHECK(ss_check_host(len ? t.data() : (const void *)"", len, digest) == PN_SS_BAD_SIZE);
+      CHECK(pn_record_header_check(len ? t.data() : (const unsigned char *)"", len, PN_STREAM_STATE_MAGIC, PN_STREAM_STATE_VERSION, "stream-state") == PN_SS_BAD_SIZE);
+    }
+    for (size_t len : {(size_t)16, (size_t)48, (size_t)64, rec.size() - 1}) {      // holds the words read first, is no record
+      std::vector<unsigned char> t(rec.begin(), rec.begin() + len);
+      CHECK(ss_check_host(t.data(), len, digest) == PN_SS_BAD_SIZE);
+    }
+    { std::vector<unsigned char> t(rec); t.push_back(0); CHECK(ss_check_host(t.data(), t.size(), digest) == PN_SS_BAD_SIZE); }
+    for (int b = 0; b < 48; b++)
+      for (int bit = 0; bit < 8; bit++) {
+        std::vector<unsigned char> t(rec);
+        t[b] ^= (unsigned char)(1 << bit);
+        const int want = b < 4 ? PN_SS_BAD_MAGIC : b < 8 ? PN_SS_BAD_VERSION : b < 12 ? PN_SS_BAD_SIZE : b < 16 ? PN_SS_OK : PN_SS_BAD_MODEL;
+        CHECK(ss_check_host(t.data(), t.size(), digest) == want);      // (word 3, the source's nn_mode, is not compared)
+      }
+    // the order of the verdicts: a record wrong in every field is refused for its magic, then its version, then its size, then its model
+    { std::vector<unsigned char> t(rec);
+      t[0] ^= 1; t[4] ^= 1; t[8] ^= 1; t[16] ^= 1;
+      CHECK(ss_check_host(t.data(), t.size(), digest) == PN_SS_BAD_MAGIC); t[0] ^= 1;
+      CHECK(ss_check_host(t.data(), t.size(), digest) == PN_SS_BAD_VERSION); t[4] ^= 1;
+      CHECK(ss_check_host(t.data(), t.size(), digest) == PN_SS_BAD_SIZE); t[8] ^= 1;
+      CHECK(ss_check_host(t.data(), t.size(), digest) == PN_SS_BAD_MODEL); }
+    // the all-or-nothing walk names the first refused record and keeps its reason
+    { std::vector<unsigned char> three(3 * rec.size());
+      for (int i = 0; i < 3; i++) memcpy(&three[i * rec.size()], rec.data(), rec.size());
+      auto check = [&](const void *r, size_t bytes) { return ss_check_host(r, bytes, digest); };
+      CHECK(pn_records_check(three.data(), 3, rec.size(), check) == 0);
+      three[2 * rec.size() + 5] ^= 1; three[1 * rec.size() + 20] ^= 1;
+      CHECK(pn_records_check(three.data(), 3, rec.size(), check) == -1);
+      CHECK(std::string(pn_last_error()) == "record 1 refused: stream-state record written under another model (pn_model_digest differs)");
+      CHECK(pn_records_check(three.data(), 1, rec.size(), check) == 0); } }
 
   // CLI helpers
   { std::vector<int> d;
