@@ -165,10 +165,14 @@ int pn_ctx_get_atten_limit(const pn_ctx *ctx, float *h_db);
    little-endian 32-bit words, [n_streams][8]:
      0  f32  in_peak       max |x| over the 480 input samples this output frame is about: the stream's input frame 6 frames
                            (2880 samples, the engine's delay: INTEGRATION.md §2) back, in the float convention (int16 / 32768),
-                           read from the history ring; 0 for the first 6 frames of a stream after a reset
-     1  f32  in_energy     sum of x * x over those samples
-     2  f32  out_peak      max |o| over the 480 output samples o before any cast (a NaN sample is ignored here)
-     3  f32  out_energy    sum of o * o
+                           read from the history ring; 0 for the first 6 frames of a stream after a reset.  The ring holds
+                           whatever a float entry point was given: a NaN sample is ignored here (0 for a frame of 480 NaNs),
+                           an infinite one gives +inf
+     1  f32  in_energy     sum of x * x over those samples: the fixed-order fp32 sum of fp32 products, so NaN as soon as one
+                           sample is NaN, +inf otherwise when a product or the sum overflows (|x| > ~1.8e19)
+     2  f32  out_peak      max |o| over the 480 output samples o before any cast (a NaN sample is ignored here: 0 for a frame
+                           of 480 NaNs; an infinite sample gives +inf)
+     3  f32  out_energy    sum of o * o, with in_energy's rules: NaN as soon as one sample is NaN, +inf on overflow otherwise
      4  f32  gain_mean     (sum of g_b) / 34 over the network's raw g (the first 34 words of the g|r tap)
      5  i32  pitch_period  the period this frame's comb filter used (pn_ctx_debug_copy's buffer 13)
      6  i32  out_clipped   output samples whose t = o * 32768 (fp32) lies outside the open interval (-32769, 32768), i.e. that do

@@ -101,6 +101,62 @@ class Down:
         return z
 
 
+# ---- the down kernel's int16 cast at its edges ------------------------------------------------------------------------------
+# A single non-zero 48 kHz sample of amplitude A at position i, zeros around it, makes every output it reaches exactly ONE rounded
+# product: z[m] = fl(g[Lm - D - i] * A), since adding zeros is exact.  Output m sees tap index Lm - i of the table (centre D), so a
+# sample at a multiple of L meets only g[0] = 1 / L and the taps that are exactly 0; any other sample meets ~2T non-zero taps of
+# both signs.  inf * 0 and NaN * anything are NaN, in numpy as on the GPU.
+def t_classes(t):
+    """t = z * 32768 (fp32) -> {class name: mask}: the ranges in which the two casts of the header behave differently.  The classes
+    are disjoint: "t <= -32769" is split into (-2^31, -32769], where the wrap still truncates, and the finite t at or beyond
+    -2^31, which together with those at or beyond +2^31 form "|t| >= 2^31", where the wrap gives 0."""
+    t = np.asarray(t, F32)
+    with np.errstate(invalid="ignore"):
+        fin = np.isfinite(t)
+        return {"[32767, 32768)": (t >= 32767) & (t < 32768), "[32768, 65536)": (t >= 32768) & (t < 65536),
+                "(-32769, -32768)": (t > -32769) & (t < -32768), "(-2^31, -32769]": (t <= -32769) & (t > -2.0 ** 31),
+                "|t| >= 2^31": fin & (np.abs(t) >= 2.0 ** 31), "+inf": t == np.inf, "-inf": t == -np.inf, "nan": np.isnan(t)}
+
+
+def _amplitude(G, tau, name):
+    """The first fp32 amplitude, growing in magnitude from the one that puts the largest tap of G at t = tau, at which some
+    product fl(fl(G * A) * 32768) lies in class `name` (a nextafter search on the model's own arithmetic)."""
+    gmax = G[np.argmax(np.abs(G))]
+    A = F32(tau / 32768.0 / float(gmax))
+    for _ in range(1 << 16):
+        if t_classes((G * A).astype(F32) * F32(32768))[name].any():
+            return A
+        A = np.nextafter(A, F32(np.copysign(np.inf, A)))
+    raise AssertionError(f"no amplitude puts a product into {name}")
+
+
+EDGE_IMPULSES = (("[32767, 32768)", 32766.9, False), ("[32768, 65536)", 32767.9, True), ("(-32769, -32768)", -32767.9, True),
+                 ("(-2^31, -32769]", -32768.9, False), ("|t| >= 2^31", 2147483000.0, False), (None, 3e38, False),
+                 (None, np.inf, False), (None, -np.inf, True), (None, np.nan, False))
+
+
+def cast_edge_rows(B, L, g):
+    """-> o [frames + 1, B, 480] fp32: 48 kHz rows of nine well-separated single samples per stream (at least 2D + L apart, so that
+    no two reach the same output), `frames` frames and one frame of zeros.  In EDGE_IMPULSES' order: five amplitudes found by _amplitude
+    for the five finite classes of t_classes — (class, starting t, on a multiple of L?) — then 3e38 (z finite, z * 32768 infinite,
+    both signs), +inf off the multiples of L (+inf and -inf), -inf ON a multiple of L (inf * 0: NaN) and a NaN.  Row r is shifted
+    by rL samples and takes another phase.  The last sample lies in the last 6L samples of the last frame before the zeros, so its
+    window reaches 2D samples into the frame of zeros through the tail."""
+    g = np.asarray(g, F32)
+    D = T * L
+    S = 2 * D + 2 * L
+    n_imp = len(EDGE_IMPULSES)
+    frames = -(-((n_imp - 1) * S + 6 * L) // FRAME48)
+    o = np.zeros((B, (frames + 1) * FRAME48), F32)
+    for r in range(B):
+        for k, (name, tau, on_multiple) in enumerate(EDGE_IMPULSES):
+            phase = 0 if on_multiple else 1 + (r + k) % (L - 1)
+            i = frames * FRAME48 - 6 * L - (n_imp - 1 - k) * S + r * L + phase
+            G = g[np.arange(1, 2 * D)[(np.arange(1, 2 * D) + i) % L == 0]]        # the taps Lm - i that sample i meets
+            o[r, i] = _amplitude(G, tau, name) if name else tau
+    return np.ascontiguousarray(o.reshape(B, frames + 1, FRAME48).transpose(1, 0, 2))
+
+
 def delay_samples(rate):
     return ENGINE_DELAY // factor(rate) + 2 * T
 

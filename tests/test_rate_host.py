@@ -110,6 +110,35 @@ def test_state_record_check(rate):
     assert api.rate_state_check(good[:12] + struct.pack("<i", 48000) + good[16:], rate) == api.SS_BAD_RATE
 
 
+@pytest.mark.parametrize("rate", list(TABLE))
+def test_cast_edge_rows_cover_every_class_of_the_down_cast(rate):
+    """The precondition of tests/test_gpu_cast_edges.py's rate tests, from the numpy model and the library's taps alone: in every
+    row of rate_model.cast_edge_rows the model's own t = z * 32768 holds a value of every class of rate_model.t_classes, the
+    samples are at least 2D + L apart, and the frame of zeros behind them still carries NaN through the tail."""
+    L = TABLE[rate][0]
+    D = api.RATE_TAPS * L
+    g = api.rate_taps(rate, True)
+    for B in (5, 1):
+        o = rmod.cast_edge_rows(B, L, g)
+        assert o.shape[1:] == (B, 480) and not o[-1].any() and o.shape[0] <= 6
+        flat = o.transpose(1, 0, 2).reshape(B, -1)
+        for r in range(B):
+            at = np.flatnonzero(flat[r])
+            assert at.size == len(rmod.EDGE_IMPULSES) and np.diff(at).min() >= 2 * D + L
+            assert at[-1] >= flat.shape[1] - 480 - 2 * D, "the last sample's window must reach the frame of zeros"
+        down = rmod.Down(B, L, g)
+        with np.errstate(all="ignore"):
+            z = np.stack([down(f) for f in o])
+            t = z * np.float32(32768)
+        for name, mask in rmod.t_classes(t).items():
+            per_row = mask.sum(axis=(0, 2))
+            print(f"{rate} Hz B={B} {name}: {per_row.tolist()}")
+            assert np.all(per_row >= 1), name
+        assert np.isnan(z[-1]).any(axis=1).all() and np.isfinite(z[-1]).any(axis=1).all()
+        # NaN is 0 in both casts, and the wrap gives 0 for whatever is not finite
+        assert (rmod.to_i16(z, True)[np.isnan(z)] == 0).all() and (rmod.to_i16(z, False)[~np.isfinite(t)] == 0).all()
+
+
 def test_design_and_record_check_under_sanitizers(tmp_path):
     """tests/c/rate_sanitize.cpp = pn_rate_design.h (+ pn_model.cpp for the error string) built WITHOUT HIP by plain g++ with
     -fsanitize=address,undefined: the design for each rate into exactly-sized tables, the record check over every truncation
