@@ -12,7 +12,8 @@
  *  (2) The batched interface the GPU needs: one context = B independent 48 kHz streams advanced
  *      in lock-step, one 10 ms frame (480 samples) per stream per call.  Plain pointers and
  *      sizes only; device pointers are raw HIP device addresses (e.g. torch's data_ptr()).
- *      8, 16 and 24 kHz streams go through a pn_rate beside the context (the rate converter, below).
+ *      8, 16 and 24 kHz streams go through a pn_rate beside the context (the rate converter, below), all at one rate or, with
+ *      a mixed converter, each stream at its own, 48 kHz included.
  *
  * All functions are thread-compatible per context; one context belongs to one HIP device.
  * Errors: functions returning int give 0 on success, <0 on failure; pn_last_error() returns a
@@ -402,8 +403,8 @@ int pn_featgen_run_files(int device, int n_jobs, const char *const *speech_paths
 /* The engine runs at 48 kHz; a pn_rate is an object BESIDE a context (like pn_featgen: it adds nothing to the context's state)
    that converts all of the context's streams from ONE low rate up to 48 kHz in front of a frame and back down behind it, on the
    GPU (csrc/pn_rate.hip).  rate_hz is 8000, 16000 or 24000 — L = 48000 / rate_hz = 6, 3, 2; any other rate is refused.  A caller
-   with mixed rates uses one context (and converter) per rate: packed weights are shared between contexts of one model, device and
-   mode, so this costs state memory only.  A frame is still 10 ms: n = 480 / L = 80 | 160 | 240 samples per stream.
+   with mixed rates uses a MIXED converter (pn_rate_create_mixed, below: a rate per stream, 48000 included, in one context), or
+   one context and converter per rate.  A frame is still 10 ms: n = 480 / L = 80 | 160 | 240 samples per stream.
 
    Arithmetic (fixed, so that a float32 model reproduces it bit for bit: tests/rate_model.py).  T = PN_RATE_TAPS = 16, D = T * L.
    Prototype filter, k = -D..D:  h[k] = sinc(k / L) * I0(8 * sqrt(1 - (k / D)^2)) / I0(8)  (a Kaiser-windowed sinc, beta = 8),
@@ -425,8 +426,8 @@ int pn_featgen_run_files(int device, int n_jobs, const char *const *speech_paths
    trunc(z * 32768) wrapped to 16 bit, or saturated while pn_ctx_set_output_saturate is on.  The frame report (pn_ctx_set_report)
    stays that of the 48 kHz signal inside the engine: 480 samples per frame, the engine's own 2880-sample delay, levels before the
    down-conversion.
-   NOT provided: the pipelined pn_submit_host_* path, device-side record export / import, per-stream rates inside one context,
-   other rates, profiling families of the two kernels.
+   NOT provided: the pipelined pn_submit_host_* path, device-side record export / import, other rates, profiling families of the
+   kernels.
 
    Host only, needing no GPU:
    pn_rate_frame_samples: n, -1 for a refused rate.  pn_rate_delay_samples: the table above, -1.  pn_rate_taps: the fp32 table,
@@ -482,6 +483,53 @@ int pn_rate_process_host_i16(pn_rate *r, const int16_t *h_in, int16_t *h_out, fl
    moves a narrowband stream between slots, contexts, devices and processes bit for bit. */
 int pn_rate_export_streams_host(pn_rate *r, const int32_t *ids, int n, void *h_records);
 int pn_rate_import_streams_host(pn_rate *r, const int32_t *ids, int n, const void *h_records);
+
+/* ---- mixed rates: 8, 16, 24 and 48 kHz streams in ONE context ---------------------------------------------------------------- */
+/* A mixed converter IS a pn_rate — every entry point above takes it — whose streams each have a rate of their own out of 8000,
+   16000, 24000 and 48000 (L = 6, 3, 2, 1), so that any free slot of a context takes the next call whatever its rate.  The rate
+   per stream lives in the converter; pn_ctx, its state and its records know nothing of it.  It differs from a single-rate
+   converter in two things only:
+   Rows.  Low-rate rows are [n_streams][PN_RATE_MIXED_ROW = 480] samples (1920 bytes in float, 960 in int16) whatever the rates,
+   because a slot's rate may change at any time; stream s at rate R uses the first n_s = pn_rate_mixed_frame_samples(R) samples
+   of its row.  The rest of an input row is ignored, the rest of an output row is left untouched (also by the _host forms).  Base
+   pointers stay 16-byte aligned.
+   A factor per stream.  For L = 6, 3, 2 the arithmetic is exactly the one above for that rate — same taps, same order, same tails
+   — so a stream gives bit for bit what it gives in a single-rate converter of its rate.  L = 1 is a copy: float rows carry the
+   input's bits up and down; int16 is (float)v / 32768 on the way up and t = o * 32768 through the wrapping or saturating cast
+   (pn_ctx_set_output_saturate) on the way down.  A 48000 stream has no tails and no record; its delay is the engine's 2880 samples.
+
+       rate_hz    L    n_s   delay (samples)
+        8000      6    80        512
+       16000      3   160        992
+       24000      2   240       1472
+       48000      1   480       2880
+
+   Host only, needing no GPU: pn_rate_mixed_frame_samples and pn_rate_mixed_delay_samples, the table above, -1 for another rate
+   (pn_rate_frame_samples(48000) and the rest of the single-rate surface keep refusing 48000); pn_rate_mixed_rates_check: 0 when
+   rates_hz[0..n) are all out of the four, else -1 with pn_last_error naming the first bad index.
+   pn_rate_create_mixed: rates_hz [n_streams] (NULL: all 48000); a bad rate returns NULL.  pn_rate_is_mixed: 1 | 0.
+   pn_rate_row_samples: samples between two rows at the low rate — n for a single-rate converter, 480 for a mixed one.
+   pn_rate_set_stream_rates: streams ids[i] (distinct, in range) continue at rates_hz[i] (out of the four); anything else refuses
+   the call with -1, nothing changed or launched; n == 0 is a no-op; refused on a single-rate converter.  Asynchronous on the
+   context's stream and ordered exactly like pn_rate_reset_streams: frames submitted before it run at the old rates, frames after
+   it at the new ones; the caller may reuse its arrays on return.  It ZEROES both tails of the listed streams — a rate change is a
+   new call, and setting a stream's current rate equals pn_rate_reset_streams — and does not touch the context: a caller whose
+   slot starts a new call also calls pn_ctx_reset_streams.  pn_rate_reset and pn_rate_reset_streams keep the rates.
+   pn_rate_get_stream_rates: the rates as last set, h_rates [n_streams]; a single-rate converter gives its rate for every stream.
+   Records: format, version and sizes are those above, so streams move between mixed and single-rate converters.  One export or
+   import call on a mixed converter handles ONE rate: the listed streams must share a rate R != 48000 now, and the records are
+   [n][pn_rate_state_bytes(R)].  Refused all-or-nothing, nothing written or launched: a list spanning two rates; a 48000 slot (it
+   has no converter state to move); on import, a record whose header names another rate than the slot's (PN_SS_BAD_RATE) — the
+   importing caller sets the slot's rate first. */
+#define PN_RATE_MIXED_ROW 480
+int pn_rate_mixed_frame_samples(int rate_hz);
+int pn_rate_mixed_delay_samples(int rate_hz);
+int pn_rate_mixed_rates_check(const int32_t *rates_hz, int n);
+pn_rate *pn_rate_create_mixed(pn_ctx *ctx, const int32_t *rates_hz);
+int pn_rate_is_mixed(const pn_rate *r);
+int pn_rate_row_samples(const pn_rate *r);
+int pn_rate_set_stream_rates(pn_rate *r, const int32_t *ids, int n, const int32_t *rates_hz);
+int pn_rate_get_stream_rates(const pn_rate *r, int32_t *h_rates);
 
 const char *pn_last_error(void);
 const char *pn_version(void);

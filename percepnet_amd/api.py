@@ -20,6 +20,8 @@ SS_OK, SS_BAD_MAGIC, SS_BAD_VERSION, SS_BAD_SIZE, SS_BAD_MODEL, SS_BAD_ARG = 0, 
 SS_BAD_RATE = -6          # pn_rate_state_check: a record of another rate
 # batched rate converter (include/percepnet_hip.h pn_rate): the rates it takes, taps per phase
 RATES = (8000, 16000, 24000)
+MIXED_RATES = (8000, 16000, 24000, 48000)     # the rate of a STREAM of a mixed converter (pn_rate_create_mixed); 48000 is a copy
+RATE_MIXED_ROW = 480                          # PN_RATE_MIXED_ROW: samples between two low-rate rows of a mixed converter
 RATE_TAPS = 16
 # per-stream frame report (include/percepnet_hip.h pn_ctx_set_report): one record of PN_REPORT_WORDS 32-bit words per stream
 REPORT_WORDS = 8
@@ -136,6 +138,16 @@ def load_library():
             getattr(L, name).argtypes = [_vp, _vp, _vp, _vp, _vp, ctypes.c_int]
         for name in ("pn_rate_export_streams_host", "pn_rate_import_streams_host"):
             getattr(L, name).argtypes = [_vp, _vp, ctypes.c_int, _vp]
+    if hasattr(L, "pn_rate_create_mixed"):
+        for name in ("pn_rate_mixed_frame_samples", "pn_rate_mixed_delay_samples"):
+            getattr(L, name).argtypes = [ctypes.c_int]
+        L.pn_rate_mixed_rates_check.argtypes = [_vp, ctypes.c_int]
+        L.pn_rate_create_mixed.restype = _vp
+        L.pn_rate_create_mixed.argtypes = [_vp, _vp]
+        for name in ("pn_rate_is_mixed", "pn_rate_row_samples"):
+            getattr(L, name).argtypes = [_vp]
+        L.pn_rate_set_stream_rates.argtypes = [_vp, _vp, ctypes.c_int, _vp]
+        L.pn_rate_get_stream_rates.argtypes = [_vp, _vp]
     L.pn_ctx_debug_copy.restype = ctypes.c_longlong
     L.pn_ctx_debug_copy.argtypes = [_vp, ctypes.c_int, _vp, ctypes.c_longlong]
     L.pn_ctx_set_profiling.argtypes = [_vp, ctypes.c_int]
@@ -474,6 +486,16 @@ def rate_state_check(record, rate_hz):
     return int(L.pn_rate_state_check(b.ctypes.data if b.size else None, b.size, int(rate_hz)))
 
 
+def rate_mixed_frame_samples(rate_hz):
+    """Samples per 10 ms frame of a stream of a mixed converter: 80 | 160 | 240 | 480; -1 for any other rate (host only)."""
+    return int(load_library().pn_rate_mixed_frame_samples(int(rate_hz)))
+
+
+def rate_mixed_delay_samples(rate_hz):
+    """Input-to-output delay in samples at rate_hz of a stream of a mixed converter: 512 | 992 | 1472 | 2880; -1 (host only)."""
+    return int(load_library().pn_rate_mixed_delay_samples(int(rate_hz)))
+
+
 class RateConverter:
     """8, 16 or 24 kHz streams through a 48 kHz Context (pn_rate): a converter beside `ctx` for all of its streams at ONE rate.
     It borrows the context (device, n_streams, HIP stream): close the converter before the context."""
@@ -591,6 +613,94 @@ class RateConverter:
         rec = np.ascontiguousarray(records, dtype=np.uint8)
         if rec.size != n * self.state_bytes:
             raise PercepNetError(f"{rec.size} record bytes for {n} streams (a record at {self.rate} Hz has {self.state_bytes})")
+        self._chk(self.L.pn_rate_import_streams_host(self.h, a.ctypes.data, n, rec.ctypes.data))
+
+
+class MixedRateConverter(RateConverter):
+    """8, 16, 24 and 48 kHz streams in ONE Context (pn_rate_create_mixed): a RateConverter with a rate per stream.  Every method
+    of RateConverter works on rows of RATE_MIXED_ROW = 480 samples, of which stream s uses the first rate_mixed_frame_samples(its
+    rate); the rest of an input row is ignored and the rest of an output row is left as it was (the host entry points return it
+    as zeros).  rates: one per stream, or None for all 48000."""
+
+    def __init__(self, ctx, rates=None):
+        self.L = ctx.L
+        self.ctx = ctx
+        self.rate = None
+        self.n_streams = ctx.n_streams
+        a = None if rates is None else np.ascontiguousarray(np.asarray(rates, dtype=np.int32).ravel())
+        if a is not None and a.size != self.n_streams:
+            raise PercepNetError(f"{a.size} rates for {self.n_streams} streams")
+        self.h = self.L.pn_rate_create_mixed(ctx.h, a.ctypes.data if a is not None else None)
+        if not self.h:
+            raise PercepNetError(_err(self.L))
+        self.frame = int(self.L.pn_rate_row_samples(self.h))
+
+    def set_stream_rates(self, ids, rates):
+        """Streams `ids` continue at `rates` from the next frame on, with zeroed converter tails (pn_rate_set_stream_rates):
+        asynchronous, ordered like reset_streams.  A slot that starts a new call also needs Context.reset_streams."""
+        a, n = self._ids(ids)
+        r = np.ascontiguousarray(np.asarray(rates, dtype=np.int32).ravel())
+        if r.size != n:
+            raise PercepNetError(f"{r.size} rates for {n} streams")
+        self._chk(self.L.pn_rate_set_stream_rates(self.h, a.ctypes.data, n, r.ctypes.data))
+
+    def stream_rates(self):
+        """-> int32 [n_streams]: the rates as last set (pn_rate_get_stream_rates)."""
+        r = np.empty(self.n_streams, np.int32)
+        self._chk(self.L.pn_rate_get_stream_rates(self.h, r.ctypes.data))
+        return r
+
+    def _host(self, name, frame, dtype, want_gr):
+        frame = np.ascontiguousarray(frame, dtype=dtype).reshape(self.n_streams, self.frame)
+        out = np.zeros_like(frame)
+        gr = np.empty((self.n_streams, 68), np.float32) if want_gr else None
+        self._chk(getattr(self.L, name)(self.h, frame.ctypes.data, out.ctypes.data, gr.ctypes.data if want_gr else None))
+        return out, gr
+
+    def run_pcm(self, pcm):
+        """percepnet_run --rates semantics: pcm = one int16 array per stream at that stream's rate -> a list of int16 arrays,
+        stream s with (frames_s - 1) * n_s samples (first output frame and partial tail dropped).  Streams may differ in length:
+        one that has ended is fed silence."""
+        if len(pcm) != self.n_streams:
+            raise PercepNetError(f"{len(pcm)} arrays for {self.n_streams} streams")
+        pcm = [np.ascontiguousarray(p, dtype=np.int16).ravel() for p in pcm]
+        ns = [rate_mixed_frame_samples(r) for r in self.stream_rates()]
+        frames = [p.size // n for p, n in zip(pcm, ns)]
+        out = [np.zeros(max(f - 1, 0) * n, np.int16) for f, n in zip(frames, ns)]
+        row = np.zeros((self.n_streams, self.frame), np.int16)
+        for t in range(max(frames, default=0)):
+            row[:] = 0
+            for s, (p, n) in enumerate(zip(pcm, ns)):
+                if t < frames[s]:
+                    row[s, :n] = p[t * n:(t + 1) * n]
+            o, _ = self.process_i16(row, want_gr=False)
+            for s, n in enumerate(ns):
+                if 0 < t < frames[s]:
+                    out[s][(t - 1) * n:t * n] = o[s, :n]
+        return out
+
+    def _record_rate(self, ids):
+        a, n = self._ids(ids)
+        rates = self.stream_rates()
+        ok = n > 0 and a.min() >= 0 and a.max() < self.n_streams
+        return a, n, (int(rates[a[0]]) if ok else 0)
+
+    def export_streams(self, ids):
+        """-> uint8 [n, rate_state_bytes(R)]: the converter state of the streams `ids`, which share the rate R != 48000."""
+        a, n, rate = self._record_rate(ids)
+        rec = np.empty((n, rate_state_bytes(rate) if rate in RATES else 16), np.uint8)
+        self._chk(self.L.pn_rate_export_streams_host(self.h, a.ctypes.data, n, rec.ctypes.data))
+        return rec
+
+    def import_streams(self, ids, records):
+        """Records of rate R into the distinct streams `ids`, all of which run at R now (set_stream_rates first); all or nothing."""
+        a, n, rate = self._record_rate(ids)
+        rec = np.ascontiguousarray(records, dtype=np.uint8)
+        want = rate_state_bytes(rate) if rate in RATES else 0
+        if n and want and rec.size != n * want:
+            raise PercepNetError(f"{rec.size} record bytes for {n} streams (a record at {rate} Hz has {want})")
+        if n and not want:                     # (a 48000 slot or a bad id: the library words the refusal; it reads no record)
+            rec = np.zeros(16, np.uint8)
         self._chk(self.L.pn_rate_import_streams_host(self.h, a.ctypes.data, n, rec.ctypes.data))
 
 

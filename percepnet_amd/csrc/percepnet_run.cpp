@@ -5,7 +5,7 @@
 // dropped, main.cpp:32-33); with a single pair ./feature_test.raw gets 68 floats per frame.
 //
 //   percepnet_run [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N]
-//                 [--rate 8000|16000|24000] [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
+//                 [--rate 8000|16000|24000 | --rates R0,R1,..] [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
 //                 in0.pcm out0.pcm [in1.pcm out1.pcm ...]
 //
 // --rate R: the files are raw int16 at R Hz instead of 48 kHz, in frames of n = 480 * R / 48000 samples (80 | 160 | 240): a rate
@@ -14,6 +14,12 @@
 // the synchronous pn_rate_process_host_i16 (the converter has no pipelined path), --report reads each frame's records after
 // it (pn_ctx_read_report) — its figures stay those of the 48 kHz signal inside the engine — and the converter's slots are reset
 // with the context's.  Without --rate nothing of this runs.
+//
+// --rates R0,R1,..: one rate per pair out of 8000, 16000, 24000 and 48000 (exclusive with --rate): a MIXED converter beside each
+// context (pn_rate_create_mixed), whose shard's slice of the list goes to its device.  Pair i is read and written in frames of
+// its own n = 480 * Ri / 48000 samples; the pinned rows are 480 samples whatever the rate; the per-pair contract is the one
+// above.  With --slots a slot taken over by a pair of another rate continues at that rate (pn_rate_set_stream_rates for the
+// restart list, where --rate calls pn_rate_reset_streams), followed by the context's reset as always.
 //
 // --atten-lim DB: every stream takes out at most DB dB of noise (pn_ctx_set_atten_limit; 0 = the input, delayed; default: no
 // limit).  A slot reset clears a stream's limit (a reset slot is a new call), so the limit is set again on every reset slot.
@@ -57,7 +63,8 @@ struct ShardRes {
   // one of three rotating pinned buffer sets; file[s] = the output file the frame of slot s belongs to (NULL: slot idle),
   // skip[s] = that frame is the pair's first output frame, which main.cpp:37 drops
   // (--report) rep: the frame's report records, pair[s]: the pair the frame of slot s belongs to
-  struct Slot { int16_t *in = NULL, *out = NULL; float *gr = NULL; uint32_t *rep = NULL; std::vector<FILE *> file; std::vector<char> skip, last; std::vector<int> pair; } slot[3];
+  // fs[s]: samples of that frame (the pair's own frame size; differs between slots only with --rates)
+  struct Slot { int16_t *in = NULL, *out = NULL; float *gr = NULL; uint32_t *rep = NULL; std::vector<FILE *> file; std::vector<char> skip, last; std::vector<int> pair; std::vector<size_t> fs; } slot[3];
   ~ShardRes() {
     for (auto &sl : slot) { pn_host_free(sl.in); pn_host_free(sl.out); pn_host_free(sl.gr); pn_host_free(sl.rep); }
     for (FILE *f : fin) if (f) fclose(f);
@@ -77,11 +84,15 @@ static bool g_numa = true, g_verbose = false;
 static float g_atten_lim = INFINITY;                  // --atten-lim: dB for every stream (inf: not set)
 static bool g_saturate = false, g_report = false;     // --saturate, --report
 static int g_rate = 0;                                // --rate: the files' sample rate (0: 48 kHz, no converter)
+static std::vector<int32_t> g_rates;                  // --rates: one rate per pair (empty: not given), a mixed converter
 // --report: what a pair's written frames add up to (one report record = PN_REPORT_WORDS words, include/percepnet_hip.h)
 struct PairStat { long frames = 0; long long clipped = 0; float peak = 0.f; double e_in = 0, e_out = 0; };
 static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, int postfilter, bool tap, int n_slots) {
   const int P = sh->count, B = n_slots > 0 && n_slots < P ? n_slots : P;
-  const size_t FS = g_rate ? (size_t)pn_rate_frame_samples(g_rate) : PN_FRAME_SIZE;     // samples per frame in the files
+  const bool mixed = !g_rates.empty();
+  const int32_t *pair_rate = mixed ? g_rates.data() + sh->first : NULL;                // --rates: this shard's slice
+  const size_t FS = mixed ? PN_RATE_MIXED_ROW : g_rate ? (size_t)pn_rate_frame_samples(g_rate) : PN_FRAME_SIZE;     // samples per pinned row
+  auto pair_fs = [&](int pair) { return mixed ? (size_t)pn_rate_mixed_frame_samples(pair_rate[pair]) : FS; };       // ... per frame in a pair's files
   auto fail = [&](int rc, const std::string &msg) { sh->rc = rc; sh->err = msg; };
   ShardRes R;
   // this thread owns the device from here on: run on the CPUs of the GPU's NUMA node BEFORE the context and the pinned
@@ -95,6 +106,7 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
   pn_ctx *cx = R.cx;
   if (!cx) return fail(3, std::string("pn_ctx_create: ") + pn_last_error());
   if (g_rate && !(R.rt = pn_rate_create(cx, g_rate))) return fail(3, std::string("pn_rate_create: ") + pn_last_error());
+  if (mixed && !(R.rt = pn_rate_create_mixed(cx, pair_rate))) return fail(3, std::string("pn_rate_create_mixed: ") + pn_last_error());   // slot s starts with pair s
   pn_rate *rt = R.rt;
   if (postfilter) pn_ctx_set_postfilter(cx, 1);
   if ((g_saturate && pn_ctx_set_output_saturate(cx, 1)) || (g_report && pn_ctx_set_report(cx, 1))) return fail(3, pn_last_error());
@@ -134,14 +146,14 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
     sl.gr = (float *)pn_host_alloc((size_t)B * 68 * sizeof(float));
     if (g_report) sl.rep = (uint32_t *)pn_host_alloc((size_t)B * PN_REPORT_WORDS * sizeof(uint32_t));
     if (!sl.in || !sl.out || !sl.gr || (g_report && !sl.rep)) return fail(5, pn_last_error());
-    sl.file.assign(B, NULL); sl.skip.assign(B, 0); sl.last.assign(B, 0); sl.pair.assign(B, 0);
+    sl.file.assign(B, NULL); sl.skip.assign(B, 0); sl.last.assign(B, 0); sl.pair.assign(B, 0); sl.fs.assign(B, FS);
   }
   std::vector<char> first(B, 1);
   auto flush = [&](Slot &sl) {                       // main.cpp:36-38 for every stream that supplied this frame
     for (int s = 0; s < B; s++) {
       if (!sl.file[s]) continue;
       if (ftap) fwrite(&sl.gr[(size_t)s * 68], sizeof(float), 68, ftap);
-      if (!sl.skip[s]) fwrite(&sl.out[(size_t)s * FS], sizeof(int16_t), FS, sl.file[s]);
+      if (!sl.skip[s]) fwrite(&sl.out[(size_t)s * FS], sizeof(int16_t), sl.fs[s], sl.file[s]);
       if (g_report) {
         PairStat &ps = stat[sl.pair[s]];
         if (!sl.skip[s]) {
@@ -160,16 +172,16 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
       if (sl.last[s]) { fclose(sl.file[s]); }        // the pair's last frame has been written: its output file is complete
     }
   };
-  std::vector<int32_t> restart;
+  std::vector<int32_t> restart, restart_rates;
   int n_alive = B;
   long t = 0;
   for (;; t++) {
     Slot &sl = slot[t % 3];
-    restart.clear();
+    restart.clear(); restart_rates.clear();
     for (int s = 0; s < B; s++) {
       int16_t *x = sl.in + (size_t)s * FS;
       sl.file[s] = NULL; sl.skip[s] = 0; sl.last[s] = 0;
-      if (fin[s] && fread(x, sizeof(int16_t), FS, fin[s]) != FS) {
+      if (fin[s] && fread(x, sizeof(int16_t), pair_fs(cur_pair[s]), fin[s]) != pair_fs(cur_pair[s])) {
         // this pair is finished (partial tail dropped, main.cpp:32-33): mark the frame it supplied last as its final one
         fclose(fin[s]); fin[s] = NULL;
         Slot &prev = slot[(t + 2) % 3];                // = frame t - 1
@@ -177,19 +189,24 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
         fout[s] = NULL;
         while (next_pair < P) {                        // the slot starts over with the next waiting pair, from this frame on
           if (!open_pair(s)) return;
-          if (fread(x, sizeof(int16_t), FS, fin[s]) == FS) { restart.push_back(s); first[s] = 1; break; }
+          if (fread(x, sizeof(int16_t), pair_fs(cur_pair[s]), fin[s]) == pair_fs(cur_pair[s])) {
+            restart.push_back(s); first[s] = 1;
+            if (mixed) restart_rates.push_back(pair_rate[cur_pair[s]]);
+            break;
+          }
           fclose(fin[s]); fin[s] = NULL; fclose(fout[s]); fout[s] = NULL;       // shorter than one frame: an empty output, next pair
         }
         if (!fin[s]) n_alive--;
       }
-      if (fin[s]) { sl.file[s] = fout[s]; sl.skip[s] = first[s]; first[s] = 0; sl.pair[s] = cur_pair[s]; }
+      if (fin[s]) { sl.file[s] = fout[s]; sl.skip[s] = first[s]; first[s] = 0; sl.pair[s] = cur_pair[s]; sl.fs[s] = pair_fs(cur_pair[s]); }
       else memset(x, 0, FS * sizeof(int16_t));
     }
     if (n_alive == 0) break;
     if (!restart.empty() && (pn_ctx_reset_streams(cx, restart.data(), (int)restart.size()) ||
-                             (rt && pn_rate_reset_streams(rt, restart.data(), (int)restart.size())) ||
+                             (rt && (mixed ? pn_rate_set_stream_rates(rt, restart.data(), (int)restart.size(), restart_rates.data())
+                                           : pn_rate_reset_streams(rt, restart.data(), (int)restart.size()))) ||
                              set_limit(restart.data(), (int)restart.size()))) return fail(5, pn_last_error());
-    if (rt) {                                          // --rate: one synchronous frame, then its report records
+    if (rt) {                                          // --rate, --rates: one synchronous frame, then its report records
       if (pn_rate_process_host_i16(rt, sl.in, sl.out, sl.gr)) return fail(5, pn_last_error());
       if (g_report && pn_ctx_read_report(cx, sl.rep)) return fail(5, pn_last_error());
     } else {
@@ -224,6 +241,17 @@ int main(int argc, char **argv) {
       g_rate = atoi(argv[++ai]);
       if (pn_rate_frame_samples(g_rate) < 0) { fprintf(stderr, "--rate: expected 8000, 16000 or 24000, got '%s'\n", argv[ai]); return 1; }
     }
+    else if (!strcmp(argv[ai], "--rates") && ai + 1 < argc) {       // one rate per pair, 48000 allowed: a mixed converter beside each context
+      const char *v = argv[++ai];
+      for (const char *q = v; ; ) {
+        char *end = NULL;
+        const long r = strtol(q, &end, 10);
+        if (end == q || (*end && *end != ',') || pn_rate_mixed_frame_samples((int)r) < 0) { fprintf(stderr, "--rates: expected a comma-separated list of 8000, 16000, 24000 or 48000, got '%s'\n", v); return 1; }
+        g_rates.push_back((int32_t)r);
+        if (!*end) break;
+        q = end + 1;
+      }
+    }
     else if (!strcmp(argv[ai], "--no-numa")) g_numa = false;         // leave the host threads' CPU affinity alone
     else if (!strcmp(argv[ai], "--verbose")) g_verbose = true;       // one line per device: its NUMA binding
     else if (!strcmp(argv[ai], "--slots") && ai + 1 < argc) n_slots = atoi(argv[++ai]);   // concurrent streams per device: pairs queue for them
@@ -239,10 +267,12 @@ int main(int argc, char **argv) {
   if (devices.empty()) devices.push_back(0);
   const int nfiles = argc - ai;
   if (nfiles < 2 || (nfiles & 1)) {
-    fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N] [--rate 8000|16000|24000] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv[0]);
+    fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N] [--rate 8000|16000|24000 | --rates R0,R1,..] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv[0]);
     return 1;
   }
   const int B = nfiles / 2;
+  if (g_rate && !g_rates.empty()) { fprintf(stderr, "--rate and --rates exclude each other\n"); return 1; }
+  if (!g_rates.empty() && (int)g_rates.size() != B) { fprintf(stderr, "--rates: %d rates for %d pairs (one per pair)\n", (int)g_rates.size(), B); return 1; }
   pn_model *m = NULL;
   if (model_path) { FILE *f = fopen(model_path, "rb"); if (f) { m = pn_model_from_file(f); fclose(f); } }
   else if (&percepnet_model_orig) m = pn_model_from_rnnmodel(&percepnet_model_orig);

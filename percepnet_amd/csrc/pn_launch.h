@@ -81,7 +81,14 @@ void pn_launch_outstage(hipStream_t st, int n_streams, const float *o, const PnD
 // device.  -1 (pn_set_error) without launching for another L.  records: state record i <-> the tails of stream d_ids[i]
 int pn_launch_rate_up(hipStream_t st, int factor, int is_i16, int n_rows, const int *d_ids, const void *in, float *out48, float *tail, const float *taps);
 int pn_launch_rate_down(hipStream_t st, int factor, int is_i16, int n_rows, const int *d_ids, const float *in48, void *out, int saturate, float *tail, const float *taps);
-void pn_launch_rate_records(hipStream_t st, int factor, int rate_hz, const int *d_ids, int n, float *tail_up, float *tail_down, void *rec, int scatter);
+// td_stride: words between the down tails of two streams (2 * 16 * factor in a single-rate converter, 192 in a mixed one)
+void pn_launch_rate_records(hipStream_t st, int factor, int rate_hz, const int *d_ids, int n, float *tail_up, float *tail_down, int td_stride, void *rec, int scatter);
+// the mixed converter's kernels: rows of PN_RATE_MIXED_ROW = 480 samples at the low rate too, stream s runs at d_factors[s] in {6, 3, 2, 1}
+// (1: a copy, no tail); tail rows [.][32] and [.][192]; taps: the tables of factor 6, 3, 2 one behind the other (193 + 97 + 65 words).
+// set_factors: d_factors[d_ids[i]] = d_vals[i] for i < n (distinct ids)
+int pn_launch_rate_up_mixed(hipStream_t st, int is_i16, int n_rows, const int *d_ids, const int *d_factors, const void *in, float *out48, float *tail, const float *taps);
+int pn_launch_rate_down_mixed(hipStream_t st, int is_i16, int n_rows, const int *d_ids, const int *d_factors, const float *in48, void *out, int saturate, float *tail, const float *taps);
+void pn_launch_rate_set_factors(hipStream_t st, const int *d_ids, const int *d_vals, int n, int *d_factors);
 // ---- the network launchers (pn_nn*.hip) -----------------------------------------------------------------------------------------
 // Device pointers of a layer's biases and weights in the formats of pn_network.h: raw (w, rw), packed fp32 or fp16 planes (wp,
 // rwp), the 16x16x4 packing of a narrow layer (wq)

@@ -1,22 +1,30 @@
-// Host side of the batched rate converter (include/percepnet_hip.h "batched rate converter"): an object BESIDE a context, built
+// Host side of the batched rate converter (include/percepnet_hip.h "batched rate converter" and "mixed rates"): an object BESIDE a context, built
 // like the feature generator — it borrows the context's device, batch size and HIP stream, and owns everything else: the two
 // tap tables on the device, the per-stream tails of the two kernels (pn_rate.hip), the 48 kHz rows between the conversions and
 // the staging rows of the host-buffer path.  Nothing of it lives in pn_ctx, its state table or its records.  Every launch goes
 // to the context's stream, so a converter call is ordered against the context's calls like they are against each other.
 #include "pn_context.h"      // the context it borrows, the launchers, dev_alloc_into, stage_ids, the id rule, host_records_sync
 #include "pn_rate_design.h"
+#include "pn_rate_mixed.h"   // the mixed converter's host rules: the four rates, a rate change, one rate per record call
 #include <string>
 #include <vector>
 
 struct pn_rate {
   pn_ctx *c;                    // borrowed: device, B, stream, the id ring, the saturate setting
-  int rate, L, n, td;           // rate_hz, 48000 / rate, samples per frame, 2D
+  int rate, L, n, td;           // rate_hz, 48000 / rate, samples per row, words per down tail row (2D).  Mixed: 0, 0, 480, 192
   size_t bytes;
-  float *taps_up, *taps_down;   // [2D + 1] h, g
-  float *tail_up, *tail_down;   // [B][32], [B][2D]: the state
+  float *taps_up, *taps_down;   // [2D + 1] h, g.  Mixed: the tables of L = 6, 3, 2 one behind the other
+  float *tail_up, *tail_down;   // [B][32], [B][td]: the state
   float *x48, *y48;             // [B][480]: the engine's input and output rows of a whole frame
   void *io_in, *io_out;         // [B][n] 4-byte words: staging rows of the host-buffer path
   float *io_gr;                 // [B][68]
+  // a mixed converter (pn_rate_create_mixed): the rate of every stream as last set (host), its factor on the device — written
+  // in stream order, so a frame submitted before a rate change still runs at the old rate — and a pinned landing place of the
+  // host-buffer path's output rows, of which only the streams' own samples go on to the caller
+  bool mixed;
+  std::vector<int32_t> rates;   // [B]
+  int *factors;                 // [B] device
+  void *h_rows;                 // [B][480] 4-byte words, pinned
   std::vector<void *> allocs;
 };
 
@@ -42,6 +50,9 @@ extern "C" size_t pn_rate_state_bytes(int rate_hz) {
   return 4 * pn_rate_record_words(L);
 }
 extern "C" int pn_rate_state_check(const void *record, size_t bytes, int rate_hz) { return pn_rate_record_check(record, bytes, rate_hz); }
+extern "C" int pn_rate_mixed_frame_samples(int rate_hz) { return pn_rate_mixed_frame(rate_hz); }
+extern "C" int pn_rate_mixed_delay_samples(int rate_hz) { return pn_rate_mixed_delay(rate_hz); }
+extern "C" int pn_rate_mixed_rates_check(const int32_t *rates_hz, int n) { return pn_rate_mixed_rates_list_check(rates_hz, n); }
 
 // ---- lifecycle ---------------------------------------------------------------------------------------------------------------
 extern "C" void pn_rate_destroy(pn_rate *r) {
@@ -49,6 +60,7 @@ extern "C" void pn_rate_destroy(pn_rate *r) {
   DeviceGuard _dg(r->c->device);
   hipStreamSynchronize(r->c->stream);
   for (void *p : r->allocs) hipFree(p);
+  if (r->h_rows) hipHostFree(r->h_rows);
   delete r;
 }
 
@@ -60,6 +72,7 @@ extern "C" pn_rate *pn_rate_create(pn_ctx *c, int rate_hz) {
   if (!_dg.ok) { pn_set_error("hipSetDevice(%d) failed", c->device); return NULL; }
   pn_rate *r = new pn_rate();
   r->c = c; r->rate = rate_hz; r->L = L; r->n = PN_FRAME / L; r->td = pn_rate_down_tail(L); r->bytes = 0;
+  r->mixed = false; r->factors = NULL; r->h_rows = NULL;
   const size_t B = (size_t)c->B, nt = (size_t)r->td + 1;
   float h[2][PN_RATE_MAX_TAPS];
   auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
@@ -76,6 +89,73 @@ extern "C" pn_rate *pn_rate_create(pn_ctx *c, int rate_hz) {
 fail:
   pn_rate_destroy(r);
   return NULL;
+}
+
+// A converter with a rate per stream: the tap tables of all three filters, tails of the largest size for every stream (a rate
+// change never reallocates), rows of 480 samples.
+extern "C" pn_rate *pn_rate_create_mixed(pn_ctx *c, const int32_t *rates_hz) {
+  if (!c) { pn_set_error("NULL argument"); return NULL; }
+  if (rates_hz && pn_rate_mixed_rates_list_check(rates_hz, c->B)) return NULL;
+  DeviceGuard _dg(c->device);
+  if (!_dg.ok) { pn_set_error("hipSetDevice(%d) failed", c->device); return NULL; }
+  pn_rate *r = new pn_rate();
+  r->c = c; r->rate = 0; r->L = 0; r->n = PN_RATE_MIXED_ROW; r->td = pn_rate_down_tail(PN_RATE_MAX_L); r->bytes = 0;
+  r->mixed = true; r->factors = NULL; r->h_rows = NULL;
+  const size_t B = (size_t)c->B;
+  if (rates_hz) r->rates.assign(rates_hz, rates_hz + B); else r->rates.assign(B, 48000);
+  static const int kL[3] = {6, 3, 2};
+  std::vector<float> h[2];
+  std::vector<int> f(B);
+  for (size_t s = 0; s < B; s++) f[s] = pn_rate_mixed_factor(r->rates[s]);
+  auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
+  for (int down = 0; down < 2; down++)
+    for (int L : kL) {
+      float t[PN_RATE_MAX_TAPS];
+      const int nt = pn_rate_design(L, down, t, PN_RATE_MAX_TAPS);
+      if (nt < 0) goto fail;
+      h[down].insert(h[down].end(), t, t + nt);
+    }
+  if (alloc((void **)&r->taps_up, h[0].size() * 4, false) || alloc((void **)&r->taps_down, h[1].size() * 4, false) ||
+      alloc((void **)&r->tail_up, B * PN_RATE_UP_TAIL * 4, true) || alloc((void **)&r->tail_down, B * r->td * 4, true) ||
+      alloc((void **)&r->x48, B * PN_FRAME * 4, true) || alloc((void **)&r->y48, B * PN_FRAME * 4, true) ||
+      alloc(&r->io_in, B * r->n * 4, true) || alloc(&r->io_out, B * r->n * 4, true) || alloc((void **)&r->io_gr, B * 68 * 4, false) ||
+      alloc((void **)&r->factors, B * sizeof(int), false)) goto fail;
+  if (hipHostMalloc(&r->h_rows, B * r->n * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); r->h_rows = NULL; pn_set_error("rate converter: no pinned memory for %zu bytes", B * r->n * 4); goto fail; }
+  // (synchronous copies: the sources are locals)
+  if (hipMemcpyAsync(r->taps_up, h[0].data(), h[0].size() * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipMemcpyAsync(r->taps_down, h[1].data(), h[1].size() * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipMemcpyAsync(r->factors, f.data(), B * sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipGetLastError(); pn_set_error("rate converter init failed"); goto fail; }
+  return r;
+fail:
+  pn_rate_destroy(r);
+  return NULL;
+}
+extern "C" int pn_rate_is_mixed(const pn_rate *r) { if (!r) { pn_set_error("NULL argument"); return -1; } return r->mixed ? 1 : 0; }
+extern "C" int pn_rate_row_samples(const pn_rate *r) { if (!r) { pn_set_error("NULL argument"); return -1; } return r->n; }
+extern "C" int pn_rate_get_stream_rates(const pn_rate *r, int32_t *h_rates) {
+  if (!r || !h_rates) { pn_set_error("NULL argument"); return -1; }
+  for (int s = 0; s < r->c->B; s++) h_rates[s] = r->mixed ? r->rates[s] : r->rate;
+  return 0;
+}
+// A rate change of the listed streams, asynchronous and ordered like pn_rate_reset_streams: the ids and the new factors go
+// through the context's id ring in one copy, one launch writes the factors, two zero the tails.
+extern "C" int pn_rate_set_stream_rates(pn_rate *r, const int32_t *ids, int n, const int32_t *rates_hz) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (!r->mixed) { pn_set_error("a single-rate converter (%d Hz) keeps its rate: per-stream rates need pn_rate_create_mixed", r->rate); return -1; }
+  if (pn_rate_mixed_set_check(r->c->B, ids, n, rates_hz)) return -1;
+  if (n == 0) return 0;
+  PN_ON_DEVICE(r->c);
+  std::vector<int> f(n);
+  for (int i = 0; i < n; i++) f[i] = pn_rate_mixed_factor(rates_hz[i]);
+  const int *d = stage_ids(r->c, ids, n, f.data(), n);
+  if (!d) return -1;
+  pn_launch_rate_set_factors(r->c->stream, d, d + ((n + 3) & ~3), n, r->factors);
+  pn_launch_zero_rows(r->c->stream, r->tail_up, PN_RATE_UP_TAIL, PN_RATE_UP_TAIL, 1, 0, d, n);
+  pn_launch_zero_rows(r->c->stream, r->tail_down, r->td, r->td, 1, 0, d, n);
+  PN_HIP_CHECK(hipGetLastError());
+  for (int i = 0; i < n; i++) r->rates[ids[i]] = rates_hz[i];
+  return 0;
 }
 
 extern "C" int pn_rate_reset(pn_rate *r) {
@@ -117,12 +197,15 @@ static int rate_aligned(const void *a, const void *b) {
   return 0;
 }
 static int rate_up(pn_rate *r, const void *d_in, int is_i16, float *d_out48, const RateRows &rows) {
-  if (pn_launch_rate_up(r->c->stream, r->L, is_i16, rows.n, rows.d_ids, d_in, d_out48, r->tail_up, r->taps_up)) return -1;
+  if (r->mixed ? pn_launch_rate_up_mixed(r->c->stream, is_i16, rows.n, rows.d_ids, r->factors, d_in, d_out48, r->tail_up, r->taps_up)
+               : pn_launch_rate_up(r->c->stream, r->L, is_i16, rows.n, rows.d_ids, d_in, d_out48, r->tail_up, r->taps_up)) return -1;
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
 static int rate_down(pn_rate *r, const float *d_in48, void *d_out, int is_i16, const RateRows &rows) {
-  if (pn_launch_rate_down(r->c->stream, r->L, is_i16, rows.n, rows.d_ids, d_in48, d_out, r->c->saturate ? 1 : 0, r->tail_down, r->taps_down)) return -1;
+  const int sat = r->c->saturate ? 1 : 0;
+  if (r->mixed ? pn_launch_rate_down_mixed(r->c->stream, is_i16, rows.n, rows.d_ids, r->factors, d_in48, d_out, sat, r->tail_down, r->taps_down)
+               : pn_launch_rate_down(r->c->stream, r->L, is_i16, rows.n, rows.d_ids, d_in48, d_out, sat, r->tail_down, r->taps_down)) return -1;
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -179,9 +262,16 @@ static int rate_process_host(pn_rate *r, const void *h_in, void *h_out, float *h
   const size_t nbytes = (size_t)c->B * r->n * (is_i16 ? 2 : 4);
   PN_HIP_CHECK(hipMemcpyAsync(r->io_in, h_in, nbytes, hipMemcpyHostToDevice, c->stream));
   if (rate_process(r, r->io_in, r->io_out, h_gr ? r->io_gr : NULL, is_i16, false, NULL, 0)) return -1;
-  PN_HIP_CHECK(hipMemcpyAsync(h_out, r->io_out, nbytes, hipMemcpyDeviceToHost, c->stream));
+  // (mixed: the rows land in the converter's pinned buffer, and only each stream's own samples go on to the caller's row)
+  PN_HIP_CHECK(hipMemcpyAsync(r->mixed ? r->h_rows : h_out, r->io_out, nbytes, hipMemcpyDeviceToHost, c->stream));
   if (h_gr) PN_HIP_CHECK(hipMemcpyAsync(h_gr, r->io_gr, (size_t)c->B * 68 * 4, hipMemcpyDeviceToHost, c->stream));
   PN_HIP_CHECK(hipStreamSynchronize(c->stream));
+  if (r->mixed) {
+    const size_t w = is_i16 ? 2 : 4;
+    for (int s = 0; s < c->B; s++)
+      memcpy(static_cast<char *>(h_out) + (size_t)s * r->n * w, static_cast<const char *>(r->h_rows) + (size_t)s * r->n * w,
+             (size_t)(PN_FRAME / pn_rate_mixed_factor(r->rates[s])) * w);
+  }
   return 0;
 }
 extern "C" int pn_rate_process_host_f32(pn_rate *r, const float *h_in, float *h_out, float *h_gr) { return rate_process_host(r, h_in, h_out, h_gr, 0); }
@@ -189,26 +279,33 @@ extern "C" int pn_rate_process_host_i16(pn_rate *r, const int16_t *h_in, int16_t
 
 // ---- state records -----------------------------------------------------------------------------------------------------------
 // Host forms only: synchronous, through the context's host form of a record transfer (host_records_sync).
-static int rate_records_host(pn_rate *r, bool import, const int32_t *ids, int n, void *h_records) {
+// rate: the records' rate — the converter's, or on a mixed one the rate the listed streams share (record_rate)
+static int rate_records_host(pn_rate *r, int rate, bool import, const int32_t *ids, int n, void *h_records) {
   pn_ctx *c = r->c;
-  return host_records_sync(c, import, h_records, (size_t)n * 4 * pn_rate_record_words(r->L), [&](void *d) {
+  const int L = pn_rate_factor(rate);
+  return host_records_sync(c, import, h_records, (size_t)n * 4 * pn_rate_record_words(L), [&](void *d) {
     const int *d_ids = stage_ids(c, ids, n);
     if (!d_ids) return -1;
-    pn_launch_rate_records(c->stream, r->L, r->rate, d_ids, n, r->tail_up, r->tail_down, d, import ? 1 : 0);
+    pn_launch_rate_records(c->stream, L, rate, d_ids, n, r->tail_up, r->tail_down, r->td, d, import ? 1 : 0);
     if (hipGetLastError() != hipSuccess) { pn_set_error(import ? "record scatter launch failed" : "record gather launch failed"); return -1; }
     return 0;
   });
 }
+static int record_rate(const pn_rate *r, const int32_t *ids, int n) { return r->mixed ? pn_rate_mixed_record_rate(r->rates.data(), ids, n) : r->rate; }
 extern "C" int pn_rate_export_streams_host(pn_rate *r, const int32_t *ids, int n, void *h_records) {
   if (!r || n < 0 || (n > 0 && (!ids || !h_records))) { pn_set_error("bad argument"); return -1; }
   if (n == 0) return 0;
   if (pn_ids_check(r->c->B, ids, n, false)) return -1;
-  return rate_records_host(r, false, ids, n, h_records);
+  const int rate = record_rate(r, ids, n);
+  if (rate < 0) return -1;
+  return rate_records_host(r, rate, false, ids, n, h_records);
 }
 extern "C" int pn_rate_import_streams_host(pn_rate *r, const int32_t *ids, int n, const void *h_records) {
   if (!r || n < 0 || (n > 0 && (!ids || !h_records))) { pn_set_error("bad argument"); return -1; }
   if (n == 0) return 0;
   if (pn_ids_check(r->c->B, ids, n, true)) return -1;
-  if (pn_records_check(h_records, n, 4 * pn_rate_record_words(r->L), [&](const void *rec, size_t b) { return pn_rate_record_check(rec, b, r->rate); })) return -1;
-  return rate_records_host(r, true, ids, n, const_cast<void *>(h_records));
+  const int rate = record_rate(r, ids, n);
+  if (rate < 0) return -1;
+  if (pn_records_check(h_records, n, 4 * pn_rate_record_words(pn_rate_factor(rate)), [&](const void *rec, size_t b) { return pn_rate_record_check(rec, b, rate); })) return -1;
+  return rate_records_host(r, rate, true, ids, n, const_cast<void *>(h_records));
 }

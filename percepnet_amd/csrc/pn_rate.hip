@@ -19,6 +19,7 @@
 // which is the converter's whole active-set story: nothing to save, nothing to restore.
 // Memory-bound by design.  Per stream and frame — up: n samples + 128 B of tail in, 1920 B out, 32 n (L - 1) multiply-adds
 // (12 800 | 10 240 | 7 680); down: 1920 B + 8 D bytes of tail in, n samples out, n (2D - 1) multiply-adds (15 280 | 15 200 | 15 120).
+// Below them: the same two kernels with a factor PER STREAM (pn_rate_create_mixed), which call the same row bodies.
 #include "pn_launch.h"
 #include "pn_pcm.h"
 #include "pn_rate_design.h"
@@ -28,6 +29,39 @@
 #define RT_T PN_RATE_TAPS
 #define RT_UT PN_RATE_UP_TAIL        // 32
 static_assert(RT_UT == 2 * RT_T && RT_UT % 4 == 0 && PN_FRAME % (8 * PN_RATE_MAX_L) == 0, "tails and rows are whole 16-byte groups");
+
+// The row bodies of the two conversions, shared by the single-rate kernels and the mixed ones (so a stream's arithmetic is one
+// piece of code whichever converter runs it).  All pointers are LDS; taps = the table of this L, h[-D..D] / g[-D..D].
+// up: buf = 32 tail samples, then the row's N = 480 / L; o receives 480.
+template <int L>
+__device__ __forceinline__ void rt_up_rows(int lane, const float *buf, float *o, const float *taps) {
+  constexpr int N = PN_FRAME / L, D = RT_T * L;
+  for (int q = lane; q < N; q += RT_LANES) {
+    float x[RT_UT];                            // x[i] = sample q - 31 + i
+#pragma unroll
+    for (int i = 0; i < RT_UT; i++) x[i] = buf[q + 1 + i];
+    o[L * q] = x[RT_T - 1];                    // phase 0: sample q - T
+#pragma unroll 1                        // (unrolled, L = 6 keeps all 160 taps in registers: 256 VGPRs)
+    for (int p = 1; p < L; p++) {
+      float acc = 0.0f;
+#pragma unroll
+      for (int i = 0; i < RT_UT; i++) acc = acc + taps[D + L * (RT_T - 1 - i) + p] * x[i];
+      o[L * q + p] = acc;
+    }
+  }
+}
+// down: buf = 2D tail samples, then the 480 of the row; z receives N = 480 / L.
+template <int L>
+__device__ __forceinline__ void rt_down_rows(int lane, const float *buf, float *z, const float *taps) {
+  constexpr int N = PN_FRAME / L, TD = 2 * RT_T * L;
+  for (int m = lane; m < N; m += RT_LANES) {
+    const float *x = buf + L * m + 1;          // x[j] = 48 kHz sample Lm - 2D + 1 + j
+    float acc = 0.0f;
+#pragma unroll 8
+    for (int j = 0; j < TD - 1; j++) acc = acc + taps[TD - 1 - j] * x[j];
+    z[m] = acc;
+  }
+}
 
 template <int L, bool I16>
 __global__ __launch_bounds__(RT_LANES * RT_WPB) void pn_rate_up_kernel(
@@ -63,19 +97,7 @@ __global__ __launch_bounds__(RT_LANES * RT_WPB) void pn_rate_up_kernel(
   }
   __syncthreads();
   if (live) {
-    for (int q = lane; q < N; q += RT_LANES) {
-      float x[RT_UT];                          // x[i] = sample q - 31 + i
-#pragma unroll
-      for (int i = 0; i < RT_UT; i++) x[i] = buf[q + 1 + i];
-      o[L * q] = x[RT_T - 1];                  // phase 0: sample q - T
-#pragma unroll 1                        // (unrolled, L = 6 keeps all 160 taps in registers: 256 VGPRs)
-      for (int p = 1; p < L; p++) {
-        float acc = 0.0f;
-#pragma unroll
-        for (int i = 0; i < RT_UT; i++) acc = acc + s_taps[D + L * (RT_T - 1 - i) + p] * x[i];
-        o[L * q + p] = acc;
-      }
-    }
+    rt_up_rows<L>(lane, buf, o, s_taps);
   }
   __syncthreads();
   if (live) {
@@ -111,13 +133,7 @@ __global__ __launch_bounds__(RT_LANES * RT_WPB) void pn_rate_down_kernel(
   }
   __syncthreads();
   if (live) {
-    for (int m = lane; m < N; m += RT_LANES) {
-      const float *x = buf + L * m + 1;        // x[j] = 48 kHz sample Lm - 2D + 1 + j
-      float acc = 0.0f;
-#pragma unroll 8
-      for (int j = 0; j < TD - 1; j++) acc = acc + s_taps[TD - 1 - j] * x[j];
-      z[m] = acc;
-    }
+    rt_down_rows<L>(lane, buf, z, s_taps);
   }
   __syncthreads();
   if (live) {
@@ -137,16 +153,140 @@ __global__ __launch_bounds__(RT_LANES * RT_WPB) void pn_rate_down_kernel(
   }
 }
 
-// State records (include/percepnet_hip.h): record i <-> the two tails of stream ids[i]; one block per record.  gather writes the
-// header too; scatter trusts it (the host import has checked every header before anything is launched).
+// ---- mixed rates: a factor per stream ------------------------------------------------------------------------------------------
+// The same two kernels with the stream's L in {6, 3, 2, 1} read from a per-stream table (include/percepnet_hip.h "mixed rates").
+// Low-rate rows are PN_RATE_MIXED_ROW = 480 samples apart whatever the stream's rate; a stream uses the first 480 / L of its row,
+// the rest of an input row is not read and the rest of an output row is not written.  Tails are rows of the largest size (32 up,
+// 192 down), of which a stream uses the first 32 / 2D words.  The block stages all three tap tables (the L = 6, 3, 2 tables one
+// behind the other: 193 + 97 + 65 words).  A wave makes its L uniform with readfirstlane and runs the row body of that L behind
+// a scalar branch; the four waves of a block may take four different branches, so the block's two barriers stand OUTSIDE them:
+// stage -> barrier -> compute -> barrier -> store.  L = 1 is a copy: the row goes straight to the output row in LDS (int16 as
+// (float)v / 32768), the compute step does nothing, and no tail is read or written.
+#define RT_ROW PN_RATE_MIXED_ROW
+#define RT_DT_MAX (2 * RT_T * PN_RATE_MAX_L)                   // 192: a stream's down tail row
+#define RT_NT(L) (2 * RT_T * (L) + 1)
+#define RT_TAPS_ALL (RT_NT(6) + RT_NT(3) + RT_NT(2))           // 355
+static_assert(RT_ROW == PN_FRAME && RT_ROW % 8 == 0, "a mixed row is a whole 48 kHz frame");
+__device__ __forceinline__ int rt_taps_offset(int L) { return L == 6 ? 0 : L == 3 ? RT_NT(6) : RT_NT(6) + RT_NT(3); }
+// the wave's factor: lanes of dead waves and factors the host never writes run nothing (0)
+__device__ __forceinline__ int rt_wave_factor(const int *factors, size_t s, bool live) {
+  const int L = __builtin_amdgcn_readfirstlane(live ? factors[s] : 0);
+  return (L == 6 || L == 3 || L == 2 || L == 1) ? L : 0;
+}
+// int16 x 8 -> two float4 / two float4 -> int16 x 8, the conversions of the single-rate kernels
+__device__ __forceinline__ void rt_i16x8_to_f32(uint4 q, float4 *d) {
+  union { uint4 q; int16_t h[8]; } u;
+  u.q = q;
+  d[0] = make_float4((float)u.h[0] / 32768.f, (float)u.h[1] / 32768.f, (float)u.h[2] / 32768.f, (float)u.h[3] / 32768.f);
+  d[1] = make_float4((float)u.h[4] / 32768.f, (float)u.h[5] / 32768.f, (float)u.h[6] / 32768.f, (float)u.h[7] / 32768.f);
+}
+__device__ __forceinline__ uint4 rt_f32x8_to_i16(const float4 *z, int saturate) {
+  const float4 a = z[0], b = z[1];
+  const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+  union { int16_t h[8]; uint4 q; } p;
+#pragma unroll
+  for (int i = 0; i < 8; i++) { const float t = v[i] * 32768; p.h[i] = saturate ? pn_f2s_sat(t) : pn_f2s(t); }
+  return p.q;
+}
+
+template <bool I16>
+__global__ __launch_bounds__(RT_LANES * RT_WPB) void pn_rate_up_mixed_kernel(
+    int n_rows, const int *__restrict__ ids,
+    const int *__restrict__ factors,           // [n_streams] L of every stream
+    const void *__restrict__ in,               // [n_streams][480] float or int16, the first 480 / L used
+    float *__restrict__ out48,                 // [n_streams][480]
+    float *__restrict__ tail,                  // [n_streams][32], read then rewritten (not for L = 1)
+    const float *__restrict__ taps) {          // h of L = 6, 3, 2, one table behind the other
+  __shared__ float s_taps[RT_TAPS_ALL];
+  __shared__ __align__(16) float s_buf[RT_WPB][RT_UT + PN_FRAME / 2];
+  __shared__ __align__(16) float s_out[RT_WPB][PN_FRAME];
+  const int lane = threadIdx.x & (RT_LANES - 1), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (int i = threadIdx.x; i < RT_TAPS_ALL; i += RT_LANES * RT_WPB) s_taps[i] = taps[i];
+  const int w = blockIdx.x * RT_WPB + wave;
+  const bool live = w < n_rows;                // (no early return: the block meets at its barriers)
+  const size_t s = live ? (size_t)(ids ? ids[w] : w) : 0;
+  const int L = rt_wave_factor(factors, s, live);
+  const int N = L ? PN_FRAME / L : 0;          // wave-uniform
+  float *buf = s_buf[wave], *o = s_out[wave];
+  // stage: the tail and the row behind it; L = 1 puts the row where the results go
+  float *row = L == 1 ? o : buf + RT_UT;
+  if (L > 1 && lane < RT_UT / 4) reinterpret_cast<float4 *>(buf)[lane] = reinterpret_cast<const float4 *>(tail + s * RT_UT)[lane];
+  if constexpr (I16) {
+    const uint4 *src = reinterpret_cast<const uint4 *>(static_cast<const int16_t *>(in) + s * RT_ROW);
+    for (int i = lane; i < N / 8; i += RT_LANES) rt_i16x8_to_f32(src[i], reinterpret_cast<float4 *>(row) + 2 * i);
+  } else {
+    const float4 *src = reinterpret_cast<const float4 *>(static_cast<const float *>(in) + s * RT_ROW);
+    for (int i = lane; i < N / 4; i += RT_LANES) reinterpret_cast<float4 *>(row)[i] = src[i];
+  }
+  __syncthreads();
+  if (L == 6) rt_up_rows<6>(lane, buf, o, s_taps + rt_taps_offset(6));
+  else if (L == 3) rt_up_rows<3>(lane, buf, o, s_taps + rt_taps_offset(3));
+  else if (L == 2) rt_up_rows<2>(lane, buf, o, s_taps + rt_taps_offset(2));
+  __syncthreads();
+  if (L) {
+    float4 *dst = reinterpret_cast<float4 *>(out48 + s * PN_FRAME);
+    for (int i = lane; i < PN_FRAME / 4; i += RT_LANES) dst[i] = reinterpret_cast<const float4 *>(o)[i];
+    if (L > 1 && lane < RT_UT / 4) reinterpret_cast<float4 *>(tail + s * RT_UT)[lane] = reinterpret_cast<const float4 *>(buf + N)[lane];
+  }
+}
+
+template <bool I16>
+__global__ __launch_bounds__(RT_LANES * RT_WPB) void pn_rate_down_mixed_kernel(
+    int n_rows, const int *__restrict__ ids,
+    const int *__restrict__ factors,           // [n_streams]
+    const float *__restrict__ in48,            // [n_streams][480]
+    void *__restrict__ out,                    // [n_streams][480] float or int16, the first 480 / L written
+    int saturate,
+    float *__restrict__ tail,                  // [n_streams][192], the first 2D read then rewritten (not for L = 1)
+    const float *__restrict__ taps) {          // g of L = 6, 3, 2, one table behind the other
+  __shared__ float s_taps[RT_TAPS_ALL];
+  __shared__ __align__(16) float s_buf[RT_WPB][RT_DT_MAX + PN_FRAME];
+  __shared__ __align__(16) float s_out[RT_WPB][PN_FRAME];
+  const int lane = threadIdx.x & (RT_LANES - 1), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (int i = threadIdx.x; i < RT_TAPS_ALL; i += RT_LANES * RT_WPB) s_taps[i] = taps[i];
+  const int w = blockIdx.x * RT_WPB + wave;
+  const bool live = w < n_rows;
+  const size_t s = live ? (size_t)(ids ? ids[w] : w) : 0;
+  const int L = rt_wave_factor(factors, s, live);
+  const int N = L ? PN_FRAME / L : 0, TD = L > 1 ? 2 * RT_T * L : 0;       // wave-uniform; TD / 4 <= 48 lanes
+  float *buf = s_buf[wave], *z = s_out[wave];
+  float *row = L == 1 ? z : buf + TD;
+  if (lane < TD / 4) reinterpret_cast<float4 *>(buf)[lane] = reinterpret_cast<const float4 *>(tail + s * RT_DT_MAX)[lane];
+  if (L) {
+    const float4 *src = reinterpret_cast<const float4 *>(in48 + s * PN_FRAME);
+    for (int i = lane; i < PN_FRAME / 4; i += RT_LANES) reinterpret_cast<float4 *>(row)[i] = src[i];
+  }
+  __syncthreads();
+  if (L == 6) rt_down_rows<6>(lane, buf, z, s_taps + rt_taps_offset(6));
+  else if (L == 3) rt_down_rows<3>(lane, buf, z, s_taps + rt_taps_offset(3));
+  else if (L == 2) rt_down_rows<2>(lane, buf, z, s_taps + rt_taps_offset(2));
+  __syncthreads();
+  if constexpr (I16) {
+    uint4 *dst = reinterpret_cast<uint4 *>(static_cast<int16_t *>(out) + s * RT_ROW);
+    for (int i = lane; i < N / 8; i += RT_LANES) dst[i] = rt_f32x8_to_i16(reinterpret_cast<const float4 *>(z) + 2 * i, saturate);
+  } else {
+    float4 *dst = reinterpret_cast<float4 *>(static_cast<float *>(out) + s * RT_ROW);
+    for (int i = lane; i < N / 4; i += RT_LANES) dst[i] = reinterpret_cast<const float4 *>(z)[i];
+  }
+  if (lane < TD / 4) reinterpret_cast<float4 *>(tail + s * RT_DT_MAX)[lane] = reinterpret_cast<const float4 *>(buf + PN_FRAME)[lane];
+}
+
+// A rate change (pn_rate_set_stream_rates): factors[ids[i]] = vals[i], ids distinct.  The tails are zeroed by the launches behind it.
+__global__ void pn_rate_set_factors_kernel(const int *__restrict__ ids, const int *__restrict__ vals, int n, int *__restrict__ factors) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) factors[ids[i]] = vals[i];
+}
+
+// State records (include/percepnet_hip.h): record i <-> the two tails of stream ids[i]; one block per record.  td = 2D words of a
+// down tail row that is td_stride words long (td in a single-rate converter, 192 in a mixed one).  gather writes the header too; scatter trusts it (the host import has checked every header before anything is launched).
 __global__ __launch_bounds__(64) void pn_rate_records_kernel(const int *__restrict__ ids, float *__restrict__ tail_up, float *__restrict__ tail_down,
-                                                             int td, uint32_t *__restrict__ rec, int rec_words, uint4 hdr, int scatter) {
+                                                             int td, int td_stride, uint32_t *__restrict__ rec, int rec_words, uint4 hdr, int scatter) {
   const size_t s = (size_t)ids[blockIdx.x];
   uint32_t *r = rec + (size_t)blockIdx.x * rec_words;
   if (!scatter && threadIdx.x == 0) *reinterpret_cast<uint4 *>(r) = hdr;
   float *body = reinterpret_cast<float *>(r + PN_RATE_STATE_HEADER_BYTES / 4);
   for (int i = threadIdx.x; i < RT_UT + td; i += blockDim.x) {
-    float *p = i < RT_UT ? tail_up + s * RT_UT + i : tail_down + s * td + (i - RT_UT);
+    float *p = i < RT_UT ? tail_up + s * RT_UT + i : tail_down + s * td_stride + (i - RT_UT);
     if (scatter) *p = body[i]; else body[i] = *p;
   }
 }
@@ -171,10 +311,30 @@ int pn_launch_rate_down(hipStream_t st, int L, int is_i16, int n_rows, const int
   RT_DISPATCH(pn_rate_down_kernel, n_rows, d_ids, in48, out, saturate, tail, taps);
   return 0;
 }
-void pn_launch_rate_records(hipStream_t st, int L, int rate_hz, const int *d_ids, int n, float *tail_up, float *tail_down, void *rec, int scatter) {
+void pn_launch_rate_records(hipStream_t st, int L, int rate_hz, const int *d_ids, int n, float *tail_up, float *tail_down, int td_stride, void *rec, int scatter) {
   if (n <= 0) return;
   uint32_t h[4];
   pn_rate_record_header(h, rate_hz);
-  hipLaunchKernelGGL(pn_rate_records_kernel, dim3(n), dim3(64), 0, st, d_ids, tail_up, tail_down, pn_rate_down_tail(L), (uint32_t *)rec,
+  hipLaunchKernelGGL(pn_rate_records_kernel, dim3(n), dim3(64), 0, st, d_ids, tail_up, tail_down, pn_rate_down_tail(L), td_stride, (uint32_t *)rec,
                      (int)pn_rate_record_words(L), make_uint4(h[0], h[1], h[2], h[3]), scatter);
+}
+
+// the mixed kernels: rows of 480 samples, the factor of every stream in d_factors, all three tap tables at taps
+int pn_launch_rate_up_mixed(hipStream_t st, int is_i16, int n_rows, const int *d_ids, const int *d_factors, const void *in, float *out48, float *tail, const float *taps) {
+  if (n_rows <= 0) return 0;
+  const dim3 grid((n_rows + RT_WPB - 1) / RT_WPB), block(RT_LANES * RT_WPB);
+  if (is_i16) hipLaunchKernelGGL(HIP_KERNEL_NAME(pn_rate_up_mixed_kernel<true>), grid, block, 0, st, n_rows, d_ids, d_factors, in, out48, tail, taps);
+  else hipLaunchKernelGGL(HIP_KERNEL_NAME(pn_rate_up_mixed_kernel<false>), grid, block, 0, st, n_rows, d_ids, d_factors, in, out48, tail, taps);
+  return 0;
+}
+int pn_launch_rate_down_mixed(hipStream_t st, int is_i16, int n_rows, const int *d_ids, const int *d_factors, const float *in48, void *out, int saturate, float *tail, const float *taps) {
+  if (n_rows <= 0) return 0;
+  const dim3 grid((n_rows + RT_WPB - 1) / RT_WPB), block(RT_LANES * RT_WPB);
+  if (is_i16) hipLaunchKernelGGL(HIP_KERNEL_NAME(pn_rate_down_mixed_kernel<true>), grid, block, 0, st, n_rows, d_ids, d_factors, in48, out, saturate, tail, taps);
+  else hipLaunchKernelGGL(HIP_KERNEL_NAME(pn_rate_down_mixed_kernel<false>), grid, block, 0, st, n_rows, d_ids, d_factors, in48, out, saturate, tail, taps);
+  return 0;
+}
+void pn_launch_rate_set_factors(hipStream_t st, const int *d_ids, const int *d_vals, int n, int *d_factors) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(pn_rate_set_factors_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d_ids, d_vals, n, d_factors);
 }
