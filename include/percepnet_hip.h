@@ -426,8 +426,7 @@ int pn_featgen_run_files(int device, int n_jobs, const char *const *speech_paths
    trunc(z * 32768) wrapped to 16 bit, or saturated while pn_ctx_set_output_saturate is on.  The frame report (pn_ctx_set_report)
    stays that of the 48 kHz signal inside the engine: 480 samples per frame, the engine's own 2880-sample delay, levels before the
    down-conversion.
-   NOT provided: the pipelined pn_submit_host_* path, device-side record export / import, other rates, profiling families of the
-   kernels.
+   NOT provided: other rates.
 
    Host only, needing no GPU:
    pn_rate_frame_samples: n, -1 for a refused rate.  pn_rate_delay_samples: the table above, -1.  pn_rate_taps: the fp32 table,
@@ -483,6 +482,50 @@ int pn_rate_process_host_i16(pn_rate *r, const int16_t *h_in, int16_t *h_out, fl
    moves a narrowband stream between slots, contexts, devices and processes bit for bit. */
 int pn_rate_export_streams_host(pn_rate *r, const int32_t *ids, int n, void *h_records);
 int pn_rate_import_streams_host(pn_rate *r, const int32_t *ids, int n, const void *h_records);
+/* The pipelined host path for a converter's frames (single-rate or mixed): pn_submit_host_* with the converter's frame in the
+   middle.  One frame is H2D of the low-rate rows on the context's h2d stream into a staging slot of the converter, then on the
+   context's stream the frame of pn_rate_process_* (up, pn_process_f32[_active], down), then D2H of the low-rate rows and of g|r
+   on the d2h stream.  It runs through the CONTEXT's pipeline — its two copy streams, slot counter, events and its bound of two
+   frames in flight — so pn_host_wait(ctx), pn_host_frames_delivered(ctx), pn_ctx_pipe_streams(ctx) and pn_host_next_report(ctx,
+   h_report) work unchanged and count frames of either kind in submission order (the next submit of either kind delivers its
+   frame's 48 kHz report records), and pn_submit_host_* and pn_rate_submit_host_* may be interleaved on one context.
+   Rows are [n_streams][pn_rate_row_samples(r)].  On a mixed converter whole rows of 480 travel both ways: the rest of an input
+   row is ignored and the rest of an output row is UNSPECIFIED on this path (no landing buffer, no per-stream host copy).  Rows of
+   streams skipped by an _active call are unspecified.  h_in / h_out / h_gr live by the rule of pn_submit_host_*.
+   pn_rate_host_pipeline_prepare: allocates the converter's second staging pair and does pn_host_pipeline_prepare(ctx); otherwise
+   the first submit does both; no later frame allocates.  pn_rate_set_stream_rates, pn_rate_reset_streams, pn_ctx_reset_streams,
+   pn_ctx_set_atten_limit and the record calls are ordered on the context's stream: frames submitted before them run under the
+   old values, frames after them under the new ones, with no wait in between.  A refused id list consumes no slot; a frame that
+   fails inside the engine returns -1 with the context's error kept.  pn_rate_destroy completes the frames in flight;
+   pn_rate_process_host_* keeps draining the pipeline first.  Results are bit for bit those of the synchronous path. */
+int pn_rate_submit_host_f32(pn_rate *r, const float *h_in, float *h_out, float *h_gr);
+int pn_rate_submit_host_i16(pn_rate *r, const int16_t *h_in, int16_t *h_out, float *h_gr);
+int pn_rate_submit_host_f32_active(pn_rate *r, const float *h_in, float *h_out, float *h_gr, const int32_t *ids, int n);
+int pn_rate_submit_host_i16_active(pn_rate *r, const int16_t *h_in, int16_t *h_out, float *h_gr, const int32_t *ids, int n);
+int pn_rate_host_pipeline_prepare(pn_rate *r);
+/* Device-side records: asynchronous on the context's stream, ordered like pn_ctx_export_streams / pn_ctx_import_streams.  Records
+   go to a 16-byte aligned device address, pn_rate_record_stride(r) bytes apart: pn_rate_state_bytes(rate) on a single-rate
+   converter, PN_RATE_STATE_MAX_BYTES on a mixed one, where the fixed stride lifts the one-rate-per-call rule of the host forms —
+   each record carries its own stream's rate.  Format, version and sizes are those above.
+   Export (duplicates allowed): record i gets the header of stream ids[i]'s current rate, that rate's size, the two tails oldest
+   first, and zeros from the record's size up to the stride.
+   Import (distinct ids, d_status required): every header is checked on the device against the SLOT's rate — the converter's, or
+   the per-stream rate a preceding pn_rate_set_stream_rates has set, in stream order — and d_status[i] receives exactly
+   pn_rate_state_check(record_i, pn_rate_state_bytes(R), R) for the slot's rate R.  A refused record leaves both tails of its
+   stream untouched; the other records of the call are imported.
+   Refused on the host with -1, nothing written or launched: a bad or (import) duplicate id, a misaligned pointer, a listed stream
+   that runs at 48000 (it has no converter state).  n == 0 is a no-op. */
+#define PN_RATE_STATE_MAX_BYTES 912
+size_t pn_rate_state_max_bytes(void);                 /* host only */
+size_t pn_rate_record_stride(const pn_rate *r);
+int pn_rate_export_streams(pn_rate *r, const int32_t *ids, int n, void *d_records);
+int pn_rate_import_streams(pn_rate *r, const int32_t *ids, int n, const void *d_records, int32_t *d_status);
+/* Timing of the converter's two kernels inside a frame: HIP events around their launches, like pn_ctx_set_profiling but owned by
+   the converter (the context's family list does not change).  Off by default; off, no event is created or recorded.  name:
+   "rate_up" | "rate_down".  pn_rate_kernel_time synchronises the context's stream. */
+int pn_rate_set_profiling(pn_rate *r, int enable);
+int pn_rate_kernel_time(pn_rate *r, const char *name, double *total_ms, int64_t *launches);
+int pn_rate_reset_profile(pn_rate *r);
 
 /* ---- mixed rates: 8, 16, 24 and 48 kHz streams in ONE context ---------------------------------------------------------------- */
 /* A mixed converter IS a pn_rate — every entry point above takes it — whose streams each have a rate of their own out of 8000,

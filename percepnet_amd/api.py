@@ -148,6 +148,23 @@ def load_library():
             getattr(L, name).argtypes = [_vp]
         L.pn_rate_set_stream_rates.argtypes = [_vp, _vp, ctypes.c_int, _vp]
         L.pn_rate_get_stream_rates.argtypes = [_vp, _vp]
+    if hasattr(L, "pn_rate_submit_host_i16"):
+        for name in ("pn_rate_submit_host_f32", "pn_rate_submit_host_i16"):
+            getattr(L, name).argtypes = [_vp, _vp, _vp, _vp]
+        for name in ("pn_rate_submit_host_f32_active", "pn_rate_submit_host_i16_active"):
+            getattr(L, name).argtypes = [_vp, _vp, _vp, _vp, _vp, ctypes.c_int]
+        L.pn_rate_host_pipeline_prepare.argtypes = [_vp]
+        L.pn_rate_state_max_bytes.restype = ctypes.c_size_t
+        L.pn_rate_state_max_bytes.argtypes = []
+        L.pn_rate_record_stride.restype = ctypes.c_size_t
+        L.pn_rate_record_stride.argtypes = [_vp]
+        L.pn_rate_export_streams.argtypes = [_vp, _vp, ctypes.c_int, _vp]
+        L.pn_rate_import_streams.argtypes = [_vp, _vp, ctypes.c_int, _vp, _vp]
+        L.pn_rate_set_profiling.argtypes = [_vp, ctypes.c_int]
+        L.pn_rate_kernel_time.argtypes = [_vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
+        L.pn_rate_reset_profile.argtypes = [_vp]
+    if hasattr(L, "pn_host_pipeline_prepare"):
+        L.pn_host_pipeline_prepare.argtypes = [_vp]
     L.pn_ctx_debug_copy.restype = ctypes.c_longlong
     L.pn_ctx_debug_copy.argtypes = [_vp, ctypes.c_int, _vp, ctypes.c_longlong]
     L.pn_ctx_set_profiling.argtypes = [_vp, ctypes.c_int]
@@ -311,6 +328,18 @@ class Context:
         if h_report is not None:
             self._chk(self.L.pn_host_next_report(self.h, h_report))
         self._chk(self.L.pn_submit_host_i16_active(self.h, h_in, h_out, h_gr, a.ctypes.data, int(a.size)))
+
+    def host_pipeline_prepare(self):
+        """Builds the pipelined host path now (pn_host_pipeline_prepare) instead of inside the first submit: tens of milliseconds
+        of queue probing that a caller on a real-time clock spends before its first frame arrives."""
+        self._chk(self.L.pn_host_pipeline_prepare(self.h))
+
+    def frames_delivered(self):
+        """Frames of the pipelined host path (the context's or a converter's) whose output has landed; non-blocking."""
+        n = int(self.L.pn_host_frames_delivered(self.h))
+        if n < 0:
+            raise PercepNetError(_err(self.L))
+        return n
 
     def pipe_streams(self):
         """'nn' / 'hl' ...: how the copy streams of the pipelined host path were obtained ('' before the first submit)"""
@@ -478,6 +507,11 @@ def rate_state_bytes(rate_hz):
     return int(load_library().pn_rate_state_bytes(int(rate_hz)))
 
 
+def rate_state_max_bytes():
+    """Bytes of the largest converter state record (8000 Hz: 912): the stride of a mixed converter's device-side records (host only)."""
+    return int(load_library().pn_rate_state_max_bytes())
+
+
 def rate_state_check(record, rate_hz):
     """PN_SS_OK (0) or the PN_SS_BAD_* verdict a converter of rate_hz gives the bytes `record` (host only, no GPU)."""
     L = load_library()
@@ -598,6 +632,60 @@ class RateConverter:
             o, _ = self.process_i16(pcm[:, t * f:(t + 1) * f], want_gr=False)
             if t > 0:
                 out[:, (t - 1) * f:t * f] = o
+        return out
+
+    # pipelined host-buffer entry points: a converter's frame through the CONTEXT's pipeline (raw host pointers to rows of
+    # [n_streams][frame]; the buffers should be pinned and must outlive delivery: Context.host_wait / frames_delivered).
+    # h_report: this frame's 48 kHz report records (pn_host_next_report); ids: only those streams advance.  On a mixed converter
+    # the part of an output row behind a stream's own samples is unspecified.
+    def _submit(self, kind, h_in, h_out, h_gr, h_report, ids):
+        if h_report is not None:
+            self._chk(self.L.pn_host_next_report(self.ctx.h, h_report))
+        if ids is None:
+            self._chk(getattr(self.L, f"pn_rate_submit_host_{kind}")(self.h, h_in, h_out, h_gr))
+        else:
+            a, n = self._ids(ids)
+            self._chk(getattr(self.L, f"pn_rate_submit_host_{kind}_active")(self.h, h_in, h_out, h_gr, a.ctypes.data, n))
+
+    def submit_host_i16(self, h_in, h_out, h_gr=None, h_report=None, ids=None):
+        self._submit("i16", h_in, h_out, h_gr, h_report, ids)
+
+    def submit_host_f32(self, h_in, h_out, h_gr=None, h_report=None, ids=None):
+        self._submit("f32", h_in, h_out, h_gr, h_report, ids)
+
+    def host_pipeline_prepare(self):
+        """The converter's second staging pair and the context's pipeline, now instead of inside the first submit."""
+        self._chk(self.L.pn_rate_host_pipeline_prepare(self.h))
+
+    # device-side records (async on the context's stream): records record_stride() bytes apart at a 16-byte aligned address
+    def record_stride(self):
+        """Bytes between two device-side records: state_bytes of the rate, or rate_state_max_bytes() on a mixed converter."""
+        return int(self.L.pn_rate_record_stride(self.h))
+
+    def export_streams_dev(self, ids, d_records):
+        a, n = self._ids(ids)
+        self._chk(self.L.pn_rate_export_streams(self.h, a.ctypes.data, n, d_records))
+
+    def import_streams_dev(self, ids, d_records, d_status):
+        """d_status (device int32 [n]) receives SS_OK or the SS_BAD_* verdict of each record against its slot's rate."""
+        a, n = self._ids(ids)
+        self._chk(self.L.pn_rate_import_streams(self.h, a.ctypes.data, n, d_records, d_status))
+
+    # timing of the two kernels inside a frame (HIP events owned by the converter; off by default)
+    def set_profiling(self, on):
+        self._chk(self.L.pn_rate_set_profiling(self.h, 1 if on else 0))
+
+    def reset_profile(self):
+        self._chk(self.L.pn_rate_reset_profile(self.h))
+
+    def kernel_times(self):
+        """-> {"rate_up": (total_ms, launches), "rate_down": (...)}"""
+        out = {}
+        for name in (b"rate_up", b"rate_down"):
+            ms = ctypes.c_double()
+            n = ctypes.c_int64()
+            self._chk(self.L.pn_rate_kernel_time(self.h, name, ctypes.byref(ms), ctypes.byref(n)))
+            out[name.decode()] = (ms.value, n.value)
         return out
 
     def export_streams(self, ids):

@@ -11,13 +11,15 @@
 // --rate R: the files are raw int16 at R Hz instead of 48 kHz, in frames of n = 480 * R / 48000 samples (80 | 160 | 240): a rate
 // converter beside each context (pn_rate) takes every frame up to 48 kHz in front of the engine and back down behind it.  The
 // per-stream contract is unchanged: (frames-1)*n samples out, first output frame and partial tail dropped.  The frames go through
-// the synchronous pn_rate_process_host_i16 (the converter has no pipelined path), --report reads each frame's records after
-// it (pn_ctx_read_report) — its figures stay those of the 48 kHz signal inside the engine — and the converter's slots are reset
+// the converter's pipelined path (pn_rate_submit_host_i16: the context's pipeline with the converter's frame in the middle) with
+// the same rotation of three pinned buffer sets as the 48 kHz path, --report gets each frame's records through
+// pn_host_next_report — its figures stay those of the 48 kHz signal inside the engine — and the converter's slots are reset
 // with the context's.  Without --rate nothing of this runs.
 //
 // --rates R0,R1,..: one rate per pair out of 8000, 16000, 24000 and 48000 (exclusive with --rate): a MIXED converter beside each
 // context (pn_rate_create_mixed), whose shard's slice of the list goes to its device.  Pair i is read and written in frames of
-// its own n = 480 * Ri / 48000 samples; the pinned rows are 480 samples whatever the rate; the per-pair contract is the one
+// its own n = 480 * Ri / 48000 samples; the pinned rows are 480 samples whatever the rate (only a pair's own n samples of an
+// output row are written to its file: the rest of the row is unspecified on the pipelined path); the per-pair contract is the one
 // above.  With --slots a slot taken over by a pair of another rate continues at that rate (pn_rate_set_stream_rates for the
 // restart list, where --rate calls pn_rate_reset_streams), followed by the context's reset as always.
 //
@@ -135,7 +137,7 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
   for (int s = 0; s < B; s++) if (!open_pair(s)) return;
   R.ftap = tap ? fopen("feature_test.raw", "wb") : NULL;
   FILE *ftap = R.ftap;
-  // Three rotating pinned buffer sets on the pipelined entry point: the files of frame t+1 are read while the GPU
+  // Three rotating pinned buffer sets on the pipelined entry point (the context's, or with --rate / --rates the converter's): the files of frame t+1 are read while the GPU
   // works on frame t, and frame t-2's output is on the host once pn_submit_host_i16(t) has returned.
   typedef ShardRes::Slot Slot;
   Slot *slot = R.slot;
@@ -206,13 +208,9 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
                              (rt && (mixed ? pn_rate_set_stream_rates(rt, restart.data(), (int)restart.size(), restart_rates.data())
                                            : pn_rate_reset_streams(rt, restart.data(), (int)restart.size()))) ||
                              set_limit(restart.data(), (int)restart.size()))) return fail(5, pn_last_error());
-    if (rt) {                                          // --rate, --rates: one synchronous frame, then its report records
-      if (pn_rate_process_host_i16(rt, sl.in, sl.out, sl.gr)) return fail(5, pn_last_error());
-      if (g_report && pn_ctx_read_report(cx, sl.rep)) return fail(5, pn_last_error());
-    } else {
-      if (g_report && pn_host_next_report(cx, sl.rep)) return fail(5, pn_last_error());
-      if (pn_submit_host_i16(cx, sl.in, sl.out, sl.gr)) return fail(5, pn_last_error());
-    }
+    if (g_report && pn_host_next_report(cx, sl.rep)) return fail(5, pn_last_error());
+    // --rate, --rates: the converter's frame through the same pipeline
+    if (rt ? pn_rate_submit_host_i16(rt, sl.in, sl.out, sl.gr) : pn_submit_host_i16(cx, sl.in, sl.out, sl.gr)) return fail(5, pn_last_error());
     if (t >= 2) flush(slot[(t - 2) % 3]);
   }
   if (pn_host_wait(cx)) return fail(5, pn_last_error());

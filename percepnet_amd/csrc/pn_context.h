@@ -2,7 +2,8 @@
 // settings, the frame's launch sequence, active set), pn_selftest.cpp (the create-time self-tests), pn_host_pipe.cpp (pipelined
 // host-buffer path, host-thread helpers), pn_stream_state.cpp (RNN-state and stream-state I/O) and pn_network.cpp (shared weights,
 // the ten-layer launch loop, row-range chains).  The training-feature generator (pn_featgen.cpp) shares the allocator, the table
-// upload and the device preamble; the rate converter (pn_rate.cpp) the id ring and the host form of a record transfer.
+// upload and the device preamble; the rate converter (pn_rate.cpp) the id ring, the host form of a record transfer and the pipelined
+// path's frame (pipe_submit).
 #pragma once
 #include <array>
 #include <functional>
@@ -109,6 +110,12 @@ int nn_selftest(pn_ctx *c);
 int dsp_selftest(pn_ctx *c);
 // ---- pn_host_pipe.cpp -------------------------------------------------------------------------------------------------------
 int pipe_make_stream(pn_ctx *c, hipStream_t *out, char how, int prio, char fallback, const std::vector<hipStream_t> &others, char *kind);
+// One frame of the pipelined path for whoever owns a frame body (the context's own frame; a rate converter's, pn_rate.cpp): the
+// owner's two staging pairs and the bytes of its rows, and the launches between them.  pipe_submit builds the pipeline when it
+// is the first frame (the caller is on the context's device).
+struct PipeStaging { void *in[2], *out[2]; size_t bytes; };
+typedef int (*PipeBody)(void *arg, void *d_in, void *d_out, float *d_gr);
+int pipe_submit(pn_ctx *c, const PipeStaging &st, const void *h_in, void *h_out, float *h_gr, PipeBody body, void *arg);
 int pipe_drain(pn_ctx *c);       // frames in flight on the pipelined path complete (the caller is on the context's device)
 void pipe_destroy(pn_ctx *c);    // the pipeline's streams and events, whole or partly built; its device buffers stay with the context
 // ---- pn_stream_state.cpp ----------------------------------------------------------------------------------------------------

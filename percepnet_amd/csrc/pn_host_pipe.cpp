@@ -128,33 +128,48 @@ int pipe_drain(pn_ctx *c) {
   PN_HIP_CHECK(hipStreamSynchronize(c->pipe.d2h));
   return 0;
 }
-// ids != NULL or n >= 0 with active = true: only the listed streams advance (pn_submit_host_*_active)
-static int submit_host(pn_ctx *c, const void *h_in, void *h_out, float *h_gr, int is_i16, bool active = false, const int32_t *ids = NULL, int n = 0) {
-  if (!c || !h_in || !h_out) { pn_set_error("NULL argument"); return -1; }
-  if (active && active_check(c, ids, n)) return -1;          // refused before the frame takes a pipeline slot
-  PN_ON_DEVICE(c);
+// One frame of the pipeline, whoever's it is (the context's own frame, or a rate converter's: pn_rate.cpp).  st: the two device
+// staging pairs of its owner and the bytes of a whole batch of rows; body(arg, d_in, d_out, d_gr) queues the frame's launches
+// on the context's stream from st.in[k] to st.out[k] (d_gr: the slot's g|r rows, or NULL).  The streams, the slot counter, the
+// events, the g|r and report slots and the two-frames-in-flight bound are the context's, so frames of either kind count in
+// submission order.  The caller has refused everything it refuses BEFORE this call: from here on the frame owns slot k.
+int pipe_submit(pn_ctx *c, const PipeStaging &st, const void *h_in, void *h_out, float *h_gr, PipeBody body, void *arg) {
   if (pipe_init(c)) return -1;
   pn_ctx::Pipe &P = c->pipe;
   const int k = (int)(P.submitted & 1);
   void *const h_report = c->next_report;                     // pn_host_next_report: this call's, whatever becomes of it
   c->next_report = NULL;
   if (P.submitted >= 2) PN_HIP_CHECK(hipEventSynchronize(P.delivered[k]));     // frame submitted-2 delivered: slot k is free
-  const size_t nbytes = (size_t)c->B * PN_FRAME * (is_i16 ? 2 : 4);
-  PN_HIP_CHECK(hipMemcpyAsync(P.in[k], h_in, nbytes, hipMemcpyHostToDevice, P.h2d));
+  PN_HIP_CHECK(hipMemcpyAsync(st.in[k], h_in, st.bytes, hipMemcpyHostToDevice, P.h2d));
   PN_HIP_CHECK(hipEventRecord(P.in_ready[k], P.h2d));
   PN_HIP_CHECK(hipStreamWaitEvent(c->stream, P.in_ready[k], 0));
-  if (active ? process_active(c, P.in[k], P.out[k], h_gr ? P.gr[k] : NULL, is_i16, ids, n)
-             : process_dev(c, P.in[k], P.out[k], h_gr ? P.gr[k] : NULL, is_i16)) return -1;
+  if (body(arg, st.in[k], st.out[k], h_gr ? P.gr[k] : NULL)) return -1;
   const size_t report_bytes = (size_t)c->B * PN_REPORT_WORDS * 4;
   if (h_report) PN_HIP_CHECK(hipMemcpyAsync(P.report[k], c->report, report_bytes, hipMemcpyDeviceToDevice, c->stream));   // the next frame rewrites c->report
   PN_HIP_CHECK(hipEventRecord(P.done[k], c->stream));
   PN_HIP_CHECK(hipStreamWaitEvent(P.d2h, P.done[k], 0));
-  PN_HIP_CHECK(hipMemcpyAsync(h_out, P.out[k], nbytes, hipMemcpyDeviceToHost, P.d2h));
+  PN_HIP_CHECK(hipMemcpyAsync(h_out, st.out[k], st.bytes, hipMemcpyDeviceToHost, P.d2h));
   if (h_gr) PN_HIP_CHECK(hipMemcpyAsync(h_gr, P.gr[k], (size_t)c->B * 68 * 4, hipMemcpyDeviceToHost, P.d2h));
   if (h_report) PN_HIP_CHECK(hipMemcpyAsync(h_report, P.report[k], report_bytes, hipMemcpyDeviceToHost, P.d2h));
   PN_HIP_CHECK(hipEventRecord(P.delivered[k], P.d2h));
   P.submitted++;
   return 0;
+}
+// the context's own frame: ids != NULL or n >= 0 with active = true: only the listed streams advance (pn_submit_host_*_active)
+struct CtxFrame { pn_ctx *c; int is_i16; bool active; const int32_t *ids; int n; };
+static int ctx_frame_body(void *arg, void *d_in, void *d_out, float *d_gr) {
+  const CtxFrame &f = *static_cast<const CtxFrame *>(arg);
+  return f.active ? process_active(f.c, d_in, d_out, d_gr, f.is_i16, f.ids, f.n) : process_dev(f.c, d_in, d_out, d_gr, f.is_i16);
+}
+static int submit_host(pn_ctx *c, const void *h_in, void *h_out, float *h_gr, int is_i16, bool active = false, const int32_t *ids = NULL, int n = 0) {
+  if (!c || !h_in || !h_out) { pn_set_error("NULL argument"); return -1; }
+  if (active && active_check(c, ids, n)) return -1;          // refused before the frame takes a pipeline slot
+  PN_ON_DEVICE(c);
+  if (pipe_init(c)) return -1;                               // (P.in[1] / P.out[1] exist from here on)
+  const pn_ctx::Pipe &P = c->pipe;
+  const PipeStaging st = {{P.in[0], P.in[1]}, {P.out[0], P.out[1]}, (size_t)c->B * PN_FRAME * (is_i16 ? 2 : 4)};
+  CtxFrame f = {c, is_i16, active, ids, n};
+  return pipe_submit(c, st, h_in, h_out, h_gr, ctx_frame_body, &f);
 }
 // "nn" / "hl" / ...: how the two copy streams of the pipelined path were obtained (pipe_init); "" before the first submit
 extern "C" const char *pn_ctx_pipe_streams(pn_ctx *c) { return (c && c->pipe.init) ? c->pipe.kind : ""; }

@@ -88,6 +88,10 @@ void pn_launch_rate_records(hipStream_t st, int factor, int rate_hz, const int *
 // set_factors: d_factors[d_ids[i]] = d_vals[i] for i < n (distinct ids)
 int pn_launch_rate_up_mixed(hipStream_t st, int is_i16, int n_rows, const int *d_ids, const int *d_factors, const void *in, float *out48, float *tail, const float *taps);
 int pn_launch_rate_down_mixed(hipStream_t st, int is_i16, int n_rows, const int *d_ids, const int *d_factors, const float *in48, void *out, int saturate, float *tail, const float *taps);
+// device-side records, stride_words apart: each slot's factor from d_factors (mixed) or `factor` (single-rate, d_factors NULL);
+// scatter: d_status[i] receives record i's verdict, a refused record moves nothing
+void pn_launch_rate_records_dev(hipStream_t st, const int *d_ids, int n, const int *d_factors, int factor, float *tail_up, float *tail_down, int td_stride,
+                                void *rec, int stride_words, int *d_status, int scatter);
 void pn_launch_rate_set_factors(hipStream_t st, const int *d_ids, const int *d_vals, int n, int *d_factors);
 // ---- the network launchers (pn_nn*.hip) -----------------------------------------------------------------------------------------
 // Device pointers of a layer's biases and weights in the formats of pn_network.h: raw (w, rw), packed fp32 or fp16 planes (wp,

@@ -1,7 +1,8 @@
 // Host side of the batched rate converter (include/percepnet_hip.h "batched rate converter" and "mixed rates"): an object BESIDE a context, built
 // like the feature generator — it borrows the context's device, batch size and HIP stream, and owns everything else: the two
 // tap tables on the device, the per-stream tails of the two kernels (pn_rate.hip), the 48 kHz rows between the conversions and
-// the staging rows of the host-buffer path.  Nothing of it lives in pn_ctx, its state table or its records.  Every launch goes
+// the staging rows of the host-buffer paths.  The pipelined path (pn_rate_submit_host_*) runs its frames through the CONTEXT's
+// pipeline (pn_host_pipe.cpp pipe_submit) with the converter's own two staging pairs.  Nothing of it lives in pn_ctx, its state table or its records.  Every launch goes
 // to the context's stream, so a converter call is ordered against the context's calls like they are against each other.
 #include "pn_context.h"      // the context it borrows, the launchers, dev_alloc_into, stage_ids, the id rule, host_records_sync
 #include "pn_rate_design.h"
@@ -16,7 +17,8 @@ struct pn_rate {
   float *taps_up, *taps_down;   // [2D + 1] h, g.  Mixed: the tables of L = 6, 3, 2 one behind the other
   float *tail_up, *tail_down;   // [B][32], [B][td]: the state
   float *x48, *y48;             // [B][480]: the engine's input and output rows of a whole frame
-  void *io_in, *io_out;         // [B][n] 4-byte words: staging rows of the host-buffer path
+  void *io_in, *io_out;         // [B][n] 4-byte words: staging rows of the host-buffer paths (slot 0 of the pipelined one)
+  void *io_in1 = NULL, *io_out1 = NULL;   // slot 1 of the pipelined path: allocated by pn_rate_host_pipeline_prepare or the first submit
   float *io_gr;                 // [B][68]
   // a mixed converter (pn_rate_create_mixed): the rate of every stream as last set (host), its factor on the device — written
   // in stream order, so a frame submitted before a rate change still runs at the old rate — and a pinned landing place of the
@@ -26,7 +28,36 @@ struct pn_rate {
   int *factors;                 // [B] device
   void *h_rows;                 // [B][480] 4-byte words, pinned
   std::vector<void *> allocs;
+  // timing of the two kernels (pn_rate_set_profiling): HIP events around their launches, like the context's families but owned
+  // here; while it is off no event exists and none is recorded
+  bool profiling = false;
+  struct Ev { int fam; hipEvent_t a, b; };
+  std::vector<Ev> events;
+  std::vector<hipEvent_t> event_pool;
+  double fam_ms[2] = {0, 0}; int64_t fam_n[2] = {0, 0};
 };
+enum { RF_UP, RF_DOWN, RF_COUNT };
+static const char *const kRateFamily[RF_COUNT] = {"rate_up", "rate_down"};
+struct RateScope {
+  pn_rate *r; int fam; hipEvent_t a, b; bool on;
+  RateScope(pn_rate *r_, int fam_) : r(r_), fam(fam_), on(r_->profiling) {
+    if (on) {
+      auto take = [&](hipEvent_t &e) { if (r->event_pool.empty()) hipEventCreate(&e); else { e = r->event_pool.back(); r->event_pool.pop_back(); } };
+      take(a); take(b); hipEventRecord(a, r->c->stream);
+    }
+  }
+  ~RateScope() { if (on) { hipEventRecord(b, r->c->stream); r->events.push_back({fam, a, b}); } }
+};
+static int rate_flush_events(pn_rate *r) {
+  PN_HIP_CHECK(hipStreamSynchronize(r->c->stream));
+  for (auto &e : r->events) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) { r->fam_ms[e.fam] += ms; r->fam_n[e.fam]++; }
+    r->event_pool.push_back(e.a); r->event_pool.push_back(e.b);
+  }
+  r->events.clear();
+  return 0;
+}
 
 // ---- host only ---------------------------------------------------------------------------------------------------------------
 extern "C" int pn_rate_frame_samples(int rate_hz) {
@@ -58,7 +89,10 @@ extern "C" int pn_rate_mixed_rates_check(const int32_t *rates_hz, int n) { retur
 extern "C" void pn_rate_destroy(pn_rate *r) {
   if (!r) return;
   DeviceGuard _dg(r->c->device);
+  (void)pipe_drain(r->c);                            // frames in flight on the pipelined path read and write the staging rows
   hipStreamSynchronize(r->c->stream);
+  for (auto &e : r->events) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
+  for (hipEvent_t e : r->event_pool) hipEventDestroy(e);
   for (void *p : r->allocs) hipFree(p);
   if (r->h_rows) hipHostFree(r->h_rows);
   delete r;
@@ -197,6 +231,7 @@ static int rate_aligned(const void *a, const void *b) {
   return 0;
 }
 static int rate_up(pn_rate *r, const void *d_in, int is_i16, float *d_out48, const RateRows &rows) {
+  RateScope sc(r, RF_UP);
   if (r->mixed ? pn_launch_rate_up_mixed(r->c->stream, is_i16, rows.n, rows.d_ids, r->factors, d_in, d_out48, r->tail_up, r->taps_up)
                : pn_launch_rate_up(r->c->stream, r->L, is_i16, rows.n, rows.d_ids, d_in, d_out48, r->tail_up, r->taps_up)) return -1;
   PN_HIP_CHECK(hipGetLastError());
@@ -204,6 +239,7 @@ static int rate_up(pn_rate *r, const void *d_in, int is_i16, float *d_out48, con
 }
 static int rate_down(pn_rate *r, const float *d_in48, void *d_out, int is_i16, const RateRows &rows) {
   const int sat = r->c->saturate ? 1 : 0;
+  RateScope sc(r, RF_DOWN);
   if (r->mixed ? pn_launch_rate_down_mixed(r->c->stream, is_i16, rows.n, rows.d_ids, r->factors, d_in48, d_out, sat, r->tail_down, r->taps_down)
                : pn_launch_rate_down(r->c->stream, r->L, is_i16, rows.n, rows.d_ids, d_in48, d_out, sat, r->tail_down, r->taps_down)) return -1;
   PN_HIP_CHECK(hipGetLastError());
@@ -234,20 +270,27 @@ extern "C" int pn_rate_down_i16(pn_rate *r, const float *d_in48, int16_t *d_out,
 // up into x48, the engine's float frame from x48 into y48 (all streams, or the listed ones through the context's own active
 // set), down from y48.  A frame the engine refuses returns -1 with its error kept; the up kernel has then advanced its tails
 // and the down kernel has not, which is why the header asks for a reset of both objects before reuse.
-static int rate_process(pn_rate *r, const void *d_in, void *d_out, float *d_gr, int is_i16, bool active, const int32_t *ids, int n) {
-  if (!r) { pn_set_error("NULL argument"); return -1; }
-  if (rate_aligned(d_in, d_out)) return -1;
+// rate_frame: the launches alone — the caller is on the context's device and has checked the rows and, when active, the list
+// (pn_ids_check, distinct), which is what lets the pipelined path refuse a list BEFORE the frame takes a pipeline slot.
+static int rate_frame(pn_rate *r, const void *d_in, void *d_out, float *d_gr, int is_i16, bool active, const int32_t *ids, int n) {
   pn_ctx *c = r->c;
-  PN_ON_DEVICE(c);
   RateRows rows = {NULL, c->B};
   if (active) {                                      // (an empty list is legal, as for pn_process_*_active: nobody advances)
-    if (pn_ids_check(r->c->B, ids, n, true)) return -1;
     rows.n = n;
     if (n > 0 && !(rows.d_ids = stage_ids(c, ids, n))) return -1;
   }
   if (rate_up(r, d_in, is_i16, r->x48, rows)) return -1;
   if (active ? pn_process_f32_active(c, r->x48, r->y48, d_gr, ids, n) : pn_process_f32(c, r->x48, r->y48, d_gr)) return -1;
-  return rate_down(r, r->y48, d_out, is_i16, rows);
+  if (rate_down(r, r->y48, d_out, is_i16, rows)) return -1;
+  if (r->events.size() >= 4096 && rate_flush_events(r)) return -1;   // profiling left on: bound the pending events
+  return 0;
+}
+static int rate_process(pn_rate *r, const void *d_in, void *d_out, float *d_gr, int is_i16, bool active, const int32_t *ids, int n) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (rate_aligned(d_in, d_out)) return -1;
+  PN_ON_DEVICE(r->c);
+  if (active && pn_ids_check(r->c->B, ids, n, true)) return -1;
+  return rate_frame(r, d_in, d_out, d_gr, is_i16, active, ids, n);
 }
 extern "C" int pn_rate_process_f32(pn_rate *r, const float *d_in, float *d_out, float *d_gr) { return rate_process(r, d_in, d_out, d_gr, 0, false, NULL, 0); }
 extern "C" int pn_rate_process_i16(pn_rate *r, const int16_t *d_in, int16_t *d_out, float *d_gr) { return rate_process(r, d_in, d_out, d_gr, 1, false, NULL, 0); }
@@ -276,6 +319,73 @@ static int rate_process_host(pn_rate *r, const void *h_in, void *h_out, float *h
 }
 extern "C" int pn_rate_process_host_f32(pn_rate *r, const float *h_in, float *h_out, float *h_gr) { return rate_process_host(r, h_in, h_out, h_gr, 0); }
 extern "C" int pn_rate_process_host_i16(pn_rate *r, const int16_t *h_in, int16_t *h_out, float *h_gr) { return rate_process_host(r, h_in, h_out, h_gr, 1); }
+
+// ---- the pipelined host path ---------------------------------------------------------------------------------------------------
+// A converter's frame through the CONTEXT's pipeline (pn_host_pipe.cpp pipe_submit): the context's copy streams, slot counter,
+// events, g|r and report slots and its two-frames-in-flight bound, so pn_host_wait, pn_host_frames_delivered and
+// pn_host_next_report count frames of either kind in submission order.  The converter adds its own staging rows — slot 0 is
+// io_in / io_out, slot 1 is allocated once — and the frame body rate_frame.  x48 / y48 stay single: the compute stream
+// serialises the frames.  Whole rows travel both ways; on a mixed converter that is 480 samples per stream, of which the
+// kernels read and write each stream's own n_s, with no landing buffer and no host copy.
+static int rate_pipe_prepare(pn_rate *r) {           // (the caller is on the context's device)
+  pn_ctx *c = r->c;
+  const size_t bytes = (size_t)c->B * r->n * 4;
+  // (a mixed converter's rows are zeroed like slot 0's, so that the part of an output row no kernel writes is never stale memory)
+  if (!r->io_in1 && dev_alloc_into(r->allocs, r->bytes, c->stream, &r->io_in1, bytes, r->mixed)) return -1;
+  if (!r->io_out1 && dev_alloc_into(r->allocs, r->bytes, c->stream, &r->io_out1, bytes, r->mixed)) return -1;
+  return pn_host_pipeline_prepare(c);
+}
+extern "C" int pn_rate_host_pipeline_prepare(pn_rate *r) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  PN_ON_DEVICE(r->c);
+  return rate_pipe_prepare(r);
+}
+struct RateFrame { pn_rate *r; int is_i16; bool active; const int32_t *ids; int n; };
+static int rate_frame_body(void *arg, void *d_in, void *d_out, float *d_gr) {
+  const RateFrame &f = *static_cast<const RateFrame *>(arg);
+  return rate_frame(f.r, d_in, d_out, d_gr, f.is_i16, f.active, f.ids, f.n);
+}
+static int rate_submit_host(pn_rate *r, const void *h_in, void *h_out, float *h_gr, int is_i16, bool active, const int32_t *ids, int n) {
+  if (!r || !h_in || !h_out) { pn_set_error("NULL argument"); return -1; }
+  pn_ctx *c = r->c;
+  if (active && pn_ids_check(c->B, ids, n, true)) return -1;          // refused before the frame takes a pipeline slot
+  PN_ON_DEVICE(c);
+  if (rate_pipe_prepare(r)) return -1;
+  const PipeStaging st = {{r->io_in, r->io_in1}, {r->io_out, r->io_out1}, (size_t)c->B * r->n * (is_i16 ? 2 : 4)};
+  RateFrame f = {r, is_i16, active, ids, n};
+  return pipe_submit(c, st, h_in, h_out, h_gr, rate_frame_body, &f);
+}
+extern "C" int pn_rate_submit_host_f32(pn_rate *r, const float *h_in, float *h_out, float *h_gr) { return rate_submit_host(r, h_in, h_out, h_gr, 0, false, NULL, 0); }
+extern "C" int pn_rate_submit_host_i16(pn_rate *r, const int16_t *h_in, int16_t *h_out, float *h_gr) { return rate_submit_host(r, h_in, h_out, h_gr, 1, false, NULL, 0); }
+extern "C" int pn_rate_submit_host_f32_active(pn_rate *r, const float *h_in, float *h_out, float *h_gr, const int32_t *ids, int n) { return rate_submit_host(r, h_in, h_out, h_gr, 0, true, ids, n); }
+extern "C" int pn_rate_submit_host_i16_active(pn_rate *r, const int16_t *h_in, int16_t *h_out, float *h_gr, const int32_t *ids, int n) { return rate_submit_host(r, h_in, h_out, h_gr, 1, true, ids, n); }
+
+// ---- timing the two kernels ----------------------------------------------------------------------------------------------------
+extern "C" int pn_rate_set_profiling(pn_rate *r, int enable) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (enable && r->event_pool.size() < 512) {         // two scopes a frame: enough for 128 frames between two reads; created outside any timed region
+    PN_ON_DEVICE(r->c);
+    while (r->event_pool.size() < 512) { hipEvent_t e; PN_HIP_CHECK(hipEventCreate(&e)); r->event_pool.push_back(e); }
+  }
+  r->profiling = enable != 0;
+  return 0;
+}
+extern "C" int pn_rate_kernel_time(pn_rate *r, const char *name, double *total_ms, int64_t *launches) {
+  if (!r || !name) { pn_set_error("NULL argument"); return -1; }
+  PN_ON_DEVICE(r->c);
+  if (rate_flush_events(r)) return -1;
+  for (int i = 0; i < RF_COUNT; i++)
+    if (!strcmp(name, kRateFamily[i])) { if (total_ms) *total_ms = r->fam_ms[i]; if (launches) *launches = r->fam_n[i]; return 0; }
+  pn_set_error("unknown converter kernel '%s' (rate_up, rate_down)", name);
+  return -1;
+}
+extern "C" int pn_rate_reset_profile(pn_rate *r) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  PN_ON_DEVICE(r->c);
+  if (rate_flush_events(r)) return -1;
+  for (int i = 0; i < RF_COUNT; i++) { r->fam_ms[i] = 0; r->fam_n[i] = 0; }
+  return 0;
+}
 
 // ---- state records -----------------------------------------------------------------------------------------------------------
 // Host forms only: synchronous, through the context's host form of a record transfer (host_records_sync).
@@ -308,4 +418,34 @@ extern "C" int pn_rate_import_streams_host(pn_rate *r, const int32_t *ids, int n
   if (rate < 0) return -1;
   if (pn_records_check(h_records, n, 4 * pn_rate_record_words(pn_rate_factor(rate)), [&](const void *rec, size_t b) { return pn_rate_record_check(rec, b, rate); })) return -1;
   return rate_records_host(r, rate, true, ids, n, const_cast<void *>(h_records));
+}
+
+// Device forms: asynchronous on the context's stream and ordered like pn_ctx_export_streams / pn_ctx_import_streams.  Records are
+// pn_rate_record_stride(r) apart — on a mixed converter the largest record's size, which is what lets one call move streams of
+// different rates: each record carries its own stream's rate, and the kernel takes rate and tail length per slot from the factor
+// table.  Everything the host can judge is refused before anything is launched (pn_rate_mixed.h pn_rate_records_list_check).
+static_assert(PN_RATE_STATE_MAX_BYTES == PN_RATE_STATE_HEADER_BYTES + 4 * (PN_RATE_UP_TAIL + 2 * PN_RATE_TAPS * PN_RATE_MAX_L) && PN_RATE_STATE_MAX_BYTES % 16 == 0,
+              "the fixed stride is the 8000 Hz record, a whole number of 16-byte groups");
+extern "C" size_t pn_rate_state_max_bytes(void) { return PN_RATE_STATE_MAX_BYTES; }
+extern "C" size_t pn_rate_record_stride(const pn_rate *r) {
+  if (!r) { pn_set_error("NULL argument"); return 0; }
+  return r->mixed ? (size_t)PN_RATE_STATE_MAX_BYTES : 4 * pn_rate_record_words(r->L);
+}
+static int rate_records_dev(pn_rate *r, bool import, const int32_t *ids, int n, void *d_records, int32_t *d_status) {
+  if (!r || n < 0 || (n > 0 && (!ids || !d_records || (import && !d_status)))) { pn_set_error("bad argument"); return -1; }
+  if (n == 0) return 0;
+  if ((uintptr_t)d_records & 15) { pn_set_error("records must be 16-byte aligned"); return -1; }
+  pn_ctx *c = r->c;
+  if (pn_rate_records_list_check(c->B, r->mixed ? r->rates.data() : NULL, ids, n, import)) return -1;
+  PN_ON_DEVICE(c);
+  const int *d = stage_ids(c, ids, n);
+  if (!d) return -1;
+  pn_launch_rate_records_dev(c->stream, d, n, r->mixed ? r->factors : NULL, r->L, r->tail_up, r->tail_down, r->td, d_records,
+                             (int)(pn_rate_record_stride(r) / 4), d_status, import ? 1 : 0);
+  PN_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+extern "C" int pn_rate_export_streams(pn_rate *r, const int32_t *ids, int n, void *d_records) { return rate_records_dev(r, false, ids, n, d_records, NULL); }
+extern "C" int pn_rate_import_streams(pn_rate *r, const int32_t *ids, int n, const void *d_records, int32_t *d_status) {
+  return rate_records_dev(r, true, ids, n, const_cast<void *>(d_records), d_status);
 }

@@ -291,6 +291,42 @@ __global__ __launch_bounds__(64) void pn_rate_records_kernel(const int *__restri
   }
 }
 
+// Device-side records (pn_rate_export_streams / pn_rate_import_streams): record i <-> the two tails of stream ids[i], records
+// stride_words apart; one block per record.  The record's rate and tail length are the SLOT's: L = factors[s] in a mixed
+// converter (the table a preceding rate change has already written, in stream order), L_all in a single-rate one; a slot without
+// a filter (48000, which the host refuses before the launch) moves nothing.
+//   gather   the header of the slot's rate, the two tails oldest first, zeros from the record's size up to the stride
+//   scatter  lane 0 gives the header's verdict (pn_rate_header_verdict, the host check's own) against the slot's rate and writes
+//            it to status[i]; behind the barrier the block copies the tails of an accepted record and leaves those of a refused
+//            one untouched — the other records of the call are still imported (the contract of pn_ss_scatter_kernel)
+__global__ __launch_bounds__(64) void pn_rate_records_dev_kernel(const int *__restrict__ ids, const int *__restrict__ factors, int L_all, float *__restrict__ tail_up,
+                                                                 float *__restrict__ tail_down, int td_stride, uint32_t *__restrict__ rec, int stride_words,
+                                                                 int *__restrict__ status, int scatter) {
+  const size_t s = (size_t)ids[blockIdx.x];
+  int L = factors ? factors[s] : L_all;                      // block-uniform
+  if (L != 6 && L != 3 && L != 2) L = 0;
+  const int rate = L ? 48000 / L : 0, td = 2 * RT_T * L, body_words = L ? RT_UT + td : 0, hdr_words = PN_RATE_STATE_HEADER_BYTES / 4;
+  uint32_t *r = rec + (size_t)blockIdx.x * stride_words;
+  float *body = reinterpret_cast<float *>(r + hdr_words);
+  __shared__ int verdict;
+  if (scatter) {
+    if (threadIdx.x == 0) {
+      const uint4 h = *reinterpret_cast<const uint4 *>(r);
+      verdict = pn_rate_header_verdict(h.x, h.y, h.z, h.w, rate);
+      status[blockIdx.x] = verdict;
+    }
+    __syncthreads();
+    if (verdict != PN_SS_OK) return;
+  } else {
+    if (L && threadIdx.x == 0) *reinterpret_cast<uint4 *>(r) = make_uint4(PN_RATE_STATE_MAGIC, PN_RATE_STATE_VERSION, 4u * (hdr_words + body_words), (uint32_t)rate);
+    for (int i = (L ? hdr_words + body_words : 0) + threadIdx.x; i < stride_words; i += blockDim.x) r[i] = 0u;
+  }
+  for (int i = threadIdx.x; i < body_words; i += blockDim.x) {
+    float *p = i < RT_UT ? tail_up + s * RT_UT + i : tail_down + s * td_stride + (i - RT_UT);
+    if (scatter) *p = body[i]; else body[i] = *p;
+  }
+}
+
 #define RT_DISPATCH(kernel, ...)                                                                                     \
   do {                                                                                                               \
     const dim3 grid((n_rows + RT_WPB - 1) / RT_WPB), block(RT_LANES * RT_WPB);                                         \
@@ -337,4 +373,11 @@ int pn_launch_rate_down_mixed(hipStream_t st, int is_i16, int n_rows, const int 
 void pn_launch_rate_set_factors(hipStream_t st, const int *d_ids, const int *d_vals, int n, int *d_factors) {
   if (n <= 0) return;
   hipLaunchKernelGGL(pn_rate_set_factors_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d_ids, d_vals, n, d_factors);
+}
+// the device-side records: d_factors (mixed) or factor (single-rate) gives each slot's rate; stride_words between two records
+void pn_launch_rate_records_dev(hipStream_t st, const int *d_ids, int n, const int *d_factors, int factor, float *tail_up, float *tail_down, int td_stride,
+                                void *rec, int stride_words, int *d_status, int scatter) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(pn_rate_records_dev_kernel, dim3(n), dim3(64), 0, st, d_ids, d_factors, factor, tail_up, tail_down, td_stride, (uint32_t *)rec, stride_words,
+                     d_status, scatter);
 }

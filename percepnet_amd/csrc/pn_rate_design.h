@@ -56,19 +56,37 @@ static inline void pn_rate_record_header(uint32_t hdr[4], int rate_hz) {
   hdr[0] = PN_RATE_STATE_MAGIC; hdr[1] = PN_RATE_STATE_VERSION;
   hdr[2] = (uint32_t)(4 * pn_rate_record_words(pn_rate_factor(rate_hz))); hdr[3] = (uint32_t)rate_hz;
 }
+// The verdict of a record HEADER in a slot of rate_hz (one of the three rates), stated once: the four header words as read
+// (little-endian), in the order every record check keeps — magic, version, the rate, then the size word.  Side-effect-free (no
+// message, no memory access), so that the device import (pn_rate.hip pn_rate_records_dev_kernel) and the host check below give the same
+// verdict for the same bytes.
+#if defined(__HIPCC__)
+#define PN_RATE_HD __host__ __device__
+#else
+#define PN_RATE_HD
+#endif
+PN_RATE_HD static inline int pn_rate_header_verdict(uint32_t magic, uint32_t version, uint32_t size_word, uint32_t rate_word, int rate_hz) {
+  const int L = rate_hz == 8000 ? 6 : rate_hz == 16000 ? 3 : rate_hz == 24000 ? 2 : 0;
+  if (!L) return PN_SS_BAD_RATE;
+  if (magic != PN_RATE_STATE_MAGIC) return PN_SS_BAD_MAGIC;
+  if (version != PN_RATE_STATE_VERSION) return PN_SS_BAD_VERSION;
+  if ((int32_t)rate_word != rate_hz) return PN_SS_BAD_RATE;
+  if (size_word != (uint32_t)(PN_RATE_STATE_HEADER_BYTES + 4 * (PN_RATE_UP_TAIL + 2 * PN_RATE_TAPS * L))) return PN_SS_BAD_SIZE;
+  return PN_SS_OK;
+}
 // is `bytes` bytes at `record` one state record of a converter of rate_hz?  Reads the 16 header bytes only, and only when
-// they are there.  The verdicts every record shares (pn_host_rules.h pn_record_header_check), then the rate, then the size.
+// they are there.  The header's verdict is pn_rate_header_verdict's; this function adds the length of the buffer and the words.
 static inline int pn_rate_record_check(const void *record, size_t bytes, int rate_hz) {
   const int L = pn_rate_factor(rate_hz);
   if (!record) { pn_set_error("NULL argument"); return PN_SS_BAD_ARG; }
   if (!L) { pn_set_error("rate %d Hz: a converter takes 8000, 16000 or 24000", rate_hz); return PN_SS_BAD_RATE; }
   const size_t want = 4 * pn_rate_record_words(L);
   const unsigned char *r = static_cast<const unsigned char *>(record);
-  const int v = pn_record_header_check(r, bytes, PN_RATE_STATE_MAGIC, PN_RATE_STATE_VERSION, "rate-state");
-  if (v == PN_SS_BAD_SIZE) pn_set_error("rate-state record of %zu bytes: a record at %d Hz has %zu", bytes, rate_hz, want);
-  if (v) return v;
-  if ((int32_t)pn_le32(r + 12) != rate_hz) { pn_set_error("rate-state record written at %d Hz, this converter runs at %d", (int32_t)pn_le32(r + 12), rate_hz); return PN_SS_BAD_RATE; }
-  if (pn_le32(r + 8) != want || bytes != want) {
+  if (bytes < 16) { pn_set_error("rate-state record of %zu bytes: a record at %d Hz has %zu", bytes, rate_hz, want); return PN_SS_BAD_SIZE; }
+  const int v = pn_rate_header_verdict(pn_le32(r), pn_le32(r + 4), pn_le32(r + 8), pn_le32(r + 12), rate_hz);
+  if (v == PN_SS_BAD_MAGIC || v == PN_SS_BAD_VERSION) return pn_record_header_check(r, bytes, PN_RATE_STATE_MAGIC, PN_RATE_STATE_VERSION, "rate-state");   // (words it)
+  if (v == PN_SS_BAD_RATE) { pn_set_error("rate-state record written at %d Hz, this converter runs at %d", (int32_t)pn_le32(r + 12), rate_hz); return v; }
+  if (v == PN_SS_BAD_SIZE || bytes != want) {
     pn_set_error("rate-state record of %zu bytes (header: %u), a record at %d Hz has %zu", bytes, pn_le32(r + 8), rate_hz, want);
     return PN_SS_BAD_SIZE;
   }

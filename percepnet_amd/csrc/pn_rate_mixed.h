@@ -55,3 +55,14 @@ static inline int pn_rate_mixed_record_rate(const int32_t *cur_rates, const int3
   }
   return R;
 }
+
+// The list of a DEVICE-side record call (pn_rate_export_streams / pn_rate_import_streams), host only: ids[0..n) in range —
+// distinct where the streams are written (import) — and none of them a 48000 slot, which has no converter state to move.
+// cur_rates: the rate of every stream as last set ([B]; NULL = a single-rate converter, which has no 48000 slot).  The fixed
+// record stride lifts the one-rate-per-call rule above: the listed streams may run at different rates.  0, or -1 with the error set.
+static inline int pn_rate_records_list_check(int B, const int32_t *cur_rates, const int32_t *ids, int n, bool distinct) {
+  if (pn_ids_check(B, ids, n, distinct)) return -1;
+  for (int i = 0; cur_rates && i < n; i++)
+    if (cur_rates[ids[i]] == 48000) { pn_set_error("stream %d runs at 48000 Hz: it has no converter state to move", (int)ids[i]); return -1; }
+  return 0;
+}
