@@ -146,6 +146,15 @@ class Oracle:
             o[k] = o[k].view(np.complex64)[..., 0]
         return o
 
+    def flush_mode(self, on):
+        """Test mutant (pno_debug_flush_mode): FTZ and DAZ of the CALLING thread on or off -> the previous state as a bool, or
+        -1 on a build without SSE.  It reaches this thread's numpy arithmetic too, and not run_batch's worker threads: restore
+        it in a `finally`."""
+        self.lib.pno_debug_flush_mode.argtypes = [ctypes.c_int]
+        self.lib.pno_debug_flush_mode.restype = ctypes.c_int
+        prev = self.lib.pno_debug_flush_mode(int(bool(on)))
+        return prev if prev < 0 else bool(prev)
+
     def train_run(self, speech, noisy, want_test_pcm=True):
         """The `percepNet` training binary on in-memory PCM -> (records [count,138], test_output [count,480])."""
         speech = np.ascontiguousarray(speech, dtype=np.int16); noisy = np.ascontiguousarray(noisy, dtype=np.int16)

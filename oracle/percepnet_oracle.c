@@ -647,6 +647,24 @@ int pno_frame_stages(pno_state *st, const float *in, float *X_ri, float *P_ri, f
 /* the stream's comb_buf (denoise.cpp:32: 5760 samples, oldest first) */
 void pno_state_comb_buf(const pno_state *st, float *dst5760) { memcpy(dst5760, st->comb_buf, sizeof(st->comb_buf)); }
 
+/* TEST INFRASTRUCTURE for tests/test_tiny_levels_host.py: the "flushing kernel" mutant.  Sets (on != 0) or clears FTZ and DAZ
+   in the CALLING THREAD's MXCSR, so that every fp32 operation this thread performs from now on (the oracle's, through its
+   single-stream entry points, and numpy's) flushes subnormal results and reads subnormal operands as zero: what a kernel
+   with one flushing instruction does, applied to all of them.  Returns the previous state (1 = FTZ or DAZ was set), or -1
+   on a build without SSE, where nothing is changed.  No arithmetic above depends on it; the tables are built once, by
+   whichever call comes first, so a caller runs the plain oracle before the mutant. */
+#if defined(__SSE__)
+#include <xmmintrin.h>
+int pno_debug_flush_mode(int on) {
+  const unsigned FTZ_DAZ = 0x8000u | 0x0040u;
+  const unsigned csr = _mm_getcsr();
+  _mm_setcsr(on ? (csr | FTZ_DAZ) : (csr & ~FTZ_DAZ));
+  return (csr & FTZ_DAZ) != 0;
+}
+#else
+int pno_debug_flush_mode(int on) { (void)on; return -1; }
+#endif
+
 /* rnnoise_process_frame denoise.cpp:508-547 */
 static void post_filtering(float *g, const float *Ey);
 

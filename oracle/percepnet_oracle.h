@@ -59,6 +59,8 @@ int pno_frame_features(pno_state *st, const float *in, float *feat70);
 int pno_frame_stages(pno_state *st, const float *in, float *X_ri, float *P_ri, float *Y_ri, float *Ex, float *Ep,
                      float *Exp, float *Ey, int *period, float *feat70);
 void pno_state_comb_buf(const pno_state *st, float *dst5760);
+/* test mutant: FTZ+DAZ of the calling thread's MXCSR on/off; returns the previous state, -1 without SSE */
+int pno_debug_flush_mode(int on);
 float pno_tansig(float x);
 float pno_sigmoid(float x);
 void pno_dense(const float *bias, const float *w, int nin, int nn, int act, float *out, const float *in);
