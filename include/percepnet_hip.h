@@ -425,7 +425,7 @@ int pn_featgen_run_files(int device, int n_jobs, const char *const *speech_paths
    The engine runs in float between the two conversions; int16 exists only at the edges: input (float)v / 32768, output
    trunc(z * 32768) wrapped to 16 bit, or saturated while pn_ctx_set_output_saturate is on.  The frame report (pn_ctx_set_report)
    stays that of the 48 kHz signal inside the engine: 480 samples per frame, the engine's own 2880-sample delay, levels before the
-   down-conversion.
+   down-conversion.  8-bit G.711 rows are the int16 edge with the companding outside it ("G.711 streams", below).
    NOT provided: other rates.
 
    Host only, needing no GPU:
@@ -573,6 +573,68 @@ int pn_rate_is_mixed(const pn_rate *r);
 int pn_rate_row_samples(const pn_rate *r);
 int pn_rate_set_stream_rates(pn_rate *r, const int32_t *ids, int n, const int32_t *rates_hz);
 int pn_rate_get_stream_rates(const pn_rate *r, int32_t *h_rates);
+
+/* ---- G.711 streams: 8-bit mu-law and A-law rows at the converter's edges ------------------------------------------------------- */
+/* A third sample format beside _f32 and _i16 on a pn_rate, single-rate or mixed: one byte per sample, G.711 mu-law (PCMU) or
+   A-law (PCMA), with a law PER STREAM.  The engine, the filters, the tails, the delays, the records (format, version, sizes)
+   and the _f32 / _i16 entry points are untouched: the 8-bit format is the int16 format with the companding outside it,
+       in    x = (float)dec(b) / 32768
+       out   enc(c), c = exactly the int16 the _i16 down-conversion writes for that sample from t = z * 32768 — through the
+             wrapping cast, or the saturating one while pn_ctx_set_output_saturate is on
+   so a G.711 stream gives, bit for bit, the encoding of what the _i16 path gives on the decoded samples.  It applies at whatever
+   rate a stream runs, 48000 in a mixed converter included (L = 1: decode, engine, encode).  A G.711 caller should turn
+   pn_ctx_set_output_saturate ON: in wrap mode a clipped sample wraps before it is encoded, exactly as on the int16 path.
+
+   Arithmetic (csrc/pn_g711.h; integer formulas with one answer per input, reproduced by tests/g711_model.py; all values int32,
+   b the byte, v the linear value in the int16 range).
+     decode  mu-law  u = ~b & 0xFF, e = (u >> 4) & 7, m = u & 15, mag = (((m << 3) + 132) << e) - 132, v = (u & 0x80) ? -mag : mag
+                     range +-32124; 0xFF and 0x7F both give 0
+             A-law   a = b ^ 0x55, e = (a >> 4) & 7, m = a & 15, mag = e == 0 ? (m << 4) + 8 : ((m << 4) + 264) << (e - 1),
+                     v = (a & 0x80) ? mag : -mag;  range +-32256, never 0 (0xD5 -> +8, 0x55 -> -8)
+     encode  neg = v < 0, mag = neg ? ~v : v (the one's-complement magnitude of the ITU software tool library, both laws)
+             mu-law  p = min((mag >> 2) + 33, 8191), e = floor(log2 p) - 5, m = (p >> (e + 1)) & 15,
+                     b = ~((neg ? 0x80 : 0) | e << 4 | m) & 0xFF
+             A-law   e = mag < 256 ? 0 : floor(log2 mag) - 7, m = (e == 0 ? mag >> 4 : mag >> (e + 3)) & 15,
+                     b = ((neg ? 0 : 0x80) | e << 4 | m) ^ 0x55
+   enc(dec(b)) == b for every byte except mu-law 0x7F -> 0xFF; both decoders equal CPython's audioop.ulaw2lin / alaw2lin, the
+   A-law encoder equals audioop.lin2alaw, the mu-law encoder equals audioop.lin2ulaw(v) for v >= 0 and audioop.lin2ulaw(~v) ^ 0x80
+   for v < 0 (audioop negates after shifting and so differs for 381 negative values).
+
+   Host only, needing no GPU: pn_g711_decode / pn_g711_encode, n samples of one law; -1 for a law that is neither of the two or a
+   NULL pointer.  pn_rate_laws_check: 0 when laws[0..n) are all out of the two, else -1 with pn_last_error naming the first bad index.
+
+   The law per stream lives in the converter, like a mixed converter's rates.  It is a SETTING, not state: mu-law for every stream
+   of a new converter; records do not carry it; pn_rate_reset, pn_rate_reset_streams, pn_rate_set_stream_rates and the record
+   calls keep it — the importing caller sets the slot's law, as it sets the slot's rate.
+   pn_rate_set_stream_laws: streams ids[i] (distinct, in range) continue under laws[i] (out of the two), on either kind of
+   converter; anything else refuses the call with -1, nothing changed or launched; n == 0 is a no-op.  Asynchronous on the
+   context's stream and ordered exactly like pn_rate_set_stream_rates: frames submitted before it run under the old law, frames
+   after it under the new one, on the pipelined path too; the caller may reuse its arrays on return.  It touches no tail.
+   pn_rate_get_stream_laws: the laws as last set, h_laws [n_streams].
+
+   Frames and kernels: the byte twins of the _i16 entry points above, with the same ordering, id-list, failure and lifetime rules.
+   Rows are [n_streams][pn_rate_row_samples(r)] BYTES — 80 | 160 | 240 on a single-rate converter, 480 on a mixed one, each a
+   multiple of 16 — at 16-byte aligned addresses.  In a mixed converter the rest of an input row is ignored, the rest of an output
+   row is left untouched on the synchronous paths and is unspecified on the pipelined one.  pn_rate_submit_host_g711* go through
+   the context's pipeline and may be interleaved with the other pn_rate_submit_host_* calls and with pn_submit_host_*;
+   pn_host_next_report works unchanged.
+   NOT provided: linear and companded rows in one call; G.711 on pn_process_* without a converter (a mixed converter whose slots
+   run at 48000 covers it); G.711 Appendix I / II (packet-loss concealment, comfort noise).  How well the model, trained on
+   full-band linear speech, cleans companded narrowband input is not measured. */
+#define PN_G711_ULAW 0
+#define PN_G711_ALAW 1
+int pn_g711_decode(int law, const uint8_t *in, int16_t *out, size_t n);
+int pn_g711_encode(int law, const int16_t *in, uint8_t *out, size_t n);
+int pn_rate_laws_check(const int32_t *laws, int n);
+int pn_rate_set_stream_laws(pn_rate *r, const int32_t *ids, int n, const int32_t *laws);
+int pn_rate_get_stream_laws(const pn_rate *r, int32_t *h_laws);
+int pn_rate_up_g711(pn_rate *r, const uint8_t *d_in, float *d_out48, const int32_t *ids, int n_ids);
+int pn_rate_down_g711(pn_rate *r, const float *d_in48, uint8_t *d_out, const int32_t *ids, int n_ids);
+int pn_rate_process_g711(pn_rate *r, const uint8_t *d_in, uint8_t *d_out, float *d_gr);
+int pn_rate_process_g711_active(pn_rate *r, const uint8_t *d_in, uint8_t *d_out, float *d_gr, const int32_t *ids, int n);
+int pn_rate_process_host_g711(pn_rate *r, const uint8_t *h_in, uint8_t *h_out, float *h_gr);
+int pn_rate_submit_host_g711(pn_rate *r, const uint8_t *h_in, uint8_t *h_out, float *h_gr);
+int pn_rate_submit_host_g711_active(pn_rate *r, const uint8_t *h_in, uint8_t *h_out, float *h_gr, const int32_t *ids, int n);
 
 const char *pn_last_error(void);
 const char *pn_version(void);

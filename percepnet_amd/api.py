@@ -23,6 +23,7 @@ RATES = (8000, 16000, 24000)
 MIXED_RATES = (8000, 16000, 24000, 48000)     # the rate of a STREAM of a mixed converter (pn_rate_create_mixed); 48000 is a copy
 RATE_MIXED_ROW = 480                          # PN_RATE_MIXED_ROW: samples between two low-rate rows of a mixed converter
 RATE_TAPS = 16
+G711_ULAW, G711_ALAW = 0, 1                   # PN_G711_*: the law of a stream's 8-bit rows (pn_rate_set_stream_laws)
 # per-stream frame report (include/percepnet_hip.h pn_ctx_set_report): one record of PN_REPORT_WORDS 32-bit words per stream
 REPORT_WORDS = 8
 REPORT_DTYPE = np.dtype([("in_peak", "<f4"), ("in_energy", "<f4"), ("out_peak", "<f4"), ("out_energy", "<f4"), ("gain_mean", "<f4"),
@@ -163,6 +164,18 @@ def load_library():
         L.pn_rate_set_profiling.argtypes = [_vp, ctypes.c_int]
         L.pn_rate_kernel_time.argtypes = [_vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
         L.pn_rate_reset_profile.argtypes = [_vp]
+    if hasattr(L, "pn_g711_decode"):
+        for name in ("pn_g711_decode", "pn_g711_encode"):
+            getattr(L, name).argtypes = [ctypes.c_int, _vp, _vp, ctypes.c_size_t]
+        L.pn_rate_laws_check.argtypes = [_vp, ctypes.c_int]
+        L.pn_rate_set_stream_laws.argtypes = [_vp, _vp, ctypes.c_int, _vp]
+        L.pn_rate_get_stream_laws.argtypes = [_vp, _vp]
+        for name in ("pn_rate_up_g711", "pn_rate_down_g711"):
+            getattr(L, name).argtypes = [_vp, _vp, _vp, _vp, ctypes.c_int]
+        for name in ("pn_rate_process_g711", "pn_rate_process_host_g711", "pn_rate_submit_host_g711"):
+            getattr(L, name).argtypes = [_vp, _vp, _vp, _vp]
+        for name in ("pn_rate_process_g711_active", "pn_rate_submit_host_g711_active"):
+            getattr(L, name).argtypes = [_vp, _vp, _vp, _vp, _vp, ctypes.c_int]
     if hasattr(L, "pn_host_pipeline_prepare"):
         L.pn_host_pipeline_prepare.argtypes = [_vp]
     L.pn_ctx_debug_copy.restype = ctypes.c_longlong
@@ -530,6 +543,26 @@ def rate_mixed_delay_samples(rate_hz):
     return int(load_library().pn_rate_mixed_delay_samples(int(rate_hz)))
 
 
+def g711_decode(law, codes):
+    """G.711 bytes -> int16 of the same shape, law = G711_ULAW | G711_ALAW (pn_g711_decode, host only)."""
+    L = load_library()
+    b = np.ascontiguousarray(codes, dtype=np.uint8)
+    out = np.empty(b.shape, np.int16)
+    if L.pn_g711_decode(int(law), b.ctypes.data, out.ctypes.data, b.size) != 0:
+        raise PercepNetError(_err(L))
+    return out
+
+
+def g711_encode(law, pcm):
+    """int16 -> G.711 bytes of the same shape, law = G711_ULAW | G711_ALAW (pn_g711_encode, host only)."""
+    L = load_library()
+    v = np.ascontiguousarray(pcm, dtype=np.int16)
+    out = np.empty(v.shape, np.uint8)
+    if L.pn_g711_encode(int(law), v.ctypes.data, out.ctypes.data, v.size) != 0:
+        raise PercepNetError(_err(L))
+    return out
+
+
 class RateConverter:
     """8, 16 or 24 kHz streams through a 48 kHz Context (pn_rate): a converter beside `ctx` for all of its streams at ONE rate.
     It borrows the context (device, n_streams, HIP stream): close the converter before the context."""
@@ -592,6 +625,53 @@ class RateConverter:
 
     def down_i16_dev(self, d_in48, d_out, ids=None):
         self._kernel("pn_rate_down_i16", d_in48, d_out, ids)
+
+    # G.711 rows (one byte per sample, a law per stream): the byte twins of the int16 entry points
+    def set_stream_laws(self, ids, laws):
+        """Streams `ids` continue under `laws` (G711_ULAW | G711_ALAW) from the next frame on (pn_rate_set_stream_laws):
+        asynchronous, ordered like reset_streams; a setting that resets, rate changes and records leave alone."""
+        a, n = self._ids(ids)
+        w = np.ascontiguousarray(np.asarray(laws, dtype=np.int32).ravel())
+        if w.size != n:
+            raise PercepNetError(f"{w.size} laws for {n} streams")
+        self._chk(self.L.pn_rate_set_stream_laws(self.h, a.ctypes.data, n, w.ctypes.data))
+
+    def stream_laws(self):
+        """-> int32 [n_streams]: the laws as last set (pn_rate_get_stream_laws); mu-law for every stream of a new converter."""
+        w = np.empty(self.n_streams, np.int32)
+        self._chk(self.L.pn_rate_get_stream_laws(self.h, w.ctypes.data))
+        return w
+
+    def up_g711_dev(self, d_in, d_out48, ids=None):
+        self._kernel("pn_rate_up_g711", d_in, d_out48, ids)
+
+    def down_g711_dev(self, d_in48, d_out, ids=None):
+        self._kernel("pn_rate_down_g711", d_in48, d_out, ids)
+
+    def process_g711_dev(self, d_in, d_out, d_gr=None, ids=None):
+        if ids is None:
+            self._chk(self.L.pn_rate_process_g711(self.h, d_in, d_out, d_gr))
+        else:
+            a, n = self._ids(ids)
+            self._chk(self.L.pn_rate_process_g711_active(self.h, d_in, d_out, d_gr, a.ctypes.data, n))
+
+    def process_g711(self, frame, want_gr=True):
+        return self._host("pn_rate_process_host_g711", frame, np.uint8, want_gr)
+
+    def submit_host_g711(self, h_in, h_out, h_gr=None, h_report=None, ids=None):
+        self._submit("g711", h_in, h_out, h_gr, h_report, ids)
+
+    def run_g711(self, codes):
+        """percepnet_run --rate R --g711 semantics for a batch: codes uint8 [B, n_frames * frame] under the streams' laws -> uint8
+        [B, (n_frames - 1) * frame] (the first output frame dropped, like run_pcm)."""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8).reshape(self.n_streams, -1)
+        f, n = self.frame, codes.shape[1] // self.frame
+        out = np.zeros((self.n_streams, max(n - 1, 0) * f), np.uint8)
+        for t in range(n):
+            o, _ = self.process_g711(codes[:, t * f:(t + 1) * f], want_gr=False)
+            if t > 0:
+                out[:, (t - 1) * f:t * f] = o
+        return out
 
     # one whole frame, device pointers: [n_streams][frame] in and out at the low rate, d_gr [n_streams][68] or None
     def process_f32_dev(self, d_in, d_out, d_gr=None, ids=None):
@@ -762,6 +842,28 @@ class MixedRateConverter(RateConverter):
                 if t < frames[s]:
                     row[s, :n] = p[t * n:(t + 1) * n]
             o, _ = self.process_i16(row, want_gr=False)
+            for s, n in enumerate(ns):
+                if 0 < t < frames[s]:
+                    out[s][(t - 1) * n:t * n] = o[s, :n]
+        return out
+
+    def run_g711(self, codes):
+        """percepnet_run --rates .. --g711 semantics: codes = one uint8 array per stream at that stream's rate and under its law
+        -> a list of uint8 arrays, like run_pcm.  A stream that has ended is fed silence."""
+        if len(codes) != self.n_streams:
+            raise PercepNetError(f"{len(codes)} arrays for {self.n_streams} streams")
+        codes = [np.ascontiguousarray(p, dtype=np.uint8).ravel() for p in codes]
+        ns = [rate_mixed_frame_samples(r) for r in self.stream_rates()]
+        idle = [0xD5 if w == G711_ALAW else 0xFF for w in self.stream_laws()]
+        frames = [p.size // n for p, n in zip(codes, ns)]
+        out = [np.zeros(max(f - 1, 0) * n, np.uint8) for f, n in zip(frames, ns)]
+        row = np.zeros((self.n_streams, self.frame), np.uint8)
+        for t in range(max(frames, default=0)):
+            for s, (p, n) in enumerate(zip(codes, ns)):
+                row[s] = idle[s]
+                if t < frames[s]:
+                    row[s, :n] = p[t * n:(t + 1) * n]
+            o, _ = self.process_g711(row, want_gr=False)
             for s, n in enumerate(ns):
                 if 0 < t < frames[s]:
                     out[s][(t - 1) * n:t * n] = o[s, :n]

@@ -55,8 +55,10 @@ RESOURCE_LIMITS = {"pn_fe_spec_in_kernel": (0, 0), "pn_fe_spec_out_kernel": (0, 
                    "pn_backend_kernel": (0, 16),
                    # shadow-operand network kernels: everything in registers (a staging array once went to scratch: +30 % time)
                    "pn_gru_x3_kernel": (0, 0), "pn_dense_x3_kernel": (0, 0),
-                   "pn_gru_d_kernel": (0, 0)}
-RESOURCE_SOURCES = ("pn_dsp_fe_split_s.hip", "pn_dsp_fe_split_p.hip", "pn_dsp.hip", "pn_nn_x3.hip", "pn_nn_d.hip")
+                   "pn_gru_d_kernel": (0, 0),
+                   # the rate converter's kernels, in every sample format (float, int16, G.711): memory-bound rows through LDS
+                   "pn_rate_": (0, 0)}
+RESOURCE_SOURCES = ("pn_dsp_fe_split_s.hip", "pn_dsp_fe_split_p.hip", "pn_dsp.hip", "pn_nn_x3.hip", "pn_nn_d.hip", "pn_rate.hip")
 
 
 def parse_resource_remarks(text):

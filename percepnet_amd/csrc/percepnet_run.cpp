@@ -5,7 +5,7 @@
 // dropped, main.cpp:32-33); with a single pair ./feature_test.raw gets 68 floats per frame.
 //
 //   percepnet_run [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N]
-//                 [--rate 8000|16000|24000 | --rates R0,R1,..] [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
+//                 [--rate 8000|16000|24000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
 //                 in0.pcm out0.pcm [in1.pcm out1.pcm ...]
 //
 // --rate R: the files are raw int16 at R Hz instead of 48 kHz, in frames of n = 480 * R / 48000 samples (80 | 160 | 240): a rate
@@ -22,6 +22,13 @@
 // output row are written to its file: the rest of the row is unspecified on the pipelined path); the per-pair contract is the one
 // above.  With --slots a slot taken over by a pair of another rate continues at that rate (pn_rate_set_stream_rates for the
 // restart list, where --rate calls pn_rate_reset_streams), followed by the context's reset as always.
+//
+// --g711 ulaw|alaw (needs --rate or --rates; on its own it is refused with the usage text): the files are raw G.711 bytes, one per
+// sample, mu-law or A-law, read and written in frames of the pair's own size; the frames go through pn_rate_submit_host_g711 (the
+// converter's 8-bit rows: decode in front of the up-conversion, encode behind the down-conversion's int16 cast).  One law covers
+// all pairs; it is a setting of the converter's slots, set once, which slot resets and rate changes keep.  The rest of the
+// contract is unchanged: first output frame and partial tail dropped, --slots, --saturate (which a G.711 caller wants: a clipped
+// sample otherwise wraps before it is encoded), --report.
 //
 // --atten-lim DB: every stream takes out at most DB dB of noise (pn_ctx_set_atten_limit; 0 = the input, delayed; default: no
 // limit).  A slot reset clears a stream's limit (a reset slot is a new call), so the limit is set again on every reset slot.
@@ -66,7 +73,7 @@ struct ShardRes {
   // skip[s] = that frame is the pair's first output frame, which main.cpp:37 drops
   // (--report) rep: the frame's report records, pair[s]: the pair the frame of slot s belongs to
   // fs[s]: samples of that frame (the pair's own frame size; differs between slots only with --rates)
-  struct Slot { int16_t *in = NULL, *out = NULL; float *gr = NULL; uint32_t *rep = NULL; std::vector<FILE *> file; std::vector<char> skip, last; std::vector<int> pair; std::vector<size_t> fs; } slot[3];
+  struct Slot { char *in = NULL, *out = NULL; float *gr = NULL; uint32_t *rep = NULL; std::vector<FILE *> file; std::vector<char> skip, last; std::vector<int> pair; std::vector<size_t> fs; } slot[3];
   ~ShardRes() {
     for (auto &sl : slot) { pn_host_free(sl.in); pn_host_free(sl.out); pn_host_free(sl.gr); pn_host_free(sl.rep); }
     for (FILE *f : fin) if (f) fclose(f);
@@ -87,6 +94,7 @@ static float g_atten_lim = INFINITY;                  // --atten-lim: dB for eve
 static bool g_saturate = false, g_report = false;     // --saturate, --report
 static int g_rate = 0;                                // --rate: the files' sample rate (0: 48 kHz, no converter)
 static std::vector<int32_t> g_rates;                  // --rates: one rate per pair (empty: not given), a mixed converter
+static int g_g711 = -1;                               // --g711: the law of every pair's files (PN_G711_*; -1: linear int16)
 // --report: what a pair's written frames add up to (one report record = PN_REPORT_WORDS words, include/percepnet_hip.h)
 struct PairStat { long frames = 0; long long clipped = 0; float peak = 0.f; double e_in = 0, e_out = 0; };
 static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, int postfilter, bool tap, int n_slots) {
@@ -94,6 +102,8 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
   const bool mixed = !g_rates.empty();
   const int32_t *pair_rate = mixed ? g_rates.data() + sh->first : NULL;                // --rates: this shard's slice
   const size_t FS = mixed ? PN_RATE_MIXED_ROW : g_rate ? (size_t)pn_rate_frame_samples(g_rate) : PN_FRAME_SIZE;     // samples per pinned row
+  const size_t SW = g_g711 >= 0 ? 1 : sizeof(int16_t);                                  // bytes per sample in the files and the pinned rows
+  const int idle = g_g711 == PN_G711_ALAW ? 0xD5 : g_g711 == PN_G711_ULAW ? 0xFF : 0;   // a sample of silence
   auto pair_fs = [&](int pair) { return mixed ? (size_t)pn_rate_mixed_frame_samples(pair_rate[pair]) : FS; };       // ... per frame in a pair's files
   auto fail = [&](int rc, const std::string &msg) { sh->rc = rc; sh->err = msg; };
   ShardRes R;
@@ -110,6 +120,11 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
   if (g_rate && !(R.rt = pn_rate_create(cx, g_rate))) return fail(3, std::string("pn_rate_create: ") + pn_last_error());
   if (mixed && !(R.rt = pn_rate_create_mixed(cx, pair_rate))) return fail(3, std::string("pn_rate_create_mixed: ") + pn_last_error());   // slot s starts with pair s
   pn_rate *rt = R.rt;
+  if (g_g711 > 0) {                                     // every slot's law, once (a new converter's is mu-law)
+    std::vector<int32_t> all(B), laws(B, g_g711);
+    for (int s = 0; s < B; s++) all[s] = s;
+    if (pn_rate_set_stream_laws(rt, all.data(), B, laws.data())) return fail(3, std::string("pn_rate_set_stream_laws: ") + pn_last_error());
+  }
   if (postfilter) pn_ctx_set_postfilter(cx, 1);
   if ((g_saturate && pn_ctx_set_output_saturate(cx, 1)) || (g_report && pn_ctx_set_report(cx, 1))) return fail(3, pn_last_error());
   auto set_limit = [&](const int32_t *ids, int n) {     // --atten-lim on these slots (after creation and after every slot reset)
@@ -143,8 +158,8 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
   Slot *slot = R.slot;
   for (int k = 0; k < 3; k++) {
     Slot &sl = slot[k];
-    sl.in = (int16_t *)pn_host_alloc((size_t)B * FS * sizeof(int16_t));
-    sl.out = (int16_t *)pn_host_alloc((size_t)B * FS * sizeof(int16_t));
+    sl.in = (char *)pn_host_alloc((size_t)B * FS * SW);
+    sl.out = (char *)pn_host_alloc((size_t)B * FS * SW);
     sl.gr = (float *)pn_host_alloc((size_t)B * 68 * sizeof(float));
     if (g_report) sl.rep = (uint32_t *)pn_host_alloc((size_t)B * PN_REPORT_WORDS * sizeof(uint32_t));
     if (!sl.in || !sl.out || !sl.gr || (g_report && !sl.rep)) return fail(5, pn_last_error());
@@ -155,7 +170,7 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
     for (int s = 0; s < B; s++) {
       if (!sl.file[s]) continue;
       if (ftap) fwrite(&sl.gr[(size_t)s * 68], sizeof(float), 68, ftap);
-      if (!sl.skip[s]) fwrite(&sl.out[(size_t)s * FS], sizeof(int16_t), sl.fs[s], sl.file[s]);
+      if (!sl.skip[s]) fwrite(&sl.out[(size_t)s * FS * SW], SW, sl.fs[s], sl.file[s]);
       if (g_report) {
         PairStat &ps = stat[sl.pair[s]];
         if (!sl.skip[s]) {
@@ -181,9 +196,9 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
     Slot &sl = slot[t % 3];
     restart.clear(); restart_rates.clear();
     for (int s = 0; s < B; s++) {
-      int16_t *x = sl.in + (size_t)s * FS;
+      char *x = sl.in + (size_t)s * FS * SW;
       sl.file[s] = NULL; sl.skip[s] = 0; sl.last[s] = 0;
-      if (fin[s] && fread(x, sizeof(int16_t), pair_fs(cur_pair[s]), fin[s]) != pair_fs(cur_pair[s])) {
+      if (fin[s] && fread(x, SW, pair_fs(cur_pair[s]), fin[s]) != pair_fs(cur_pair[s])) {
         // this pair is finished (partial tail dropped, main.cpp:32-33): mark the frame it supplied last as its final one
         fclose(fin[s]); fin[s] = NULL;
         Slot &prev = slot[(t + 2) % 3];                // = frame t - 1
@@ -191,7 +206,7 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
         fout[s] = NULL;
         while (next_pair < P) {                        // the slot starts over with the next waiting pair, from this frame on
           if (!open_pair(s)) return;
-          if (fread(x, sizeof(int16_t), pair_fs(cur_pair[s]), fin[s]) == pair_fs(cur_pair[s])) {
+          if (fread(x, SW, pair_fs(cur_pair[s]), fin[s]) == pair_fs(cur_pair[s])) {
             restart.push_back(s); first[s] = 1;
             if (mixed) restart_rates.push_back(pair_rate[cur_pair[s]]);
             break;
@@ -201,7 +216,7 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
         if (!fin[s]) n_alive--;
       }
       if (fin[s]) { sl.file[s] = fout[s]; sl.skip[s] = first[s]; first[s] = 0; sl.pair[s] = cur_pair[s]; sl.fs[s] = pair_fs(cur_pair[s]); }
-      else memset(x, 0, FS * sizeof(int16_t));
+      else memset(x, idle, FS * SW);
     }
     if (n_alive == 0) break;
     if (!restart.empty() && (pn_ctx_reset_streams(cx, restart.data(), (int)restart.size()) ||
@@ -210,7 +225,9 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
                              set_limit(restart.data(), (int)restart.size()))) return fail(5, pn_last_error());
     if (g_report && pn_host_next_report(cx, sl.rep)) return fail(5, pn_last_error());
     // --rate, --rates: the converter's frame through the same pipeline
-    if (rt ? pn_rate_submit_host_i16(rt, sl.in, sl.out, sl.gr) : pn_submit_host_i16(cx, sl.in, sl.out, sl.gr)) return fail(5, pn_last_error());
+    if (g_g711 >= 0 ? pn_rate_submit_host_g711(rt, (const uint8_t *)sl.in, (uint8_t *)sl.out, sl.gr)
+                    : rt ? pn_rate_submit_host_i16(rt, (const int16_t *)sl.in, (int16_t *)sl.out, sl.gr)
+                         : pn_submit_host_i16(cx, (const int16_t *)sl.in, (int16_t *)sl.out, sl.gr)) return fail(5, pn_last_error());
     if (t >= 2) flush(slot[(t - 2) % 3]);
   }
   if (pn_host_wait(cx)) return fail(5, pn_last_error());
@@ -250,6 +267,11 @@ int main(int argc, char **argv) {
         q = end + 1;
       }
     }
+    else if (!strcmp(argv[ai], "--g711") && ai + 1 < argc) {        // the files are G.711 bytes of this law (needs --rate or --rates)
+      const char *v = argv[++ai];
+      g_g711 = !strcmp(v, "ulaw") ? PN_G711_ULAW : !strcmp(v, "alaw") ? PN_G711_ALAW : -1;
+      if (g_g711 < 0) { fprintf(stderr, "--g711: expected ulaw or alaw, got '%s'\n", v); return 1; }
+    }
     else if (!strcmp(argv[ai], "--no-numa")) g_numa = false;         // leave the host threads' CPU affinity alone
     else if (!strcmp(argv[ai], "--verbose")) g_verbose = true;       // one line per device: its NUMA binding
     else if (!strcmp(argv[ai], "--slots") && ai + 1 < argc) n_slots = atoi(argv[++ai]);   // concurrent streams per device: pairs queue for them
@@ -264,8 +286,9 @@ int main(int argc, char **argv) {
   }
   if (devices.empty()) devices.push_back(0);
   const int nfiles = argc - ai;
-  if (nfiles < 2 || (nfiles & 1)) {
-    fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N] [--rate 8000|16000|24000 | --rates R0,R1,..] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv[0]);
+  if (nfiles < 2 || (nfiles & 1) || (g_g711 >= 0 && !g_rate && g_rates.empty())) {
+    if (g_g711 >= 0 && !g_rate && g_rates.empty()) fprintf(stderr, "--g711 needs --rate or --rates: G.711 rows go through a rate converter\n");
+    fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N] [--rate 8000|16000|24000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv[0]);
     return 1;
   }
   const int B = nfiles / 2;

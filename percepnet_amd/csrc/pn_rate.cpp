@@ -7,6 +7,7 @@
 #include "pn_context.h"      // the context it borrows, the launchers, dev_alloc_into, stage_ids, the id rule, host_records_sync
 #include "pn_rate_design.h"
 #include "pn_rate_mixed.h"   // the mixed converter's host rules: the four rates, a rate change, one rate per record call
+#include "pn_g711.h"         // the 8-bit sample format: the companding and what a list of laws must be
 #include <string>
 #include <vector>
 
@@ -27,6 +28,10 @@ struct pn_rate {
   std::vector<int32_t> rates;   // [B]
   int *factors;                 // [B] device
   void *h_rows;                 // [B][480] 4-byte words, pinned
+  // G.711 rows (pn_rate_*_g711): the law of every stream as last set (host) and on the device, written in stream order like the
+  // factors.  A setting, not state: every reset, rate change and record call leaves it alone.  Default: mu-law everywhere
+  std::vector<int32_t> laws;    // [B]
+  int *d_laws = NULL;           // [B] device
   std::vector<void *> allocs;
   // timing of the two kernels (pn_rate_set_profiling): HIP events around their launches, like the context's families but owned
   // here; while it is off no event exists and none is recorded
@@ -84,6 +89,9 @@ extern "C" int pn_rate_state_check(const void *record, size_t bytes, int rate_hz
 extern "C" int pn_rate_mixed_frame_samples(int rate_hz) { return pn_rate_mixed_frame(rate_hz); }
 extern "C" int pn_rate_mixed_delay_samples(int rate_hz) { return pn_rate_mixed_delay(rate_hz); }
 extern "C" int pn_rate_mixed_rates_check(const int32_t *rates_hz, int n) { return pn_rate_mixed_rates_list_check(rates_hz, n); }
+extern "C" int pn_g711_decode(int law, const uint8_t *in, int16_t *out, size_t n) { return pn_g711_decode_host(law, in, out, n); }
+extern "C" int pn_g711_encode(int law, const int16_t *in, uint8_t *out, size_t n) { return pn_g711_encode_host(law, in, out, n); }
+extern "C" int pn_rate_laws_check(const int32_t *laws, int n) { return pn_g711_laws_list_check(laws, n); }
 
 // ---- lifecycle ---------------------------------------------------------------------------------------------------------------
 extern "C" void pn_rate_destroy(pn_rate *r) {
@@ -106,7 +114,7 @@ extern "C" pn_rate *pn_rate_create(pn_ctx *c, int rate_hz) {
   if (!_dg.ok) { pn_set_error("hipSetDevice(%d) failed", c->device); return NULL; }
   pn_rate *r = new pn_rate();
   r->c = c; r->rate = rate_hz; r->L = L; r->n = PN_FRAME / L; r->td = pn_rate_down_tail(L); r->bytes = 0;
-  r->mixed = false; r->factors = NULL; r->h_rows = NULL;
+  r->mixed = false; r->factors = NULL; r->h_rows = NULL; r->laws.assign((size_t)c->B, PN_G711_ULAW);
   const size_t B = (size_t)c->B, nt = (size_t)r->td + 1;
   float h[2][PN_RATE_MAX_TAPS];
   auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
@@ -114,7 +122,8 @@ extern "C" pn_rate *pn_rate_create(pn_ctx *c, int rate_hz) {
   if (alloc((void **)&r->taps_up, nt * 4, false) || alloc((void **)&r->taps_down, nt * 4, false) ||
       alloc((void **)&r->tail_up, B * PN_RATE_UP_TAIL * 4, true) || alloc((void **)&r->tail_down, B * r->td * 4, true) ||
       alloc((void **)&r->x48, B * PN_FRAME * 4, true) || alloc((void **)&r->y48, B * PN_FRAME * 4, true) ||
-      alloc(&r->io_in, B * r->n * 4, false) || alloc(&r->io_out, B * r->n * 4, false) || alloc((void **)&r->io_gr, B * 68 * 4, false)) goto fail;
+      alloc(&r->io_in, B * r->n * 4, false) || alloc(&r->io_out, B * r->n * 4, false) || alloc((void **)&r->io_gr, B * 68 * 4, false) ||
+      alloc((void **)&r->d_laws, B * sizeof(int), true)) goto fail;
   // (synchronous copies: h is on this stack)
   if (hipMemcpyAsync(r->taps_up, h[0], nt * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
       hipMemcpyAsync(r->taps_down, h[1], nt * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
@@ -134,7 +143,7 @@ extern "C" pn_rate *pn_rate_create_mixed(pn_ctx *c, const int32_t *rates_hz) {
   if (!_dg.ok) { pn_set_error("hipSetDevice(%d) failed", c->device); return NULL; }
   pn_rate *r = new pn_rate();
   r->c = c; r->rate = 0; r->L = 0; r->n = PN_RATE_MIXED_ROW; r->td = pn_rate_down_tail(PN_RATE_MAX_L); r->bytes = 0;
-  r->mixed = true; r->factors = NULL; r->h_rows = NULL;
+  r->mixed = true; r->factors = NULL; r->h_rows = NULL; r->laws.assign((size_t)c->B, PN_G711_ULAW);
   const size_t B = (size_t)c->B;
   if (rates_hz) r->rates.assign(rates_hz, rates_hz + B); else r->rates.assign(B, 48000);
   static const int kL[3] = {6, 3, 2};
@@ -153,7 +162,7 @@ extern "C" pn_rate *pn_rate_create_mixed(pn_ctx *c, const int32_t *rates_hz) {
       alloc((void **)&r->tail_up, B * PN_RATE_UP_TAIL * 4, true) || alloc((void **)&r->tail_down, B * r->td * 4, true) ||
       alloc((void **)&r->x48, B * PN_FRAME * 4, true) || alloc((void **)&r->y48, B * PN_FRAME * 4, true) ||
       alloc(&r->io_in, B * r->n * 4, true) || alloc(&r->io_out, B * r->n * 4, true) || alloc((void **)&r->io_gr, B * 68 * 4, false) ||
-      alloc((void **)&r->factors, B * sizeof(int), false)) goto fail;
+      alloc((void **)&r->factors, B * sizeof(int), false) || alloc((void **)&r->d_laws, B * sizeof(int), true)) goto fail;
   if (hipHostMalloc(&r->h_rows, B * r->n * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); r->h_rows = NULL; pn_set_error("rate converter: no pinned memory for %zu bytes", B * r->n * 4); goto fail; }
   // (synchronous copies: the sources are locals)
   if (hipMemcpyAsync(r->taps_up, h[0].data(), h[0].size() * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
@@ -189,6 +198,26 @@ extern "C" int pn_rate_set_stream_rates(pn_rate *r, const int32_t *ids, int n, c
   pn_launch_zero_rows(r->c->stream, r->tail_down, r->td, r->td, 1, 0, d, n);
   PN_HIP_CHECK(hipGetLastError());
   for (int i = 0; i < n; i++) r->rates[ids[i]] = rates_hz[i];
+  return 0;
+}
+
+// A law change of the listed streams (G.711 rows), asynchronous and ordered like a rate change: the ids and the new laws go through
+// the context's id ring in one copy, one launch writes the table.  No tail is touched: the law is a setting of the edges.
+extern "C" int pn_rate_set_stream_laws(pn_rate *r, const int32_t *ids, int n, const int32_t *laws) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (pn_g711_laws_set_check(r->c->B, ids, n, laws)) return -1;
+  if (n == 0) return 0;
+  PN_ON_DEVICE(r->c);
+  const int *d = stage_ids(r->c, ids, n, laws, n);
+  if (!d) return -1;
+  pn_launch_rate_set_factors(r->c->stream, d, d + ((n + 3) & ~3), n, r->d_laws);
+  PN_HIP_CHECK(hipGetLastError());
+  for (int i = 0; i < n; i++) r->laws[ids[i]] = laws[i];
+  return 0;
+}
+extern "C" int pn_rate_get_stream_laws(const pn_rate *r, int32_t *h_laws) {
+  if (!r || !h_laws) { pn_set_error("NULL argument"); return -1; }
+  for (int s = 0; s < r->c->B; s++) h_laws[s] = r->laws[s];
   return 0;
 }
 
@@ -230,41 +259,43 @@ static int rate_aligned(const void *a, const void *b) {
   if (((uintptr_t)a | (uintptr_t)b) & 15) { pn_set_error("rate converter rows must be 16-byte aligned"); return -1; }
   return 0;
 }
-static int rate_up(pn_rate *r, const void *d_in, int is_i16, float *d_out48, const RateRows &rows) {
+static int rate_up(pn_rate *r, const void *d_in, int fmt, float *d_out48, const RateRows &rows) {
   RateScope sc(r, RF_UP);
-  if (r->mixed ? pn_launch_rate_up_mixed(r->c->stream, is_i16, rows.n, rows.d_ids, r->factors, d_in, d_out48, r->tail_up, r->taps_up)
-               : pn_launch_rate_up(r->c->stream, r->L, is_i16, rows.n, rows.d_ids, d_in, d_out48, r->tail_up, r->taps_up)) return -1;
+  if (r->mixed ? pn_launch_rate_up_mixed(r->c->stream, fmt, rows.n, rows.d_ids, r->factors, r->d_laws, d_in, d_out48, r->tail_up, r->taps_up)
+               : pn_launch_rate_up(r->c->stream, r->L, fmt, rows.n, rows.d_ids, r->d_laws, d_in, d_out48, r->tail_up, r->taps_up)) return -1;
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
-static int rate_down(pn_rate *r, const float *d_in48, void *d_out, int is_i16, const RateRows &rows) {
+static int rate_down(pn_rate *r, const float *d_in48, void *d_out, int fmt, const RateRows &rows) {
   const int sat = r->c->saturate ? 1 : 0;
   RateScope sc(r, RF_DOWN);
-  if (r->mixed ? pn_launch_rate_down_mixed(r->c->stream, is_i16, rows.n, rows.d_ids, r->factors, d_in48, d_out, sat, r->tail_down, r->taps_down)
-               : pn_launch_rate_down(r->c->stream, r->L, is_i16, rows.n, rows.d_ids, d_in48, d_out, sat, r->tail_down, r->taps_down)) return -1;
+  if (r->mixed ? pn_launch_rate_down_mixed(r->c->stream, fmt, rows.n, rows.d_ids, r->factors, r->d_laws, d_in48, d_out, sat, r->tail_down, r->taps_down)
+               : pn_launch_rate_down(r->c->stream, r->L, fmt, rows.n, rows.d_ids, r->d_laws, d_in48, d_out, sat, r->tail_down, r->taps_down)) return -1;
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
-static int rate_up_call(pn_rate *r, const void *d_in, int is_i16, float *d_out48, const int32_t *ids, int n) {
+static int rate_up_call(pn_rate *r, const void *d_in, int fmt, float *d_out48, const int32_t *ids, int n) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   if (rate_aligned(d_in, d_out48)) return -1;
   PN_ON_DEVICE(r->c);
   RateRows rows;
   if (rate_rows(r, ids, n, &rows)) return -1;
-  return rate_up(r, d_in, is_i16, d_out48, rows);
+  return rate_up(r, d_in, fmt, d_out48, rows);
 }
-static int rate_down_call(pn_rate *r, const float *d_in48, void *d_out, int is_i16, const int32_t *ids, int n) {
+static int rate_down_call(pn_rate *r, const float *d_in48, void *d_out, int fmt, const int32_t *ids, int n) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   if (rate_aligned(d_in48, d_out)) return -1;
   PN_ON_DEVICE(r->c);
   RateRows rows;
   if (rate_rows(r, ids, n, &rows)) return -1;
-  return rate_down(r, d_in48, d_out, is_i16, rows);
+  return rate_down(r, d_in48, d_out, fmt, rows);
 }
-extern "C" int pn_rate_up_f32(pn_rate *r, const float *d_in, float *d_out48, const int32_t *ids, int n_ids) { return rate_up_call(r, d_in, 0, d_out48, ids, n_ids); }
-extern "C" int pn_rate_up_i16(pn_rate *r, const int16_t *d_in, float *d_out48, const int32_t *ids, int n_ids) { return rate_up_call(r, d_in, 1, d_out48, ids, n_ids); }
-extern "C" int pn_rate_down_f32(pn_rate *r, const float *d_in48, float *d_out, const int32_t *ids, int n_ids) { return rate_down_call(r, d_in48, d_out, 0, ids, n_ids); }
-extern "C" int pn_rate_down_i16(pn_rate *r, const float *d_in48, int16_t *d_out, const int32_t *ids, int n_ids) { return rate_down_call(r, d_in48, d_out, 1, ids, n_ids); }
+extern "C" int pn_rate_up_f32(pn_rate *r, const float *d_in, float *d_out48, const int32_t *ids, int n_ids) { return rate_up_call(r, d_in, PN_FMT_F32, d_out48, ids, n_ids); }
+extern "C" int pn_rate_up_i16(pn_rate *r, const int16_t *d_in, float *d_out48, const int32_t *ids, int n_ids) { return rate_up_call(r, d_in, PN_FMT_I16, d_out48, ids, n_ids); }
+extern "C" int pn_rate_up_g711(pn_rate *r, const uint8_t *d_in, float *d_out48, const int32_t *ids, int n_ids) { return rate_up_call(r, d_in, PN_FMT_G711, d_out48, ids, n_ids); }
+extern "C" int pn_rate_down_f32(pn_rate *r, const float *d_in48, float *d_out, const int32_t *ids, int n_ids) { return rate_down_call(r, d_in48, d_out, PN_FMT_F32, ids, n_ids); }
+extern "C" int pn_rate_down_i16(pn_rate *r, const float *d_in48, int16_t *d_out, const int32_t *ids, int n_ids) { return rate_down_call(r, d_in48, d_out, PN_FMT_I16, ids, n_ids); }
+extern "C" int pn_rate_down_g711(pn_rate *r, const float *d_in48, uint8_t *d_out, const int32_t *ids, int n_ids) { return rate_down_call(r, d_in48, d_out, PN_FMT_G711, ids, n_ids); }
 
 // ---- one whole frame -----------------------------------------------------------------------------------------------------------
 // up into x48, the engine's float frame from x48 into y48 (all streams, or the listed ones through the context's own active
@@ -272,53 +303,56 @@ extern "C" int pn_rate_down_i16(pn_rate *r, const float *d_in48, int16_t *d_out,
 // and the down kernel has not, which is why the header asks for a reset of both objects before reuse.
 // rate_frame: the launches alone — the caller is on the context's device and has checked the rows and, when active, the list
 // (pn_ids_check, distinct), which is what lets the pipelined path refuse a list BEFORE the frame takes a pipeline slot.
-static int rate_frame(pn_rate *r, const void *d_in, void *d_out, float *d_gr, int is_i16, bool active, const int32_t *ids, int n) {
+static int rate_frame(pn_rate *r, const void *d_in, void *d_out, float *d_gr, int fmt, bool active, const int32_t *ids, int n) {
   pn_ctx *c = r->c;
   RateRows rows = {NULL, c->B};
   if (active) {                                      // (an empty list is legal, as for pn_process_*_active: nobody advances)
     rows.n = n;
     if (n > 0 && !(rows.d_ids = stage_ids(c, ids, n))) return -1;
   }
-  if (rate_up(r, d_in, is_i16, r->x48, rows)) return -1;
+  if (rate_up(r, d_in, fmt, r->x48, rows)) return -1;
   if (active ? pn_process_f32_active(c, r->x48, r->y48, d_gr, ids, n) : pn_process_f32(c, r->x48, r->y48, d_gr)) return -1;
-  if (rate_down(r, r->y48, d_out, is_i16, rows)) return -1;
+  if (rate_down(r, r->y48, d_out, fmt, rows)) return -1;
   if (r->events.size() >= 4096 && rate_flush_events(r)) return -1;   // profiling left on: bound the pending events
   return 0;
 }
-static int rate_process(pn_rate *r, const void *d_in, void *d_out, float *d_gr, int is_i16, bool active, const int32_t *ids, int n) {
+static int rate_process(pn_rate *r, const void *d_in, void *d_out, float *d_gr, int fmt, bool active, const int32_t *ids, int n) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   if (rate_aligned(d_in, d_out)) return -1;
   PN_ON_DEVICE(r->c);
   if (active && pn_ids_check(r->c->B, ids, n, true)) return -1;
-  return rate_frame(r, d_in, d_out, d_gr, is_i16, active, ids, n);
+  return rate_frame(r, d_in, d_out, d_gr, fmt, active, ids, n);
 }
-extern "C" int pn_rate_process_f32(pn_rate *r, const float *d_in, float *d_out, float *d_gr) { return rate_process(r, d_in, d_out, d_gr, 0, false, NULL, 0); }
-extern "C" int pn_rate_process_i16(pn_rate *r, const int16_t *d_in, int16_t *d_out, float *d_gr) { return rate_process(r, d_in, d_out, d_gr, 1, false, NULL, 0); }
-extern "C" int pn_rate_process_f32_active(pn_rate *r, const float *d_in, float *d_out, float *d_gr, const int32_t *ids, int n) { return rate_process(r, d_in, d_out, d_gr, 0, true, ids, n); }
-extern "C" int pn_rate_process_i16_active(pn_rate *r, const int16_t *d_in, int16_t *d_out, float *d_gr, const int32_t *ids, int n) { return rate_process(r, d_in, d_out, d_gr, 1, true, ids, n); }
+extern "C" int pn_rate_process_f32(pn_rate *r, const float *d_in, float *d_out, float *d_gr) { return rate_process(r, d_in, d_out, d_gr, PN_FMT_F32, false, NULL, 0); }
+extern "C" int pn_rate_process_i16(pn_rate *r, const int16_t *d_in, int16_t *d_out, float *d_gr) { return rate_process(r, d_in, d_out, d_gr, PN_FMT_I16, false, NULL, 0); }
+extern "C" int pn_rate_process_g711(pn_rate *r, const uint8_t *d_in, uint8_t *d_out, float *d_gr) { return rate_process(r, d_in, d_out, d_gr, PN_FMT_G711, false, NULL, 0); }
+extern "C" int pn_rate_process_f32_active(pn_rate *r, const float *d_in, float *d_out, float *d_gr, const int32_t *ids, int n) { return rate_process(r, d_in, d_out, d_gr, PN_FMT_F32, true, ids, n); }
+extern "C" int pn_rate_process_i16_active(pn_rate *r, const int16_t *d_in, int16_t *d_out, float *d_gr, const int32_t *ids, int n) { return rate_process(r, d_in, d_out, d_gr, PN_FMT_I16, true, ids, n); }
+extern "C" int pn_rate_process_g711_active(pn_rate *r, const uint8_t *d_in, uint8_t *d_out, float *d_gr, const int32_t *ids, int n) { return rate_process(r, d_in, d_out, d_gr, PN_FMT_G711, true, ids, n); }
 
-static int rate_process_host(pn_rate *r, const void *h_in, void *h_out, float *h_gr, int is_i16) {
+static int rate_process_host(pn_rate *r, const void *h_in, void *h_out, float *h_gr, int fmt) {
   if (!r || !h_in || !h_out) { pn_set_error("NULL argument"); return -1; }
   pn_ctx *c = r->c;
   PN_ON_DEVICE(c);
   if (pn_host_wait(c)) return -1;                    // frames in flight on the context's pipelined path complete first
-  const size_t nbytes = (size_t)c->B * r->n * (is_i16 ? 2 : 4);
+  const size_t nbytes = (size_t)c->B * r->n * pn_fmt_bytes(fmt);
   PN_HIP_CHECK(hipMemcpyAsync(r->io_in, h_in, nbytes, hipMemcpyHostToDevice, c->stream));
-  if (rate_process(r, r->io_in, r->io_out, h_gr ? r->io_gr : NULL, is_i16, false, NULL, 0)) return -1;
+  if (rate_process(r, r->io_in, r->io_out, h_gr ? r->io_gr : NULL, fmt, false, NULL, 0)) return -1;
   // (mixed: the rows land in the converter's pinned buffer, and only each stream's own samples go on to the caller's row)
   PN_HIP_CHECK(hipMemcpyAsync(r->mixed ? r->h_rows : h_out, r->io_out, nbytes, hipMemcpyDeviceToHost, c->stream));
   if (h_gr) PN_HIP_CHECK(hipMemcpyAsync(h_gr, r->io_gr, (size_t)c->B * 68 * 4, hipMemcpyDeviceToHost, c->stream));
   PN_HIP_CHECK(hipStreamSynchronize(c->stream));
   if (r->mixed) {
-    const size_t w = is_i16 ? 2 : 4;
+    const size_t w = pn_fmt_bytes(fmt);
     for (int s = 0; s < c->B; s++)
       memcpy(static_cast<char *>(h_out) + (size_t)s * r->n * w, static_cast<const char *>(r->h_rows) + (size_t)s * r->n * w,
              (size_t)(PN_FRAME / pn_rate_mixed_factor(r->rates[s])) * w);
   }
   return 0;
 }
-extern "C" int pn_rate_process_host_f32(pn_rate *r, const float *h_in, float *h_out, float *h_gr) { return rate_process_host(r, h_in, h_out, h_gr, 0); }
-extern "C" int pn_rate_process_host_i16(pn_rate *r, const int16_t *h_in, int16_t *h_out, float *h_gr) { return rate_process_host(r, h_in, h_out, h_gr, 1); }
+extern "C" int pn_rate_process_host_f32(pn_rate *r, const float *h_in, float *h_out, float *h_gr) { return rate_process_host(r, h_in, h_out, h_gr, PN_FMT_F32); }
+extern "C" int pn_rate_process_host_i16(pn_rate *r, const int16_t *h_in, int16_t *h_out, float *h_gr) { return rate_process_host(r, h_in, h_out, h_gr, PN_FMT_I16); }
+extern "C" int pn_rate_process_host_g711(pn_rate *r, const uint8_t *h_in, uint8_t *h_out, float *h_gr) { return rate_process_host(r, h_in, h_out, h_gr, PN_FMT_G711); }
 
 // ---- the pipelined host path ---------------------------------------------------------------------------------------------------
 // A converter's frame through the CONTEXT's pipeline (pn_host_pipe.cpp pipe_submit): the context's copy streams, slot counter,
@@ -340,25 +374,27 @@ extern "C" int pn_rate_host_pipeline_prepare(pn_rate *r) {
   PN_ON_DEVICE(r->c);
   return rate_pipe_prepare(r);
 }
-struct RateFrame { pn_rate *r; int is_i16; bool active; const int32_t *ids; int n; };
+struct RateFrame { pn_rate *r; int fmt; bool active; const int32_t *ids; int n; };
 static int rate_frame_body(void *arg, void *d_in, void *d_out, float *d_gr) {
   const RateFrame &f = *static_cast<const RateFrame *>(arg);
-  return rate_frame(f.r, d_in, d_out, d_gr, f.is_i16, f.active, f.ids, f.n);
+  return rate_frame(f.r, d_in, d_out, d_gr, f.fmt, f.active, f.ids, f.n);
 }
-static int rate_submit_host(pn_rate *r, const void *h_in, void *h_out, float *h_gr, int is_i16, bool active, const int32_t *ids, int n) {
+static int rate_submit_host(pn_rate *r, const void *h_in, void *h_out, float *h_gr, int fmt, bool active, const int32_t *ids, int n) {
   if (!r || !h_in || !h_out) { pn_set_error("NULL argument"); return -1; }
   pn_ctx *c = r->c;
   if (active && pn_ids_check(c->B, ids, n, true)) return -1;          // refused before the frame takes a pipeline slot
   PN_ON_DEVICE(c);
   if (rate_pipe_prepare(r)) return -1;
-  const PipeStaging st = {{r->io_in, r->io_in1}, {r->io_out, r->io_out1}, (size_t)c->B * r->n * (is_i16 ? 2 : 4)};
-  RateFrame f = {r, is_i16, active, ids, n};
+  const PipeStaging st = {{r->io_in, r->io_in1}, {r->io_out, r->io_out1}, (size_t)c->B * r->n * pn_fmt_bytes(fmt)};
+  RateFrame f = {r, fmt, active, ids, n};
   return pipe_submit(c, st, h_in, h_out, h_gr, rate_frame_body, &f);
 }
-extern "C" int pn_rate_submit_host_f32(pn_rate *r, const float *h_in, float *h_out, float *h_gr) { return rate_submit_host(r, h_in, h_out, h_gr, 0, false, NULL, 0); }
-extern "C" int pn_rate_submit_host_i16(pn_rate *r, const int16_t *h_in, int16_t *h_out, float *h_gr) { return rate_submit_host(r, h_in, h_out, h_gr, 1, false, NULL, 0); }
-extern "C" int pn_rate_submit_host_f32_active(pn_rate *r, const float *h_in, float *h_out, float *h_gr, const int32_t *ids, int n) { return rate_submit_host(r, h_in, h_out, h_gr, 0, true, ids, n); }
-extern "C" int pn_rate_submit_host_i16_active(pn_rate *r, const int16_t *h_in, int16_t *h_out, float *h_gr, const int32_t *ids, int n) { return rate_submit_host(r, h_in, h_out, h_gr, 1, true, ids, n); }
+extern "C" int pn_rate_submit_host_f32(pn_rate *r, const float *h_in, float *h_out, float *h_gr) { return rate_submit_host(r, h_in, h_out, h_gr, PN_FMT_F32, false, NULL, 0); }
+extern "C" int pn_rate_submit_host_i16(pn_rate *r, const int16_t *h_in, int16_t *h_out, float *h_gr) { return rate_submit_host(r, h_in, h_out, h_gr, PN_FMT_I16, false, NULL, 0); }
+extern "C" int pn_rate_submit_host_g711(pn_rate *r, const uint8_t *h_in, uint8_t *h_out, float *h_gr) { return rate_submit_host(r, h_in, h_out, h_gr, PN_FMT_G711, false, NULL, 0); }
+extern "C" int pn_rate_submit_host_f32_active(pn_rate *r, const float *h_in, float *h_out, float *h_gr, const int32_t *ids, int n) { return rate_submit_host(r, h_in, h_out, h_gr, PN_FMT_F32, true, ids, n); }
+extern "C" int pn_rate_submit_host_i16_active(pn_rate *r, const int16_t *h_in, int16_t *h_out, float *h_gr, const int32_t *ids, int n) { return rate_submit_host(r, h_in, h_out, h_gr, PN_FMT_I16, true, ids, n); }
+extern "C" int pn_rate_submit_host_g711_active(pn_rate *r, const uint8_t *h_in, uint8_t *h_out, float *h_gr, const int32_t *ids, int n) { return rate_submit_host(r, h_in, h_out, h_gr, PN_FMT_G711, true, ids, n); }
 
 // ---- timing the two kernels ----------------------------------------------------------------------------------------------------
 extern "C" int pn_rate_set_profiling(pn_rate *r, int enable) {

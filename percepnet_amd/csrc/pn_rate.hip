@@ -22,13 +22,72 @@
 // Below them: the same two kernels with a factor PER STREAM (pn_rate_create_mixed), which call the same row bodies.
 #include "pn_launch.h"
 #include "pn_pcm.h"
+#include "pn_g711.h"
 #include "pn_rate_design.h"
 
 #define RT_LANES 64
 #define RT_WPB 4                     // wavefronts (= streams) per block
 #define RT_T PN_RATE_TAPS
 #define RT_UT PN_RATE_UP_TAIL        // 32
-static_assert(RT_UT == 2 * RT_T && RT_UT % 4 == 0 && PN_FRAME % (8 * PN_RATE_MAX_L) == 0, "tails and rows are whole 16-byte groups");
+static_assert(RT_UT == 2 * RT_T && RT_UT % 4 == 0 && PN_FRAME % (16 * PN_RATE_MAX_L) == 0, "tails and rows are whole 16-byte groups, in every sample format");
+
+// The sample formats of the low-rate rows (pn_launch.h PN_FMT_*): a format enters only where a row is staged into LDS and where it
+// leaves, so the row bodies below are the one piece of code every format runs.  int16: x = (float)v / 32768 in, the wrapping or
+// saturating cast of t = z * 32768 out.  G.711 (8 bit, pn_g711.h): the int16 format with the companding outside it — in
+// x = (float)dec(b) / 32768, out enc(c) of exactly the int16 c the int16 format writes — so a G.711 stream gives bit for bit
+// the encoding of what the int16 path gives on the decoded samples.  One 16-byte access carries 4 | 8 | 16 samples.
+// int16 x 8 -> two float4 / two float4 -> int16 x 8
+__device__ __forceinline__ void rt_i16x8_to_f32(uint4 q, float4 *d) {
+  union { uint4 q; int16_t h[8]; } u;
+  u.q = q;
+  d[0] = make_float4((float)u.h[0] / 32768.f, (float)u.h[1] / 32768.f, (float)u.h[2] / 32768.f, (float)u.h[3] / 32768.f);
+  d[1] = make_float4((float)u.h[4] / 32768.f, (float)u.h[5] / 32768.f, (float)u.h[6] / 32768.f, (float)u.h[7] / 32768.f);
+}
+__device__ __forceinline__ uint4 rt_f32x8_to_i16(const float4 *z, int saturate) {
+  const float4 a = z[0], b = z[1];
+  const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+  union { int16_t h[8]; uint4 q; } p;
+#pragma unroll
+  for (int i = 0; i < 8; i++) { const float t = v[i] * 32768; p.h[i] = saturate ? pn_f2s_sat(t) : pn_f2s(t); }
+  return p.q;
+}
+// G.711 x 16 -> four float4 / four float4 -> G.711 x 16: integer ALU on the lane's own 16 bytes, sample i in byte i.  ALAW is
+// the wave's law, uniform (rt_wave_law) and branched on by the caller, so that a lane runs one law's formulas.
+template <bool ALAW>
+__device__ __forceinline__ void rt_g711x16_to_f32(uint4 q, float4 *d) {
+  const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    float f[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const uint32_t b = (w[k] >> (8 * j)) & 0xFFu;
+      f[j] = (float)(ALAW ? pn_g711_dec_alaw(b) : pn_g711_dec_ulaw(b)) / 32768.f;
+    }
+    d[k] = make_float4(f[0], f[1], f[2], f[3]);
+  }
+}
+template <bool ALAW>
+__device__ __forceinline__ uint4 rt_f32x16_to_g711(const float4 *z, int saturate) {
+  uint32_t w[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const float4 a = z[k];
+    const float v[4] = {a.x, a.y, a.z, a.w};
+    w[k] = 0u;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const float t = v[j] * 32768;
+      const int32_t c = saturate ? pn_f2s_sat(t) : pn_f2s(t);
+      w[k] |= (ALAW ? pn_g711_enc_alaw(c) : pn_g711_enc_ulaw(c)) << (8 * j);
+    }
+  }
+  return make_uint4(w[0], w[1], w[2], w[3]);
+}
+// the wave's law from the per-stream table (pn_rate_set_stream_laws), uniform; lanes of dead waves run mu-law on nothing
+__device__ __forceinline__ int rt_wave_law(const int *laws, size_t s, bool live) {
+  return __builtin_amdgcn_readfirstlane(live ? laws[s] : 0);
+}
 
 // The row bodies of the two conversions, shared by the single-rate kernels and the mixed ones (so a stream's arithmetic is one
 // piece of code whichever converter runs it).  All pointers are LDS; taps = the table of this L, h[-D..D] / g[-D..D].
@@ -63,15 +122,16 @@ __device__ __forceinline__ void rt_down_rows(int lane, const float *buf, float *
   }
 }
 
-template <int L, bool I16>
+template <int L, int FMT>
 __global__ __launch_bounds__(RT_LANES * RT_WPB) void pn_rate_up_kernel(
     int n_rows, const int *__restrict__ ids,   // rows to run; ids == NULL: row w is stream w
-    const void *__restrict__ in,               // [n_streams][N] float or int16
+    const int *__restrict__ laws,              // [n_streams] G.711 only: the law of every stream
+    const void *__restrict__ in,               // [n_streams][N] float, int16 or G.711 bytes
     float *__restrict__ out48,                 // [n_streams][480]
     float *__restrict__ tail,                  // [n_streams][32], read then rewritten
     const float *__restrict__ taps) {          // h[-D..D]
   constexpr int N = PN_FRAME / L, D = RT_T * L, NT = 2 * D + 1;
-  static_assert(N % 8 == 0 && N / 4 <= RT_LANES, "one 16-byte load per lane covers a row");
+  static_assert(N % 16 == 0 && N / 4 <= RT_LANES, "one 16-byte load per lane covers a row");
   __shared__ float s_taps[NT];
   __shared__ __align__(16) float s_buf[RT_WPB][RT_UT + N];
   __shared__ __align__(16) float s_out[RT_WPB][PN_FRAME];
@@ -83,7 +143,14 @@ __global__ __launch_bounds__(RT_LANES * RT_WPB) void pn_rate_up_kernel(
   float *buf = s_buf[wave], *o = s_out[wave];
   if (live) {
     if (lane < RT_UT / 4) reinterpret_cast<float4 *>(buf)[lane] = reinterpret_cast<const float4 *>(tail + s * RT_UT)[lane];
-    if constexpr (I16) {
+    if constexpr (FMT == PN_FMT_G711) {
+      const int law = rt_wave_law(laws, s, live);
+      if (lane < N / 16) {
+        const uint4 q = reinterpret_cast<const uint4 *>(static_cast<const uint8_t *>(in) + s * N)[lane];
+        float4 *d = reinterpret_cast<float4 *>(buf + RT_UT) + 4 * lane;
+        if (law == PN_G711_ALAW) rt_g711x16_to_f32<true>(q, d); else rt_g711x16_to_f32<false>(q, d);
+      }
+    } else if constexpr (FMT == PN_FMT_I16) {
       if (lane < N / 8) {
         union { uint4 q; int16_t h[8]; } u;
         u.q = reinterpret_cast<const uint4 *>(static_cast<const int16_t *>(in) + s * N)[lane];
@@ -107,16 +174,17 @@ __global__ __launch_bounds__(RT_LANES * RT_WPB) void pn_rate_up_kernel(
   }
 }
 
-template <int L, bool I16>
+template <int L, int FMT>
 __global__ __launch_bounds__(RT_LANES * RT_WPB) void pn_rate_down_kernel(
     int n_rows, const int *__restrict__ ids,
+    const int *__restrict__ laws,              // [n_streams] G.711 only
     const float *__restrict__ in48,            // [n_streams][480]
-    void *__restrict__ out,                    // [n_streams][N] float or int16
-    int saturate,                              // int16 only: the saturating cast instead of the wrap
+    void *__restrict__ out,                    // [n_streams][N] float, int16 or G.711 bytes
+    int saturate,                              // int16 and G.711: the saturating cast instead of the wrap
     float *__restrict__ tail,                  // [n_streams][2D], read then rewritten
     const float *__restrict__ taps) {          // g[-D..D]
   constexpr int N = PN_FRAME / L, D = RT_T * L, TD = 2 * D, NT = 2 * D + 1;
-  static_assert(TD % 4 == 0 && TD / 4 <= RT_LANES && N % 8 == 0 && N / 4 <= RT_LANES, "one 16-byte access per lane covers a tail and an output row");
+  static_assert(TD % 4 == 0 && TD / 4 <= RT_LANES && N % 16 == 0 && N / 4 <= RT_LANES, "one 16-byte access per lane covers a tail and an output row");
   __shared__ float s_taps[NT];
   __shared__ __align__(16) float s_buf[RT_WPB][TD + PN_FRAME];
   __shared__ __align__(16) float s_out[RT_WPB][N];
@@ -137,7 +205,14 @@ __global__ __launch_bounds__(RT_LANES * RT_WPB) void pn_rate_down_kernel(
   }
   __syncthreads();
   if (live) {
-    if constexpr (I16) {
+    if constexpr (FMT == PN_FMT_G711) {
+      const int law = rt_wave_law(laws, s, live);
+      if (lane < N / 16) {
+        const float4 *zz = reinterpret_cast<const float4 *>(z) + 4 * lane;
+        reinterpret_cast<uint4 *>(static_cast<uint8_t *>(out) + s * N)[lane] =
+            law == PN_G711_ALAW ? rt_f32x16_to_g711<true>(zz, saturate) : rt_f32x16_to_g711<false>(zz, saturate);
+      }
+    } else if constexpr (FMT == PN_FMT_I16) {
       if (lane < N / 8) {
         const float4 a = reinterpret_cast<const float4 *>(z)[2 * lane], b = reinterpret_cast<const float4 *>(z)[2 * lane + 1];
         const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
@@ -173,27 +248,12 @@ __device__ __forceinline__ int rt_wave_factor(const int *factors, size_t s, bool
   const int L = __builtin_amdgcn_readfirstlane(live ? factors[s] : 0);
   return (L == 6 || L == 3 || L == 2 || L == 1) ? L : 0;
 }
-// int16 x 8 -> two float4 / two float4 -> int16 x 8, the conversions of the single-rate kernels
-__device__ __forceinline__ void rt_i16x8_to_f32(uint4 q, float4 *d) {
-  union { uint4 q; int16_t h[8]; } u;
-  u.q = q;
-  d[0] = make_float4((float)u.h[0] / 32768.f, (float)u.h[1] / 32768.f, (float)u.h[2] / 32768.f, (float)u.h[3] / 32768.f);
-  d[1] = make_float4((float)u.h[4] / 32768.f, (float)u.h[5] / 32768.f, (float)u.h[6] / 32768.f, (float)u.h[7] / 32768.f);
-}
-__device__ __forceinline__ uint4 rt_f32x8_to_i16(const float4 *z, int saturate) {
-  const float4 a = z[0], b = z[1];
-  const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-  union { int16_t h[8]; uint4 q; } p;
-#pragma unroll
-  for (int i = 0; i < 8; i++) { const float t = v[i] * 32768; p.h[i] = saturate ? pn_f2s_sat(t) : pn_f2s(t); }
-  return p.q;
-}
-
-template <bool I16>
+template <int FMT>
 __global__ __launch_bounds__(RT_LANES * RT_WPB) void pn_rate_up_mixed_kernel(
     int n_rows, const int *__restrict__ ids,
     const int *__restrict__ factors,           // [n_streams] L of every stream
-    const void *__restrict__ in,               // [n_streams][480] float or int16, the first 480 / L used
+    const int *__restrict__ laws,              // [n_streams] G.711 only: the law of every stream
+    const void *__restrict__ in,               // [n_streams][480] float, int16 or G.711 bytes, the first 480 / L used
     float *__restrict__ out48,                 // [n_streams][480]
     float *__restrict__ tail,                  // [n_streams][32], read then rewritten (not for L = 1)
     const float *__restrict__ taps) {          // h of L = 6, 3, 2, one table behind the other
@@ -211,7 +271,12 @@ __global__ __launch_bounds__(RT_LANES * RT_WPB) void pn_rate_up_mixed_kernel(
   // stage: the tail and the row behind it; L = 1 puts the row where the results go
   float *row = L == 1 ? o : buf + RT_UT;
   if (L > 1 && lane < RT_UT / 4) reinterpret_cast<float4 *>(buf)[lane] = reinterpret_cast<const float4 *>(tail + s * RT_UT)[lane];
-  if constexpr (I16) {
+  if constexpr (FMT == PN_FMT_G711) {
+    const int law = rt_wave_law(laws, s, live);
+    const uint4 *src = reinterpret_cast<const uint4 *>(static_cast<const uint8_t *>(in) + s * RT_ROW);
+    if (law == PN_G711_ALAW) for (int i = lane; i < N / 16; i += RT_LANES) rt_g711x16_to_f32<true>(src[i], reinterpret_cast<float4 *>(row) + 4 * i);
+    else for (int i = lane; i < N / 16; i += RT_LANES) rt_g711x16_to_f32<false>(src[i], reinterpret_cast<float4 *>(row) + 4 * i);
+  } else if constexpr (FMT == PN_FMT_I16) {
     const uint4 *src = reinterpret_cast<const uint4 *>(static_cast<const int16_t *>(in) + s * RT_ROW);
     for (int i = lane; i < N / 8; i += RT_LANES) rt_i16x8_to_f32(src[i], reinterpret_cast<float4 *>(row) + 2 * i);
   } else {
@@ -230,12 +295,13 @@ __global__ __launch_bounds__(RT_LANES * RT_WPB) void pn_rate_up_mixed_kernel(
   }
 }
 
-template <bool I16>
+template <int FMT>
 __global__ __launch_bounds__(RT_LANES * RT_WPB) void pn_rate_down_mixed_kernel(
     int n_rows, const int *__restrict__ ids,
     const int *__restrict__ factors,           // [n_streams]
+    const int *__restrict__ laws,              // [n_streams] G.711 only
     const float *__restrict__ in48,            // [n_streams][480]
-    void *__restrict__ out,                    // [n_streams][480] float or int16, the first 480 / L written
+    void *__restrict__ out,                    // [n_streams][480] float, int16 or G.711 bytes, the first 480 / L written
     int saturate,
     float *__restrict__ tail,                  // [n_streams][192], the first 2D read then rewritten (not for L = 1)
     const float *__restrict__ taps) {          // g of L = 6, 3, 2, one table behind the other
@@ -261,7 +327,12 @@ __global__ __launch_bounds__(RT_LANES * RT_WPB) void pn_rate_down_mixed_kernel(
   else if (L == 3) rt_down_rows<3>(lane, buf, z, s_taps + rt_taps_offset(3));
   else if (L == 2) rt_down_rows<2>(lane, buf, z, s_taps + rt_taps_offset(2));
   __syncthreads();
-  if constexpr (I16) {
+  if constexpr (FMT == PN_FMT_G711) {
+    const int law = rt_wave_law(laws, s, live);
+    uint4 *dst = reinterpret_cast<uint4 *>(static_cast<uint8_t *>(out) + s * RT_ROW);
+    if (law == PN_G711_ALAW) for (int i = lane; i < N / 16; i += RT_LANES) dst[i] = rt_f32x16_to_g711<true>(reinterpret_cast<const float4 *>(z) + 4 * i, saturate);
+    else for (int i = lane; i < N / 16; i += RT_LANES) dst[i] = rt_f32x16_to_g711<false>(reinterpret_cast<const float4 *>(z) + 4 * i, saturate);
+  } else if constexpr (FMT == PN_FMT_I16) {
     uint4 *dst = reinterpret_cast<uint4 *>(static_cast<int16_t *>(out) + s * RT_ROW);
     for (int i = lane; i < N / 8; i += RT_LANES) dst[i] = rt_f32x8_to_i16(reinterpret_cast<const float4 *>(z) + 2 * i, saturate);
   } else {
@@ -272,6 +343,7 @@ __global__ __launch_bounds__(RT_LANES * RT_WPB) void pn_rate_down_mixed_kernel(
 }
 
 // A rate change (pn_rate_set_stream_rates): factors[ids[i]] = vals[i], ids distinct.  The tails are zeroed by the launches behind it.
+// A law change (pn_rate_set_stream_laws) writes the law table the same way, in stream order, and touches no tail.
 __global__ void pn_rate_set_factors_kernel(const int *__restrict__ ids, const int *__restrict__ vals, int n, int *__restrict__ factors) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) factors[ids[i]] = vals[i];
@@ -327,24 +399,38 @@ __global__ __launch_bounds__(64) void pn_rate_records_dev_kernel(const int *__re
   }
 }
 
+#define RT_LAUNCH(kernel, fmt_, ...)                                                                                    \
+  do {                                                                                                               \
+    if (fmt == PN_FMT_G711) hipLaunchKernelGGL(HIP_KERNEL_NAME(kernel<fmt_ PN_FMT_G711>), grid, block, 0, st, __VA_ARGS__);  \
+    else if (fmt == PN_FMT_I16) hipLaunchKernelGGL(HIP_KERNEL_NAME(kernel<fmt_ PN_FMT_I16>), grid, block, 0, st, __VA_ARGS__); \
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(kernel<fmt_ PN_FMT_F32>), grid, block, 0, st, __VA_ARGS__);               \
+  } while (0)
+#define RT_COMMA ,
 #define RT_DISPATCH(kernel, ...)                                                                                     \
   do {                                                                                                               \
     const dim3 grid((n_rows + RT_WPB - 1) / RT_WPB), block(RT_LANES * RT_WPB);                                         \
-    if (L == 6) { if (is_i16) hipLaunchKernelGGL(HIP_KERNEL_NAME(kernel<6, true>), grid, block, 0, st, __VA_ARGS__); else hipLaunchKernelGGL(HIP_KERNEL_NAME(kernel<6, false>), grid, block, 0, st, __VA_ARGS__); } \
-    else if (L == 3) { if (is_i16) hipLaunchKernelGGL(HIP_KERNEL_NAME(kernel<3, true>), grid, block, 0, st, __VA_ARGS__); else hipLaunchKernelGGL(HIP_KERNEL_NAME(kernel<3, false>), grid, block, 0, st, __VA_ARGS__); } \
-    else { if (is_i16) hipLaunchKernelGGL(HIP_KERNEL_NAME(kernel<2, true>), grid, block, 0, st, __VA_ARGS__); else hipLaunchKernelGGL(HIP_KERNEL_NAME(kernel<2, false>), grid, block, 0, st, __VA_ARGS__); } \
+    if (L == 6) RT_LAUNCH(kernel, 6 RT_COMMA, __VA_ARGS__);                                                            \
+    else if (L == 3) RT_LAUNCH(kernel, 3 RT_COMMA, __VA_ARGS__);                                                       \
+    else RT_LAUNCH(kernel, 2 RT_COMMA, __VA_ARGS__);                                                                   \
   } while (0)
-
-int pn_launch_rate_up(hipStream_t st, int L, int is_i16, int n_rows, const int *d_ids, const void *in, float *out48, float *tail, const float *taps) {
-  if (L != 2 && L != 3 && L != 6) { pn_set_error("pn_launch_rate_up: no kernel for L = %d", L); return -1; }
-  if (n_rows <= 0) return 0;
-  RT_DISPATCH(pn_rate_up_kernel, n_rows, d_ids, in, out48, tail, taps);
+static int rt_fmt_check(const char *who, int fmt, const int *d_laws) {
+  if (fmt != PN_FMT_F32 && fmt != PN_FMT_I16 && fmt != PN_FMT_G711) { pn_set_error("%s: no kernel for sample format %d", who, fmt); return -1; }
+  if (fmt == PN_FMT_G711 && !d_laws) { pn_set_error("%s: G.711 rows need the law table", who); return -1; }
   return 0;
 }
-int pn_launch_rate_down(hipStream_t st, int L, int is_i16, int n_rows, const int *d_ids, const float *in48, void *out, int saturate, float *tail, const float *taps) {
-  if (L != 2 && L != 3 && L != 6) { pn_set_error("pn_launch_rate_down: no kernel for L = %d", L); return -1; }
+
+int pn_launch_rate_up(hipStream_t st, int L, int fmt, int n_rows, const int *d_ids, const int *d_laws, const void *in, float *out48, float *tail, const float *taps) {
+  if (L != 2 && L != 3 && L != 6) { pn_set_error("pn_launch_rate_up: no kernel for L = %d", L); return -1; }
+  if (rt_fmt_check("pn_launch_rate_up", fmt, d_laws)) return -1;
   if (n_rows <= 0) return 0;
-  RT_DISPATCH(pn_rate_down_kernel, n_rows, d_ids, in48, out, saturate, tail, taps);
+  RT_DISPATCH(pn_rate_up_kernel, n_rows, d_ids, d_laws, in, out48, tail, taps);
+  return 0;
+}
+int pn_launch_rate_down(hipStream_t st, int L, int fmt, int n_rows, const int *d_ids, const int *d_laws, const float *in48, void *out, int saturate, float *tail, const float *taps) {
+  if (L != 2 && L != 3 && L != 6) { pn_set_error("pn_launch_rate_down: no kernel for L = %d", L); return -1; }
+  if (rt_fmt_check("pn_launch_rate_down", fmt, d_laws)) return -1;
+  if (n_rows <= 0) return 0;
+  RT_DISPATCH(pn_rate_down_kernel, n_rows, d_ids, d_laws, in48, out, saturate, tail, taps);
   return 0;
 }
 void pn_launch_rate_records(hipStream_t st, int L, int rate_hz, const int *d_ids, int n, float *tail_up, float *tail_down, int td_stride, void *rec, int scatter) {
@@ -356,18 +442,18 @@ void pn_launch_rate_records(hipStream_t st, int L, int rate_hz, const int *d_ids
 }
 
 // the mixed kernels: rows of 480 samples, the factor of every stream in d_factors, all three tap tables at taps
-int pn_launch_rate_up_mixed(hipStream_t st, int is_i16, int n_rows, const int *d_ids, const int *d_factors, const void *in, float *out48, float *tail, const float *taps) {
+int pn_launch_rate_up_mixed(hipStream_t st, int fmt, int n_rows, const int *d_ids, const int *d_factors, const int *d_laws, const void *in, float *out48, float *tail, const float *taps) {
+  if (rt_fmt_check("pn_launch_rate_up_mixed", fmt, d_laws)) return -1;
   if (n_rows <= 0) return 0;
   const dim3 grid((n_rows + RT_WPB - 1) / RT_WPB), block(RT_LANES * RT_WPB);
-  if (is_i16) hipLaunchKernelGGL(HIP_KERNEL_NAME(pn_rate_up_mixed_kernel<true>), grid, block, 0, st, n_rows, d_ids, d_factors, in, out48, tail, taps);
-  else hipLaunchKernelGGL(HIP_KERNEL_NAME(pn_rate_up_mixed_kernel<false>), grid, block, 0, st, n_rows, d_ids, d_factors, in, out48, tail, taps);
+  RT_LAUNCH(pn_rate_up_mixed_kernel, , n_rows, d_ids, d_factors, d_laws, in, out48, tail, taps);
   return 0;
 }
-int pn_launch_rate_down_mixed(hipStream_t st, int is_i16, int n_rows, const int *d_ids, const int *d_factors, const float *in48, void *out, int saturate, float *tail, const float *taps) {
+int pn_launch_rate_down_mixed(hipStream_t st, int fmt, int n_rows, const int *d_ids, const int *d_factors, const int *d_laws, const float *in48, void *out, int saturate, float *tail, const float *taps) {
+  if (rt_fmt_check("pn_launch_rate_down_mixed", fmt, d_laws)) return -1;
   if (n_rows <= 0) return 0;
   const dim3 grid((n_rows + RT_WPB - 1) / RT_WPB), block(RT_LANES * RT_WPB);
-  if (is_i16) hipLaunchKernelGGL(HIP_KERNEL_NAME(pn_rate_down_mixed_kernel<true>), grid, block, 0, st, n_rows, d_ids, d_factors, in48, out, saturate, tail, taps);
-  else hipLaunchKernelGGL(HIP_KERNEL_NAME(pn_rate_down_mixed_kernel<false>), grid, block, 0, st, n_rows, d_ids, d_factors, in48, out, saturate, tail, taps);
+  RT_LAUNCH(pn_rate_down_mixed_kernel, , n_rows, d_ids, d_factors, d_laws, in48, out, saturate, tail, taps);
   return 0;
 }
 void pn_launch_rate_set_factors(hipStream_t st, const int *d_ids, const int *d_vals, int n, int *d_factors) {
