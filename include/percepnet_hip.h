@@ -522,7 +522,7 @@ int pn_rate_export_streams(pn_rate *r, const int32_t *ids, int n, void *d_record
 int pn_rate_import_streams(pn_rate *r, const int32_t *ids, int n, const void *d_records, int32_t *d_status);
 /* Timing of the converter's two kernels inside a frame: HIP events around their launches, like pn_ctx_set_profiling but owned by
    the converter (the context's family list does not change).  Off by default; off, no event is created or recorded.  name:
-   "rate_up" | "rate_down".  pn_rate_kernel_time synchronises the context's stream. */
+   "rate_up" | "rate_down" | "rate_mix" (the conference mix, below).  pn_rate_kernel_time synchronises the context's stream. */
 int pn_rate_set_profiling(pn_rate *r, int enable);
 int pn_rate_kernel_time(pn_rate *r, const char *name, double *total_ms, int64_t *launches);
 int pn_rate_reset_profile(pn_rate *r);
@@ -635,6 +635,57 @@ int pn_rate_process_g711_active(pn_rate *r, const uint8_t *d_in, uint8_t *d_out,
 int pn_rate_process_host_g711(pn_rate *r, const uint8_t *h_in, uint8_t *h_out, float *h_gr);
 int pn_rate_submit_host_g711(pn_rate *r, const uint8_t *h_in, uint8_t *h_out, float *h_gr);
 int pn_rate_submit_host_g711_active(pn_rate *r, const uint8_t *h_in, uint8_t *h_out, float *h_gr, const int32_t *ids, int n);
+
+/* ---- conferences: every stream hears the sum of the others --------------------------------------------------------------------- */
+/* A conference id PER STREAM on a pn_rate, single-rate or mixed: between the engine and the down-conversion, where every stream's
+   enhanced frame is a 48 kHz float row whatever its rate and coding, each member of a conference gets the sum of the OTHER
+   members' rows ("mix-minus"), on the GPU (csrc/pn_rate_mix.hip).  An 8 kHz A-law, a 16 kHz linear and a 48 kHz float
+   participant meet there in one format.  No new sample format, row shape or entry point for frames: every pn_rate_process_*,
+   _active, pn_rate_process_host_* and pn_rate_submit_host_* call in f32 / i16 / g711 runs it.
+
+   Arithmetic.  For a frame, A = the streams that advance (all of them, or the _active list); y[m][0..480) = the engine's float
+   output row of stream m.
+     stream s in A, conference c:  o[s][j] = sum of y[m][j] over the members m of c with m != s and m in A, m ASCENDING,
+                                   in fp32 as acc = +0.0f, acc = acc + y[m][j].  A lone member hears +0.0.
+     stream s in A, PN_CONF_NONE:  o[s] = y[s], bit for bit — what every stream gets while no conference exists.
+     stream not in A:              contributes nothing (its y row is stale and is not read) and gets no output, as everywhere.
+   The order depends on slots only — no atomics, no cross-lane sums — so a row is the same in every batch size and block, and a
+   float32 model reproduces it, NaN, inf and -0.0 included (tests/conf_model.py).  The down-conversion (or the 48000 copy) then
+   reads o instead of y, with the stream's own rate, format, law and the context's wrapping or saturating cast.  A sum of
+   voices clips where one voice does not: a conference caller should turn pn_ctx_set_output_saturate ON.
+   A participant who only LISTENS (muted, DTX) must still advance to hear: feed it frames of silence and keep it on the list.
+   The mix has no state and nothing upstream depends on it: the engine's state, the delays, the converter's tails and records and
+   the g|r tap are unchanged, and the frame report (pn_ctx_set_report) stays about the stream's OWN output before the mix.
+   The down-converter's tail holds, as always, the last 2D samples of what it converted — for a conference member that is the mix —
+   so the first 2T = 32 low-rate samples of a stream's first frame after joining or leaving a conference still filter the signal
+   it heard before (nothing at 48000, which has no filter); pn_rate_reset_streams clears that where it matters.
+
+   A conference is a number in [0, n_streams); PN_CONF_NONE (every stream of a new converter) is none; a conference holds at most
+   PN_CONF_MAX_MEMBERS streams.  The id is a SETTING, not state: records do not carry it; pn_rate_reset, pn_rate_reset_streams,
+   pn_rate_set_stream_rates and the record calls keep it — a slot that starts a new call is taken out of its conference by the
+   caller.  Conferences live in one converter: none spans two contexts or devices.
+   pn_rate_confs_check (host only, needs no GPU): 0 when confs[0..n) are all PN_CONF_NONE or in [0, n_streams), else -1 with
+   pn_last_error naming the first bad index.
+   pn_rate_set_stream_confs: streams ids[i] (distinct, in range) continue in conference confs[i].  Refused with -1, nothing
+   changed or launched: a bad or duplicate id, a bad value, or a conference that would hold more than PN_CONF_MAX_MEMBERS streams
+   AFTER the change (pn_last_error names it and its size) — so one call may swap members of two full conferences.  n == 0 is a
+   no-op.  Asynchronous on the context's stream and ordered exactly like pn_rate_set_stream_laws: frames submitted before it use
+   the old table, frames after it the new one, on the pipelined path too, with no wait; the caller may reuse its arrays on return.
+   The first call that puts a stream into a conference allocates the device buffers (a second [n_streams][480] row set, the member
+   table: 128 bytes per stream, a stamp per stream); no frame ever allocates.
+   pn_rate_get_stream_confs: the table as last set, h_confs [n_streams].
+   While no stream of the converter is in a conference a frame launches exactly what it launches without this section.
+   pn_rate_mix_f32: the kernel on its own, like pn_rate_up_* / pn_rate_down_*: d_in48 -> d_out48, both [n_streams][480] float at
+   16-byte aligned device addresses, asynchronous.  d_in48 == d_out48, or row sets that overlap, are refused.  ids == NULL: every
+   stream advances; otherwise only the n_ids listed rows are read and written, and unlisted members contribute nothing.
+   pn_rate_kernel_time takes "rate_mix" beside "rate_up" and "rate_down".
+   NOT provided: loudest-N selection, per-member gains, conferences of more than 32, a clipped-sample count of the mix. */
+#define PN_CONF_NONE (-1)
+#define PN_CONF_MAX_MEMBERS 32
+int pn_rate_confs_check(const int32_t *confs, int n, int n_streams);
+int pn_rate_set_stream_confs(pn_rate *r, const int32_t *ids, int n, const int32_t *confs);
+int pn_rate_get_stream_confs(const pn_rate *r, int32_t *h_confs);
+int pn_rate_mix_f32(pn_rate *r, const float *d_in48, float *d_out48, const int32_t *ids, int n_ids);
 
 const char *pn_last_error(void);
 const char *pn_version(void);

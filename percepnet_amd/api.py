@@ -24,6 +24,7 @@ MIXED_RATES = (8000, 16000, 24000, 48000)     # the rate of a STREAM of a mixed 
 RATE_MIXED_ROW = 480                          # PN_RATE_MIXED_ROW: samples between two low-rate rows of a mixed converter
 RATE_TAPS = 16
 G711_ULAW, G711_ALAW = 0, 1                   # PN_G711_*: the law of a stream's 8-bit rows (pn_rate_set_stream_laws)
+CONF_NONE, CONF_MAX_MEMBERS = -1, 32          # PN_CONF_*: no conference; the most streams one holds (pn_rate_set_stream_confs)
 # per-stream frame report (include/percepnet_hip.h pn_ctx_set_report): one record of PN_REPORT_WORDS 32-bit words per stream
 REPORT_WORDS = 8
 REPORT_DTYPE = np.dtype([("in_peak", "<f4"), ("in_energy", "<f4"), ("out_peak", "<f4"), ("out_energy", "<f4"), ("gain_mean", "<f4"),
@@ -176,6 +177,11 @@ def load_library():
             getattr(L, name).argtypes = [_vp, _vp, _vp, _vp]
         for name in ("pn_rate_process_g711_active", "pn_rate_submit_host_g711_active"):
             getattr(L, name).argtypes = [_vp, _vp, _vp, _vp, _vp, ctypes.c_int]
+    if hasattr(L, "pn_rate_set_stream_confs"):
+        L.pn_rate_confs_check.argtypes = [_vp, ctypes.c_int, ctypes.c_int]
+        L.pn_rate_set_stream_confs.argtypes = [_vp, _vp, ctypes.c_int, _vp]
+        L.pn_rate_get_stream_confs.argtypes = [_vp, _vp]
+        L.pn_rate_mix_f32.argtypes = [_vp, _vp, _vp, _vp, ctypes.c_int]
     if hasattr(L, "pn_host_pipeline_prepare"):
         L.pn_host_pipeline_prepare.argtypes = [_vp]
     L.pn_ctx_debug_copy.restype = ctypes.c_longlong
@@ -563,6 +569,15 @@ def g711_encode(law, pcm):
     return out
 
 
+def rate_confs_check(confs, n_streams):
+    """Raises PercepNetError naming the first entry of `confs` that is neither CONF_NONE nor a conference of a converter of
+    n_streams streams, a number in [0, n_streams) (pn_rate_confs_check, host only)."""
+    L = load_library()
+    a = np.ascontiguousarray(np.asarray(confs, dtype=np.int32).ravel())
+    if L.pn_rate_confs_check(a.ctypes.data, int(a.size), int(n_streams)) != 0:
+        raise PercepNetError(_err(L))
+
+
 class RateConverter:
     """8, 16 or 24 kHz streams through a 48 kHz Context (pn_rate): a converter beside `ctx` for all of its streams at ONE rate.
     It borrows the context (device, n_streams, HIP stream): close the converter before the context."""
@@ -673,6 +688,28 @@ class RateConverter:
                 out[:, (t - 1) * f:t * f] = o
         return out
 
+    # conferences: every member hears the fp32 sum of the OTHER members' enhanced 48 kHz rows, members in ascending slot order
+    def set_stream_confs(self, ids, confs):
+        """Streams `ids` continue in the conferences `confs` (CONF_NONE, or a number in [0, n_streams)) from the next frame on
+        (pn_rate_set_stream_confs): asynchronous, ordered like set_stream_laws; a setting that resets, rate changes and records
+        leave alone.  A conference holds at most CONF_MAX_MEMBERS streams.  A member that only listens is fed silence and stays
+        on the id list; mixes clip, so turn Context.set_output_saturate on."""
+        a, n = self._ids(ids)
+        w = np.ascontiguousarray(np.asarray(confs, dtype=np.int32).ravel())
+        if w.size != n:
+            raise PercepNetError(f"{w.size} conferences for {n} streams")
+        self._chk(self.L.pn_rate_set_stream_confs(self.h, a.ctypes.data, n, w.ctypes.data))
+
+    def stream_confs(self):
+        """-> int32 [n_streams]: the conferences as last set (pn_rate_get_stream_confs); CONF_NONE everywhere on a new converter."""
+        w = np.empty(self.n_streams, np.int32)
+        self._chk(self.L.pn_rate_get_stream_confs(self.h, w.ctypes.data))
+        return w
+
+    def mix_f32_dev(self, d_in48, d_out48, ids=None):
+        """The mix kernel on its own (pn_rate_mix_f32): device rows [n_streams][480] float, which must not overlap."""
+        self._kernel("pn_rate_mix_f32", d_in48, d_out48, ids)
+
     # one whole frame, device pointers: [n_streams][frame] in and out at the low rate, d_gr [n_streams][68] or None
     def process_f32_dev(self, d_in, d_out, d_gr=None, ids=None):
         if ids is None:
@@ -758,14 +795,14 @@ class RateConverter:
     def reset_profile(self):
         self._chk(self.L.pn_rate_reset_profile(self.h))
 
-    def kernel_times(self):
-        """-> {"rate_up": (total_ms, launches), "rate_down": (...)}"""
+    def kernel_times(self, names=("rate_up", "rate_down")):
+        """-> {"rate_up": (total_ms, launches), "rate_down": (...)}; names: which kernels ("rate_mix" is the conference mix)"""
         out = {}
-        for name in (b"rate_up", b"rate_down"):
+        for name in names:
             ms = ctypes.c_double()
             n = ctypes.c_int64()
-            self._chk(self.L.pn_rate_kernel_time(self.h, name, ctypes.byref(ms), ctypes.byref(n)))
-            out[name.decode()] = (ms.value, n.value)
+            self._chk(self.L.pn_rate_kernel_time(self.h, name.encode(), ctypes.byref(ms), ctypes.byref(n)))
+            out[name] = (ms.value, n.value)
         return out
 
     def export_streams(self, ids):

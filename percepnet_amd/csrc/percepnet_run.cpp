@@ -5,7 +5,7 @@
 // dropped, main.cpp:32-33); with a single pair ./feature_test.raw gets 68 floats per frame.
 //
 //   percepnet_run [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N]
-//                 [--rate 8000|16000|24000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
+//                 [--rate 8000|16000|24000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,..] [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
 //                 in0.pcm out0.pcm [in1.pcm out1.pcm ...]
 //
 // --rate R: the files are raw int16 at R Hz instead of 48 kHz, in frames of n = 480 * R / 48000 samples (80 | 160 | 240): a rate
@@ -29,6 +29,16 @@
 // all pairs; it is a setting of the converter's slots, set once, which slot resets and rate changes keep.  The rest of the
 // contract is unchanged: first output frame and partial tail dropped, --slots, --saturate (which a G.711 caller wants: a clipped
 // sample otherwise wraps before it is encoded), --report.
+//
+// --conference C0,C1,..: one entry per pair, a conference number in [0, pairs) or `-` for none: output file i holds what participant
+// i HEARS — the sum of the other members' enhanced signals (pn_rate_set_stream_confs: the mix between the engine and the
+// down-conversion, at 48 kHz, whatever the members' rates and codings) — and a pair marked `-` gets its own enhanced signal as
+// always.  It needs a converter: with --rate or --rates it uses theirs, alone it makes a mixed converter of all 48000 (the files
+// are then int16 at 48 kHz).  It combines with --g711 and --saturate (which a conference wants: a sum of voices clips where one
+// voice does not).  The frames go through pn_rate_submit_host_*_active with the list of the pairs that still have input: a pair
+// whose input has ended is no longer listed, so it contributes nothing instead of silence-through-the-engine, and its file is
+// complete.  Refused with --slots (a conference's members play from the start, side by side) and with more than one device (a
+// conference lives in one context).  --report stays about each pair's OWN output before the mix.
 //
 // --atten-lim DB: every stream takes out at most DB dB of noise (pn_ctx_set_atten_limit; 0 = the input, delayed; default: no
 // limit).  A slot reset clears a stream's limit (a reset slot is a new call), so the limit is set again on every reset slot.
@@ -95,6 +105,7 @@ static bool g_saturate = false, g_report = false;     // --saturate, --report
 static int g_rate = 0;                                // --rate: the files' sample rate (0: 48 kHz, no converter)
 static std::vector<int32_t> g_rates;                  // --rates: one rate per pair (empty: not given), a mixed converter
 static int g_g711 = -1;                               // --g711: the law of every pair's files (PN_G711_*; -1: linear int16)
+static std::vector<int32_t> g_confs;                  // --conference: one conference per pair (empty: not given; PN_CONF_NONE for `-`)
 // --report: what a pair's written frames add up to (one report record = PN_REPORT_WORDS words, include/percepnet_hip.h)
 struct PairStat { long frames = 0; long long clipped = 0; float peak = 0.f; double e_in = 0, e_out = 0; };
 static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, int postfilter, bool tap, int n_slots) {
@@ -124,6 +135,12 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
     std::vector<int32_t> all(B), laws(B, g_g711);
     for (int s = 0; s < B; s++) all[s] = s;
     if (pn_rate_set_stream_laws(rt, all.data(), B, laws.data())) return fail(3, std::string("pn_rate_set_stream_laws: ") + pn_last_error());
+  }
+  const bool conf = !g_confs.empty();
+  if (conf) {                                           // every slot's conference, once (one device, no --slots: slot s plays pair s)
+    std::vector<int32_t> all(B);
+    for (int s = 0; s < B; s++) all[s] = s;
+    if (pn_rate_set_stream_confs(rt, all.data(), B, g_confs.data() + sh->first)) return fail(3, std::string("pn_rate_set_stream_confs: ") + pn_last_error());
   }
   if (postfilter) pn_ctx_set_postfilter(cx, 1);
   if ((g_saturate && pn_ctx_set_output_saturate(cx, 1)) || (g_report && pn_ctx_set_report(cx, 1))) return fail(3, pn_last_error());
@@ -189,12 +206,12 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
       if (sl.last[s]) { fclose(sl.file[s]); }        // the pair's last frame has been written: its output file is complete
     }
   };
-  std::vector<int32_t> restart, restart_rates;
+  std::vector<int32_t> restart, restart_rates, live;   // live (--conference): the slots whose pair still has input, this frame's id list
   int n_alive = B;
   long t = 0;
   for (;; t++) {
     Slot &sl = slot[t % 3];
-    restart.clear(); restart_rates.clear();
+    restart.clear(); restart_rates.clear(); live.clear();
     for (int s = 0; s < B; s++) {
       char *x = sl.in + (size_t)s * FS * SW;
       sl.file[s] = NULL; sl.skip[s] = 0; sl.last[s] = 0;
@@ -217,6 +234,7 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
       }
       if (fin[s]) { sl.file[s] = fout[s]; sl.skip[s] = first[s]; first[s] = 0; sl.pair[s] = cur_pair[s]; sl.fs[s] = pair_fs(cur_pair[s]); }
       else memset(x, idle, FS * SW);
+      if (fin[s]) live.push_back(s);
     }
     if (n_alive == 0) break;
     if (!restart.empty() && (pn_ctx_reset_streams(cx, restart.data(), (int)restart.size()) ||
@@ -225,7 +243,10 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
                              set_limit(restart.data(), (int)restart.size()))) return fail(5, pn_last_error());
     if (g_report && pn_host_next_report(cx, sl.rep)) return fail(5, pn_last_error());
     // --rate, --rates: the converter's frame through the same pipeline
-    if (g_g711 >= 0 ? pn_rate_submit_host_g711(rt, (const uint8_t *)sl.in, (uint8_t *)sl.out, sl.gr)
+    // --conference: only the pairs that still have input advance, so an ended one is no member of this frame's mix
+    if (conf ? (g_g711 >= 0 ? pn_rate_submit_host_g711_active(rt, (const uint8_t *)sl.in, (uint8_t *)sl.out, sl.gr, live.data(), (int)live.size())
+                            : pn_rate_submit_host_i16_active(rt, (const int16_t *)sl.in, (int16_t *)sl.out, sl.gr, live.data(), (int)live.size()))
+        : g_g711 >= 0 ? pn_rate_submit_host_g711(rt, (const uint8_t *)sl.in, (uint8_t *)sl.out, sl.gr)
                     : rt ? pn_rate_submit_host_i16(rt, (const int16_t *)sl.in, (int16_t *)sl.out, sl.gr)
                          : pn_submit_host_i16(cx, (const int16_t *)sl.in, (int16_t *)sl.out, sl.gr)) return fail(5, pn_last_error());
     if (t >= 2) flush(slot[(t - 2) % 3]);
@@ -272,6 +293,19 @@ int main(int argc, char **argv) {
       g_g711 = !strcmp(v, "ulaw") ? PN_G711_ULAW : !strcmp(v, "alaw") ? PN_G711_ALAW : -1;
       if (g_g711 < 0) { fprintf(stderr, "--g711: expected ulaw or alaw, got '%s'\n", v); return 1; }
     }
+    else if (!strcmp(argv[ai], "--conference") && ai + 1 < argc) {  // one conference per pair, `-` for none (pn_rate_set_stream_confs)
+      const char *v = argv[++ai];
+      for (const char *q = v; ; ) {
+        char *end = NULL;
+        long c = PN_CONF_NONE;
+        if (*q == '-' && (q[1] == ',' || !q[1])) end = const_cast<char *>(q) + 1;
+        else c = strtol(q, &end, 10);
+        if (end == q || (*end && *end != ',') || c < PN_CONF_NONE || c > 0x7fffffff) { fprintf(stderr, "--conference: expected a comma-separated list of conference numbers or '-', got '%s'\n", v); return 1; }
+        g_confs.push_back((int32_t)c);
+        if (!*end) break;
+        q = end + 1;
+      }
+    }
     else if (!strcmp(argv[ai], "--no-numa")) g_numa = false;         // leave the host threads' CPU affinity alone
     else if (!strcmp(argv[ai], "--verbose")) g_verbose = true;       // one line per device: its NUMA binding
     else if (!strcmp(argv[ai], "--slots") && ai + 1 < argc) n_slots = atoi(argv[++ai]);   // concurrent streams per device: pairs queue for them
@@ -288,12 +322,19 @@ int main(int argc, char **argv) {
   const int nfiles = argc - ai;
   if (nfiles < 2 || (nfiles & 1) || (g_g711 >= 0 && !g_rate && g_rates.empty())) {
     if (g_g711 >= 0 && !g_rate && g_rates.empty()) fprintf(stderr, "--g711 needs --rate or --rates: G.711 rows go through a rate converter\n");
-    fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N] [--rate 8000|16000|24000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv[0]);
+    fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N] [--rate 8000|16000|24000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,..] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv[0]);
     return 1;
   }
   const int B = nfiles / 2;
   if (g_rate && !g_rates.empty()) { fprintf(stderr, "--rate and --rates exclude each other\n"); return 1; }
   if (!g_rates.empty() && (int)g_rates.size() != B) { fprintf(stderr, "--rates: %d rates for %d pairs (one per pair)\n", (int)g_rates.size(), B); return 1; }
+  if (!g_confs.empty()) {
+    if ((int)g_confs.size() != B) { fprintf(stderr, "--conference: %d entries for %d pairs (one per pair)\n", (int)g_confs.size(), B); return 1; }
+    if (n_slots > 0) { fprintf(stderr, "--conference and --slots exclude each other: the members of a conference play side by side from the start\n"); return 1; }
+    if (devices.size() > 1) { fprintf(stderr, "--conference takes one device: a conference lives in one context\n"); return 1; }
+    if (pn_rate_confs_check(g_confs.data(), B, B)) { fprintf(stderr, "--conference: %s\n", pn_last_error()); return 1; }
+    if (!g_rate && g_rates.empty()) g_rates.assign(B, 48000);        // on its own: a mixed converter of all 48000
+  }
   pn_model *m = NULL;
   if (model_path) { FILE *f = fopen(model_path, "rb"); if (f) { m = pn_model_from_file(f); fclose(f); } }
   else if (&percepnet_model_orig) m = pn_model_from_rnnmodel(&percepnet_model_orig);

@@ -97,6 +97,15 @@ int pn_launch_rate_down_mixed(hipStream_t st, int fmt, int n_rows, const int *d_
 void pn_launch_rate_records_dev(hipStream_t st, const int *d_ids, int n, const int *d_factors, int factor, float *tail_up, float *tail_down, int td_stride,
                                 void *rec, int stride_words, int *d_status, int scatter);
 void pn_launch_rate_set_factors(hipStream_t st, const int *d_ids, const int *d_vals, int n, int *d_factors);
+// the conference mix (pn_rate_mix.hip; rules in pn_conf.h): rows d_ids[0..n_rows) or, with d_ids == NULL, streams 0..n_rows of in48
+// [.][480] -> out48 [.][480], which must not overlap.  d_conf [n_streams]: the conference of every stream (NULL: nobody is in one,
+// every row is copied); d_members [n_streams][32]: the members of conference c in row c, ascending, -1 behind them.  With a list the
+// members that advance are those whose d_stamp word equals tick (conf_stamp, launched in front: d_stamp[d_ids[i]] = tick).
+// conf_rows: row d_touched[i] of d_members = d_rows[i][0..32), i < k
+void pn_launch_rate_mix(hipStream_t st, int n_rows, const int *d_ids, const int *d_conf, const int *d_members, const uint32_t *d_stamp, uint32_t tick,
+                        const float *in48, float *out48);
+void pn_launch_rate_conf_stamp(hipStream_t st, const int *d_ids, int n, uint32_t *d_stamp, uint32_t tick);
+void pn_launch_rate_conf_rows(hipStream_t st, const int *d_touched, const int *d_rows, int k, int *d_members);
 // ---- the network launchers (pn_nn*.hip) -----------------------------------------------------------------------------------------
 // Device pointers of a layer's biases and weights in the formats of pn_network.h: raw (w, rw), packed fp32 or fp16 planes (wp,
 // rwp), the 16x16x4 packing of a narrow layer (wq)

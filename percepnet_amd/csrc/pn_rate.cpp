@@ -8,6 +8,7 @@
 #include "pn_rate_design.h"
 #include "pn_rate_mixed.h"   // the mixed converter's host rules: the four rates, a rate change, one rate per record call
 #include "pn_g711.h"         // the 8-bit sample format: the companding and what a list of laws must be
+#include "pn_conf.h"         // conferences: what an id must be, the table after a change, the members in ascending order
 #include <string>
 #include <vector>
 
@@ -32,17 +33,25 @@ struct pn_rate {
   // factors.  A setting, not state: every reset, rate change and record call leaves it alone.  Default: mu-law everywhere
   std::vector<int32_t> laws;    // [B]
   int *d_laws = NULL;           // [B] device
+  // conferences (pn_rate_set_stream_confs): the conference of every stream as last set (host) and on the device, the member
+  // rows and the second 48 kHz row set the mix writes and the down-conversion then reads.  A setting like the law; the device
+  // side exists from the first call that puts a stream into a conference.  in_conf == 0: a frame launches nothing of it
+  std::vector<int32_t> confs;   // [B]
+  int in_conf = 0;              // streams in a conference
+  float *o48 = NULL;            // [B][480]
+  int *d_conf = NULL, *d_members = NULL;   // [B], [B][32]
+  uint32_t *d_stamp = NULL, tick = 0;      // [B]: == tick where the stream is on this frame's id list
   std::vector<void *> allocs;
-  // timing of the two kernels (pn_rate_set_profiling): HIP events around their launches, like the context's families but owned
+  // timing of the kernels (pn_rate_set_profiling): HIP events around their launches, like the context's families but owned
   // here; while it is off no event exists and none is recorded
   bool profiling = false;
   struct Ev { int fam; hipEvent_t a, b; };
   std::vector<Ev> events;
   std::vector<hipEvent_t> event_pool;
-  double fam_ms[2] = {0, 0}; int64_t fam_n[2] = {0, 0};
+  double fam_ms[3] = {0, 0, 0}; int64_t fam_n[3] = {0, 0, 0};
 };
-enum { RF_UP, RF_DOWN, RF_COUNT };
-static const char *const kRateFamily[RF_COUNT] = {"rate_up", "rate_down"};
+enum { RF_UP, RF_DOWN, RF_MIX, RF_COUNT };
+static const char *const kRateFamily[RF_COUNT] = {"rate_up", "rate_down", "rate_mix"};
 struct RateScope {
   pn_rate *r; int fam; hipEvent_t a, b; bool on;
   RateScope(pn_rate *r_, int fam_) : r(r_), fam(fam_), on(r_->profiling) {
@@ -92,6 +101,7 @@ extern "C" int pn_rate_mixed_rates_check(const int32_t *rates_hz, int n) { retur
 extern "C" int pn_g711_decode(int law, const uint8_t *in, int16_t *out, size_t n) { return pn_g711_decode_host(law, in, out, n); }
 extern "C" int pn_g711_encode(int law, const int16_t *in, uint8_t *out, size_t n) { return pn_g711_encode_host(law, in, out, n); }
 extern "C" int pn_rate_laws_check(const int32_t *laws, int n) { return pn_g711_laws_list_check(laws, n); }
+extern "C" int pn_rate_confs_check(const int32_t *confs, int n, int n_streams) { return pn_conf_list_check(confs, n, n_streams); }
 
 // ---- lifecycle ---------------------------------------------------------------------------------------------------------------
 extern "C" void pn_rate_destroy(pn_rate *r) {
@@ -114,7 +124,7 @@ extern "C" pn_rate *pn_rate_create(pn_ctx *c, int rate_hz) {
   if (!_dg.ok) { pn_set_error("hipSetDevice(%d) failed", c->device); return NULL; }
   pn_rate *r = new pn_rate();
   r->c = c; r->rate = rate_hz; r->L = L; r->n = PN_FRAME / L; r->td = pn_rate_down_tail(L); r->bytes = 0;
-  r->mixed = false; r->factors = NULL; r->h_rows = NULL; r->laws.assign((size_t)c->B, PN_G711_ULAW);
+  r->mixed = false; r->factors = NULL; r->h_rows = NULL; r->laws.assign((size_t)c->B, PN_G711_ULAW); r->confs.assign((size_t)c->B, PN_CONF_NONE);
   const size_t B = (size_t)c->B, nt = (size_t)r->td + 1;
   float h[2][PN_RATE_MAX_TAPS];
   auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
@@ -143,7 +153,7 @@ extern "C" pn_rate *pn_rate_create_mixed(pn_ctx *c, const int32_t *rates_hz) {
   if (!_dg.ok) { pn_set_error("hipSetDevice(%d) failed", c->device); return NULL; }
   pn_rate *r = new pn_rate();
   r->c = c; r->rate = 0; r->L = 0; r->n = PN_RATE_MIXED_ROW; r->td = pn_rate_down_tail(PN_RATE_MAX_L); r->bytes = 0;
-  r->mixed = true; r->factors = NULL; r->h_rows = NULL; r->laws.assign((size_t)c->B, PN_G711_ULAW);
+  r->mixed = true; r->factors = NULL; r->h_rows = NULL; r->laws.assign((size_t)c->B, PN_G711_ULAW); r->confs.assign((size_t)c->B, PN_CONF_NONE);
   const size_t B = (size_t)c->B;
   if (rates_hz) r->rates.assign(rates_hz, rates_hz + B); else r->rates.assign(B, 48000);
   static const int kL[3] = {6, 3, 2};
@@ -221,6 +231,53 @@ extern "C" int pn_rate_get_stream_laws(const pn_rate *r, int32_t *h_laws) {
   return 0;
 }
 
+// A conference change of the listed streams, ordered like a law change.  Everything is decided on the host first (pn_conf.h
+// pn_conf_change: the table after the change, the conferences it touches and their member rows); then the ids with their new
+// conferences and the touched rows go through the context's id ring, in bounded pieces, each followed by the launch that reads it.
+// No tail is touched.  The device side is allocated by the first call that needs it — here, never inside a frame.
+static int conf_buffers(pn_rate *r) {                // (the caller is on the context's device)
+  if (r->d_conf) return 0;
+  pn_ctx *c = r->c;
+  const size_t B = (size_t)c->B;
+  float *o48 = NULL; int *conf = NULL, *members = NULL; uint32_t *stamp = NULL;
+  auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
+  if (alloc((void **)&o48, B * PN_FRAME * 4, true) || alloc((void **)&conf, B * sizeof(int), false) ||
+      alloc((void **)&members, B * PN_CONF_MAX_MEMBERS * sizeof(int), false) || alloc((void **)&stamp, B * sizeof(uint32_t), true)) return -1;
+  PN_HIP_CHECK(hipMemsetAsync(conf, 0xFF, B * sizeof(int), c->stream));                               // PN_CONF_NONE
+  PN_HIP_CHECK(hipMemsetAsync(members, 0xFF, B * PN_CONF_MAX_MEMBERS * sizeof(int), c->stream));     // -1: no member
+  r->o48 = o48; r->d_members = members; r->d_stamp = stamp; r->tick = 0; r->d_conf = conf;
+  return 0;
+}
+extern "C" int pn_rate_set_stream_confs(pn_rate *r, const int32_t *ids, int n, const int32_t *confs) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  PnConfChange ch;
+  if (pn_conf_change(r->confs, ids, n, confs, &ch)) return -1;
+  if (n == 0 || (!r->d_conf && ch.in_conf == 0)) return 0;          // (nobody has ever been in a conference, and nobody is now)
+  PN_ON_DEVICE(r->c);
+  if (conf_buffers(r)) return -1;
+  for (int at = 0; at < n; at += 16384) {
+    const int m = n - at < 16384 ? n - at : 16384;
+    const int *d = stage_ids(r->c, ids + at, m, confs + at, m);
+    if (!d) return -1;
+    pn_launch_rate_set_factors(r->c->stream, d, d + ((m + 3) & ~3), m, r->d_conf);
+  }
+  const int k = (int)ch.touched.size();
+  for (int at = 0; at < k; at += 512) {
+    const int m = k - at < 512 ? k - at : 512;
+    const int *d = stage_ids(r->c, ch.touched.data() + at, m, ch.rows.data() + (size_t)at * PN_CONF_MAX_MEMBERS, m * PN_CONF_MAX_MEMBERS);
+    if (!d) return -1;
+    pn_launch_rate_conf_rows(r->c->stream, d, d + ((m + 3) & ~3), m, r->d_members);
+  }
+  PN_HIP_CHECK(hipGetLastError());
+  r->confs.swap(ch.next); r->in_conf = ch.in_conf;
+  return 0;
+}
+extern "C" int pn_rate_get_stream_confs(const pn_rate *r, int32_t *h_confs) {
+  if (!r || !h_confs) { pn_set_error("NULL argument"); return -1; }
+  for (int s = 0; s < r->c->B; s++) h_confs[s] = r->confs[s];
+  return 0;
+}
+
 extern "C" int pn_rate_reset(pn_rate *r) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   PN_ON_DEVICE(r->c);
@@ -274,6 +331,18 @@ static int rate_down(pn_rate *r, const float *d_in48, void *d_out, int fmt, cons
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
+// the mix: with a list, the listed streams' stamps first (which members advance is then known on the device), then one launch over the rows
+static int rate_mix(pn_rate *r, const float *d_in48, float *d_out48, const RateRows &rows) {
+  if (rows.n <= 0) return 0;
+  if (rows.d_ids && r->d_conf) {
+    if (++r->tick == 0) { PN_HIP_CHECK(hipMemsetAsync(r->d_stamp, 0, (size_t)r->c->B * sizeof(uint32_t), r->c->stream)); r->tick = 1; }   // (2^32 frames on)
+    pn_launch_rate_conf_stamp(r->c->stream, rows.d_ids, rows.n, r->d_stamp, r->tick);
+  }
+  RateScope sc(r, RF_MIX);
+  pn_launch_rate_mix(r->c->stream, rows.n, rows.d_ids, r->d_conf, r->d_members, r->d_stamp, r->tick, d_in48, d_out48);
+  PN_HIP_CHECK(hipGetLastError());
+  return 0;
+}
 static int rate_up_call(pn_rate *r, const void *d_in, int fmt, float *d_out48, const int32_t *ids, int n) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   if (rate_aligned(d_in, d_out48)) return -1;
@@ -296,10 +365,20 @@ extern "C" int pn_rate_up_g711(pn_rate *r, const uint8_t *d_in, float *d_out48, 
 extern "C" int pn_rate_down_f32(pn_rate *r, const float *d_in48, float *d_out, const int32_t *ids, int n_ids) { return rate_down_call(r, d_in48, d_out, PN_FMT_F32, ids, n_ids); }
 extern "C" int pn_rate_down_i16(pn_rate *r, const float *d_in48, int16_t *d_out, const int32_t *ids, int n_ids) { return rate_down_call(r, d_in48, d_out, PN_FMT_I16, ids, n_ids); }
 extern "C" int pn_rate_down_g711(pn_rate *r, const float *d_in48, uint8_t *d_out, const int32_t *ids, int n_ids) { return rate_down_call(r, d_in48, d_out, PN_FMT_G711, ids, n_ids); }
+extern "C" int pn_rate_mix_f32(pn_rate *r, const float *d_in48, float *d_out48, const int32_t *ids, int n_ids) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (rate_aligned(d_in48, d_out48)) return -1;
+  const uintptr_t a = (uintptr_t)d_in48, b = (uintptr_t)d_out48, span = (uintptr_t)r->c->B * PN_FRAME * 4;
+  if (a < b + span && b < a + span) { pn_set_error("the mix reads every member's row for every listener: its input and output rows must not overlap"); return -1; }
+  PN_ON_DEVICE(r->c);
+  RateRows rows;
+  if (rate_rows(r, ids, n_ids, &rows)) return -1;
+  return rate_mix(r, d_in48, d_out48, rows);
+}
 
 // ---- one whole frame -----------------------------------------------------------------------------------------------------------
 // up into x48, the engine's float frame from x48 into y48 (all streams, or the listed ones through the context's own active
-// set), down from y48.  A frame the engine refuses returns -1 with its error kept; the up kernel has then advanced its tails
+// set), down from y48 — or, while a stream is in a conference, the mix from y48 into o48 and down from o48.  A frame the engine refuses returns -1 with its error kept; the up kernel has then advanced its tails
 // and the down kernel has not, which is why the header asks for a reset of both objects before reuse.
 // rate_frame: the launches alone — the caller is on the context's device and has checked the rows and, when active, the list
 // (pn_ids_check, distinct), which is what lets the pipelined path refuse a list BEFORE the frame takes a pipeline slot.
@@ -312,7 +391,12 @@ static int rate_frame(pn_rate *r, const void *d_in, void *d_out, float *d_gr, in
   }
   if (rate_up(r, d_in, fmt, r->x48, rows)) return -1;
   if (active ? pn_process_f32_active(c, r->x48, r->y48, d_gr, ids, n) : pn_process_f32(c, r->x48, r->y48, d_gr)) return -1;
-  if (rate_down(r, r->y48, d_out, fmt, rows)) return -1;
+  const float *o = r->y48;
+  if (r->in_conf > 0) {                              // somebody is in a conference: the mix writes every advancing stream's row of o48
+    if (rate_mix(r, r->y48, r->o48, rows)) return -1;
+    o = r->o48;
+  }
+  if (rate_down(r, o, d_out, fmt, rows)) return -1;
   if (r->events.size() >= 4096 && rate_flush_events(r)) return -1;   // profiling left on: bound the pending events
   return 0;
 }
@@ -396,12 +480,12 @@ extern "C" int pn_rate_submit_host_f32_active(pn_rate *r, const float *h_in, flo
 extern "C" int pn_rate_submit_host_i16_active(pn_rate *r, const int16_t *h_in, int16_t *h_out, float *h_gr, const int32_t *ids, int n) { return rate_submit_host(r, h_in, h_out, h_gr, PN_FMT_I16, true, ids, n); }
 extern "C" int pn_rate_submit_host_g711_active(pn_rate *r, const uint8_t *h_in, uint8_t *h_out, float *h_gr, const int32_t *ids, int n) { return rate_submit_host(r, h_in, h_out, h_gr, PN_FMT_G711, true, ids, n); }
 
-// ---- timing the two kernels ----------------------------------------------------------------------------------------------------
+// ---- timing the kernels --------------------------------------------------------------------------------------------------------
 extern "C" int pn_rate_set_profiling(pn_rate *r, int enable) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
-  if (enable && r->event_pool.size() < 512) {         // two scopes a frame: enough for 128 frames between two reads; created outside any timed region
+  if (enable && r->event_pool.size() < 768) {         // up to three scopes a frame: enough for 128 frames between two reads; created outside any timed region
     PN_ON_DEVICE(r->c);
-    while (r->event_pool.size() < 512) { hipEvent_t e; PN_HIP_CHECK(hipEventCreate(&e)); r->event_pool.push_back(e); }
+    while (r->event_pool.size() < 768) { hipEvent_t e; PN_HIP_CHECK(hipEventCreate(&e)); r->event_pool.push_back(e); }
   }
   r->profiling = enable != 0;
   return 0;
@@ -412,7 +496,7 @@ extern "C" int pn_rate_kernel_time(pn_rate *r, const char *name, double *total_m
   if (rate_flush_events(r)) return -1;
   for (int i = 0; i < RF_COUNT; i++)
     if (!strcmp(name, kRateFamily[i])) { if (total_ms) *total_ms = r->fam_ms[i]; if (launches) *launches = r->fam_n[i]; return 0; }
-  pn_set_error("unknown converter kernel '%s' (rate_up, rate_down)", name);
+  pn_set_error("unknown converter kernel '%s' (rate_up, rate_down, rate_mix)", name);
   return -1;
 }
 extern "C" int pn_rate_reset_profile(pn_rate *r) {
