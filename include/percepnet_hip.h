@@ -679,13 +679,94 @@ int pn_rate_submit_host_g711_active(pn_rate *r, const uint8_t *h_in, uint8_t *h_
    16-byte aligned device addresses, asynchronous.  d_in48 == d_out48, or row sets that overlap, are refused.  ids == NULL: every
    stream advances; otherwise only the n_ids listed rows are read and written, and unlisted members contribute nothing.
    pn_rate_kernel_time takes "rate_mix" beside "rate_up" and "rate_down".
-   NOT provided: loudest-N selection, per-member gains, conferences of more than 32, a clipped-sample count of the mix. */
+   Loudest-N selection, per-member gains and a report of the mix: the next section.
+   NOT provided: conferences of more than 32 members or across contexts. */
 #define PN_CONF_NONE (-1)
 #define PN_CONF_MAX_MEMBERS 32
 int pn_rate_confs_check(const int32_t *confs, int n, int n_streams);
 int pn_rate_set_stream_confs(pn_rate *r, const int32_t *ids, int n, const int32_t *confs);
 int pn_rate_get_stream_confs(const pn_rate *r, int32_t *h_confs);
 int pn_rate_mix_f32(pn_rate *r, const float *d_in48, float *d_out48, const int32_t *ids, int n_ids);
+
+/* ---- conferences: loudest-N talkers, send gains, mix report ---------------------------------------------------------------------- */
+/* A bridge mixes the few loudest talkers, lets an operator mute or trim a member, and tells the application who speaks and whether
+   the sum clipped.  Three settings of the conference mix above and one report, all on the GPU in the mix's own launch
+   (csrc/pn_rate_mix.hip pn_rate_mix_sel_kernel), with fixed arithmetic that a float32 model reproduces bit for bit
+   (tests/mix_sel_model.py; the host's statement of the level and the selection: csrc/pn_mix_rules.h).
+
+   Arithmetic, for one frame: A = the streams that advance, y[m] = the engine's float row of stream m, c = a conference.
+     send gain g_m: fp32, finite, >= 0, default 1.0f.  g_m == 0 MUTES the member: it is no talker, its row is not read (an inf or
+       NaN in it reaches nobody), it contributes nothing, it is never selected — and it still hears.  Otherwise its contribution
+       is x[m][j] = g_m * y[m][j], one fp32 product, never fused with the add behind it.  Gains act inside a conference only: a
+       PN_CONF_NONE stream gets y[s] bit for bit whatever its gain.
+     talkers of c: its members in A with g_m != 0.
+     level of a talker: E_m = the sum of x*x over its 480 samples in ONE order: the products rounded separately; group q = j / 4
+       (120 groups) sums its four products in index order from +0.0f; the 120 group sums, padded with +0.0f to 128, are two halves
+       of 64; each half folds by the xor butterfly v[i] = v[i] + v[i ^ stride] with strides 32, 16, 8, 4, 2, 1; E = half0[0] +
+       half1[0].  That is the order of the mix kernel's layout (thread t owns columns 4t..4t+3, two wavefronts) and NOT the order
+       of the frame report's out_energy, whose last bits differ.
+     hold: one factor d per converter, fp32 in [0, 1), default 0.  h = d * L_prev[m];  L_m = (d != 0 && isfinite(h) && h > E_m) ?
+       h : E_m — a peak hold with exponential release.  d == 0: L = E exactly; a non-finite level never sticks.  L is the only new
+       STATE: one float per stream.  An advancing muted member's level becomes +0.0.
+     selection: every conference NUMBER c has N_c in [0, 32], default 0 = everybody.  key(L) = the uint32 bits of L with the sign
+       bit cleared (NaN ranks above +inf; two NaNs rank by their bits).  Talker m is selected iff N_c == 0, or fewer than N_c
+       talkers q of c have key(L_q) > key(L_m) or (key(L_q) == key(L_m) and q < m): ties go to the lower slot.
+     mix: listener s in A of conference c gets o[s][j] = the sum of x[m][j] over the SELECTED talkers m != s, m ascending, from
+       acc = +0.0f in plain fp32 adds — the rule of the section above with "advancing member" replaced by "selected talker".  A
+       selected talker hears the other selected ones, everybody else all of them.  With all gains 1 and N_c 0 or at least the
+       number of talkers the rows are bit for bit those of the section above.
+   Mix report (optional): PN_MIX_REPORT_WORDS = 4 little-endian words per stream, [n_streams][4], written for every stream in A;
+   the rows of other streams are left as they were:
+     word 0  f32 level        L_s; +0.0 for a muted member and for a stream without a conference
+     word 1  u32 flags        bit 0 selected this frame, bit 1 muted, bit 2 in a conference
+     word 2  f32 mix_peak     max |o[s][j]| from 0 with fmax, so a NaN sample is ignored (the frame report's peak rule); 0 without a
+                              conference
+     word 3  i32 mix_clipped  the samples of o[s] whose t = o * 32768 lies outside (-32769, 32768), NaN counting: the frame report's
+                              out_clipped rule applied to what the stream HEARS; 0 without a conference
+
+   Setting calls.  Id lists follow the context's rules (distinct, in range); a bad id, a duplicate or a bad value refuses the call
+   with -1, pn_last_error names the first offender, and nothing is changed or launched; n == 0 is a no-op.  Asynchronous on the
+   context's stream and ordered exactly like pn_rate_set_stream_confs: frames submitted before the call use the old values, frames
+   after it the new ones, on the pipelined path too, with no wait; the caller may reuse its arrays on return.
+     pn_rate_set_stream_mix_gains: gains[i] for stream ids[i]; NaN, inf and negative gains are refused, -0.0f is 0.
+     pn_rate_get_stream_mix_gains: h_gains [n_streams].
+     pn_rate_set_conf_speakers: confs[i] distinct conference numbers in [0, n_streams), max_speakers[i] in [0, PN_CONF_MAX_MEMBERS].
+     pn_rate_get_conf_speakers: h_n [n_streams], indexed by conference number.
+     pn_rate_set_mix_hold: d outside [0, 1) or NaN is refused; zeroes every stream's level, in stream order.  pn_rate_get_mix_hold.
+     pn_rate_set_mix_report(r, enable); pn_rate_read_mix_report: the last frame's records to h_report [n_streams][4] words,
+     synchronising like pn_ctx_read_report; pn_rate_read_mix_report_dev: the same into a device buffer, asynchronous on the
+     context's stream.  Both return -1 while the report is off.  Delivery through pn_host_next_report is NOT provided: on the
+     pipelined path read the records with pn_rate_read_mix_report_dev between two submits, or after pn_host_wait.
+   Host only, needing no GPU: pn_rate_mix_gains_check (0, or -1 naming the first bad index); pn_mix_level: E of a row of 480
+   contributions x (the gain already applied; NaN and pn_last_error for a NULL row); pn_mix_select: levels[0..k) of one
+   conference's talkers in ascending slot order, n_max = N_c, selected[i] = 1 | 0; returns how many are selected, -1 for k or
+   n_max outside [0, 32].
+   Lifecycle.  Gains, N_c, the hold factor and the report switch are SETTINGS: records do not carry them (format, version and sizes
+   are unchanged); pn_rate_reset, pn_rate_reset_streams, rate changes and the record calls keep them; N_c belongs to the conference
+   number and survives the conference emptying.  The level L is state that records do not carry: zeroed by pn_rate_reset, and for
+   the listed streams by pn_rate_reset_streams, pn_rate_set_stream_rates and pn_rate_set_stream_confs, for all streams by
+   pn_rate_set_mix_hold; a stream that does not advance keeps it; an import leaves the slot's own level.  The device buffers
+   (gains, N_c, levels, report rows) are allocated inside the setting calls, never inside a frame.
+   When it runs.  While every gain is 1.0f, every N_c is 0, d is 0 and the mix report is off, a frame (and pn_rate_mix_f32) launches
+   exactly what it launches without this section, and the levels are not touched.  Otherwise the mix is the selecting kernel, in
+   every entry point the mix runs in, pn_rate_mix_f32 included, which then also advances the levels; while a setting is off its
+   default the mix runs even when no stream is in a conference (every row is then a copy, every record zero).  It is timed under
+   "rate_mix".
+   NOT provided: conferences of more than 32 members or across contexts, selection by voice activity rather than energy, the mix
+   report on pn_host_next_report. */
+#define PN_MIX_REPORT_WORDS 4
+int pn_rate_mix_gains_check(const float *gains, int n);
+float pn_mix_level(const float *row480);
+int pn_mix_select(const float *levels, int k, int n_max, uint8_t *selected);
+int pn_rate_set_stream_mix_gains(pn_rate *r, const int32_t *ids, int n, const float *gains);
+int pn_rate_get_stream_mix_gains(const pn_rate *r, float *h_gains);
+int pn_rate_set_conf_speakers(pn_rate *r, const int32_t *confs, int n, const int32_t *max_speakers);
+int pn_rate_get_conf_speakers(const pn_rate *r, int32_t *h_n);
+int pn_rate_set_mix_hold(pn_rate *r, float d);
+float pn_rate_get_mix_hold(const pn_rate *r);
+int pn_rate_set_mix_report(pn_rate *r, int enable);
+int pn_rate_read_mix_report(pn_rate *r, void *h_report);
+int pn_rate_read_mix_report_dev(pn_rate *r, void *d_report);
 
 const char *pn_last_error(void);
 const char *pn_version(void);

@@ -25,6 +25,9 @@ RATE_MIXED_ROW = 480                          # PN_RATE_MIXED_ROW: samples betwe
 RATE_TAPS = 16
 G711_ULAW, G711_ALAW = 0, 1                   # PN_G711_*: the law of a stream's 8-bit rows (pn_rate_set_stream_laws)
 CONF_NONE, CONF_MAX_MEMBERS = -1, 32          # PN_CONF_*: no conference; the most streams one holds (pn_rate_set_stream_confs)
+MIX_REPORT_WORDS = 4                          # PN_MIX_REPORT_WORDS: words of one record of the mix report (pn_rate_set_mix_report)
+MIX_SELECTED, MIX_MUTED, MIX_IN_CONF = 1, 2, 4                      # its flags
+MIX_REPORT_DTYPE = np.dtype([("level", "<f4"), ("flags", "<u4"), ("mix_peak", "<f4"), ("mix_clipped", "<i4")])
 # per-stream frame report (include/percepnet_hip.h pn_ctx_set_report): one record of PN_REPORT_WORDS 32-bit words per stream
 REPORT_WORDS = 8
 REPORT_DTYPE = np.dtype([("in_peak", "<f4"), ("in_energy", "<f4"), ("out_peak", "<f4"), ("out_energy", "<f4"), ("gain_mean", "<f4"),
@@ -182,6 +185,19 @@ def load_library():
         L.pn_rate_set_stream_confs.argtypes = [_vp, _vp, ctypes.c_int, _vp]
         L.pn_rate_get_stream_confs.argtypes = [_vp, _vp]
         L.pn_rate_mix_f32.argtypes = [_vp, _vp, _vp, _vp, ctypes.c_int]
+    if hasattr(L, "pn_rate_set_conf_speakers"):
+        L.pn_rate_mix_gains_check.argtypes = [_vp, ctypes.c_int]
+        L.pn_mix_level.restype = ctypes.c_float
+        L.pn_mix_level.argtypes = [_vp]
+        L.pn_mix_select.argtypes = [_vp, ctypes.c_int, ctypes.c_int, _vp]
+        for name in ("pn_rate_set_stream_mix_gains", "pn_rate_set_conf_speakers"):
+            getattr(L, name).argtypes = [_vp, _vp, ctypes.c_int, _vp]
+        for name in ("pn_rate_get_stream_mix_gains", "pn_rate_get_conf_speakers", "pn_rate_read_mix_report", "pn_rate_read_mix_report_dev"):
+            getattr(L, name).argtypes = [_vp, _vp]
+        L.pn_rate_set_mix_hold.argtypes = [_vp, ctypes.c_float]
+        L.pn_rate_get_mix_hold.restype = ctypes.c_float
+        L.pn_rate_get_mix_hold.argtypes = [_vp]
+        L.pn_rate_set_mix_report.argtypes = [_vp, ctypes.c_int]
     if hasattr(L, "pn_host_pipeline_prepare"):
         L.pn_host_pipeline_prepare.argtypes = [_vp]
     L.pn_ctx_debug_copy.restype = ctypes.c_longlong
@@ -578,6 +594,35 @@ def rate_confs_check(confs, n_streams):
         raise PercepNetError(_err(L))
 
 
+def rate_mix_gains_check(gains):
+    """Raises PercepNetError naming the first entry of `gains` that is no send gain of the conference mix, a finite value >= 0
+    (pn_rate_mix_gains_check, host only)."""
+    L = load_library()
+    a = np.ascontiguousarray(np.asarray(gains, dtype=np.float32).ravel())
+    if L.pn_rate_mix_gains_check(a.ctypes.data, int(a.size)) != 0:
+        raise PercepNetError(_err(L))
+
+
+def mix_level(row):
+    """The level E of one talker's 480 contributions (the send gain already applied) in the mix kernel's summation order
+    (pn_mix_level, host only) -> numpy float32 scalar."""
+    a = np.ascontiguousarray(row, dtype=np.float32).ravel()
+    if a.size != 480:
+        raise PercepNetError(f"a row of {a.size} samples: a 48 kHz row has 480")
+    return np.float32(load_library().pn_mix_level(a.ctypes.data))
+
+
+def mix_select(levels, n_max):
+    """Which of one conference's talkers (their levels, ascending slot order) the loudest-N rule selects (pn_mix_select, host
+    only): n_max = 0 selects everybody -> bool [k]."""
+    L = load_library()
+    a = np.ascontiguousarray(np.asarray(levels, dtype=np.float32).ravel())
+    sel = np.zeros(max(int(a.size), 1), np.uint8)
+    if L.pn_mix_select(a.ctypes.data, int(a.size), int(n_max), sel.ctypes.data) < 0:
+        raise PercepNetError(_err(L))
+    return sel[:a.size].astype(bool)
+
+
 class RateConverter:
     """8, 16 or 24 kHz streams through a 48 kHz Context (pn_rate): a converter beside `ctx` for all of its streams at ONE rate.
     It borrows the context (device, n_streams, HIP stream): close the converter before the context."""
@@ -709,6 +754,57 @@ class RateConverter:
     def mix_f32_dev(self, d_in48, d_out48, ids=None):
         """The mix kernel on its own (pn_rate_mix_f32): device rows [n_streams][480] float, which must not overlap."""
         self._kernel("pn_rate_mix_f32", d_in48, d_out48, ids)
+
+    # loudest-N talkers, send gains, hold and the mix report: settings of the conference mix, ordered like set_stream_confs
+    def set_stream_mix_gains(self, ids, gains):
+        """Streams `ids` send into their conferences with `gains` (finite, >= 0; 0 mutes: the member still hears) from the next
+        frame on (pn_rate_set_stream_mix_gains)."""
+        a, n = self._ids(ids)
+        w = np.ascontiguousarray(np.asarray(gains, dtype=np.float32).ravel())
+        if w.size != n:
+            raise PercepNetError(f"{w.size} gains for {n} streams")
+        self._chk(self.L.pn_rate_set_stream_mix_gains(self.h, a.ctypes.data, n, w.ctypes.data))
+
+    def stream_mix_gains(self):
+        """-> float32 [n_streams]: the send gains as last set (pn_rate_get_stream_mix_gains); 1 everywhere on a new converter."""
+        w = np.empty(self.n_streams, np.float32)
+        self._chk(self.L.pn_rate_get_stream_mix_gains(self.h, w.ctypes.data))
+        return w
+
+    def set_conf_speakers(self, confs, max_speakers):
+        """The conferences numbered `confs` mix their `max_speakers` loudest talkers only, 0 = everybody, at most
+        CONF_MAX_MEMBERS (pn_rate_set_conf_speakers); the number keeps its cap while the conference is empty."""
+        a, n = self._ids(confs)
+        w = np.ascontiguousarray(np.asarray(max_speakers, dtype=np.int32).ravel())
+        if w.size != n:
+            raise PercepNetError(f"{w.size} caps for {n} conferences")
+        self._chk(self.L.pn_rate_set_conf_speakers(self.h, a.ctypes.data, n, w.ctypes.data))
+
+    def conf_speakers(self):
+        """-> int32 [n_streams], indexed by conference number (pn_rate_get_conf_speakers); 0 everywhere on a new converter."""
+        w = np.empty(self.n_streams, np.int32)
+        self._chk(self.L.pn_rate_get_conf_speakers(self.h, w.ctypes.data))
+        return w
+
+    def set_mix_hold(self, d):
+        """The hold factor of the talkers' levels, in [0, 1); 0 = no hold (pn_rate_set_mix_hold).  Zeroes every stream's level."""
+        self._chk(self.L.pn_rate_set_mix_hold(self.h, float(d)))
+
+    def mix_hold(self):
+        return float(self.L.pn_rate_get_mix_hold(self.h))
+
+    def set_mix_report(self, on):
+        self._chk(self.L.pn_rate_set_mix_report(self.h, 1 if on else 0))
+
+    def read_mix_report(self):
+        """-> MIX_REPORT_DTYPE [n_streams]: the records of the last mix (pn_rate_read_mix_report, synchronising)."""
+        rep = np.empty(self.n_streams, MIX_REPORT_DTYPE)
+        self._chk(self.L.pn_rate_read_mix_report(self.h, rep.ctypes.data))
+        return rep
+
+    def read_mix_report_dev(self, d_report):
+        """The same into device memory [n_streams][4] words, asynchronous on the context's stream (pn_rate_read_mix_report_dev)."""
+        self._chk(self.L.pn_rate_read_mix_report_dev(self.h, d_report))
 
     # one whole frame, device pointers: [n_streams][frame] in and out at the low rate, d_gr [n_streams][68] or None
     def process_f32_dev(self, d_in, d_out, d_gr=None, ids=None):

@@ -5,7 +5,7 @@
 // dropped, main.cpp:32-33); with a single pair ./feature_test.raw gets 68 floats per frame.
 //
 //   percepnet_run [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N]
-//                 [--rate 8000|16000|24000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,..] [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
+//                 [--rate 8000|16000|24000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
 //                 in0.pcm out0.pcm [in1.pcm out1.pcm ...]
 //
 // --rate R: the files are raw int16 at R Hz instead of 48 kHz, in frames of n = 480 * R / 48000 samples (80 | 160 | 240): a rate
@@ -39,6 +39,9 @@
 // whose input has ended is no longer listed, so it contributes nothing instead of silence-through-the-engine, and its file is
 // complete.  Refused with --slots (a conference's members play from the start, side by side) and with more than one device (a
 // conference lives in one context).  --report stays about each pair's OWN output before the mix.
+// --conf-speakers N: every conference mixes its N loudest talkers only (pn_rate_set_conf_speakers; 0 = everybody, up to 32);
+// --mix-gains G0,G1,..: one send gain per pair (pn_rate_set_stream_mix_gains; 0 mutes the pair, which still hears).  Both need
+// --conference and are refused without it.
 //
 // --atten-lim DB: every stream takes out at most DB dB of noise (pn_ctx_set_atten_limit; 0 = the input, delayed; default: no
 // limit).  A slot reset clears a stream's limit (a reset slot is a new call), so the limit is set again on every reset slot.
@@ -106,6 +109,8 @@ static int g_rate = 0;                                // --rate: the files' samp
 static std::vector<int32_t> g_rates;                  // --rates: one rate per pair (empty: not given), a mixed converter
 static int g_g711 = -1;                               // --g711: the law of every pair's files (PN_G711_*; -1: linear int16)
 static std::vector<int32_t> g_confs;                  // --conference: one conference per pair (empty: not given; PN_CONF_NONE for `-`)
+static int g_conf_speakers = -1;                      // --conf-speakers: N of every conference (-1: not given)
+static std::vector<float> g_mix_gains;                // --mix-gains: one send gain per pair (empty: not given)
 // --report: what a pair's written frames add up to (one report record = PN_REPORT_WORDS words, include/percepnet_hip.h)
 struct PairStat { long frames = 0; long long clipped = 0; float peak = 0.f; double e_in = 0, e_out = 0; };
 static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, int postfilter, bool tap, int n_slots) {
@@ -141,6 +146,12 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
     std::vector<int32_t> all(B);
     for (int s = 0; s < B; s++) all[s] = s;
     if (pn_rate_set_stream_confs(rt, all.data(), B, g_confs.data() + sh->first)) return fail(3, std::string("pn_rate_set_stream_confs: ") + pn_last_error());
+    if (g_conf_speakers >= 0) {                         // one cap for every conference number
+      std::vector<int32_t> caps(B, g_conf_speakers);
+      if (pn_rate_set_conf_speakers(rt, all.data(), B, caps.data())) return fail(3, std::string("pn_rate_set_conf_speakers: ") + pn_last_error());
+    }
+    if (!g_mix_gains.empty() && pn_rate_set_stream_mix_gains(rt, all.data(), B, g_mix_gains.data() + sh->first))
+      return fail(3, std::string("pn_rate_set_stream_mix_gains: ") + pn_last_error());
   }
   if (postfilter) pn_ctx_set_postfilter(cx, 1);
   if ((g_saturate && pn_ctx_set_output_saturate(cx, 1)) || (g_report && pn_ctx_set_report(cx, 1))) return fail(3, pn_last_error());
@@ -306,6 +317,24 @@ int main(int argc, char **argv) {
         q = end + 1;
       }
     }
+    else if (!strcmp(argv[ai], "--conf-speakers") && ai + 1 < argc) {   // the loudest N talkers of every conference (pn_rate_set_conf_speakers)
+      const char *v = argv[++ai];
+      char *end = NULL;
+      const long n = strtol(v, &end, 10);
+      if (end == v || *end || n < 0 || n > PN_CONF_MAX_MEMBERS) { fprintf(stderr, "--conf-speakers: expected a number in [0, %d], got '%s'\n", PN_CONF_MAX_MEMBERS, v); return 1; }
+      g_conf_speakers = (int)n;
+    }
+    else if (!strcmp(argv[ai], "--mix-gains") && ai + 1 < argc) {   // one send gain per pair (pn_rate_set_stream_mix_gains)
+      const char *v = argv[++ai];
+      for (const char *q = v; ; ) {
+        char *end = NULL;
+        const float g = strtof(q, &end);
+        if (end == q || (*end && *end != ',')) { fprintf(stderr, "--mix-gains: expected a comma-separated list of gains, got '%s'\n", v); return 1; }
+        g_mix_gains.push_back(g);
+        if (!*end) break;
+        q = end + 1;
+      }
+    }
     else if (!strcmp(argv[ai], "--no-numa")) g_numa = false;         // leave the host threads' CPU affinity alone
     else if (!strcmp(argv[ai], "--verbose")) g_verbose = true;       // one line per device: its NUMA binding
     else if (!strcmp(argv[ai], "--slots") && ai + 1 < argc) n_slots = atoi(argv[++ai]);   // concurrent streams per device: pairs queue for them
@@ -322,12 +351,20 @@ int main(int argc, char **argv) {
   const int nfiles = argc - ai;
   if (nfiles < 2 || (nfiles & 1) || (g_g711 >= 0 && !g_rate && g_rates.empty())) {
     if (g_g711 >= 0 && !g_rate && g_rates.empty()) fprintf(stderr, "--g711 needs --rate or --rates: G.711 rows go through a rate converter\n");
-    fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N] [--rate 8000|16000|24000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,..] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv[0]);
+    fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N] [--rate 8000|16000|24000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv[0]);
     return 1;
   }
   const int B = nfiles / 2;
   if (g_rate && !g_rates.empty()) { fprintf(stderr, "--rate and --rates exclude each other\n"); return 1; }
   if (!g_rates.empty() && (int)g_rates.size() != B) { fprintf(stderr, "--rates: %d rates for %d pairs (one per pair)\n", (int)g_rates.size(), B); return 1; }
+  if (g_confs.empty() && (g_conf_speakers >= 0 || !g_mix_gains.empty())) {
+    fprintf(stderr, "%s needs --conference: it is a setting of the conference mix\n", g_conf_speakers >= 0 ? "--conf-speakers" : "--mix-gains");
+    return 1;
+  }
+  if (!g_mix_gains.empty()) {
+    if ((int)g_mix_gains.size() != B) { fprintf(stderr, "--mix-gains: %d gains for %d pairs (one per pair)\n", (int)g_mix_gains.size(), B); return 1; }
+    if (pn_rate_mix_gains_check(g_mix_gains.data(), B)) { fprintf(stderr, "--mix-gains: %s\n", pn_last_error()); return 1; }
+  }
   if (!g_confs.empty()) {
     if ((int)g_confs.size() != B) { fprintf(stderr, "--conference: %d entries for %d pairs (one per pair)\n", (int)g_confs.size(), B); return 1; }
     if (n_slots > 0) { fprintf(stderr, "--conference and --slots exclude each other: the members of a conference play side by side from the start\n"); return 1; }

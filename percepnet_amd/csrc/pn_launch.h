@@ -104,6 +104,10 @@ void pn_launch_rate_set_factors(hipStream_t st, const int *d_ids, const int *d_v
 // conf_rows: row d_touched[i] of d_members = d_rows[i][0..32), i < k
 void pn_launch_rate_mix(hipStream_t st, int n_rows, const int *d_ids, const int *d_conf, const int *d_members, const uint32_t *d_stamp, uint32_t tick,
                         const float *in48, float *out48);
+// the same with loudest-N selection, send gains and the mix report (pn_mix_rules.h): d_gains [n_streams], d_caps [n_streams] by
+// conference number, d_level [n_streams] read and written, d_report [n_streams][4] words or NULL.  d_conf is not NULL here
+void pn_launch_rate_mix_sel(hipStream_t st, int n_rows, const int *d_ids, const int *d_conf, const int *d_members, const uint32_t *d_stamp, uint32_t tick,
+                            const float *in48, float *out48, const float *d_gains, const int *d_caps, float *d_level, float hold, void *d_report);
 void pn_launch_rate_conf_stamp(hipStream_t st, const int *d_ids, int n, uint32_t *d_stamp, uint32_t tick);
 void pn_launch_rate_conf_rows(hipStream_t st, const int *d_touched, const int *d_rows, int k, int *d_members);
 // ---- the network launchers (pn_nn*.hip) -----------------------------------------------------------------------------------------

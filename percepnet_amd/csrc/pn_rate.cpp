@@ -9,6 +9,7 @@
 #include "pn_rate_mixed.h"   // the mixed converter's host rules: the four rates, a rate change, one rate per record call
 #include "pn_g711.h"         // the 8-bit sample format: the companding and what a list of laws must be
 #include "pn_conf.h"         // conferences: what an id must be, the table after a change, the members in ascending order
+#include "pn_mix_rules.h"    // loudest-N, send gains, hold: what the settings must be; the level and the selection for the host
 #include <string>
 #include <vector>
 
@@ -41,6 +42,17 @@ struct pn_rate {
   float *o48 = NULL;            // [B][480]
   int *d_conf = NULL, *d_members = NULL;   // [B], [B][32]
   uint32_t *d_stamp = NULL, tick = 0;      // [B]: == tick where the stream is on this frame's id list
+  // loudest-N selection, send gains, hold and the mix report (pn_mix_rules.h): SETTINGS as last set (host) and on the device, and the
+  // one new state, a level per stream.  While every setting is at its default (mix_plain) rate_mix launches the plain kernel and
+  // none of the device side is read; it is allocated by the first setting call that leaves the defaults, never inside a frame
+  std::vector<float> gains;     // [B], 1.0f
+  std::vector<int32_t> caps;    // [B] N_c by conference number, 0: everybody
+  int gains_off = 0, caps_on = 0;          // how many gains are not 1.0f, how many caps not 0
+  float hold = 0.0f;            // d
+  bool mix_report = false;
+  float *d_gains = NULL, *d_level = NULL;  // [B], [B]
+  int *d_caps = NULL;                      // [B]
+  void *d_mix_report = NULL;               // [B][PN_MIX_REPORT_WORDS] words
   std::vector<void *> allocs;
   // timing of the kernels (pn_rate_set_profiling): HIP events around their launches, like the context's families but owned
   // here; while it is off no event exists and none is recorded
@@ -102,6 +114,9 @@ extern "C" int pn_g711_decode(int law, const uint8_t *in, int16_t *out, size_t n
 extern "C" int pn_g711_encode(int law, const int16_t *in, uint8_t *out, size_t n) { return pn_g711_encode_host(law, in, out, n); }
 extern "C" int pn_rate_laws_check(const int32_t *laws, int n) { return pn_g711_laws_list_check(laws, n); }
 extern "C" int pn_rate_confs_check(const int32_t *confs, int n, int n_streams) { return pn_conf_list_check(confs, n, n_streams); }
+extern "C" int pn_rate_mix_gains_check(const float *gains, int n) { return pn_mix_gains_list_check(gains, n); }
+extern "C" float pn_mix_level(const float *row480) { if (!row480) { pn_set_error("NULL argument"); return NAN; } return pn_mix_level_host(row480); }
+extern "C" int pn_mix_select(const float *levels, int k, int n_max, uint8_t *selected) { return pn_mix_select_host(levels, k, n_max, selected); }
 
 // ---- lifecycle ---------------------------------------------------------------------------------------------------------------
 extern "C" void pn_rate_destroy(pn_rate *r) {
@@ -125,6 +140,7 @@ extern "C" pn_rate *pn_rate_create(pn_ctx *c, int rate_hz) {
   pn_rate *r = new pn_rate();
   r->c = c; r->rate = rate_hz; r->L = L; r->n = PN_FRAME / L; r->td = pn_rate_down_tail(L); r->bytes = 0;
   r->mixed = false; r->factors = NULL; r->h_rows = NULL; r->laws.assign((size_t)c->B, PN_G711_ULAW); r->confs.assign((size_t)c->B, PN_CONF_NONE);
+  r->gains.assign((size_t)c->B, 1.0f); r->caps.assign((size_t)c->B, 0);
   const size_t B = (size_t)c->B, nt = (size_t)r->td + 1;
   float h[2][PN_RATE_MAX_TAPS];
   auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
@@ -154,6 +170,7 @@ extern "C" pn_rate *pn_rate_create_mixed(pn_ctx *c, const int32_t *rates_hz) {
   pn_rate *r = new pn_rate();
   r->c = c; r->rate = 0; r->L = 0; r->n = PN_RATE_MIXED_ROW; r->td = pn_rate_down_tail(PN_RATE_MAX_L); r->bytes = 0;
   r->mixed = true; r->factors = NULL; r->h_rows = NULL; r->laws.assign((size_t)c->B, PN_G711_ULAW); r->confs.assign((size_t)c->B, PN_CONF_NONE);
+  r->gains.assign((size_t)c->B, 1.0f); r->caps.assign((size_t)c->B, 0);
   const size_t B = (size_t)c->B;
   if (rates_hz) r->rates.assign(rates_hz, rates_hz + B); else r->rates.assign(B, 48000);
   static const int kL[3] = {6, 3, 2};
@@ -206,6 +223,7 @@ extern "C" int pn_rate_set_stream_rates(pn_rate *r, const int32_t *ids, int n, c
   pn_launch_rate_set_factors(r->c->stream, d, d + ((n + 3) & ~3), n, r->factors);
   pn_launch_zero_rows(r->c->stream, r->tail_up, PN_RATE_UP_TAIL, PN_RATE_UP_TAIL, 1, 0, d, n);
   pn_launch_zero_rows(r->c->stream, r->tail_down, r->td, r->td, 1, 0, d, n);
+  pn_launch_zero_rows(r->c->stream, r->d_level, 1, 1, 1, 0, d, n);       // (nothing while no level exists)
   PN_HIP_CHECK(hipGetLastError());
   for (int i = 0; i < n; i++) r->rates[ids[i]] = rates_hz[i];
   return 0;
@@ -260,6 +278,7 @@ extern "C" int pn_rate_set_stream_confs(pn_rate *r, const int32_t *ids, int n, c
     const int *d = stage_ids(r->c, ids + at, m, confs + at, m);
     if (!d) return -1;
     pn_launch_rate_set_factors(r->c->stream, d, d + ((m + 3) & ~3), m, r->d_conf);
+    pn_launch_zero_rows(r->c->stream, r->d_level, 1, 1, 1, 0, d, m);     // a listed stream's level starts again
   }
   const int k = (int)ch.touched.size();
   for (int at = 0; at < k; at += 512) {
@@ -278,11 +297,106 @@ extern "C" int pn_rate_get_stream_confs(const pn_rate *r, int32_t *h_confs) {
   return 0;
 }
 
+// ---- loudest-N talkers, send gains, hold, mix report (include/percepnet_hip.h; rules pn_mix_rules.h) ---------------------------
+// Settings, written in stream order through the context's id ring like the conference table, so a frame submitted before a call
+// runs under the old values.  "plain": every setting at its default — rate_mix then launches what it always launched.
+static bool mix_plain(const pn_rate *r) { return r->gains_off == 0 && r->caps_on == 0 && r->hold == 0.0f && !r->mix_report; }
+static int mix_buffers(pn_rate *r) {                 // (the caller is on the context's device)
+  if (conf_buffers(r)) return -1;
+  if (r->d_level) return 0;
+  pn_ctx *c = r->c;
+  const size_t B = (size_t)c->B;
+  float *gains = NULL, *level = NULL; int *caps = NULL;
+  auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
+  if (alloc((void **)&gains, B * 4, false) || alloc((void **)&caps, B * sizeof(int), true) || alloc((void **)&level, B * 4, true)) return -1;
+  PN_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)gains, 0x3f800000, B, c->stream));                  // 1.0f
+  r->d_gains = gains; r->d_caps = caps; r->d_level = level;
+  return 0;
+}
+// dst[ids[i]] = words[i] through the id ring, in bounded pieces, each followed by the launch that reads it
+static int mix_set_words(pn_rate *r, const int32_t *ids, int n, const void *words, int *dst) {
+  for (int at = 0; at < n; at += 16384) {
+    const int m = n - at < 16384 ? n - at : 16384;
+    const int *d = stage_ids(r->c, ids + at, m, static_cast<const int32_t *>(words) + at, m);
+    if (!d) return -1;
+    pn_launch_rate_set_factors(r->c->stream, d, d + ((m + 3) & ~3), m, dst);
+  }
+  PN_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+extern "C" int pn_rate_set_stream_mix_gains(pn_rate *r, const int32_t *ids, int n, const float *gains) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (pn_mix_gains_set_check(r->c->B, ids, n, gains)) return -1;
+  if (n == 0) return 0;
+  std::vector<float> g(gains, gains + n);
+  bool all_one = true;
+  for (float &v : g) { if (v == 0.0f) v = 0.0f; all_one &= v == 1.0f; }     // (-0.0f is 0)
+  if (!r->d_level && all_one) return 0;                                        // (nothing has ever left the defaults, and nothing does)
+  PN_ON_DEVICE(r->c);
+  if (mix_buffers(r) || mix_set_words(r, ids, n, g.data(), reinterpret_cast<int *>(r->d_gains))) return -1;
+  for (int i = 0; i < n; i++) { r->gains_off += (g[i] != 1.0f) - (r->gains[ids[i]] != 1.0f); r->gains[ids[i]] = g[i]; }
+  return 0;
+}
+extern "C" int pn_rate_get_stream_mix_gains(const pn_rate *r, float *h_gains) {
+  if (!r || !h_gains) { pn_set_error("NULL argument"); return -1; }
+  for (int s = 0; s < r->c->B; s++) h_gains[s] = r->gains[s];
+  return 0;
+}
+extern "C" int pn_rate_set_conf_speakers(pn_rate *r, const int32_t *confs, int n, const int32_t *max_speakers) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (pn_mix_speakers_set_check(r->c->B, confs, n, max_speakers)) return -1;
+  if (n == 0) return 0;
+  bool all_zero = true;
+  for (int i = 0; i < n; i++) all_zero &= max_speakers[i] == 0;
+  if (!r->d_level && all_zero) return 0;
+  PN_ON_DEVICE(r->c);
+  if (mix_buffers(r) || mix_set_words(r, confs, n, max_speakers, r->d_caps)) return -1;
+  for (int i = 0; i < n; i++) { r->caps_on += (max_speakers[i] != 0) - (r->caps[confs[i]] != 0); r->caps[confs[i]] = max_speakers[i]; }
+  return 0;
+}
+extern "C" int pn_rate_get_conf_speakers(const pn_rate *r, int32_t *h_n) {
+  if (!r || !h_n) { pn_set_error("NULL argument"); return -1; }
+  for (int s = 0; s < r->c->B; s++) h_n[s] = r->caps[s];
+  return 0;
+}
+// the hold factor travels as an argument of every launch, so it is ordered like one; the levels go to zero in stream order
+extern "C" int pn_rate_set_mix_hold(pn_rate *r, float d) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (pn_mix_hold_check(d)) return -1;
+  if (d == 0.0f) d = 0.0f;
+  PN_ON_DEVICE(r->c);
+  if (d != 0.0f && mix_buffers(r)) return -1;
+  if (r->d_level) PN_HIP_CHECK(hipMemsetAsync(r->d_level, 0, (size_t)r->c->B * 4, r->c->stream));
+  r->hold = d;
+  return 0;
+}
+extern "C" float pn_rate_get_mix_hold(const pn_rate *r) { if (!r) { pn_set_error("NULL argument"); return NAN; } return r->hold; }
+extern "C" int pn_rate_set_mix_report(pn_rate *r, int enable) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (enable && !r->d_mix_report) {
+    PN_ON_DEVICE(r->c);
+    if (mix_buffers(r) || dev_alloc_into(r->allocs, r->bytes, r->c->stream, &r->d_mix_report, (size_t)r->c->B * PN_MIX_REPORT_WORDS * 4, true)) return -1;
+  }
+  r->mix_report = enable != 0;
+  return 0;
+}
+static int mix_report_copy(pn_rate *r, void *dst, hipMemcpyKind kind) {
+  if (!r || !dst) { pn_set_error("NULL argument"); return -1; }
+  if (!r->mix_report) { pn_set_error("the mix report is off (pn_rate_set_mix_report)"); return -1; }
+  PN_ON_DEVICE(r->c);
+  PN_HIP_CHECK(hipMemcpyAsync(dst, r->d_mix_report, (size_t)r->c->B * PN_MIX_REPORT_WORDS * 4, kind, r->c->stream));
+  if (kind == hipMemcpyDeviceToHost) PN_HIP_CHECK(hipStreamSynchronize(r->c->stream));
+  return 0;
+}
+extern "C" int pn_rate_read_mix_report(pn_rate *r, void *h_report) { return mix_report_copy(r, h_report, hipMemcpyDeviceToHost); }
+extern "C" int pn_rate_read_mix_report_dev(pn_rate *r, void *d_report) { return mix_report_copy(r, d_report, hipMemcpyDeviceToDevice); }
+
 extern "C" int pn_rate_reset(pn_rate *r) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   PN_ON_DEVICE(r->c);
   PN_HIP_CHECK(hipMemsetAsync(r->tail_up, 0, (size_t)r->c->B * PN_RATE_UP_TAIL * 4, r->c->stream));
   PN_HIP_CHECK(hipMemsetAsync(r->tail_down, 0, (size_t)r->c->B * r->td * 4, r->c->stream));
+  if (r->d_level) PN_HIP_CHECK(hipMemsetAsync(r->d_level, 0, (size_t)r->c->B * 4, r->c->stream));
   return 0;
 }
 
@@ -295,6 +409,7 @@ extern "C" int pn_rate_reset_streams(pn_rate *r, const int32_t *ids, int n) {
   if (!d) return -1;
   pn_launch_zero_rows(r->c->stream, r->tail_up, PN_RATE_UP_TAIL, PN_RATE_UP_TAIL, 1, 0, d, n);
   pn_launch_zero_rows(r->c->stream, r->tail_down, r->td, r->td, 1, 0, d, n);
+  pn_launch_zero_rows(r->c->stream, r->d_level, 1, 1, 1, 0, d, n);
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -339,7 +454,9 @@ static int rate_mix(pn_rate *r, const float *d_in48, float *d_out48, const RateR
     pn_launch_rate_conf_stamp(r->c->stream, rows.d_ids, rows.n, r->d_stamp, r->tick);
   }
   RateScope sc(r, RF_MIX);
-  pn_launch_rate_mix(r->c->stream, rows.n, rows.d_ids, r->d_conf, r->d_members, r->d_stamp, r->tick, d_in48, d_out48);
+  if (mix_plain(r)) pn_launch_rate_mix(r->c->stream, rows.n, rows.d_ids, r->d_conf, r->d_members, r->d_stamp, r->tick, d_in48, d_out48);
+  else pn_launch_rate_mix_sel(r->c->stream, rows.n, rows.d_ids, r->d_conf, r->d_members, r->d_stamp, r->tick, d_in48, d_out48, r->d_gains, r->d_caps,
+                              r->d_level, r->hold, r->mix_report ? r->d_mix_report : NULL);
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -392,7 +509,7 @@ static int rate_frame(pn_rate *r, const void *d_in, void *d_out, float *d_gr, in
   if (rate_up(r, d_in, fmt, r->x48, rows)) return -1;
   if (active ? pn_process_f32_active(c, r->x48, r->y48, d_gr, ids, n) : pn_process_f32(c, r->x48, r->y48, d_gr)) return -1;
   const float *o = r->y48;
-  if (r->in_conf > 0) {                              // somebody is in a conference: the mix writes every advancing stream's row of o48
+  if (r->in_conf > 0 || !mix_plain(r)) {             // somebody is in a conference (or a mix setting is on): the mix writes every advancing stream's row of o48
     if (rate_mix(r, r->y48, r->o48, rows)) return -1;
     o = r->o48;
   }

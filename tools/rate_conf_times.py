@@ -4,6 +4,8 @@
 
 A mixed converter with 8000 / 16000 / 24000 / 48000 by slot, int16 rows, and four tables: every stream without a conference, and
 every stream in a conference of 2, of 4 and of 32 (neighbouring slots, so the members of one conference run at all four rates).
+With a library that has loudest-N selection five more, which run the selecting kernel: conferences of 4, 8 and 32 that mix their
+N = 3 loudest talkers, conferences of 32 with send gains only (0.5 everywhere, N = 0) and with the mix report only.
 Per table:
   kernels   the converter's own profiling (pn_rate_set_profiling: HIP events around each launch on the context's stream; a figure is
             the MEAN of `launches` launches) of pn_rate_mix_f32 and pn_rate_down_i16 on their own — with no conference the mix is
@@ -12,8 +14,9 @@ Per table:
             same rows reaches here (measured with the same events, through torch), and the fraction of it the mix reaches
   frame     wall time of `launches` whole frames (pn_rate_process_i16) behind one synchronise, per frame
 The tables take turns round by round; one warm-up round is thrown away; the median of the rounds with the smallest and largest.
-With a library that has no conferences (PERCEPNET_LIB pointing at an older build) only the no-conference frame time is measured:
-that is how the parent's frame time in DESIGN 4.8 was taken, in the same process setup."""
+With a library that has no conferences (PERCEPNET_LIB pointing at an older build) only the no-conference frame time is measured,
+and with one that has no selection only the first four tables: that is how the parent's figures in DESIGN 4.8 were taken, in the
+same process setup."""
 import json
 import os
 import sys
@@ -43,10 +46,19 @@ def main():
     ctx = api.Context(model, B)
     rc = api.MixedRateConverter(ctx, np.array(api.MIXED_RATES, np.int32)[np.arange(B) % 4])
     has = hasattr(ctx.L, "pn_rate_set_stream_confs")
+    has_sel = hasattr(ctx.L, "pn_rate_set_conf_speakers")
+    conf_of = lambda k: (np.arange(B, dtype=np.int32) // k) * k                  # the conference's number: its lowest slot
     tables = {"none": np.full(B, NONE, np.int32)}
+    setting = {}                                                                 # table -> (N of every conference, gain of every stream, report)
     if has:
         for k in (2, 4, 32):
-            tables[f"of {k}"] = (np.arange(B, dtype=np.int32) // k) * k          # the conference's number: its lowest slot
+            tables[f"of {k}"] = conf_of(k)
+    if has_sel:
+        for k in (4, 8, 32):
+            tables[f"of {k} N=3"] = conf_of(k)
+            setting[f"of {k} N=3"] = (3, 1.0, False)
+        tables["of 32 gains"], setting["of 32 gains"] = conf_of(32), (0, 0.5, False)
+        tables["of 32 report"], setting["of 32 report"] = conf_of(32), (0, 1.0, True)
     g = torch.Generator(device=DEV).manual_seed(1)
     y48 = torch.rand((B, 480), device=DEV, generator=g) * 2 - 1
     o48 = torch.empty_like(y48)
@@ -66,7 +78,7 @@ def main():
             copy_ms.append(a.elapsed_time(b) / N)
     bound_ms = float(np.median(copy_ms))
     moved = 2 * 1920 * B
-    result = {"streams": B, "launches_per_round": N, "rounds": ROUNDS, "library_has_conferences": has,
+    result = {"streams": B, "launches_per_round": N, "rounds": ROUNDS, "library_has_conferences": has, "library_has_selection": has_sel,
               "copy": dict(stat(copy_ms), bytes=moved, gb_per_s=moved / bound_ms / 1e6)}
     print(f"{B} streams, mean of {N} launches, median (min-max) of {ROUNDS} rounds, ms")
     print(f"  device-to-device copy of the rows: {bound_ms:.4f} ms = {moved / bound_ms / 1e6:.0f} GB/s for {moved} bytes")
@@ -76,6 +88,11 @@ def main():
         for name, table in tables.items():
             if has:
                 rc.set_stream_confs(all_ids, table)
+                if has_sel:
+                    n_max, gain, report = setting.get(name, (0, 1.0, False))
+                    rc.set_conf_speakers(all_ids, np.full(B, n_max, np.int32))
+                    rc.set_stream_mix_gains(all_ids, np.full(B, gain, np.float32))
+                    rc.set_mix_report(report)
                 rc.set_profiling(True)
                 rc.reset_profile()
                 for _ in range(N):
@@ -95,7 +112,7 @@ def main():
                 means[name]["frame"].append((time.perf_counter() - t0) * 1e3 / N)
     for name in tables:
         res = {k: stat(v) for k, v in means[name].items() if v}
-        line = f"  {name:8s} frame {res['frame']['median_ms']:.3f} ({res['frame']['min_ms']:.3f}-{res['frame']['max_ms']:.3f})"
+        line = f"  {name:12s} frame {res['frame']['median_ms']:.3f} ({res['frame']['min_ms']:.3f}-{res['frame']['max_ms']:.3f})"
         if has:
             res["fraction_of_bound"] = bound_ms / res["rate_mix"]["median_ms"]
             line += (f"   rate_mix {res['rate_mix']['median_ms']:.4f} ({res['rate_mix']['min_ms']:.4f}-{res['rate_mix']['max_ms']:.4f})"
