@@ -12,7 +12,7 @@
  *  (2) The batched interface the GPU needs: one context = B independent 48 kHz streams advanced
  *      in lock-step, one 10 ms frame (480 samples) per stream per call.  Plain pointers and
  *      sizes only; device pointers are raw HIP device addresses (e.g. torch's data_ptr()).
- *      8, 16 and 24 kHz streams go through a pn_rate beside the context (the rate converter, below), all at one rate or, with
+ *      8, 16, 24 and 32 kHz streams go through a pn_rate beside the context (the rate converter, below), all at one rate or, with
  *      a mixed converter, each stream at its own, 48 kHz included.
  *
  * All functions are thread-compatible per context; one context belongs to one HIP device.
@@ -399,34 +399,45 @@ int pn_featgen_run_files(int device, int n_jobs, const char *const *speech_paths
                          const int *counts, const char *const *out_paths, const char *const *test_out_paths,
                          const char *const *test_in_paths);
 
-/* ---- batched rate converter: 8, 16 and 24 kHz streams through a 48 kHz context ------------------------------------------- */
+/* ---- batched rate converter: 8, 16, 24 and 32 kHz streams through a 48 kHz context --------------------------------------- */
 /* The engine runs at 48 kHz; a pn_rate is an object BESIDE a context (like pn_featgen: it adds nothing to the context's state)
    that converts all of the context's streams from ONE low rate up to 48 kHz in front of a frame and back down behind it, on the
-   GPU (csrc/pn_rate.hip).  rate_hz is 8000, 16000 or 24000 — L = 48000 / rate_hz = 6, 3, 2; any other rate is refused.  A caller
+   GPU (csrc/pn_rate.hip).  rate_hz is 8000, 16000 or 24000 — L = 48000 / rate_hz = 6, 3, 2 — or 32000, the rational rate
+   48000 * M / L with (L, M) = (3, 2) ("32000 Hz", below); any other rate is refused.  A caller
    with mixed rates uses a MIXED converter (pn_rate_create_mixed, below: a rate per stream, 48000 included, in one context), or
-   one context and converter per rate.  A frame is still 10 ms: n = 480 / L = 80 | 160 | 240 samples per stream.
+   one context and converter per rate.  A frame is still 10 ms: n = 480 M / L = 80 | 160 | 240 | 320 samples per stream.
 
-   Arithmetic (fixed, so that a float32 model reproduces it bit for bit: tests/rate_model.py).  T = PN_RATE_TAPS = 16, D = T * L.
+   Arithmetic (fixed, so that a float32 model reproduces it bit for bit: tests/rate_model.py, and tests/rate32_model.py for
+   32000).  T = PN_RATE_TAPS = 16, D = T * L.  For the integer factors (M = 1):
    Prototype filter, k = -D..D:  h[k] = sinc(k / L) * I0(8 * sqrt(1 - (k / D)^2)) / I0(8)  (a Kaiser-windowed sinc, beta = 8),
    computed in double for k >= 0, mirrored, h[0] = 1 and h[jL] = 0 (j != 0) exactly, rounded to fp32 once; the down-converter's taps
    are g[k] = (float)(h_double[k] / L).
      up    y[Lq + p] = sum_m x[m] * h[L(q - T - m) + p]:  phase p = 0 is the copy y[Lq] = x[q - T] (the input's bits), phases
            1..L-1 sum over the 32 samples x[q - 2T + 1 .. q].  Per-stream state: the last 32 low-rate input samples.
      down  z[m] = sum_{i = Lm - 2D + 1}^{Lm - 1} g[Lm - D - i] * o[i].  Per-stream state: the last 2D 48 kHz samples (192 | 96 | 64).
+   32000 Hz: up by L = 3 with every M = 2nd output kept, and down from 48 kHz samples that sit M apart on the L-times grid.  The
+   prototype h is the L = 3 table (16000's), bit for bit; the down taps are g[k] = (float)(h_double[k] * 2 / 3).
+     up    output j of a frame: q = (2j) div 3, p = (2j) mod 3 (480 * 2 / 3 is whole, so the pattern restarts with every frame and
+           no phase is carried).  p = 0 is the copy y[j] = x[q - T]; p = 1, 2: y[j] = sum_{i = 0..31} h[3(15 - i) + p] * x[q - 31 + i]
+           — the 16 kHz interpolation of the same samples with every second output kept.  State: the last 32 input samples.
+     down  z[m] = sum_i g[3m - 48 - 2i] * o[i] over every i with (3m - 96) / 2 < i < 3m / 2, ascending: 47 terms for even m, 48 for
+           odd m, taps that are exactly 0 included.  State: the last 2D / M = 48 samples at 48 kHz (the oldest is never read).
    Every sum runs oldest sample first from acc = 0.0f as acc = acc + c * x, product and sum separately rounded (no FMA), so a
    stream's output does not depend on the batch size, its slot or the block it ran in.
-   Delay from an input sample to the same sample in the output, in low-rate samples: 2880 / L + 2T
+   Delay from an input sample to the same sample in the output, in low-rate samples: 2880 M / L + 2T
 
-       rate_hz    L    n     delay (samples)   delay (ms)   state record (bytes)
-        8000      6    80        512              64           912
-       16000      3   160        992              62           528
-       24000      2   240       1472              61.33        400
+       rate_hz   (L, M)   n     delay (samples)   delay (ms)   state record (bytes)
+        8000     (6, 1)   80        512              64           912
+       16000     (3, 1)  160        992              62           528
+       24000     (2, 1)  240       1472              61.33        400
+       32000     (3, 2)  320       1952              61           336
 
    The engine runs in float between the two conversions; int16 exists only at the edges: input (float)v / 32768, output
    trunc(z * 32768) wrapped to 16 bit, or saturated while pn_ctx_set_output_saturate is on.  The frame report (pn_ctx_set_report)
    stays that of the 48 kHz signal inside the engine: 480 samples per frame, the engine's own 2880-sample delay, levels before the
    down-conversion.  8-bit G.711 rows are the int16 edge with the companding outside it ("G.711 streams", below).
-   NOT provided: other rates.
+   The model was trained on full-band speech; its quality on 32 kHz input (as on the other low rates) is not measured here.
+   NOT provided: other rates.  44100, 12000, 96000 and every rate not named above are refused.
 
    Host only, needing no GPU:
    pn_rate_frame_samples: n, -1 for a refused rate.  pn_rate_delay_samples: the table above, -1.  pn_rate_taps: the fp32 table,
@@ -434,8 +445,8 @@ int pn_featgen_run_files(int device, int n_jobs, const char *const *speech_paths
    cap < 2D + 1.  pn_rate_state_bytes: the record size, 0 for a refused rate.  pn_rate_state_check: is `bytes` bytes at `record`
    one state record of a converter of rate_hz?  PN_SS_OK or a PN_SS_BAD_* code (pn_last_error says why).
    State record (little-endian): 16-byte header — uint32 magic PN_RATE_STATE_MAGIC | uint32 version PN_RATE_STATE_VERSION |
-   uint32 record bytes | int32 rate_hz — then the 32 fp32 words of the up-converter's tail and the 2D words of the
-   down-converter's, each oldest sample first. */
+   uint32 record bytes | int32 rate_hz — then the 32 fp32 words of the up-converter's tail and the 2D / M words (192 | 96 | 64 |
+   48) of the down-converter's, each oldest sample first. */
 #define PN_RATE_TAPS 16
 #define PN_RATE_STATE_MAGIC 0x53524e50u        /* "PNRS" */
 #define PN_RATE_STATE_VERSION 1
@@ -527,32 +538,33 @@ int pn_rate_set_profiling(pn_rate *r, int enable);
 int pn_rate_kernel_time(pn_rate *r, const char *name, double *total_ms, int64_t *launches);
 int pn_rate_reset_profile(pn_rate *r);
 
-/* ---- mixed rates: 8, 16, 24 and 48 kHz streams in ONE context ---------------------------------------------------------------- */
+/* ---- mixed rates: 8, 16, 24 and 48 kHz streams, and 32 kHz ones, in ONE context --------------------------------------------- */
 /* A mixed converter IS a pn_rate — every entry point above takes it — whose streams each have a rate of their own out of 8000,
-   16000, 24000 and 48000 (L = 6, 3, 2, 1), so that any free slot of a context takes the next call whatever its rate.  The rate
+   16000, 24000, 32000 and 48000 (L = 6, 3, 2, the rational (3, 2), and 1), so that any free slot of a context takes the next call whatever its rate.  The rate
    per stream lives in the converter; pn_ctx, its state and its records know nothing of it.  It differs from a single-rate
    converter in two things only:
    Rows.  Low-rate rows are [n_streams][PN_RATE_MIXED_ROW = 480] samples (1920 bytes in float, 960 in int16) whatever the rates,
    because a slot's rate may change at any time; stream s at rate R uses the first n_s = pn_rate_mixed_frame_samples(R) samples
    of its row.  The rest of an input row is ignored, the rest of an output row is left untouched (also by the _host forms).  Base
    pointers stay 16-byte aligned.
-   A factor per stream.  For L = 6, 3, 2 the arithmetic is exactly the one above for that rate — same taps, same order, same tails
+   A factor per stream.  For 8000, 16000, 24000 and 32000 the arithmetic is exactly the one above for that rate — same taps, same order, same tails
    — so a stream gives bit for bit what it gives in a single-rate converter of its rate.  L = 1 is a copy: float rows carry the
    input's bits up and down; int16 is (float)v / 32768 on the way up and t = o * 32768 through the wrapping or saturating cast
    (pn_ctx_set_output_saturate) on the way down.  A 48000 stream has no tails and no record; its delay is the engine's 2880 samples.
 
-       rate_hz    L    n_s   delay (samples)
-        8000      6    80        512
-       16000      3   160        992
-       24000      2   240       1472
-       48000      1   480       2880
+       rate_hz   (L, M)   n_s   delay (samples)
+        8000     (6, 1)   80        512
+       16000     (3, 1)  160        992
+       24000     (2, 1)  240       1472
+       32000     (3, 2)  320       1952
+       48000     (1, 1)  480       2880
 
    Host only, needing no GPU: pn_rate_mixed_frame_samples and pn_rate_mixed_delay_samples, the table above, -1 for another rate
    (pn_rate_frame_samples(48000) and the rest of the single-rate surface keep refusing 48000); pn_rate_mixed_rates_check: 0 when
-   rates_hz[0..n) are all out of the four, else -1 with pn_last_error naming the first bad index.
+   rates_hz[0..n) are all out of the five, else -1 with pn_last_error naming the first bad index.
    pn_rate_create_mixed: rates_hz [n_streams] (NULL: all 48000); a bad rate returns NULL.  pn_rate_is_mixed: 1 | 0.
    pn_rate_row_samples: samples between two rows at the low rate — n for a single-rate converter, 480 for a mixed one.
-   pn_rate_set_stream_rates: streams ids[i] (distinct, in range) continue at rates_hz[i] (out of the four); anything else refuses
+   pn_rate_set_stream_rates: streams ids[i] (distinct, in range) continue at rates_hz[i] (out of the five); anything else refuses
    the call with -1, nothing changed or launched; n == 0 is a no-op; refused on a single-rate converter.  Asynchronous on the
    context's stream and ordered exactly like pn_rate_reset_streams: frames submitted before it run at the old rates, frames after
    it at the new ones; the caller may reuse its arrays on return.  It ZEROES both tails of the listed streams — a rate change is a

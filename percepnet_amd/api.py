@@ -21,6 +21,8 @@ SS_BAD_RATE = -6          # pn_rate_state_check: a record of another rate
 # batched rate converter (include/percepnet_hip.h pn_rate): the rates it takes, taps per phase
 RATES = (8000, 16000, 24000)
 MIXED_RATES = (8000, 16000, 24000, 48000)     # the rate of a STREAM of a mixed converter (pn_rate_create_mixed); 48000 is a copy
+RATES_ALL = RATES + (32000,)                  # every rate a converter takes: 32000 is the rational 3:2 row (n = 320), the others 48000 / L
+MIXED_RATES_ALL = (8000, 16000, 24000, 32000, 48000)
 RATE_MIXED_ROW = 480                          # PN_RATE_MIXED_ROW: samples between two low-rate rows of a mixed converter
 RATE_TAPS = 16
 G711_ULAW, G711_ALAW = 0, 1                   # PN_G711_*: the law of a stream's 8-bit rows (pn_rate_set_stream_laws)
@@ -516,29 +518,28 @@ def stream_state_check(record, model):
 
 
 def rate_frame_samples(rate_hz):
-    """Samples per 10 ms frame at rate_hz: 80 | 160 | 240; -1 for a rate no converter takes (pn_rate_frame_samples, host only)."""
+    """Samples per 10 ms frame at rate_hz: 80 | 160 | 240 | 320; -1 for a rate no converter takes (pn_rate_frame_samples, host only)."""
     return int(load_library().pn_rate_frame_samples(int(rate_hz)))
 
 
 def rate_delay_samples(rate_hz):
-    """Input-to-output delay of a converted stream in samples at rate_hz: 512 | 992 | 1472; -1 for a refused rate (host only)."""
+    """Input-to-output delay of a converted stream in samples at rate_hz: 512 | 992 | 1472 | 1952; -1 for a refused rate (host only)."""
     return int(load_library().pn_rate_delay_samples(int(rate_hz)))
 
 
 def rate_taps(rate_hz, down=False):
-    """The converter's fp32 taps for k = -D..D, D = 16 * 48000 / rate_hz: h (up) or g = h / L (down) (pn_rate_taps, host only)."""
+    """The converter's fp32 taps for k = -D..D, D = 16 L for a rate of 48000 M / L: h (up) or g = h M / L (down); 32000 is
+    (L, M) = (3, 2) and its h the table of 16000 (pn_rate_taps, host only)."""
     L = load_library()
-    n = rate_frame_samples(rate_hz)
+    t = np.empty(2 * RATE_TAPS * 6 + 1, np.float32)    # PN_RATE_MAX_TAPS: room for the longest table; the library says how many it wrote
+    n = int(L.pn_rate_taps(int(rate_hz), int(bool(down)), t.ctypes.data, int(t.size)))
     if n < 0:
         raise PercepNetError(_err(L))
-    t = np.empty(2 * RATE_TAPS * (FRAME // n) + 1, np.float32)
-    if L.pn_rate_taps(int(rate_hz), int(bool(down)), t.ctypes.data, int(t.size)) != t.size:
-        raise PercepNetError(_err(L))
-    return t
+    return t[:n].copy()
 
 
 def rate_state_bytes(rate_hz):
-    """Bytes of one converter state record at rate_hz: 912 | 528 | 400; 0 for a refused rate (host only)."""
+    """Bytes of one converter state record at rate_hz: 912 | 528 | 400 | 336; 0 for a refused rate (host only)."""
     return int(load_library().pn_rate_state_bytes(int(rate_hz)))
 
 
@@ -556,12 +557,12 @@ def rate_state_check(record, rate_hz):
 
 
 def rate_mixed_frame_samples(rate_hz):
-    """Samples per 10 ms frame of a stream of a mixed converter: 80 | 160 | 240 | 480; -1 for any other rate (host only)."""
+    """Samples per 10 ms frame of a stream of a mixed converter: 80 | 160 | 240 | 320 | 480; -1 for any other rate (host only)."""
     return int(load_library().pn_rate_mixed_frame_samples(int(rate_hz)))
 
 
 def rate_mixed_delay_samples(rate_hz):
-    """Input-to-output delay in samples at rate_hz of a stream of a mixed converter: 512 | 992 | 1472 | 2880; -1 (host only)."""
+    """Input-to-output delay in samples at rate_hz of a stream of a mixed converter: 512 | 992 | 1472 | 1952 | 2880; -1 (host only)."""
     return int(load_library().pn_rate_mixed_delay_samples(int(rate_hz)))
 
 
@@ -624,7 +625,7 @@ def mix_select(levels, n_max):
 
 
 class RateConverter:
-    """8, 16 or 24 kHz streams through a 48 kHz Context (pn_rate): a converter beside `ctx` for all of its streams at ONE rate.
+    """8, 16, 24 or 32 kHz streams through a 48 kHz Context (pn_rate): a converter beside `ctx` for all of its streams at ONE rate.
     It borrows the context (device, n_streams, HIP stream): close the converter before the context."""
 
     def __init__(self, ctx, rate_hz):
@@ -918,7 +919,7 @@ class RateConverter:
 
 
 class MixedRateConverter(RateConverter):
-    """8, 16, 24 and 48 kHz streams in ONE Context (pn_rate_create_mixed): a RateConverter with a rate per stream.  Every method
+    """8, 16, 24, 32 and 48 kHz streams in ONE Context (pn_rate_create_mixed): a RateConverter with a rate per stream.  Every method
     of RateConverter works on rows of RATE_MIXED_ROW = 480 samples, of which stream s uses the first rate_mixed_frame_samples(its
     rate); the rest of an input row is ignored and the rest of an output row is left as it was (the host entry points return it
     as zeros).  rates: one per stream, or None for all 48000."""
@@ -1011,7 +1012,7 @@ class MixedRateConverter(RateConverter):
     def export_streams(self, ids):
         """-> uint8 [n, rate_state_bytes(R)]: the converter state of the streams `ids`, which share the rate R != 48000."""
         a, n, rate = self._record_rate(ids)
-        rec = np.empty((n, rate_state_bytes(rate) if rate in RATES else 16), np.uint8)
+        rec = np.empty((n, rate_state_bytes(rate) if rate in RATES_ALL else 16), np.uint8)
         self._chk(self.L.pn_rate_export_streams_host(self.h, a.ctypes.data, n, rec.ctypes.data))
         return rec
 
@@ -1019,7 +1020,7 @@ class MixedRateConverter(RateConverter):
         """Records of rate R into the distinct streams `ids`, all of which run at R now (set_stream_rates first); all or nothing."""
         a, n, rate = self._record_rate(ids)
         rec = np.ascontiguousarray(records, dtype=np.uint8)
-        want = rate_state_bytes(rate) if rate in RATES else 0
+        want = rate_state_bytes(rate) if rate in RATES_ALL else 0
         if n and want and rec.size != n * want:
             raise PercepNetError(f"{rec.size} record bytes for {n} streams (a record at {rate} Hz has {want})")
         if n and not want:                     # (a 48000 slot or a bad id: the library words the refusal; it reads no record)

@@ -5,10 +5,10 @@
 // dropped, main.cpp:32-33); with a single pair ./feature_test.raw gets 68 floats per frame.
 //
 //   percepnet_run [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N]
-//                 [--rate 8000|16000|24000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
+//                 [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
 //                 in0.pcm out0.pcm [in1.pcm out1.pcm ...]
 //
-// --rate R: the files are raw int16 at R Hz instead of 48 kHz, in frames of n = 480 * R / 48000 samples (80 | 160 | 240): a rate
+// --rate R: the files are raw int16 at R Hz instead of 48 kHz, in frames of n = 480 * R / 48000 samples (80 | 160 | 240 | 320): a rate
 // converter beside each context (pn_rate) takes every frame up to 48 kHz in front of the engine and back down behind it.  The
 // per-stream contract is unchanged: (frames-1)*n samples out, first output frame and partial tail dropped.  The frames go through
 // the converter's pipelined path (pn_rate_submit_host_i16: the context's pipeline with the converter's frame in the middle) with
@@ -16,7 +16,7 @@
 // pn_host_next_report — its figures stay those of the 48 kHz signal inside the engine — and the converter's slots are reset
 // with the context's.  Without --rate nothing of this runs.
 //
-// --rates R0,R1,..: one rate per pair out of 8000, 16000, 24000 and 48000 (exclusive with --rate): a MIXED converter beside each
+// --rates R0,R1,..: one rate per pair out of 8000, 16000, 24000, 32000 and 48000 (exclusive with --rate): a MIXED converter beside each
 // context (pn_rate_create_mixed), whose shard's slice of the list goes to its device.  Pair i is read and written in frames of
 // its own n = 480 * Ri / 48000 samples; the pinned rows are 480 samples whatever the rate (only a pair's own n samples of an
 // output row are written to its file: the rest of the row is unspecified on the pipelined path); the per-pair contract is the one
@@ -267,6 +267,12 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
   for (int s = 0; s < B; s++) fout[s] = NULL;        // every output file was closed with its last frame
 }
 
+// the usage text, for a command line without pairs and for a rate no converter takes.  Returns the exit status, 1.
+static int usage(const char *argv0) {
+  fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N] [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv0);
+  return 1;
+}
+
 int main(int argc, char **argv) {
   const char *model_path = getenv("PERCEPNET_MODEL");
   int nn_mode = PN_NN_MFMA, postfilter = 0, ai = 1, n_slots = 0;
@@ -286,14 +292,14 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[ai], "--report")) g_report = true;         // one line of levels and clipping per pair (pn_ctx_set_report)
     else if (!strcmp(argv[ai], "--rate") && ai + 1 < argc) {        // the files' sample rate: a rate converter beside each context (pn_rate)
       g_rate = atoi(argv[++ai]);
-      if (pn_rate_frame_samples(g_rate) < 0) { fprintf(stderr, "--rate: expected 8000, 16000 or 24000, got '%s'\n", argv[ai]); return 1; }
+      if (pn_rate_frame_samples(g_rate) < 0) { fprintf(stderr, "--rate: expected 8000, 16000, 24000 or 32000, got '%s'\n", argv[ai]); return usage(argv[0]); }
     }
     else if (!strcmp(argv[ai], "--rates") && ai + 1 < argc) {       // one rate per pair, 48000 allowed: a mixed converter beside each context
       const char *v = argv[++ai];
       for (const char *q = v; ; ) {
         char *end = NULL;
         const long r = strtol(q, &end, 10);
-        if (end == q || (*end && *end != ',') || pn_rate_mixed_frame_samples((int)r) < 0) { fprintf(stderr, "--rates: expected a comma-separated list of 8000, 16000, 24000 or 48000, got '%s'\n", v); return 1; }
+        if (end == q || (*end && *end != ',') || pn_rate_mixed_frame_samples((int)r) < 0) { fprintf(stderr, "--rates: expected a comma-separated list of 8000, 16000, 24000, 32000 or 48000, got '%s'\n", v); return usage(argv[0]); }
         g_rates.push_back((int32_t)r);
         if (!*end) break;
         q = end + 1;
@@ -351,8 +357,7 @@ int main(int argc, char **argv) {
   const int nfiles = argc - ai;
   if (nfiles < 2 || (nfiles & 1) || (g_g711 >= 0 && !g_rate && g_rates.empty())) {
     if (g_g711 >= 0 && !g_rate && g_rates.empty()) fprintf(stderr, "--g711 needs --rate or --rates: G.711 rows go through a rate converter\n");
-    fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N] [--rate 8000|16000|24000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv[0]);
-    return 1;
+    return usage(argv[0]);
   }
   const int B = nfiles / 2;
   if (g_rate && !g_rates.empty()) { fprintf(stderr, "--rate and --rates exclude each other\n"); return 1; }

@@ -75,20 +75,21 @@ void pn_launch_backend(hipStream_t st, const PnTables *T, int n_streams, const f
 // hist_slot of the side's history ring.  One wavefront per stream, no grid cap.
 void pn_launch_outstage(hipStream_t st, int n_streams, const float *o, const PnDspSide &s, int hist_slot, const float *gr,
                         int16_t *pcm, int saturate, void *report);
-// the rate converter (pn_rate.hip; factor = 48000 / rate = 6 | 3 | 2, arithmetic in pn_rate_design.h): one wavefront per row, rows d_ids[0..n_rows) or,
-// with d_ids == NULL, streams 0..n_rows.  up: in [.][480 / factor] samples of format fmt -> out48 [.][480], tail [.][32]; down: in48 [.][480] ->
-// out [.][480 / factor] samples of format fmt (int16 and G.711: the wrapping or saturating cast), tail [.][2 * 16 * factor]; taps: the
-// 2 * 16 * factor + 1 fp32 taps on the device.  fmt: the sample format of the low-rate rows — float, int16, or 8-bit G.711 with the law of
+// the rate converter (pn_rate.hip; factor: a rate's code of pn_rate_design.h, L = 48000 / rate = 6 | 3 | 2, or PN_RATE_F_3_2 for 32000, whose sizes
+// pn_rate_factor_frame, pn_rate_down_tail and pn_rate_factor_L give): one wavefront per row, rows d_ids[0..n_rows) or,
+// with d_ids == NULL, streams 0..n_rows.  up: in [.][pn_rate_factor_frame(factor)] samples of format fmt -> out48 [.][480], tail [.][32]; down: in48 [.][480] ->
+// out [.][pn_rate_factor_frame(factor)] samples of format fmt (int16 and G.711: the wrapping or saturating cast), tail [.][pn_rate_down_tail(factor)]; taps: the
+// 2 * 16 * pn_rate_factor_L(factor) + 1 fp32 taps on the device.  fmt: the sample format of the low-rate rows — float, int16, or 8-bit G.711 with the law of
 // stream s in d_laws[s] (pn_g711.h; d_laws may be NULL for the other two).  -1 (pn_set_error) without launching for another L or format.
 // records: state record i <-> the tails of stream d_ids[i]
 enum { PN_FMT_F32 = 0, PN_FMT_I16 = 1, PN_FMT_G711 = 2 };
 static inline size_t pn_fmt_bytes(int fmt) { return fmt == PN_FMT_G711 ? 1 : fmt == PN_FMT_I16 ? 2 : 4; }
 int pn_launch_rate_up(hipStream_t st, int factor, int fmt, int n_rows, const int *d_ids, const int *d_laws, const void *in, float *out48, float *tail, const float *taps);
 int pn_launch_rate_down(hipStream_t st, int factor, int fmt, int n_rows, const int *d_ids, const int *d_laws, const float *in48, void *out, int saturate, float *tail, const float *taps);
-// td_stride: words between the down tails of two streams (2 * 16 * factor in a single-rate converter, 192 in a mixed one)
+// td_stride: words between the down tails of two streams (pn_rate_down_tail(factor) in a single-rate converter, 192 in a mixed one)
 void pn_launch_rate_records(hipStream_t st, int factor, int rate_hz, const int *d_ids, int n, float *tail_up, float *tail_down, int td_stride, void *rec, int scatter);
-// the mixed converter's kernels: rows of PN_RATE_MIXED_ROW = 480 samples at the low rate too, stream s runs at d_factors[s] in {6, 3, 2, 1}
-// (1: a copy, no tail); tail rows [.][32] and [.][192]; taps: the tables of factor 6, 3, 2 one behind the other (193 + 97 + 65 words).
+// the mixed converter's kernels: rows of PN_RATE_MIXED_ROW = 480 samples at the low rate too, stream s runs at d_factors[s] in {6, 3, 2, 1, PN_RATE_F_3_2}
+// (1: a copy, no tail); tail rows [.][32] and [.][192]; taps: the tables of factor 6, 3, 2 one behind the other (193 + 97 + 65 words), going down the 97 of 32000 behind them.
 // set_factors: d_factors[d_ids[i]] = d_vals[i] for i < n (distinct ids); the law table is written by the same launch
 int pn_launch_rate_up_mixed(hipStream_t st, int fmt, int n_rows, const int *d_ids, const int *d_factors, const int *d_laws, const void *in, float *out48, float *tail, const float *taps);
 int pn_launch_rate_down_mixed(hipStream_t st, int fmt, int n_rows, const int *d_ids, const int *d_factors, const int *d_laws, const float *in48, void *out, int saturate, float *tail, const float *taps);

@@ -6,7 +6,7 @@
 // to the context's stream, so a converter call is ordered against the context's calls like they are against each other.
 #include "pn_context.h"      // the context it borrows, the launchers, dev_alloc_into, stage_ids, the id rule, host_records_sync
 #include "pn_rate_design.h"
-#include "pn_rate_mixed.h"   // the mixed converter's host rules: the four rates, a rate change, one rate per record call
+#include "pn_rate_mixed.h"   // the mixed converter's host rules: the five rates, a rate change, one rate per record call
 #include "pn_g711.h"         // the 8-bit sample format: the companding and what a list of laws must be
 #include "pn_conf.h"         // conferences: what an id must be, the table after a change, the members in ascending order
 #include "pn_mix_rules.h"    // loudest-N, send gains, hold: what the settings must be; the level and the selection for the host
@@ -15,9 +15,9 @@
 
 struct pn_rate {
   pn_ctx *c;                    // borrowed: device, B, stream, the id ring, the saturate setting
-  int rate, L, n, td;           // rate_hz, 48000 / rate, samples per row, words per down tail row (2D).  Mixed: 0, 0, 480, 192
+  int rate, f, n, td;           // rate_hz, its factor (pn_rate_design.h: L, or PN_RATE_F_3_2 for 32000), samples per row, words per down tail row (2D / M).  Mixed: 0, 0, 480, 192
   size_t bytes;
-  float *taps_up, *taps_down;   // [2D + 1] h, g.  Mixed: the tables of L = 6, 3, 2 one behind the other
+  float *taps_up, *taps_down;   // [2D + 1] h, g.  Mixed: the tables of L = 6, 3, 2 one behind the other, and behind them the g of 32000
   float *tail_up, *tail_down;   // [B][32], [B][td]: the state
   float *x48, *y48;             // [B][480]: the engine's input and output rows of a whole frame
   void *io_in, *io_out;         // [B][n] 4-byte words: staging rows of the host-buffer paths (slot 0 of the pipelined one)
@@ -87,24 +87,24 @@ static int rate_flush_events(pn_rate *r) {
 
 // ---- host only ---------------------------------------------------------------------------------------------------------------
 extern "C" int pn_rate_frame_samples(int rate_hz) {
-  const int L = pn_rate_factor(rate_hz);
-  if (!L) { pn_set_error("rate %d Hz: a converter takes 8000, 16000 or 24000", rate_hz); return -1; }
-  return PN_FRAME / L;
+  const int f = pn_rate_factor(rate_hz);
+  if (!f) { pn_set_error("rate %d Hz: a converter takes " PN_RATE_TEXT, rate_hz); return -1; }
+  return pn_rate_factor_frame(f);
 }
 extern "C" int pn_rate_delay_samples(int rate_hz) {
-  const int L = pn_rate_factor(rate_hz);
-  if (!L) { pn_set_error("rate %d Hz: a converter takes 8000, 16000 or 24000", rate_hz); return -1; }
-  return 6 * PN_FRAME / L + 2 * PN_RATE_TAPS;          // the engine's 2880 samples at the low rate, T up and T down
+  const int f = pn_rate_factor(rate_hz);
+  if (!f) { pn_set_error("rate %d Hz: a converter takes " PN_RATE_TEXT, rate_hz); return -1; }
+  return pn_rate_factor_delay(f);                      // the engine's 2880 samples at the low rate, T up and T down
 }
 extern "C" int pn_rate_taps(int rate_hz, int down, float *taps, int cap) {
-  const int L = pn_rate_factor(rate_hz);
-  if (!L) { pn_set_error("rate %d Hz: a converter takes 8000, 16000 or 24000", rate_hz); return -1; }
-  return pn_rate_design(L, down, taps, cap);
+  const int f = pn_rate_factor(rate_hz);
+  if (!f) { pn_set_error("rate %d Hz: a converter takes " PN_RATE_TEXT, rate_hz); return -1; }
+  return pn_rate_design(f, down, taps, cap);
 }
 extern "C" size_t pn_rate_state_bytes(int rate_hz) {
-  const int L = pn_rate_factor(rate_hz);
-  if (!L) { pn_set_error("rate %d Hz: a converter takes 8000, 16000 or 24000", rate_hz); return 0; }
-  return 4 * pn_rate_record_words(L);
+  const int f = pn_rate_factor(rate_hz);
+  if (!f) { pn_set_error("rate %d Hz: a converter takes " PN_RATE_TEXT, rate_hz); return 0; }
+  return 4 * pn_rate_record_words(f);
 }
 extern "C" int pn_rate_state_check(const void *record, size_t bytes, int rate_hz) { return pn_rate_record_check(record, bytes, rate_hz); }
 extern "C" int pn_rate_mixed_frame_samples(int rate_hz) { return pn_rate_mixed_frame(rate_hz); }
@@ -133,18 +133,18 @@ extern "C" void pn_rate_destroy(pn_rate *r) {
 
 extern "C" pn_rate *pn_rate_create(pn_ctx *c, int rate_hz) {
   if (!c) { pn_set_error("NULL argument"); return NULL; }
-  const int L = pn_rate_factor(rate_hz);
-  if (!L) { pn_set_error("rate %d Hz: a converter takes 8000, 16000 or 24000", rate_hz); return NULL; }
+  const int f = pn_rate_factor(rate_hz);
+  if (!f) { pn_set_error("rate %d Hz: a converter takes " PN_RATE_TEXT, rate_hz); return NULL; }
   DeviceGuard _dg(c->device);
   if (!_dg.ok) { pn_set_error("hipSetDevice(%d) failed", c->device); return NULL; }
   pn_rate *r = new pn_rate();
-  r->c = c; r->rate = rate_hz; r->L = L; r->n = PN_FRAME / L; r->td = pn_rate_down_tail(L); r->bytes = 0;
+  r->c = c; r->rate = rate_hz; r->f = f; r->n = pn_rate_factor_frame(f); r->td = pn_rate_down_tail(f); r->bytes = 0;
   r->mixed = false; r->factors = NULL; r->h_rows = NULL; r->laws.assign((size_t)c->B, PN_G711_ULAW); r->confs.assign((size_t)c->B, PN_CONF_NONE);
   r->gains.assign((size_t)c->B, 1.0f); r->caps.assign((size_t)c->B, 0);
-  const size_t B = (size_t)c->B, nt = (size_t)r->td + 1;
+  const size_t B = (size_t)c->B, nt = 2 * (size_t)PN_RATE_TAPS * pn_rate_factor_L(f) + 1;
   float h[2][PN_RATE_MAX_TAPS];
   auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
-  if (pn_rate_design(L, 0, h[0], PN_RATE_MAX_TAPS) < 0 || pn_rate_design(L, 1, h[1], PN_RATE_MAX_TAPS) < 0) goto fail;
+  if (pn_rate_design(f, 0, h[0], PN_RATE_MAX_TAPS) < 0 || pn_rate_design(f, 1, h[1], PN_RATE_MAX_TAPS) < 0) goto fail;
   if (alloc((void **)&r->taps_up, nt * 4, false) || alloc((void **)&r->taps_down, nt * 4, false) ||
       alloc((void **)&r->tail_up, B * PN_RATE_UP_TAIL * 4, true) || alloc((void **)&r->tail_down, B * r->td * 4, true) ||
       alloc((void **)&r->x48, B * PN_FRAME * 4, true) || alloc((void **)&r->y48, B * PN_FRAME * 4, true) ||
@@ -160,7 +160,7 @@ fail:
   return NULL;
 }
 
-// A converter with a rate per stream: the tap tables of all three filters, tails of the largest size for every stream (a rate
+// A converter with a rate per stream: the tap tables of all four filters, tails of the largest size for every stream (a rate
 // change never reallocates), rows of 480 samples.
 extern "C" pn_rate *pn_rate_create_mixed(pn_ctx *c, const int32_t *rates_hz) {
   if (!c) { pn_set_error("NULL argument"); return NULL; }
@@ -168,20 +168,21 @@ extern "C" pn_rate *pn_rate_create_mixed(pn_ctx *c, const int32_t *rates_hz) {
   DeviceGuard _dg(c->device);
   if (!_dg.ok) { pn_set_error("hipSetDevice(%d) failed", c->device); return NULL; }
   pn_rate *r = new pn_rate();
-  r->c = c; r->rate = 0; r->L = 0; r->n = PN_RATE_MIXED_ROW; r->td = pn_rate_down_tail(PN_RATE_MAX_L); r->bytes = 0;
+  r->c = c; r->rate = 0; r->f = 0; r->n = PN_RATE_MIXED_ROW; r->td = pn_rate_down_tail(PN_RATE_MAX_L); r->bytes = 0;
   r->mixed = true; r->factors = NULL; r->h_rows = NULL; r->laws.assign((size_t)c->B, PN_G711_ULAW); r->confs.assign((size_t)c->B, PN_CONF_NONE);
   r->gains.assign((size_t)c->B, 1.0f); r->caps.assign((size_t)c->B, 0);
   const size_t B = (size_t)c->B;
   if (rates_hz) r->rates.assign(rates_hz, rates_hz + B); else r->rates.assign(B, 48000);
-  static const int kL[3] = {6, 3, 2};
+  static const int kF[4] = {6, 3, 2, PN_RATE_F_3_2};   // (the order of pn_rate.hip rt_taps_offset; the h of 32000 is the table of 3 and is not staged twice)
   std::vector<float> h[2];
   std::vector<int> f(B);
   for (size_t s = 0; s < B; s++) f[s] = pn_rate_mixed_factor(r->rates[s]);
   auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
   for (int down = 0; down < 2; down++)
-    for (int L : kL) {
+    for (int f : kF) {
+      if (!down && f == PN_RATE_F_3_2) continue;
       float t[PN_RATE_MAX_TAPS];
-      const int nt = pn_rate_design(L, down, t, PN_RATE_MAX_TAPS);
+      const int nt = pn_rate_design(f, down, t, PN_RATE_MAX_TAPS);
       if (nt < 0) goto fail;
       h[down].insert(h[down].end(), t, t + nt);
     }
@@ -434,7 +435,7 @@ static int rate_aligned(const void *a, const void *b) {
 static int rate_up(pn_rate *r, const void *d_in, int fmt, float *d_out48, const RateRows &rows) {
   RateScope sc(r, RF_UP);
   if (r->mixed ? pn_launch_rate_up_mixed(r->c->stream, fmt, rows.n, rows.d_ids, r->factors, r->d_laws, d_in, d_out48, r->tail_up, r->taps_up)
-               : pn_launch_rate_up(r->c->stream, r->L, fmt, rows.n, rows.d_ids, r->d_laws, d_in, d_out48, r->tail_up, r->taps_up)) return -1;
+               : pn_launch_rate_up(r->c->stream, r->f, fmt, rows.n, rows.d_ids, r->d_laws, d_in, d_out48, r->tail_up, r->taps_up)) return -1;
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -442,7 +443,7 @@ static int rate_down(pn_rate *r, const float *d_in48, void *d_out, int fmt, cons
   const int sat = r->c->saturate ? 1 : 0;
   RateScope sc(r, RF_DOWN);
   if (r->mixed ? pn_launch_rate_down_mixed(r->c->stream, fmt, rows.n, rows.d_ids, r->factors, r->d_laws, d_in48, d_out, sat, r->tail_down, r->taps_down)
-               : pn_launch_rate_down(r->c->stream, r->L, fmt, rows.n, rows.d_ids, r->d_laws, d_in48, d_out, sat, r->tail_down, r->taps_down)) return -1;
+               : pn_launch_rate_down(r->c->stream, r->f, fmt, rows.n, rows.d_ids, r->d_laws, d_in48, d_out, sat, r->tail_down, r->taps_down)) return -1;
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -547,7 +548,7 @@ static int rate_process_host(pn_rate *r, const void *h_in, void *h_out, float *h
     const size_t w = pn_fmt_bytes(fmt);
     for (int s = 0; s < c->B; s++)
       memcpy(static_cast<char *>(h_out) + (size_t)s * r->n * w, static_cast<const char *>(r->h_rows) + (size_t)s * r->n * w,
-             (size_t)(PN_FRAME / pn_rate_mixed_factor(r->rates[s])) * w);
+             (size_t)pn_rate_factor_frame(pn_rate_mixed_factor(r->rates[s])) * w);
   }
   return 0;
 }
@@ -629,11 +630,11 @@ extern "C" int pn_rate_reset_profile(pn_rate *r) {
 // rate: the records' rate — the converter's, or on a mixed one the rate the listed streams share (record_rate)
 static int rate_records_host(pn_rate *r, int rate, bool import, const int32_t *ids, int n, void *h_records) {
   pn_ctx *c = r->c;
-  const int L = pn_rate_factor(rate);
-  return host_records_sync(c, import, h_records, (size_t)n * 4 * pn_rate_record_words(L), [&](void *d) {
+  const int f = pn_rate_factor(rate);
+  return host_records_sync(c, import, h_records, (size_t)n * 4 * pn_rate_record_words(f), [&](void *d) {
     const int *d_ids = stage_ids(c, ids, n);
     if (!d_ids) return -1;
-    pn_launch_rate_records(c->stream, L, rate, d_ids, n, r->tail_up, r->tail_down, r->td, d, import ? 1 : 0);
+    pn_launch_rate_records(c->stream, f, rate, d_ids, n, r->tail_up, r->tail_down, r->td, d, import ? 1 : 0);
     if (hipGetLastError() != hipSuccess) { pn_set_error(import ? "record scatter launch failed" : "record gather launch failed"); return -1; }
     return 0;
   });
@@ -666,7 +667,7 @@ static_assert(PN_RATE_STATE_MAX_BYTES == PN_RATE_STATE_HEADER_BYTES + 4 * (PN_RA
 extern "C" size_t pn_rate_state_max_bytes(void) { return PN_RATE_STATE_MAX_BYTES; }
 extern "C" size_t pn_rate_record_stride(const pn_rate *r) {
   if (!r) { pn_set_error("NULL argument"); return 0; }
-  return r->mixed ? (size_t)PN_RATE_STATE_MAX_BYTES : 4 * pn_rate_record_words(r->L);
+  return r->mixed ? (size_t)PN_RATE_STATE_MAX_BYTES : 4 * pn_rate_record_words(r->f);
 }
 static int rate_records_dev(pn_rate *r, bool import, const int32_t *ids, int n, void *d_records, int32_t *d_status) {
   if (!r || n < 0 || (n > 0 && (!ids || !d_records || (import && !d_status)))) { pn_set_error("bad argument"); return -1; }
@@ -677,7 +678,7 @@ static int rate_records_dev(pn_rate *r, bool import, const int32_t *ids, int n, 
   PN_ON_DEVICE(c);
   const int *d = stage_ids(c, ids, n);
   if (!d) return -1;
-  pn_launch_rate_records_dev(c->stream, d, n, r->mixed ? r->factors : NULL, r->L, r->tail_up, r->tail_down, r->td, d_records,
+  pn_launch_rate_records_dev(c->stream, d, n, r->mixed ? r->factors : NULL, r->f, r->tail_up, r->tail_down, r->td, d_records,
                              (int)(pn_rate_record_stride(r) / 4), d_status, import ? 1 : 0);
   PN_HIP_CHECK(hipGetLastError());
   return 0;

@@ -1,28 +1,28 @@
 // The mixed rate converter's rules that need no GPU, each stated once — HIP-free (builds with -DPN_NO_HIP), checked on the CPU by
 // tests/c/rate_mixed_sanitize.cpp under the sanitizers and by tests/test_rate_mixed_host.py through the C-ABI
-// (include/percepnet_hip.h "mixed rates"): the four per-stream rates and their sizes, what a list of rates and a rate change must
+// (include/percepnet_hip.h "mixed rates"): the five per-stream rates and their sizes, what a list of rates and a rate change must
 // be, and the one-rate-per-call rule of the state records.  48000 is a rate of a STREAM of a mixed converter (L = 1, a copy); no
 // single-rate converter, no filter design and no state record has it (pn_rate_design.h keeps refusing it).
 #pragma once
 #include "pn_rate_design.h"
 
-#define PN_RATE_MIXED_TEXT "8000, 16000, 24000 or 48000"
+#define PN_RATE_MIXED_TEXT "8000, 16000, 24000, 32000 or 48000"
 
-// L = 48000 / rate_hz for the four rates a stream of a mixed converter takes, 0 for every other
+// the factor (pn_rate_design.h) of the five rates a stream of a mixed converter takes, 0 for every other
 static inline int pn_rate_mixed_factor(int rate_hz) { return rate_hz == 48000 ? 1 : pn_rate_factor(rate_hz); }
 static inline int pn_rate_mixed_frame(int rate_hz) {
-  const int L = pn_rate_mixed_factor(rate_hz);
-  if (!L) { pn_set_error("rate %d Hz: a stream of a mixed converter takes " PN_RATE_MIXED_TEXT, rate_hz); return -1; }
-  return PN_FRAME / L;
+  const int f = pn_rate_mixed_factor(rate_hz);
+  if (!f) { pn_set_error("rate %d Hz: a stream of a mixed converter takes " PN_RATE_MIXED_TEXT, rate_hz); return -1; }
+  return pn_rate_factor_frame(f);
 }
 // the engine's 2880 samples at the stream's rate, plus T up and T down where there is a filter
 static inline int pn_rate_mixed_delay(int rate_hz) {
-  const int L = pn_rate_mixed_factor(rate_hz);
-  if (!L) { pn_set_error("rate %d Hz: a stream of a mixed converter takes " PN_RATE_MIXED_TEXT, rate_hz); return -1; }
-  return 6 * PN_FRAME / L + (L > 1 ? 2 * PN_RATE_TAPS : 0);
+  const int f = pn_rate_mixed_factor(rate_hz);
+  if (!f) { pn_set_error("rate %d Hz: a stream of a mixed converter takes " PN_RATE_MIXED_TEXT, rate_hz); return -1; }
+  return pn_rate_factor_delay(f);
 }
 
-// rates_hz[0..n): every one of the four.  -1 with pn_last_error naming the FIRST bad index; n == 0 is a legal list.
+// rates_hz[0..n): every one of the five.  -1 with pn_last_error naming the FIRST bad index; n == 0 is a legal list.
 static inline int pn_rate_mixed_rates_list_check(const int32_t *rates_hz, int n) {
   if (n < 0 || (n > 0 && !rates_hz)) { pn_set_error("bad argument"); return -1; }
   for (int i = 0; i < n; i++)
