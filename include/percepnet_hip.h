@@ -533,7 +533,7 @@ int pn_rate_export_streams(pn_rate *r, const int32_t *ids, int n, void *d_record
 int pn_rate_import_streams(pn_rate *r, const int32_t *ids, int n, const void *d_records, int32_t *d_status);
 /* Timing of the converter's two kernels inside a frame: HIP events around their launches, like pn_ctx_set_profiling but owned by
    the converter (the context's family list does not change).  Off by default; off, no event is created or recorded.  name:
-   "rate_up" | "rate_down" | "rate_mix" (the conference mix, below).  pn_rate_kernel_time synchronises the context's stream. */
+   "rate_up" | "rate_down" | "rate_mix" (the conference mix, below) | "rate_plc" (packet-loss concealment, below).  pn_rate_kernel_time synchronises the context's stream. */
 int pn_rate_set_profiling(pn_rate *r, int enable);
 int pn_rate_kernel_time(pn_rate *r, const char *name, double *total_ms, int64_t *launches);
 int pn_rate_reset_profile(pn_rate *r);
@@ -631,7 +631,7 @@ int pn_rate_get_stream_rates(const pn_rate *r, int32_t *h_rates);
    the context's pipeline and may be interleaved with the other pn_rate_submit_host_* calls and with pn_submit_host_*;
    pn_host_next_report works unchanged.
    NOT provided: linear and companded rows in one call; G.711 on pn_process_* without a converter (a mixed converter whose slots
-   run at 48000 covers it); G.711 Appendix I / II (packet-loss concealment, comfort noise).  How well the model, trained on
+   run at 48000 covers it); G.711 Appendix II comfort noise (packet-loss concealment: its own section below).  How well the model, trained on
    full-band linear speech, cleans companded narrowband input is not measured. */
 #define PN_G711_ULAW 0
 #define PN_G711_ALAW 1
@@ -779,6 +779,83 @@ float pn_rate_get_mix_hold(const pn_rate *r);
 int pn_rate_set_mix_report(pn_rate *r, int enable);
 int pn_rate_read_mix_report(pn_rate *r, void *h_report);
 int pn_rate_read_mix_report_dev(pn_rate *r, void *d_report);
+
+/* ---- packet-loss concealment: lost frames filled on the GPU ---------------------------------------------------------------------- */
+/* A stream whose packet did not arrive for a 10 ms tick is neither left off the id list (a hole, the engine's state spliced across
+   it) nor fed zeros (a click into the pitch and GRU state): its 48 kHz row is SYNTHESISED, a waveform substitution in the spirit of
+   G.711 Appendix I restated for 48 kHz float rows, with no added delay.  It runs in one kernel (csrc/pn_rate_plc.hip) between the
+   up-conversion and the engine, in place on the rows the engine reads, on a pn_rate of any kind (a mixed converter at 48000 covers
+   streams that need no conversion).  The engine sees a signal that is continuous in time; the mix, the down-conversion, the frame
+   report and the mix report need no change and are unchanged.  OFF by default: a converter that never enables it launches exactly
+   what it launches without this section, and one that enables it and loses nothing produces the same bits.
+
+   The rule, with every rounding and summation order, is csrc/pn_plc_rules.h (HIP-free); tests/plc_model.py restates it in numpy
+   float32 and the kernel matches both bit for bit.  Every fp32 operation is singly rounded, no product is contracted into an add.
+   State per stream (PN_PLC_STATE_BYTES = 10576 bytes, allocated by the first enable, never inside a frame): hist[1920], the last
+   four rows the engine was given, real or synthetic, newest at hist[1919] (a ring of four rows with a head per stream); q[720],
+   the period buffer; the lag P; r, the consecutive lost frames so far; the lost frames since reset.
+     received, r == 0:  the row goes into the history and is not altered.
+     first lost frame:  the lag.  Coarse: d[k] = hist[6k+5], k < 320; for l = 40..120, c = sum over k = 160..319 ascending of
+                        d[k] d[k-l], e = the sum of d[k-l]^2; score = c*c / e where c > 0, e > 0 and the quotient is no NaN, else 0;
+                        the best score wins, strictly greater in ascending l (ties and all zeros: the smallest lag).  Fine: L over
+                        [max(240, 6l-5), min(720, 6l+5)], the same score over k = 960..1919, summed as 8 interleaved parts
+                        (k = 960 + 8i + j, i ascending) that are then added in ascending j; same tie rule: P.
+                        The period: q[i] = hist[1920-P+i] for i < P - O, O = P/4; behind that a = hist[1920-P+i],
+                        b = hist[1920-2P+i], w = ((i - (P-O)) + 0.5) / O, q[i] = a + w (b - a).
+     lost frame:        x[n] = g(m) q[m mod P], m = 480 r + n; g = 1 for m < 480, (2880 - m) / 2400 up to 2880, then the sample is
+                        +0.0: 20 % per 10 ms, silence after 60 ms.  The row goes into the history; r += 1.
+     first received frame after a loss: n < 240: x[n] = syn + w (real - syn), w = (2n+1) / 480; n >= 240: the real bits; r = 0.
+   A lost stream's INPUT row is never read (NaN in it is harmless) and its up-conversion tail is left as it was: the up kernel is
+   launched over the advancing streams minus the lost ones.  A frame with nothing lost launches the up kernel exactly as before.
+
+   pn_rate_set_plc(r, enable): the first enable allocates and zeroes the state, and makes room in the context's id ring for a list
+     of n_streams ids, so that no frame allocates.  While on, every frame launches the concealer between the up-conversion and the
+     engine; while off nothing new is launched or read, and marks are dropped.  The frames of a pause are missing from the
+     histories, so enabling again after a disable zeroes the PLC state of every stream (lost counts included), like pn_rate_reset.
+   pn_rate_set_lost(r, ids, n): the listed streams are lost in the NEXT frame submitted on this converter (any pn_rate_process_*,
+     _active, _host or pn_rate_submit_host_* call, or pn_rate_plc_f32), and only in that one.  Calls before one frame add up.
+     Asynchronous on the context's stream and ordered exactly like pn_rate_set_stream_laws, on the pipelined path too, with no
+     wait.  Refused with -1, nothing changed or launched: a bad or duplicate id, or while PLC is off.  A marked stream that does
+     not advance in that frame (it is not on the _active list) keeps all its state; its mark is dropped.  A list goes to the device
+     in chunks of 16384 ids; should the device refuse a later chunk (-1, a HIP error), the streams of the chunks before it are
+     marked, on the host and on the device alike.
+   pn_rate_plc_f32(r, d_x48, ids, n_ids): the kernel on its own, in place on [n_streams][480] float rows at a 16-byte aligned
+     device address, ids as for pn_rate_up_*; it consumes the marks.  Refused while PLC is off.
+   pn_rate_kernel_time takes "rate_plc".
+   PLC report (optional; pn_rate_set_plc_report, pn_rate_read_plc_report synchronising, pn_rate_read_plc_report_dev asynchronous on
+     the context's stream; -1 while off): PN_PLC_REPORT_WORDS = 4 little-endian uint32 words per stream, [n_streams][4], written for
+     every stream that advances:
+     word 0  flags   PN_PLC_CONCEALED the row is synthetic, PN_PLC_CROSSFADE it is the cross-fade out of a loss, PN_PLC_SILENT the
+                     synthetic row lies wholly behind the fade (all +0.0)
+     word 1  P       the lag of the last search, 0 before the first
+     word 2  run     consecutive lost frames including this one; 0 for a received frame
+     word 3  lost    lost frames since reset
+   Lifecycle.  pn_rate_reset zeroes the PLC state of every stream; pn_rate_reset_streams and pn_rate_set_stream_rates that of the
+   listed ones: a following loss conceals from an empty history, that is with silence.  Law, conference and mix settings do not touch
+   it.  Records (pn_rate_export_streams*) do not carry it: pn_rate_import_streams and pn_rate_import_streams_host zero the PLC state
+   of the slots they write (the device form whatever status a record gets), so a moved stream starts with an empty history in its
+   new slot and hears nothing of the slot's previous stream.
+   Host only, needing no GPU: pn_plc_pitch (hist[1920] -> P), pn_plc_period (hist, P in [240, 720] -> q[0..P); -1 otherwise),
+   pn_plc_gain (m -> g(m)).
+   NOT provided: Appendix I's lengthening of the repeated segment to two and three periods on long losses; Appendix II comfort noise;
+   concealment on pn_process_* without a converter; PLC state in the records.  How the model's output quality fares on concealed
+   frames is not measured. */
+#define PN_PLC_HIST 1920
+#define PN_PLC_P_MIN 240
+#define PN_PLC_P_MAX 720
+#define PN_PLC_REPORT_WORDS 4
+#define PN_PLC_CONCEALED 1
+#define PN_PLC_CROSSFADE 2
+#define PN_PLC_SILENT 4
+int pn_plc_pitch(const float *hist1920);
+int pn_plc_period(const float *hist1920, int P, float *q);
+float pn_plc_gain(int64_t m);
+int pn_rate_set_plc(pn_rate *r, int enable);
+int pn_rate_set_lost(pn_rate *r, const int32_t *ids, int n);
+int pn_rate_plc_f32(pn_rate *r, float *d_x48, const int32_t *ids, int n_ids);
+int pn_rate_set_plc_report(pn_rate *r, int enable);
+int pn_rate_read_plc_report(pn_rate *r, void *h_report);
+int pn_rate_read_plc_report_dev(pn_rate *r, void *d_report);
 
 const char *pn_last_error(void);
 const char *pn_version(void);

@@ -30,6 +30,11 @@ CONF_NONE, CONF_MAX_MEMBERS = -1, 32          # PN_CONF_*: no conference; the mo
 MIX_REPORT_WORDS = 4                          # PN_MIX_REPORT_WORDS: words of one record of the mix report (pn_rate_set_mix_report)
 MIX_SELECTED, MIX_MUTED, MIX_IN_CONF = 1, 2, 4                      # its flags
 MIX_REPORT_DTYPE = np.dtype([("level", "<f4"), ("flags", "<u4"), ("mix_peak", "<f4"), ("mix_clipped", "<i4")])
+# packet-loss concealment (include/percepnet_hip.h "packet-loss concealment"): PN_PLC_*
+PLC_HIST, PLC_P_MIN, PLC_P_MAX = 1920, 240, 720
+PLC_REPORT_WORDS = 4
+PLC_CONCEALED, PLC_CROSSFADE, PLC_SILENT = 1, 2, 4                  # its flags
+PLC_REPORT_DTYPE = np.dtype([("flags", "<u4"), ("period", "<u4"), ("run", "<u4"), ("lost", "<u4")])
 # per-stream frame report (include/percepnet_hip.h pn_ctx_set_report): one record of PN_REPORT_WORDS 32-bit words per stream
 REPORT_WORDS = 8
 REPORT_DTYPE = np.dtype([("in_peak", "<f4"), ("in_energy", "<f4"), ("out_peak", "<f4"), ("out_energy", "<f4"), ("gain_mean", "<f4"),
@@ -200,6 +205,17 @@ def load_library():
         L.pn_rate_get_mix_hold.restype = ctypes.c_float
         L.pn_rate_get_mix_hold.argtypes = [_vp]
         L.pn_rate_set_mix_report.argtypes = [_vp, ctypes.c_int]
+    if hasattr(L, "pn_rate_set_plc"):
+        L.pn_plc_pitch.argtypes = [_vp]
+        L.pn_plc_period.argtypes = [_vp, ctypes.c_int, _vp]
+        L.pn_plc_gain.restype = ctypes.c_float
+        L.pn_plc_gain.argtypes = [ctypes.c_int64]
+        for name in ("pn_rate_set_plc", "pn_rate_set_plc_report"):
+            getattr(L, name).argtypes = [_vp, ctypes.c_int]
+        L.pn_rate_set_lost.argtypes = [_vp, _vp, ctypes.c_int]
+        L.pn_rate_plc_f32.argtypes = [_vp, _vp, _vp, ctypes.c_int]
+        for name in ("pn_rate_read_plc_report", "pn_rate_read_plc_report_dev"):
+            getattr(L, name).argtypes = [_vp, _vp]
     if hasattr(L, "pn_host_pipeline_prepare"):
         L.pn_host_pipeline_prepare.argtypes = [_vp]
     L.pn_ctx_debug_copy.restype = ctypes.c_longlong
@@ -624,6 +640,31 @@ def mix_select(levels, n_max):
     return sel[:a.size].astype(bool)
 
 
+def plc_pitch(hist):
+    """The lag P in [PLC_P_MIN, PLC_P_MAX] the concealer finds on a history of PLC_HIST samples, newest last (pn_plc_pitch, host only)."""
+    a = np.ascontiguousarray(hist, dtype=np.float32).ravel()
+    if a.size != PLC_HIST:
+        raise PercepNetError(f"a history of {a.size} samples: the concealer keeps {PLC_HIST}")
+    return int(load_library().pn_plc_pitch(a.ctypes.data))
+
+
+def plc_period(hist, P):
+    """The period buffer q[0..P) of a history and a lag (pn_plc_period, host only) -> float32 [P]."""
+    L = load_library()
+    a = np.ascontiguousarray(hist, dtype=np.float32).ravel()
+    if a.size != PLC_HIST:
+        raise PercepNetError(f"a history of {a.size} samples: the concealer keeps {PLC_HIST}")
+    q = np.empty(max(int(P), 1), np.float32)
+    if L.pn_plc_period(a.ctypes.data, int(P), q.ctypes.data) != 0:
+        raise PercepNetError(_err(L))
+    return q
+
+
+def plc_gain(m):
+    """g(m): the gain of the synthetic sample m samples into a loss (pn_plc_gain, host only) -> numpy float32 scalar."""
+    return np.float32(load_library().pn_plc_gain(int(m)))
+
+
 class RateConverter:
     """8, 16, 24 or 32 kHz streams through a 48 kHz Context (pn_rate): a converter beside `ctx` for all of its streams at ONE rate.
     It borrows the context (device, n_streams, HIP stream): close the converter before the context."""
@@ -807,6 +848,35 @@ class RateConverter:
         """The same into device memory [n_streams][4] words, asynchronous on the context's stream (pn_rate_read_mix_report_dev)."""
         self._chk(self.L.pn_rate_read_mix_report_dev(self.h, d_report))
 
+    # packet-loss concealment: a lost stream's 48 kHz row is synthesised from its history, between the up-conversion and the engine
+    def set_plc(self, on):
+        """Packet-loss concealment on or off (pn_rate_set_plc); the first enable allocates the per-stream state."""
+        self._chk(self.L.pn_rate_set_plc(self.h, 1 if on else 0))
+
+    def set_lost(self, ids):
+        """Streams `ids` are lost in the NEXT frame submitted on this converter, and only in that one (pn_rate_set_lost):
+        asynchronous, ordered like set_stream_laws; calls before one frame add up.  Refused while PLC is off."""
+        a, n = self._ids(ids)
+        self._chk(self.L.pn_rate_set_lost(self.h, a.ctypes.data if a is not None else None, n))
+
+    def plc_f32_dev(self, d_x48, ids=None):
+        """The concealer on its own, in place on device rows [n_streams][480] float (pn_rate_plc_f32); it consumes the marks."""
+        a, n = self._ids(ids)
+        self._chk(self.L.pn_rate_plc_f32(self.h, d_x48, a.ctypes.data if a is not None else None, n))
+
+    def set_plc_report(self, on):
+        self._chk(self.L.pn_rate_set_plc_report(self.h, 1 if on else 0))
+
+    def read_plc_report(self):
+        """-> PLC_REPORT_DTYPE [n_streams]: the records of the last frame (pn_rate_read_plc_report, synchronising)."""
+        rep = np.empty(self.n_streams, PLC_REPORT_DTYPE)
+        self._chk(self.L.pn_rate_read_plc_report(self.h, rep.ctypes.data))
+        return rep
+
+    def read_plc_report_dev(self, d_report):
+        """The same into device memory [n_streams][4] words, asynchronous on the context's stream (pn_rate_read_plc_report_dev)."""
+        self._chk(self.L.pn_rate_read_plc_report_dev(self.h, d_report))
+
     # one whole frame, device pointers: [n_streams][frame] in and out at the low rate, d_gr [n_streams][68] or None
     def process_f32_dev(self, d_in, d_out, d_gr=None, ids=None):
         if ids is None:
@@ -893,7 +963,8 @@ class RateConverter:
         self._chk(self.L.pn_rate_reset_profile(self.h))
 
     def kernel_times(self, names=("rate_up", "rate_down")):
-        """-> {"rate_up": (total_ms, launches), "rate_down": (...)}; names: which kernels ("rate_mix" is the conference mix)"""
+        """-> {"rate_up": (total_ms, launches), "rate_down": (...)}; names: which kernels ("rate_mix" is the conference mix,
+        "rate_plc" the packet-loss concealer)"""
         out = {}
         for name in names:
             ms = ctypes.c_double()

@@ -5,7 +5,7 @@
 // dropped, main.cpp:32-33); with a single pair ./feature_test.raw gets 68 floats per frame.
 //
 //   percepnet_run [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N]
-//                 [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
+//                 [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--plc [--lose P:F0-F1,P:F,..]] [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
 //                 in0.pcm out0.pcm [in1.pcm out1.pcm ...]
 //
 // --rate R: the files are raw int16 at R Hz instead of 48 kHz, in frames of n = 480 * R / 48000 samples (80 | 160 | 240 | 320): a rate
@@ -42,6 +42,10 @@
 // --conf-speakers N: every conference mixes its N loudest talkers only (pn_rate_set_conf_speakers; 0 = everybody, up to 32);
 // --mix-gains G0,G1,..: one send gain per pair (pn_rate_set_stream_mix_gains; 0 mutes the pair, which still hears).  Both need
 // --conference and are refused without it.
+// --plc: packet-loss concealment on the converter (pn_rate_set_plc): with --rate or --rates it uses theirs, alone it makes a mixed
+// converter of all 48000, as --conference does.  --lose P:F0-F1,P:F,..: pair P (counted over the whole command line, from 0) loses its
+// frames F0..F1 (or the one frame F; a pair's frames count from 0): the frame is still READ from the pair's input and discarded, so the
+// files stay aligned, and pn_rate_set_lost marks the pair's slot in front of that frame's submit.  --lose without --plc is refused.
 //
 // --atten-lim DB: every stream takes out at most DB dB of noise (pn_ctx_set_atten_limit; 0 = the input, delayed; default: no
 // limit).  A slot reset clears a stream's limit (a reset slot is a new call), so the limit is set again on every reset slot.
@@ -111,6 +115,9 @@ static int g_g711 = -1;                               // --g711: the law of ever
 static std::vector<int32_t> g_confs;                  // --conference: one conference per pair (empty: not given; PN_CONF_NONE for `-`)
 static int g_conf_speakers = -1;                      // --conf-speakers: N of every conference (-1: not given)
 static std::vector<float> g_mix_gains;                // --mix-gains: one send gain per pair (empty: not given)
+static bool g_plc = false;                            // --plc: packet-loss concealment on the converter
+struct LoseRange { long pair, f0, f1; };
+static std::vector<LoseRange> g_lose;                 // --lose: pair, first and last lost frame of the pair
 // --report: what a pair's written frames add up to (one report record = PN_REPORT_WORDS words, include/percepnet_hip.h)
 struct PairStat { long frames = 0; long long clipped = 0; float peak = 0.f; double e_in = 0, e_out = 0; };
 static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, int postfilter, bool tap, int n_slots) {
@@ -153,6 +160,7 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
     if (!g_mix_gains.empty() && pn_rate_set_stream_mix_gains(rt, all.data(), B, g_mix_gains.data() + sh->first))
       return fail(3, std::string("pn_rate_set_stream_mix_gains: ") + pn_last_error());
   }
+  if (g_plc && pn_rate_set_plc(rt, 1)) return fail(3, std::string("pn_rate_set_plc: ") + pn_last_error());
   if (postfilter) pn_ctx_set_postfilter(cx, 1);
   if ((g_saturate && pn_ctx_set_output_saturate(cx, 1)) || (g_report && pn_ctx_set_report(cx, 1))) return fail(3, pn_last_error());
   auto set_limit = [&](const int32_t *ids, int n) {     // --atten-lim on these slots (after creation and after every slot reset)
@@ -169,10 +177,11 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
   fin.assign(B, NULL); fout.assign(B, NULL);
   int next_pair = 0;
   std::vector<int> cur_pair(B, 0);
+  std::vector<long> pair_frame(B, 0);                   // --lose: the frames the pair playing in a slot has supplied so far
   std::vector<PairStat> stat(g_report ? P : 0);
   auto open_pair = [&](int s) -> bool {                 // the next waiting pair starts playing in slot s
     const char *pi = paths[2 * (sh->first + next_pair)], *po = paths[2 * (sh->first + next_pair) + 1];
-    cur_pair[s] = next_pair++;
+    cur_pair[s] = next_pair++; pair_frame[s] = 0;
     fin[s] = fopen(pi, "rb"); fout[s] = fopen(po, "wb");
     if (!fin[s] || !fout[s]) { fail(4, std::string("cannot open ") + pi + " / " + po); return false; }
     return true;
@@ -218,11 +227,12 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
     }
   };
   std::vector<int32_t> restart, restart_rates, live;   // live (--conference): the slots whose pair still has input, this frame's id list
+  std::vector<int32_t> lost;                           // --lose: the slots whose pair loses this frame
   int n_alive = B;
   long t = 0;
   for (;; t++) {
     Slot &sl = slot[t % 3];
-    restart.clear(); restart_rates.clear(); live.clear();
+    restart.clear(); restart_rates.clear(); live.clear(); lost.clear();
     for (int s = 0; s < B; s++) {
       char *x = sl.in + (size_t)s * FS * SW;
       sl.file[s] = NULL; sl.skip[s] = 0; sl.last[s] = 0;
@@ -246,12 +256,18 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
       if (fin[s]) { sl.file[s] = fout[s]; sl.skip[s] = first[s]; first[s] = 0; sl.pair[s] = cur_pair[s]; sl.fs[s] = pair_fs(cur_pair[s]); }
       else memset(x, idle, FS * SW);
       if (fin[s]) live.push_back(s);
+      if (fin[s]) {                                    // the frame was read, so the files stay aligned; lost: its samples never reach the device's kernels
+        for (const LoseRange &lr : g_lose)
+          if (lr.pair == sh->first + cur_pair[s] && pair_frame[s] >= lr.f0 && pair_frame[s] <= lr.f1) { lost.push_back(s); break; }
+        pair_frame[s]++;
+      }
     }
     if (n_alive == 0) break;
     if (!restart.empty() && (pn_ctx_reset_streams(cx, restart.data(), (int)restart.size()) ||
                              (rt && (mixed ? pn_rate_set_stream_rates(rt, restart.data(), (int)restart.size(), restart_rates.data())
                                            : pn_rate_reset_streams(rt, restart.data(), (int)restart.size()))) ||
                              set_limit(restart.data(), (int)restart.size()))) return fail(5, pn_last_error());
+    if (!lost.empty() && pn_rate_set_lost(rt, lost.data(), (int)lost.size())) return fail(5, pn_last_error());
     if (g_report && pn_host_next_report(cx, sl.rep)) return fail(5, pn_last_error());
     // --rate, --rates: the converter's frame through the same pipeline
     // --conference: only the pairs that still have input advance, so an ended one is no member of this frame's mix
@@ -269,7 +285,7 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
 
 // the usage text, for a command line without pairs and for a rate no converter takes.  Returns the exit status, 1.
 static int usage(const char *argv0) {
-  fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N] [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv0);
+  fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N] [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--plc [--lose P:F0-F1,P:F,..]] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv0);
   return 1;
 }
 
@@ -341,6 +357,22 @@ int main(int argc, char **argv) {
         q = end + 1;
       }
     }
+    else if (!strcmp(argv[ai], "--plc")) g_plc = true;               // packet-loss concealment on the converter (pn_rate_set_plc)
+    else if (!strcmp(argv[ai], "--lose") && ai + 1 < argc) {        // pair:frame or pair:first-last, lost frames (pn_rate_set_lost)
+      const char *v = argv[++ai];
+      for (const char *q = v; ; ) {
+        char *end = NULL;
+        LoseRange lr;
+        lr.pair = strtol(q, &end, 10);
+        bool ok = end != q && *end == ':' && lr.pair >= 0;
+        if (ok) { q = end + 1; lr.f0 = lr.f1 = strtol(q, &end, 10); ok = end != q && lr.f0 >= 0; }
+        if (ok && *end == '-') { q = end + 1; lr.f1 = strtol(q, &end, 10); ok = end != q && lr.f1 >= lr.f0; }
+        if (!ok || (*end && *end != ',')) { fprintf(stderr, "--lose: expected a comma-separated list of pair:frame or pair:first-last, got '%s'\n", v); return 1; }
+        g_lose.push_back(lr);
+        if (!*end) break;
+        q = end + 1;
+      }
+    }
     else if (!strcmp(argv[ai], "--no-numa")) g_numa = false;         // leave the host threads' CPU affinity alone
     else if (!strcmp(argv[ai], "--verbose")) g_verbose = true;       // one line per device: its NUMA binding
     else if (!strcmp(argv[ai], "--slots") && ai + 1 < argc) n_slots = atoi(argv[++ai]);   // concurrent streams per device: pairs queue for them
@@ -377,6 +409,10 @@ int main(int argc, char **argv) {
     if (pn_rate_confs_check(g_confs.data(), B, B)) { fprintf(stderr, "--conference: %s\n", pn_last_error()); return 1; }
     if (!g_rate && g_rates.empty()) g_rates.assign(B, 48000);        // on its own: a mixed converter of all 48000
   }
+  if (!g_lose.empty() && !g_plc) { fprintf(stderr, "--lose needs --plc: a lost frame is filled by the packet-loss concealment\n"); return 1; }
+  for (const LoseRange &lr : g_lose)
+    if (lr.pair >= B) { fprintf(stderr, "--lose: pair %ld of %d pairs (pairs count from 0)\n", lr.pair, B); return 1; }
+  if (g_plc && !g_rate && g_rates.empty()) g_rates.assign(B, 48000);        // on its own: a mixed converter of all 48000
   pn_model *m = NULL;
   if (model_path) { FILE *f = fopen(model_path, "rb"); if (f) { m = pn_model_from_file(f); fclose(f); } }
   else if (&percepnet_model_orig) m = pn_model_from_rnnmodel(&percepnet_model_orig);

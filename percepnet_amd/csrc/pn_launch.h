@@ -111,6 +111,11 @@ void pn_launch_rate_mix_sel(hipStream_t st, int n_rows, const int *d_ids, const 
                             const float *in48, float *out48, const float *d_gains, const int *d_caps, float *d_level, float hold, void *d_report);
 void pn_launch_rate_conf_stamp(hipStream_t st, const int *d_ids, int n, uint32_t *d_stamp, uint32_t tick);
 void pn_launch_rate_conf_rows(hipStream_t st, const int *d_touched, const int *d_rows, int k, int *d_members);
+// packet-loss concealment (pn_rate_plc.hip; the rule pn_plc_rules.h): rows d_ids[0..n_rows) or, with d_ids == NULL, streams 0..n_rows of
+// x48 [.][480], in place.  A stream whose d_lost word equals tick is lost this frame (conf_stamp writes the marks).  State: hist
+// [n_streams][1920], q [n_streams][720], meta [n_streams][4] words; d_report [n_streams][4] words or NULL
+void pn_launch_rate_plc(hipStream_t st, int n_rows, const int *d_ids, const uint32_t *d_lost, uint32_t tick, float *x48, float *hist, float *q,
+                        void *meta, void *d_report);
 // ---- the network launchers (pn_nn*.hip) -----------------------------------------------------------------------------------------
 // Device pointers of a layer's biases and weights in the formats of pn_network.h: raw (w, rw), packed fp32 or fp16 planes (wp,
 // rwp), the 16x16x4 packing of a narrow layer (wq)

@@ -10,6 +10,7 @@
 #include "pn_g711.h"         // the 8-bit sample format: the companding and what a list of laws must be
 #include "pn_conf.h"         // conferences: what an id must be, the table after a change, the members in ascending order
 #include "pn_mix_rules.h"    // loudest-N, send gains, hold: what the settings must be; the level and the selection for the host
+#include "pn_plc_rules.h"    // packet-loss concealment: the signal rule for the host, the sizes of the state
 #include <string>
 #include <vector>
 
@@ -53,6 +54,16 @@ struct pn_rate {
   float *d_gains = NULL, *d_level = NULL;  // [B], [B]
   int *d_caps = NULL;                      // [B]
   void *d_mix_report = NULL;               // [B][PN_MIX_REPORT_WORDS] words
+  // packet-loss concealment (pn_rate_set_plc; the rule pn_plc_rules.h): the state — history ring, period buffer and four meta words per
+  // stream — exists from the first enable on, never allocated inside a frame.  Marks (pn_rate_set_lost): a stamp word per stream on
+  // the device, == plc_tick where the stream is lost in the NEXT frame, written in stream order through the id ring; the host keeps
+  // the same marks, which is how a frame knows whom to leave out of the up-conversion.  A frame consumes them: plc_tick moves on
+  bool plc = false, plc_report = false;
+  float *d_plc_hist = NULL, *d_plc_q = NULL;           // [B][1920], [B][720]
+  void *d_plc_meta = NULL, *d_plc_report = NULL;      // [B][4] words each
+  uint32_t *d_plc_lost = NULL, plc_tick = 1;          // [B]
+  std::vector<uint8_t> lost_mark;                     // [B]
+  std::vector<int32_t> lost_ids, up_ids;              // the marked streams; a frame's "advancing minus lost"
   std::vector<void *> allocs;
   // timing of the kernels (pn_rate_set_profiling): HIP events around their launches, like the context's families but owned
   // here; while it is off no event exists and none is recorded
@@ -60,10 +71,10 @@ struct pn_rate {
   struct Ev { int fam; hipEvent_t a, b; };
   std::vector<Ev> events;
   std::vector<hipEvent_t> event_pool;
-  double fam_ms[3] = {0, 0, 0}; int64_t fam_n[3] = {0, 0, 0};
+  double fam_ms[4] = {0, 0, 0, 0}; int64_t fam_n[4] = {0, 0, 0, 0};
 };
-enum { RF_UP, RF_DOWN, RF_MIX, RF_COUNT };
-static const char *const kRateFamily[RF_COUNT] = {"rate_up", "rate_down", "rate_mix"};
+enum { RF_UP, RF_DOWN, RF_MIX, RF_PLC, RF_COUNT };
+static const char *const kRateFamily[RF_COUNT] = {"rate_up", "rate_down", "rate_mix", "rate_plc"};
 struct RateScope {
   pn_rate *r; int fam; hipEvent_t a, b; bool on;
   RateScope(pn_rate *r_, int fam_) : r(r_), fam(fam_), on(r_->profiling) {
@@ -117,6 +128,9 @@ extern "C" int pn_rate_confs_check(const int32_t *confs, int n, int n_streams) {
 extern "C" int pn_rate_mix_gains_check(const float *gains, int n) { return pn_mix_gains_list_check(gains, n); }
 extern "C" float pn_mix_level(const float *row480) { if (!row480) { pn_set_error("NULL argument"); return NAN; } return pn_mix_level_host(row480); }
 extern "C" int pn_mix_select(const float *levels, int k, int n_max, uint8_t *selected) { return pn_mix_select_host(levels, k, n_max, selected); }
+extern "C" int pn_plc_pitch(const float *hist1920) { if (!hist1920) { pn_set_error("NULL argument"); return -1; } return pn_plc_pitch_host(hist1920); }
+extern "C" int pn_plc_period(const float *hist1920, int P, float *q) { return pn_plc_period_host(hist1920, P, q); }
+extern "C" float pn_plc_gain(int64_t m) { return pn_plc_gain_host(m); }
 
 // ---- lifecycle ---------------------------------------------------------------------------------------------------------------
 extern "C" void pn_rate_destroy(pn_rate *r) {
@@ -209,6 +223,12 @@ extern "C" int pn_rate_get_stream_rates(const pn_rate *r, int32_t *h_rates) {
   for (int s = 0; s < r->c->B; s++) h_rates[s] = r->mixed ? r->rates[s] : r->rate;
   return 0;
 }
+// the PLC state of the staged streams d[0..n) goes to zero: an empty history, no lag, no run (nothing while PLC was never enabled)
+static void plc_zero_rows(pn_rate *r, const int *d, int n) {
+  pn_launch_zero_rows(r->c->stream, r->d_plc_hist, PN_PLC_HIST, PN_PLC_HIST, 1, 0, d, n);
+  pn_launch_zero_rows(r->c->stream, r->d_plc_q, PN_PLC_P_MAX, PN_PLC_P_MAX, 1, 0, d, n);
+  pn_launch_zero_rows(r->c->stream, r->d_plc_meta, 4, 4, 1, 0, d, n);
+}
 // A rate change of the listed streams, asynchronous and ordered like pn_rate_reset_streams: the ids and the new factors go
 // through the context's id ring in one copy, one launch writes the factors, two zero the tails.
 extern "C" int pn_rate_set_stream_rates(pn_rate *r, const int32_t *ids, int n, const int32_t *rates_hz) {
@@ -225,6 +245,7 @@ extern "C" int pn_rate_set_stream_rates(pn_rate *r, const int32_t *ids, int n, c
   pn_launch_zero_rows(r->c->stream, r->tail_up, PN_RATE_UP_TAIL, PN_RATE_UP_TAIL, 1, 0, d, n);
   pn_launch_zero_rows(r->c->stream, r->tail_down, r->td, r->td, 1, 0, d, n);
   pn_launch_zero_rows(r->c->stream, r->d_level, 1, 1, 1, 0, d, n);       // (nothing while no level exists)
+  plc_zero_rows(r, d, n);
   PN_HIP_CHECK(hipGetLastError());
   for (int i = 0; i < n; i++) r->rates[ids[i]] = rates_hz[i];
   return 0;
@@ -392,12 +413,93 @@ static int mix_report_copy(pn_rate *r, void *dst, hipMemcpyKind kind) {
 extern "C" int pn_rate_read_mix_report(pn_rate *r, void *h_report) { return mix_report_copy(r, h_report, hipMemcpyDeviceToHost); }
 extern "C" int pn_rate_read_mix_report_dev(pn_rate *r, void *d_report) { return mix_report_copy(r, d_report, hipMemcpyDeviceToDevice); }
 
+// ---- packet-loss concealment (include/percepnet_hip.h; the rule pn_plc_rules.h; the kernel pn_rate_plc.hip) ----------------------
+static int plc_drop_marks(pn_rate *r) {              // (the caller is on the context's device)
+  for (int32_t s : r->lost_ids) r->lost_mark[s] = 0;
+  r->lost_ids.clear();
+  if (++r->plc_tick == 0) {                          // (2^32 frames on: no stale stamp may meet the new tick)
+    PN_HIP_CHECK(hipMemsetAsync(r->d_plc_lost, 0, (size_t)r->c->B * sizeof(uint32_t), r->c->stream));
+    r->plc_tick = 1;
+  }
+  return 0;
+}
+extern "C" int pn_rate_set_plc(pn_rate *r, int enable) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  PN_ON_DEVICE(r->c);
+  if (enable && !r->d_plc_meta) {
+    pn_ctx *c = r->c;
+    const size_t B = (size_t)c->B;
+    float *hist = NULL, *q = NULL; void *meta = NULL; uint32_t *lost = NULL;
+    auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
+    if (alloc((void **)&hist, B * PN_PLC_HIST * 4, true) || alloc((void **)&q, B * PN_PLC_P_MAX * 4, true) || alloc(&meta, B * 16, true) ||
+        alloc((void **)&lost, B * sizeof(uint32_t), true)) return -1;
+    r->lost_mark.assign(B, 0); r->lost_ids.reserve(B);
+    r->d_plc_hist = hist; r->d_plc_q = q; r->d_plc_lost = lost; r->plc_tick = 1; r->d_plc_meta = meta;
+    // room in the id ring for the longest list a frame stages, "every stream but the lost ones", so that no frame grows the ring:
+    // the identity list goes through it once, read by nobody
+    r->up_ids.resize(B);
+    for (size_t s = 0; s < B; s++) r->up_ids[s] = (int32_t)s;
+    if (!stage_ids(c, r->up_ids.data(), (int)B)) return -1;
+    r->up_ids.clear();
+  } else if (enable && !r->plc) {
+    // on again after a pause: the frames in between are missing from the histories, so every stream starts with an empty one
+    PN_HIP_CHECK(hipMemsetAsync(r->d_plc_hist, 0, (size_t)r->c->B * PN_PLC_HIST * 4, r->c->stream));
+    PN_HIP_CHECK(hipMemsetAsync(r->d_plc_q, 0, (size_t)r->c->B * PN_PLC_P_MAX * 4, r->c->stream));
+    PN_HIP_CHECK(hipMemsetAsync(r->d_plc_meta, 0, (size_t)r->c->B * 16, r->c->stream));
+  }
+  if (!enable && r->plc && plc_drop_marks(r)) return -1;
+  r->plc = enable != 0;
+  return 0;
+}
+extern "C" int pn_rate_set_lost(pn_rate *r, const int32_t *ids, int n) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (!r->plc) { pn_set_error("packet-loss concealment is off (pn_rate_set_plc)"); return -1; }
+  if (pn_ids_check(r->c->B, ids, n, true)) return -1;
+  if (n == 0) return 0;
+  PN_ON_DEVICE(r->c);
+  for (int at = 0; at < n; at += 16384) {
+    const int m = n - at < 16384 ? n - at : 16384;
+    const int *d = stage_ids(r->c, ids + at, m);
+    if (!d) return -1;
+    pn_launch_rate_conf_stamp(r->c->stream, d, m, r->d_plc_lost, r->plc_tick);
+    PN_HIP_CHECK(hipGetLastError());
+    // the host's marks chunk by chunk, right behind the device's: a device failure at a later chunk leaves the two in step
+    for (int i = at; i < at + m; i++)
+      if (!r->lost_mark[ids[i]]) { r->lost_mark[ids[i]] = 1; r->lost_ids.push_back(ids[i]); }
+  }
+  return 0;
+}
+extern "C" int pn_rate_set_plc_report(pn_rate *r, int enable) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (enable && !r->d_plc_report) {
+    PN_ON_DEVICE(r->c);
+    if (dev_alloc_into(r->allocs, r->bytes, r->c->stream, &r->d_plc_report, (size_t)r->c->B * PN_PLC_REPORT_WORDS * 4, true)) return -1;
+  }
+  r->plc_report = enable != 0;
+  return 0;
+}
+static int plc_report_copy(pn_rate *r, void *dst, hipMemcpyKind kind) {
+  if (!r || !dst) { pn_set_error("NULL argument"); return -1; }
+  if (!r->plc_report) { pn_set_error("the PLC report is off (pn_rate_set_plc_report)"); return -1; }
+  PN_ON_DEVICE(r->c);
+  PN_HIP_CHECK(hipMemcpyAsync(dst, r->d_plc_report, (size_t)r->c->B * PN_PLC_REPORT_WORDS * 4, kind, r->c->stream));
+  if (kind == hipMemcpyDeviceToHost) PN_HIP_CHECK(hipStreamSynchronize(r->c->stream));
+  return 0;
+}
+extern "C" int pn_rate_read_plc_report(pn_rate *r, void *h_report) { return plc_report_copy(r, h_report, hipMemcpyDeviceToHost); }
+extern "C" int pn_rate_read_plc_report_dev(pn_rate *r, void *d_report) { return plc_report_copy(r, d_report, hipMemcpyDeviceToDevice); }
+
 extern "C" int pn_rate_reset(pn_rate *r) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   PN_ON_DEVICE(r->c);
   PN_HIP_CHECK(hipMemsetAsync(r->tail_up, 0, (size_t)r->c->B * PN_RATE_UP_TAIL * 4, r->c->stream));
   PN_HIP_CHECK(hipMemsetAsync(r->tail_down, 0, (size_t)r->c->B * r->td * 4, r->c->stream));
   if (r->d_level) PN_HIP_CHECK(hipMemsetAsync(r->d_level, 0, (size_t)r->c->B * 4, r->c->stream));
+  if (r->d_plc_meta) {
+    PN_HIP_CHECK(hipMemsetAsync(r->d_plc_hist, 0, (size_t)r->c->B * PN_PLC_HIST * 4, r->c->stream));
+    PN_HIP_CHECK(hipMemsetAsync(r->d_plc_q, 0, (size_t)r->c->B * PN_PLC_P_MAX * 4, r->c->stream));
+    PN_HIP_CHECK(hipMemsetAsync(r->d_plc_meta, 0, (size_t)r->c->B * 16, r->c->stream));
+  }
   return 0;
 }
 
@@ -411,6 +513,7 @@ extern "C" int pn_rate_reset_streams(pn_rate *r, const int32_t *ids, int n) {
   pn_launch_zero_rows(r->c->stream, r->tail_up, PN_RATE_UP_TAIL, PN_RATE_UP_TAIL, 1, 0, d, n);
   pn_launch_zero_rows(r->c->stream, r->tail_down, r->td, r->td, 1, 0, d, n);
   pn_launch_zero_rows(r->c->stream, r->d_level, 1, 1, 1, 0, d, n);
+  plc_zero_rows(r, d, n);
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -461,6 +564,16 @@ static int rate_mix(pn_rate *r, const float *d_in48, float *d_out48, const RateR
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
+// the concealer over the rows, in place; it consumes the marks: the tick moves on, and the host's copy of them is cleared
+static int rate_plc(pn_rate *r, float *d_x48, const RateRows &rows) {
+  {
+    RateScope sc(r, RF_PLC);
+    pn_launch_rate_plc(r->c->stream, rows.n, rows.d_ids, r->d_plc_lost, r->plc_tick, d_x48, r->d_plc_hist, r->d_plc_q, r->d_plc_meta,
+                       r->plc_report ? r->d_plc_report : NULL);
+  }
+  PN_HIP_CHECK(hipGetLastError());
+  return plc_drop_marks(r);
+}
 static int rate_up_call(pn_rate *r, const void *d_in, int fmt, float *d_out48, const int32_t *ids, int n) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   if (rate_aligned(d_in, d_out48)) return -1;
@@ -493,9 +606,18 @@ extern "C" int pn_rate_mix_f32(pn_rate *r, const float *d_in48, float *d_out48, 
   if (rate_rows(r, ids, n_ids, &rows)) return -1;
   return rate_mix(r, d_in48, d_out48, rows);
 }
+extern "C" int pn_rate_plc_f32(pn_rate *r, float *d_x48, const int32_t *ids, int n_ids) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (!r->plc) { pn_set_error("packet-loss concealment is off (pn_rate_set_plc)"); return -1; }
+  if (rate_aligned(d_x48, d_x48)) return -1;
+  PN_ON_DEVICE(r->c);
+  RateRows rows;
+  if (rate_rows(r, ids, n_ids, &rows)) return -1;
+  return rate_plc(r, d_x48, rows);
+}
 
 // ---- one whole frame -----------------------------------------------------------------------------------------------------------
-// up into x48, the engine's float frame from x48 into y48 (all streams, or the listed ones through the context's own active
+// up into x48, while packet-loss concealment is on the concealer in place on x48, the engine's float frame from x48 into y48 (all streams, or the listed ones through the context's own active
 // set), down from y48 — or, while a stream is in a conference, the mix from y48 into o48 and down from o48.  A frame the engine refuses returns -1 with its error kept; the up kernel has then advanced its tails
 // and the down kernel has not, which is why the header asks for a reset of both objects before reuse.
 // rate_frame: the launches alone — the caller is on the context's device and has checked the rows and, when active, the list
@@ -503,11 +625,27 @@ extern "C" int pn_rate_mix_f32(pn_rate *r, const float *d_in48, float *d_out48, 
 static int rate_frame(pn_rate *r, const void *d_in, void *d_out, float *d_gr, int fmt, bool active, const int32_t *ids, int n) {
   pn_ctx *c = r->c;
   RateRows rows = {NULL, c->B};
+  // marked streams: the up-conversion runs over "advancing minus lost" — its own staged list, in front of the frame's — so a lost
+  // stream's input row is never read and its tail stays.  Nobody marked, or no marked stream advancing: the launch of always
+  bool up_done = false;
+  if (r->plc && !r->lost_ids.empty()) {
+    r->up_ids.clear();
+    if (active) { for (int i = 0; i < n; i++) if (!r->lost_mark[ids[i]]) r->up_ids.push_back(ids[i]); }
+    else for (int s = 0; s < c->B; s++) if (!r->lost_mark[s]) r->up_ids.push_back(s);
+    const int nu = (int)r->up_ids.size();
+    if (nu != (active ? n : c->B)) {
+      RateRows up = {NULL, nu};
+      if (nu > 0 && !(up.d_ids = stage_ids(c, r->up_ids.data(), nu))) return -1;
+      if (nu > 0 && rate_up(r, d_in, fmt, r->x48, up)) return -1;
+      up_done = true;
+    }
+  }
   if (active) {                                      // (an empty list is legal, as for pn_process_*_active: nobody advances)
     rows.n = n;
     if (n > 0 && !(rows.d_ids = stage_ids(c, ids, n))) return -1;
   }
-  if (rate_up(r, d_in, fmt, r->x48, rows)) return -1;
+  if (!up_done && rate_up(r, d_in, fmt, r->x48, rows)) return -1;
+  if (r->plc && rate_plc(r, r->x48, rows)) return -1;
   if (active ? pn_process_f32_active(c, r->x48, r->y48, d_gr, ids, n) : pn_process_f32(c, r->x48, r->y48, d_gr)) return -1;
   const float *o = r->y48;
   if (r->in_conf > 0 || !mix_plain(r)) {             // somebody is in a conference (or a mix setting is on): the mix writes every advancing stream's row of o48
@@ -601,9 +739,9 @@ extern "C" int pn_rate_submit_host_g711_active(pn_rate *r, const uint8_t *h_in, 
 // ---- timing the kernels --------------------------------------------------------------------------------------------------------
 extern "C" int pn_rate_set_profiling(pn_rate *r, int enable) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
-  if (enable && r->event_pool.size() < 768) {         // up to three scopes a frame: enough for 128 frames between two reads; created outside any timed region
+  if (enable && r->event_pool.size() < 1024) {        // up to four scopes a frame: enough for 128 frames between two reads; created outside any timed region
     PN_ON_DEVICE(r->c);
-    while (r->event_pool.size() < 768) { hipEvent_t e; PN_HIP_CHECK(hipEventCreate(&e)); r->event_pool.push_back(e); }
+    while (r->event_pool.size() < 1024) { hipEvent_t e; PN_HIP_CHECK(hipEventCreate(&e)); r->event_pool.push_back(e); }
   }
   r->profiling = enable != 0;
   return 0;
@@ -614,7 +752,7 @@ extern "C" int pn_rate_kernel_time(pn_rate *r, const char *name, double *total_m
   if (rate_flush_events(r)) return -1;
   for (int i = 0; i < RF_COUNT; i++)
     if (!strcmp(name, kRateFamily[i])) { if (total_ms) *total_ms = r->fam_ms[i]; if (launches) *launches = r->fam_n[i]; return 0; }
-  pn_set_error("unknown converter kernel '%s' (rate_up, rate_down, rate_mix)", name);
+  pn_set_error("unknown converter kernel '%s' (rate_up, rate_down, rate_mix, rate_plc)", name);
   return -1;
 }
 extern "C" int pn_rate_reset_profile(pn_rate *r) {
@@ -635,6 +773,7 @@ static int rate_records_host(pn_rate *r, int rate, bool import, const int32_t *i
     const int *d_ids = stage_ids(c, ids, n);
     if (!d_ids) return -1;
     pn_launch_rate_records(c->stream, f, rate, d_ids, n, r->tail_up, r->tail_down, r->td, d, import ? 1 : 0);
+    if (import) plc_zero_rows(r, d_ids, n);          // the slot is now another stream: it starts with an empty history
     if (hipGetLastError() != hipSuccess) { pn_set_error(import ? "record scatter launch failed" : "record gather launch failed"); return -1; }
     return 0;
   });
@@ -680,6 +819,7 @@ static int rate_records_dev(pn_rate *r, bool import, const int32_t *ids, int n, 
   if (!d) return -1;
   pn_launch_rate_records_dev(c->stream, d, n, r->mixed ? r->factors : NULL, r->f, r->tail_up, r->tail_down, r->td, d_records,
                              (int)(pn_rate_record_stride(r) / 4), d_status, import ? 1 : 0);
+  if (import) plc_zero_rows(r, d, n);                // the slot is now another stream: it starts with an empty history, whatever its record's status
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
