@@ -533,7 +533,7 @@ int pn_rate_export_streams(pn_rate *r, const int32_t *ids, int n, void *d_record
 int pn_rate_import_streams(pn_rate *r, const int32_t *ids, int n, const void *d_records, int32_t *d_status);
 /* Timing of the converter's two kernels inside a frame: HIP events around their launches, like pn_ctx_set_profiling but owned by
    the converter (the context's family list does not change).  Off by default; off, no event is created or recorded.  name:
-   "rate_up" | "rate_down" | "rate_mix" (the conference mix, below) | "rate_plc" (packet-loss concealment, below).  pn_rate_kernel_time synchronises the context's stream. */
+   "rate_up" | "rate_down" | "rate_mix" (the conference mix, below) | "rate_plc" (packet-loss concealment, below) | "rate_agc" (automatic level control, below).  pn_rate_kernel_time synchronises the context's stream. */
 int pn_rate_set_profiling(pn_rate *r, int enable);
 int pn_rate_kernel_time(pn_rate *r, const char *name, double *total_ms, int64_t *launches);
 int pn_rate_reset_profile(pn_rate *r);
@@ -856,6 +856,105 @@ int pn_rate_plc_f32(pn_rate *r, float *d_x48, const int32_t *ids, int n_ids);
 int pn_rate_set_plc_report(pn_rate *r, int enable);
 int pn_rate_read_plc_report(pn_rate *r, void *h_report);
 int pn_rate_read_plc_report_dev(pn_rate *r, void *d_report);
+
+/* ---- automatic level control: talkers levelled on the GPU ------------------------------------------------------------------------ */
+/* A quiet phone caller and a hot headset otherwise enter a conference at whatever level they arrive: loudest-N ranks raw frame
+   energy, the fp32 sum of several voices clips, and the only lever is the static send gain.  Automatic gain control (AGC) brings each
+   LEVELLED stream's enhanced 48 kHz row towards a target RMS of its own.  It runs in one kernel (csrc/pn_rate_agc.hip) behind the
+   engine — the noise is gone there, so a plain energy gate separates speech from pauses, and every stream is a 48 kHz float row
+   whatever its rate or coding — and in front of the mix or the down-conversion, in place on the engine's output rows, on a pn_rate of
+   any kind.  So the mix, its levels, loudest-N selection and the send gains all see levelled rows; a stream without a conference
+   hears its own levelled output; the engine's frame report (pn_ctx_set_report) and the g|r tap stay about the row BEFORE AGC.
+   OFF by default: a converter that never enables it launches exactly what it launches without this section.  While on, a frame
+   launches the kernel only while at least one stream's target is non-zero (the host keeps that count).
+
+   The rule, with every rounding and summation order, is csrc/pn_agc_rules.h (HIP-free); tests/agc_model.py restates it in numpy
+   float32 and the kernel matches both bit for bit.  Every fp32 operation is singly rounded, no product is contracted into an add,
+   `/` and sqrtf are the correctly rounded ones.  Samples are in the float convention (int16 / 32768).
+   Parameters, one set per converter, PN_AGC_N_PARAMS = 8 floats:
+     0 PN_AGC_MAX_GAIN  Gmax [1, 1024] 16          1 PN_AGC_MIN_GAIN  Gmin [1/1024, 1] 0.125       2 PN_AGC_GATE_RMS theta [0, 1] 0.001
+     3 PN_AGC_ATTACK    (level rising) (0, 1] 0.5  4 PN_AGC_RELEASE   (level falling) (0, 1] 0.05
+     5 PN_AGC_STEP_UP   largest gain ratio per frame [1, 2] 1.0592537 (+0.5 dB)    6 PN_AGC_STEP_DOWN (0, 1] 0.8912509 (-1 dB)
+     7 PN_AGC_CEILING   c (0, 1] 32767/32768
+   Target, one fp32 per stream: T, the wanted RMS in (0, 1]; 0 (also -0.0f), the default of every stream: not levelled.
+   State per stream (16 bytes, allocated by the first enable, never inside a frame): lev, the smoothed frame energy; gain, whose bits
+   0 mean "fresh" and read as 1.0f; adapted, the frames that adapted (saturating); one spare word, always 0.
+   One frame of an advancing stream, y = its 480-sample row from the engine; concealed = PLC filled this frame for it:
+     T == 0:   the row and the state are not touched; the report row is {1.0f, +0.0f, 0, +0.0f}.
+     E:        the energy of y in the mix's order (pn_mix_level): products rounded separately, 120 groups of four from +0.0f in index
+               order, padded to 128, two halves of 64 folded by the xor butterfly 32..1, E = half0[0] + half1[0].
+     p:        max |y[j]| from +0.0f with fmaxf, so a NaN sample is ignored.     Eg = (theta*theta)*480.0f, Tt = (T*T)*480.0f.
+     voiced:   E > Eg && E <= FLT_MAX && !concealed.
+     level:    not voiced: lev' = lev.  Voiced, lev == 0: lev' = E.  Voiced otherwise: a = E > lev ? attack : release, d = E - lev,
+               t = a*d, lev' = lev + t.
+     desired:  voiced: g* = sqrtf(Tt / lev'), then g* > Gmax -> Gmax (AT_MAX), then g* < Gmin -> Gmin (AT_MIN).  Otherwise g* = g0, the
+               stored gain (1.0f when fresh): a pause, a concealed frame and a row of NaN or inf HOLD the gain.
+     slew:     hi = g0*step_up, lo = g0*step_down, g1 = fminf(fmaxf(g*, lo), hi).
+     limiter:  m = fmaxf(g0, g1); if p <= FLT_MAX && p*m > c (LIMITED): gl = fmaxf(c / p, Gmin), g0' = fminf(g0, gl),
+               g1' = fminf(g1, gl); otherwise g0' = g0, g1' = g1.  A row whose peak exceeds c / Gmin is beyond rescue and CLIPS.
+     apply:    w_j = (float)(2j+1) / 960.0f, d = g1' - g0', out[j] = y[j] * (g0' + w_j*d): one product, one add, one product, none
+               fused.  With g0' == g1' == 1.0f the row keeps its bits, -0.0 included.
+     state:    lev = lev', gain = g1', adapted += voiced.
+
+   pn_rate_set_agc(r, enable): the first enable allocates and zeroes the state and the target table; a frame never allocates.
+     Enabling again after a disable zeroes every stream's state (the frames of the pause are missing from the levels); targets and
+     parameters stay.  While off nothing new is launched or read.
+   pn_rate_set_agc_params(r, params[8]) / pn_rate_get_agc_params: one set for the converter, from the next frame submitted on (they
+     travel as an argument of every launch, so they are ordered like one).  Refused with -1, nothing changed: NaN or a value outside
+     its range, pn_last_error naming the FIRST bad index.  Host only: pn_agc_default_params(params[8]), pn_agc_params_check(params[8]).
+   pn_rate_set_stream_agc_targets(r, ids, n, targets) / pn_rate_get_stream_agc_targets / pn_rate_agc_targets_check(targets, n): the id
+     list rules of pn_rate_set_stream_mix_gains (distinct ids in range, the first offender named, n == 0 a no-op); every target 0 or in
+     (0, 1], NaN refused.  Asynchronous on the context's stream and ordered against frames exactly like the mix gains, on the pipelined
+     path too.  It changes the target only; the state stays.  Refused while AGC is off.
+   pn_rate_agc_f32(r, d_y48, ids, n_ids): the kernel on its own, in place on [n_streams][480] float rows at a 16-byte aligned device
+     address, ids as for pn_rate_up_*; nobody counts as concealed.  Refused while AGC is off.
+   pn_agc_frame(params, target, state4, row_in480, row_out480, concealed) -> flags, or -1 for a bad argument: host only, the rule above
+     on one row (row_out may be row_in); state4: the four state words, read and written.
+   pn_rate_kernel_time takes "rate_agc".
+   AGC report (optional; pn_rate_set_agc_report, pn_rate_read_agc_report synchronising, pn_rate_read_agc_report_dev asynchronous on
+     the context's stream; -1 while off): PN_AGC_REPORT_WORDS = 4 little-endian 32-bit words per stream, [n_streams][4], written for
+     every stream that advances in a frame that launches the kernel:
+     word 0  f32 g1'     the gain at the row's end, the stored one
+     word 1  f32 lev'    the smoothed energy
+     word 2  u32 flags   PN_AGC_ON the stream is levelled, PN_AGC_ADAPTED the frame was voiced, PN_AGC_LIMITED the limiter acted,
+                         PN_AGC_AT_MAX / PN_AGC_AT_MIN the desired gain was clamped, PN_AGC_HELD_LOST the frame was concealed
+     word 3  f32 p       the row's peak before the gain
+   Lifecycle.  pn_rate_reset zeroes the AGC state of every stream; pn_rate_reset_streams, pn_rate_set_stream_rates and both import
+   forms (pn_rate_import_streams, pn_rate_import_streams_host) that of the listed slots.  A stream that does not advance keeps its
+   state.  Targets, parameters and the switches are settings that survive all of those.  Records do not carry the AGC state; their
+   format and sizes are untouched.  With PLC on, a stream is concealed in the frame whose marks the concealer consumed; once in 2^32
+   frames, when the concealer's tick wraps, that frame's concealed streams count as received.
+   NOT provided: a limiter on the mix OUTPUT (a sum of levelled voices still clips: turn saturation on); targets in dBFS; AGC state in
+   the records; AGC without a converter; loudness weighting (K-weighting); any measurement of perceived quality. */
+#define PN_AGC_N_PARAMS 8
+#define PN_AGC_MAX_GAIN 0
+#define PN_AGC_MIN_GAIN 1
+#define PN_AGC_GATE_RMS 2
+#define PN_AGC_ATTACK 3
+#define PN_AGC_RELEASE 4
+#define PN_AGC_STEP_UP 5
+#define PN_AGC_STEP_DOWN 6
+#define PN_AGC_CEILING 7
+#define PN_AGC_REPORT_WORDS 4
+#define PN_AGC_ON 1
+#define PN_AGC_ADAPTED 2
+#define PN_AGC_LIMITED 4
+#define PN_AGC_AT_MAX 8
+#define PN_AGC_AT_MIN 16
+#define PN_AGC_HELD_LOST 32
+int pn_agc_default_params(float *params8);                /* host only */
+int pn_agc_params_check(const float *params8);            /* host only */
+int pn_agc_frame(const float *params8, float target, uint32_t *state4, const float *row_in480, float *row_out480, int concealed);   /* host only */
+int pn_rate_agc_targets_check(const float *targets, int n);   /* host only */
+int pn_rate_set_agc(pn_rate *r, int enable);
+int pn_rate_set_agc_params(pn_rate *r, const float *params8);
+int pn_rate_get_agc_params(const pn_rate *r, float *params8);
+int pn_rate_set_stream_agc_targets(pn_rate *r, const int32_t *ids, int n, const float *targets);
+int pn_rate_get_stream_agc_targets(const pn_rate *r, float *h_targets);
+int pn_rate_agc_f32(pn_rate *r, float *d_y48, const int32_t *ids, int n_ids);
+int pn_rate_set_agc_report(pn_rate *r, int enable);
+int pn_rate_read_agc_report(pn_rate *r, void *h_report);
+int pn_rate_read_agc_report_dev(pn_rate *r, void *d_report);
 
 const char *pn_last_error(void);
 const char *pn_version(void);

@@ -35,6 +35,13 @@ PLC_HIST, PLC_P_MIN, PLC_P_MAX = 1920, 240, 720
 PLC_REPORT_WORDS = 4
 PLC_CONCEALED, PLC_CROSSFADE, PLC_SILENT = 1, 2, 4                  # its flags
 PLC_REPORT_DTYPE = np.dtype([("flags", "<u4"), ("period", "<u4"), ("run", "<u4"), ("lost", "<u4")])
+# automatic level control (include/percepnet_hip.h "automatic level control"): PN_AGC_*
+AGC_N_PARAMS = 8
+AGC_MAX_GAIN, AGC_MIN_GAIN, AGC_GATE_RMS, AGC_ATTACK, AGC_RELEASE, AGC_STEP_UP, AGC_STEP_DOWN, AGC_CEILING = range(8)   # parameter indices
+AGC_REPORT_WORDS = 4
+AGC_ON, AGC_ADAPTED, AGC_LIMITED, AGC_AT_MAX, AGC_AT_MIN, AGC_HELD_LOST = 1, 2, 4, 8, 16, 32   # its flags
+AGC_REPORT_DTYPE = np.dtype([("gain", "<f4"), ("level", "<f4"), ("flags", "<u4"), ("peak", "<f4")])
+AGC_STATE_DTYPE = np.dtype([("level", "<f4"), ("gain", "<f4"), ("adapted", "<u4"), ("spare", "<u4")])   # the four state words of agc_frame
 # per-stream frame report (include/percepnet_hip.h pn_ctx_set_report): one record of PN_REPORT_WORDS 32-bit words per stream
 REPORT_WORDS = 8
 REPORT_DTYPE = np.dtype([("in_peak", "<f4"), ("in_energy", "<f4"), ("out_peak", "<f4"), ("out_energy", "<f4"), ("gain_mean", "<f4"),
@@ -216,6 +223,18 @@ def load_library():
         L.pn_rate_plc_f32.argtypes = [_vp, _vp, _vp, ctypes.c_int]
         for name in ("pn_rate_read_plc_report", "pn_rate_read_plc_report_dev"):
             getattr(L, name).argtypes = [_vp, _vp]
+    if hasattr(L, "pn_rate_set_agc"):
+        for name in ("pn_agc_default_params", "pn_agc_params_check"):
+            getattr(L, name).argtypes = [_vp]
+        L.pn_agc_frame.argtypes = [_vp, ctypes.c_float, _vp, _vp, _vp, ctypes.c_int]
+        L.pn_rate_agc_targets_check.argtypes = [_vp, ctypes.c_int]
+        for name in ("pn_rate_set_agc", "pn_rate_set_agc_report"):
+            getattr(L, name).argtypes = [_vp, ctypes.c_int]
+        for name in ("pn_rate_set_agc_params", "pn_rate_get_agc_params", "pn_rate_get_stream_agc_targets", "pn_rate_read_agc_report",
+                     "pn_rate_read_agc_report_dev"):
+            getattr(L, name).argtypes = [_vp, _vp]
+        L.pn_rate_set_stream_agc_targets.argtypes = [_vp, _vp, ctypes.c_int, _vp]
+        L.pn_rate_agc_f32.argtypes = [_vp, _vp, _vp, ctypes.c_int]
     if hasattr(L, "pn_host_pipeline_prepare"):
         L.pn_host_pipeline_prepare.argtypes = [_vp]
     L.pn_ctx_debug_copy.restype = ctypes.c_longlong
@@ -665,6 +684,43 @@ def plc_gain(m):
     return np.float32(load_library().pn_plc_gain(int(m)))
 
 
+def agc_default_params():
+    """-> float32 [AGC_N_PARAMS]: the level control's default parameters (pn_agc_default_params, host only)."""
+    p = np.empty(AGC_N_PARAMS, np.float32)
+    load_library().pn_agc_default_params(p.ctypes.data)
+    return p
+
+
+def _agc_params(params):
+    p = np.ascontiguousarray(params, dtype=np.float32).ravel()
+    if p.size != AGC_N_PARAMS:
+        raise PercepNetError(f"{p.size} AGC parameters: a set has {AGC_N_PARAMS}")
+    return p
+
+
+def agc_params_check(params):
+    """Raises PercepNetError naming the first parameter that is NaN or outside its range (pn_agc_params_check, host only)."""
+    L = load_library()
+    if L.pn_agc_params_check(_agc_params(params).ctypes.data) != 0:
+        raise PercepNetError(_err(L))
+
+
+def agc_frame(params, target, state, row, concealed=False):
+    """One frame of the level control on one row of 480 samples (pn_agc_frame, host only).  state: AGC_STATE_DTYPE scalar array
+    (np.zeros((), AGC_STATE_DTYPE) is fresh), updated IN PLACE -> (float32 [480] the levelled row, the flags)."""
+    L = load_library()
+    y = np.ascontiguousarray(row, dtype=np.float32).ravel()
+    if y.size != 480:
+        raise PercepNetError(f"a row of {y.size} samples: the level control takes 480")
+    if not isinstance(state, np.ndarray) or state.dtype != AGC_STATE_DTYPE or state.size != 1 or not state.flags.c_contiguous or not state.flags.writeable:
+        raise PercepNetError("state: one writable AGC_STATE_DTYPE record")
+    out = np.empty(480, np.float32)
+    flags = L.pn_agc_frame(_agc_params(params).ctypes.data, float(np.float32(target)), state.ctypes.data, y.ctypes.data, out.ctypes.data, 1 if concealed else 0)
+    if flags < 0:
+        raise PercepNetError(_err(L))
+    return out, int(flags)
+
+
 class RateConverter:
     """8, 16, 24 or 32 kHz streams through a 48 kHz Context (pn_rate): a converter beside `ctx` for all of its streams at ONE rate.
     It borrows the context (device, n_streams, HIP stream): close the converter before the context."""
@@ -877,6 +933,55 @@ class RateConverter:
         """The same into device memory [n_streams][4] words, asynchronous on the context's stream (pn_rate_read_plc_report_dev)."""
         self._chk(self.L.pn_rate_read_plc_report_dev(self.h, d_report))
 
+    # automatic level control: a levelled stream's enhanced 48 kHz row is brought towards its target RMS, between the engine and the mix
+    def set_agc(self, on):
+        """Automatic level control on or off (pn_rate_set_agc); the first enable allocates the per-stream state and targets."""
+        self._chk(self.L.pn_rate_set_agc(self.h, 1 if on else 0))
+
+    def set_agc_params(self, params):
+        """The converter's AGC_N_PARAMS parameters from the next frame on (pn_rate_set_agc_params); refused as a whole, naming the
+        first that is NaN or outside its range."""
+        self._chk(self.L.pn_rate_set_agc_params(self.h, _agc_params(params).ctypes.data))
+
+    def agc_params(self):
+        """-> float32 [AGC_N_PARAMS] as last set (pn_rate_get_agc_params); agc_default_params() on a new converter."""
+        p = np.empty(AGC_N_PARAMS, np.float32)
+        self._chk(self.L.pn_rate_get_agc_params(self.h, p.ctypes.data))
+        return p
+
+    def set_stream_agc_targets(self, ids, targets):
+        """Streams `ids` are levelled towards the RMS `targets` (in (0, 1]; 0 = not levelled) from the next frame on
+        (pn_rate_set_stream_agc_targets): asynchronous, ordered like set_stream_mix_gains; the state stays.  Refused while AGC is off."""
+        a, n = self._ids(ids)
+        w = np.ascontiguousarray(np.asarray(targets, dtype=np.float32).ravel())
+        if w.size != n:
+            raise PercepNetError(f"{w.size} targets for {n} streams")
+        self._chk(self.L.pn_rate_set_stream_agc_targets(self.h, a.ctypes.data, n, w.ctypes.data))
+
+    def stream_agc_targets(self):
+        """-> float32 [n_streams]: the targets as last set (pn_rate_get_stream_agc_targets); 0 everywhere on a new converter."""
+        w = np.empty(self.n_streams, np.float32)
+        self._chk(self.L.pn_rate_get_stream_agc_targets(self.h, w.ctypes.data))
+        return w
+
+    def agc_f32_dev(self, d_y48, ids=None):
+        """The level control on its own, in place on device rows [n_streams][480] float (pn_rate_agc_f32); nobody counts as concealed."""
+        a, n = self._ids(ids)
+        self._chk(self.L.pn_rate_agc_f32(self.h, d_y48, a.ctypes.data if a is not None else None, n))
+
+    def set_agc_report(self, on):
+        self._chk(self.L.pn_rate_set_agc_report(self.h, 1 if on else 0))
+
+    def read_agc_report(self):
+        """-> AGC_REPORT_DTYPE [n_streams]: the records of the last frame that ran the level control (pn_rate_read_agc_report, synchronising)."""
+        rep = np.empty(self.n_streams, AGC_REPORT_DTYPE)
+        self._chk(self.L.pn_rate_read_agc_report(self.h, rep.ctypes.data))
+        return rep
+
+    def read_agc_report_dev(self, d_report):
+        """The same into device memory [n_streams][4] words, asynchronous on the context's stream (pn_rate_read_agc_report_dev)."""
+        self._chk(self.L.pn_rate_read_agc_report_dev(self.h, d_report))
+
     # one whole frame, device pointers: [n_streams][frame] in and out at the low rate, d_gr [n_streams][68] or None
     def process_f32_dev(self, d_in, d_out, d_gr=None, ids=None):
         if ids is None:
@@ -964,7 +1069,7 @@ class RateConverter:
 
     def kernel_times(self, names=("rate_up", "rate_down")):
         """-> {"rate_up": (total_ms, launches), "rate_down": (...)}; names: which kernels ("rate_mix" is the conference mix,
-        "rate_plc" the packet-loss concealer)"""
+        "rate_plc" the packet-loss concealer, "rate_agc" the level control)"""
         out = {}
         for name in names:
             ms = ctypes.c_double()

@@ -116,6 +116,12 @@ void pn_launch_rate_conf_rows(hipStream_t st, const int *d_touched, const int *d
 // [n_streams][1920], q [n_streams][720], meta [n_streams][4] words; d_report [n_streams][4] words or NULL
 void pn_launch_rate_plc(hipStream_t st, int n_rows, const int *d_ids, const uint32_t *d_lost, uint32_t tick, float *x48, float *hist, float *q,
                         void *meta, void *d_report);
+// automatic level control (pn_rate_agc.hip; the rule pn_agc_rules.h): rows d_ids[0..n_rows) or, with d_ids == NULL, streams 0..n_rows of
+// y48 [.][480], in place.  d_targets [n_streams]: +0.0 = the stream is not levelled; a stream whose d_lost word equals tick was concealed
+// this frame (d_lost == NULL: nobody); params: the converter's PN_AGC_N_PARAMS floats on the HOST, passed by value.  State [n_streams][4]
+// words; d_report [n_streams][4] words or NULL
+void pn_launch_rate_agc(hipStream_t st, int n_rows, const int *d_ids, const float *d_targets, const uint32_t *d_lost, uint32_t tick, const float *params,
+                        float *y48, void *state, void *d_report);
 // ---- the network launchers (pn_nn*.hip) -----------------------------------------------------------------------------------------
 // Device pointers of a layer's biases and weights in the formats of pn_network.h: raw (w, rw), packed fp32 or fp16 planes (wp,
 // rwp), the 16x16x4 packing of a narrow layer (wq)

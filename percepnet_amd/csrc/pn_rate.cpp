@@ -11,9 +11,11 @@
 #include "pn_conf.h"         // conferences: what an id must be, the table after a change, the members in ascending order
 #include "pn_mix_rules.h"    // loudest-N, send gains, hold: what the settings must be; the level and the selection for the host
 #include "pn_plc_rules.h"    // packet-loss concealment: the signal rule for the host, the sizes of the state
+#include "pn_agc_rules.h"    // automatic level control: the rule for the host, what parameters and targets must be
 #include <string>
 #include <vector>
 
+enum { RF_UP, RF_DOWN, RF_MIX, RF_PLC, RF_AGC, RF_COUNT };   // the timed kernels (pn_rate_kernel_time), named by kRateFamily below
 struct pn_rate {
   pn_ctx *c;                    // borrowed: device, B, stream, the id ring, the saturate setting
   int rate, f, n, td;           // rate_hz, its factor (pn_rate_design.h: L, or PN_RATE_F_3_2 for 32000), samples per row, words per down tail row (2D / M).  Mixed: 0, 0, 480, 192
@@ -64,6 +66,15 @@ struct pn_rate {
   uint32_t *d_plc_lost = NULL, plc_tick = 1;          // [B]
   std::vector<uint8_t> lost_mark;                     // [B]
   std::vector<int32_t> lost_ids, up_ids;              // the marked streams; a frame's "advancing minus lost"
+  // automatic level control (pn_rate_set_agc; the rule pn_agc_rules.h): SETTINGS — the switch, the converter's parameters, a target per
+  // stream as last set (host) and on the device, written in stream order through the id ring like the send gains — and the state, four
+  // words per stream.  The device side exists from the first enable on.  agc_on == 0: a frame launches nothing of it
+  bool agc = false, agc_report = false;
+  float agc_params[PN_AGC_N_PARAMS];
+  std::vector<float> agc_targets;                     // [B], 0
+  int agc_on = 0;                                     // streams whose target is not 0
+  float *d_agc_targets = NULL;                        // [B]
+  void *d_agc_state = NULL, *d_agc_report = NULL;     // [B][4] words each
   std::vector<void *> allocs;
   // timing of the kernels (pn_rate_set_profiling): HIP events around their launches, like the context's families but owned
   // here; while it is off no event exists and none is recorded
@@ -71,10 +82,9 @@ struct pn_rate {
   struct Ev { int fam; hipEvent_t a, b; };
   std::vector<Ev> events;
   std::vector<hipEvent_t> event_pool;
-  double fam_ms[4] = {0, 0, 0, 0}; int64_t fam_n[4] = {0, 0, 0, 0};
+  double fam_ms[RF_COUNT] = {}; int64_t fam_n[RF_COUNT] = {};
 };
-enum { RF_UP, RF_DOWN, RF_MIX, RF_PLC, RF_COUNT };
-static const char *const kRateFamily[RF_COUNT] = {"rate_up", "rate_down", "rate_mix", "rate_plc"};
+static const char *const kRateFamily[RF_COUNT] = {"rate_up", "rate_down", "rate_mix", "rate_plc", "rate_agc"};
 struct RateScope {
   pn_rate *r; int fam; hipEvent_t a, b; bool on;
   RateScope(pn_rate *r_, int fam_) : r(r_), fam(fam_), on(r_->profiling) {
@@ -131,6 +141,12 @@ extern "C" int pn_mix_select(const float *levels, int k, int n_max, uint8_t *sel
 extern "C" int pn_plc_pitch(const float *hist1920) { if (!hist1920) { pn_set_error("NULL argument"); return -1; } return pn_plc_pitch_host(hist1920); }
 extern "C" int pn_plc_period(const float *hist1920, int P, float *q) { return pn_plc_period_host(hist1920, P, q); }
 extern "C" float pn_plc_gain(int64_t m) { return pn_plc_gain_host(m); }
+extern "C" int pn_agc_default_params(float *params8) { if (!params8) { pn_set_error("NULL argument"); return -1; } pn_agc_default_params_host(params8); return 0; }
+extern "C" int pn_agc_params_check(const float *params8) { return pn_agc_params_check_host(params8); }
+extern "C" int pn_agc_frame(const float *params8, float target, uint32_t *state4, const float *row_in480, float *row_out480, int concealed) {
+  return pn_agc_frame_host(params8, target, state4, row_in480, row_out480, concealed);
+}
+extern "C" int pn_rate_agc_targets_check(const float *targets, int n) { return pn_agc_targets_list_check(targets, n); }
 
 // ---- lifecycle ---------------------------------------------------------------------------------------------------------------
 extern "C" void pn_rate_destroy(pn_rate *r) {
@@ -155,6 +171,7 @@ extern "C" pn_rate *pn_rate_create(pn_ctx *c, int rate_hz) {
   r->c = c; r->rate = rate_hz; r->f = f; r->n = pn_rate_factor_frame(f); r->td = pn_rate_down_tail(f); r->bytes = 0;
   r->mixed = false; r->factors = NULL; r->h_rows = NULL; r->laws.assign((size_t)c->B, PN_G711_ULAW); r->confs.assign((size_t)c->B, PN_CONF_NONE);
   r->gains.assign((size_t)c->B, 1.0f); r->caps.assign((size_t)c->B, 0);
+  r->agc_targets.assign((size_t)c->B, 0.0f); pn_agc_default_params_host(r->agc_params);
   const size_t B = (size_t)c->B, nt = 2 * (size_t)PN_RATE_TAPS * pn_rate_factor_L(f) + 1;
   float h[2][PN_RATE_MAX_TAPS];
   auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
@@ -185,6 +202,7 @@ extern "C" pn_rate *pn_rate_create_mixed(pn_ctx *c, const int32_t *rates_hz) {
   r->c = c; r->rate = 0; r->f = 0; r->n = PN_RATE_MIXED_ROW; r->td = pn_rate_down_tail(PN_RATE_MAX_L); r->bytes = 0;
   r->mixed = true; r->factors = NULL; r->h_rows = NULL; r->laws.assign((size_t)c->B, PN_G711_ULAW); r->confs.assign((size_t)c->B, PN_CONF_NONE);
   r->gains.assign((size_t)c->B, 1.0f); r->caps.assign((size_t)c->B, 0);
+  r->agc_targets.assign((size_t)c->B, 0.0f); pn_agc_default_params_host(r->agc_params);
   const size_t B = (size_t)c->B;
   if (rates_hz) r->rates.assign(rates_hz, rates_hz + B); else r->rates.assign(B, 48000);
   static const int kF[4] = {6, 3, 2, PN_RATE_F_3_2};   // (the order of pn_rate.hip rt_taps_offset; the h of 32000 is the table of 3 and is not staged twice)
@@ -229,6 +247,8 @@ static void plc_zero_rows(pn_rate *r, const int *d, int n) {
   pn_launch_zero_rows(r->c->stream, r->d_plc_q, PN_PLC_P_MAX, PN_PLC_P_MAX, 1, 0, d, n);
   pn_launch_zero_rows(r->c->stream, r->d_plc_meta, 4, 4, 1, 0, d, n);
 }
+// the AGC state of the staged streams d[0..n) goes to zero: no level, a fresh gain (nothing while AGC was never enabled)
+static void agc_zero_rows(pn_rate *r, const int *d, int n) { pn_launch_zero_rows(r->c->stream, r->d_agc_state, 4, 4, 1, 0, d, n); }
 // A rate change of the listed streams, asynchronous and ordered like pn_rate_reset_streams: the ids and the new factors go
 // through the context's id ring in one copy, one launch writes the factors, two zero the tails.
 extern "C" int pn_rate_set_stream_rates(pn_rate *r, const int32_t *ids, int n, const int32_t *rates_hz) {
@@ -246,6 +266,7 @@ extern "C" int pn_rate_set_stream_rates(pn_rate *r, const int32_t *ids, int n, c
   pn_launch_zero_rows(r->c->stream, r->tail_down, r->td, r->td, 1, 0, d, n);
   pn_launch_zero_rows(r->c->stream, r->d_level, 1, 1, 1, 0, d, n);       // (nothing while no level exists)
   plc_zero_rows(r, d, n);
+  agc_zero_rows(r, d, n);
   PN_HIP_CHECK(hipGetLastError());
   for (int i = 0; i < n; i++) r->rates[ids[i]] = rates_hz[i];
   return 0;
@@ -489,6 +510,73 @@ static int plc_report_copy(pn_rate *r, void *dst, hipMemcpyKind kind) {
 extern "C" int pn_rate_read_plc_report(pn_rate *r, void *h_report) { return plc_report_copy(r, h_report, hipMemcpyDeviceToHost); }
 extern "C" int pn_rate_read_plc_report_dev(pn_rate *r, void *d_report) { return plc_report_copy(r, d_report, hipMemcpyDeviceToDevice); }
 
+// ---- automatic level control (include/percepnet_hip.h; the rule pn_agc_rules.h; the kernel pn_rate_agc.hip) -----------------------
+extern "C" int pn_rate_set_agc(pn_rate *r, int enable) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  PN_ON_DEVICE(r->c);
+  if (enable && !r->d_agc_state) {
+    pn_ctx *c = r->c;
+    const size_t B = (size_t)c->B;
+    float *targets = NULL; void *state = NULL;
+    auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
+    if (alloc((void **)&targets, B * 4, true) || alloc(&state, B * PN_AGC_STATE_BYTES, true)) return -1;
+    r->d_agc_targets = targets; r->d_agc_state = state;
+  } else if (enable && !r->agc) {
+    // on again after a pause: the frames in between are missing from the levels, so every stream starts fresh
+    PN_HIP_CHECK(hipMemsetAsync(r->d_agc_state, 0, (size_t)r->c->B * PN_AGC_STATE_BYTES, r->c->stream));
+  }
+  r->agc = enable != 0;
+  return 0;
+}
+// the parameters travel as an argument of every launch, so a change is ordered like one
+extern "C" int pn_rate_set_agc_params(pn_rate *r, const float *params8) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (pn_agc_params_check_host(params8)) return -1;
+  memcpy(r->agc_params, params8, sizeof(r->agc_params));
+  return 0;
+}
+extern "C" int pn_rate_get_agc_params(const pn_rate *r, float *params8) {
+  if (!r || !params8) { pn_set_error("NULL argument"); return -1; }
+  memcpy(params8, r->agc_params, sizeof(r->agc_params));
+  return 0;
+}
+extern "C" int pn_rate_set_stream_agc_targets(pn_rate *r, const int32_t *ids, int n, const float *targets) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (!r->agc) { pn_set_error("automatic level control is off (pn_rate_set_agc)"); return -1; }
+  if (pn_agc_targets_set_check(r->c->B, ids, n, targets)) return -1;
+  if (n == 0) return 0;
+  std::vector<float> t(targets, targets + n);
+  for (float &v : t) if (v == 0.0f) v = 0.0f;                                   // (-0.0f is 0)
+  PN_ON_DEVICE(r->c);
+  if (mix_set_words(r, ids, n, t.data(), reinterpret_cast<int *>(r->d_agc_targets))) return -1;
+  for (int i = 0; i < n; i++) { r->agc_on += (t[i] != 0.0f) - (r->agc_targets[ids[i]] != 0.0f); r->agc_targets[ids[i]] = t[i]; }
+  return 0;
+}
+extern "C" int pn_rate_get_stream_agc_targets(const pn_rate *r, float *h_targets) {
+  if (!r || !h_targets) { pn_set_error("NULL argument"); return -1; }
+  for (int s = 0; s < r->c->B; s++) h_targets[s] = r->agc_targets[s];
+  return 0;
+}
+extern "C" int pn_rate_set_agc_report(pn_rate *r, int enable) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (enable && !r->d_agc_report) {
+    PN_ON_DEVICE(r->c);
+    if (dev_alloc_into(r->allocs, r->bytes, r->c->stream, &r->d_agc_report, (size_t)r->c->B * PN_AGC_REPORT_WORDS * 4, true)) return -1;
+  }
+  r->agc_report = enable != 0;
+  return 0;
+}
+static int agc_report_copy(pn_rate *r, void *dst, hipMemcpyKind kind) {
+  if (!r || !dst) { pn_set_error("NULL argument"); return -1; }
+  if (!r->agc_report) { pn_set_error("the AGC report is off (pn_rate_set_agc_report)"); return -1; }
+  PN_ON_DEVICE(r->c);
+  PN_HIP_CHECK(hipMemcpyAsync(dst, r->d_agc_report, (size_t)r->c->B * PN_AGC_REPORT_WORDS * 4, kind, r->c->stream));
+  if (kind == hipMemcpyDeviceToHost) PN_HIP_CHECK(hipStreamSynchronize(r->c->stream));
+  return 0;
+}
+extern "C" int pn_rate_read_agc_report(pn_rate *r, void *h_report) { return agc_report_copy(r, h_report, hipMemcpyDeviceToHost); }
+extern "C" int pn_rate_read_agc_report_dev(pn_rate *r, void *d_report) { return agc_report_copy(r, d_report, hipMemcpyDeviceToDevice); }
+
 extern "C" int pn_rate_reset(pn_rate *r) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   PN_ON_DEVICE(r->c);
@@ -500,6 +588,7 @@ extern "C" int pn_rate_reset(pn_rate *r) {
     PN_HIP_CHECK(hipMemsetAsync(r->d_plc_q, 0, (size_t)r->c->B * PN_PLC_P_MAX * 4, r->c->stream));
     PN_HIP_CHECK(hipMemsetAsync(r->d_plc_meta, 0, (size_t)r->c->B * 16, r->c->stream));
   }
+  if (r->d_agc_state) PN_HIP_CHECK(hipMemsetAsync(r->d_agc_state, 0, (size_t)r->c->B * PN_AGC_STATE_BYTES, r->c->stream));
   return 0;
 }
 
@@ -514,6 +603,7 @@ extern "C" int pn_rate_reset_streams(pn_rate *r, const int32_t *ids, int n) {
   pn_launch_zero_rows(r->c->stream, r->tail_down, r->td, r->td, 1, 0, d, n);
   pn_launch_zero_rows(r->c->stream, r->d_level, 1, 1, 1, 0, d, n);
   plc_zero_rows(r, d, n);
+  agc_zero_rows(r, d, n);
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -574,6 +664,16 @@ static int rate_plc(pn_rate *r, float *d_x48, const RateRows &rows) {
   PN_HIP_CHECK(hipGetLastError());
   return plc_drop_marks(r);
 }
+// the level control over the rows, in place; d_lost / tick: the concealer's stamps and the tick it used for this frame (NULL: nobody is concealed)
+static int rate_agc(pn_rate *r, float *d_y48, const RateRows &rows, const uint32_t *d_lost, uint32_t tick) {
+  {
+    RateScope sc(r, RF_AGC);
+    pn_launch_rate_agc(r->c->stream, rows.n, rows.d_ids, r->d_agc_targets, d_lost, tick, r->agc_params, d_y48, r->d_agc_state,
+                       r->agc_report ? r->d_agc_report : NULL);
+  }
+  PN_HIP_CHECK(hipGetLastError());
+  return 0;
+}
 static int rate_up_call(pn_rate *r, const void *d_in, int fmt, float *d_out48, const int32_t *ids, int n) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   if (rate_aligned(d_in, d_out48)) return -1;
@@ -615,10 +715,19 @@ extern "C" int pn_rate_plc_f32(pn_rate *r, float *d_x48, const int32_t *ids, int
   if (rate_rows(r, ids, n_ids, &rows)) return -1;
   return rate_plc(r, d_x48, rows);
 }
+extern "C" int pn_rate_agc_f32(pn_rate *r, float *d_y48, const int32_t *ids, int n_ids) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (!r->agc) { pn_set_error("automatic level control is off (pn_rate_set_agc)"); return -1; }
+  if (rate_aligned(d_y48, d_y48)) return -1;
+  PN_ON_DEVICE(r->c);
+  RateRows rows;
+  if (rate_rows(r, ids, n_ids, &rows)) return -1;
+  return rate_agc(r, d_y48, rows, NULL, 0);
+}
 
 // ---- one whole frame -----------------------------------------------------------------------------------------------------------
 // up into x48, while packet-loss concealment is on the concealer in place on x48, the engine's float frame from x48 into y48 (all streams, or the listed ones through the context's own active
-// set), down from y48 — or, while a stream is in a conference, the mix from y48 into o48 and down from o48.  A frame the engine refuses returns -1 with its error kept; the up kernel has then advanced its tails
+// set), while automatic level control is on and a stream has a target the level control in place on y48, down from y48 — or, while a stream is in a conference, the mix from y48 into o48 and down from o48.  A frame the engine refuses returns -1 with its error kept; the up kernel has then advanced its tails
 // and the down kernel has not, which is why the header asks for a reset of both objects before reuse.
 // rate_frame: the launches alone — the caller is on the context's device and has checked the rows and, when active, the list
 // (pn_ids_check, distinct), which is what lets the pipelined path refuse a list BEFORE the frame takes a pipeline slot.
@@ -645,8 +754,12 @@ static int rate_frame(pn_rate *r, const void *d_in, void *d_out, float *d_gr, in
     if (n > 0 && !(rows.d_ids = stage_ids(c, ids, n))) return -1;
   }
   if (!up_done && rate_up(r, d_in, fmt, r->x48, rows)) return -1;
+  const uint32_t plc_tick_used = r->plc_tick;        // the tick the concealer stamps this frame's lost streams with: rate_plc moves it on
+  const bool concealing = r->plc;
   if (r->plc && rate_plc(r, r->x48, rows)) return -1;
   if (active ? pn_process_f32_active(c, r->x48, r->y48, d_gr, ids, n) : pn_process_f32(c, r->x48, r->y48, d_gr)) return -1;
+  // the level control, while on and somebody has a target: in place on y48, so the mix, its levels and the down-conversion see levelled rows
+  if (r->agc && r->agc_on > 0 && rate_agc(r, r->y48, rows, concealing ? r->d_plc_lost : NULL, plc_tick_used)) return -1;
   const float *o = r->y48;
   if (r->in_conf > 0 || !mix_plain(r)) {             // somebody is in a conference (or a mix setting is on): the mix writes every advancing stream's row of o48
     if (rate_mix(r, r->y48, r->o48, rows)) return -1;
@@ -739,7 +852,7 @@ extern "C" int pn_rate_submit_host_g711_active(pn_rate *r, const uint8_t *h_in, 
 // ---- timing the kernels --------------------------------------------------------------------------------------------------------
 extern "C" int pn_rate_set_profiling(pn_rate *r, int enable) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
-  if (enable && r->event_pool.size() < 1024) {        // up to four scopes a frame: enough for 128 frames between two reads; created outside any timed region
+  if (enable && r->event_pool.size() < 1024) {        // up to five scopes a frame (up, plc, agc, mix, down): enough for 102 frames between two reads; created outside any timed region
     PN_ON_DEVICE(r->c);
     while (r->event_pool.size() < 1024) { hipEvent_t e; PN_HIP_CHECK(hipEventCreate(&e)); r->event_pool.push_back(e); }
   }
@@ -752,7 +865,7 @@ extern "C" int pn_rate_kernel_time(pn_rate *r, const char *name, double *total_m
   if (rate_flush_events(r)) return -1;
   for (int i = 0; i < RF_COUNT; i++)
     if (!strcmp(name, kRateFamily[i])) { if (total_ms) *total_ms = r->fam_ms[i]; if (launches) *launches = r->fam_n[i]; return 0; }
-  pn_set_error("unknown converter kernel '%s' (rate_up, rate_down, rate_mix, rate_plc)", name);
+  pn_set_error("unknown converter kernel '%s' (rate_up, rate_down, rate_mix, rate_plc, rate_agc)", name);
   return -1;
 }
 extern "C" int pn_rate_reset_profile(pn_rate *r) {
@@ -773,7 +886,7 @@ static int rate_records_host(pn_rate *r, int rate, bool import, const int32_t *i
     const int *d_ids = stage_ids(c, ids, n);
     if (!d_ids) return -1;
     pn_launch_rate_records(c->stream, f, rate, d_ids, n, r->tail_up, r->tail_down, r->td, d, import ? 1 : 0);
-    if (import) plc_zero_rows(r, d_ids, n);          // the slot is now another stream: it starts with an empty history
+    if (import) { plc_zero_rows(r, d_ids, n); agc_zero_rows(r, d_ids, n); }   // the slot is now another stream: it starts with an empty history and a fresh gain
     if (hipGetLastError() != hipSuccess) { pn_set_error(import ? "record scatter launch failed" : "record gather launch failed"); return -1; }
     return 0;
   });
@@ -819,7 +932,7 @@ static int rate_records_dev(pn_rate *r, bool import, const int32_t *ids, int n, 
   if (!d) return -1;
   pn_launch_rate_records_dev(c->stream, d, n, r->mixed ? r->factors : NULL, r->f, r->tail_up, r->tail_down, r->td, d_records,
                              (int)(pn_rate_record_stride(r) / 4), d_status, import ? 1 : 0);
-  if (import) plc_zero_rows(r, d, n);                // the slot is now another stream: it starts with an empty history, whatever its record's status
+  if (import) { plc_zero_rows(r, d, n); agc_zero_rows(r, d, n); }   // the slot is now another stream: it starts with an empty history and a fresh gain, whatever its record's status
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
