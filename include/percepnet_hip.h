@@ -533,7 +533,7 @@ int pn_rate_export_streams(pn_rate *r, const int32_t *ids, int n, void *d_record
 int pn_rate_import_streams(pn_rate *r, const int32_t *ids, int n, const void *d_records, int32_t *d_status);
 /* Timing of the converter's two kernels inside a frame: HIP events around their launches, like pn_ctx_set_profiling but owned by
    the converter (the context's family list does not change).  Off by default; off, no event is created or recorded.  name:
-   "rate_up" | "rate_down" | "rate_mix" (the conference mix, below) | "rate_plc" (packet-loss concealment, below) | "rate_agc" (automatic level control, below).  pn_rate_kernel_time synchronises the context's stream. */
+   "rate_up" | "rate_down" | "rate_mix" (the conference mix, below) | "rate_plc" (packet-loss concealment, below) | "rate_agc" (automatic level control, below) | "rate_lim" (the output limiter, below).  pn_rate_kernel_time synchronises the context's stream. */
 int pn_rate_set_profiling(pn_rate *r, int enable);
 int pn_rate_kernel_time(pn_rate *r, const char *name, double *total_ms, int64_t *launches);
 int pn_rate_reset_profile(pn_rate *r);
@@ -924,8 +924,9 @@ int pn_rate_read_plc_report_dev(pn_rate *r, void *d_report);
    state.  Targets, parameters and the switches are settings that survive all of those.  Records do not carry the AGC state; their
    format and sizes are untouched.  With PLC on, a stream is concealed in the frame whose marks the concealer consumed; once in 2^32
    frames, when the concealer's tick wraps, that frame's concealed streams count as received.
-   NOT provided: a limiter on the mix OUTPUT (a sum of levelled voices still clips: turn saturation on); targets in dBFS; AGC state in
-   the records; AGC without a converter; loudness weighting (K-weighting); any measurement of perceived quality. */
+   A sum of levelled voices can still pass full scale: the output limiter (next section) keeps the mix under a ceiling.
+   NOT provided: targets in dBFS; AGC state in the records; AGC without a converter; loudness weighting (K-weighting); any
+   measurement of perceived quality. */
 #define PN_AGC_N_PARAMS 8
 #define PN_AGC_MAX_GAIN 0
 #define PN_AGC_MIN_GAIN 1
@@ -955,6 +956,88 @@ int pn_rate_agc_f32(pn_rate *r, float *d_y48, const int32_t *ids, int n_ids);
 int pn_rate_set_agc_report(pn_rate *r, int enable);
 int pn_rate_read_agc_report(pn_rate *r, void *h_report);
 int pn_rate_read_agc_report_dev(pn_rate *r, void *d_report);
+
+/* ---- output limiter: a mix that does not clip ------------------------------------------------------------------------------------- */
+/* The level control brings every talker to the same RMS and the mix then sums up to 31 of them, so the sum leaves the int16 / G.711
+   range; pn_ctx_set_output_saturate turns the wrap into hard clipping, which is audible.  The output limiter is a per-stream gain
+   as the LAST stage in front of the down-conversion, in one kernel (csrc/pn_rate_lim.hip), in place on the 48 kHz float row the
+   down-conversion is about to read: the mix row of a conference member, every other stream's own (levelled) output, on a pn_rate of
+   any kind.  The whole 10 ms row is in hand there, so the gain looks ahead INSIDE the row without adding delay: it ramps down from
+   the previous row's end value and is at the needed gain exactly at the first sample that needs it.
+   OFF by default: a converter that never sets a ceiling launches exactly what it launches without this section, and a frame launches
+   the kernel only while at least one stream's ceiling is non-zero (the host keeps that count).  The mix report's mix_peak /
+   mix_clipped stay about the mix BEFORE the limiter, the frame report and the g|r tap about the stream's own output; the limiter's
+   report is the new information.
+
+   The rule, with every rounding and the proof of the guarantee, is csrc/pn_lim_rules.h (HIP-free); tests/lim_model.py restates it in
+   numpy float32 and the kernel matches both bit for bit.  Every fp32 operation is singly rounded, `/` is the correctly rounded one.
+   Ceiling, one fp32 per stream: c in [1/1024, 1] (float convention, int16 / 32768); 0 (also -0.0f), the default: not limited.
+   Parameters, one set per converter, PN_LIM_N_PARAMS = 2 floats:
+     0 PN_LIM_RELEASE  R, the largest gain ratio per frame on the way back to 1   [1, 2]   1.0592537 (+0.5 dB, the AGC's step)
+     1 PN_LIM_HOLD     H, the frames the gain is held after an attack             a whole number in [0, 1000]   2
+   State per stream (16 bytes, allocated by the first pn_rate_set_stream_limiter that sets a ceiling, never inside a frame): gain,
+   whose bits 0 mean "fresh" and read as 1.0f; hold, the frames still to hold; limited, the frames whose gain was under 1
+   (saturating); one spare word, always 0.
+   One frame of an advancing stream with c > 0, o = its 480-sample row:
+     g0, h:      the stored gain and hold count.       p = max |o[j]| from +0.0f with fmaxf, so a NaN sample is ignored.
+     non-finite: !(p <= FLT_MAX) (NONFINITE): row and state are not touched.
+     needed:     p > c: q = c / p; if p*q > c, q becomes the float one bit below it; gl = q.  Otherwise gl = 1.0f.
+     attack:     gl < g0 (ATTACK | ACTIVE): k = the first j with |o[j]|*g0 > c, or 480; out[j] = o[j] * (g0 + ((float)j / (float)k) *
+                 (gl - g0)) for j < k and o[j]*gl for j >= k; g1 = gl, h' = H.  The gain steps only when k == 0.
+     otherwise:  h > 0 (HOLDING): g1 = g0, h' = h - 1.  h == 0: g1 = fminf(fminf(g0*R, 1.0f), gl), RELEASING when g1 > g0.  ACTIVE when
+                 g0 < 1 or g1 < 1.  The row is scaled by the level control's ramp between g0 and g1 (out[j] = o[j] * (g0 + w_j*(g1 - g0)),
+                 w_j = (float)(2j+1) / 960.0f); with g0 == g1 == 1.0f the row is NOT written and keeps its bits.
+     state:      gain = g1, hold = h', limited += ACTIVE.
+   Guarantee: for every finite row, |out[j]| <= c as floats for every sample that is not NaN (rounding is monotone; pn_lim_rules.h).
+
+   pn_rate_set_stream_limiter(r, ids, n, ceilings) / pn_rate_get_stream_limiter / pn_rate_limiter_ceilings_check(ceilings, n): the id
+     list rules of pn_rate_set_stream_agc_targets (distinct ids in range, the first offender named, n == 0 a no-op); every ceiling 0
+     or in [1/1024, 1], NaN refused; a refused call changes and launches nothing.  Asynchronous on the context's stream and ordered
+     against frames exactly like the AGC targets, on the pipelined path too.  It changes the ceiling only; the state stays.
+   pn_rate_set_limiter_params(r, params[2]) / pn_rate_get_limiter_params: one set for the converter, from the next frame submitted on
+     (an argument of every launch).  Refused with -1, nothing changed: NaN, a value outside its range, a hold that is no whole
+     number, pn_last_error naming the FIRST bad index.  Host only: pn_lim_default_params(params[2]), pn_lim_params_check(params[2]).
+   pn_rate_lim_f32(r, d_o48, ids, n_ids): the kernel on its own, in place on [n_streams][480] float rows at a 16-byte aligned device
+     address, ids as for pn_rate_up_*.
+   pn_lim_frame(params, ceiling, state4, row_in480, row_out480, report4) -> flags, or -1 for a bad argument: host only, the rule above
+     on one row (row_out may be row_in); state4: the four state words, read and written; report4: the report row, or NULL.
+   pn_rate_kernel_time takes "rate_lim".
+   Limiter report (optional; pn_rate_set_limiter_report, pn_rate_read_limiter_report synchronising, pn_rate_read_limiter_report_dev
+     asynchronous on the context's stream; -1 while off): PN_LIM_REPORT_WORDS = 4 little-endian 32-bit words per stream,
+     [n_streams][4], written for every stream that advances in a frame that launches the kernel:
+     word 0  f32 g1       the gain at the row's end, the stored one (a non-finite row: g0)
+     word 1  f32 p        the row's peak before the gain
+     word 2  u32 flags    PN_LIM_ON the stream is limited, PN_LIM_ATTACK the gain came down inside this row, PN_LIM_HOLDING,
+                          PN_LIM_RELEASING the gain rose, PN_LIM_ACTIVE the row met a gain under 1, PN_LIM_NONFINITE
+     word 3  u32 limited  the frames that were ACTIVE
+     A stream whose ceiling is 0: {1.0f, +0.0f, 0, 0}.
+   Lifecycle.  pn_rate_reset zeroes the limiter state of every stream; pn_rate_reset_streams, pn_rate_set_stream_rates and both import
+   forms that of the listed slots.  A stream that does not advance keeps its state.  Ceilings, parameters and the report switch are
+   settings that survive all of those.  Records do not carry the limiter state; their format and sizes are untouched.
+   NOT provided: look-ahead beyond the row (that would add delay); limiter state in the records; a limiter without a converter; any
+   measurement of perceived quality. */
+#define PN_LIM_N_PARAMS 2
+#define PN_LIM_RELEASE 0
+#define PN_LIM_HOLD 1
+#define PN_LIM_REPORT_WORDS 4
+#define PN_LIM_ON 1
+#define PN_LIM_ATTACK 2
+#define PN_LIM_HOLDING 4
+#define PN_LIM_RELEASING 8
+#define PN_LIM_ACTIVE 16
+#define PN_LIM_NONFINITE 32
+int pn_lim_default_params(float *params2);                /* host only */
+int pn_lim_params_check(const float *params2);            /* host only */
+int pn_lim_frame(const float *params2, float ceiling, uint32_t *state4, const float *row_in480, float *row_out480, uint32_t *report4);   /* host only */
+int pn_rate_limiter_ceilings_check(const float *ceilings, int n);   /* host only */
+int pn_rate_set_stream_limiter(pn_rate *r, const int32_t *ids, int n, const float *ceilings);
+int pn_rate_get_stream_limiter(const pn_rate *r, float *h_ceilings);
+int pn_rate_set_limiter_params(pn_rate *r, const float *params2);
+int pn_rate_get_limiter_params(const pn_rate *r, float *params2);
+int pn_rate_lim_f32(pn_rate *r, float *d_o48, const int32_t *ids, int n_ids);
+int pn_rate_set_limiter_report(pn_rate *r, int enable);
+int pn_rate_read_limiter_report(pn_rate *r, void *h_report);
+int pn_rate_read_limiter_report_dev(pn_rate *r, void *d_report);
 
 const char *pn_last_error(void);
 const char *pn_version(void);

@@ -42,6 +42,13 @@ AGC_REPORT_WORDS = 4
 AGC_ON, AGC_ADAPTED, AGC_LIMITED, AGC_AT_MAX, AGC_AT_MIN, AGC_HELD_LOST = 1, 2, 4, 8, 16, 32   # its flags
 AGC_REPORT_DTYPE = np.dtype([("gain", "<f4"), ("level", "<f4"), ("flags", "<u4"), ("peak", "<f4")])
 AGC_STATE_DTYPE = np.dtype([("level", "<f4"), ("gain", "<f4"), ("adapted", "<u4"), ("spare", "<u4")])   # the four state words of agc_frame
+# output limiter (include/percepnet_hip.h "output limiter"): PN_LIM_*
+LIM_N_PARAMS = 2
+LIM_RELEASE, LIM_HOLD = range(2)                                                # parameter indices
+LIM_REPORT_WORDS = 4
+LIM_ON, LIM_ATTACK, LIM_HOLDING, LIM_RELEASING, LIM_ACTIVE, LIM_NONFINITE = 1, 2, 4, 8, 16, 32   # its flags
+LIM_REPORT_DTYPE = np.dtype([("gain", "<f4"), ("peak", "<f4"), ("flags", "<u4"), ("limited", "<u4")])
+LIM_STATE_DTYPE = np.dtype([("gain", "<f4"), ("hold", "<u4"), ("limited", "<u4"), ("spare", "<u4")])   # the four state words of lim_frame
 # per-stream frame report (include/percepnet_hip.h pn_ctx_set_report): one record of PN_REPORT_WORDS 32-bit words per stream
 REPORT_WORDS = 8
 REPORT_DTYPE = np.dtype([("in_peak", "<f4"), ("in_energy", "<f4"), ("out_peak", "<f4"), ("out_energy", "<f4"), ("gain_mean", "<f4"),
@@ -235,6 +242,17 @@ def load_library():
             getattr(L, name).argtypes = [_vp, _vp]
         L.pn_rate_set_stream_agc_targets.argtypes = [_vp, _vp, ctypes.c_int, _vp]
         L.pn_rate_agc_f32.argtypes = [_vp, _vp, _vp, ctypes.c_int]
+    if hasattr(L, "pn_rate_set_stream_limiter"):
+        for name in ("pn_lim_default_params", "pn_lim_params_check"):
+            getattr(L, name).argtypes = [_vp]
+        L.pn_lim_frame.argtypes = [_vp, ctypes.c_float, _vp, _vp, _vp, _vp]
+        L.pn_rate_limiter_ceilings_check.argtypes = [_vp, ctypes.c_int]
+        L.pn_rate_set_limiter_report.argtypes = [_vp, ctypes.c_int]
+        for name in ("pn_rate_set_limiter_params", "pn_rate_get_limiter_params", "pn_rate_get_stream_limiter", "pn_rate_read_limiter_report",
+                     "pn_rate_read_limiter_report_dev"):
+            getattr(L, name).argtypes = [_vp, _vp]
+        L.pn_rate_set_stream_limiter.argtypes = [_vp, _vp, ctypes.c_int, _vp]
+        L.pn_rate_lim_f32.argtypes = [_vp, _vp, _vp, ctypes.c_int]
     if hasattr(L, "pn_host_pipeline_prepare"):
         L.pn_host_pipeline_prepare.argtypes = [_vp]
     L.pn_ctx_debug_copy.restype = ctypes.c_longlong
@@ -721,6 +739,45 @@ def agc_frame(params, target, state, row, concealed=False):
     return out, int(flags)
 
 
+def lim_default_params():
+    """-> float32 [LIM_N_PARAMS]: the output limiter's default parameters (pn_lim_default_params, host only)."""
+    p = np.empty(LIM_N_PARAMS, np.float32)
+    load_library().pn_lim_default_params(p.ctypes.data)
+    return p
+
+
+def _lim_params(params):
+    p = np.ascontiguousarray(params, dtype=np.float32).ravel()
+    if p.size != LIM_N_PARAMS:
+        raise PercepNetError(f"{p.size} limiter parameters: a set has {LIM_N_PARAMS}")
+    return p
+
+
+def lim_params_check(params):
+    """Raises PercepNetError naming the first parameter that is NaN or outside its range (pn_lim_params_check, host only)."""
+    L = load_library()
+    if L.pn_lim_params_check(_lim_params(params).ctypes.data) != 0:
+        raise PercepNetError(_err(L))
+
+
+def lim_frame(params, ceiling, state, row, want_report=False):
+    """One frame of the output limiter on one row of 480 samples (pn_lim_frame, host only).  state: LIM_STATE_DTYPE scalar array
+    (np.zeros((), LIM_STATE_DTYPE) is fresh), updated IN PLACE -> (float32 [480] the limited row, the flags[, the LIM_REPORT_DTYPE row])."""
+    L = load_library()
+    y = np.ascontiguousarray(row, dtype=np.float32).ravel()
+    if y.size != 480:
+        raise PercepNetError(f"a row of {y.size} samples: the limiter takes 480")
+    if not isinstance(state, np.ndarray) or state.dtype != LIM_STATE_DTYPE or state.size != 1 or not state.flags.c_contiguous or not state.flags.writeable:
+        raise PercepNetError("state: one writable LIM_STATE_DTYPE record")
+    out = np.empty(480, np.float32)
+    rep = np.zeros((), LIM_REPORT_DTYPE)
+    flags = L.pn_lim_frame(_lim_params(params).ctypes.data, float(np.float32(ceiling)), state.ctypes.data, y.ctypes.data, out.ctypes.data,
+                           rep.ctypes.data if want_report else None)
+    if flags < 0:
+        raise PercepNetError(_err(L))
+    return (out, int(flags), rep) if want_report else (out, int(flags))
+
+
 class RateConverter:
     """8, 16, 24 or 32 kHz streams through a 48 kHz Context (pn_rate): a converter beside `ctx` for all of its streams at ONE rate.
     It borrows the context (device, n_streams, HIP stream): close the converter before the context."""
@@ -982,6 +1039,51 @@ class RateConverter:
         """The same into device memory [n_streams][4] words, asynchronous on the context's stream (pn_rate_read_agc_report_dev)."""
         self._chk(self.L.pn_rate_read_agc_report_dev(self.h, d_report))
 
+    # the output limiter: a per-stream gain as the last stage in front of the down-conversion keeps a limited stream's output under its ceiling
+    def set_stream_limiter(self, ids, ceilings):
+        """Streams `ids` are limited to the `ceilings` (in [1/1024, 1]; 0 = not limited) from the next frame on
+        (pn_rate_set_stream_limiter): asynchronous, ordered like set_stream_agc_targets; the state stays."""
+        a, n = self._ids(ids)
+        w = np.ascontiguousarray(np.asarray(ceilings, dtype=np.float32).ravel())
+        if w.size != n:
+            raise PercepNetError(f"{w.size} ceilings for {n} streams")
+        self._chk(self.L.pn_rate_set_stream_limiter(self.h, a.ctypes.data, n, w.ctypes.data))
+
+    def stream_limiter(self):
+        """-> float32 [n_streams]: the ceilings as last set (pn_rate_get_stream_limiter); 0 everywhere on a new converter."""
+        w = np.empty(self.n_streams, np.float32)
+        self._chk(self.L.pn_rate_get_stream_limiter(self.h, w.ctypes.data))
+        return w
+
+    def set_limiter_params(self, params):
+        """The converter's LIM_N_PARAMS parameters from the next frame on (pn_rate_set_limiter_params); refused as a whole, naming the
+        first that is NaN or outside its range."""
+        self._chk(self.L.pn_rate_set_limiter_params(self.h, _lim_params(params).ctypes.data))
+
+    def limiter_params(self):
+        """-> float32 [LIM_N_PARAMS] as last set (pn_rate_get_limiter_params); lim_default_params() on a new converter."""
+        p = np.empty(LIM_N_PARAMS, np.float32)
+        self._chk(self.L.pn_rate_get_limiter_params(self.h, p.ctypes.data))
+        return p
+
+    def lim_f32_dev(self, d_o48, ids=None):
+        """The output limiter on its own, in place on device rows [n_streams][480] float (pn_rate_lim_f32)."""
+        a, n = self._ids(ids)
+        self._chk(self.L.pn_rate_lim_f32(self.h, d_o48, a.ctypes.data if a is not None else None, n))
+
+    def set_limiter_report(self, on):
+        self._chk(self.L.pn_rate_set_limiter_report(self.h, 1 if on else 0))
+
+    def read_limiter_report(self):
+        """-> LIM_REPORT_DTYPE [n_streams]: the records of the last frame that ran the limiter (pn_rate_read_limiter_report, synchronising)."""
+        rep = np.empty(self.n_streams, LIM_REPORT_DTYPE)
+        self._chk(self.L.pn_rate_read_limiter_report(self.h, rep.ctypes.data))
+        return rep
+
+    def read_limiter_report_dev(self, d_report):
+        """The same into device memory [n_streams][4] words, asynchronous on the context's stream (pn_rate_read_limiter_report_dev)."""
+        self._chk(self.L.pn_rate_read_limiter_report_dev(self.h, d_report))
+
     # one whole frame, device pointers: [n_streams][frame] in and out at the low rate, d_gr [n_streams][68] or None
     def process_f32_dev(self, d_in, d_out, d_gr=None, ids=None):
         if ids is None:
@@ -1069,7 +1171,7 @@ class RateConverter:
 
     def kernel_times(self, names=("rate_up", "rate_down")):
         """-> {"rate_up": (total_ms, launches), "rate_down": (...)}; names: which kernels ("rate_mix" is the conference mix,
-        "rate_plc" the packet-loss concealer, "rate_agc" the level control)"""
+        "rate_plc" the packet-loss concealer, "rate_agc" the level control, "rate_lim" the output limiter)"""
         out = {}
         for name in names:
             ms = ctypes.c_double()

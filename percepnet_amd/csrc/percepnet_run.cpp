@@ -5,7 +5,7 @@
 // dropped, main.cpp:32-33); with a single pair ./feature_test.raw gets 68 floats per frame.
 //
 //   percepnet_run [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N]
-//                 [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--plc [--lose P:F0-F1,P:F,..]] [--agc RMS [--agc-max-gain G]] [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
+//                 [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--plc [--lose P:F0-F1,P:F,..]] [--agc RMS [--agc-max-gain G]] [--limiter CEIL [--limiter-hold H]] [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
 //                 in0.pcm out0.pcm [in1.pcm out1.pcm ...]
 //
 // --rate R: the files are raw int16 at R Hz instead of 48 kHz, in frames of n = 480 * R / 48000 samples (80 | 160 | 240 | 320): a rate
@@ -51,6 +51,11 @@
 // again and keeps its target), in front of the mix where there is one.  With --rate or --rates it uses their converter, alone it makes a
 // mixed converter of all 48000, as --plc does.  --agc-max-gain G: the largest gain, in [1, 1024] (parameter PN_AGC_MAX_GAIN; default 16);
 // it needs --agc.
+// --limiter CEIL: the output limiter on the converter (pn_rate_set_stream_limiter): every pair's output — its conference's mix where it is
+// in one — stays under the linear ceiling CEIL in [1/1024, 1] (parsed with strtof; set for every slot, once: a slot reset starts the
+// slot's gain again and keeps its ceiling).  With --rate or --rates it uses their converter, alone it makes a mixed converter of all
+// 48000, as --agc does.  --limiter-hold H: the frames the gain is held after an attack, a whole number in [0, 1000] (parameter
+// PN_LIM_HOLD; default 2); it needs --limiter.
 //
 // --atten-lim DB: every stream takes out at most DB dB of noise (pn_ctx_set_atten_limit; 0 = the input, delayed; default: no
 // limit).  A slot reset clears a stream's limit (a reset slot is a new call), so the limit is set again on every reset slot.
@@ -124,6 +129,7 @@ static bool g_plc = false;                            // --plc: packet-loss conc
 struct LoseRange { long pair, f0, f1; };
 static std::vector<LoseRange> g_lose;                 // --lose: pair, first and last lost frame of the pair
 static float g_agc = 0.0f, g_agc_max_gain = 0.0f;     // --agc: every pair's target RMS (0: not given); --agc-max-gain (0: not given)
+static float g_limiter = 0.0f, g_limiter_hold = -1.0f; // --limiter: every pair's ceiling (0: not given); --limiter-hold (-1: not given)
 // --report: what a pair's written frames add up to (one report record = PN_REPORT_WORDS words, include/percepnet_hip.h)
 struct PairStat { long frames = 0; long long clipped = 0; float peak = 0.f; double e_in = 0, e_out = 0; };
 static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, int postfilter, bool tap, int n_slots) {
@@ -176,6 +182,16 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
     if (g_agc_max_gain > 0.0f) params[PN_AGC_MAX_GAIN] = g_agc_max_gain;
     if (pn_rate_set_agc(rt, 1) || pn_rate_set_agc_params(rt, params) || pn_rate_set_stream_agc_targets(rt, all.data(), B, targets.data()))
       return fail(3, std::string("--agc: ") + pn_last_error());
+  }
+  if (g_limiter > 0.0f) {                               // every slot's ceiling, once (a setting: slot resets and rate changes keep it)
+    std::vector<int32_t> all(B);
+    std::vector<float> ceilings(B, g_limiter);
+    float params[PN_LIM_N_PARAMS];
+    for (int s = 0; s < B; s++) all[s] = s;
+    pn_lim_default_params(params);
+    if (g_limiter_hold >= 0.0f) params[PN_LIM_HOLD] = g_limiter_hold;
+    if (pn_rate_set_limiter_params(rt, params) || pn_rate_set_stream_limiter(rt, all.data(), B, ceilings.data()))
+      return fail(3, std::string("--limiter: ") + pn_last_error());
   }
   if (postfilter) pn_ctx_set_postfilter(cx, 1);
   if ((g_saturate && pn_ctx_set_output_saturate(cx, 1)) || (g_report && pn_ctx_set_report(cx, 1))) return fail(3, pn_last_error());
@@ -301,7 +317,7 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
 
 // the usage text, for a command line without pairs and for a rate no converter takes.  Returns the exit status, 1.
 static int usage(const char *argv0) {
-  fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N] [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--plc [--lose P:F0-F1,P:F,..]] [--agc RMS [--agc-max-gain G]] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv0);
+  fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N] [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--plc [--lose P:F0-F1,P:F,..]] [--agc RMS [--agc-max-gain G]] [--limiter CEIL [--limiter-hold H]] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv0);
   return 1;
 }
 
@@ -401,6 +417,21 @@ int main(int argc, char **argv) {
       g_agc_max_gain = strtof(v, &end);
       if (end == v || *end || !(g_agc_max_gain >= 1.0f && g_agc_max_gain <= 1024.0f)) { fprintf(stderr, "--agc-max-gain: expected a gain in [1, 1024], got '%s'\n", v); return 1; }
     }
+    else if (!strcmp(argv[ai], "--limiter") && ai + 1 < argc) {     // every pair's ceiling, linear (pn_rate_set_stream_limiter)
+      const char *v = argv[++ai];
+      char *end = NULL;
+      g_limiter = strtof(v, &end);
+      if (end == v || *end || !(g_limiter >= 1.0f / 1024.0f && g_limiter <= 1.0f)) { fprintf(stderr, "--limiter: expected a linear ceiling in [1/1024, 1], got '%s'\n", v); return 1; }
+    }
+    else if (!strcmp(argv[ai], "--limiter-hold") && ai + 1 < argc) {   // the frames the limiter holds its gain after an attack (PN_LIM_HOLD)
+      const char *v = argv[++ai];
+      char *end = NULL;
+      g_limiter_hold = strtof(v, &end);
+      float params[PN_LIM_N_PARAMS];
+      pn_lim_default_params(params);
+      params[PN_LIM_HOLD] = g_limiter_hold;
+      if (end == v || *end || pn_lim_params_check(params)) { fprintf(stderr, "--limiter-hold: expected a whole number of frames in [0, 1000], got '%s'\n", v); return 1; }
+    }
     else if (!strcmp(argv[ai], "--no-numa")) g_numa = false;        // leave the host threads' CPU affinity alone
     else if (!strcmp(argv[ai], "--verbose")) g_verbose = true;       // one line per device: its NUMA binding
     else if (!strcmp(argv[ai], "--slots") && ai + 1 < argc) n_slots = atoi(argv[++ai]);   // concurrent streams per device: pairs queue for them
@@ -441,7 +472,8 @@ int main(int argc, char **argv) {
   for (const LoseRange &lr : g_lose)
     if (lr.pair >= B) { fprintf(stderr, "--lose: pair %ld of %d pairs (pairs count from 0)\n", lr.pair, B); return 1; }
   if (g_agc_max_gain > 0.0f && !(g_agc > 0.0f)) { fprintf(stderr, "--agc-max-gain needs --agc: it is a parameter of the level control\n"); return 1; }
-  if ((g_plc || g_agc > 0.0f) && !g_rate && g_rates.empty()) g_rates.assign(B, 48000);        // on its own: a mixed converter of all 48000
+  if (g_limiter_hold >= 0.0f && !(g_limiter > 0.0f)) { fprintf(stderr, "--limiter-hold needs --limiter: it is a parameter of the output limiter\n"); return 1; }
+  if ((g_plc || g_agc > 0.0f || g_limiter > 0.0f) && !g_rate && g_rates.empty()) g_rates.assign(B, 48000);        // on its own: a mixed converter of all 48000
   pn_model *m = NULL;
   if (model_path) { FILE *f = fopen(model_path, "rb"); if (f) { m = pn_model_from_file(f); fclose(f); } }
   else if (&percepnet_model_orig) m = pn_model_from_rnnmodel(&percepnet_model_orig);

@@ -122,6 +122,10 @@ void pn_launch_rate_plc(hipStream_t st, int n_rows, const int *d_ids, const uint
 // words; d_report [n_streams][4] words or NULL
 void pn_launch_rate_agc(hipStream_t st, int n_rows, const int *d_ids, const float *d_targets, const uint32_t *d_lost, uint32_t tick, const float *params,
                         float *y48, void *state, void *d_report);
+// the output limiter (pn_rate_lim.hip; the rule pn_lim_rules.h): rows d_ids[0..n_rows) or, with d_ids == NULL, streams 0..n_rows of o48
+// [.][480], in place.  d_ceilings [n_streams]: +0.0 = the stream is not limited; params: the converter's PN_LIM_N_PARAMS floats on the
+// HOST, passed by value.  State [n_streams][4] words; d_report [n_streams][4] words or NULL
+void pn_launch_rate_lim(hipStream_t st, int n_rows, const int *d_ids, const float *d_ceilings, const float *params, float *o48, void *state, void *d_report);
 // ---- the network launchers (pn_nn*.hip) -----------------------------------------------------------------------------------------
 // Device pointers of a layer's biases and weights in the formats of pn_network.h: raw (w, rw), packed fp32 or fp16 planes (wp,
 // rwp), the 16x16x4 packing of a narrow layer (wq)

@@ -12,10 +12,11 @@
 #include "pn_mix_rules.h"    // loudest-N, send gains, hold: what the settings must be; the level and the selection for the host
 #include "pn_plc_rules.h"    // packet-loss concealment: the signal rule for the host, the sizes of the state
 #include "pn_agc_rules.h"    // automatic level control: the rule for the host, what parameters and targets must be
+#include "pn_lim_rules.h"    // the output limiter: the rule for the host, what parameters and ceilings must be
 #include <string>
 #include <vector>
 
-enum { RF_UP, RF_DOWN, RF_MIX, RF_PLC, RF_AGC, RF_COUNT };   // the timed kernels (pn_rate_kernel_time), named by kRateFamily below
+enum { RF_UP, RF_DOWN, RF_MIX, RF_PLC, RF_AGC, RF_LIM, RF_COUNT };   // the timed kernels (pn_rate_kernel_time), named by kRateFamily below
 struct pn_rate {
   pn_ctx *c;                    // borrowed: device, B, stream, the id ring, the saturate setting
   int rate, f, n, td;           // rate_hz, its factor (pn_rate_design.h: L, or PN_RATE_F_3_2 for 32000), samples per row, words per down tail row (2D / M).  Mixed: 0, 0, 480, 192
@@ -75,6 +76,15 @@ struct pn_rate {
   int agc_on = 0;                                     // streams whose target is not 0
   float *d_agc_targets = NULL;                        // [B]
   void *d_agc_state = NULL, *d_agc_report = NULL;     // [B][4] words each
+  // the output limiter (pn_rate_set_stream_limiter; the rule pn_lim_rules.h): SETTINGS — the converter's parameters, a ceiling per stream
+  // as last set (host) and on the device, written in stream order through the id ring like the AGC targets, the report switch — and the
+  // state, four words per stream.  The device side exists from the first call that sets a ceiling on.  lim_on == 0: a frame launches nothing of it
+  bool lim_report = false;
+  float lim_params[PN_LIM_N_PARAMS];
+  std::vector<float> lim_ceilings;                    // [B], 0
+  int lim_on = 0;                                     // streams whose ceiling is not 0
+  float *d_lim_ceilings = NULL;                       // [B]
+  void *d_lim_state = NULL, *d_lim_report = NULL;     // [B][4] words each
   std::vector<void *> allocs;
   // timing of the kernels (pn_rate_set_profiling): HIP events around their launches, like the context's families but owned
   // here; while it is off no event exists and none is recorded
@@ -84,7 +94,7 @@ struct pn_rate {
   std::vector<hipEvent_t> event_pool;
   double fam_ms[RF_COUNT] = {}; int64_t fam_n[RF_COUNT] = {};
 };
-static const char *const kRateFamily[RF_COUNT] = {"rate_up", "rate_down", "rate_mix", "rate_plc", "rate_agc"};
+static const char *const kRateFamily[RF_COUNT] = {"rate_up", "rate_down", "rate_mix", "rate_plc", "rate_agc", "rate_lim"};
 struct RateScope {
   pn_rate *r; int fam; hipEvent_t a, b; bool on;
   RateScope(pn_rate *r_, int fam_) : r(r_), fam(fam_), on(r_->profiling) {
@@ -147,6 +157,12 @@ extern "C" int pn_agc_frame(const float *params8, float target, uint32_t *state4
   return pn_agc_frame_host(params8, target, state4, row_in480, row_out480, concealed);
 }
 extern "C" int pn_rate_agc_targets_check(const float *targets, int n) { return pn_agc_targets_list_check(targets, n); }
+extern "C" int pn_lim_default_params(float *params2) { if (!params2) { pn_set_error("NULL argument"); return -1; } pn_lim_default_params_host(params2); return 0; }
+extern "C" int pn_lim_params_check(const float *params2) { return pn_lim_params_check_host(params2); }
+extern "C" int pn_lim_frame(const float *params2, float ceiling, uint32_t *state4, const float *row_in480, float *row_out480, uint32_t *report4) {
+  return pn_lim_frame_host(params2, ceiling, state4, row_in480, row_out480, report4);
+}
+extern "C" int pn_rate_limiter_ceilings_check(const float *ceilings, int n) { return pn_lim_ceilings_list_check(ceilings, n); }
 
 // ---- lifecycle ---------------------------------------------------------------------------------------------------------------
 extern "C" void pn_rate_destroy(pn_rate *r) {
@@ -172,6 +188,7 @@ extern "C" pn_rate *pn_rate_create(pn_ctx *c, int rate_hz) {
   r->mixed = false; r->factors = NULL; r->h_rows = NULL; r->laws.assign((size_t)c->B, PN_G711_ULAW); r->confs.assign((size_t)c->B, PN_CONF_NONE);
   r->gains.assign((size_t)c->B, 1.0f); r->caps.assign((size_t)c->B, 0);
   r->agc_targets.assign((size_t)c->B, 0.0f); pn_agc_default_params_host(r->agc_params);
+  r->lim_ceilings.assign((size_t)c->B, 0.0f); pn_lim_default_params_host(r->lim_params);
   const size_t B = (size_t)c->B, nt = 2 * (size_t)PN_RATE_TAPS * pn_rate_factor_L(f) + 1;
   float h[2][PN_RATE_MAX_TAPS];
   auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
@@ -203,6 +220,7 @@ extern "C" pn_rate *pn_rate_create_mixed(pn_ctx *c, const int32_t *rates_hz) {
   r->mixed = true; r->factors = NULL; r->h_rows = NULL; r->laws.assign((size_t)c->B, PN_G711_ULAW); r->confs.assign((size_t)c->B, PN_CONF_NONE);
   r->gains.assign((size_t)c->B, 1.0f); r->caps.assign((size_t)c->B, 0);
   r->agc_targets.assign((size_t)c->B, 0.0f); pn_agc_default_params_host(r->agc_params);
+  r->lim_ceilings.assign((size_t)c->B, 0.0f); pn_lim_default_params_host(r->lim_params);
   const size_t B = (size_t)c->B;
   if (rates_hz) r->rates.assign(rates_hz, rates_hz + B); else r->rates.assign(B, 48000);
   static const int kF[4] = {6, 3, 2, PN_RATE_F_3_2};   // (the order of pn_rate.hip rt_taps_offset; the h of 32000 is the table of 3 and is not staged twice)
@@ -249,6 +267,8 @@ static void plc_zero_rows(pn_rate *r, const int *d, int n) {
 }
 // the AGC state of the staged streams d[0..n) goes to zero: no level, a fresh gain (nothing while AGC was never enabled)
 static void agc_zero_rows(pn_rate *r, const int *d, int n) { pn_launch_zero_rows(r->c->stream, r->d_agc_state, 4, 4, 1, 0, d, n); }
+// the limiter state of the staged streams d[0..n) goes to zero: a fresh gain, no hold (nothing while no ceiling was ever set)
+static void lim_zero_rows(pn_rate *r, const int *d, int n) { pn_launch_zero_rows(r->c->stream, r->d_lim_state, 4, 4, 1, 0, d, n); }
 // A rate change of the listed streams, asynchronous and ordered like pn_rate_reset_streams: the ids and the new factors go
 // through the context's id ring in one copy, one launch writes the factors, two zero the tails.
 extern "C" int pn_rate_set_stream_rates(pn_rate *r, const int32_t *ids, int n, const int32_t *rates_hz) {
@@ -267,6 +287,7 @@ extern "C" int pn_rate_set_stream_rates(pn_rate *r, const int32_t *ids, int n, c
   pn_launch_zero_rows(r->c->stream, r->d_level, 1, 1, 1, 0, d, n);       // (nothing while no level exists)
   plc_zero_rows(r, d, n);
   agc_zero_rows(r, d, n);
+  lim_zero_rows(r, d, n);
   PN_HIP_CHECK(hipGetLastError());
   for (int i = 0; i < n; i++) r->rates[ids[i]] = rates_hz[i];
   return 0;
@@ -577,6 +598,67 @@ static int agc_report_copy(pn_rate *r, void *dst, hipMemcpyKind kind) {
 extern "C" int pn_rate_read_agc_report(pn_rate *r, void *h_report) { return agc_report_copy(r, h_report, hipMemcpyDeviceToHost); }
 extern "C" int pn_rate_read_agc_report_dev(pn_rate *r, void *d_report) { return agc_report_copy(r, d_report, hipMemcpyDeviceToDevice); }
 
+// ---- the output limiter (include/percepnet_hip.h; the rule pn_lim_rules.h; the kernel pn_rate_lim.hip) ----------------------------
+static int lim_buffers(pn_rate *r) {                 // (the caller is on the context's device)
+  if (r->d_lim_state) return 0;
+  pn_ctx *c = r->c;
+  const size_t B = (size_t)c->B;
+  float *ceilings = NULL; void *state = NULL;
+  auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
+  if (alloc((void **)&ceilings, B * 4, true) || alloc(&state, B * PN_LIM_STATE_BYTES, true)) return -1;
+  r->d_lim_ceilings = ceilings; r->d_lim_state = state;
+  return 0;
+}
+extern "C" int pn_rate_set_stream_limiter(pn_rate *r, const int32_t *ids, int n, const float *ceilings) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (pn_lim_ceilings_set_check(r->c->B, ids, n, ceilings)) return -1;
+  if (n == 0) return 0;
+  std::vector<float> v(ceilings, ceilings + n);
+  bool all_zero = true;
+  for (float &x : v) { if (x == 0.0f) x = 0.0f; all_zero &= x == 0.0f; }       // (-0.0f is 0)
+  if (!r->d_lim_state && all_zero) return 0;                                     // (no ceiling has ever been set, and none is)
+  PN_ON_DEVICE(r->c);
+  if (lim_buffers(r) || mix_set_words(r, ids, n, v.data(), reinterpret_cast<int *>(r->d_lim_ceilings))) return -1;
+  for (int i = 0; i < n; i++) { r->lim_on += (v[i] != 0.0f) - (r->lim_ceilings[ids[i]] != 0.0f); r->lim_ceilings[ids[i]] = v[i]; }
+  return 0;
+}
+extern "C" int pn_rate_get_stream_limiter(const pn_rate *r, float *h_ceilings) {
+  if (!r || !h_ceilings) { pn_set_error("NULL argument"); return -1; }
+  for (int s = 0; s < r->c->B; s++) h_ceilings[s] = r->lim_ceilings[s];
+  return 0;
+}
+// the parameters travel as an argument of every launch, so a change is ordered like one
+extern "C" int pn_rate_set_limiter_params(pn_rate *r, const float *params2) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (pn_lim_params_check_host(params2)) return -1;
+  memcpy(r->lim_params, params2, sizeof(r->lim_params));
+  return 0;
+}
+extern "C" int pn_rate_get_limiter_params(const pn_rate *r, float *params2) {
+  if (!r || !params2) { pn_set_error("NULL argument"); return -1; }
+  memcpy(params2, r->lim_params, sizeof(r->lim_params));
+  return 0;
+}
+extern "C" int pn_rate_set_limiter_report(pn_rate *r, int enable) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (enable && !r->d_lim_report) {
+    PN_ON_DEVICE(r->c);
+    if (dev_alloc_into(r->allocs, r->bytes, r->c->stream, &r->d_lim_report, (size_t)r->c->B * PN_LIM_REPORT_WORDS * 4, true)) return -1;
+  }
+  r->lim_report = enable != 0;
+  return 0;
+}
+static int lim_report_copy(pn_rate *r, void *dst, hipMemcpyKind kind) {
+  if (!r || !dst) { pn_set_error("NULL argument"); return -1; }
+  if (!r->lim_report) { pn_set_error("the limiter report is off (pn_rate_set_limiter_report)"); return -1; }
+  PN_ON_DEVICE(r->c);
+  PN_HIP_CHECK(hipMemcpyAsync(dst, r->d_lim_report, (size_t)r->c->B * PN_LIM_REPORT_WORDS * 4, kind, r->c->stream));
+  if (kind == hipMemcpyDeviceToHost) PN_HIP_CHECK(hipStreamSynchronize(r->c->stream));
+  return 0;
+}
+extern "C" int pn_rate_read_limiter_report(pn_rate *r, void *h_report) { return lim_report_copy(r, h_report, hipMemcpyDeviceToHost); }
+extern "C" int pn_rate_read_limiter_report_dev(pn_rate *r, void *d_report) { return lim_report_copy(r, d_report, hipMemcpyDeviceToDevice); }
+
 extern "C" int pn_rate_reset(pn_rate *r) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   PN_ON_DEVICE(r->c);
@@ -589,6 +671,7 @@ extern "C" int pn_rate_reset(pn_rate *r) {
     PN_HIP_CHECK(hipMemsetAsync(r->d_plc_meta, 0, (size_t)r->c->B * 16, r->c->stream));
   }
   if (r->d_agc_state) PN_HIP_CHECK(hipMemsetAsync(r->d_agc_state, 0, (size_t)r->c->B * PN_AGC_STATE_BYTES, r->c->stream));
+  if (r->d_lim_state) PN_HIP_CHECK(hipMemsetAsync(r->d_lim_state, 0, (size_t)r->c->B * PN_LIM_STATE_BYTES, r->c->stream));
   return 0;
 }
 
@@ -604,6 +687,7 @@ extern "C" int pn_rate_reset_streams(pn_rate *r, const int32_t *ids, int n) {
   pn_launch_zero_rows(r->c->stream, r->d_level, 1, 1, 1, 0, d, n);
   plc_zero_rows(r, d, n);
   agc_zero_rows(r, d, n);
+  lim_zero_rows(r, d, n);
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -674,6 +758,15 @@ static int rate_agc(pn_rate *r, float *d_y48, const RateRows &rows, const uint32
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
+// the output limiter over the rows, in place on the rows the down-conversion reads next
+static int rate_lim(pn_rate *r, float *d_o48, const RateRows &rows) {
+  {
+    RateScope sc(r, RF_LIM);
+    pn_launch_rate_lim(r->c->stream, rows.n, rows.d_ids, r->d_lim_ceilings, r->lim_params, d_o48, r->d_lim_state, r->lim_report ? r->d_lim_report : NULL);
+  }
+  PN_HIP_CHECK(hipGetLastError());
+  return 0;
+}
 static int rate_up_call(pn_rate *r, const void *d_in, int fmt, float *d_out48, const int32_t *ids, int n) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   if (rate_aligned(d_in, d_out48)) return -1;
@@ -724,10 +817,19 @@ extern "C" int pn_rate_agc_f32(pn_rate *r, float *d_y48, const int32_t *ids, int
   if (rate_rows(r, ids, n_ids, &rows)) return -1;
   return rate_agc(r, d_y48, rows, NULL, 0);
 }
+extern "C" int pn_rate_lim_f32(pn_rate *r, float *d_o48, const int32_t *ids, int n_ids) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (rate_aligned(d_o48, d_o48)) return -1;
+  PN_ON_DEVICE(r->c);
+  RateRows rows;
+  if (rate_rows(r, ids, n_ids, &rows)) return -1;
+  if (lim_buffers(r)) return -1;                     // (no ceiling was ever set: every stream is off, the state exists from here on)
+  return rate_lim(r, d_o48, rows);
+}
 
 // ---- one whole frame -----------------------------------------------------------------------------------------------------------
 // up into x48, while packet-loss concealment is on the concealer in place on x48, the engine's float frame from x48 into y48 (all streams, or the listed ones through the context's own active
-// set), while automatic level control is on and a stream has a target the level control in place on y48, down from y48 — or, while a stream is in a conference, the mix from y48 into o48 and down from o48.  A frame the engine refuses returns -1 with its error kept; the up kernel has then advanced its tails
+// set), while automatic level control is on and a stream has a target the level control in place on y48, down from y48 — or, while a stream is in a conference, the mix from y48 into o48 and down from o48 — and in front of the down-conversion, while a stream has a ceiling, the output limiter in place on the rows it reads.  A frame the engine refuses returns -1 with its error kept; the up kernel has then advanced its tails
 // and the down kernel has not, which is why the header asks for a reset of both objects before reuse.
 // rate_frame: the launches alone — the caller is on the context's device and has checked the rows and, when active, the list
 // (pn_ids_check, distinct), which is what lets the pipelined path refuse a list BEFORE the frame takes a pipeline slot.
@@ -760,11 +862,13 @@ static int rate_frame(pn_rate *r, const void *d_in, void *d_out, float *d_gr, in
   if (active ? pn_process_f32_active(c, r->x48, r->y48, d_gr, ids, n) : pn_process_f32(c, r->x48, r->y48, d_gr)) return -1;
   // the level control, while on and somebody has a target: in place on y48, so the mix, its levels and the down-conversion see levelled rows
   if (r->agc && r->agc_on > 0 && rate_agc(r, r->y48, rows, concealing ? r->d_plc_lost : NULL, plc_tick_used)) return -1;
-  const float *o = r->y48;
+  float *o = r->y48;
   if (r->in_conf > 0 || !mix_plain(r)) {             // somebody is in a conference (or a mix setting is on): the mix writes every advancing stream's row of o48
     if (rate_mix(r, r->y48, r->o48, rows)) return -1;
     o = r->o48;
   }
+  // the output limiter, while somebody has a ceiling: in place on the rows the down-conversion reads — mix rows, or the streams' own
+  if (r->lim_on > 0 && rate_lim(r, o, rows)) return -1;
   if (rate_down(r, o, d_out, fmt, rows)) return -1;
   if (r->events.size() >= 4096 && rate_flush_events(r)) return -1;   // profiling left on: bound the pending events
   return 0;
@@ -852,7 +956,7 @@ extern "C" int pn_rate_submit_host_g711_active(pn_rate *r, const uint8_t *h_in, 
 // ---- timing the kernels --------------------------------------------------------------------------------------------------------
 extern "C" int pn_rate_set_profiling(pn_rate *r, int enable) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
-  if (enable && r->event_pool.size() < 1024) {        // up to five scopes a frame (up, plc, agc, mix, down): enough for 102 frames between two reads; created outside any timed region
+  if (enable && r->event_pool.size() < 1024) {        // up to six scopes a frame (up, plc, agc, mix, lim, down): enough for 85 frames between two reads; created outside any timed region
     PN_ON_DEVICE(r->c);
     while (r->event_pool.size() < 1024) { hipEvent_t e; PN_HIP_CHECK(hipEventCreate(&e)); r->event_pool.push_back(e); }
   }
@@ -865,7 +969,7 @@ extern "C" int pn_rate_kernel_time(pn_rate *r, const char *name, double *total_m
   if (rate_flush_events(r)) return -1;
   for (int i = 0; i < RF_COUNT; i++)
     if (!strcmp(name, kRateFamily[i])) { if (total_ms) *total_ms = r->fam_ms[i]; if (launches) *launches = r->fam_n[i]; return 0; }
-  pn_set_error("unknown converter kernel '%s' (rate_up, rate_down, rate_mix, rate_plc, rate_agc)", name);
+  pn_set_error("unknown converter kernel '%s' (rate_up, rate_down, rate_mix, rate_plc, rate_agc, rate_lim)", name);
   return -1;
 }
 extern "C" int pn_rate_reset_profile(pn_rate *r) {
@@ -886,7 +990,7 @@ static int rate_records_host(pn_rate *r, int rate, bool import, const int32_t *i
     const int *d_ids = stage_ids(c, ids, n);
     if (!d_ids) return -1;
     pn_launch_rate_records(c->stream, f, rate, d_ids, n, r->tail_up, r->tail_down, r->td, d, import ? 1 : 0);
-    if (import) { plc_zero_rows(r, d_ids, n); agc_zero_rows(r, d_ids, n); }   // the slot is now another stream: it starts with an empty history and a fresh gain
+    if (import) { plc_zero_rows(r, d_ids, n); agc_zero_rows(r, d_ids, n); lim_zero_rows(r, d_ids, n); }   // the slot is now another stream: it starts with an empty history and fresh gains
     if (hipGetLastError() != hipSuccess) { pn_set_error(import ? "record scatter launch failed" : "record gather launch failed"); return -1; }
     return 0;
   });
@@ -932,7 +1036,7 @@ static int rate_records_dev(pn_rate *r, bool import, const int32_t *ids, int n, 
   if (!d) return -1;
   pn_launch_rate_records_dev(c->stream, d, n, r->mixed ? r->factors : NULL, r->f, r->tail_up, r->tail_down, r->td, d_records,
                              (int)(pn_rate_record_stride(r) / 4), d_status, import ? 1 : 0);
-  if (import) { plc_zero_rows(r, d, n); agc_zero_rows(r, d, n); }   // the slot is now another stream: it starts with an empty history and a fresh gain, whatever its record's status
+  if (import) { plc_zero_rows(r, d, n); agc_zero_rows(r, d, n); lim_zero_rows(r, d, n); }   // the slot is now another stream: it starts with an empty history and fresh gains, whatever its record's status
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
