@@ -307,7 +307,8 @@ enum {
   PN_SS_BAD_SIZE = -3,      /* a buffer of the wrong size, or a header that names another record size */
   PN_SS_BAD_MODEL = -4,     /* written under another model (pn_model_digest differs) */
   PN_SS_BAD_ARG = -5,       /* NULL record or model */
-  PN_SS_BAD_RATE = -6       /* pn_rate_state_check: written by a converter of another rate, or a rate no converter has */
+  PN_SS_BAD_RATE = -6,      /* pn_rate_state_check: written by a converter of another rate, or a rate no converter has */
+  PN_SS_BAD_STATE = -7      /* pn_rate_call_state_check: a body that breaks an invariant its kernels rely on, or an unknown section */
 };
 size_t pn_stream_state_bytes(void);            /* PN_STREAM_STATE_BYTES */
 /* Host only, needs no GPU: is `bytes` bytes at `record` one record that a context of `model` accepts?  PN_SS_OK or a
@@ -832,14 +833,14 @@ int pn_rate_read_mix_report_dev(pn_rate *r, void *d_report);
      word 3  lost    lost frames since reset
    Lifecycle.  pn_rate_reset zeroes the PLC state of every stream; pn_rate_reset_streams and pn_rate_set_stream_rates that of the
    listed ones: a following loss conceals from an empty history, that is with silence.  Law, conference and mix settings do not touch
-   it.  Records (pn_rate_export_streams*) do not carry it: pn_rate_import_streams and pn_rate_import_streams_host zero the PLC state
-   of the slots they write (the device form whatever status a record gets), so a moved stream starts with an empty history in its
-   new slot and hears nothing of the slot's previous stream.
+   it.  The tails records (pn_rate_export_streams*) do not carry it: pn_rate_import_streams and pn_rate_import_streams_host zero the
+   PLC state of the slots they write (the device form whatever status a record gets), so the slot hears nothing of its previous
+   stream; the call-state record ("call-state records", below), imported behind them, brings the moved stream's own history.
    Host only, needing no GPU: pn_plc_pitch (hist[1920] -> P), pn_plc_period (hist, P in [240, 720] -> q[0..P); -1 otherwise),
    pn_plc_gain (m -> g(m)).
    NOT provided: Appendix I's lengthening of the repeated segment to two and three periods on long losses; Appendix II comfort noise;
-   concealment on pn_process_* without a converter; PLC state in the records.  How the model's output quality fares on concealed
-   frames is not measured. */
+   concealment on pn_process_* without a converter; lost marks set for the next frame in any record (a mover sets them again).  How
+   the model's output quality fares on concealed frames is not measured. */
 #define PN_PLC_HIST 1920
 #define PN_PLC_P_MIN 240
 #define PN_PLC_P_MAX 720
@@ -921,12 +922,12 @@ int pn_rate_read_plc_report_dev(pn_rate *r, void *d_report);
      word 3  f32 p       the row's peak before the gain
    Lifecycle.  pn_rate_reset zeroes the AGC state of every stream; pn_rate_reset_streams, pn_rate_set_stream_rates and both import
    forms (pn_rate_import_streams, pn_rate_import_streams_host) that of the listed slots.  A stream that does not advance keeps its
-   state.  Targets, parameters and the switches are settings that survive all of those.  Records do not carry the AGC state; their
-   format and sizes are untouched.  With PLC on, a stream is concealed in the frame whose marks the concealer consumed; once in 2^32
+   state.  Targets, parameters and the switches are settings that survive all of those.  The tails records do not carry the AGC
+   state and their format and sizes are untouched; the call-state record ("call-state records", below) carries it.  With PLC on, a stream is concealed in the frame whose marks the concealer consumed; once in 2^32
    frames, when the concealer's tick wraps, that frame's concealed streams count as received.
    A sum of levelled voices can still pass full scale: the output limiter (next section) keeps the mix under a ceiling.
-   NOT provided: targets in dBFS; AGC state in the records; AGC without a converter; loudness weighting (K-weighting); any
-   measurement of perceived quality. */
+   NOT provided: targets in dBFS; targets and parameters in any record (they are settings: a mover sets them on the target); AGC
+   without a converter; loudness weighting (K-weighting); any measurement of perceived quality. */
 #define PN_AGC_N_PARAMS 8
 #define PN_AGC_MAX_GAIN 0
 #define PN_AGC_MIN_GAIN 1
@@ -1013,9 +1014,10 @@ int pn_rate_read_agc_report_dev(pn_rate *r, void *d_report);
      A stream whose ceiling is 0: {1.0f, +0.0f, 0, 0}.
    Lifecycle.  pn_rate_reset zeroes the limiter state of every stream; pn_rate_reset_streams, pn_rate_set_stream_rates and both import
    forms that of the listed slots.  A stream that does not advance keeps its state.  Ceilings, parameters and the report switch are
-   settings that survive all of those.  Records do not carry the limiter state; their format and sizes are untouched.
-   NOT provided: look-ahead beyond the row (that would add delay); limiter state in the records; a limiter without a converter; any
-   measurement of perceived quality. */
+   settings that survive all of those.  The tails records do not carry the limiter state and their format and sizes are untouched;
+   the call-state record ("call-state records", below) carries it.
+   NOT provided: look-ahead beyond the row (that would add delay); ceilings and parameters in any record (they are settings: a mover
+   sets them on the target); a limiter without a converter; any measurement of perceived quality. */
 #define PN_LIM_N_PARAMS 2
 #define PN_LIM_RELEASE 0
 #define PN_LIM_HOLD 1
@@ -1038,6 +1040,76 @@ int pn_rate_lim_f32(pn_rate *r, float *d_o48, const int32_t *ids, int n_ids);
 int pn_rate_set_limiter_report(pn_rate *r, int enable);
 int pn_rate_read_limiter_report(pn_rate *r, void *h_report);
 int pn_rate_read_limiter_report_dev(pn_rate *r, void *d_report);
+
+/* ---- call-state records: a live call moves whole ------------------------------------------------------------------------------- */
+/* The tails record above carries the two filters' tails.  The concealer's history, the level control's gain, the limiter's gain and
+   hold and the level the loudest-N hold keeps live on the converter too, and pn_rate_import_streams[_host] zero them on purpose
+   (the slot is another stream's now).  A SECOND record with entry points of its own carries them, so that a stream moved between
+   slots, contexts, devices and processes continues bit for bit: the frame after the move is the frame an unbroken run gives,
+   also in the middle of a loss, of a limiter hold or of an AGC slew.  The record does not depend on the stream's rate: one size for
+   every rate, and a 48000 stream of a mixed converter — which has no tails record — has this one.
+   The layout and the verdict are stated once in csrc/pn_call_rules.h (HIP-free); tests/call_state_model.py restates both.
+
+   Record (little-endian, PN_RATE_CALL_STATE_BYTES = 10640, every section 16-byte aligned):
+     header 16 B: uint32 magic PN_RATE_CALL_MAGIC | uint32 version PN_RATE_CALL_VERSION | uint32 record bytes | uint32 section mask
+     body, words:    0 PN_CALL_W_HIST  1920 f32  the concealer's history in its LINEAR view, oldest sample first
+                  1920 PN_CALL_W_Q      720 f32  its period buffer
+                  2640 PN_CALL_W_META     4 u32  P | r | lost | 0   (the ring's head is normalised away: the record is phase-free)
+                  2644 PN_CALL_W_AGC      4 u32  the level control's state: lev | gain | adapted | spare
+                  2648 PN_CALL_W_LIM      4 u32  the limiter's state: gain | hold | limited | spare
+                  2652 PN_CALL_W_MIX      4      the held level f32 | 3 zero words
+   Section mask: PN_CALL_PLC | PN_CALL_AGC | PN_CALL_LIM | PN_CALL_MIX, the states the exporting converter HELD — PLC while its switch
+   is on, AGC once it was ever enabled, the limiter once a ceiling was ever set, MIX once a mix setting ever left its default
+   (pn_rate_call_state_sections gives the mask).  A section whose bit is clear is all zero.
+   pn_rate_call_state_check (host only): PN_SS_OK, or PN_SS_BAD_ARG (NULL), PN_SS_BAD_MAGIC, PN_SS_BAD_VERSION, PN_SS_BAD_SIZE (the
+   buffer or the size word is not 10640), or PN_SS_BAD_STATE: a mask with an unknown bit; a present section that breaks an invariant
+   its kernel relies on — PLC: P == 0 or 240 <= P <= 720, r > 0 only with P != 0, word 3 zero; AGC: lev >= 0 and no NaN, gain bits 0
+   or a value in [1/1024, 1024], spare 0; limiter: gain bits 0 or a value in (0, 1], spare 0; MIX: level finite and >= 0, padding 0
+   — or an absent section that is not all zero.
+
+   Export (duplicates allowed): record i gets the header with the converter's mask, the held sections of stream ids[i] — the PLC
+   ring in age order — and zeros everywhere else.
+   Import (distinct ids): each record is judged on its own.  Section by section, an accepted record's section that the target holds
+   is written (the ring at head 0); a section the target holds and the record lacks is ZEROED (a fresh state); a section the record
+   has and the target does not hold is dropped.  A refused record leaves its stream exactly as it was.
+   Device forms: asynchronous on the context's stream and ordered like pn_rate_export_streams, on the pipelined path too; records at a
+   16-byte aligned device address, PN_RATE_CALL_STATE_BYTES apart; d_status[i] (required) receives exactly
+   pn_rate_call_state_check(record_i, PN_RATE_CALL_STATE_BYTES), and the other records of the call are still imported.  Refused on the
+   host with -1, nothing written or launched: a bad or (import) duplicate id, a misaligned or NULL pointer.  n == 0 is a no-op.
+   Host forms: synchronous like pn_rate_export_streams_host (frames in flight complete first); the import checks EVERY record before
+   anything is launched and is all-or-nothing.
+   No call allocates state: a converter that holds nothing exports records with mask 0, and an import into it writes nothing and
+   still reports PN_SS_OK.  Both converter kinds, every rate.
+
+   The order a mover follows on the target:
+     1. the settings: rates, laws, conferences, send gains, caps and hold, AGC switch, parameters and targets, ceilings and limiter
+        parameters, the PLC switch (several of them reset the state they govern, which is why they come first);
+     2. pn_ctx_import_streams — the engine's state;
+     3. pn_rate_import_streams — the tails (not for a 48000 stream); it still zeroes the four states;
+     4. pn_rate_import_call_state — the four states.
+   NOT state, and not carried by any record: lost marks set for the next frame (pn_rate_set_lost; the mover sets them again), every
+   setting, every report row. */
+#define PN_RATE_CALL_MAGIC 0x53434e50u         /* "PNCS" */
+#define PN_RATE_CALL_VERSION 1
+#define PN_RATE_CALL_STATE_BYTES 10640
+#define PN_CALL_PLC 1
+#define PN_CALL_AGC 2
+#define PN_CALL_LIM 4
+#define PN_CALL_MIX 8
+#define PN_CALL_W_HIST 0
+#define PN_CALL_W_Q 1920
+#define PN_CALL_W_META 2640
+#define PN_CALL_W_AGC 2644
+#define PN_CALL_W_LIM 2648
+#define PN_CALL_W_MIX 2652
+#define PN_CALL_BODY_WORDS 2656
+size_t pn_rate_call_state_bytes(void);                                    /* host only */
+int pn_rate_call_state_check(const void *record, size_t bytes);           /* host only */
+int pn_rate_call_state_sections(const pn_rate *r);                        /* the held mask; -1 for NULL */
+int pn_rate_export_call_state(pn_rate *r, const int32_t *ids, int n, void *d_records);
+int pn_rate_import_call_state(pn_rate *r, const int32_t *ids, int n, const void *d_records, int32_t *d_status);
+int pn_rate_export_call_state_host(pn_rate *r, const int32_t *ids, int n, void *h_records);
+int pn_rate_import_call_state_host(pn_rate *r, const int32_t *ids, int n, const void *h_records);
 
 const char *pn_last_error(void);
 const char *pn_version(void);

@@ -49,6 +49,11 @@ LIM_REPORT_WORDS = 4
 LIM_ON, LIM_ATTACK, LIM_HOLDING, LIM_RELEASING, LIM_ACTIVE, LIM_NONFINITE = 1, 2, 4, 8, 16, 32   # its flags
 LIM_REPORT_DTYPE = np.dtype([("gain", "<f4"), ("peak", "<f4"), ("flags", "<u4"), ("limited", "<u4")])
 LIM_STATE_DTYPE = np.dtype([("gain", "<f4"), ("hold", "<u4"), ("limited", "<u4"), ("spare", "<u4")])   # the four state words of lim_frame
+# call-state records (include/percepnet_hip.h "call-state records"): PN_RATE_CALL_*, PN_CALL_*
+SS_BAD_STATE = -7         # pn_rate_call_state_check: a body that breaks an invariant, an unknown section, words in an absent section
+RATE_CALL_MAGIC, RATE_CALL_VERSION, RATE_CALL_STATE_BYTES = 0x53434E50, 1, 10640
+CALL_PLC, CALL_AGC, CALL_LIM, CALL_MIX = 1, 2, 4, 8                             # the section mask
+CALL_W_HIST, CALL_W_Q, CALL_W_META, CALL_W_AGC, CALL_W_LIM, CALL_W_MIX, CALL_BODY_WORDS = 0, 1920, 2640, 2644, 2648, 2652, 2656   # body word offsets
 # per-stream frame report (include/percepnet_hip.h pn_ctx_set_report): one record of PN_REPORT_WORDS 32-bit words per stream
 REPORT_WORDS = 8
 REPORT_DTYPE = np.dtype([("in_peak", "<f4"), ("in_energy", "<f4"), ("out_peak", "<f4"), ("out_energy", "<f4"), ("gain_mean", "<f4"),
@@ -253,6 +258,14 @@ def load_library():
             getattr(L, name).argtypes = [_vp, _vp]
         L.pn_rate_set_stream_limiter.argtypes = [_vp, _vp, ctypes.c_int, _vp]
         L.pn_rate_lim_f32.argtypes = [_vp, _vp, _vp, ctypes.c_int]
+    if hasattr(L, "pn_rate_export_call_state"):
+        L.pn_rate_call_state_bytes.restype = ctypes.c_size_t
+        L.pn_rate_call_state_bytes.argtypes = []
+        L.pn_rate_call_state_check.argtypes = [_vp, ctypes.c_size_t]
+        L.pn_rate_call_state_sections.argtypes = [_vp]
+        for name in ("pn_rate_export_call_state", "pn_rate_export_call_state_host", "pn_rate_import_call_state_host"):
+            getattr(L, name).argtypes = [_vp, _vp, ctypes.c_int, _vp]
+        L.pn_rate_import_call_state.argtypes = [_vp, _vp, ctypes.c_int, _vp, _vp]
     if hasattr(L, "pn_host_pipeline_prepare"):
         L.pn_host_pipeline_prepare.argtypes = [_vp]
     L.pn_ctx_debug_copy.restype = ctypes.c_longlong
@@ -607,6 +620,19 @@ def rate_state_check(record, rate_hz):
     b = np.ascontiguousarray(np.frombuffer(bytes(record), np.uint8)) if not isinstance(record, np.ndarray) else \
         np.ascontiguousarray(record, dtype=np.uint8)
     return int(L.pn_rate_state_check(b.ctypes.data if b.size else None, b.size, int(rate_hz)))
+
+
+def rate_call_state_bytes():
+    """Bytes of one call-state record, whatever the stream's rate: 10640 (pn_rate_call_state_bytes, host only)."""
+    return int(load_library().pn_rate_call_state_bytes())
+
+
+def rate_call_state_check(record):
+    """PN_SS_OK (0) or the PN_SS_BAD_* verdict of the bytes `record` as a call-state record (pn_rate_call_state_check, host only)."""
+    L = load_library()
+    b = np.ascontiguousarray(np.frombuffer(bytes(record), np.uint8)) if not isinstance(record, np.ndarray) else \
+        np.ascontiguousarray(record).view(np.uint8).reshape(-1)
+    return int(L.pn_rate_call_state_check(b.ctypes.data if b.size else None, b.size))
 
 
 def rate_mixed_frame_samples(rate_hz):
@@ -1161,6 +1187,42 @@ class RateConverter:
         """d_status (device int32 [n]) receives SS_OK or the SS_BAD_* verdict of each record against its slot's rate."""
         a, n = self._ids(ids)
         self._chk(self.L.pn_rate_import_streams(self.h, a.ctypes.data, n, d_records, d_status))
+
+    # call-state records (include/percepnet_hip.h "call-state records"): the PLC, AGC, limiter and level state, one size for every
+    # rate; imported BEHIND import_streams, which zeroes those states.  Defined here once: a mixed converter uses them unchanged
+    def call_state_sections(self):
+        """-> the CALL_* mask of the states this converter holds (pn_rate_call_state_sections)."""
+        m = int(self.L.pn_rate_call_state_sections(self.h))
+        if m < 0:
+            raise PercepNetError(_err(self.L))
+        return m
+
+    def export_call_state_dev(self, ids, d_records):
+        """Records RATE_CALL_STATE_BYTES apart at a 16-byte aligned device address, asynchronous (pn_rate_export_call_state)."""
+        a, n = self._ids(ids)
+        self._chk(self.L.pn_rate_export_call_state(self.h, a.ctypes.data, n, d_records))
+
+    def import_call_state_dev(self, ids, d_records, d_status):
+        """d_status (device int32 [n]) receives SS_OK or the SS_BAD_* verdict of each record; a refused record leaves its stream
+        as it was, the others are imported (pn_rate_import_call_state)."""
+        a, n = self._ids(ids)
+        self._chk(self.L.pn_rate_import_call_state(self.h, a.ctypes.data, n, d_records, d_status))
+
+    def export_call_state(self, ids):
+        """-> uint8 [n, RATE_CALL_STATE_BYTES]: the call state of the streams `ids` (pn_rate_export_call_state_host)."""
+        a, n = self._ids(ids)
+        rec = np.empty((n, RATE_CALL_STATE_BYTES), np.uint8)
+        self._chk(self.L.pn_rate_export_call_state_host(self.h, a.ctypes.data, n, rec.ctypes.data))
+        return rec
+
+    def import_call_state(self, ids, records):
+        """Records from export_call_state of any converter into the distinct streams `ids`; every record is checked first, all
+        or nothing (pn_rate_import_call_state_host)."""
+        a, n = self._ids(ids)
+        rec = np.ascontiguousarray(records).view(np.uint8).reshape(-1)
+        if rec.size != n * RATE_CALL_STATE_BYTES:
+            raise PercepNetError(f"{rec.size} record bytes for {n} streams (a call-state record has {RATE_CALL_STATE_BYTES})")
+        self._chk(self.L.pn_rate_import_call_state_host(self.h, a.ctypes.data, n, rec.ctypes.data))
 
     # timing of the two kernels inside a frame (HIP events owned by the converter; off by default)
     def set_profiling(self, on):

@@ -5,7 +5,7 @@
 // dropped, main.cpp:32-33); with a single pair ./feature_test.raw gets 68 floats per frame.
 //
 //   percepnet_run [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N]
-//                 [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--plc [--lose P:F0-F1,P:F,..]] [--agc RMS [--agc-max-gain G]] [--limiter CEIL [--limiter-hold H]] [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
+//                 [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--plc [--lose P:F0-F1,P:F,..]] [--agc RMS [--agc-max-gain G]] [--limiter CEIL [--limiter-hold H]] [--migrate-at F] [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
 //                 in0.pcm out0.pcm [in1.pcm out1.pcm ...]
 //
 // --rate R: the files are raw int16 at R Hz instead of 48 kHz, in frames of n = 480 * R / 48000 samples (80 | 160 | 240 | 320): a rate
@@ -56,6 +56,11 @@
 // slot's gain again and keeps its ceiling).  With --rate or --rates it uses their converter, alone it makes a mixed converter of all
 // 48000, as --agc does.  --limiter-hold H: the frames the gain is held after an attack, a whole number in [0, 1000] (parameter
 // PN_LIM_HOLD; default 2); it needs --limiter.
+// --migrate-at F (needs a converter — --rate, --rates or an option that makes one — and one device): when frame F (the shard's frames
+// count from 0) has been delivered, the run builds a SECOND context and converter with the same settings, moves every slot there with
+// all three record kinds in the mover's order of include/percepnet_hip.h "call-state records" (the engine's, the converter's tails,
+// the call state), destroys the first pair and goes on: what a caller does who rebalances live calls.  The output files are byte for
+// byte those of the run without the option.
 //
 // --atten-lim DB: every stream takes out at most DB dB of noise (pn_ctx_set_atten_limit; 0 = the input, delayed; default: no
 // limit).  A slot reset clears a stream's limit (a reset slot is a new call), so the limit is set again on every reset slot.
@@ -130,6 +135,7 @@ struct LoseRange { long pair, f0, f1; };
 static std::vector<LoseRange> g_lose;                 // --lose: pair, first and last lost frame of the pair
 static float g_agc = 0.0f, g_agc_max_gain = 0.0f;     // --agc: every pair's target RMS (0: not given); --agc-max-gain (0: not given)
 static float g_limiter = 0.0f, g_limiter_hold = -1.0f; // --limiter: every pair's ceiling (0: not given); --limiter-hold (-1: not given)
+static long g_migrate_at = -1;                        // --migrate-at: the frame behind which every slot moves to a second context and converter (-1: not given)
 // --report: what a pair's written frames add up to (one report record = PN_REPORT_WORDS words, include/percepnet_hip.h)
 struct PairStat { long frames = 0; long long clipped = 0; float peak = 0.f; double e_in = 0, e_out = 0; };
 static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, int postfilter, bool tap, int n_slots) {
@@ -149,62 +155,70 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
     pn_bind_thread_to_device_numa(sh->device, msg, sizeof(msg));
     if (g_verbose) fprintf(stderr, "percepnet_run: %s\n", msg);
   }
-  R.cx = pn_ctx_create(m, sh->device, B, nn_mode, NULL);
-  pn_ctx *cx = R.cx;
-  if (!cx) return fail(3, std::string("pn_ctx_create: ") + pn_last_error());
-  if (g_rate && !(R.rt = pn_rate_create(cx, g_rate))) return fail(3, std::string("pn_rate_create: ") + pn_last_error());
-  if (mixed && !(R.rt = pn_rate_create_mixed(cx, pair_rate))) return fail(3, std::string("pn_rate_create_mixed: ") + pn_last_error());   // slot s starts with pair s
-  pn_rate *rt = R.rt;
-  if (g_g711 > 0) {                                     // every slot's law, once (a new converter's is mu-law)
-    std::vector<int32_t> all(B), laws(B, g_g711);
-    for (int s = 0; s < B; s++) all[s] = s;
-    if (pn_rate_set_stream_laws(rt, all.data(), B, laws.data())) return fail(3, std::string("pn_rate_set_stream_laws: ") + pn_last_error());
-  }
   const bool conf = !g_confs.empty();
-  if (conf) {                                           // every slot's conference, once (one device, no --slots: slot s plays pair s)
-    std::vector<int32_t> all(B);
-    for (int s = 0; s < B; s++) all[s] = s;
-    if (pn_rate_set_stream_confs(rt, all.data(), B, g_confs.data() + sh->first)) return fail(3, std::string("pn_rate_set_stream_confs: ") + pn_last_error());
-    if (g_conf_speakers >= 0) {                         // one cap for every conference number
-      std::vector<int32_t> caps(B, g_conf_speakers);
-      if (pn_rate_set_conf_speakers(rt, all.data(), B, caps.data())) return fail(3, std::string("pn_rate_set_conf_speakers: ") + pn_last_error());
-    }
-    if (!g_mix_gains.empty() && pn_rate_set_stream_mix_gains(rt, all.data(), B, g_mix_gains.data() + sh->first))
-      return fail(3, std::string("pn_rate_set_stream_mix_gains: ") + pn_last_error());
-  }
-  if (g_plc && pn_rate_set_plc(rt, 1)) return fail(3, std::string("pn_rate_set_plc: ") + pn_last_error());
-  if (g_agc > 0.0f) {                                   // every slot's target, once (a setting: slot resets and rate changes keep it)
-    std::vector<int32_t> all(B);
-    std::vector<float> targets(B, g_agc);
-    float params[PN_AGC_N_PARAMS];
-    for (int s = 0; s < B; s++) all[s] = s;
-    pn_agc_default_params(params);
-    if (g_agc_max_gain > 0.0f) params[PN_AGC_MAX_GAIN] = g_agc_max_gain;
-    if (pn_rate_set_agc(rt, 1) || pn_rate_set_agc_params(rt, params) || pn_rate_set_stream_agc_targets(rt, all.data(), B, targets.data()))
-      return fail(3, std::string("--agc: ") + pn_last_error());
-  }
-  if (g_limiter > 0.0f) {                               // every slot's ceiling, once (a setting: slot resets and rate changes keep it)
-    std::vector<int32_t> all(B);
-    std::vector<float> ceilings(B, g_limiter);
-    float params[PN_LIM_N_PARAMS];
-    for (int s = 0; s < B; s++) all[s] = s;
-    pn_lim_default_params(params);
-    if (g_limiter_hold >= 0.0f) params[PN_LIM_HOLD] = g_limiter_hold;
-    if (pn_rate_set_limiter_params(rt, params) || pn_rate_set_stream_limiter(rt, all.data(), B, ceilings.data()))
-      return fail(3, std::string("--limiter: ") + pn_last_error());
-  }
-  if (postfilter) pn_ctx_set_postfilter(cx, 1);
-  if ((g_saturate && pn_ctx_set_output_saturate(cx, 1)) || (g_report && pn_ctx_set_report(cx, 1))) return fail(3, pn_last_error());
-  auto set_limit = [&](const int32_t *ids, int n) {     // --atten-lim on these slots (after creation and after every slot reset)
+  auto set_limit = [&](pn_ctx *c, const int32_t *ids, int n) {     // --atten-lim on these slots (after creation and after every slot reset)
     if (isinf(g_atten_lim) || n == 0) return 0;
     std::vector<float> db(n, g_atten_lim);
-    return pn_ctx_set_atten_limit(cx, ids, n, db.data());
+    return pn_ctx_set_atten_limit(c, ids, n, db.data());
   };
-  {
-    std::vector<int32_t> all(B);
-    for (int s = 0; s < B; s++) all[s] = s;
-    if (set_limit(all.data(), B)) return fail(3, std::string("pn_ctx_set_atten_limit: ") + pn_last_error());
-  }
+  // A context, the converter beside it and every setting of the command line: at the start (slot s starts with pair s, rates =
+  // pair_rate), and once more for --migrate-at (rates = the slots' rates at that frame).  false: the error is in sh, and the
+  // caller owns whatever cx and rt hold by then
+  auto make = [&](pn_ctx *&cx, pn_rate *&rt, const int32_t *rates) -> bool {
+    auto bad = [&](const std::string &msg) { fail(3, msg); return false; };
+    cx = pn_ctx_create(m, sh->device, B, nn_mode, NULL);
+    if (!cx) return bad(std::string("pn_ctx_create: ") + pn_last_error());
+    if (g_rate && !(rt = pn_rate_create(cx, g_rate))) return bad(std::string("pn_rate_create: ") + pn_last_error());
+    if (mixed && !(rt = pn_rate_create_mixed(cx, rates))) return bad(std::string("pn_rate_create_mixed: ") + pn_last_error());
+    if (g_g711 > 0) {                                     // every slot's law, once (a new converter's is mu-law)
+      std::vector<int32_t> all(B), laws(B, g_g711);
+      for (int s = 0; s < B; s++) all[s] = s;
+      if (pn_rate_set_stream_laws(rt, all.data(), B, laws.data())) return bad(std::string("pn_rate_set_stream_laws: ") + pn_last_error());
+    }
+    if (conf) {                                           // every slot's conference, once (one device, no --slots: slot s plays pair s)
+      std::vector<int32_t> all(B);
+      for (int s = 0; s < B; s++) all[s] = s;
+      if (pn_rate_set_stream_confs(rt, all.data(), B, g_confs.data() + sh->first)) return bad(std::string("pn_rate_set_stream_confs: ") + pn_last_error());
+      if (g_conf_speakers >= 0) {                         // one cap for every conference number
+        std::vector<int32_t> caps(B, g_conf_speakers);
+        if (pn_rate_set_conf_speakers(rt, all.data(), B, caps.data())) return bad(std::string("pn_rate_set_conf_speakers: ") + pn_last_error());
+      }
+      if (!g_mix_gains.empty() && pn_rate_set_stream_mix_gains(rt, all.data(), B, g_mix_gains.data() + sh->first))
+        return bad(std::string("pn_rate_set_stream_mix_gains: ") + pn_last_error());
+    }
+    if (g_plc && pn_rate_set_plc(rt, 1)) return bad(std::string("pn_rate_set_plc: ") + pn_last_error());
+    if (g_agc > 0.0f) {                                   // every slot's target, once (a setting: slot resets and rate changes keep it)
+      std::vector<int32_t> all(B);
+      std::vector<float> targets(B, g_agc);
+      float params[PN_AGC_N_PARAMS];
+      for (int s = 0; s < B; s++) all[s] = s;
+      pn_agc_default_params(params);
+      if (g_agc_max_gain > 0.0f) params[PN_AGC_MAX_GAIN] = g_agc_max_gain;
+      if (pn_rate_set_agc(rt, 1) || pn_rate_set_agc_params(rt, params) || pn_rate_set_stream_agc_targets(rt, all.data(), B, targets.data()))
+        return bad(std::string("--agc: ") + pn_last_error());
+    }
+    if (g_limiter > 0.0f) {                               // every slot's ceiling, once (a setting: slot resets and rate changes keep it)
+      std::vector<int32_t> all(B);
+      std::vector<float> ceilings(B, g_limiter);
+      float params[PN_LIM_N_PARAMS];
+      for (int s = 0; s < B; s++) all[s] = s;
+      pn_lim_default_params(params);
+      if (g_limiter_hold >= 0.0f) params[PN_LIM_HOLD] = g_limiter_hold;
+      if (pn_rate_set_limiter_params(rt, params) || pn_rate_set_stream_limiter(rt, all.data(), B, ceilings.data()))
+        return bad(std::string("--limiter: ") + pn_last_error());
+    }
+    if (postfilter) pn_ctx_set_postfilter(cx, 1);
+    if ((g_saturate && pn_ctx_set_output_saturate(cx, 1)) || (g_report && pn_ctx_set_report(cx, 1))) return bad(pn_last_error());
+    {
+      std::vector<int32_t> all(B);
+      for (int s = 0; s < B; s++) all[s] = s;
+      if (set_limit(cx, all.data(), B)) return bad(std::string("pn_ctx_set_atten_limit: ") + pn_last_error());
+    }
+    return true;
+  };
+  if (!make(R.cx, R.rt, pair_rate)) return;
+  pn_ctx *cx = R.cx;
+  pn_rate *rt = R.rt;
   std::vector<FILE *> &fin = R.fin, &fout = R.fout;
   fin.assign(B, NULL); fout.assign(B, NULL);
   int next_pair = 0;
@@ -258,6 +272,40 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
       if (sl.last[s]) { fclose(sl.file[s]); }        // the pair's last frame has been written: its output file is complete
     }
   };
+  // --migrate-at: a second context and converter with the same settings, every slot's three records across, the first pair destroyed.
+  // The order is the mover's (include/percepnet_hip.h "call-state records"): settings, the engine's record, the tails — one call per
+  // rate, none for a 48000 slot — and the call state, which the tails' import has just zeroed.  1: failed, the error is in sh
+  auto migrate = [&]() -> int {
+    if (pn_host_wait(cx)) { fail(5, pn_last_error()); return 1; }
+    std::vector<int32_t> all(B), rates(B);
+    for (int s = 0; s < B; s++) all[s] = s;
+    if (pn_rate_get_stream_rates(rt, rates.data())) { fail(5, pn_last_error()); return 1; }
+    pn_ctx *cx2 = NULL;
+    pn_rate *rt2 = NULL;
+    auto moved = [&]() -> bool {
+      if (!make(cx2, rt2, rates.data())) return false;
+      std::vector<char> rec((size_t)B * pn_stream_state_bytes());
+      if (pn_ctx_export_streams_host(cx, all.data(), B, rec.data()) || pn_ctx_import_streams_host(cx2, all.data(), B, rec.data())) return false;
+      for (int rate : {8000, 16000, 24000, 32000}) {
+        std::vector<int32_t> ids;
+        for (int s = 0; s < B; s++) if (rates[s] == rate) ids.push_back(s);
+        if (ids.empty()) continue;
+        rec.resize(ids.size() * pn_rate_state_bytes(rate));
+        if (pn_rate_export_streams_host(rt, ids.data(), (int)ids.size(), rec.data()) || pn_rate_import_streams_host(rt2, ids.data(), (int)ids.size(), rec.data())) return false;
+      }
+      rec.resize((size_t)B * pn_rate_call_state_bytes());
+      return !(pn_rate_export_call_state_host(rt, all.data(), B, rec.data()) || pn_rate_import_call_state_host(rt2, all.data(), B, rec.data()));
+    };
+    if (!moved()) {
+      if (!sh->rc) fail(5, std::string("--migrate-at: ") + pn_last_error());
+      pn_rate_destroy(rt2); pn_ctx_destroy(cx2);
+      return 1;
+    }
+    pn_rate_destroy(rt); pn_ctx_destroy(cx);
+    R.cx = cx = cx2; R.rt = rt = rt2;
+    if (g_verbose) fprintf(stderr, "percepnet_run: %d slots moved to a second context behind frame %ld\n", B, g_migrate_at);
+    return 0;
+  };
   std::vector<int32_t> restart, restart_rates, live;   // live (--conference): the slots whose pair still has input, this frame's id list
   std::vector<int32_t> lost;                           // --lose: the slots whose pair loses this frame
   int n_alive = B;
@@ -295,10 +343,13 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
       }
     }
     if (n_alive == 0) break;
+    if (t == g_migrate_at + 1 && g_migrate_at >= 0) {   // frame F is submitted: deliver it, then every slot moves
+      if (migrate()) return;
+    }
     if (!restart.empty() && (pn_ctx_reset_streams(cx, restart.data(), (int)restart.size()) ||
                              (rt && (mixed ? pn_rate_set_stream_rates(rt, restart.data(), (int)restart.size(), restart_rates.data())
                                            : pn_rate_reset_streams(rt, restart.data(), (int)restart.size()))) ||
-                             set_limit(restart.data(), (int)restart.size()))) return fail(5, pn_last_error());
+                             set_limit(cx, restart.data(), (int)restart.size()))) return fail(5, pn_last_error());
     if (!lost.empty() && pn_rate_set_lost(rt, lost.data(), (int)lost.size())) return fail(5, pn_last_error());
     if (g_report && pn_host_next_report(cx, sl.rep)) return fail(5, pn_last_error());
     // --rate, --rates: the converter's frame through the same pipeline
@@ -317,7 +368,7 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
 
 // the usage text, for a command line without pairs and for a rate no converter takes.  Returns the exit status, 1.
 static int usage(const char *argv0) {
-  fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N] [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--plc [--lose P:F0-F1,P:F,..]] [--agc RMS [--agc-max-gain G]] [--limiter CEIL [--limiter-hold H]] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv0);
+  fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N] [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--plc [--lose P:F0-F1,P:F,..]] [--agc RMS [--agc-max-gain G]] [--limiter CEIL [--limiter-hold H]] [--migrate-at F] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv0);
   return 1;
 }
 
@@ -432,6 +483,12 @@ int main(int argc, char **argv) {
       params[PN_LIM_HOLD] = g_limiter_hold;
       if (end == v || *end || pn_lim_params_check(params)) { fprintf(stderr, "--limiter-hold: expected a whole number of frames in [0, 1000], got '%s'\n", v); return 1; }
     }
+    else if (!strcmp(argv[ai], "--migrate-at") && ai + 1 < argc) {    // move every slot to a second context and converter behind this frame
+      const char *v = argv[++ai];
+      char *end = NULL;
+      g_migrate_at = strtol(v, &end, 10);
+      if (end == v || *end || g_migrate_at < 0) { fprintf(stderr, "--migrate-at: expected a frame number >= 0, got '%s'\n", v); return 1; }
+    }
     else if (!strcmp(argv[ai], "--no-numa")) g_numa = false;        // leave the host threads' CPU affinity alone
     else if (!strcmp(argv[ai], "--verbose")) g_verbose = true;       // one line per device: its NUMA binding
     else if (!strcmp(argv[ai], "--slots") && ai + 1 < argc) n_slots = atoi(argv[++ai]);   // concurrent streams per device: pairs queue for them
@@ -474,6 +531,10 @@ int main(int argc, char **argv) {
   if (g_agc_max_gain > 0.0f && !(g_agc > 0.0f)) { fprintf(stderr, "--agc-max-gain needs --agc: it is a parameter of the level control\n"); return 1; }
   if (g_limiter_hold >= 0.0f && !(g_limiter > 0.0f)) { fprintf(stderr, "--limiter-hold needs --limiter: it is a parameter of the output limiter\n"); return 1; }
   if ((g_plc || g_agc > 0.0f || g_limiter > 0.0f) && !g_rate && g_rates.empty()) g_rates.assign(B, 48000);        // on its own: a mixed converter of all 48000
+  if (g_migrate_at >= 0) {
+    if (devices.size() > 1) { fprintf(stderr, "--migrate-at takes one device: the slots move between two contexts of one device\n"); return 1; }
+    if (!g_rate && g_rates.empty()) { fprintf(stderr, "--migrate-at needs a converter (--rate or --rates): it moves the converter's records with the engine's\n"); return 1; }
+  }
   pn_model *m = NULL;
   if (model_path) { FILE *f = fopen(model_path, "rb"); if (f) { m = pn_model_from_file(f); fclose(f); } }
   else if (&percepnet_model_orig) m = pn_model_from_rnnmodel(&percepnet_model_orig);

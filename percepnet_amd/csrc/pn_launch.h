@@ -126,6 +126,11 @@ void pn_launch_rate_agc(hipStream_t st, int n_rows, const int *d_ids, const floa
 // [.][480], in place.  d_ceilings [n_streams]: +0.0 = the stream is not limited; params: the converter's PN_LIM_N_PARAMS floats on the
 // HOST, passed by value.  State [n_streams][4] words; d_report [n_streams][4] words or NULL
 void pn_launch_rate_lim(hipStream_t st, int n_rows, const int *d_ids, const float *d_ceilings, const float *params, float *o48, void *state, void *d_report);
+// call-state records (pn_rate_call.hip; layout and verdict pn_call_rules.h): record i of rec [n][PN_RATE_CALL_STATE_BYTES] (16-byte aligned)
+// <-> the PLC, AGC, limiter and level state of stream d_ids[i].  held: the PN_CALL_* states the converter holds — a state's pointers
+// are read only under its bit and may be NULL otherwise.  scatter: d_status[i] receives record i's verdict, a refused record moves nothing
+void pn_launch_rate_call_state(hipStream_t st, const int *d_ids, int n, uint32_t held, float *hist, float *q, void *meta, void *agc_state, void *lim_state,
+                               float *level, void *rec, int *d_status, int scatter);
 // ---- the network launchers (pn_nn*.hip) -----------------------------------------------------------------------------------------
 // Device pointers of a layer's biases and weights in the formats of pn_network.h: raw (w, rw), packed fp32 or fp16 planes (wp,
 // rwp), the 16x16x4 packing of a narrow layer (wq)

@@ -13,6 +13,7 @@
 #include "pn_plc_rules.h"    // packet-loss concealment: the signal rule for the host, the sizes of the state
 #include "pn_agc_rules.h"    // automatic level control: the rule for the host, what parameters and targets must be
 #include "pn_lim_rules.h"    // the output limiter: the rule for the host, what parameters and ceilings must be
+#include "pn_call_rules.h"   // call-state records: the layout and the verdict
 #include <string>
 #include <vector>
 
@@ -1043,4 +1044,56 @@ static int rate_records_dev(pn_rate *r, bool import, const int32_t *ids, int n, 
 extern "C" int pn_rate_export_streams(pn_rate *r, const int32_t *ids, int n, void *d_records) { return rate_records_dev(r, false, ids, n, d_records, NULL); }
 extern "C" int pn_rate_import_streams(pn_rate *r, const int32_t *ids, int n, const void *d_records, int32_t *d_status) {
   return rate_records_dev(r, true, ids, n, const_cast<void *>(d_records), d_status);
+}
+
+// ---- call-state records (include/percepnet_hip.h; layout and verdict pn_call_rules.h; the kernel pn_rate_call.hip) ----------------
+// The second record of a stream: the PLC, AGC, limiter and level state, whatever its rate.  Nothing here allocates state: a section
+// the converter does not hold is zero on export and dropped on import.
+static uint32_t call_held(const pn_rate *r) {
+  return (r->plc ? PN_CALL_PLC : 0u) | (r->d_agc_state ? PN_CALL_AGC : 0u) | (r->d_lim_state ? PN_CALL_LIM : 0u) | (r->d_level ? PN_CALL_MIX : 0u);
+}
+extern "C" size_t pn_rate_call_state_bytes(void) { return PN_RATE_CALL_STATE_BYTES; }
+extern "C" int pn_rate_call_state_check(const void *record, size_t bytes) { return pn_call_record_check(record, bytes); }
+extern "C" int pn_rate_call_state_sections(const pn_rate *r) { if (!r) { pn_set_error("NULL argument"); return -1; } return (int)call_held(r); }
+// the launch alone: the caller is on the context's device and has checked ids, pointers and alignment
+static int call_state_launch(pn_rate *r, bool import, const int32_t *ids, int n, void *d_records, int32_t *d_status) {
+  const int *d = stage_ids(r->c, ids, n);
+  if (!d) return -1;
+  pn_launch_rate_call_state(r->c->stream, d, n, call_held(r), r->d_plc_hist, r->d_plc_q, r->d_plc_meta, r->d_agc_state, r->d_lim_state, r->d_level, d_records,
+                            d_status, import ? 1 : 0);
+  PN_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+static int call_state_dev(pn_rate *r, bool import, const int32_t *ids, int n, void *d_records, int32_t *d_status) {
+  if (!r || n < 0 || (n > 0 && (!ids || !d_records || (import && !d_status)))) { pn_set_error("bad argument"); return -1; }
+  if (n == 0) return 0;
+  if ((uintptr_t)d_records & 15) { pn_set_error("records must be 16-byte aligned"); return -1; }
+  if (pn_ids_check(r->c->B, ids, n, import)) return -1;
+  PN_ON_DEVICE(r->c);
+  return call_state_launch(r, import, ids, n, d_records, d_status);
+}
+extern "C" int pn_rate_export_call_state(pn_rate *r, const int32_t *ids, int n, void *d_records) { return call_state_dev(r, false, ids, n, d_records, NULL); }
+extern "C" int pn_rate_import_call_state(pn_rate *r, const int32_t *ids, int n, const void *d_records, int32_t *d_status) {
+  return call_state_dev(r, true, ids, n, const_cast<void *>(d_records), d_status);
+}
+// Host forms: synchronous through host_records_sync, like the tails records'.  The import judges every record with the kernel's own
+// verdict before anything is launched; the statuses the kernel then writes come back with the transfer and must all be PN_SS_OK.
+extern "C" int pn_rate_export_call_state_host(pn_rate *r, const int32_t *ids, int n, void *h_records) {
+  if (!r || n < 0 || (n > 0 && (!ids || !h_records))) { pn_set_error("bad argument"); return -1; }
+  if (n == 0) return 0;
+  if (pn_ids_check(r->c->B, ids, n, false)) return -1;
+  return host_records_sync(r->c, false, h_records, (size_t)n * PN_RATE_CALL_STATE_BYTES, [&](void *d) { return call_state_launch(r, false, ids, n, d, NULL); });
+}
+extern "C" int pn_rate_import_call_state_host(pn_rate *r, const int32_t *ids, int n, const void *h_records) {
+  if (!r || n < 0 || (n > 0 && (!ids || !h_records))) { pn_set_error("bad argument"); return -1; }
+  if (n == 0) return 0;
+  if (pn_ids_check(r->c->B, ids, n, true)) return -1;
+  if (pn_records_check(h_records, n, PN_RATE_CALL_STATE_BYTES, [&](const void *rec, size_t b) { return pn_call_record_check(rec, b); })) return -1;
+  const size_t bytes = (size_t)n * PN_RATE_CALL_STATE_BYTES;
+  std::vector<int32_t> status(n, 0);
+  int rc = host_records_sync(r->c, true, const_cast<void *>(h_records), bytes, [&](void *d) {
+    return call_state_launch(r, true, ids, n, d, reinterpret_cast<int32_t *>(static_cast<char *>(d) + bytes)); }, status.data(), (size_t)n * sizeof(int32_t));
+  for (int i = 0; i < n && !rc; i++)
+    if (status[i]) { pn_set_error("record %d refused on the device (%d) after passing the host check", i, status[i]); rc = -1; }
+  return rc;
 }
