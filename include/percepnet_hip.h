@@ -534,7 +534,7 @@ int pn_rate_export_streams(pn_rate *r, const int32_t *ids, int n, void *d_record
 int pn_rate_import_streams(pn_rate *r, const int32_t *ids, int n, const void *d_records, int32_t *d_status);
 /* Timing of the converter's two kernels inside a frame: HIP events around their launches, like pn_ctx_set_profiling but owned by
    the converter (the context's family list does not change).  Off by default; off, no event is created or recorded.  name:
-   "rate_up" | "rate_down" | "rate_mix" (the conference mix, below) | "rate_plc" (packet-loss concealment, below) | "rate_agc" (automatic level control, below) | "rate_lim" (the output limiter, below).  pn_rate_kernel_time synchronises the context's stream. */
+   "rate_up" | "rate_down" | "rate_mix" (the conference mix, below) | "rate_plc" (packet-loss concealment, below) | "rate_agc" (automatic level control, below) | "rate_lim" (the output limiter, below) | "rate_dtmf" (DTMF detection, below).  pn_rate_kernel_time synchronises the context's stream. */
 int pn_rate_set_profiling(pn_rate *r, int enable);
 int pn_rate_kernel_time(pn_rate *r, const char *name, double *total_ms, int64_t *launches);
 int pn_rate_reset_profile(pn_rate *r);
@@ -1110,6 +1110,103 @@ int pn_rate_export_call_state(pn_rate *r, const int32_t *ids, int n, void *d_rec
 int pn_rate_import_call_state(pn_rate *r, const int32_t *ids, int n, const void *d_records, int32_t *d_status);
 int pn_rate_export_call_state_host(pn_rate *r, const int32_t *ids, int n, void *h_records);
 int pn_rate_import_call_state_host(pn_rate *r, const int32_t *ids, int n, const void *h_records);
+
+/* ---- DTMF detection: a pressed key is read on the GPU ------------------------------------------------------------------------------ */
+/* "Press 1 to mute", PINs and menu choices arrive as in-band dual tones (DTMF).  The detector reads each ENABLED stream's 48 kHz fp32
+   row behind the up-conversion and the concealer and IN FRONT of the engine — the network keeps speech and drops everything else, and
+   what it does to a dual tone is unmeasured — in one kernel (csrc/pn_rate_dtmf.hip), on a pn_rate of any kind, whatever the stream's
+   rate or coding.  It only reads the rows: the audio is bit for bit what it is without detection, the tone included.
+   OFF by default for every stream: a converter on which no stream is enabled launches exactly what it launches without this section
+   (the host keeps the count of enabled streams).
+
+   The rule, with every rounding and summation order, is csrc/pn_dtmf_rules.h (HIP-free); tests/dtmf_model.py restates it in numpy
+   float32 and the kernel matches both bit for bit.  Every fp32 operation is singly rounded, no product is contracted into an add.
+   Frequencies f[0..3] = 697, 770, 852, 941 Hz (rows), f[4..7] = 1209, 1336, 1477, 1633 Hz (columns); the digit code of row r and column c
+   is the ASCII of "123A456B789C*0#D"[4r + c].  Tables in double, narrowed once: m = (f[k]*j) % 48000 in integers,
+   a = 6.283185307179586*m/48000.0, ct[k][j] = (float)cos(a), st[k][j] = (float)sin(a), j = 0..479; the frame's rotation cr[k], ci[k]
+   from m = (f[k]*480) % 48000.  pn_dtmf_tables(ct[8][480], st[8][480], rot16 = cr then ci) copies them out (host only).
+   Parameters, one set per converter, PN_DTMF_N_PARAMS = 7 floats:
+     0 PN_DTMF_MIN_RMS   [0, 1] 0.005     1 PN_DTMF_PURITY (0, 1] 0.5      2 PN_DTMF_TWIST_FWD [1, 100] 6.3   3 PN_DTMF_TWIST_REV [1, 100] 6.3
+     4 PN_DTMF_REL       [1, 100] 6.3     5 PN_DTMF_ON_FRAMES, 6 PN_DTMF_OFF_FRAMES: whole numbers in [1, 100], 3 and 2
+   State per stream (96 bytes = 24 words, allocated by the first enabling, never inside a frame; all zero is fresh): 0..7 Cp, 8..15 Sp,
+   16 Ep — the previous row's half sums — 17 cand | run << 16, 18 cur | gap << 16, 19 dur, 20 count, 21 last4, 22 and 23 zero.
+   One frame of an advancing, enabled stream, x = its 480-sample row:
+     half sums: C[k] = sum x[j]*ct[k][j], S[k] = sum x[j]*st[k][j], Ec = sum x[j]*x[j]; all 17 in the order of pn_mix_level: products
+                rounded separately, 120 groups of four from +0.0f in index order, padded to 128, two halves of 64 folded by the xor
+                butterfly 32..1, the sum = half0[0] + half1[0].
+     window:    the 20 ms of the previous row and this one: A = Cp + (C*cr - S*ci), B = Sp + (S*cr + C*ci), every product and sum rounded
+                separately in that bracketing; P[k] = A*A + B*B; E = Ep + Ec; then Cp, Sp, Ep = C, S, Ec.
+     peaks:     Pr = -1.0f, r = 0; k = 0..3 in order: P[k] > Pr -> Pr = P[k], r = k; Pc and c likewise over k = 4..7.  Ties go to the lower
+                index, a NaN never wins.
+     hit:       E <= FLT_MAX && E >= (min_rms*min_rms)*960.0f && Pr + Pc >= (purity*480.0f)*E && Pc <= Pr*twist_fwd && Pr <= Pc*twist_rev
+                && P[k]*rel <= its group's peak for every other k of either group; any NaN makes it false.  (A pure dual tone has
+                P[r] + P[c] = 480 E.)      d = the digit code on a hit, else 0.
+     debounce:  1. d != 0 && d == cand: run += 1 (saturating at 65535); otherwise cand = d, run = d ? 1 : 0.
+                2. cur != 0 && d == cur: gap = 0, dur += 1.
+                3. cur != 0 && d != cur: gap += 1; gap >= off_frames: END, the ended digit and its dur go to the report, cur = 0 (gap and
+                   dur too); otherwise dur += 1.
+                4. cur == 0 && d != 0 && run >= on_frames: cur = d, gap = 0, dur = run, count += 1 (saturating), BEGIN,
+                   last4 = (last4 << 8) | d.   (With on_frames = off_frames = 1 a changed digit ENDs and BEGINs in one frame.)
+     concealed (PLC filled this frame for the stream): the whole state stays, the row is not read; the report repeats cur with HELD_LOST.
+     not enabled: neither the row nor the state is read; the report row is four zero words.
+
+   pn_rate_set_stream_dtmf(r, ids, n, on) / pn_rate_get_stream_dtmf(r, h_on[n_streams]): the id list rules of
+     pn_rate_set_stream_limiter (distinct ids in range, the first offender named, n == 0 a no-op); on[i] != 0 enables.  A setting,
+     asynchronous on the context's stream and ordered against frames like the limiter's ceilings, on the pipelined path too.  The first
+     enabling allocates the state, the switch words and the tables; a frame never allocates.  Enabling a stream that was off zeroes its
+     state; enabling one that is on, or disabling, leaves it.
+   pn_rate_set_dtmf_params(r, params[7]) / pn_rate_get_dtmf_params: one set for the converter, from the next frame submitted on (they
+     travel as an argument of every launch, so they are ordered like one).  Refused with -1, nothing changed: NaN, a value outside its
+     range or a frame count that is no whole number, pn_last_error naming the FIRST bad index.  Host only: pn_dtmf_default_params,
+     pn_dtmf_params_check.
+   pn_rate_dtmf_f32(r, d_x48, ids, n_ids): the kernel on its own over [n_streams][480] float rows at a 16-byte aligned device address,
+     ids as for pn_rate_up_*; nobody counts as concealed.
+   pn_dtmf_frame(params, state24, row480, concealed, report4) -> the report's flags, or -1 for a bad argument: host only, the rule above
+     on one row of an enabled stream; state24 is read and written, report4 may be NULL.
+   pn_rate_kernel_time takes "rate_dtmf".
+   DTMF report (optional; pn_rate_set_dtmf_report, pn_rate_read_dtmf_report synchronising, pn_rate_read_dtmf_report_dev asynchronous on
+     the context's stream; -1 while off): PN_DTMF_REPORT_WORDS = 4 little-endian 32-bit words per stream, [n_streams][4], written for
+     every stream that advances in a frame that launches the kernel:
+     word 0  flags | cur << 8 | ended << 16: PN_DTMF_ON the stream is enabled, PN_DTMF_HIT this frame's window is a digit's,
+             PN_DTMF_BEGIN cur began in this frame, PN_DTMF_END `ended` ended in it, PN_DTMF_HELD_LOST the frame was concealed
+     word 1  the dur of cur in frames — or, with cur == 0 in a frame that ENDs, of the digit that ended
+     word 2  count, the digits begun since the state was fresh
+     word 3  last4, the four digits begun last, newest in the low byte: a caller that reads less often than every frame loses none
+   It is NOT part of pn_host_next_report.
+   Lifecycle.  pn_rate_reset zeroes the detector state of every stream; pn_rate_reset_streams, pn_rate_set_stream_rates and both import
+   forms (pn_rate_import_streams, pn_rate_import_streams_host) that of the listed slots.  A stream that does not advance keeps its
+   state.  Switches and parameters are settings that survive all of those.  NO record carries the detector state — the three record
+   formats are untouched — so a digit in flight when a call moves is reported AGAIN with BEGIN on the target (count and last4 start
+   from zero there).  With PLC on, a stream is concealed in the frame whose marks the concealer consumed.
+   NOT provided: removing or muting the tone in the audio; RFC 4733 events; second-harmonic talk-off tests; any claim of Q.24
+   conformance; detection without a converter; detector state in a record; the report on pn_host_next_report. */
+#define PN_DTMF_N_PARAMS 7
+#define PN_DTMF_MIN_RMS 0
+#define PN_DTMF_PURITY 1
+#define PN_DTMF_TWIST_FWD 2
+#define PN_DTMF_TWIST_REV 3
+#define PN_DTMF_REL 4
+#define PN_DTMF_ON_FRAMES 5
+#define PN_DTMF_OFF_FRAMES 6
+#define PN_DTMF_REPORT_WORDS 4
+#define PN_DTMF_ON 1
+#define PN_DTMF_HIT 2
+#define PN_DTMF_BEGIN 4
+#define PN_DTMF_END 8
+#define PN_DTMF_HELD_LOST 16
+int pn_dtmf_default_params(float *params7);               /* host only */
+int pn_dtmf_params_check(const float *params7);           /* host only */
+int pn_dtmf_frame(const float *params7, uint32_t *state24, const float *row480, int concealed, uint32_t *report4);   /* host only */
+int pn_dtmf_tables(float *ct, float *st, float *rot16);   /* host only */
+int pn_rate_set_stream_dtmf(pn_rate *r, const int32_t *ids, int n, const uint8_t *on);
+int pn_rate_get_stream_dtmf(const pn_rate *r, uint8_t *h_on);
+int pn_rate_set_dtmf_params(pn_rate *r, const float *params7);
+int pn_rate_get_dtmf_params(const pn_rate *r, float *params7);
+int pn_rate_dtmf_f32(pn_rate *r, const float *d_x48, const int32_t *ids, int n_ids);
+int pn_rate_set_dtmf_report(pn_rate *r, int enable);
+int pn_rate_read_dtmf_report(pn_rate *r, void *h_report);
+int pn_rate_read_dtmf_report_dev(pn_rate *r, void *d_report);
+int pn_rate_debug_dtmf_state(pn_rate *r, void *h_state);   /* tests and debugging: [n_streams][24] state words to the host, synchronising; zeros while no stream was ever enabled */
 
 const char *pn_last_error(void);
 const char *pn_version(void);

@@ -49,6 +49,13 @@ LIM_REPORT_WORDS = 4
 LIM_ON, LIM_ATTACK, LIM_HOLDING, LIM_RELEASING, LIM_ACTIVE, LIM_NONFINITE = 1, 2, 4, 8, 16, 32   # its flags
 LIM_REPORT_DTYPE = np.dtype([("gain", "<f4"), ("peak", "<f4"), ("flags", "<u4"), ("limited", "<u4")])
 LIM_STATE_DTYPE = np.dtype([("gain", "<f4"), ("hold", "<u4"), ("limited", "<u4"), ("spare", "<u4")])   # the four state words of lim_frame
+# DTMF detection (include/percepnet_hip.h "DTMF detection"): PN_DTMF_*
+DTMF_N_PARAMS = 7
+DTMF_MIN_RMS, DTMF_PURITY, DTMF_TWIST_FWD, DTMF_TWIST_REV, DTMF_REL, DTMF_ON_FRAMES, DTMF_OFF_FRAMES = range(7)   # parameter indices
+DTMF_REPORT_WORDS, DTMF_STATE_WORDS = 4, 24
+DTMF_ON, DTMF_HIT, DTMF_BEGIN, DTMF_END, DTMF_HELD_LOST = 1, 2, 4, 8, 16          # its flags, the low byte of report word 0
+DTMF_REPORT_DTYPE = np.dtype([("word0", "<u4"), ("dur", "<u4"), ("count", "<u4"), ("last4", "<u4")])   # word0: flags | cur << 8 | ended << 16
+DTMF_ROWS_PER_PASS = 2048    # the kernel's grid covers this many rows at once (csrc/pn_launch.h PN_DTMF_MAX_BLOCKS blocks of four); beyond it a block makes further passes
 # call-state records (include/percepnet_hip.h "call-state records"): PN_RATE_CALL_*, PN_CALL_*
 SS_BAD_STATE = -7         # pn_rate_call_state_check: a body that breaks an invariant, an unknown section, words in an absent section
 RATE_CALL_MAGIC, RATE_CALL_VERSION, RATE_CALL_STATE_BYTES = 0x53434E50, 1, 10640
@@ -266,6 +273,17 @@ def load_library():
         for name in ("pn_rate_export_call_state", "pn_rate_export_call_state_host", "pn_rate_import_call_state_host"):
             getattr(L, name).argtypes = [_vp, _vp, ctypes.c_int, _vp]
         L.pn_rate_import_call_state.argtypes = [_vp, _vp, ctypes.c_int, _vp, _vp]
+    if hasattr(L, "pn_rate_set_stream_dtmf"):
+        for name in ("pn_dtmf_default_params", "pn_dtmf_params_check"):
+            getattr(L, name).argtypes = [_vp]
+        L.pn_dtmf_frame.argtypes = [_vp, _vp, _vp, ctypes.c_int, _vp]
+        L.pn_dtmf_tables.argtypes = [_vp, _vp, _vp]
+        L.pn_rate_set_dtmf_report.argtypes = [_vp, ctypes.c_int]
+        for name in ("pn_rate_set_dtmf_params", "pn_rate_get_dtmf_params", "pn_rate_get_stream_dtmf", "pn_rate_read_dtmf_report",
+                     "pn_rate_read_dtmf_report_dev", "pn_rate_debug_dtmf_state"):
+            getattr(L, name).argtypes = [_vp, _vp]
+        L.pn_rate_set_stream_dtmf.argtypes = [_vp, _vp, ctypes.c_int, _vp]
+        L.pn_rate_dtmf_f32.argtypes = [_vp, _vp, _vp, ctypes.c_int]
     if hasattr(L, "pn_host_pipeline_prepare"):
         L.pn_host_pipeline_prepare.argtypes = [_vp]
     L.pn_ctx_debug_copy.restype = ctypes.c_longlong
@@ -804,6 +822,53 @@ def lim_frame(params, ceiling, state, row, want_report=False):
     return (out, int(flags), rep) if want_report else (out, int(flags))
 
 
+def dtmf_default_params():
+    """-> float32 [DTMF_N_PARAMS]: the DTMF detector's default parameters (pn_dtmf_default_params, host only)."""
+    p = np.empty(DTMF_N_PARAMS, np.float32)
+    load_library().pn_dtmf_default_params(p.ctypes.data)
+    return p
+
+
+def _dtmf_params(params):
+    p = np.ascontiguousarray(params, dtype=np.float32).ravel()
+    if p.size != DTMF_N_PARAMS:
+        raise PercepNetError(f"{p.size} DTMF parameters: a set has {DTMF_N_PARAMS}")
+    return p
+
+
+def dtmf_params_check(params):
+    """Raises PercepNetError naming the first parameter that is NaN, outside its range or no whole number where one is asked
+    (pn_dtmf_params_check, host only)."""
+    L = load_library()
+    if L.pn_dtmf_params_check(_dtmf_params(params).ctypes.data) != 0:
+        raise PercepNetError(_err(L))
+
+
+def dtmf_tables():
+    """-> (ct float32 [8, 480], st float32 [8, 480], rot float32 [16] = cr then ci): the detector's tables (pn_dtmf_tables, host only)."""
+    ct, st, rot = np.empty((8, 480), np.float32), np.empty((8, 480), np.float32), np.empty(16, np.float32)
+    L = load_library()
+    if L.pn_dtmf_tables(ct.ctypes.data, st.ctypes.data, rot.ctypes.data) != 0:
+        raise PercepNetError(_err(L))
+    return ct, st, rot
+
+
+def dtmf_frame(params, state, row, concealed=False):
+    """One frame of the DTMF detector on one row of 480 samples of an enabled stream (pn_dtmf_frame, host only).  state: uint32
+    [DTMF_STATE_WORDS] (zeros are fresh), updated IN PLACE -> (the flags, the DTMF_REPORT_DTYPE row)."""
+    L = load_library()
+    x = np.ascontiguousarray(row, dtype=np.float32).ravel()
+    if x.size != 480:
+        raise PercepNetError(f"a row of {x.size} samples: the detector takes 480")
+    if not isinstance(state, np.ndarray) or state.dtype != np.uint32 or state.size != DTMF_STATE_WORDS or not state.flags.c_contiguous or not state.flags.writeable:
+        raise PercepNetError(f"state: {DTMF_STATE_WORDS} writable contiguous uint32 words")
+    rep = np.zeros((), DTMF_REPORT_DTYPE)
+    flags = L.pn_dtmf_frame(_dtmf_params(params).ctypes.data, state.ctypes.data, x.ctypes.data, 1 if concealed else 0, rep.ctypes.data)
+    if flags < 0:
+        raise PercepNetError(_err(L))
+    return int(flags), rep
+
+
 class RateConverter:
     """8, 16, 24 or 32 kHz streams through a 48 kHz Context (pn_rate): a converter beside `ctx` for all of its streams at ONE rate.
     It borrows the context (device, n_streams, HIP stream): close the converter before the context."""
@@ -1188,6 +1253,60 @@ class RateConverter:
         a, n = self._ids(ids)
         self._chk(self.L.pn_rate_import_streams(self.h, a.ctypes.data, n, d_records, d_status))
 
+    # DTMF detection: an enabled stream's 48 kHz row is read behind the concealer and in front of the engine; the audio is untouched
+    def set_stream_dtmf(self, ids, on):
+        """Detection on or off for the streams `ids` from the next frame on (pn_rate_set_stream_dtmf): asynchronous, ordered like
+        set_stream_limiter.  `on`: one value for all of them or one per id.  A stream that was off starts from the fresh state."""
+        a, n = self._ids(ids)
+        w = np.asarray(on).astype(bool).astype(np.uint8).ravel()
+        if w.size == 1:
+            w = np.repeat(w, n)
+        if w.size != n:
+            raise PercepNetError(f"{w.size} switches for {n} streams")
+        w = np.ascontiguousarray(w)
+        self._chk(self.L.pn_rate_set_stream_dtmf(self.h, a.ctypes.data, n, w.ctypes.data))
+
+    def stream_dtmf(self):
+        """-> uint8 [n_streams]: the switches as last set (pn_rate_get_stream_dtmf); 0 everywhere on a new converter."""
+        w = np.empty(self.n_streams, np.uint8)
+        self._chk(self.L.pn_rate_get_stream_dtmf(self.h, w.ctypes.data))
+        return w
+
+    def set_dtmf_params(self, params):
+        """The converter's DTMF_N_PARAMS parameters from the next frame on (pn_rate_set_dtmf_params); refused as a whole, naming the
+        first bad one."""
+        self._chk(self.L.pn_rate_set_dtmf_params(self.h, _dtmf_params(params).ctypes.data))
+
+    def dtmf_params(self):
+        """-> float32 [DTMF_N_PARAMS] as last set (pn_rate_get_dtmf_params); dtmf_default_params() on a new converter."""
+        p = np.empty(DTMF_N_PARAMS, np.float32)
+        self._chk(self.L.pn_rate_get_dtmf_params(self.h, p.ctypes.data))
+        return p
+
+    def dtmf_f32_dev(self, d_x48, ids=None):
+        """The detector on its own over device rows [n_streams][480] float, which it only reads (pn_rate_dtmf_f32); nobody counts as concealed."""
+        a, n = self._ids(ids)
+        self._chk(self.L.pn_rate_dtmf_f32(self.h, d_x48, a.ctypes.data if a is not None else None, n))
+
+    def set_dtmf_report(self, on):
+        self._chk(self.L.pn_rate_set_dtmf_report(self.h, 1 if on else 0))
+
+    def read_dtmf_report(self):
+        """-> DTMF_REPORT_DTYPE [n_streams]: the records of the last frame that ran the detector (pn_rate_read_dtmf_report, synchronising)."""
+        rep = np.empty(self.n_streams, DTMF_REPORT_DTYPE)
+        self._chk(self.L.pn_rate_read_dtmf_report(self.h, rep.ctypes.data))
+        return rep
+
+    def dtmf_state(self):
+        """-> uint32 [n_streams, DTMF_STATE_WORDS]: the detector's state words (pn_rate_debug_dtmf_state, synchronising): for tests."""
+        st = np.empty((self.n_streams, DTMF_STATE_WORDS), np.uint32)
+        self._chk(self.L.pn_rate_debug_dtmf_state(self.h, st.ctypes.data))
+        return st
+
+    def read_dtmf_report_dev(self, d_report):
+        """The same into device memory [n_streams][4] words, asynchronous on the context's stream (pn_rate_read_dtmf_report_dev)."""
+        self._chk(self.L.pn_rate_read_dtmf_report_dev(self.h, d_report))
+
     # call-state records (include/percepnet_hip.h "call-state records"): the PLC, AGC, limiter and level state, one size for every
     # rate; imported BEHIND import_streams, which zeroes those states.  Defined here once: a mixed converter uses them unchanged
     def call_state_sections(self):
@@ -1233,7 +1352,7 @@ class RateConverter:
 
     def kernel_times(self, names=("rate_up", "rate_down")):
         """-> {"rate_up": (total_ms, launches), "rate_down": (...)}; names: which kernels ("rate_mix" is the conference mix,
-        "rate_plc" the packet-loss concealer, "rate_agc" the level control, "rate_lim" the output limiter)"""
+        "rate_plc" the packet-loss concealer, "rate_agc" the level control, "rate_lim" the output limiter, "rate_dtmf" the DTMF detector)"""
         out = {}
         for name in names:
             ms = ctypes.c_double()

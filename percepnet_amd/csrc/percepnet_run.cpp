@@ -5,7 +5,7 @@
 // dropped, main.cpp:32-33); with a single pair ./feature_test.raw gets 68 floats per frame.
 //
 //   percepnet_run [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N]
-//                 [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--plc [--lose P:F0-F1,P:F,..]] [--agc RMS [--agc-max-gain G]] [--limiter CEIL [--limiter-hold H]] [--migrate-at F] [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
+//                 [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--plc [--lose P:F0-F1,P:F,..]] [--agc RMS [--agc-max-gain G]] [--limiter CEIL [--limiter-hold H]] [--dtmf [--dtmf-on-frames N]] [--migrate-at F] [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
 //                 in0.pcm out0.pcm [in1.pcm out1.pcm ...]
 //
 // --rate R: the files are raw int16 at R Hz instead of 48 kHz, in frames of n = 480 * R / 48000 samples (80 | 160 | 240 | 320): a rate
@@ -56,6 +56,14 @@
 // slot's gain again and keeps its ceiling).  With --rate or --rates it uses their converter, alone it makes a mixed converter of all
 // 48000, as --agc does.  --limiter-hold H: the frames the gain is held after an attack, a whole number in [0, 1000] (parameter
 // PN_LIM_HOLD; default 2); it needs --limiter.
+// --dtmf: in-band DTMF detection on the converter (pn_rate_set_stream_dtmf for every slot, once: a slot reset starts the slot's detector
+// again and keeps its switch): one line "dtmf: pair P frame F digit D" on stdout for every digit that BEGINs, P counted over the whole
+// command line and F over the pair's frames, both from 0.  The audio is untouched.  The DTMF report is not part of the pipelined
+// path's report, so the run reads it (pn_rate_read_dtmf_report, synchronising) behind every submit: with --dtmf a frame's GPU work no
+// longer overlaps the next frame's file reads.  With --rate or --rates it uses their converter, alone it makes a mixed converter of all
+// 48000, as --agc does.  --dtmf-on-frames N: the hits in a row that begin a digit, a whole number in [1, 100] (parameter
+// PN_DTMF_ON_FRAMES; default 3); it needs --dtmf.  With --migrate-at a digit in flight at the move is reported again: no record carries
+// the detector's state.
 // --migrate-at F (needs a converter — --rate, --rates or an option that makes one — and one device): when frame F (the shard's frames
 // count from 0) has been delivered, the run builds a SECOND context and converter with the same settings, moves every slot there with
 // all three record kinds in the mover's order of include/percepnet_hip.h "call-state records" (the engine's, the converter's tails,
@@ -134,6 +142,8 @@ static bool g_plc = false;                            // --plc: packet-loss conc
 struct LoseRange { long pair, f0, f1; };
 static std::vector<LoseRange> g_lose;                 // --lose: pair, first and last lost frame of the pair
 static float g_agc = 0.0f, g_agc_max_gain = 0.0f;     // --agc: every pair's target RMS (0: not given); --agc-max-gain (0: not given)
+static bool g_dtmf = false;                            // --dtmf: detection on every pair
+static float g_dtmf_on_frames = 0.0f;                  // --dtmf-on-frames (0: not given)
 static float g_limiter = 0.0f, g_limiter_hold = -1.0f; // --limiter: every pair's ceiling (0: not given); --limiter-hold (-1: not given)
 static long g_migrate_at = -1;                        // --migrate-at: the frame behind which every slot moves to a second context and converter (-1: not given)
 // --report: what a pair's written frames add up to (one report record = PN_REPORT_WORDS words, include/percepnet_hip.h)
@@ -207,6 +217,16 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
       if (pn_rate_set_limiter_params(rt, params) || pn_rate_set_stream_limiter(rt, all.data(), B, ceilings.data()))
         return bad(std::string("--limiter: ") + pn_last_error());
     }
+    if (g_dtmf) {                                         // every slot's switch, once (a setting: slot resets and rate changes keep it)
+      std::vector<int32_t> all(B);
+      std::vector<uint8_t> on(B, 1);
+      float params[PN_DTMF_N_PARAMS];
+      for (int s = 0; s < B; s++) all[s] = s;
+      pn_dtmf_default_params(params);
+      if (g_dtmf_on_frames > 0.0f) params[PN_DTMF_ON_FRAMES] = g_dtmf_on_frames;
+      if (pn_rate_set_dtmf_params(rt, params) || pn_rate_set_stream_dtmf(rt, all.data(), B, on.data()) || pn_rate_set_dtmf_report(rt, 1))
+        return bad(std::string("--dtmf: ") + pn_last_error());
+    }
     if (postfilter) pn_ctx_set_postfilter(cx, 1);
     if ((g_saturate && pn_ctx_set_output_saturate(cx, 1)) || (g_report && pn_ctx_set_report(cx, 1))) return bad(pn_last_error());
     {
@@ -225,6 +245,7 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
   std::vector<int> cur_pair(B, 0);
   std::vector<long> pair_frame(B, 0);                   // --lose: the frames the pair playing in a slot has supplied so far
   std::vector<PairStat> stat(g_report ? P : 0);
+  std::vector<uint32_t> dtmf_rep(g_dtmf ? (size_t)B * PN_DTMF_REPORT_WORDS : 0);
   auto open_pair = [&](int s) -> bool {                 // the next waiting pair starts playing in slot s
     const char *pi = paths[2 * (sh->first + next_pair)], *po = paths[2 * (sh->first + next_pair) + 1];
     cur_pair[s] = next_pair++; pair_frame[s] = 0;
@@ -359,6 +380,13 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
         : g_g711 >= 0 ? pn_rate_submit_host_g711(rt, (const uint8_t *)sl.in, (uint8_t *)sl.out, sl.gr)
                     : rt ? pn_rate_submit_host_i16(rt, (const int16_t *)sl.in, (int16_t *)sl.out, sl.gr)
                          : pn_submit_host_i16(cx, (const int16_t *)sl.in, (int16_t *)sl.out, sl.gr)) return fail(5, pn_last_error());
+    if (g_dtmf) {                                      // this frame's digits: the read waits for the frame just submitted
+      if (pn_rate_read_dtmf_report(rt, dtmf_rep.data())) return fail(5, pn_last_error());
+      for (int s = 0; s < B; s++) {
+        const uint32_t w0 = dtmf_rep[(size_t)s * PN_DTMF_REPORT_WORDS];
+        if (sl.file[s] && (w0 & PN_DTMF_BEGIN)) printf("dtmf: pair %d frame %ld digit %c\n", sh->first + cur_pair[s], pair_frame[s] - 1, (char)((w0 >> 8) & 0xff));
+      }
+    }
     if (t >= 2) flush(slot[(t - 2) % 3]);
   }
   if (pn_host_wait(cx)) return fail(5, pn_last_error());
@@ -368,7 +396,7 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
 
 // the usage text, for a command line without pairs and for a rate no converter takes.  Returns the exit status, 1.
 static int usage(const char *argv0) {
-  fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N] [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--plc [--lose P:F0-F1,P:F,..]] [--agc RMS [--agc-max-gain G]] [--limiter CEIL [--limiter-hold H]] [--migrate-at F] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv0);
+  fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N] [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--plc [--lose P:F0-F1,P:F,..]] [--agc RMS [--agc-max-gain G]] [--limiter CEIL [--limiter-hold H]] [--dtmf [--dtmf-on-frames N]] [--migrate-at F] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv0);
   return 1;
 }
 
@@ -483,6 +511,16 @@ int main(int argc, char **argv) {
       params[PN_LIM_HOLD] = g_limiter_hold;
       if (end == v || *end || pn_lim_params_check(params)) { fprintf(stderr, "--limiter-hold: expected a whole number of frames in [0, 1000], got '%s'\n", v); return 1; }
     }
+    else if (!strcmp(argv[ai], "--dtmf")) g_dtmf = true;            // DTMF detection on every pair (pn_rate_set_stream_dtmf)
+    else if (!strcmp(argv[ai], "--dtmf-on-frames") && ai + 1 < argc) {   // the hits in a row that begin a digit (PN_DTMF_ON_FRAMES)
+      const char *v = argv[++ai];
+      char *end = NULL;
+      g_dtmf_on_frames = strtof(v, &end);
+      float params[PN_DTMF_N_PARAMS];
+      pn_dtmf_default_params(params);
+      params[PN_DTMF_ON_FRAMES] = g_dtmf_on_frames;
+      if (end == v || *end || pn_dtmf_params_check(params)) { fprintf(stderr, "--dtmf-on-frames: expected a whole number of frames in [1, 100], got '%s'\n", v); return 1; }
+    }
     else if (!strcmp(argv[ai], "--migrate-at") && ai + 1 < argc) {    // move every slot to a second context and converter behind this frame
       const char *v = argv[++ai];
       char *end = NULL;
@@ -530,7 +568,8 @@ int main(int argc, char **argv) {
     if (lr.pair >= B) { fprintf(stderr, "--lose: pair %ld of %d pairs (pairs count from 0)\n", lr.pair, B); return 1; }
   if (g_agc_max_gain > 0.0f && !(g_agc > 0.0f)) { fprintf(stderr, "--agc-max-gain needs --agc: it is a parameter of the level control\n"); return 1; }
   if (g_limiter_hold >= 0.0f && !(g_limiter > 0.0f)) { fprintf(stderr, "--limiter-hold needs --limiter: it is a parameter of the output limiter\n"); return 1; }
-  if ((g_plc || g_agc > 0.0f || g_limiter > 0.0f) && !g_rate && g_rates.empty()) g_rates.assign(B, 48000);        // on its own: a mixed converter of all 48000
+  if (g_dtmf_on_frames > 0.0f && !g_dtmf) { fprintf(stderr, "--dtmf-on-frames needs --dtmf: it is a parameter of the DTMF detector\n"); return 1; }
+  if ((g_plc || g_agc > 0.0f || g_limiter > 0.0f || g_dtmf) && !g_rate && g_rates.empty()) g_rates.assign(B, 48000);        // on its own: a mixed converter of all 48000
   if (g_migrate_at >= 0) {
     if (devices.size() > 1) { fprintf(stderr, "--migrate-at takes one device: the slots move between two contexts of one device\n"); return 1; }
     if (!g_rate && g_rates.empty()) { fprintf(stderr, "--migrate-at needs a converter (--rate or --rates): it moves the converter's records with the engine's\n"); return 1; }

@@ -126,6 +126,14 @@ void pn_launch_rate_agc(hipStream_t st, int n_rows, const int *d_ids, const floa
 // [.][480], in place.  d_ceilings [n_streams]: +0.0 = the stream is not limited; params: the converter's PN_LIM_N_PARAMS floats on the
 // HOST, passed by value.  State [n_streams][4] words; d_report [n_streams][4] words or NULL
 void pn_launch_rate_lim(hipStream_t st, int n_rows, const int *d_ids, const float *d_ceilings, const float *params, float *o48, void *state, void *d_report);
+// in-band DTMF detection (pn_rate_dtmf.hip; the rule pn_dtmf_rules.h): rows d_ids[0..n_rows) or, with d_ids == NULL, streams 0..n_rows of
+// x48 [.][480], which it only reads.  d_on [n_streams] words: 0 = detection is off for the stream; a stream whose d_lost word equals tick
+// was concealed this frame (d_lost == NULL: nobody); params, rot16: the converter's PN_DTMF_N_PARAMS floats and the frame rotation on
+// the HOST, passed by value; d_tab: ct [8][480] then st [8][480], 16-byte aligned.  State [n_streams][24] words; d_report [n_streams][4]
+// words or NULL.  The grid has at most PN_DTMF_MAX_BLOCKS blocks of four rows: beyond 4 * PN_DTMF_MAX_BLOCKS rows a block makes further passes
+#define PN_DTMF_MAX_BLOCKS 512
+void pn_launch_rate_dtmf(hipStream_t st, int n_rows, const int *d_ids, const int *d_on, const uint32_t *d_lost, uint32_t tick, const float *params, const float *rot16,
+                         const float *d_tab, const float *x48, void *state, void *d_report);
 // call-state records (pn_rate_call.hip; layout and verdict pn_call_rules.h): record i of rec [n][PN_RATE_CALL_STATE_BYTES] (16-byte aligned)
 // <-> the PLC, AGC, limiter and level state of stream d_ids[i].  held: the PN_CALL_* states the converter holds — a state's pointers
 // are read only under its bit and may be NULL otherwise.  scatter: d_status[i] receives record i's verdict, a refused record moves nothing

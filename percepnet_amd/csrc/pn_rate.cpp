@@ -14,10 +14,11 @@
 #include "pn_agc_rules.h"    // automatic level control: the rule for the host, what parameters and targets must be
 #include "pn_lim_rules.h"    // the output limiter: the rule for the host, what parameters and ceilings must be
 #include "pn_call_rules.h"   // call-state records: the layout and the verdict
+#include "pn_dtmf_rules.h"   // DTMF detection: the rule for the host, what parameters must be, the tables
 #include <string>
 #include <vector>
 
-enum { RF_UP, RF_DOWN, RF_MIX, RF_PLC, RF_AGC, RF_LIM, RF_COUNT };   // the timed kernels (pn_rate_kernel_time), named by kRateFamily below
+enum { RF_UP, RF_DOWN, RF_MIX, RF_PLC, RF_AGC, RF_LIM, RF_DTMF, RF_COUNT };   // the timed kernels (pn_rate_kernel_time), named by kRateFamily below
 struct pn_rate {
   pn_ctx *c;                    // borrowed: device, B, stream, the id ring, the saturate setting
   int rate, f, n, td;           // rate_hz, its factor (pn_rate_design.h: L, or PN_RATE_F_3_2 for 32000), samples per row, words per down tail row (2D / M).  Mixed: 0, 0, 480, 192
@@ -86,6 +87,16 @@ struct pn_rate {
   int lim_on = 0;                                     // streams whose ceiling is not 0
   float *d_lim_ceilings = NULL;                       // [B]
   void *d_lim_state = NULL, *d_lim_report = NULL;     // [B][4] words each
+  // DTMF detection (pn_rate_set_stream_dtmf; the rule pn_dtmf_rules.h): SETTINGS — the converter's parameters, a switch per stream as last
+  // set (host) and as a word on the device, written in stream order through the id ring like the ceilings — and the state, 24 words per
+  // stream.  The device side (with the twiddle tables) exists from the first enabling on.  dtmf_on == 0: a frame launches nothing of it
+  bool dtmf_report = false;
+  float dtmf_params[PN_DTMF_N_PARAMS];
+  std::vector<uint8_t> dtmf_sw;                       // [B], 0
+  int dtmf_on = 0;                                    // streams whose switch is on
+  int *d_dtmf_on = NULL;                              // [B] words
+  float *d_dtmf_tab = NULL;                           // ct [8][480], st [8][480]
+  void *d_dtmf_state = NULL, *d_dtmf_report = NULL;   // [B][24] and [B][4] words
   std::vector<void *> allocs;
   // timing of the kernels (pn_rate_set_profiling): HIP events around their launches, like the context's families but owned
   // here; while it is off no event exists and none is recorded
@@ -95,7 +106,7 @@ struct pn_rate {
   std::vector<hipEvent_t> event_pool;
   double fam_ms[RF_COUNT] = {}; int64_t fam_n[RF_COUNT] = {};
 };
-static const char *const kRateFamily[RF_COUNT] = {"rate_up", "rate_down", "rate_mix", "rate_plc", "rate_agc", "rate_lim"};
+static const char *const kRateFamily[RF_COUNT] = {"rate_up", "rate_down", "rate_mix", "rate_plc", "rate_agc", "rate_lim", "rate_dtmf"};
 struct RateScope {
   pn_rate *r; int fam; hipEvent_t a, b; bool on;
   RateScope(pn_rate *r_, int fam_) : r(r_), fam(fam_), on(r_->profiling) {
@@ -163,6 +174,12 @@ extern "C" int pn_lim_params_check(const float *params2) { return pn_lim_params_
 extern "C" int pn_lim_frame(const float *params2, float ceiling, uint32_t *state4, const float *row_in480, float *row_out480, uint32_t *report4) {
   return pn_lim_frame_host(params2, ceiling, state4, row_in480, row_out480, report4);
 }
+extern "C" int pn_dtmf_default_params(float *params7) { if (!params7) { pn_set_error("NULL argument"); return -1; } pn_dtmf_default_params_host(params7); return 0; }
+extern "C" int pn_dtmf_params_check(const float *params7) { return pn_dtmf_params_check_host(params7); }
+extern "C" int pn_dtmf_frame(const float *params7, uint32_t *state24, const float *row480, int concealed, uint32_t *report4) {
+  return pn_dtmf_frame_host(params7, state24, row480, concealed, report4);
+}
+extern "C" int pn_dtmf_tables(float *ct, float *st, float *rot16) { return pn_dtmf_tables_host(ct, st, rot16); }
 extern "C" int pn_rate_limiter_ceilings_check(const float *ceilings, int n) { return pn_lim_ceilings_list_check(ceilings, n); }
 
 // ---- lifecycle ---------------------------------------------------------------------------------------------------------------
@@ -190,6 +207,7 @@ extern "C" pn_rate *pn_rate_create(pn_ctx *c, int rate_hz) {
   r->gains.assign((size_t)c->B, 1.0f); r->caps.assign((size_t)c->B, 0);
   r->agc_targets.assign((size_t)c->B, 0.0f); pn_agc_default_params_host(r->agc_params);
   r->lim_ceilings.assign((size_t)c->B, 0.0f); pn_lim_default_params_host(r->lim_params);
+  r->dtmf_sw.assign((size_t)c->B, 0); pn_dtmf_default_params_host(r->dtmf_params);
   const size_t B = (size_t)c->B, nt = 2 * (size_t)PN_RATE_TAPS * pn_rate_factor_L(f) + 1;
   float h[2][PN_RATE_MAX_TAPS];
   auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
@@ -222,6 +240,7 @@ extern "C" pn_rate *pn_rate_create_mixed(pn_ctx *c, const int32_t *rates_hz) {
   r->gains.assign((size_t)c->B, 1.0f); r->caps.assign((size_t)c->B, 0);
   r->agc_targets.assign((size_t)c->B, 0.0f); pn_agc_default_params_host(r->agc_params);
   r->lim_ceilings.assign((size_t)c->B, 0.0f); pn_lim_default_params_host(r->lim_params);
+  r->dtmf_sw.assign((size_t)c->B, 0); pn_dtmf_default_params_host(r->dtmf_params);
   const size_t B = (size_t)c->B;
   if (rates_hz) r->rates.assign(rates_hz, rates_hz + B); else r->rates.assign(B, 48000);
   static const int kF[4] = {6, 3, 2, PN_RATE_F_3_2};   // (the order of pn_rate.hip rt_taps_offset; the h of 32000 is the table of 3 and is not staged twice)
@@ -270,6 +289,8 @@ static void plc_zero_rows(pn_rate *r, const int *d, int n) {
 static void agc_zero_rows(pn_rate *r, const int *d, int n) { pn_launch_zero_rows(r->c->stream, r->d_agc_state, 4, 4, 1, 0, d, n); }
 // the limiter state of the staged streams d[0..n) goes to zero: a fresh gain, no hold (nothing while no ceiling was ever set)
 static void lim_zero_rows(pn_rate *r, const int *d, int n) { pn_launch_zero_rows(r->c->stream, r->d_lim_state, 4, 4, 1, 0, d, n); }
+// the detector state of the staged streams d[0..n) goes to zero: no half sums, no digit (nothing while no stream was ever enabled)
+static void dtmf_zero_rows(pn_rate *r, const int *d, int n) { pn_launch_zero_rows(r->c->stream, r->d_dtmf_state, PN_DTMF_STATE_WORDS, PN_DTMF_STATE_WORDS, 1, 0, d, n); }
 // A rate change of the listed streams, asynchronous and ordered like pn_rate_reset_streams: the ids and the new factors go
 // through the context's id ring in one copy, one launch writes the factors, two zero the tails.
 extern "C" int pn_rate_set_stream_rates(pn_rate *r, const int32_t *ids, int n, const int32_t *rates_hz) {
@@ -289,6 +310,7 @@ extern "C" int pn_rate_set_stream_rates(pn_rate *r, const int32_t *ids, int n, c
   plc_zero_rows(r, d, n);
   agc_zero_rows(r, d, n);
   lim_zero_rows(r, d, n);
+  dtmf_zero_rows(r, d, n);
   PN_HIP_CHECK(hipGetLastError());
   for (int i = 0; i < n; i++) r->rates[ids[i]] = rates_hz[i];
   return 0;
@@ -660,6 +682,87 @@ static int lim_report_copy(pn_rate *r, void *dst, hipMemcpyKind kind) {
 extern "C" int pn_rate_read_limiter_report(pn_rate *r, void *h_report) { return lim_report_copy(r, h_report, hipMemcpyDeviceToHost); }
 extern "C" int pn_rate_read_limiter_report_dev(pn_rate *r, void *d_report) { return lim_report_copy(r, d_report, hipMemcpyDeviceToDevice); }
 
+// ---- DTMF detection (include/percepnet_hip.h; the rule pn_dtmf_rules.h; the kernel pn_rate_dtmf.hip) ------------------------------
+static int dtmf_buffers(pn_rate *r) {                // (the caller is on the context's device)
+  if (r->d_dtmf_state) return 0;
+  pn_ctx *c = r->c;
+  const size_t B = (size_t)c->B;
+  const PnDtmfTables &T = pn_dtmf_tables_ref();
+  int *on = NULL; float *tab = NULL; void *state = NULL;
+  auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
+  if (alloc((void **)&on, B * 4, true) || alloc((void **)&tab, sizeof(T.ct) + sizeof(T.st), false) || alloc(&state, B * PN_DTMF_STATE_BYTES, true)) return -1;
+  static_assert(offsetof(PnDtmfTables, st) == sizeof(T.ct), "ct and st are one block");
+  PN_HIP_CHECK(hipMemcpyAsync(tab, T.ct, sizeof(T.ct) + sizeof(T.st), hipMemcpyHostToDevice, c->stream));   // (from a static table: the source outlives the copy)
+  r->d_dtmf_on = on; r->d_dtmf_tab = tab; r->d_dtmf_state = state;
+  return 0;
+}
+extern "C" int pn_rate_set_stream_dtmf(pn_rate *r, const int32_t *ids, int n, const uint8_t *on) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (pn_dtmf_on_set_check(r->c->B, ids, n, on)) return -1;
+  if (n == 0) return 0;
+  std::vector<int32_t> v(n), fresh;
+  bool all_off = true;
+  for (int i = 0; i < n; i++) { v[i] = on[i] ? 1 : 0; all_off &= !on[i]; if (on[i] && !r->dtmf_sw[ids[i]]) fresh.push_back(ids[i]); }
+  if (!r->d_dtmf_state && all_off) return 0;                                     // (no stream has ever been enabled, and none is)
+  PN_ON_DEVICE(r->c);
+  if (dtmf_buffers(r)) return -1;
+  for (size_t at = 0; at < fresh.size(); at += 16384) {                            // a stream that was off starts from the fresh state
+    const int m = (int)(fresh.size() - at < 16384 ? fresh.size() - at : 16384);
+    const int *d = stage_ids(r->c, fresh.data() + at, m);
+    if (!d) return -1;
+    dtmf_zero_rows(r, d, m);
+  }
+  if (mix_set_words(r, ids, n, v.data(), r->d_dtmf_on)) return -1;
+  for (int i = 0; i < n; i++) { r->dtmf_on += v[i] - (r->dtmf_sw[ids[i]] ? 1 : 0); r->dtmf_sw[ids[i]] = (uint8_t)v[i]; }
+  return 0;
+}
+extern "C" int pn_rate_get_stream_dtmf(const pn_rate *r, uint8_t *h_on) {
+  if (!r || !h_on) { pn_set_error("NULL argument"); return -1; }
+  for (int s = 0; s < r->c->B; s++) h_on[s] = r->dtmf_sw[s];
+  return 0;
+}
+// the parameters travel as an argument of every launch, so a change is ordered like one
+extern "C" int pn_rate_set_dtmf_params(pn_rate *r, const float *params7) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (pn_dtmf_params_check_host(params7)) return -1;
+  memcpy(r->dtmf_params, params7, sizeof(r->dtmf_params));
+  return 0;
+}
+extern "C" int pn_rate_get_dtmf_params(const pn_rate *r, float *params7) {
+  if (!r || !params7) { pn_set_error("NULL argument"); return -1; }
+  memcpy(params7, r->dtmf_params, sizeof(r->dtmf_params));
+  return 0;
+}
+extern "C" int pn_rate_set_dtmf_report(pn_rate *r, int enable) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (enable && !r->d_dtmf_report) {
+    PN_ON_DEVICE(r->c);
+    if (dev_alloc_into(r->allocs, r->bytes, r->c->stream, &r->d_dtmf_report, (size_t)r->c->B * PN_DTMF_REPORT_WORDS * 4, true)) return -1;
+  }
+  r->dtmf_report = enable != 0;
+  return 0;
+}
+static int dtmf_report_copy(pn_rate *r, void *dst, hipMemcpyKind kind) {
+  if (!r || !dst) { pn_set_error("NULL argument"); return -1; }
+  if (!r->dtmf_report) { pn_set_error("the DTMF report is off (pn_rate_set_dtmf_report)"); return -1; }
+  PN_ON_DEVICE(r->c);
+  PN_HIP_CHECK(hipMemcpyAsync(dst, r->d_dtmf_report, (size_t)r->c->B * PN_DTMF_REPORT_WORDS * 4, kind, r->c->stream));
+  if (kind == hipMemcpyDeviceToHost) PN_HIP_CHECK(hipStreamSynchronize(r->c->stream));
+  return 0;
+}
+// the detector state of every stream to the host, synchronising (tests and debugging); zeros while no stream was ever enabled
+extern "C" int pn_rate_debug_dtmf_state(pn_rate *r, void *h_state) {
+  if (!r || !h_state) { pn_set_error("NULL argument"); return -1; }
+  const size_t bytes = (size_t)r->c->B * PN_DTMF_STATE_BYTES;
+  if (!r->d_dtmf_state) { memset(h_state, 0, bytes); return 0; }
+  PN_ON_DEVICE(r->c);
+  PN_HIP_CHECK(hipMemcpyAsync(h_state, r->d_dtmf_state, bytes, hipMemcpyDeviceToHost, r->c->stream));
+  PN_HIP_CHECK(hipStreamSynchronize(r->c->stream));
+  return 0;
+}
+extern "C" int pn_rate_read_dtmf_report(pn_rate *r, void *h_report) { return dtmf_report_copy(r, h_report, hipMemcpyDeviceToHost); }
+extern "C" int pn_rate_read_dtmf_report_dev(pn_rate *r, void *d_report) { return dtmf_report_copy(r, d_report, hipMemcpyDeviceToDevice); }
+
 extern "C" int pn_rate_reset(pn_rate *r) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   PN_ON_DEVICE(r->c);
@@ -673,6 +776,7 @@ extern "C" int pn_rate_reset(pn_rate *r) {
   }
   if (r->d_agc_state) PN_HIP_CHECK(hipMemsetAsync(r->d_agc_state, 0, (size_t)r->c->B * PN_AGC_STATE_BYTES, r->c->stream));
   if (r->d_lim_state) PN_HIP_CHECK(hipMemsetAsync(r->d_lim_state, 0, (size_t)r->c->B * PN_LIM_STATE_BYTES, r->c->stream));
+  if (r->d_dtmf_state) PN_HIP_CHECK(hipMemsetAsync(r->d_dtmf_state, 0, (size_t)r->c->B * PN_DTMF_STATE_BYTES, r->c->stream));
   return 0;
 }
 
@@ -689,6 +793,7 @@ extern "C" int pn_rate_reset_streams(pn_rate *r, const int32_t *ids, int n) {
   plc_zero_rows(r, d, n);
   agc_zero_rows(r, d, n);
   lim_zero_rows(r, d, n);
+  dtmf_zero_rows(r, d, n);
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -768,6 +873,16 @@ static int rate_lim(pn_rate *r, float *d_o48, const RateRows &rows) {
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
+// the DTMF detector over the rows, which it only reads; d_lost / tick as for the level control
+static int rate_dtmf(pn_rate *r, const float *d_x48, const RateRows &rows, const uint32_t *d_lost, uint32_t tick) {
+  {
+    RateScope sc(r, RF_DTMF);
+    pn_launch_rate_dtmf(r->c->stream, rows.n, rows.d_ids, r->d_dtmf_on, d_lost, tick, r->dtmf_params, pn_dtmf_tables_ref().rot, r->d_dtmf_tab, d_x48,
+                        r->d_dtmf_state, r->dtmf_report ? r->d_dtmf_report : NULL);
+  }
+  PN_HIP_CHECK(hipGetLastError());
+  return 0;
+}
 static int rate_up_call(pn_rate *r, const void *d_in, int fmt, float *d_out48, const int32_t *ids, int n) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   if (rate_aligned(d_in, d_out48)) return -1;
@@ -827,6 +942,15 @@ extern "C" int pn_rate_lim_f32(pn_rate *r, float *d_o48, const int32_t *ids, int
   if (lim_buffers(r)) return -1;                     // (no ceiling was ever set: every stream is off, the state exists from here on)
   return rate_lim(r, d_o48, rows);
 }
+extern "C" int pn_rate_dtmf_f32(pn_rate *r, const float *d_x48, const int32_t *ids, int n_ids) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (rate_aligned(d_x48, d_x48)) return -1;
+  PN_ON_DEVICE(r->c);
+  RateRows rows;
+  if (rate_rows(r, ids, n_ids, &rows)) return -1;
+  if (dtmf_buffers(r)) return -1;                    // (no stream was ever enabled: every stream is off, the state exists from here on)
+  return rate_dtmf(r, d_x48, rows, NULL, 0);
+}
 
 // ---- one whole frame -----------------------------------------------------------------------------------------------------------
 // up into x48, while packet-loss concealment is on the concealer in place on x48, the engine's float frame from x48 into y48 (all streams, or the listed ones through the context's own active
@@ -860,6 +984,8 @@ static int rate_frame(pn_rate *r, const void *d_in, void *d_out, float *d_gr, in
   const uint32_t plc_tick_used = r->plc_tick;        // the tick the concealer stamps this frame's lost streams with: rate_plc moves it on
   const bool concealing = r->plc;
   if (r->plc && rate_plc(r, r->x48, rows)) return -1;
+  // the DTMF detector, while somebody is enabled: behind the concealer and in front of the engine, reading x48 only
+  if (r->dtmf_on > 0 && rate_dtmf(r, r->x48, rows, concealing ? r->d_plc_lost : NULL, plc_tick_used)) return -1;
   if (active ? pn_process_f32_active(c, r->x48, r->y48, d_gr, ids, n) : pn_process_f32(c, r->x48, r->y48, d_gr)) return -1;
   // the level control, while on and somebody has a target: in place on y48, so the mix, its levels and the down-conversion see levelled rows
   if (r->agc && r->agc_on > 0 && rate_agc(r, r->y48, rows, concealing ? r->d_plc_lost : NULL, plc_tick_used)) return -1;
@@ -957,7 +1083,7 @@ extern "C" int pn_rate_submit_host_g711_active(pn_rate *r, const uint8_t *h_in, 
 // ---- timing the kernels --------------------------------------------------------------------------------------------------------
 extern "C" int pn_rate_set_profiling(pn_rate *r, int enable) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
-  if (enable && r->event_pool.size() < 1024) {        // up to six scopes a frame (up, plc, agc, mix, lim, down): enough for 85 frames between two reads; created outside any timed region
+  if (enable && r->event_pool.size() < 1024) {        // up to seven scopes a frame (up, plc, dtmf, agc, mix, lim, down): enough for 73 frames between two reads; created outside any timed region
     PN_ON_DEVICE(r->c);
     while (r->event_pool.size() < 1024) { hipEvent_t e; PN_HIP_CHECK(hipEventCreate(&e)); r->event_pool.push_back(e); }
   }
@@ -970,7 +1096,7 @@ extern "C" int pn_rate_kernel_time(pn_rate *r, const char *name, double *total_m
   if (rate_flush_events(r)) return -1;
   for (int i = 0; i < RF_COUNT; i++)
     if (!strcmp(name, kRateFamily[i])) { if (total_ms) *total_ms = r->fam_ms[i]; if (launches) *launches = r->fam_n[i]; return 0; }
-  pn_set_error("unknown converter kernel '%s' (rate_up, rate_down, rate_mix, rate_plc, rate_agc, rate_lim)", name);
+  pn_set_error("unknown converter kernel '%s' (rate_up, rate_down, rate_mix, rate_plc, rate_agc, rate_lim, rate_dtmf)", name);
   return -1;
 }
 extern "C" int pn_rate_reset_profile(pn_rate *r) {
@@ -991,7 +1117,7 @@ static int rate_records_host(pn_rate *r, int rate, bool import, const int32_t *i
     const int *d_ids = stage_ids(c, ids, n);
     if (!d_ids) return -1;
     pn_launch_rate_records(c->stream, f, rate, d_ids, n, r->tail_up, r->tail_down, r->td, d, import ? 1 : 0);
-    if (import) { plc_zero_rows(r, d_ids, n); agc_zero_rows(r, d_ids, n); lim_zero_rows(r, d_ids, n); }   // the slot is now another stream: it starts with an empty history and fresh gains
+    if (import) { plc_zero_rows(r, d_ids, n); agc_zero_rows(r, d_ids, n); lim_zero_rows(r, d_ids, n); dtmf_zero_rows(r, d_ids, n); }   // the slot is now another stream: it starts with an empty history and fresh gains
     if (hipGetLastError() != hipSuccess) { pn_set_error(import ? "record scatter launch failed" : "record gather launch failed"); return -1; }
     return 0;
   });
@@ -1037,7 +1163,7 @@ static int rate_records_dev(pn_rate *r, bool import, const int32_t *ids, int n, 
   if (!d) return -1;
   pn_launch_rate_records_dev(c->stream, d, n, r->mixed ? r->factors : NULL, r->f, r->tail_up, r->tail_down, r->td, d_records,
                              (int)(pn_rate_record_stride(r) / 4), d_status, import ? 1 : 0);
-  if (import) { plc_zero_rows(r, d, n); agc_zero_rows(r, d, n); lim_zero_rows(r, d, n); }   // the slot is now another stream: it starts with an empty history and fresh gains, whatever its record's status
+  if (import) { plc_zero_rows(r, d, n); agc_zero_rows(r, d, n); lim_zero_rows(r, d, n); dtmf_zero_rows(r, d, n); }   // the slot is now another stream: it starts with an empty history and fresh gains, whatever its record's status
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
