@@ -534,7 +534,7 @@ int pn_rate_export_streams(pn_rate *r, const int32_t *ids, int n, void *d_record
 int pn_rate_import_streams(pn_rate *r, const int32_t *ids, int n, const void *d_records, int32_t *d_status);
 /* Timing of the converter's two kernels inside a frame: HIP events around their launches, like pn_ctx_set_profiling but owned by
    the converter (the context's family list does not change).  Off by default; off, no event is created or recorded.  name:
-   "rate_up" | "rate_down" | "rate_mix" (the conference mix, below) | "rate_plc" (packet-loss concealment, below) | "rate_agc" (automatic level control, below) | "rate_lim" (the output limiter, below) | "rate_dtmf" (DTMF detection, below).  pn_rate_kernel_time synchronises the context's stream. */
+   "rate_up" | "rate_down" | "rate_mix" (the conference mix, below) | "rate_plc" (packet-loss concealment, below) | "rate_agc" (automatic level control, below) | "rate_lim" (the output limiter, below) | "rate_dtmf" (DTMF detection, below) | "rate_clamp" (DTMF removal, below).  pn_rate_kernel_time synchronises the context's stream. */
 int pn_rate_set_profiling(pn_rate *r, int enable);
 int pn_rate_kernel_time(pn_rate *r, const char *name, double *total_ms, int64_t *launches);
 int pn_rate_reset_profile(pn_rate *r);
@@ -1178,7 +1178,8 @@ int pn_rate_import_call_state_host(pn_rate *r, const int32_t *ids, int n, const 
    state.  Switches and parameters are settings that survive all of those.  NO record carries the detector state — the three record
    formats are untouched — so a digit in flight when a call moves is reported AGAIN with BEGIN on the target (count and last4 start
    from zero there).  With PLC on, a stream is concealed in the frame whose marks the concealer consumed.
-   NOT provided: removing or muting the tone in the audio; RFC 4733 events; second-harmonic talk-off tests; any claim of Q.24
+   Removing the tone from the audio and RFC 4733 events: the next section.
+   NOT provided: second-harmonic talk-off tests; any claim of Q.24
    conformance; detection without a converter; detector state in a record; the report on pn_host_next_report. */
 #define PN_DTMF_N_PARAMS 7
 #define PN_DTMF_MIN_RMS 0
@@ -1207,6 +1208,105 @@ int pn_rate_set_dtmf_report(pn_rate *r, int enable);
 int pn_rate_read_dtmf_report(pn_rate *r, void *h_report);
 int pn_rate_read_dtmf_report_dev(pn_rate *r, void *d_report);
 int pn_rate_debug_dtmf_state(pn_rate *r, void *h_state);   /* tests and debugging: [n_streams][24] state words to the host, synchronising; zeros while no stream was ever enabled */
+
+/* ---- DTMF removal: a pressed key is muted ahead of the mix, and handed on as an RFC 4733 event -------------------------------------- */
+/* A member who types a PIN is heard by the whole conference, the tone competes in loudest-N and drives the level control, and a gateway
+   behind the bridge detects the digit a second time.  With removal ON for a stream, detected DTMF is taken out of its enhanced 48 kHz
+   row (y48) by one kernel (csrc/pn_rate_dtmf_clamp.hip) BEHIND the engine and IN FRONT of the level control, the mix, the limiter and
+   the down-conversion.  It costs no delay: output row t of pn_process_* is input row t - 6 (60 ms, whole rows), the detector sits in
+   front of the engine, so this stage knows the verdict on a row five frames before the row comes out and removes a digit from its first
+   sample, with a fade in front of it.  OFF by default for every stream: a converter on which removal is on for nobody launches exactly
+   what it launches without this section and produces the same bytes (the host keeps the count).  Removal needs detection (DTMF
+   detection, above) on the same stream; a stream with removal on and detection off is left alone.
+
+   The rule is csrc/pn_dtmf_clamp_rules.h (HIP-free); tests/dtmf_clamp_model.py restates it in numpy and the kernel matches both bit for
+   bit.  The stage reads the detector's REPORT row of this frame (flags | cur << 8 | ended << 16, dur, ..) and nothing else of it; while
+   removal is on for some stream the detector's kernel writes its report whether or not pn_rate_set_dtmf_report is on (reading it
+   stays refused while that is off).  The detector, its state, its rule and its report are unchanged.
+   Parameters, one set per converter, PN_DTMF_CLAMP_N_PARAMS = 4 int32:
+     0 PN_DTMF_CLAMP_PRE   rows removed in front of a marked row [0, 4] 1      1 PN_DTMF_CLAMP_POST  rows removed behind one [0, 8] 0
+     2 PN_DTMF_CLAMP_VOLUME  the volume field of a payload [0, 63] 10          3 PN_DTMF_CLAMP_TS_PER_FRAME  RTP units per frame [1, 65535] 80
+   In time: a mark of input row p is final by frame p + on_frames (PN_DTMF_ON_FRAMES), so nothing is late exactly when
+   on_frames + pre <= 5.  Calls that would break this are refused as a whole, naming the values: pn_rate_set_dtmf_clamp_params,
+   pn_rate_set_stream_dtmf_clamp (switching somebody on) and, while removal is on for some stream, pn_rate_set_dtmf_params.
+   State per stream (16 bytes = 4 words, in an array of its own, allocated by the first enabling, never inside a frame; all zero is
+   fresh): w0 marks, a 32-bit shift register, bit i the mark of input row t - i; w1 bit 0 cut: the previous output row ended at gain 0;
+   w2 rows muted so far (saturating); w3 the dur of the previous frame's ongoing event.
+   One frame of an advancing stream with removal on, det = the detector's report row of this frame:
+     marks:    marks <<= 1.  det four zero words (detection off): nothing is set.  Otherwise BEGIN with duration dur (the run of hits):
+               bits 0..min(dur, 31) are set (a hit window spans two rows, dur hits cover dur + 1 rows).  Otherwise cur != 0: bit 0 is
+               set, gap frames and concealed frames (HELD_LOST) of a digit included.
+     decision: M(k) = any mark bit in [k - pre, k + post] clipped to 0..31; the output row is input row t - 6: m = M(6), m_next = M(5);
+               the gain at the row's end e = (m || m_next) ? 0 : 1, at its start s = cut ? 0 : 1.
+     the row:  m: all 480 samples become +0.0f, written without being read (a NaN in a removed row is gone), MUTED; with s == 1 the cut
+               is hard: LATE.  !m, s 1, e 0: fade out, x[j] * ((float)(479 - j) / 480.0f), FADE_OUT.  !m, s 0, e 1: fade in,
+               x[j] * ((float)(j + 1) / 480.0f), FADE_IN.  !m, s 0, e 0: zeros, FADE_OUT | FADE_IN.  s 1, e 1: the row is neither read
+               nor written.  Each ramp value is one correctly rounded fp32 quotient, each product rounded once.  Then cut = (e == 0).
+     events (RFC 4733 section 2.3): a payload is the 32-bit value event << 24 | E << 23 | volume << 16 | duration, to be sent big-endian;
+               event 0..9 for '0'..'9', 10 '*', 11 '#', 12..15 'A'..'D'; duration = min(dur * ts_per_frame, 65535).  While cur != 0: the
+               ongoing event, E = 0 (a concealed frame repeats it).  In a frame with END: the ended digit, E = 1, with the dur of the
+               previous frame's ongoing event (w3; one frame's where the state never saw the digit ongoing).  0 means no event; a real
+               payload is never 0.  Events are about the INPUT: they run 60 ms AHEAD of the audio they describe.
+   Removal report (optional; pn_rate_set_dtmf_clamp_report, pn_rate_read_dtmf_clamp_report synchronising,
+     pn_rate_read_dtmf_clamp_report_dev asynchronous on the context's stream; -1 while off): PN_DTMF_CLAMP_REPORT_WORDS = 4 little-endian
+     32-bit words per stream, [n_streams][4], written for every stream that advances in a frame that launches the kernel; four zero words
+     for a stream that is not on:
+     word 0  flags: PN_DTMF_CLAMP_ON | MUTED | FADE_OUT | FADE_IN | LATE | EVENT (word 1 holds one) | EVENT_END (word 2 holds one)
+     word 1  the ongoing payload      word 2  the ended payload      word 3  rows muted so far
+   It is NOT part of pn_host_next_report.
+
+   pn_rate_set_stream_dtmf_clamp(r, ids, n, on) / pn_rate_get_stream_dtmf_clamp(r, h_on[n_streams]): the id list rules of
+     pn_rate_set_stream_dtmf; asynchronous on the context's stream and ordered against frames like it, on the pipelined path too.  The
+     first enabling allocates the state, the switch words and the detector's report rows; a frame never allocates.  Enabling a stream
+     that was off zeroes its removal state; enabling one that is on, or disabling, leaves it.
+   pn_rate_set_dtmf_clamp_params(r, params[4]) / pn_rate_get_dtmf_clamp_params: from the next frame submitted on (an argument of every
+     launch).  Refused with -1, nothing changed: a value outside its range, pn_last_error naming the FIRST bad index, or a guard that
+     is not in time.  Host only: pn_dtmf_clamp_default_params; pn_dtmf_clamp_params_check(params, dtmf_params7) — dtmf_params7 may be
+     NULL, otherwise the in-time condition is checked against its PN_DTMF_ON_FRAMES.
+   pn_rate_dtmf_clamp_f32(r, d_y48, ids, n_ids): the kernel on its own over [n_streams][480] float rows at a 16-byte aligned device
+     address, ids as for pn_rate_up_*, reading the detector's report rows as the last detector launch (or
+     pn_rate_debug_set_dtmf_report) left them.
+   pn_dtmf_clamp_frame(params, state4, det_report4, row480, report4) -> the report's flags, or -1 for a bad argument: host only, the
+     rule above on one row of a stream with removal on; state4 and row480 are read and written, det_report4 NULL means detection off,
+     report4 may be NULL.  It does not check the in-time condition: a guard that is too long reports LATE.
+   pn_dtmf_event_payload(digit, end, volume, dur, ts_per_frame) -> the payload, 0 for a digit that is none or arguments out of range.
+   pn_rate_kernel_time takes "rate_clamp".
+   Lifecycle.  pn_rate_reset zeroes the removal state of every stream; pn_rate_reset_streams, pn_rate_set_stream_rates and both import
+   forms that of the listed slots, wherever the detector's state goes to zero.  A stream that does not advance keeps its state.
+   Switches and parameters are settings that survive all of those.  NO record carries the removal state; the call-state record and its
+   10 640 bytes are unchanged.
+   Known limit: concealed frames among a digit's first on_frames hits are not counted in dur, so up to that many rows of its head stay.
+   What the engine smears past the marked rows (its comb filter reaches 16 ms back) is measured in DESIGN.md section 4.8, not fixed.
+   NOT provided: generating tones from received events; a volume measured from the tone; segmenting events longer than 65535 units;
+   removal without a converter or without detection; removal or detector state in a record; either report on pn_host_next_report; notch
+   filtering instead of muting; comfort noise in the gap. */
+#define PN_DTMF_CLAMP_N_PARAMS 4
+#define PN_DTMF_CLAMP_PRE 0
+#define PN_DTMF_CLAMP_POST 1
+#define PN_DTMF_CLAMP_VOLUME 2
+#define PN_DTMF_CLAMP_TS_PER_FRAME 3
+#define PN_DTMF_CLAMP_REPORT_WORDS 4
+#define PN_DTMF_CLAMP_ON 1
+#define PN_DTMF_CLAMP_MUTED 2
+#define PN_DTMF_CLAMP_FADE_OUT 4
+#define PN_DTMF_CLAMP_FADE_IN 8
+#define PN_DTMF_CLAMP_LATE 16
+#define PN_DTMF_CLAMP_EVENT 32
+#define PN_DTMF_CLAMP_EVENT_END 64
+int pn_dtmf_clamp_default_params(int32_t *params4);                                  /* host only */
+int pn_dtmf_clamp_params_check(const int32_t *params4, const float *dtmf_params7);   /* host only */
+int pn_dtmf_clamp_frame(const int32_t *params4, uint32_t *state4, const uint32_t *det_report4, float *row480, uint32_t *report4);   /* host only */
+uint32_t pn_dtmf_event_payload(int digit, int end, int volume, uint32_t dur, int ts_per_frame);   /* host only */
+int pn_rate_set_stream_dtmf_clamp(pn_rate *r, const int32_t *ids, int n, const uint8_t *on);
+int pn_rate_get_stream_dtmf_clamp(const pn_rate *r, uint8_t *h_on);
+int pn_rate_set_dtmf_clamp_params(pn_rate *r, const int32_t *params4);
+int pn_rate_get_dtmf_clamp_params(const pn_rate *r, int32_t *params4);
+int pn_rate_dtmf_clamp_f32(pn_rate *r, float *d_y48, const int32_t *ids, int n_ids);
+int pn_rate_set_dtmf_clamp_report(pn_rate *r, int enable);
+int pn_rate_read_dtmf_clamp_report(pn_rate *r, void *h_report);
+int pn_rate_read_dtmf_clamp_report_dev(pn_rate *r, void *d_report);
+int pn_rate_debug_dtmf_clamp_state(pn_rate *r, void *h_state);   /* tests and debugging: [n_streams][4] state words to the host, synchronising; zeros while no stream was ever enabled */
+int pn_rate_debug_set_dtmf_report(pn_rate *r, const void *h_report);   /* TESTS ONLY, never in a product: [n_streams][4] words OVERWRITE the detector's report rows — the buffer pn_rate_read_dtmf_report reads too — so that pn_rate_dtmf_clamp_f32 can be run over hand-made rows; synchronising; as a side effect it allocates what removal needs.  The next detector launch overwrites them again */
 
 const char *pn_last_error(void);
 const char *pn_version(void);

@@ -55,6 +55,13 @@ DTMF_MIN_RMS, DTMF_PURITY, DTMF_TWIST_FWD, DTMF_TWIST_REV, DTMF_REL, DTMF_ON_FRA
 DTMF_REPORT_WORDS, DTMF_STATE_WORDS = 4, 24
 DTMF_ON, DTMF_HIT, DTMF_BEGIN, DTMF_END, DTMF_HELD_LOST = 1, 2, 4, 8, 16          # its flags, the low byte of report word 0
 DTMF_REPORT_DTYPE = np.dtype([("word0", "<u4"), ("dur", "<u4"), ("count", "<u4"), ("last4", "<u4")])   # word0: flags | cur << 8 | ended << 16
+# DTMF removal (include/percepnet_hip.h "DTMF removal"): PN_DTMF_CLAMP_*
+DTMF_CLAMP_N_PARAMS = 4
+DTMF_CLAMP_PRE, DTMF_CLAMP_POST, DTMF_CLAMP_VOLUME, DTMF_CLAMP_TS_PER_FRAME = range(4)   # parameter indices
+DTMF_CLAMP_REPORT_WORDS, DTMF_CLAMP_STATE_WORDS = 4, 4
+DTMF_CLAMP_ON, DTMF_CLAMP_MUTED, DTMF_CLAMP_FADE_OUT, DTMF_CLAMP_FADE_IN, DTMF_CLAMP_LATE, DTMF_CLAMP_EVENT, DTMF_CLAMP_EVENT_END = 1, 2, 4, 8, 16, 32, 64   # report word 0
+DTMF_CLAMP_REPORT_DTYPE = np.dtype([("flags", "<u4"), ("event", "<u4"), ("event_end", "<u4"), ("muted", "<u4")])   # event, event_end: RFC 4733 payloads, 0 for none
+DTMF_CLAMP_DELAY = 6         # output row t is input row t - 6: events run this many frames ahead of the audio they describe
 DTMF_ROWS_PER_PASS = 2048    # the kernel's grid covers this many rows at once (csrc/pn_launch.h PN_DTMF_MAX_BLOCKS blocks of four); beyond it a block makes further passes
 # call-state records (include/percepnet_hip.h "call-state records"): PN_RATE_CALL_*, PN_CALL_*
 SS_BAD_STATE = -7         # pn_rate_call_state_check: a body that breaks an invariant, an unknown section, words in an absent section
@@ -284,6 +291,18 @@ def load_library():
             getattr(L, name).argtypes = [_vp, _vp]
         L.pn_rate_set_stream_dtmf.argtypes = [_vp, _vp, ctypes.c_int, _vp]
         L.pn_rate_dtmf_f32.argtypes = [_vp, _vp, _vp, ctypes.c_int]
+    if hasattr(L, "pn_rate_set_stream_dtmf_clamp"):
+        L.pn_dtmf_clamp_default_params.argtypes = [_vp]
+        L.pn_dtmf_clamp_params_check.argtypes = [_vp, _vp]
+        L.pn_dtmf_clamp_frame.argtypes = [_vp, _vp, _vp, _vp, _vp]
+        L.pn_dtmf_event_payload.restype = ctypes.c_uint32
+        L.pn_dtmf_event_payload.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int]
+        L.pn_rate_set_dtmf_clamp_report.argtypes = [_vp, ctypes.c_int]
+        for name in ("pn_rate_set_dtmf_clamp_params", "pn_rate_get_dtmf_clamp_params", "pn_rate_get_stream_dtmf_clamp", "pn_rate_read_dtmf_clamp_report",
+                     "pn_rate_read_dtmf_clamp_report_dev", "pn_rate_debug_dtmf_clamp_state", "pn_rate_debug_set_dtmf_report"):
+            getattr(L, name).argtypes = [_vp, _vp]
+        L.pn_rate_set_stream_dtmf_clamp.argtypes = [_vp, _vp, ctypes.c_int, _vp]
+        L.pn_rate_dtmf_clamp_f32.argtypes = [_vp, _vp, _vp, ctypes.c_int]
     if hasattr(L, "pn_host_pipeline_prepare"):
         L.pn_host_pipeline_prepare.argtypes = [_vp]
     L.pn_ctx_debug_copy.restype = ctypes.c_longlong
@@ -869,6 +888,61 @@ def dtmf_frame(params, state, row, concealed=False):
     return int(flags), rep
 
 
+def dtmf_clamp_default_params():
+    """-> int32 [DTMF_CLAMP_N_PARAMS]: DTMF removal's default parameters (pn_dtmf_clamp_default_params, host only)."""
+    p = np.empty(DTMF_CLAMP_N_PARAMS, np.int32)
+    load_library().pn_dtmf_clamp_default_params(p.ctypes.data)
+    return p
+
+
+def _dtmf_clamp_params(params):
+    p = np.asarray(params).ravel()
+    if p.size != DTMF_CLAMP_N_PARAMS:
+        raise PercepNetError(f"{p.size} DTMF removal parameters: a set has {DTMF_CLAMP_N_PARAMS}")
+    if not np.issubdtype(p.dtype, np.integer) and not np.all(p == np.floor(p)):
+        raise PercepNetError("DTMF removal parameters are whole numbers")
+    return np.ascontiguousarray(p, dtype=np.int32)
+
+
+def dtmf_clamp_params_check(params, dtmf_params=None):
+    """Raises PercepNetError naming the first parameter outside its range or, with the detector's parameters given, a guard that is
+    not in time: on_frames + pre > 5 (pn_dtmf_clamp_params_check, host only)."""
+    L = load_library()
+    d = _dtmf_params(dtmf_params) if dtmf_params is not None else None
+    if L.pn_dtmf_clamp_params_check(_dtmf_clamp_params(params).ctypes.data, d.ctypes.data if d is not None else None) != 0:
+        raise PercepNetError(_err(L))
+
+
+def dtmf_event_payload(digit, end, volume, dur, ts_per_frame):
+    """-> the RFC 4733 payload of `digit` (a character or its code) after dur frames as a 32-bit value, to be sent big-endian; 0 for
+    a digit that is none (pn_dtmf_event_payload, host only)."""
+    code = ord(digit) if isinstance(digit, str) else int(digit)
+    return int(load_library().pn_dtmf_event_payload(code, 1 if end else 0, int(volume), int(dur) & 0xffffffff, int(ts_per_frame)))
+
+
+def dtmf_clamp_frame(params, state, det_report, row):
+    """One frame of DTMF removal on one row of 480 samples of a stream with removal on (pn_dtmf_clamp_frame, host only).  state:
+    uint32 [DTMF_CLAMP_STATE_WORDS] (zeros are fresh), row: float32 [480], both updated IN PLACE; det_report: the detector's four
+    report words of this frame, None: detection off -> (the flags, the DTMF_CLAMP_REPORT_DTYPE row).  The in-time condition is not
+    checked here."""
+    L = load_library()
+    if not isinstance(row, np.ndarray) or row.dtype != np.float32 or row.size != 480 or not row.flags.c_contiguous or not row.flags.writeable:
+        raise PercepNetError("row: 480 writable contiguous float32 samples")
+    if not isinstance(state, np.ndarray) or state.dtype != np.uint32 or state.size != DTMF_CLAMP_STATE_WORDS or not state.flags.c_contiguous or not state.flags.writeable:
+        raise PercepNetError(f"state: {DTMF_CLAMP_STATE_WORDS} writable contiguous uint32 words")
+    det = None
+    if det_report is not None:
+        det = np.ascontiguousarray(np.asarray(det_report).view(np.uint32) if isinstance(det_report, np.ndarray) and det_report.dtype == DTMF_REPORT_DTYPE else det_report,
+                                   dtype=np.uint32).ravel()
+        if det.size != DTMF_REPORT_WORDS:
+            raise PercepNetError(f"a detector report row of {det.size} words: it has {DTMF_REPORT_WORDS}")
+    rep = np.zeros((), DTMF_CLAMP_REPORT_DTYPE)
+    flags = L.pn_dtmf_clamp_frame(_dtmf_clamp_params(params).ctypes.data, state.ctypes.data, det.ctypes.data if det is not None else None, row.ctypes.data, rep.ctypes.data)
+    if flags < 0:
+        raise PercepNetError(_err(L))
+    return int(flags), rep
+
+
 class RateConverter:
     """8, 16, 24 or 32 kHz streams through a 48 kHz Context (pn_rate): a converter beside `ctx` for all of its streams at ONE rate.
     It borrows the context (device, n_streams, HIP stream): close the converter before the context."""
@@ -1307,6 +1381,72 @@ class RateConverter:
         """The same into device memory [n_streams][4] words, asynchronous on the context's stream (pn_rate_read_dtmf_report_dev)."""
         self._chk(self.L.pn_rate_read_dtmf_report_dev(self.h, d_report))
 
+    # DTMF removal: a detected digit is muted in the stream's enhanced 48 kHz row, behind the engine and in front of the level control
+    def set_stream_dtmf_clamp(self, ids, on):
+        """Removal on or off for the streams `ids` from the next frame on (pn_rate_set_stream_dtmf_clamp): asynchronous, ordered like
+        set_stream_dtmf.  `on`: one value for all of them or one per id.  A stream that was off starts from the fresh state.  Refused
+        while the detector's on_frames + pre > 5.  It acts on streams whose detection is on too."""
+        a, n = self._ids(ids)
+        w = np.asarray(on).astype(bool).astype(np.uint8).ravel()
+        if w.size == 1:
+            w = np.repeat(w, n)
+        if w.size != n:
+            raise PercepNetError(f"{w.size} switches for {n} streams")
+        w = np.ascontiguousarray(w)
+        self._chk(self.L.pn_rate_set_stream_dtmf_clamp(self.h, a.ctypes.data, n, w.ctypes.data))
+
+    def stream_dtmf_clamp(self):
+        """-> uint8 [n_streams]: the switches as last set (pn_rate_get_stream_dtmf_clamp); 0 everywhere on a new converter."""
+        w = np.empty(self.n_streams, np.uint8)
+        self._chk(self.L.pn_rate_get_stream_dtmf_clamp(self.h, w.ctypes.data))
+        return w
+
+    def set_dtmf_clamp_params(self, params):
+        """The converter's DTMF_CLAMP_N_PARAMS parameters from the next frame on (pn_rate_set_dtmf_clamp_params); refused as a whole,
+        naming the first bad one or the two values that are not in time."""
+        self._chk(self.L.pn_rate_set_dtmf_clamp_params(self.h, _dtmf_clamp_params(params).ctypes.data))
+
+    def dtmf_clamp_params(self):
+        """-> int32 [DTMF_CLAMP_N_PARAMS] as last set (pn_rate_get_dtmf_clamp_params); dtmf_clamp_default_params() on a new converter."""
+        p = np.empty(DTMF_CLAMP_N_PARAMS, np.int32)
+        self._chk(self.L.pn_rate_get_dtmf_clamp_params(self.h, p.ctypes.data))
+        return p
+
+    def dtmf_clamp_f32_dev(self, d_y48, ids=None):
+        """The removal stage on its own over device rows [n_streams][480] float, in place (pn_rate_dtmf_clamp_f32); it reads the
+        detector's report rows as the last detector launch, or set_dtmf_report_rows, left them."""
+        a, n = self._ids(ids)
+        self._chk(self.L.pn_rate_dtmf_clamp_f32(self.h, d_y48, a.ctypes.data if a is not None else None, n))
+
+    def set_dtmf_clamp_report(self, on):
+        self._chk(self.L.pn_rate_set_dtmf_clamp_report(self.h, 1 if on else 0))
+
+    def read_dtmf_clamp_report(self):
+        """-> DTMF_CLAMP_REPORT_DTYPE [n_streams]: the records of the last frame that ran the stage (pn_rate_read_dtmf_clamp_report,
+        synchronising).  The events are about the input: DTMF_CLAMP_DELAY frames ahead of the audio they describe."""
+        rep = np.empty(self.n_streams, DTMF_CLAMP_REPORT_DTYPE)
+        self._chk(self.L.pn_rate_read_dtmf_clamp_report(self.h, rep.ctypes.data))
+        return rep
+
+    def read_dtmf_clamp_report_dev(self, d_report):
+        """The same into device memory [n_streams][4] words, asynchronous on the context's stream (pn_rate_read_dtmf_clamp_report_dev)."""
+        self._chk(self.L.pn_rate_read_dtmf_clamp_report_dev(self.h, d_report))
+
+    def dtmf_clamp_state(self):
+        """-> uint32 [n_streams, DTMF_CLAMP_STATE_WORDS]: the removal state words (pn_rate_debug_dtmf_clamp_state, synchronising): for tests."""
+        st = np.empty((self.n_streams, DTMF_CLAMP_STATE_WORDS), np.uint32)
+        self._chk(self.L.pn_rate_debug_dtmf_clamp_state(self.h, st.ctypes.data))
+        return st
+
+    def set_dtmf_report_rows(self, rows):
+        """TESTS ONLY: uint32 [n_streams, 4] overwrite the detector's report rows — the buffer read_dtmf_report reads too — so that
+        dtmf_clamp_f32_dev can run over hand-made rows (pn_rate_debug_set_dtmf_report, synchronising; it allocates what removal
+        needs).  The next detector launch overwrites them again."""
+        w = np.ascontiguousarray(rows, dtype=np.uint32)
+        if w.size != self.n_streams * DTMF_REPORT_WORDS:
+            raise PercepNetError(f"{w.size} words: the detector's report has {self.n_streams * DTMF_REPORT_WORDS}")
+        self._chk(self.L.pn_rate_debug_set_dtmf_report(self.h, w.ctypes.data))
+
     # call-state records (include/percepnet_hip.h "call-state records"): the PLC, AGC, limiter and level state, one size for every
     # rate; imported BEHIND import_streams, which zeroes those states.  Defined here once: a mixed converter uses them unchanged
     def call_state_sections(self):
@@ -1352,7 +1492,8 @@ class RateConverter:
 
     def kernel_times(self, names=("rate_up", "rate_down")):
         """-> {"rate_up": (total_ms, launches), "rate_down": (...)}; names: which kernels ("rate_mix" is the conference mix,
-        "rate_plc" the packet-loss concealer, "rate_agc" the level control, "rate_lim" the output limiter, "rate_dtmf" the DTMF detector)"""
+        "rate_plc" the packet-loss concealer, "rate_agc" the level control, "rate_lim" the output limiter, "rate_dtmf" the DTMF detector,
+        "rate_clamp" DTMF removal)"""
         out = {}
         for name in names:
             ms = ctypes.c_double()

@@ -5,7 +5,7 @@
 // dropped, main.cpp:32-33); with a single pair ./feature_test.raw gets 68 floats per frame.
 //
 //   percepnet_run [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N]
-//                 [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--plc [--lose P:F0-F1,P:F,..]] [--agc RMS [--agc-max-gain G]] [--limiter CEIL [--limiter-hold H]] [--dtmf [--dtmf-on-frames N]] [--migrate-at F] [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
+//                 [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--plc [--lose P:F0-F1,P:F,..]] [--agc RMS [--agc-max-gain G]] [--limiter CEIL [--limiter-hold H]] [--dtmf [--dtmf-on-frames N]] [--dtmf-clamp [--dtmf-guard PRE,POST]] [--migrate-at F] [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
 //                 in0.pcm out0.pcm [in1.pcm out1.pcm ...]
 //
 // --rate R: the files are raw int16 at R Hz instead of 48 kHz, in frames of n = 480 * R / 48000 samples (80 | 160 | 240 | 320): a rate
@@ -64,6 +64,12 @@
 // 48000, as --agc does.  --dtmf-on-frames N: the hits in a row that begin a digit, a whole number in [1, 100] (parameter
 // PN_DTMF_ON_FRAMES; default 3); it needs --dtmf.  With --migrate-at a digit in flight at the move is reported again: no record carries
 // the detector's state.
+// --dtmf-clamp (needs --dtmf): DTMF removal on every slot (pn_rate_set_stream_dtmf_clamp, once, like --dtmf): a detected digit is muted in
+// the pair's enhanced audio, with a fade in front and behind, at no added delay; one line "dtmf-event: pair P frame F event N end E
+// duration D" on stdout for every frame that carries an ENDED RFC 4733 event (N the event code 0..15, E its end bit, D its duration in
+// units of an 8 kHz RTP clock), read behind every submit like the digits.  F is the frame of the INPUT: the audio it describes leaves six
+// frames later.  --dtmf-guard PRE,POST: the rows removed in front of and behind a digit's marked rows, whole numbers in [0, 4] and
+// [0, 8] (parameters PN_DTMF_CLAMP_PRE and PN_DTMF_CLAMP_POST; default 1,0); it needs --dtmf-clamp, and on_frames + PRE must be <= 5.
 // --migrate-at F (needs a converter — --rate, --rates or an option that makes one — and one device): when frame F (the shard's frames
 // count from 0) has been delivered, the run builds a SECOND context and converter with the same settings, moves every slot there with
 // all three record kinds in the mover's order of include/percepnet_hip.h "call-state records" (the engine's, the converter's tails,
@@ -144,6 +150,8 @@ static std::vector<LoseRange> g_lose;                 // --lose: pair, first and
 static float g_agc = 0.0f, g_agc_max_gain = 0.0f;     // --agc: every pair's target RMS (0: not given); --agc-max-gain (0: not given)
 static bool g_dtmf = false;                            // --dtmf: detection on every pair
 static float g_dtmf_on_frames = 0.0f;                  // --dtmf-on-frames (0: not given)
+static bool g_dtmf_clamp = false;                      // --dtmf-clamp: removal on every pair
+static int g_dtmf_guard[2] = {-1, -1};                 // --dtmf-guard PRE,POST (-1: not given)
 static float g_limiter = 0.0f, g_limiter_hold = -1.0f; // --limiter: every pair's ceiling (0: not given); --limiter-hold (-1: not given)
 static long g_migrate_at = -1;                        // --migrate-at: the frame behind which every slot moves to a second context and converter (-1: not given)
 // --report: what a pair's written frames add up to (one report record = PN_REPORT_WORDS words, include/percepnet_hip.h)
@@ -227,6 +235,16 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
       if (pn_rate_set_dtmf_params(rt, params) || pn_rate_set_stream_dtmf(rt, all.data(), B, on.data()) || pn_rate_set_dtmf_report(rt, 1))
         return bad(std::string("--dtmf: ") + pn_last_error());
     }
+    if (g_dtmf_clamp) {                                   // every slot's switch, once, behind the detector's parameters
+      std::vector<int32_t> all(B);
+      std::vector<uint8_t> on(B, 1);
+      int32_t params[PN_DTMF_CLAMP_N_PARAMS];
+      for (int s = 0; s < B; s++) all[s] = s;
+      pn_dtmf_clamp_default_params(params);
+      if (g_dtmf_guard[0] >= 0) { params[PN_DTMF_CLAMP_PRE] = g_dtmf_guard[0]; params[PN_DTMF_CLAMP_POST] = g_dtmf_guard[1]; }
+      if (pn_rate_set_dtmf_clamp_params(rt, params) || pn_rate_set_stream_dtmf_clamp(rt, all.data(), B, on.data()) || pn_rate_set_dtmf_clamp_report(rt, 1))
+        return bad(std::string("--dtmf-clamp: ") + pn_last_error());
+    }
     if (postfilter) pn_ctx_set_postfilter(cx, 1);
     if ((g_saturate && pn_ctx_set_output_saturate(cx, 1)) || (g_report && pn_ctx_set_report(cx, 1))) return bad(pn_last_error());
     {
@@ -245,7 +263,7 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
   std::vector<int> cur_pair(B, 0);
   std::vector<long> pair_frame(B, 0);                   // --lose: the frames the pair playing in a slot has supplied so far
   std::vector<PairStat> stat(g_report ? P : 0);
-  std::vector<uint32_t> dtmf_rep(g_dtmf ? (size_t)B * PN_DTMF_REPORT_WORDS : 0);
+  std::vector<uint32_t> dtmf_rep(g_dtmf ? (size_t)B * PN_DTMF_REPORT_WORDS : 0), clamp_rep(g_dtmf_clamp ? (size_t)B * PN_DTMF_CLAMP_REPORT_WORDS : 0);
   auto open_pair = [&](int s) -> bool {                 // the next waiting pair starts playing in slot s
     const char *pi = paths[2 * (sh->first + next_pair)], *po = paths[2 * (sh->first + next_pair) + 1];
     cur_pair[s] = next_pair++; pair_frame[s] = 0;
@@ -387,6 +405,14 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
         if (sl.file[s] && (w0 & PN_DTMF_BEGIN)) printf("dtmf: pair %d frame %ld digit %c\n", sh->first + cur_pair[s], pair_frame[s] - 1, (char)((w0 >> 8) & 0xff));
       }
     }
+    if (g_dtmf_clamp) {                                // this frame's ended events
+      if (pn_rate_read_dtmf_clamp_report(rt, clamp_rep.data())) return fail(5, pn_last_error());
+      for (int s = 0; s < B; s++) {
+        const uint32_t *w = &clamp_rep[(size_t)s * PN_DTMF_CLAMP_REPORT_WORDS];
+        if (sl.file[s] && (w[0] & PN_DTMF_CLAMP_EVENT_END))
+          printf("dtmf-event: pair %d frame %ld event %u end %u duration %u\n", sh->first + cur_pair[s], pair_frame[s] - 1, w[2] >> 24, (w[2] >> 23) & 1u, w[2] & 0xffffu);
+      }
+    }
     if (t >= 2) flush(slot[(t - 2) % 3]);
   }
   if (pn_host_wait(cx)) return fail(5, pn_last_error());
@@ -396,7 +422,7 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
 
 // the usage text, for a command line without pairs and for a rate no converter takes.  Returns the exit status, 1.
 static int usage(const char *argv0) {
-  fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N] [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--plc [--lose P:F0-F1,P:F,..]] [--agc RMS [--agc-max-gain G]] [--limiter CEIL [--limiter-hold H]] [--dtmf [--dtmf-on-frames N]] [--migrate-at F] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv0);
+  fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N] [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--plc [--lose P:F0-F1,P:F,..]] [--agc RMS [--agc-max-gain G]] [--limiter CEIL [--limiter-hold H]] [--dtmf [--dtmf-on-frames N]] [--dtmf-clamp [--dtmf-guard PRE,POST]] [--migrate-at F] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv0);
   return 1;
 }
 
@@ -521,6 +547,21 @@ int main(int argc, char **argv) {
       params[PN_DTMF_ON_FRAMES] = g_dtmf_on_frames;
       if (end == v || *end || pn_dtmf_params_check(params)) { fprintf(stderr, "--dtmf-on-frames: expected a whole number of frames in [1, 100], got '%s'\n", v); return 1; }
     }
+    else if (!strcmp(argv[ai], "--dtmf-clamp")) g_dtmf_clamp = true;   // DTMF removal on every pair (pn_rate_set_stream_dtmf_clamp)
+    else if (!strcmp(argv[ai], "--dtmf-guard") && ai + 1 < argc) {    // rows removed in front of and behind a digit (PN_DTMF_CLAMP_PRE, PN_DTMF_CLAMP_POST)
+      const char *v = argv[++ai];
+      char *end = NULL;
+      int32_t params[PN_DTMF_CLAMP_N_PARAMS];
+      pn_dtmf_clamp_default_params(params);
+      const long pre = strtol(v, &end, 10);
+      bool ok = end != v && *end == ',';
+      const char *v2 = ok ? end + 1 : v;
+      const long post = ok ? strtol(v2, &end, 10) : 0;
+      ok = ok && end != v2 && !*end && pre >= 0 && pre <= 100 && post >= 0 && post <= 100;
+      if (ok) { params[PN_DTMF_CLAMP_PRE] = (int32_t)pre; params[PN_DTMF_CLAMP_POST] = (int32_t)post; }
+      if (!ok || pn_dtmf_clamp_params_check(params, NULL)) { fprintf(stderr, "--dtmf-guard: expected PRE,POST, whole numbers in [0, 4] and [0, 8], got '%s'\n", v); return 1; }
+      g_dtmf_guard[0] = (int)pre; g_dtmf_guard[1] = (int)post;
+    }
     else if (!strcmp(argv[ai], "--migrate-at") && ai + 1 < argc) {    // move every slot to a second context and converter behind this frame
       const char *v = argv[++ai];
       char *end = NULL;
@@ -569,6 +610,16 @@ int main(int argc, char **argv) {
   if (g_agc_max_gain > 0.0f && !(g_agc > 0.0f)) { fprintf(stderr, "--agc-max-gain needs --agc: it is a parameter of the level control\n"); return 1; }
   if (g_limiter_hold >= 0.0f && !(g_limiter > 0.0f)) { fprintf(stderr, "--limiter-hold needs --limiter: it is a parameter of the output limiter\n"); return 1; }
   if (g_dtmf_on_frames > 0.0f && !g_dtmf) { fprintf(stderr, "--dtmf-on-frames needs --dtmf: it is a parameter of the DTMF detector\n"); return 1; }
+  if (g_dtmf_clamp && !g_dtmf) { fprintf(stderr, "--dtmf-clamp needs --dtmf: a digit is removed where the detector finds it\n"); return 1; }
+  if (g_dtmf_guard[0] >= 0 && !g_dtmf_clamp) { fprintf(stderr, "--dtmf-guard needs --dtmf-clamp: it is a parameter of DTMF removal\n"); return 1; }
+  if (g_dtmf_clamp) {                                  // the guard in front must be in time for the detector's on_frames
+    float dp[PN_DTMF_N_PARAMS];
+    int32_t cp[PN_DTMF_CLAMP_N_PARAMS];
+    pn_dtmf_default_params(dp); pn_dtmf_clamp_default_params(cp);
+    if (g_dtmf_on_frames > 0.0f) dp[PN_DTMF_ON_FRAMES] = g_dtmf_on_frames;
+    if (g_dtmf_guard[0] >= 0) { cp[PN_DTMF_CLAMP_PRE] = g_dtmf_guard[0]; cp[PN_DTMF_CLAMP_POST] = g_dtmf_guard[1]; }
+    if (pn_dtmf_clamp_params_check(cp, dp)) { fprintf(stderr, "--dtmf-clamp: %s\n", pn_last_error()); return 1; }
+  }
   if ((g_plc || g_agc > 0.0f || g_limiter > 0.0f || g_dtmf) && !g_rate && g_rates.empty()) g_rates.assign(B, 48000);        // on its own: a mixed converter of all 48000
   if (g_migrate_at >= 0) {
     if (devices.size() > 1) { fprintf(stderr, "--migrate-at takes one device: the slots move between two contexts of one device\n"); return 1; }

@@ -134,6 +134,12 @@ void pn_launch_rate_lim(hipStream_t st, int n_rows, const int *d_ids, const floa
 #define PN_DTMF_MAX_BLOCKS 512
 void pn_launch_rate_dtmf(hipStream_t st, int n_rows, const int *d_ids, const int *d_on, const uint32_t *d_lost, uint32_t tick, const float *params, const float *rot16,
                          const float *d_tab, const float *x48, void *state, void *d_report);
+// DTMF removal (pn_rate_dtmf_clamp.hip; the rule pn_dtmf_clamp_rules.h): rows d_ids[0..n_rows) or, with d_ids == NULL, streams 0..n_rows
+// of y48 [.][480], in place.  d_on [n_streams] words: 0 = removal is off for the stream; params: the converter's PN_DTMF_CLAMP_N_PARAMS
+// int32 on the HOST, passed by value; d_det_report [n_streams][4] words: the detector's report rows of this frame, or NULL: detection is
+// off for everybody.  State [n_streams][4] words; d_report [n_streams][4] words or NULL
+void pn_launch_rate_dtmf_clamp(hipStream_t st, int n_rows, const int *d_ids, const int *d_on, const int32_t *params, const void *d_det_report, float *y48,
+                               void *state, void *d_report);
 // call-state records (pn_rate_call.hip; layout and verdict pn_call_rules.h): record i of rec [n][PN_RATE_CALL_STATE_BYTES] (16-byte aligned)
 // <-> the PLC, AGC, limiter and level state of stream d_ids[i].  held: the PN_CALL_* states the converter holds — a state's pointers
 // are read only under its bit and may be NULL otherwise.  scatter: d_status[i] receives record i's verdict, a refused record moves nothing

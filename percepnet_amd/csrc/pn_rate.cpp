@@ -15,10 +15,11 @@
 #include "pn_lim_rules.h"    // the output limiter: the rule for the host, what parameters and ceilings must be
 #include "pn_call_rules.h"   // call-state records: the layout and the verdict
 #include "pn_dtmf_rules.h"   // DTMF detection: the rule for the host, what parameters must be, the tables
+#include "pn_dtmf_clamp_rules.h"   // DTMF removal: the rule for the host, what parameters must be, when a guard is in time
 #include <string>
 #include <vector>
 
-enum { RF_UP, RF_DOWN, RF_MIX, RF_PLC, RF_AGC, RF_LIM, RF_DTMF, RF_COUNT };   // the timed kernels (pn_rate_kernel_time), named by kRateFamily below
+enum { RF_UP, RF_DOWN, RF_MIX, RF_PLC, RF_AGC, RF_LIM, RF_DTMF, RF_CLAMP, RF_COUNT };   // the timed kernels (pn_rate_kernel_time), named by kRateFamily below
 struct pn_rate {
   pn_ctx *c;                    // borrowed: device, B, stream, the id ring, the saturate setting
   int rate, f, n, td;           // rate_hz, its factor (pn_rate_design.h: L, or PN_RATE_F_3_2 for 32000), samples per row, words per down tail row (2D / M).  Mixed: 0, 0, 480, 192
@@ -97,6 +98,16 @@ struct pn_rate {
   int *d_dtmf_on = NULL;                              // [B] words
   float *d_dtmf_tab = NULL;                           // ct [8][480], st [8][480]
   void *d_dtmf_state = NULL, *d_dtmf_report = NULL;   // [B][24] and [B][4] words
+  // DTMF removal (pn_rate_set_stream_dtmf_clamp; the rule pn_dtmf_clamp_rules.h): SETTINGS — the converter's parameters, a switch per stream as
+  // last set (host) and as a word on the device, written in stream order through the id ring like the detector's — and the state, four words
+  // per stream.  The device side exists from the first enabling on, and with it d_dtmf_report: while clamp_on > 0 the detector writes its
+  // report rows whether or not the user reads them (dtmf_report).  clamp_on == 0: a frame launches nothing of it
+  bool clamp_report = false;
+  int32_t clamp_params[PN_DTMF_CLAMP_N_PARAMS];
+  std::vector<uint8_t> clamp_sw;                      // [B], 0
+  int clamp_on = 0;                                   // streams whose switch is on
+  int *d_clamp_on = NULL;                             // [B] words
+  void *d_clamp_state = NULL, *d_clamp_report = NULL; // [B][4] words each
   std::vector<void *> allocs;
   // timing of the kernels (pn_rate_set_profiling): HIP events around their launches, like the context's families but owned
   // here; while it is off no event exists and none is recorded
@@ -106,7 +117,7 @@ struct pn_rate {
   std::vector<hipEvent_t> event_pool;
   double fam_ms[RF_COUNT] = {}; int64_t fam_n[RF_COUNT] = {};
 };
-static const char *const kRateFamily[RF_COUNT] = {"rate_up", "rate_down", "rate_mix", "rate_plc", "rate_agc", "rate_lim", "rate_dtmf"};
+static const char *const kRateFamily[RF_COUNT] = {"rate_up", "rate_down", "rate_mix", "rate_plc", "rate_agc", "rate_lim", "rate_dtmf", "rate_clamp"};
 struct RateScope {
   pn_rate *r; int fam; hipEvent_t a, b; bool on;
   RateScope(pn_rate *r_, int fam_) : r(r_), fam(fam_), on(r_->profiling) {
@@ -180,6 +191,18 @@ extern "C" int pn_dtmf_frame(const float *params7, uint32_t *state24, const floa
   return pn_dtmf_frame_host(params7, state24, row480, concealed, report4);
 }
 extern "C" int pn_dtmf_tables(float *ct, float *st, float *rot16) { return pn_dtmf_tables_host(ct, st, rot16); }
+extern "C" int pn_dtmf_clamp_default_params(int32_t *params4) { if (!params4) { pn_set_error("NULL argument"); return -1; } pn_dtmf_clamp_default_params_host(params4); return 0; }
+extern "C" int pn_dtmf_clamp_params_check(const int32_t *params4, const float *dtmf_params7) {
+  if (dtmf_params7 && pn_dtmf_params_check_host(dtmf_params7)) return -1;
+  return pn_dtmf_clamp_params_check_host(params4, dtmf_params7 ? (int)dtmf_params7[PN_DTMF_ON_FRAMES] : 0);
+}
+extern "C" int pn_dtmf_clamp_frame(const int32_t *params4, uint32_t *state4, const uint32_t *det_report4, float *row480, uint32_t *report4) {
+  return pn_dtmf_clamp_frame_host(params4, state4, det_report4, row480, report4);
+}
+extern "C" uint32_t pn_dtmf_event_payload(int digit, int end, int volume, uint32_t dur, int ts_per_frame) {
+  if (digit < 0 || volume < 0 || volume > 63 || ts_per_frame < 1 || ts_per_frame > 65535) return 0u;
+  return pn_dtmf_event_payload_hd((uint32_t)digit, end != 0, (uint32_t)volume, dur, (uint32_t)ts_per_frame);
+}
 extern "C" int pn_rate_limiter_ceilings_check(const float *ceilings, int n) { return pn_lim_ceilings_list_check(ceilings, n); }
 
 // ---- lifecycle ---------------------------------------------------------------------------------------------------------------
@@ -208,6 +231,7 @@ extern "C" pn_rate *pn_rate_create(pn_ctx *c, int rate_hz) {
   r->agc_targets.assign((size_t)c->B, 0.0f); pn_agc_default_params_host(r->agc_params);
   r->lim_ceilings.assign((size_t)c->B, 0.0f); pn_lim_default_params_host(r->lim_params);
   r->dtmf_sw.assign((size_t)c->B, 0); pn_dtmf_default_params_host(r->dtmf_params);
+  r->clamp_sw.assign((size_t)c->B, 0); pn_dtmf_clamp_default_params_host(r->clamp_params);
   const size_t B = (size_t)c->B, nt = 2 * (size_t)PN_RATE_TAPS * pn_rate_factor_L(f) + 1;
   float h[2][PN_RATE_MAX_TAPS];
   auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
@@ -241,6 +265,7 @@ extern "C" pn_rate *pn_rate_create_mixed(pn_ctx *c, const int32_t *rates_hz) {
   r->agc_targets.assign((size_t)c->B, 0.0f); pn_agc_default_params_host(r->agc_params);
   r->lim_ceilings.assign((size_t)c->B, 0.0f); pn_lim_default_params_host(r->lim_params);
   r->dtmf_sw.assign((size_t)c->B, 0); pn_dtmf_default_params_host(r->dtmf_params);
+  r->clamp_sw.assign((size_t)c->B, 0); pn_dtmf_clamp_default_params_host(r->clamp_params);
   const size_t B = (size_t)c->B;
   if (rates_hz) r->rates.assign(rates_hz, rates_hz + B); else r->rates.assign(B, 48000);
   static const int kF[4] = {6, 3, 2, PN_RATE_F_3_2};   // (the order of pn_rate.hip rt_taps_offset; the h of 32000 is the table of 3 and is not staged twice)
@@ -290,7 +315,11 @@ static void agc_zero_rows(pn_rate *r, const int *d, int n) { pn_launch_zero_rows
 // the limiter state of the staged streams d[0..n) goes to zero: a fresh gain, no hold (nothing while no ceiling was ever set)
 static void lim_zero_rows(pn_rate *r, const int *d, int n) { pn_launch_zero_rows(r->c->stream, r->d_lim_state, 4, 4, 1, 0, d, n); }
 // the detector state of the staged streams d[0..n) goes to zero: no half sums, no digit (nothing while no stream was ever enabled)
-static void dtmf_zero_rows(pn_rate *r, const int *d, int n) { pn_launch_zero_rows(r->c->stream, r->d_dtmf_state, PN_DTMF_STATE_WORDS, PN_DTMF_STATE_WORDS, 1, 0, d, n); }
+// ... and with it the removal state: no marks, no cut, no event (nothing while removal was never enabled)
+static void dtmf_zero_rows(pn_rate *r, const int *d, int n) {
+  pn_launch_zero_rows(r->c->stream, r->d_dtmf_state, PN_DTMF_STATE_WORDS, PN_DTMF_STATE_WORDS, 1, 0, d, n);
+  pn_launch_zero_rows(r->c->stream, r->d_clamp_state, PN_DTMF_CLAMP_STATE_WORDS, PN_DTMF_CLAMP_STATE_WORDS, 1, 0, d, n);
+}
 // A rate change of the listed streams, asynchronous and ordered like pn_rate_reset_streams: the ids and the new factors go
 // through the context's id ring in one copy, one launch writes the factors, two zero the tails.
 extern "C" int pn_rate_set_stream_rates(pn_rate *r, const int32_t *ids, int n, const int32_t *rates_hz) {
@@ -710,7 +739,7 @@ extern "C" int pn_rate_set_stream_dtmf(pn_rate *r, const int32_t *ids, int n, co
     const int m = (int)(fresh.size() - at < 16384 ? fresh.size() - at : 16384);
     const int *d = stage_ids(r->c, fresh.data() + at, m);
     if (!d) return -1;
-    dtmf_zero_rows(r, d, m);
+    pn_launch_zero_rows(r->c->stream, r->d_dtmf_state, PN_DTMF_STATE_WORDS, PN_DTMF_STATE_WORDS, 1, 0, d, m);
   }
   if (mix_set_words(r, ids, n, v.data(), r->d_dtmf_on)) return -1;
   for (int i = 0; i < n; i++) { r->dtmf_on += v[i] - (r->dtmf_sw[ids[i]] ? 1 : 0); r->dtmf_sw[ids[i]] = (uint8_t)v[i]; }
@@ -725,6 +754,8 @@ extern "C" int pn_rate_get_stream_dtmf(const pn_rate *r, uint8_t *h_on) {
 extern "C" int pn_rate_set_dtmf_params(pn_rate *r, const float *params7) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   if (pn_dtmf_params_check_host(params7)) return -1;
+  // while removal is on for somebody its guard in front must stay in time
+  if (r->clamp_on > 0 && pn_dtmf_clamp_params_check_host(r->clamp_params, (int)params7[PN_DTMF_ON_FRAMES])) return -1;
   memcpy(r->dtmf_params, params7, sizeof(r->dtmf_params));
   return 0;
 }
@@ -763,6 +794,97 @@ extern "C" int pn_rate_debug_dtmf_state(pn_rate *r, void *h_state) {
 extern "C" int pn_rate_read_dtmf_report(pn_rate *r, void *h_report) { return dtmf_report_copy(r, h_report, hipMemcpyDeviceToHost); }
 extern "C" int pn_rate_read_dtmf_report_dev(pn_rate *r, void *d_report) { return dtmf_report_copy(r, d_report, hipMemcpyDeviceToDevice); }
 
+// ---- DTMF removal (include/percepnet_hip.h; the rule pn_dtmf_clamp_rules.h; the kernel pn_rate_dtmf_clamp.hip) ---------------------
+static int clamp_buffers(pn_rate *r) {               // (the caller is on the context's device)
+  if (r->d_clamp_state) return 0;
+  pn_ctx *c = r->c;
+  const size_t B = (size_t)c->B;
+  int *on = NULL; void *state = NULL;
+  auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
+  // the detector's report rows, which this stage reads: the user's buffer if there is one, otherwise one of the same kind
+  if (!r->d_dtmf_report && alloc(&r->d_dtmf_report, B * PN_DTMF_REPORT_WORDS * 4, true)) return -1;
+  if (alloc((void **)&on, B * 4, true) || alloc(&state, B * PN_DTMF_CLAMP_STATE_BYTES, true)) return -1;
+  r->d_clamp_on = on; r->d_clamp_state = state;
+  return 0;
+}
+extern "C" int pn_rate_set_stream_dtmf_clamp(pn_rate *r, const int32_t *ids, int n, const uint8_t *on) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (pn_dtmf_clamp_on_set_check(r->c->B, ids, n, on)) return -1;
+  if (n == 0) return 0;
+  std::vector<int32_t> v(n), fresh;
+  bool all_off = true;
+  for (int i = 0; i < n; i++) { v[i] = on[i] ? 1 : 0; all_off &= !on[i]; if (on[i] && !r->clamp_sw[ids[i]]) fresh.push_back(ids[i]); }
+  if (!all_off && pn_dtmf_clamp_params_check_host(r->clamp_params, (int)r->dtmf_params[PN_DTMF_ON_FRAMES])) return -1;
+  if (!r->d_clamp_state && all_off) return 0;                                    // (no stream has ever been enabled, and none is)
+  PN_ON_DEVICE(r->c);
+  if (clamp_buffers(r)) return -1;
+  for (size_t at = 0; at < fresh.size(); at += 16384) {                            // a stream that was off starts from the fresh state
+    const int m = (int)(fresh.size() - at < 16384 ? fresh.size() - at : 16384);
+    const int *d = stage_ids(r->c, fresh.data() + at, m);
+    if (!d) return -1;
+    pn_launch_zero_rows(r->c->stream, r->d_clamp_state, PN_DTMF_CLAMP_STATE_WORDS, PN_DTMF_CLAMP_STATE_WORDS, 1, 0, d, m);
+  }
+  if (mix_set_words(r, ids, n, v.data(), r->d_clamp_on)) return -1;
+  for (int i = 0; i < n; i++) { r->clamp_on += v[i] - (r->clamp_sw[ids[i]] ? 1 : 0); r->clamp_sw[ids[i]] = (uint8_t)v[i]; }
+  return 0;
+}
+extern "C" int pn_rate_get_stream_dtmf_clamp(const pn_rate *r, uint8_t *h_on) {
+  if (!r || !h_on) { pn_set_error("NULL argument"); return -1; }
+  for (int s = 0; s < r->c->B; s++) h_on[s] = r->clamp_sw[s];
+  return 0;
+}
+// the parameters travel as an argument of every launch, so a change is ordered like one
+extern "C" int pn_rate_set_dtmf_clamp_params(pn_rate *r, const int32_t *params4) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (pn_dtmf_clamp_params_check_host(params4, (int)r->dtmf_params[PN_DTMF_ON_FRAMES])) return -1;
+  memcpy(r->clamp_params, params4, sizeof(r->clamp_params));
+  return 0;
+}
+extern "C" int pn_rate_get_dtmf_clamp_params(const pn_rate *r, int32_t *params4) {
+  if (!r || !params4) { pn_set_error("NULL argument"); return -1; }
+  memcpy(params4, r->clamp_params, sizeof(r->clamp_params));
+  return 0;
+}
+extern "C" int pn_rate_set_dtmf_clamp_report(pn_rate *r, int enable) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (enable && !r->d_clamp_report) {
+    PN_ON_DEVICE(r->c);
+    if (dev_alloc_into(r->allocs, r->bytes, r->c->stream, &r->d_clamp_report, (size_t)r->c->B * PN_DTMF_CLAMP_REPORT_WORDS * 4, true)) return -1;
+  }
+  r->clamp_report = enable != 0;
+  return 0;
+}
+static int clamp_report_copy(pn_rate *r, void *dst, hipMemcpyKind kind) {
+  if (!r || !dst) { pn_set_error("NULL argument"); return -1; }
+  if (!r->clamp_report) { pn_set_error("the DTMF removal report is off (pn_rate_set_dtmf_clamp_report)"); return -1; }
+  PN_ON_DEVICE(r->c);
+  PN_HIP_CHECK(hipMemcpyAsync(dst, r->d_clamp_report, (size_t)r->c->B * PN_DTMF_CLAMP_REPORT_WORDS * 4, kind, r->c->stream));
+  if (kind == hipMemcpyDeviceToHost) PN_HIP_CHECK(hipStreamSynchronize(r->c->stream));
+  return 0;
+}
+extern "C" int pn_rate_read_dtmf_clamp_report(pn_rate *r, void *h_report) { return clamp_report_copy(r, h_report, hipMemcpyDeviceToHost); }
+extern "C" int pn_rate_read_dtmf_clamp_report_dev(pn_rate *r, void *d_report) { return clamp_report_copy(r, d_report, hipMemcpyDeviceToDevice); }
+// the removal state of every stream to the host, synchronising (tests and debugging); zeros while no stream was ever enabled
+extern "C" int pn_rate_debug_dtmf_clamp_state(pn_rate *r, void *h_state) {
+  if (!r || !h_state) { pn_set_error("NULL argument"); return -1; }
+  const size_t bytes = (size_t)r->c->B * PN_DTMF_CLAMP_STATE_BYTES;
+  if (!r->d_clamp_state) { memset(h_state, 0, bytes); return 0; }
+  PN_ON_DEVICE(r->c);
+  PN_HIP_CHECK(hipMemcpyAsync(h_state, r->d_clamp_state, bytes, hipMemcpyDeviceToHost, r->c->stream));
+  PN_HIP_CHECK(hipStreamSynchronize(r->c->stream));
+  return 0;
+}
+// TESTS ONLY: the detector's report rows — the user's buffer too — overwritten from the host, synchronising, so that the stand-alone stage
+// can be run over hand-made rows; the next detector launch overwrites them again
+extern "C" int pn_rate_debug_set_dtmf_report(pn_rate *r, const void *h_report) {
+  if (!r || !h_report) { pn_set_error("NULL argument"); return -1; }
+  PN_ON_DEVICE(r->c);
+  if (clamp_buffers(r)) return -1;
+  PN_HIP_CHECK(hipMemcpyAsync(r->d_dtmf_report, h_report, (size_t)r->c->B * PN_DTMF_REPORT_WORDS * 4, hipMemcpyHostToDevice, r->c->stream));
+  PN_HIP_CHECK(hipStreamSynchronize(r->c->stream));
+  return 0;
+}
+
 extern "C" int pn_rate_reset(pn_rate *r) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   PN_ON_DEVICE(r->c);
@@ -777,6 +899,7 @@ extern "C" int pn_rate_reset(pn_rate *r) {
   if (r->d_agc_state) PN_HIP_CHECK(hipMemsetAsync(r->d_agc_state, 0, (size_t)r->c->B * PN_AGC_STATE_BYTES, r->c->stream));
   if (r->d_lim_state) PN_HIP_CHECK(hipMemsetAsync(r->d_lim_state, 0, (size_t)r->c->B * PN_LIM_STATE_BYTES, r->c->stream));
   if (r->d_dtmf_state) PN_HIP_CHECK(hipMemsetAsync(r->d_dtmf_state, 0, (size_t)r->c->B * PN_DTMF_STATE_BYTES, r->c->stream));
+  if (r->d_clamp_state) PN_HIP_CHECK(hipMemsetAsync(r->d_clamp_state, 0, (size_t)r->c->B * PN_DTMF_CLAMP_STATE_BYTES, r->c->stream));
   return 0;
 }
 
@@ -878,7 +1001,18 @@ static int rate_dtmf(pn_rate *r, const float *d_x48, const RateRows &rows, const
   {
     RateScope sc(r, RF_DTMF);
     pn_launch_rate_dtmf(r->c->stream, rows.n, rows.d_ids, r->d_dtmf_on, d_lost, tick, r->dtmf_params, pn_dtmf_tables_ref().rot, r->d_dtmf_tab, d_x48,
-                        r->d_dtmf_state, r->dtmf_report ? r->d_dtmf_report : NULL);
+                        r->d_dtmf_state, r->dtmf_report || r->clamp_on > 0 ? r->d_dtmf_report : NULL);
+  }
+  PN_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+// DTMF removal over the rows, in place on y48; det: the detector ran in this frame (or the caller vouches for its report rows), otherwise
+// every stream counts as "detection off"
+static int rate_clamp(pn_rate *r, float *d_y48, const RateRows &rows, bool det) {
+  {
+    RateScope sc(r, RF_CLAMP);
+    pn_launch_rate_dtmf_clamp(r->c->stream, rows.n, rows.d_ids, r->d_clamp_on, r->clamp_params, det ? r->d_dtmf_report : NULL, d_y48, r->d_clamp_state,
+                              r->clamp_report ? r->d_clamp_report : NULL);
   }
   PN_HIP_CHECK(hipGetLastError());
   return 0;
@@ -952,6 +1086,16 @@ extern "C" int pn_rate_dtmf_f32(pn_rate *r, const float *d_x48, const int32_t *i
   return rate_dtmf(r, d_x48, rows, NULL, 0);
 }
 
+extern "C" int pn_rate_dtmf_clamp_f32(pn_rate *r, float *d_y48, const int32_t *ids, int n_ids) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (rate_aligned(d_y48, d_y48)) return -1;
+  PN_ON_DEVICE(r->c);
+  RateRows rows;
+  if (rate_rows(r, ids, n_ids, &rows)) return -1;
+  if (clamp_buffers(r)) return -1;                   // (no stream was ever enabled: every stream is off, the state exists from here on)
+  return rate_clamp(r, d_y48, rows, true);
+}
+
 // ---- one whole frame -----------------------------------------------------------------------------------------------------------
 // up into x48, while packet-loss concealment is on the concealer in place on x48, the engine's float frame from x48 into y48 (all streams, or the listed ones through the context's own active
 // set), while automatic level control is on and a stream has a target the level control in place on y48, down from y48 — or, while a stream is in a conference, the mix from y48 into o48 and down from o48 — and in front of the down-conversion, while a stream has a ceiling, the output limiter in place on the rows it reads.  A frame the engine refuses returns -1 with its error kept; the up kernel has then advanced its tails
@@ -987,6 +1131,9 @@ static int rate_frame(pn_rate *r, const void *d_in, void *d_out, float *d_gr, in
   // the DTMF detector, while somebody is enabled: behind the concealer and in front of the engine, reading x48 only
   if (r->dtmf_on > 0 && rate_dtmf(r, r->x48, rows, concealing ? r->d_plc_lost : NULL, plc_tick_used)) return -1;
   if (active ? pn_process_f32_active(c, r->x48, r->y48, d_gr, ids, n) : pn_process_f32(c, r->x48, r->y48, d_gr)) return -1;
+  // DTMF removal, while somebody has it on: in place on y48, so the level control, the mix, the limiter and the down-conversion never see the
+  // tone.  The detector's report rows are this frame's only if it ran (somebody has detection on); otherwise nobody has a digit
+  if (r->clamp_on > 0 && rate_clamp(r, r->y48, rows, r->dtmf_on > 0)) return -1;
   // the level control, while on and somebody has a target: in place on y48, so the mix, its levels and the down-conversion see levelled rows
   if (r->agc && r->agc_on > 0 && rate_agc(r, r->y48, rows, concealing ? r->d_plc_lost : NULL, plc_tick_used)) return -1;
   float *o = r->y48;
@@ -1083,7 +1230,7 @@ extern "C" int pn_rate_submit_host_g711_active(pn_rate *r, const uint8_t *h_in, 
 // ---- timing the kernels --------------------------------------------------------------------------------------------------------
 extern "C" int pn_rate_set_profiling(pn_rate *r, int enable) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
-  if (enable && r->event_pool.size() < 1024) {        // up to seven scopes a frame (up, plc, dtmf, agc, mix, lim, down): enough for 73 frames between two reads; created outside any timed region
+  if (enable && r->event_pool.size() < 1024) {        // up to eight scopes a frame (up, plc, dtmf, clamp, agc, mix, lim, down): enough for 64 frames between two reads; created outside any timed region
     PN_ON_DEVICE(r->c);
     while (r->event_pool.size() < 1024) { hipEvent_t e; PN_HIP_CHECK(hipEventCreate(&e)); r->event_pool.push_back(e); }
   }
@@ -1096,7 +1243,7 @@ extern "C" int pn_rate_kernel_time(pn_rate *r, const char *name, double *total_m
   if (rate_flush_events(r)) return -1;
   for (int i = 0; i < RF_COUNT; i++)
     if (!strcmp(name, kRateFamily[i])) { if (total_ms) *total_ms = r->fam_ms[i]; if (launches) *launches = r->fam_n[i]; return 0; }
-  pn_set_error("unknown converter kernel '%s' (rate_up, rate_down, rate_mix, rate_plc, rate_agc, rate_lim, rate_dtmf)", name);
+  pn_set_error("unknown converter kernel '%s' (rate_up, rate_down, rate_mix, rate_plc, rate_agc, rate_lim, rate_dtmf, rate_clamp)", name);
   return -1;
 }
 extern "C" int pn_rate_reset_profile(pn_rate *r) {
