@@ -1,38 +1,54 @@
 // Host side of the batched rate converter (include/percepnet_hip.h "batched rate converter" and "mixed rates"): an object BESIDE a context, built
 // like the feature generator — it borrows the context's device, batch size and HIP stream, and owns everything else: the two
-// tap tables on the device, the per-stream tails of the two kernels (pn_rate.hip), the 48 kHz rows between the conversions and
+// tap tables on the device, the per-stream state (the tails of the two kernels of pn_rate.hip and the state of every stage behind them), the 48 kHz rows between the conversions and
 // the staging rows of the host-buffer paths.  The pipelined path (pn_rate_submit_host_*) runs its frames through the CONTEXT's
 // pipeline (pn_host_pipe.cpp pipe_submit) with the converter's own two staging pairs.  Nothing of it lives in pn_ctx, its state table or its records.  Every launch goes
 // to the context's stream, so a converter call is ordered against the context's calls like they are against each other.
+//
+// What is stated once, and where: the per-stream STATE — its buffers, their widths, the events that clear them, their sections of the
+// call-state record — is the table of pn_rate_layout.h, held as pn_rate::st[] and walked by state_clear_all / state_clear_rows /
+// state_alloc below; a new stage's state is one entry there.  A STAGE — its timed family, its report — is a row of kRateStage, served by
+// rate_set_report / rate_report_copy.  A per-stream SETTING goes through rate_set_words and comes back through rate_get.
 #include "pn_context.h"      // the context it borrows, the launchers, dev_alloc_into, stage_ids, the id rule, host_records_sync
-#include "pn_rate_design.h"
+#include "pn_rate_layout.h"  // the per-stream state, and through it every stage's rules: pn_rate_design.h, pn_call_rules.h (pn_plc_rules.h,
+                             // pn_agc_rules.h, pn_lim_rules.h, pn_mix_rules.h), pn_dtmf_rules.h, pn_dtmf_clamp_rules.h
 #include "pn_rate_mixed.h"   // the mixed converter's host rules: the five rates, a rate change, one rate per record call
 #include "pn_g711.h"         // the 8-bit sample format: the companding and what a list of laws must be
 #include "pn_conf.h"         // conferences: what an id must be, the table after a change, the members in ascending order
-#include "pn_mix_rules.h"    // loudest-N, send gains, hold: what the settings must be; the level and the selection for the host
-#include "pn_plc_rules.h"    // packet-loss concealment: the signal rule for the host, the sizes of the state
-#include "pn_agc_rules.h"    // automatic level control: the rule for the host, what parameters and targets must be
-#include "pn_lim_rules.h"    // the output limiter: the rule for the host, what parameters and ceilings must be
-#include "pn_call_rules.h"   // call-state records: the layout and the verdict
-#include "pn_dtmf_rules.h"   // DTMF detection: the rule for the host, what parameters must be, the tables
-#include "pn_dtmf_clamp_rules.h"   // DTMF removal: the rule for the host, what parameters must be, when a guard is in time
 #include <string>
 #include <vector>
 
-enum { RF_UP, RF_DOWN, RF_MIX, RF_PLC, RF_AGC, RF_LIM, RF_DTMF, RF_CLAMP, RF_COUNT };   // the timed kernels (pn_rate_kernel_time), named by kRateFamily below
+// the stages: the timed kernels (pn_rate_kernel_time) and their reports
+enum { RF_UP, RF_DOWN, RF_MIX, RF_PLC, RF_AGC, RF_LIM, RF_DTMF, RF_CLAMP, RF_COUNT };
+struct RateStage { const char *family; int report_words; const char *report_off; };   // report_words per stream, 0: the stage has no report
+static const RateStage kRateStage[RF_COUNT] = {
+    {"rate_up", 0, NULL},
+    {"rate_down", 0, NULL},
+    {"rate_mix", PN_MIX_REPORT_WORDS, "the mix report is off (pn_rate_set_mix_report)"},
+    {"rate_plc", PN_PLC_REPORT_WORDS, "the PLC report is off (pn_rate_set_plc_report)"},
+    {"rate_agc", PN_AGC_REPORT_WORDS, "the AGC report is off (pn_rate_set_agc_report)"},
+    {"rate_lim", PN_LIM_REPORT_WORDS, "the limiter report is off (pn_rate_set_limiter_report)"},
+    {"rate_dtmf", PN_DTMF_REPORT_WORDS, "the DTMF report is off (pn_rate_set_dtmf_report)"},
+    {"rate_clamp", PN_DTMF_CLAMP_REPORT_WORDS, "the DTMF removal report is off (pn_rate_set_dtmf_clamp_report)"},
+};
+enum { RATE_PIECE = 16384 };    // ids a setting stages through the id ring at a time
+
 struct pn_rate {
   pn_ctx *c;                    // borrowed: device, B, stream, the id ring, the saturate setting
   int rate, f, n, td;           // rate_hz, its factor (pn_rate_design.h: L, or PN_RATE_F_3_2 for 32000), samples per row, words per down tail row (2D / M).  Mixed: 0, 0, 480, 192
   size_t bytes;
   float *taps_up, *taps_down;   // [2D + 1] h, g.  Mixed: the tables of L = 6, 3, 2 one behind the other, and behind them the g of 32000
-  float *tail_up, *tail_down;   // [B][32], [B][td]: the state
+  void *st[PN_RS_COUNT] = {};   // the per-stream state, [B][pn_rate_state_words] each (pn_rate_layout.h): NULL until the owning stage is first used
+  void *d_report[RF_COUNT] = {};   // [B][kRateStage[].report_words] words: allocated by the first enabling of the report
+  bool report[RF_COUNT] = {};      // the report switches
   float *x48, *y48;             // [B][480]: the engine's input and output rows of a whole frame
   void *io_in, *io_out;         // [B][n] 4-byte words: staging rows of the host-buffer paths (slot 0 of the pipelined one)
   void *io_in1 = NULL, *io_out1 = NULL;   // slot 1 of the pipelined path: allocated by pn_rate_host_pipeline_prepare or the first submit
   float *io_gr;                 // [B][68]
-  // a mixed converter (pn_rate_create_mixed): the rate of every stream as last set (host), its factor on the device — written
-  // in stream order, so a frame submitted before a rate change still runs at the old rate — and a pinned landing place of the
-  // host-buffer path's output rows, of which only the streams' own samples go on to the caller
+  // the rate of every stream as last set (host; a single-rate converter: its rate everywhere).  A mixed converter
+  // (pn_rate_create_mixed) has its factor on the device — written in stream order, so a frame submitted before a rate change still
+  // runs at the old rate — and a pinned landing place of the host-buffer path's output rows, of which only the streams' own samples
+  // go on to the caller
   bool mixed;
   std::vector<int32_t> rates;   // [B]
   int *factors;                 // [B] device
@@ -50,64 +66,53 @@ struct pn_rate {
   int *d_conf = NULL, *d_members = NULL;   // [B], [B][32]
   uint32_t *d_stamp = NULL, tick = 0;      // [B]: == tick where the stream is on this frame's id list
   // loudest-N selection, send gains, hold and the mix report (pn_mix_rules.h): SETTINGS as last set (host) and on the device, and the
-  // one new state, a level per stream.  While every setting is at its default (mix_plain) rate_mix launches the plain kernel and
+  // one new state, a level per stream (st[PN_RS_LEVEL]).  While every setting is at its default (mix_plain) rate_mix launches the plain kernel and
   // none of the device side is read; it is allocated by the first setting call that leaves the defaults, never inside a frame
   std::vector<float> gains;     // [B], 1.0f
   std::vector<int32_t> caps;    // [B] N_c by conference number, 0: everybody
   int gains_off = 0, caps_on = 0;          // how many gains are not 1.0f, how many caps not 0
   float hold = 0.0f;            // d
-  bool mix_report = false;
-  float *d_gains = NULL, *d_level = NULL;  // [B], [B]
-  int *d_caps = NULL;                      // [B]
-  void *d_mix_report = NULL;               // [B][PN_MIX_REPORT_WORDS] words
+  float *d_gains = NULL;        // [B]
+  int *d_caps = NULL;           // [B]
   // packet-loss concealment (pn_rate_set_plc; the rule pn_plc_rules.h): the state — history ring, period buffer and four meta words per
   // stream — exists from the first enable on, never allocated inside a frame.  Marks (pn_rate_set_lost): a stamp word per stream on
   // the device, == plc_tick where the stream is lost in the NEXT frame, written in stream order through the id ring; the host keeps
   // the same marks, which is how a frame knows whom to leave out of the up-conversion.  A frame consumes them: plc_tick moves on
-  bool plc = false, plc_report = false;
-  float *d_plc_hist = NULL, *d_plc_q = NULL;           // [B][1920], [B][720]
-  void *d_plc_meta = NULL, *d_plc_report = NULL;      // [B][4] words each
+  bool plc = false;
   uint32_t *d_plc_lost = NULL, plc_tick = 1;          // [B]
   std::vector<uint8_t> lost_mark;                     // [B]
   std::vector<int32_t> lost_ids, up_ids;              // the marked streams; a frame's "advancing minus lost"
   // automatic level control (pn_rate_set_agc; the rule pn_agc_rules.h): SETTINGS — the switch, the converter's parameters, a target per
   // stream as last set (host) and on the device, written in stream order through the id ring like the send gains — and the state, four
   // words per stream.  The device side exists from the first enable on.  agc_on == 0: a frame launches nothing of it
-  bool agc = false, agc_report = false;
+  bool agc = false;
   float agc_params[PN_AGC_N_PARAMS];
   std::vector<float> agc_targets;                     // [B], 0
   int agc_on = 0;                                     // streams whose target is not 0
   float *d_agc_targets = NULL;                        // [B]
-  void *d_agc_state = NULL, *d_agc_report = NULL;     // [B][4] words each
   // the output limiter (pn_rate_set_stream_limiter; the rule pn_lim_rules.h): SETTINGS — the converter's parameters, a ceiling per stream
-  // as last set (host) and on the device, written in stream order through the id ring like the AGC targets, the report switch — and the
+  // as last set (host) and on the device, written in stream order through the id ring like the AGC targets — and the
   // state, four words per stream.  The device side exists from the first call that sets a ceiling on.  lim_on == 0: a frame launches nothing of it
-  bool lim_report = false;
   float lim_params[PN_LIM_N_PARAMS];
   std::vector<float> lim_ceilings;                    // [B], 0
   int lim_on = 0;                                     // streams whose ceiling is not 0
   float *d_lim_ceilings = NULL;                       // [B]
-  void *d_lim_state = NULL, *d_lim_report = NULL;     // [B][4] words each
   // DTMF detection (pn_rate_set_stream_dtmf; the rule pn_dtmf_rules.h): SETTINGS — the converter's parameters, a switch per stream as last
   // set (host) and as a word on the device, written in stream order through the id ring like the ceilings — and the state, 24 words per
   // stream.  The device side (with the twiddle tables) exists from the first enabling on.  dtmf_on == 0: a frame launches nothing of it
-  bool dtmf_report = false;
   float dtmf_params[PN_DTMF_N_PARAMS];
   std::vector<uint8_t> dtmf_sw;                       // [B], 0
   int dtmf_on = 0;                                    // streams whose switch is on
   int *d_dtmf_on = NULL;                              // [B] words
   float *d_dtmf_tab = NULL;                           // ct [8][480], st [8][480]
-  void *d_dtmf_state = NULL, *d_dtmf_report = NULL;   // [B][24] and [B][4] words
   // DTMF removal (pn_rate_set_stream_dtmf_clamp; the rule pn_dtmf_clamp_rules.h): SETTINGS — the converter's parameters, a switch per stream as
   // last set (host) and as a word on the device, written in stream order through the id ring like the detector's — and the state, four words
-  // per stream.  The device side exists from the first enabling on, and with it d_dtmf_report: while clamp_on > 0 the detector writes its
-  // report rows whether or not the user reads them (dtmf_report).  clamp_on == 0: a frame launches nothing of it
-  bool clamp_report = false;
+  // per stream.  The device side exists from the first enabling on, and with it d_report[RF_DTMF]: while clamp_on > 0 the detector writes its
+  // report rows whether or not the user reads them (report[RF_DTMF]).  clamp_on == 0: a frame launches nothing of it
   int32_t clamp_params[PN_DTMF_CLAMP_N_PARAMS];
   std::vector<uint8_t> clamp_sw;                      // [B], 0
   int clamp_on = 0;                                   // streams whose switch is on
   int *d_clamp_on = NULL;                             // [B] words
-  void *d_clamp_state = NULL, *d_clamp_report = NULL; // [B][4] words each
   std::vector<void *> allocs;
   // timing of the kernels (pn_rate_set_profiling): HIP events around their launches, like the context's families but owned
   // here; while it is off no event exists and none is recorded
@@ -117,7 +122,6 @@ struct pn_rate {
   std::vector<hipEvent_t> event_pool;
   double fam_ms[RF_COUNT] = {}; int64_t fam_n[RF_COUNT] = {};
 };
-static const char *const kRateFamily[RF_COUNT] = {"rate_up", "rate_down", "rate_mix", "rate_plc", "rate_agc", "rate_lim", "rate_dtmf", "rate_clamp"};
 struct RateScope {
   pn_rate *r; int fam; hipEvent_t a, b; bool on;
   RateScope(pn_rate *r_, int fam_) : r(r_), fam(fam_), on(r_->profiling) {
@@ -140,26 +144,16 @@ static int rate_flush_events(pn_rate *r) {
 }
 
 // ---- host only ---------------------------------------------------------------------------------------------------------------
-extern "C" int pn_rate_frame_samples(int rate_hz) {
+static int rate_factor_or_error(int rate_hz) {       // the factor of a single-rate converter's rate, or 0 with the error set
   const int f = pn_rate_factor(rate_hz);
-  if (!f) { pn_set_error("rate %d Hz: a converter takes " PN_RATE_TEXT, rate_hz); return -1; }
-  return pn_rate_factor_frame(f);
+  if (!f) pn_set_error("rate %d Hz: a converter takes " PN_RATE_TEXT, rate_hz);
+  return f;
 }
-extern "C" int pn_rate_delay_samples(int rate_hz) {
-  const int f = pn_rate_factor(rate_hz);
-  if (!f) { pn_set_error("rate %d Hz: a converter takes " PN_RATE_TEXT, rate_hz); return -1; }
-  return pn_rate_factor_delay(f);                      // the engine's 2880 samples at the low rate, T up and T down
-}
-extern "C" int pn_rate_taps(int rate_hz, int down, float *taps, int cap) {
-  const int f = pn_rate_factor(rate_hz);
-  if (!f) { pn_set_error("rate %d Hz: a converter takes " PN_RATE_TEXT, rate_hz); return -1; }
-  return pn_rate_design(f, down, taps, cap);
-}
-extern "C" size_t pn_rate_state_bytes(int rate_hz) {
-  const int f = pn_rate_factor(rate_hz);
-  if (!f) { pn_set_error("rate %d Hz: a converter takes " PN_RATE_TEXT, rate_hz); return 0; }
-  return 4 * pn_rate_record_words(f);
-}
+extern "C" int pn_rate_frame_samples(int rate_hz) { const int f = rate_factor_or_error(rate_hz); return f ? pn_rate_factor_frame(f) : -1; }
+// the engine's 2880 samples at the low rate, T up and T down
+extern "C" int pn_rate_delay_samples(int rate_hz) { const int f = rate_factor_or_error(rate_hz); return f ? pn_rate_factor_delay(f) : -1; }
+extern "C" int pn_rate_taps(int rate_hz, int down, float *taps, int cap) { const int f = rate_factor_or_error(rate_hz); return f ? pn_rate_design(f, down, taps, cap) : -1; }
+extern "C" size_t pn_rate_state_bytes(int rate_hz) { const int f = rate_factor_or_error(rate_hz); return f ? 4 * pn_rate_record_words(f) : 0; }
 extern "C" int pn_rate_state_check(const void *record, size_t bytes, int rate_hz) { return pn_rate_record_check(record, bytes, rate_hz); }
 extern "C" int pn_rate_mixed_frame_samples(int rate_hz) { return pn_rate_mixed_frame(rate_hz); }
 extern "C" int pn_rate_mixed_delay_samples(int rate_hz) { return pn_rate_mixed_delay(rate_hz); }
@@ -205,6 +199,131 @@ extern "C" uint32_t pn_dtmf_event_payload(int digit, int end, int volume, uint32
 }
 extern "C" int pn_rate_limiter_ceilings_check(const float *ceilings, int n) { return pn_lim_ceilings_list_check(ceilings, n); }
 
+// ---- the shared routines: allocation, the state table's walks, reports, per-stream settings ----------------------------------------
+// (callers are on the context's device.)  Device memory of the converter; p is written on success only, which is what lets a stage
+// allocate into locals and store its pointers in pn_rate once ALL of them are there: a failed enable leaves the stage "never enabled"
+template <class T>
+static int rate_alloc(pn_rate *r, T *&p, size_t bytes, bool zero) {
+  void *v = NULL;
+  if (dev_alloc_into(r->allocs, r->bytes, r->c->stream, &v, bytes, zero)) return -1;
+  p = static_cast<T *>(v);
+  return 0;
+}
+static float *stf(const pn_rate *r, int e) { return static_cast<float *>(r->st[e]); }
+static size_t state_bytes(const pn_rate *r, int e) { return (size_t)r->c->B * pn_rate_state_words(e, r->td) * 4; }
+// the state buffers of `stage`, zeroed, into p[] — r->st itself, or a stage's locals that state_commit stores behind its other allocations
+static int state_alloc(pn_rate *r, int stage, void *p[PN_RS_COUNT]) {
+  for (int e = 0; e < PN_RS_COUNT; e++)
+    if (pn_kRateState[e].stage == stage && rate_alloc(r, p[e], state_bytes(r, e), true)) return -1;
+  return 0;
+}
+static void state_commit(pn_rate *r, int stage, void *const p[PN_RS_COUNT]) {
+  for (int e = 0; e < PN_RS_COUNT; e++) if (pn_kRateState[e].stage == stage) r->st[e] = p[e];
+}
+// The two zeroing rules.  What `event` (of `stage`, where it is a stage's event) clears goes to zero for every stream ...
+static int state_clear_all(pn_rate *r, unsigned event, int stage = -1) {
+  for (int e = 0; e < PN_RS_COUNT; e++)
+    if (pn_rate_state_cleared(e, event, stage) && r->st[e]) PN_HIP_CHECK(hipMemsetAsync(r->st[e], 0, state_bytes(r, e), r->c->stream));
+  return 0;
+}
+// ... or for the staged streams d[0..n) (nothing where the buffer does not exist: pn_launch_zero_rows)
+static void state_clear_rows(pn_rate *r, unsigned event, const int *d, int n, int stage = -1) {
+  for (int e = 0; e < PN_RS_COUNT; e++) {
+    const int w = pn_rate_state_words(e, r->td);
+    if (pn_rate_state_cleared(e, event, stage)) pn_launch_zero_rows(r->c->stream, r->st[e], w, w, 1, 0, d, n);
+  }
+}
+// a stage switched on for streams that were off: they start from the fresh state.  Staged in pieces, in front of the switch write
+static int state_switch_on(pn_rate *r, int stage, const std::vector<int32_t> &fresh) {
+  for (size_t at = 0; at < fresh.size(); at += RATE_PIECE) {
+    const int m = (int)(fresh.size() - at < RATE_PIECE ? fresh.size() - at : RATE_PIECE);
+    const int *d = stage_ids(r->c, fresh.data() + at, m);
+    if (!d) return -1;
+    state_clear_rows(r, PN_RE_SWITCH_ON, d, m, stage);
+  }
+  return 0;
+}
+// the state of entry e of every stream to the host, synchronising (tests and debugging); zeros while the buffer does not exist
+static int state_debug_copy(pn_rate *r, int e, void *h_state) {
+  if (!r || !h_state) { pn_set_error("NULL argument"); return -1; }
+  if (!r->st[e]) { memset(h_state, 0, state_bytes(r, e)); return 0; }
+  PN_ON_DEVICE(r->c);
+  PN_HIP_CHECK(hipMemcpyAsync(h_state, r->st[e], state_bytes(r, e), hipMemcpyDeviceToHost, r->c->stream));
+  PN_HIP_CHECK(hipStreamSynchronize(r->c->stream));
+  return 0;
+}
+
+// a stage's report: the switch — the rows are allocated by the first enabling — what a launch is handed, and the two reads
+static int mix_buffers(pn_rate *r);
+static size_t report_bytes(const pn_rate *r, int fam) { return (size_t)r->c->B * kRateStage[fam].report_words * 4; }
+static int rate_set_report(pn_rate *r, int fam, int enable) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (enable && !r->d_report[fam]) {
+    PN_ON_DEVICE(r->c);
+    if (fam == RF_MIX && mix_buffers(r)) return -1;  // (the mix report is written by the selecting kernel, which reads the settings' device side)
+    if (rate_alloc(r, r->d_report[fam], report_bytes(r, fam), true)) return -1;
+  }
+  r->report[fam] = enable != 0;
+  return 0;
+}
+static void *rate_report(const pn_rate *r, int fam) { return r->report[fam] ? r->d_report[fam] : NULL; }
+static int rate_report_copy(pn_rate *r, int fam, void *dst, hipMemcpyKind kind) {
+  if (!r || !dst) { pn_set_error("NULL argument"); return -1; }
+  if (!r->report[fam]) { pn_set_error("%s", kRateStage[fam].report_off); return -1; }
+  PN_ON_DEVICE(r->c);
+  PN_HIP_CHECK(hipMemcpyAsync(dst, r->d_report[fam], report_bytes(r, fam), kind, r->c->stream));
+  if (kind == hipMemcpyDeviceToHost) PN_HIP_CHECK(hipStreamSynchronize(r->c->stream));
+  return 0;
+}
+
+// A per-stream word setting (the caller has checked the list): dst[ids[i]] = v[i] in stream order through the context's id ring, so a frame
+// submitted before the call runs under the old values.  Nothing while the stage's device side does not exist and no value leaves
+// `neutral` ("nothing has ever left the defaults, and nothing does"); otherwise `buffers` allocates it on first use — here, never inside
+// a frame — `before` runs the stage's own launches that must precede the write, the words go through the ring in bounded pieces, each
+// followed by the launch that reads it, and the host's copy follows with `on`, its count of values that are not neutral.
+template <class T, class D, class H, class Before>
+static int rate_set_words(pn_rate *r, const int32_t *ids, int n, const T *v, T neutral, D *&dst, int (*buffers)(pn_rate *), std::vector<H> &host, int &on, Before before) {
+  static_assert(sizeof(T) == 4 && sizeof(D) == 4, "a word");
+  bool all_neutral = true;
+  for (int i = 0; i < n; i++) all_neutral &= v[i] == neutral;
+  if (n == 0 || (!dst && all_neutral)) return 0;
+  PN_ON_DEVICE(r->c);
+  if ((buffers && buffers(r)) || before()) return -1;
+  for (int at = 0; at < n; at += RATE_PIECE) {
+    const int m = n - at < RATE_PIECE ? n - at : RATE_PIECE;
+    const int *d = stage_ids(r->c, ids + at, m, v + at, m);
+    if (!d) return -1;
+    pn_launch_rate_set_factors(r->c->stream, d, d + ((m + 3) & ~3), m, reinterpret_cast<int *>(dst));
+  }
+  PN_HIP_CHECK(hipGetLastError());
+  for (int i = 0; i < n; i++) { on += (v[i] != neutral) - (host[ids[i]] != (H)neutral); host[ids[i]] = (H)v[i]; }
+  return 0;
+}
+template <class T, class D, class H>
+static int rate_set_words(pn_rate *r, const int32_t *ids, int n, const T *v, T neutral, D *&dst, int (*buffers)(pn_rate *), std::vector<H> &host, int &on) {
+  return rate_set_words(r, ids, n, v, neutral, dst, buffers, host, on, [] { return 0; });
+}
+static std::vector<float> plus_zero(const float *v, int n) {   // (-0.0f is 0)
+  std::vector<float> o(v, v + n);
+  for (float &x : o) if (x == 0.0f) x = 0.0f;
+  return o;
+}
+// a whole table of settings to the caller
+template <class H, class O>
+static int rate_get(const pn_rate *r, std::vector<H> pn_rate::*host, O *out) {
+  if (!r || !out) { pn_set_error("NULL argument"); return -1; }
+  for (int s = 0; s < r->c->B; s++) out[s] = (r->*host)[s];
+  return 0;
+}
+
+// a stage's parameters to the caller
+template <class T, size_t N>
+static int rate_get_params(const pn_rate *r, T (pn_rate::*params)[N], T *out) {
+  if (!r || !out) { pn_set_error("NULL argument"); return -1; }
+  memcpy(out, r->*params, sizeof(T) * N);
+  return 0;
+}
+
 // ---- lifecycle ---------------------------------------------------------------------------------------------------------------
 extern "C" void pn_rate_destroy(pn_rate *r) {
   if (!r) return;
@@ -218,110 +337,67 @@ extern "C" void pn_rate_destroy(pn_rate *r) {
   delete r;
 }
 
-extern "C" pn_rate *pn_rate_create(pn_ctx *c, int rate_hz) {
-  if (!c) { pn_set_error("NULL argument"); return NULL; }
-  const int f = pn_rate_factor(rate_hz);
-  if (!f) { pn_set_error("rate %d Hz: a converter takes " PN_RATE_TEXT, rate_hz); return NULL; }
+// f: the factor of rate_hz, or 0 for a converter with a rate per stream (rates_hz, NULL: 48000 everywhere): the tap tables of all four
+// filters, tails of the largest size for every stream (a rate change never reallocates), rows of 480 samples, zeroed so that the part
+// of a row no kernel writes is never stale memory.  The caller has checked the rates.
+static pn_rate *rate_create(pn_ctx *c, int rate_hz, int f, const int32_t *rates_hz) {
   DeviceGuard _dg(c->device);
   if (!_dg.ok) { pn_set_error("hipSetDevice(%d) failed", c->device); return NULL; }
-  pn_rate *r = new pn_rate();
-  r->c = c; r->rate = rate_hz; r->f = f; r->n = pn_rate_factor_frame(f); r->td = pn_rate_down_tail(f); r->bytes = 0;
-  r->mixed = false; r->factors = NULL; r->h_rows = NULL; r->laws.assign((size_t)c->B, PN_G711_ULAW); r->confs.assign((size_t)c->B, PN_CONF_NONE);
-  r->gains.assign((size_t)c->B, 1.0f); r->caps.assign((size_t)c->B, 0);
-  r->agc_targets.assign((size_t)c->B, 0.0f); pn_agc_default_params_host(r->agc_params);
-  r->lim_ceilings.assign((size_t)c->B, 0.0f); pn_lim_default_params_host(r->lim_params);
-  r->dtmf_sw.assign((size_t)c->B, 0); pn_dtmf_default_params_host(r->dtmf_params);
-  r->clamp_sw.assign((size_t)c->B, 0); pn_dtmf_clamp_default_params_host(r->clamp_params);
-  const size_t B = (size_t)c->B, nt = 2 * (size_t)PN_RATE_TAPS * pn_rate_factor_L(f) + 1;
-  float h[2][PN_RATE_MAX_TAPS];
-  auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
-  if (pn_rate_design(f, 0, h[0], PN_RATE_MAX_TAPS) < 0 || pn_rate_design(f, 1, h[1], PN_RATE_MAX_TAPS) < 0) goto fail;
-  if (alloc((void **)&r->taps_up, nt * 4, false) || alloc((void **)&r->taps_down, nt * 4, false) ||
-      alloc((void **)&r->tail_up, B * PN_RATE_UP_TAIL * 4, true) || alloc((void **)&r->tail_down, B * r->td * 4, true) ||
-      alloc((void **)&r->x48, B * PN_FRAME * 4, true) || alloc((void **)&r->y48, B * PN_FRAME * 4, true) ||
-      alloc(&r->io_in, B * r->n * 4, false) || alloc(&r->io_out, B * r->n * 4, false) || alloc((void **)&r->io_gr, B * 68 * 4, false) ||
-      alloc((void **)&r->d_laws, B * sizeof(int), true)) goto fail;
-  // (synchronous copies: h is on this stack)
-  if (hipMemcpyAsync(r->taps_up, h[0], nt * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-      hipMemcpyAsync(r->taps_down, h[1], nt * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-      hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipGetLastError(); pn_set_error("rate converter init failed"); goto fail; }
-  return r;
-fail:
-  pn_rate_destroy(r);
-  return NULL;
-}
-
-// A converter with a rate per stream: the tap tables of all four filters, tails of the largest size for every stream (a rate
-// change never reallocates), rows of 480 samples.
-extern "C" pn_rate *pn_rate_create_mixed(pn_ctx *c, const int32_t *rates_hz) {
-  if (!c) { pn_set_error("NULL argument"); return NULL; }
-  if (rates_hz && pn_rate_mixed_rates_list_check(rates_hz, c->B)) return NULL;
-  DeviceGuard _dg(c->device);
-  if (!_dg.ok) { pn_set_error("hipSetDevice(%d) failed", c->device); return NULL; }
-  pn_rate *r = new pn_rate();
-  r->c = c; r->rate = 0; r->f = 0; r->n = PN_RATE_MIXED_ROW; r->td = pn_rate_down_tail(PN_RATE_MAX_L); r->bytes = 0;
-  r->mixed = true; r->factors = NULL; r->h_rows = NULL; r->laws.assign((size_t)c->B, PN_G711_ULAW); r->confs.assign((size_t)c->B, PN_CONF_NONE);
-  r->gains.assign((size_t)c->B, 1.0f); r->caps.assign((size_t)c->B, 0);
-  r->agc_targets.assign((size_t)c->B, 0.0f); pn_agc_default_params_host(r->agc_params);
-  r->lim_ceilings.assign((size_t)c->B, 0.0f); pn_lim_default_params_host(r->lim_params);
-  r->dtmf_sw.assign((size_t)c->B, 0); pn_dtmf_default_params_host(r->dtmf_params);
-  r->clamp_sw.assign((size_t)c->B, 0); pn_dtmf_clamp_default_params_host(r->clamp_params);
+  const bool mixed = f == 0;
   const size_t B = (size_t)c->B;
-  if (rates_hz) r->rates.assign(rates_hz, rates_hz + B); else r->rates.assign(B, 48000);
+  pn_rate *r = new pn_rate();
+  r->c = c; r->rate = rate_hz; r->f = f; r->mixed = mixed; r->bytes = 0; r->factors = NULL; r->h_rows = NULL;
+  r->n = mixed ? PN_RATE_MIXED_ROW : pn_rate_factor_frame(f); r->td = pn_rate_down_tail(mixed ? PN_RATE_MAX_L : f);
+  if (rates_hz) r->rates.assign(rates_hz, rates_hz + B); else r->rates.assign(B, mixed ? 48000 : rate_hz);
+  r->laws.assign(B, PN_G711_ULAW); r->confs.assign(B, PN_CONF_NONE);
+  r->gains.assign(B, 1.0f); r->caps.assign(B, 0);
+  r->agc_targets.assign(B, 0.0f); pn_agc_default_params_host(r->agc_params);
+  r->lim_ceilings.assign(B, 0.0f); pn_lim_default_params_host(r->lim_params);
+  r->dtmf_sw.assign(B, 0); pn_dtmf_default_params_host(r->dtmf_params);
+  r->clamp_sw.assign(B, 0); pn_dtmf_clamp_default_params_host(r->clamp_params);
   static const int kF[4] = {6, 3, 2, PN_RATE_F_3_2};   // (the order of pn_rate.hip rt_taps_offset; the h of 32000 is the table of 3 and is not staged twice)
   std::vector<float> h[2];
-  std::vector<int> f(B);
-  for (size_t s = 0; s < B; s++) f[s] = pn_rate_mixed_factor(r->rates[s]);
-  auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
+  std::vector<int> fs(B);
+  for (size_t s = 0; s < B; s++) fs[s] = pn_rate_mixed_factor(r->rates[s]);
   for (int down = 0; down < 2; down++)
-    for (int f : kF) {
-      if (!down && f == PN_RATE_F_3_2) continue;
+    for (int g : kF) {
+      if (mixed ? !down && g == PN_RATE_F_3_2 : g != f) continue;
       float t[PN_RATE_MAX_TAPS];
-      const int nt = pn_rate_design(f, down, t, PN_RATE_MAX_TAPS);
+      const int nt = pn_rate_design(g, down, t, PN_RATE_MAX_TAPS);
       if (nt < 0) goto fail;
       h[down].insert(h[down].end(), t, t + nt);
     }
-  if (alloc((void **)&r->taps_up, h[0].size() * 4, false) || alloc((void **)&r->taps_down, h[1].size() * 4, false) ||
-      alloc((void **)&r->tail_up, B * PN_RATE_UP_TAIL * 4, true) || alloc((void **)&r->tail_down, B * r->td * 4, true) ||
-      alloc((void **)&r->x48, B * PN_FRAME * 4, true) || alloc((void **)&r->y48, B * PN_FRAME * 4, true) ||
-      alloc(&r->io_in, B * r->n * 4, true) || alloc(&r->io_out, B * r->n * 4, true) || alloc((void **)&r->io_gr, B * 68 * 4, false) ||
-      alloc((void **)&r->factors, B * sizeof(int), false) || alloc((void **)&r->d_laws, B * sizeof(int), true)) goto fail;
-  if (hipHostMalloc(&r->h_rows, B * r->n * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); r->h_rows = NULL; pn_set_error("rate converter: no pinned memory for %zu bytes", B * r->n * 4); goto fail; }
+  if (rate_alloc(r, r->taps_up, h[0].size() * 4, false) || rate_alloc(r, r->taps_down, h[1].size() * 4, false) || state_alloc(r, PN_RST_CORE, r->st) ||
+      rate_alloc(r, r->x48, B * PN_FRAME * 4, true) || rate_alloc(r, r->y48, B * PN_FRAME * 4, true) ||
+      rate_alloc(r, r->io_in, B * r->n * 4, mixed) || rate_alloc(r, r->io_out, B * r->n * 4, mixed) || rate_alloc(r, r->io_gr, B * 68 * 4, false) ||
+      rate_alloc(r, r->d_laws, B * sizeof(int), true) || (mixed && rate_alloc(r, r->factors, B * sizeof(int), false))) goto fail;
+  if (mixed && hipHostMalloc(&r->h_rows, B * r->n * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); r->h_rows = NULL; pn_set_error("rate converter: no pinned memory for %zu bytes", B * r->n * 4); goto fail; }
   // (synchronous copies: the sources are locals)
   if (hipMemcpyAsync(r->taps_up, h[0].data(), h[0].size() * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
       hipMemcpyAsync(r->taps_down, h[1].data(), h[1].size() * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-      hipMemcpyAsync(r->factors, f.data(), B * sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      (mixed && hipMemcpyAsync(r->factors, fs.data(), B * sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
       hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipGetLastError(); pn_set_error("rate converter init failed"); goto fail; }
   return r;
 fail:
   pn_rate_destroy(r);
   return NULL;
 }
+extern "C" pn_rate *pn_rate_create(pn_ctx *c, int rate_hz) {
+  if (!c) { pn_set_error("NULL argument"); return NULL; }
+  const int f = rate_factor_or_error(rate_hz);
+  return f ? rate_create(c, rate_hz, f, NULL) : NULL;
+}
+extern "C" pn_rate *pn_rate_create_mixed(pn_ctx *c, const int32_t *rates_hz) {
+  if (!c) { pn_set_error("NULL argument"); return NULL; }
+  if (rates_hz && pn_rate_mixed_rates_list_check(rates_hz, c->B)) return NULL;
+  return rate_create(c, 0, 0, rates_hz);
+}
 extern "C" int pn_rate_is_mixed(const pn_rate *r) { if (!r) { pn_set_error("NULL argument"); return -1; } return r->mixed ? 1 : 0; }
 extern "C" int pn_rate_row_samples(const pn_rate *r) { if (!r) { pn_set_error("NULL argument"); return -1; } return r->n; }
-extern "C" int pn_rate_get_stream_rates(const pn_rate *r, int32_t *h_rates) {
-  if (!r || !h_rates) { pn_set_error("NULL argument"); return -1; }
-  for (int s = 0; s < r->c->B; s++) h_rates[s] = r->mixed ? r->rates[s] : r->rate;
-  return 0;
-}
-// the PLC state of the staged streams d[0..n) goes to zero: an empty history, no lag, no run (nothing while PLC was never enabled)
-static void plc_zero_rows(pn_rate *r, const int *d, int n) {
-  pn_launch_zero_rows(r->c->stream, r->d_plc_hist, PN_PLC_HIST, PN_PLC_HIST, 1, 0, d, n);
-  pn_launch_zero_rows(r->c->stream, r->d_plc_q, PN_PLC_P_MAX, PN_PLC_P_MAX, 1, 0, d, n);
-  pn_launch_zero_rows(r->c->stream, r->d_plc_meta, 4, 4, 1, 0, d, n);
-}
-// the AGC state of the staged streams d[0..n) goes to zero: no level, a fresh gain (nothing while AGC was never enabled)
-static void agc_zero_rows(pn_rate *r, const int *d, int n) { pn_launch_zero_rows(r->c->stream, r->d_agc_state, 4, 4, 1, 0, d, n); }
-// the limiter state of the staged streams d[0..n) goes to zero: a fresh gain, no hold (nothing while no ceiling was ever set)
-static void lim_zero_rows(pn_rate *r, const int *d, int n) { pn_launch_zero_rows(r->c->stream, r->d_lim_state, 4, 4, 1, 0, d, n); }
-// the detector state of the staged streams d[0..n) goes to zero: no half sums, no digit (nothing while no stream was ever enabled)
-// ... and with it the removal state: no marks, no cut, no event (nothing while removal was never enabled)
-static void dtmf_zero_rows(pn_rate *r, const int *d, int n) {
-  pn_launch_zero_rows(r->c->stream, r->d_dtmf_state, PN_DTMF_STATE_WORDS, PN_DTMF_STATE_WORDS, 1, 0, d, n);
-  pn_launch_zero_rows(r->c->stream, r->d_clamp_state, PN_DTMF_CLAMP_STATE_WORDS, PN_DTMF_CLAMP_STATE_WORDS, 1, 0, d, n);
-}
+extern "C" int pn_rate_get_stream_rates(const pn_rate *r, int32_t *h_rates) { return rate_get(r, &pn_rate::rates, h_rates); }
+
 // A rate change of the listed streams, asynchronous and ordered like pn_rate_reset_streams: the ids and the new factors go
-// through the context's id ring in one copy, one launch writes the factors, two zero the tails.
+// through the context's id ring in one copy, one launch writes the factors, the state table's walk zeroes the streams' state.
 extern "C" int pn_rate_set_stream_rates(pn_rate *r, const int32_t *ids, int n, const int32_t *rates_hz) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   if (!r->mixed) { pn_set_error("a single-rate converter (%d Hz) keeps its rate: per-stream rates need pn_rate_create_mixed", r->rate); return -1; }
@@ -333,20 +409,14 @@ extern "C" int pn_rate_set_stream_rates(pn_rate *r, const int32_t *ids, int n, c
   const int *d = stage_ids(r->c, ids, n, f.data(), n);
   if (!d) return -1;
   pn_launch_rate_set_factors(r->c->stream, d, d + ((n + 3) & ~3), n, r->factors);
-  pn_launch_zero_rows(r->c->stream, r->tail_up, PN_RATE_UP_TAIL, PN_RATE_UP_TAIL, 1, 0, d, n);
-  pn_launch_zero_rows(r->c->stream, r->tail_down, r->td, r->td, 1, 0, d, n);
-  pn_launch_zero_rows(r->c->stream, r->d_level, 1, 1, 1, 0, d, n);       // (nothing while no level exists)
-  plc_zero_rows(r, d, n);
-  agc_zero_rows(r, d, n);
-  lim_zero_rows(r, d, n);
-  dtmf_zero_rows(r, d, n);
+  state_clear_rows(r, PN_RE_RATE, d, n);
   PN_HIP_CHECK(hipGetLastError());
   for (int i = 0; i < n; i++) r->rates[ids[i]] = rates_hz[i];
   return 0;
 }
 
 // A law change of the listed streams (G.711 rows), asynchronous and ordered like a rate change: the ids and the new laws go through
-// the context's id ring in one copy, one launch writes the table.  No tail is touched: the law is a setting of the edges.
+// the context's id ring in one copy, one launch writes the table.  No state is touched: the law is a setting of the edges.
 extern "C" int pn_rate_set_stream_laws(pn_rate *r, const int32_t *ids, int n, const int32_t *laws) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   if (pn_g711_laws_set_check(r->c->B, ids, n, laws)) return -1;
@@ -359,24 +429,19 @@ extern "C" int pn_rate_set_stream_laws(pn_rate *r, const int32_t *ids, int n, co
   for (int i = 0; i < n; i++) r->laws[ids[i]] = laws[i];
   return 0;
 }
-extern "C" int pn_rate_get_stream_laws(const pn_rate *r, int32_t *h_laws) {
-  if (!r || !h_laws) { pn_set_error("NULL argument"); return -1; }
-  for (int s = 0; s < r->c->B; s++) h_laws[s] = r->laws[s];
-  return 0;
-}
+extern "C" int pn_rate_get_stream_laws(const pn_rate *r, int32_t *h_laws) { return rate_get(r, &pn_rate::laws, h_laws); }
 
 // A conference change of the listed streams, ordered like a law change.  Everything is decided on the host first (pn_conf.h
 // pn_conf_change: the table after the change, the conferences it touches and their member rows); then the ids with their new
 // conferences and the touched rows go through the context's id ring, in bounded pieces, each followed by the launch that reads it.
-// No tail is touched.  The device side is allocated by the first call that needs it — here, never inside a frame.
+// Of the state only a listed stream's level starts again.  The device side is allocated by the first call that needs it — here, never inside a frame.
 static int conf_buffers(pn_rate *r) {                // (the caller is on the context's device)
   if (r->d_conf) return 0;
   pn_ctx *c = r->c;
   const size_t B = (size_t)c->B;
   float *o48 = NULL; int *conf = NULL, *members = NULL; uint32_t *stamp = NULL;
-  auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
-  if (alloc((void **)&o48, B * PN_FRAME * 4, true) || alloc((void **)&conf, B * sizeof(int), false) ||
-      alloc((void **)&members, B * PN_CONF_MAX_MEMBERS * sizeof(int), false) || alloc((void **)&stamp, B * sizeof(uint32_t), true)) return -1;
+  if (rate_alloc(r, o48, B * PN_FRAME * 4, true) || rate_alloc(r, conf, B * sizeof(int), false) ||
+      rate_alloc(r, members, B * PN_CONF_MAX_MEMBERS * sizeof(int), false) || rate_alloc(r, stamp, B * sizeof(uint32_t), true)) return -1;
   PN_HIP_CHECK(hipMemsetAsync(conf, 0xFF, B * sizeof(int), c->stream));                               // PN_CONF_NONE
   PN_HIP_CHECK(hipMemsetAsync(members, 0xFF, B * PN_CONF_MAX_MEMBERS * sizeof(int), c->stream));     // -1: no member
   r->o48 = o48; r->d_members = members; r->d_stamp = stamp; r->tick = 0; r->d_conf = conf;
@@ -389,12 +454,12 @@ extern "C" int pn_rate_set_stream_confs(pn_rate *r, const int32_t *ids, int n, c
   if (n == 0 || (!r->d_conf && ch.in_conf == 0)) return 0;          // (nobody has ever been in a conference, and nobody is now)
   PN_ON_DEVICE(r->c);
   if (conf_buffers(r)) return -1;
-  for (int at = 0; at < n; at += 16384) {
-    const int m = n - at < 16384 ? n - at : 16384;
+  for (int at = 0; at < n; at += RATE_PIECE) {
+    const int m = n - at < RATE_PIECE ? n - at : RATE_PIECE;
     const int *d = stage_ids(r->c, ids + at, m, confs + at, m);
     if (!d) return -1;
     pn_launch_rate_set_factors(r->c->stream, d, d + ((m + 3) & ~3), m, r->d_conf);
-    pn_launch_zero_rows(r->c->stream, r->d_level, 1, 1, 1, 0, d, m);     // a listed stream's level starts again
+    state_clear_rows(r, PN_RE_CONF, d, m);
   }
   const int k = (int)ch.touched.size();
   for (int at = 0; at < k; at += 512) {
@@ -407,74 +472,33 @@ extern "C" int pn_rate_set_stream_confs(pn_rate *r, const int32_t *ids, int n, c
   r->confs.swap(ch.next); r->in_conf = ch.in_conf;
   return 0;
 }
-extern "C" int pn_rate_get_stream_confs(const pn_rate *r, int32_t *h_confs) {
-  if (!r || !h_confs) { pn_set_error("NULL argument"); return -1; }
-  for (int s = 0; s < r->c->B; s++) h_confs[s] = r->confs[s];
-  return 0;
-}
+extern "C" int pn_rate_get_stream_confs(const pn_rate *r, int32_t *h_confs) { return rate_get(r, &pn_rate::confs, h_confs); }
 
 // ---- loudest-N talkers, send gains, hold, mix report (include/percepnet_hip.h; rules pn_mix_rules.h) ---------------------------
 // Settings, written in stream order through the context's id ring like the conference table, so a frame submitted before a call
 // runs under the old values.  "plain": every setting at its default — rate_mix then launches what it always launched.
-static bool mix_plain(const pn_rate *r) { return r->gains_off == 0 && r->caps_on == 0 && r->hold == 0.0f && !r->mix_report; }
+static bool mix_plain(const pn_rate *r) { return r->gains_off == 0 && r->caps_on == 0 && r->hold == 0.0f && !r->report[RF_MIX]; }
 static int mix_buffers(pn_rate *r) {                 // (the caller is on the context's device)
   if (conf_buffers(r)) return -1;
-  if (r->d_level) return 0;
-  pn_ctx *c = r->c;
-  const size_t B = (size_t)c->B;
-  float *gains = NULL, *level = NULL; int *caps = NULL;
-  auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
-  if (alloc((void **)&gains, B * 4, false) || alloc((void **)&caps, B * sizeof(int), true) || alloc((void **)&level, B * 4, true)) return -1;
-  PN_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)gains, 0x3f800000, B, c->stream));                  // 1.0f
-  r->d_gains = gains; r->d_caps = caps; r->d_level = level;
-  return 0;
-}
-// dst[ids[i]] = words[i] through the id ring, in bounded pieces, each followed by the launch that reads it
-static int mix_set_words(pn_rate *r, const int32_t *ids, int n, const void *words, int *dst) {
-  for (int at = 0; at < n; at += 16384) {
-    const int m = n - at < 16384 ? n - at : 16384;
-    const int *d = stage_ids(r->c, ids + at, m, static_cast<const int32_t *>(words) + at, m);
-    if (!d) return -1;
-    pn_launch_rate_set_factors(r->c->stream, d, d + ((m + 3) & ~3), m, dst);
-  }
-  PN_HIP_CHECK(hipGetLastError());
+  if (r->d_gains) return 0;
+  float *gains = NULL; int *caps = NULL; void *st[PN_RS_COUNT] = {};
+  if (rate_alloc(r, gains, (size_t)r->c->B * 4, false) || rate_alloc(r, caps, (size_t)r->c->B * sizeof(int), true) || state_alloc(r, PN_RST_MIX, st)) return -1;
+  PN_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)gains, 0x3f800000, (size_t)r->c->B, r->c->stream));                  // 1.0f
+  r->d_caps = caps; state_commit(r, PN_RST_MIX, st); r->d_gains = gains;
   return 0;
 }
 extern "C" int pn_rate_set_stream_mix_gains(pn_rate *r, const int32_t *ids, int n, const float *gains) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   if (pn_mix_gains_set_check(r->c->B, ids, n, gains)) return -1;
-  if (n == 0) return 0;
-  std::vector<float> g(gains, gains + n);
-  bool all_one = true;
-  for (float &v : g) { if (v == 0.0f) v = 0.0f; all_one &= v == 1.0f; }     // (-0.0f is 0)
-  if (!r->d_level && all_one) return 0;                                        // (nothing has ever left the defaults, and nothing does)
-  PN_ON_DEVICE(r->c);
-  if (mix_buffers(r) || mix_set_words(r, ids, n, g.data(), reinterpret_cast<int *>(r->d_gains))) return -1;
-  for (int i = 0; i < n; i++) { r->gains_off += (g[i] != 1.0f) - (r->gains[ids[i]] != 1.0f); r->gains[ids[i]] = g[i]; }
-  return 0;
+  return rate_set_words(r, ids, n, plus_zero(gains, n).data(), 1.0f, r->d_gains, mix_buffers, r->gains, r->gains_off);
 }
-extern "C" int pn_rate_get_stream_mix_gains(const pn_rate *r, float *h_gains) {
-  if (!r || !h_gains) { pn_set_error("NULL argument"); return -1; }
-  for (int s = 0; s < r->c->B; s++) h_gains[s] = r->gains[s];
-  return 0;
-}
+extern "C" int pn_rate_get_stream_mix_gains(const pn_rate *r, float *h_gains) { return rate_get(r, &pn_rate::gains, h_gains); }
 extern "C" int pn_rate_set_conf_speakers(pn_rate *r, const int32_t *confs, int n, const int32_t *max_speakers) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   if (pn_mix_speakers_set_check(r->c->B, confs, n, max_speakers)) return -1;
-  if (n == 0) return 0;
-  bool all_zero = true;
-  for (int i = 0; i < n; i++) all_zero &= max_speakers[i] == 0;
-  if (!r->d_level && all_zero) return 0;
-  PN_ON_DEVICE(r->c);
-  if (mix_buffers(r) || mix_set_words(r, confs, n, max_speakers, r->d_caps)) return -1;
-  for (int i = 0; i < n; i++) { r->caps_on += (max_speakers[i] != 0) - (r->caps[confs[i]] != 0); r->caps[confs[i]] = max_speakers[i]; }
-  return 0;
+  return rate_set_words(r, confs, n, max_speakers, (int32_t)0, r->d_caps, mix_buffers, r->caps, r->caps_on);
 }
-extern "C" int pn_rate_get_conf_speakers(const pn_rate *r, int32_t *h_n) {
-  if (!r || !h_n) { pn_set_error("NULL argument"); return -1; }
-  for (int s = 0; s < r->c->B; s++) h_n[s] = r->caps[s];
-  return 0;
-}
+extern "C" int pn_rate_get_conf_speakers(const pn_rate *r, int32_t *h_n) { return rate_get(r, &pn_rate::caps, h_n); }
 // the hold factor travels as an argument of every launch, so it is ordered like one; the levels go to zero in stream order
 extern "C" int pn_rate_set_mix_hold(pn_rate *r, float d) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
@@ -482,30 +506,14 @@ extern "C" int pn_rate_set_mix_hold(pn_rate *r, float d) {
   if (d == 0.0f) d = 0.0f;
   PN_ON_DEVICE(r->c);
   if (d != 0.0f && mix_buffers(r)) return -1;
-  if (r->d_level) PN_HIP_CHECK(hipMemsetAsync(r->d_level, 0, (size_t)r->c->B * 4, r->c->stream));
+  if (state_clear_all(r, PN_RE_HOLD)) return -1;
   r->hold = d;
   return 0;
 }
 extern "C" float pn_rate_get_mix_hold(const pn_rate *r) { if (!r) { pn_set_error("NULL argument"); return NAN; } return r->hold; }
-extern "C" int pn_rate_set_mix_report(pn_rate *r, int enable) {
-  if (!r) { pn_set_error("NULL argument"); return -1; }
-  if (enable && !r->d_mix_report) {
-    PN_ON_DEVICE(r->c);
-    if (mix_buffers(r) || dev_alloc_into(r->allocs, r->bytes, r->c->stream, &r->d_mix_report, (size_t)r->c->B * PN_MIX_REPORT_WORDS * 4, true)) return -1;
-  }
-  r->mix_report = enable != 0;
-  return 0;
-}
-static int mix_report_copy(pn_rate *r, void *dst, hipMemcpyKind kind) {
-  if (!r || !dst) { pn_set_error("NULL argument"); return -1; }
-  if (!r->mix_report) { pn_set_error("the mix report is off (pn_rate_set_mix_report)"); return -1; }
-  PN_ON_DEVICE(r->c);
-  PN_HIP_CHECK(hipMemcpyAsync(dst, r->d_mix_report, (size_t)r->c->B * PN_MIX_REPORT_WORDS * 4, kind, r->c->stream));
-  if (kind == hipMemcpyDeviceToHost) PN_HIP_CHECK(hipStreamSynchronize(r->c->stream));
-  return 0;
-}
-extern "C" int pn_rate_read_mix_report(pn_rate *r, void *h_report) { return mix_report_copy(r, h_report, hipMemcpyDeviceToHost); }
-extern "C" int pn_rate_read_mix_report_dev(pn_rate *r, void *d_report) { return mix_report_copy(r, d_report, hipMemcpyDeviceToDevice); }
+extern "C" int pn_rate_set_mix_report(pn_rate *r, int enable) { return rate_set_report(r, RF_MIX, enable); }
+extern "C" int pn_rate_read_mix_report(pn_rate *r, void *h_report) { return rate_report_copy(r, RF_MIX, h_report, hipMemcpyDeviceToHost); }
+extern "C" int pn_rate_read_mix_report_dev(pn_rate *r, void *d_report) { return rate_report_copy(r, RF_MIX, d_report, hipMemcpyDeviceToDevice); }
 
 // ---- packet-loss concealment (include/percepnet_hip.h; the rule pn_plc_rules.h; the kernel pn_rate_plc.hip) ----------------------
 static int plc_drop_marks(pn_rate *r) {              // (the caller is on the context's device)
@@ -520,15 +528,13 @@ static int plc_drop_marks(pn_rate *r) {              // (the caller is on the co
 extern "C" int pn_rate_set_plc(pn_rate *r, int enable) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   PN_ON_DEVICE(r->c);
-  if (enable && !r->d_plc_meta) {
+  if (enable && !r->d_plc_lost) {
     pn_ctx *c = r->c;
     const size_t B = (size_t)c->B;
-    float *hist = NULL, *q = NULL; void *meta = NULL; uint32_t *lost = NULL;
-    auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
-    if (alloc((void **)&hist, B * PN_PLC_HIST * 4, true) || alloc((void **)&q, B * PN_PLC_P_MAX * 4, true) || alloc(&meta, B * 16, true) ||
-        alloc((void **)&lost, B * sizeof(uint32_t), true)) return -1;
+    void *st[PN_RS_COUNT] = {}; uint32_t *lost = NULL;
+    if (state_alloc(r, PN_RST_PLC, st) || rate_alloc(r, lost, B * sizeof(uint32_t), true)) return -1;
     r->lost_mark.assign(B, 0); r->lost_ids.reserve(B);
-    r->d_plc_hist = hist; r->d_plc_q = q; r->d_plc_lost = lost; r->plc_tick = 1; r->d_plc_meta = meta;
+    state_commit(r, PN_RST_PLC, st); r->plc_tick = 1; r->d_plc_lost = lost;
     // room in the id ring for the longest list a frame stages, "every stream but the lost ones", so that no frame grows the ring:
     // the identity list goes through it once, read by nobody
     r->up_ids.resize(B);
@@ -537,9 +543,7 @@ extern "C" int pn_rate_set_plc(pn_rate *r, int enable) {
     r->up_ids.clear();
   } else if (enable && !r->plc) {
     // on again after a pause: the frames in between are missing from the histories, so every stream starts with an empty one
-    PN_HIP_CHECK(hipMemsetAsync(r->d_plc_hist, 0, (size_t)r->c->B * PN_PLC_HIST * 4, r->c->stream));
-    PN_HIP_CHECK(hipMemsetAsync(r->d_plc_q, 0, (size_t)r->c->B * PN_PLC_P_MAX * 4, r->c->stream));
-    PN_HIP_CHECK(hipMemsetAsync(r->d_plc_meta, 0, (size_t)r->c->B * 16, r->c->stream));
+    if (state_clear_all(r, PN_RE_AGAIN, PN_RST_PLC)) return -1;
   }
   if (!enable && r->plc && plc_drop_marks(r)) return -1;
   r->plc = enable != 0;
@@ -551,8 +555,8 @@ extern "C" int pn_rate_set_lost(pn_rate *r, const int32_t *ids, int n) {
   if (pn_ids_check(r->c->B, ids, n, true)) return -1;
   if (n == 0) return 0;
   PN_ON_DEVICE(r->c);
-  for (int at = 0; at < n; at += 16384) {
-    const int m = n - at < 16384 ? n - at : 16384;
+  for (int at = 0; at < n; at += RATE_PIECE) {
+    const int m = n - at < RATE_PIECE ? n - at : RATE_PIECE;
     const int *d = stage_ids(r->c, ids + at, m);
     if (!d) return -1;
     pn_launch_rate_conf_stamp(r->c->stream, d, m, r->d_plc_lost, r->plc_tick);
@@ -563,40 +567,21 @@ extern "C" int pn_rate_set_lost(pn_rate *r, const int32_t *ids, int n) {
   }
   return 0;
 }
-extern "C" int pn_rate_set_plc_report(pn_rate *r, int enable) {
-  if (!r) { pn_set_error("NULL argument"); return -1; }
-  if (enable && !r->d_plc_report) {
-    PN_ON_DEVICE(r->c);
-    if (dev_alloc_into(r->allocs, r->bytes, r->c->stream, &r->d_plc_report, (size_t)r->c->B * PN_PLC_REPORT_WORDS * 4, true)) return -1;
-  }
-  r->plc_report = enable != 0;
-  return 0;
-}
-static int plc_report_copy(pn_rate *r, void *dst, hipMemcpyKind kind) {
-  if (!r || !dst) { pn_set_error("NULL argument"); return -1; }
-  if (!r->plc_report) { pn_set_error("the PLC report is off (pn_rate_set_plc_report)"); return -1; }
-  PN_ON_DEVICE(r->c);
-  PN_HIP_CHECK(hipMemcpyAsync(dst, r->d_plc_report, (size_t)r->c->B * PN_PLC_REPORT_WORDS * 4, kind, r->c->stream));
-  if (kind == hipMemcpyDeviceToHost) PN_HIP_CHECK(hipStreamSynchronize(r->c->stream));
-  return 0;
-}
-extern "C" int pn_rate_read_plc_report(pn_rate *r, void *h_report) { return plc_report_copy(r, h_report, hipMemcpyDeviceToHost); }
-extern "C" int pn_rate_read_plc_report_dev(pn_rate *r, void *d_report) { return plc_report_copy(r, d_report, hipMemcpyDeviceToDevice); }
+extern "C" int pn_rate_set_plc_report(pn_rate *r, int enable) { return rate_set_report(r, RF_PLC, enable); }
+extern "C" int pn_rate_read_plc_report(pn_rate *r, void *h_report) { return rate_report_copy(r, RF_PLC, h_report, hipMemcpyDeviceToHost); }
+extern "C" int pn_rate_read_plc_report_dev(pn_rate *r, void *d_report) { return rate_report_copy(r, RF_PLC, d_report, hipMemcpyDeviceToDevice); }
 
 // ---- automatic level control (include/percepnet_hip.h; the rule pn_agc_rules.h; the kernel pn_rate_agc.hip) -----------------------
 extern "C" int pn_rate_set_agc(pn_rate *r, int enable) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   PN_ON_DEVICE(r->c);
-  if (enable && !r->d_agc_state) {
-    pn_ctx *c = r->c;
-    const size_t B = (size_t)c->B;
-    float *targets = NULL; void *state = NULL;
-    auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
-    if (alloc((void **)&targets, B * 4, true) || alloc(&state, B * PN_AGC_STATE_BYTES, true)) return -1;
-    r->d_agc_targets = targets; r->d_agc_state = state;
+  if (enable && !r->d_agc_targets) {
+    float *targets = NULL; void *st[PN_RS_COUNT] = {};
+    if (rate_alloc(r, targets, (size_t)r->c->B * 4, true) || state_alloc(r, PN_RST_AGC, st)) return -1;
+    state_commit(r, PN_RST_AGC, st); r->d_agc_targets = targets;
   } else if (enable && !r->agc) {
     // on again after a pause: the frames in between are missing from the levels, so every stream starts fresh
-    PN_HIP_CHECK(hipMemsetAsync(r->d_agc_state, 0, (size_t)r->c->B * PN_AGC_STATE_BYTES, r->c->stream));
+    if (state_clear_all(r, PN_RE_AGAIN, PN_RST_AGC)) return -1;
   }
   r->agc = enable != 0;
   return 0;
@@ -608,77 +593,32 @@ extern "C" int pn_rate_set_agc_params(pn_rate *r, const float *params8) {
   memcpy(r->agc_params, params8, sizeof(r->agc_params));
   return 0;
 }
-extern "C" int pn_rate_get_agc_params(const pn_rate *r, float *params8) {
-  if (!r || !params8) { pn_set_error("NULL argument"); return -1; }
-  memcpy(params8, r->agc_params, sizeof(r->agc_params));
-  return 0;
-}
+extern "C" int pn_rate_get_agc_params(const pn_rate *r, float *params8) { return rate_get_params(r, &pn_rate::agc_params, params8); }
 extern "C" int pn_rate_set_stream_agc_targets(pn_rate *r, const int32_t *ids, int n, const float *targets) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   if (!r->agc) { pn_set_error("automatic level control is off (pn_rate_set_agc)"); return -1; }
   if (pn_agc_targets_set_check(r->c->B, ids, n, targets)) return -1;
-  if (n == 0) return 0;
-  std::vector<float> t(targets, targets + n);
-  for (float &v : t) if (v == 0.0f) v = 0.0f;                                   // (-0.0f is 0)
-  PN_ON_DEVICE(r->c);
-  if (mix_set_words(r, ids, n, t.data(), reinterpret_cast<int *>(r->d_agc_targets))) return -1;
-  for (int i = 0; i < n; i++) { r->agc_on += (t[i] != 0.0f) - (r->agc_targets[ids[i]] != 0.0f); r->agc_targets[ids[i]] = t[i]; }
-  return 0;
+  return rate_set_words(r, ids, n, plus_zero(targets, n).data(), 0.0f, r->d_agc_targets, NULL, r->agc_targets, r->agc_on);   // (on: the device side exists)
 }
-extern "C" int pn_rate_get_stream_agc_targets(const pn_rate *r, float *h_targets) {
-  if (!r || !h_targets) { pn_set_error("NULL argument"); return -1; }
-  for (int s = 0; s < r->c->B; s++) h_targets[s] = r->agc_targets[s];
-  return 0;
-}
-extern "C" int pn_rate_set_agc_report(pn_rate *r, int enable) {
-  if (!r) { pn_set_error("NULL argument"); return -1; }
-  if (enable && !r->d_agc_report) {
-    PN_ON_DEVICE(r->c);
-    if (dev_alloc_into(r->allocs, r->bytes, r->c->stream, &r->d_agc_report, (size_t)r->c->B * PN_AGC_REPORT_WORDS * 4, true)) return -1;
-  }
-  r->agc_report = enable != 0;
-  return 0;
-}
-static int agc_report_copy(pn_rate *r, void *dst, hipMemcpyKind kind) {
-  if (!r || !dst) { pn_set_error("NULL argument"); return -1; }
-  if (!r->agc_report) { pn_set_error("the AGC report is off (pn_rate_set_agc_report)"); return -1; }
-  PN_ON_DEVICE(r->c);
-  PN_HIP_CHECK(hipMemcpyAsync(dst, r->d_agc_report, (size_t)r->c->B * PN_AGC_REPORT_WORDS * 4, kind, r->c->stream));
-  if (kind == hipMemcpyDeviceToHost) PN_HIP_CHECK(hipStreamSynchronize(r->c->stream));
-  return 0;
-}
-extern "C" int pn_rate_read_agc_report(pn_rate *r, void *h_report) { return agc_report_copy(r, h_report, hipMemcpyDeviceToHost); }
-extern "C" int pn_rate_read_agc_report_dev(pn_rate *r, void *d_report) { return agc_report_copy(r, d_report, hipMemcpyDeviceToDevice); }
+extern "C" int pn_rate_get_stream_agc_targets(const pn_rate *r, float *h_targets) { return rate_get(r, &pn_rate::agc_targets, h_targets); }
+extern "C" int pn_rate_set_agc_report(pn_rate *r, int enable) { return rate_set_report(r, RF_AGC, enable); }
+extern "C" int pn_rate_read_agc_report(pn_rate *r, void *h_report) { return rate_report_copy(r, RF_AGC, h_report, hipMemcpyDeviceToHost); }
+extern "C" int pn_rate_read_agc_report_dev(pn_rate *r, void *d_report) { return rate_report_copy(r, RF_AGC, d_report, hipMemcpyDeviceToDevice); }
 
 // ---- the output limiter (include/percepnet_hip.h; the rule pn_lim_rules.h; the kernel pn_rate_lim.hip) ----------------------------
 static int lim_buffers(pn_rate *r) {                 // (the caller is on the context's device)
-  if (r->d_lim_state) return 0;
-  pn_ctx *c = r->c;
-  const size_t B = (size_t)c->B;
-  float *ceilings = NULL; void *state = NULL;
-  auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
-  if (alloc((void **)&ceilings, B * 4, true) || alloc(&state, B * PN_LIM_STATE_BYTES, true)) return -1;
-  r->d_lim_ceilings = ceilings; r->d_lim_state = state;
+  if (r->d_lim_ceilings) return 0;
+  float *ceilings = NULL; void *st[PN_RS_COUNT] = {};
+  if (rate_alloc(r, ceilings, (size_t)r->c->B * 4, true) || state_alloc(r, PN_RST_LIM, st)) return -1;
+  state_commit(r, PN_RST_LIM, st); r->d_lim_ceilings = ceilings;
   return 0;
 }
 extern "C" int pn_rate_set_stream_limiter(pn_rate *r, const int32_t *ids, int n, const float *ceilings) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   if (pn_lim_ceilings_set_check(r->c->B, ids, n, ceilings)) return -1;
-  if (n == 0) return 0;
-  std::vector<float> v(ceilings, ceilings + n);
-  bool all_zero = true;
-  for (float &x : v) { if (x == 0.0f) x = 0.0f; all_zero &= x == 0.0f; }       // (-0.0f is 0)
-  if (!r->d_lim_state && all_zero) return 0;                                     // (no ceiling has ever been set, and none is)
-  PN_ON_DEVICE(r->c);
-  if (lim_buffers(r) || mix_set_words(r, ids, n, v.data(), reinterpret_cast<int *>(r->d_lim_ceilings))) return -1;
-  for (int i = 0; i < n; i++) { r->lim_on += (v[i] != 0.0f) - (r->lim_ceilings[ids[i]] != 0.0f); r->lim_ceilings[ids[i]] = v[i]; }
-  return 0;
+  return rate_set_words(r, ids, n, plus_zero(ceilings, n).data(), 0.0f, r->d_lim_ceilings, lim_buffers, r->lim_ceilings, r->lim_on);
 }
-extern "C" int pn_rate_get_stream_limiter(const pn_rate *r, float *h_ceilings) {
-  if (!r || !h_ceilings) { pn_set_error("NULL argument"); return -1; }
-  for (int s = 0; s < r->c->B; s++) h_ceilings[s] = r->lim_ceilings[s];
-  return 0;
-}
+extern "C" int pn_rate_get_stream_limiter(const pn_rate *r, float *h_ceilings) { return rate_get(r, &pn_rate::lim_ceilings, h_ceilings); }
 // the parameters travel as an argument of every launch, so a change is ordered like one
 extern "C" int pn_rate_set_limiter_params(pn_rate *r, const float *params2) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
@@ -686,70 +626,45 @@ extern "C" int pn_rate_set_limiter_params(pn_rate *r, const float *params2) {
   memcpy(r->lim_params, params2, sizeof(r->lim_params));
   return 0;
 }
-extern "C" int pn_rate_get_limiter_params(const pn_rate *r, float *params2) {
-  if (!r || !params2) { pn_set_error("NULL argument"); return -1; }
-  memcpy(params2, r->lim_params, sizeof(r->lim_params));
-  return 0;
-}
-extern "C" int pn_rate_set_limiter_report(pn_rate *r, int enable) {
-  if (!r) { pn_set_error("NULL argument"); return -1; }
-  if (enable && !r->d_lim_report) {
-    PN_ON_DEVICE(r->c);
-    if (dev_alloc_into(r->allocs, r->bytes, r->c->stream, &r->d_lim_report, (size_t)r->c->B * PN_LIM_REPORT_WORDS * 4, true)) return -1;
-  }
-  r->lim_report = enable != 0;
-  return 0;
-}
-static int lim_report_copy(pn_rate *r, void *dst, hipMemcpyKind kind) {
-  if (!r || !dst) { pn_set_error("NULL argument"); return -1; }
-  if (!r->lim_report) { pn_set_error("the limiter report is off (pn_rate_set_limiter_report)"); return -1; }
-  PN_ON_DEVICE(r->c);
-  PN_HIP_CHECK(hipMemcpyAsync(dst, r->d_lim_report, (size_t)r->c->B * PN_LIM_REPORT_WORDS * 4, kind, r->c->stream));
-  if (kind == hipMemcpyDeviceToHost) PN_HIP_CHECK(hipStreamSynchronize(r->c->stream));
-  return 0;
-}
-extern "C" int pn_rate_read_limiter_report(pn_rate *r, void *h_report) { return lim_report_copy(r, h_report, hipMemcpyDeviceToHost); }
-extern "C" int pn_rate_read_limiter_report_dev(pn_rate *r, void *d_report) { return lim_report_copy(r, d_report, hipMemcpyDeviceToDevice); }
+extern "C" int pn_rate_get_limiter_params(const pn_rate *r, float *params2) { return rate_get_params(r, &pn_rate::lim_params, params2); }
+extern "C" int pn_rate_set_limiter_report(pn_rate *r, int enable) { return rate_set_report(r, RF_LIM, enable); }
+extern "C" int pn_rate_read_limiter_report(pn_rate *r, void *h_report) { return rate_report_copy(r, RF_LIM, h_report, hipMemcpyDeviceToHost); }
+extern "C" int pn_rate_read_limiter_report_dev(pn_rate *r, void *d_report) { return rate_report_copy(r, RF_LIM, d_report, hipMemcpyDeviceToDevice); }
 
-// ---- DTMF detection (include/percepnet_hip.h; the rule pn_dtmf_rules.h; the kernel pn_rate_dtmf.hip) ------------------------------
+// ---- DTMF detection and removal (include/percepnet_hip.h; the rules pn_dtmf_rules.h, pn_dtmf_clamp_rules.h; the kernels pn_rate_dtmf.hip, pn_rate_dtmf_clamp.hip)
 static int dtmf_buffers(pn_rate *r) {                // (the caller is on the context's device)
-  if (r->d_dtmf_state) return 0;
-  pn_ctx *c = r->c;
-  const size_t B = (size_t)c->B;
+  if (r->d_dtmf_on) return 0;
   const PnDtmfTables &T = pn_dtmf_tables_ref();
-  int *on = NULL; float *tab = NULL; void *state = NULL;
-  auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
-  if (alloc((void **)&on, B * 4, true) || alloc((void **)&tab, sizeof(T.ct) + sizeof(T.st), false) || alloc(&state, B * PN_DTMF_STATE_BYTES, true)) return -1;
+  int *on = NULL; float *tab = NULL; void *st[PN_RS_COUNT] = {};
+  if (rate_alloc(r, on, (size_t)r->c->B * 4, true) || rate_alloc(r, tab, sizeof(T.ct) + sizeof(T.st), false) || state_alloc(r, PN_RST_DTMF, st)) return -1;
   static_assert(offsetof(PnDtmfTables, st) == sizeof(T.ct), "ct and st are one block");
-  PN_HIP_CHECK(hipMemcpyAsync(tab, T.ct, sizeof(T.ct) + sizeof(T.st), hipMemcpyHostToDevice, c->stream));   // (from a static table: the source outlives the copy)
-  r->d_dtmf_on = on; r->d_dtmf_tab = tab; r->d_dtmf_state = state;
+  PN_HIP_CHECK(hipMemcpyAsync(tab, T.ct, sizeof(T.ct) + sizeof(T.st), hipMemcpyHostToDevice, r->c->stream));   // (from a static table: the source outlives the copy)
+  r->d_dtmf_tab = tab; state_commit(r, PN_RST_DTMF, st); r->d_dtmf_on = on;
   return 0;
+}
+// This stage's own rule: it reads the detector's report rows, so it allocates them — the user's buffer if there is one, otherwise one
+// of the same kind — and while clamp_on > 0 the detector writes them whatever report[RF_DTMF] says (rate_dtmf)
+static int clamp_buffers(pn_rate *r) {               // (the caller is on the context's device)
+  if (r->d_clamp_on) return 0;
+  int *on = NULL; void *st[PN_RS_COUNT] = {};
+  if (!r->d_report[RF_DTMF] && rate_alloc(r, r->d_report[RF_DTMF], report_bytes(r, RF_DTMF), true)) return -1;
+  if (rate_alloc(r, on, (size_t)r->c->B * 4, true) || state_alloc(r, PN_RST_CLAMP, st)) return -1;
+  state_commit(r, PN_RST_CLAMP, st); r->d_clamp_on = on;
+  return 0;
+}
+// switches as words, and the listed streams that come on from off
+static void switch_words(const std::vector<uint8_t> &sw, const int32_t *ids, int n, const uint8_t *on, std::vector<int32_t> &v, std::vector<int32_t> &fresh) {
+  v.resize(n);
+  for (int i = 0; i < n; i++) { v[i] = on[i] ? 1 : 0; if (on[i] && !sw[ids[i]]) fresh.push_back(ids[i]); }
 }
 extern "C" int pn_rate_set_stream_dtmf(pn_rate *r, const int32_t *ids, int n, const uint8_t *on) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   if (pn_dtmf_on_set_check(r->c->B, ids, n, on)) return -1;
-  if (n == 0) return 0;
-  std::vector<int32_t> v(n), fresh;
-  bool all_off = true;
-  for (int i = 0; i < n; i++) { v[i] = on[i] ? 1 : 0; all_off &= !on[i]; if (on[i] && !r->dtmf_sw[ids[i]]) fresh.push_back(ids[i]); }
-  if (!r->d_dtmf_state && all_off) return 0;                                     // (no stream has ever been enabled, and none is)
-  PN_ON_DEVICE(r->c);
-  if (dtmf_buffers(r)) return -1;
-  for (size_t at = 0; at < fresh.size(); at += 16384) {                            // a stream that was off starts from the fresh state
-    const int m = (int)(fresh.size() - at < 16384 ? fresh.size() - at : 16384);
-    const int *d = stage_ids(r->c, fresh.data() + at, m);
-    if (!d) return -1;
-    pn_launch_zero_rows(r->c->stream, r->d_dtmf_state, PN_DTMF_STATE_WORDS, PN_DTMF_STATE_WORDS, 1, 0, d, m);
-  }
-  if (mix_set_words(r, ids, n, v.data(), r->d_dtmf_on)) return -1;
-  for (int i = 0; i < n; i++) { r->dtmf_on += v[i] - (r->dtmf_sw[ids[i]] ? 1 : 0); r->dtmf_sw[ids[i]] = (uint8_t)v[i]; }
-  return 0;
+  std::vector<int32_t> v, fresh;
+  switch_words(r->dtmf_sw, ids, n, on, v, fresh);
+  return rate_set_words(r, ids, n, v.data(), (int32_t)0, r->d_dtmf_on, dtmf_buffers, r->dtmf_sw, r->dtmf_on, [&] { return state_switch_on(r, PN_RST_DTMF, fresh); });
 }
-extern "C" int pn_rate_get_stream_dtmf(const pn_rate *r, uint8_t *h_on) {
-  if (!r || !h_on) { pn_set_error("NULL argument"); return -1; }
-  for (int s = 0; s < r->c->B; s++) h_on[s] = r->dtmf_sw[s];
-  return 0;
-}
+extern "C" int pn_rate_get_stream_dtmf(const pn_rate *r, uint8_t *h_on) { return rate_get(r, &pn_rate::dtmf_sw, h_on); }
 // the parameters travel as an argument of every launch, so a change is ordered like one
 extern "C" int pn_rate_set_dtmf_params(pn_rate *r, const float *params7) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
@@ -759,80 +674,23 @@ extern "C" int pn_rate_set_dtmf_params(pn_rate *r, const float *params7) {
   memcpy(r->dtmf_params, params7, sizeof(r->dtmf_params));
   return 0;
 }
-extern "C" int pn_rate_get_dtmf_params(const pn_rate *r, float *params7) {
-  if (!r || !params7) { pn_set_error("NULL argument"); return -1; }
-  memcpy(params7, r->dtmf_params, sizeof(r->dtmf_params));
-  return 0;
-}
-extern "C" int pn_rate_set_dtmf_report(pn_rate *r, int enable) {
-  if (!r) { pn_set_error("NULL argument"); return -1; }
-  if (enable && !r->d_dtmf_report) {
-    PN_ON_DEVICE(r->c);
-    if (dev_alloc_into(r->allocs, r->bytes, r->c->stream, &r->d_dtmf_report, (size_t)r->c->B * PN_DTMF_REPORT_WORDS * 4, true)) return -1;
-  }
-  r->dtmf_report = enable != 0;
-  return 0;
-}
-static int dtmf_report_copy(pn_rate *r, void *dst, hipMemcpyKind kind) {
-  if (!r || !dst) { pn_set_error("NULL argument"); return -1; }
-  if (!r->dtmf_report) { pn_set_error("the DTMF report is off (pn_rate_set_dtmf_report)"); return -1; }
-  PN_ON_DEVICE(r->c);
-  PN_HIP_CHECK(hipMemcpyAsync(dst, r->d_dtmf_report, (size_t)r->c->B * PN_DTMF_REPORT_WORDS * 4, kind, r->c->stream));
-  if (kind == hipMemcpyDeviceToHost) PN_HIP_CHECK(hipStreamSynchronize(r->c->stream));
-  return 0;
-}
-// the detector state of every stream to the host, synchronising (tests and debugging); zeros while no stream was ever enabled
-extern "C" int pn_rate_debug_dtmf_state(pn_rate *r, void *h_state) {
-  if (!r || !h_state) { pn_set_error("NULL argument"); return -1; }
-  const size_t bytes = (size_t)r->c->B * PN_DTMF_STATE_BYTES;
-  if (!r->d_dtmf_state) { memset(h_state, 0, bytes); return 0; }
-  PN_ON_DEVICE(r->c);
-  PN_HIP_CHECK(hipMemcpyAsync(h_state, r->d_dtmf_state, bytes, hipMemcpyDeviceToHost, r->c->stream));
-  PN_HIP_CHECK(hipStreamSynchronize(r->c->stream));
-  return 0;
-}
-extern "C" int pn_rate_read_dtmf_report(pn_rate *r, void *h_report) { return dtmf_report_copy(r, h_report, hipMemcpyDeviceToHost); }
-extern "C" int pn_rate_read_dtmf_report_dev(pn_rate *r, void *d_report) { return dtmf_report_copy(r, d_report, hipMemcpyDeviceToDevice); }
+extern "C" int pn_rate_get_dtmf_params(const pn_rate *r, float *params7) { return rate_get_params(r, &pn_rate::dtmf_params, params7); }
+extern "C" int pn_rate_set_dtmf_report(pn_rate *r, int enable) { return rate_set_report(r, RF_DTMF, enable); }
+extern "C" int pn_rate_read_dtmf_report(pn_rate *r, void *h_report) { return rate_report_copy(r, RF_DTMF, h_report, hipMemcpyDeviceToHost); }
+extern "C" int pn_rate_read_dtmf_report_dev(pn_rate *r, void *d_report) { return rate_report_copy(r, RF_DTMF, d_report, hipMemcpyDeviceToDevice); }
+extern "C" int pn_rate_debug_dtmf_state(pn_rate *r, void *h_state) { return state_debug_copy(r, PN_RS_DTMF, h_state); }
 
-// ---- DTMF removal (include/percepnet_hip.h; the rule pn_dtmf_clamp_rules.h; the kernel pn_rate_dtmf_clamp.hip) ---------------------
-static int clamp_buffers(pn_rate *r) {               // (the caller is on the context's device)
-  if (r->d_clamp_state) return 0;
-  pn_ctx *c = r->c;
-  const size_t B = (size_t)c->B;
-  int *on = NULL; void *state = NULL;
-  auto alloc = [&](void **p, size_t bytes, bool zero) { return dev_alloc_into(r->allocs, r->bytes, c->stream, p, bytes, zero); };
-  // the detector's report rows, which this stage reads: the user's buffer if there is one, otherwise one of the same kind
-  if (!r->d_dtmf_report && alloc(&r->d_dtmf_report, B * PN_DTMF_REPORT_WORDS * 4, true)) return -1;
-  if (alloc((void **)&on, B * 4, true) || alloc(&state, B * PN_DTMF_CLAMP_STATE_BYTES, true)) return -1;
-  r->d_clamp_on = on; r->d_clamp_state = state;
-  return 0;
-}
 extern "C" int pn_rate_set_stream_dtmf_clamp(pn_rate *r, const int32_t *ids, int n, const uint8_t *on) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   if (pn_dtmf_clamp_on_set_check(r->c->B, ids, n, on)) return -1;
-  if (n == 0) return 0;
-  std::vector<int32_t> v(n), fresh;
-  bool all_off = true;
-  for (int i = 0; i < n; i++) { v[i] = on[i] ? 1 : 0; all_off &= !on[i]; if (on[i] && !r->clamp_sw[ids[i]]) fresh.push_back(ids[i]); }
-  if (!all_off && pn_dtmf_clamp_params_check_host(r->clamp_params, (int)r->dtmf_params[PN_DTMF_ON_FRAMES])) return -1;
-  if (!r->d_clamp_state && all_off) return 0;                                    // (no stream has ever been enabled, and none is)
-  PN_ON_DEVICE(r->c);
-  if (clamp_buffers(r)) return -1;
-  for (size_t at = 0; at < fresh.size(); at += 16384) {                            // a stream that was off starts from the fresh state
-    const int m = (int)(fresh.size() - at < 16384 ? fresh.size() - at : 16384);
-    const int *d = stage_ids(r->c, fresh.data() + at, m);
-    if (!d) return -1;
-    pn_launch_zero_rows(r->c->stream, r->d_clamp_state, PN_DTMF_CLAMP_STATE_WORDS, PN_DTMF_CLAMP_STATE_WORDS, 1, 0, d, m);
-  }
-  if (mix_set_words(r, ids, n, v.data(), r->d_clamp_on)) return -1;
-  for (int i = 0; i < n; i++) { r->clamp_on += v[i] - (r->clamp_sw[ids[i]] ? 1 : 0); r->clamp_sw[ids[i]] = (uint8_t)v[i]; }
-  return 0;
+  std::vector<int32_t> v, fresh;
+  switch_words(r->clamp_sw, ids, n, on, v, fresh);
+  bool any_on = false;
+  for (int32_t w : v) any_on |= w != 0;
+  if (any_on && pn_dtmf_clamp_params_check_host(r->clamp_params, (int)r->dtmf_params[PN_DTMF_ON_FRAMES])) return -1;
+  return rate_set_words(r, ids, n, v.data(), (int32_t)0, r->d_clamp_on, clamp_buffers, r->clamp_sw, r->clamp_on, [&] { return state_switch_on(r, PN_RST_CLAMP, fresh); });
 }
-extern "C" int pn_rate_get_stream_dtmf_clamp(const pn_rate *r, uint8_t *h_on) {
-  if (!r || !h_on) { pn_set_error("NULL argument"); return -1; }
-  for (int s = 0; s < r->c->B; s++) h_on[s] = r->clamp_sw[s];
-  return 0;
-}
+extern "C" int pn_rate_get_stream_dtmf_clamp(const pn_rate *r, uint8_t *h_on) { return rate_get(r, &pn_rate::clamp_sw, h_on); }
 // the parameters travel as an argument of every launch, so a change is ordered like one
 extern "C" int pn_rate_set_dtmf_clamp_params(pn_rate *r, const int32_t *params4) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
@@ -840,69 +698,28 @@ extern "C" int pn_rate_set_dtmf_clamp_params(pn_rate *r, const int32_t *params4)
   memcpy(r->clamp_params, params4, sizeof(r->clamp_params));
   return 0;
 }
-extern "C" int pn_rate_get_dtmf_clamp_params(const pn_rate *r, int32_t *params4) {
-  if (!r || !params4) { pn_set_error("NULL argument"); return -1; }
-  memcpy(params4, r->clamp_params, sizeof(r->clamp_params));
-  return 0;
-}
-extern "C" int pn_rate_set_dtmf_clamp_report(pn_rate *r, int enable) {
-  if (!r) { pn_set_error("NULL argument"); return -1; }
-  if (enable && !r->d_clamp_report) {
-    PN_ON_DEVICE(r->c);
-    if (dev_alloc_into(r->allocs, r->bytes, r->c->stream, &r->d_clamp_report, (size_t)r->c->B * PN_DTMF_CLAMP_REPORT_WORDS * 4, true)) return -1;
-  }
-  r->clamp_report = enable != 0;
-  return 0;
-}
-static int clamp_report_copy(pn_rate *r, void *dst, hipMemcpyKind kind) {
-  if (!r || !dst) { pn_set_error("NULL argument"); return -1; }
-  if (!r->clamp_report) { pn_set_error("the DTMF removal report is off (pn_rate_set_dtmf_clamp_report)"); return -1; }
-  PN_ON_DEVICE(r->c);
-  PN_HIP_CHECK(hipMemcpyAsync(dst, r->d_clamp_report, (size_t)r->c->B * PN_DTMF_CLAMP_REPORT_WORDS * 4, kind, r->c->stream));
-  if (kind == hipMemcpyDeviceToHost) PN_HIP_CHECK(hipStreamSynchronize(r->c->stream));
-  return 0;
-}
-extern "C" int pn_rate_read_dtmf_clamp_report(pn_rate *r, void *h_report) { return clamp_report_copy(r, h_report, hipMemcpyDeviceToHost); }
-extern "C" int pn_rate_read_dtmf_clamp_report_dev(pn_rate *r, void *d_report) { return clamp_report_copy(r, d_report, hipMemcpyDeviceToDevice); }
-// the removal state of every stream to the host, synchronising (tests and debugging); zeros while no stream was ever enabled
-extern "C" int pn_rate_debug_dtmf_clamp_state(pn_rate *r, void *h_state) {
-  if (!r || !h_state) { pn_set_error("NULL argument"); return -1; }
-  const size_t bytes = (size_t)r->c->B * PN_DTMF_CLAMP_STATE_BYTES;
-  if (!r->d_clamp_state) { memset(h_state, 0, bytes); return 0; }
-  PN_ON_DEVICE(r->c);
-  PN_HIP_CHECK(hipMemcpyAsync(h_state, r->d_clamp_state, bytes, hipMemcpyDeviceToHost, r->c->stream));
-  PN_HIP_CHECK(hipStreamSynchronize(r->c->stream));
-  return 0;
-}
+extern "C" int pn_rate_get_dtmf_clamp_params(const pn_rate *r, int32_t *params4) { return rate_get_params(r, &pn_rate::clamp_params, params4); }
+extern "C" int pn_rate_set_dtmf_clamp_report(pn_rate *r, int enable) { return rate_set_report(r, RF_CLAMP, enable); }
+extern "C" int pn_rate_read_dtmf_clamp_report(pn_rate *r, void *h_report) { return rate_report_copy(r, RF_CLAMP, h_report, hipMemcpyDeviceToHost); }
+extern "C" int pn_rate_read_dtmf_clamp_report_dev(pn_rate *r, void *d_report) { return rate_report_copy(r, RF_CLAMP, d_report, hipMemcpyDeviceToDevice); }
+extern "C" int pn_rate_debug_dtmf_clamp_state(pn_rate *r, void *h_state) { return state_debug_copy(r, PN_RS_CLAMP, h_state); }
 // TESTS ONLY: the detector's report rows — the user's buffer too — overwritten from the host, synchronising, so that the stand-alone stage
 // can be run over hand-made rows; the next detector launch overwrites them again
 extern "C" int pn_rate_debug_set_dtmf_report(pn_rate *r, const void *h_report) {
   if (!r || !h_report) { pn_set_error("NULL argument"); return -1; }
   PN_ON_DEVICE(r->c);
   if (clamp_buffers(r)) return -1;
-  PN_HIP_CHECK(hipMemcpyAsync(r->d_dtmf_report, h_report, (size_t)r->c->B * PN_DTMF_REPORT_WORDS * 4, hipMemcpyHostToDevice, r->c->stream));
+  PN_HIP_CHECK(hipMemcpyAsync(r->d_report[RF_DTMF], h_report, report_bytes(r, RF_DTMF), hipMemcpyHostToDevice, r->c->stream));
   PN_HIP_CHECK(hipStreamSynchronize(r->c->stream));
   return 0;
 }
 
+// ---- the two resets: what they clear is the state table's ------------------------------------------------------------------------
 extern "C" int pn_rate_reset(pn_rate *r) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   PN_ON_DEVICE(r->c);
-  PN_HIP_CHECK(hipMemsetAsync(r->tail_up, 0, (size_t)r->c->B * PN_RATE_UP_TAIL * 4, r->c->stream));
-  PN_HIP_CHECK(hipMemsetAsync(r->tail_down, 0, (size_t)r->c->B * r->td * 4, r->c->stream));
-  if (r->d_level) PN_HIP_CHECK(hipMemsetAsync(r->d_level, 0, (size_t)r->c->B * 4, r->c->stream));
-  if (r->d_plc_meta) {
-    PN_HIP_CHECK(hipMemsetAsync(r->d_plc_hist, 0, (size_t)r->c->B * PN_PLC_HIST * 4, r->c->stream));
-    PN_HIP_CHECK(hipMemsetAsync(r->d_plc_q, 0, (size_t)r->c->B * PN_PLC_P_MAX * 4, r->c->stream));
-    PN_HIP_CHECK(hipMemsetAsync(r->d_plc_meta, 0, (size_t)r->c->B * 16, r->c->stream));
-  }
-  if (r->d_agc_state) PN_HIP_CHECK(hipMemsetAsync(r->d_agc_state, 0, (size_t)r->c->B * PN_AGC_STATE_BYTES, r->c->stream));
-  if (r->d_lim_state) PN_HIP_CHECK(hipMemsetAsync(r->d_lim_state, 0, (size_t)r->c->B * PN_LIM_STATE_BYTES, r->c->stream));
-  if (r->d_dtmf_state) PN_HIP_CHECK(hipMemsetAsync(r->d_dtmf_state, 0, (size_t)r->c->B * PN_DTMF_STATE_BYTES, r->c->stream));
-  if (r->d_clamp_state) PN_HIP_CHECK(hipMemsetAsync(r->d_clamp_state, 0, (size_t)r->c->B * PN_DTMF_CLAMP_STATE_BYTES, r->c->stream));
-  return 0;
+  return state_clear_all(r, PN_RE_RESET);
 }
-
 extern "C" int pn_rate_reset_streams(pn_rate *r, const int32_t *ids, int n) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
   if (pn_ids_check(r->c->B, ids, n, false)) return -1;
@@ -910,13 +727,7 @@ extern "C" int pn_rate_reset_streams(pn_rate *r, const int32_t *ids, int n) {
   PN_ON_DEVICE(r->c);
   const int *d = stage_ids(r->c, ids, n);
   if (!d) return -1;
-  pn_launch_zero_rows(r->c->stream, r->tail_up, PN_RATE_UP_TAIL, PN_RATE_UP_TAIL, 1, 0, d, n);
-  pn_launch_zero_rows(r->c->stream, r->tail_down, r->td, r->td, 1, 0, d, n);
-  pn_launch_zero_rows(r->c->stream, r->d_level, 1, 1, 1, 0, d, n);
-  plc_zero_rows(r, d, n);
-  agc_zero_rows(r, d, n);
-  lim_zero_rows(r, d, n);
-  dtmf_zero_rows(r, d, n);
+  state_clear_rows(r, PN_RE_RESET_STREAMS, d, n);
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -940,16 +751,16 @@ static int rate_aligned(const void *a, const void *b) {
 }
 static int rate_up(pn_rate *r, const void *d_in, int fmt, float *d_out48, const RateRows &rows) {
   RateScope sc(r, RF_UP);
-  if (r->mixed ? pn_launch_rate_up_mixed(r->c->stream, fmt, rows.n, rows.d_ids, r->factors, r->d_laws, d_in, d_out48, r->tail_up, r->taps_up)
-               : pn_launch_rate_up(r->c->stream, r->f, fmt, rows.n, rows.d_ids, r->d_laws, d_in, d_out48, r->tail_up, r->taps_up)) return -1;
+  if (r->mixed ? pn_launch_rate_up_mixed(r->c->stream, fmt, rows.n, rows.d_ids, r->factors, r->d_laws, d_in, d_out48, stf(r, PN_RS_TAIL_UP), r->taps_up)
+               : pn_launch_rate_up(r->c->stream, r->f, fmt, rows.n, rows.d_ids, r->d_laws, d_in, d_out48, stf(r, PN_RS_TAIL_UP), r->taps_up)) return -1;
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
 static int rate_down(pn_rate *r, const float *d_in48, void *d_out, int fmt, const RateRows &rows) {
   const int sat = r->c->saturate ? 1 : 0;
   RateScope sc(r, RF_DOWN);
-  if (r->mixed ? pn_launch_rate_down_mixed(r->c->stream, fmt, rows.n, rows.d_ids, r->factors, r->d_laws, d_in48, d_out, sat, r->tail_down, r->taps_down)
-               : pn_launch_rate_down(r->c->stream, r->f, fmt, rows.n, rows.d_ids, r->d_laws, d_in48, d_out, sat, r->tail_down, r->taps_down)) return -1;
+  if (r->mixed ? pn_launch_rate_down_mixed(r->c->stream, fmt, rows.n, rows.d_ids, r->factors, r->d_laws, d_in48, d_out, sat, stf(r, PN_RS_TAIL_DOWN), r->taps_down)
+               : pn_launch_rate_down(r->c->stream, r->f, fmt, rows.n, rows.d_ids, r->d_laws, d_in48, d_out, sat, stf(r, PN_RS_TAIL_DOWN), r->taps_down)) return -1;
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -963,74 +774,59 @@ static int rate_mix(pn_rate *r, const float *d_in48, float *d_out48, const RateR
   RateScope sc(r, RF_MIX);
   if (mix_plain(r)) pn_launch_rate_mix(r->c->stream, rows.n, rows.d_ids, r->d_conf, r->d_members, r->d_stamp, r->tick, d_in48, d_out48);
   else pn_launch_rate_mix_sel(r->c->stream, rows.n, rows.d_ids, r->d_conf, r->d_members, r->d_stamp, r->tick, d_in48, d_out48, r->d_gains, r->d_caps,
-                              r->d_level, r->hold, r->mix_report ? r->d_mix_report : NULL);
+                              stf(r, PN_RS_LEVEL), r->hold, rate_report(r, RF_MIX));
+  PN_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+// a stage's launch inside its timed scope, then the launch's verdict
+template <class Launch>
+static int rate_timed(pn_rate *r, int fam, Launch launch) {
+  { RateScope sc(r, fam); launch(); }
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
 // the concealer over the rows, in place; it consumes the marks: the tick moves on, and the host's copy of them is cleared
 static int rate_plc(pn_rate *r, float *d_x48, const RateRows &rows) {
-  {
-    RateScope sc(r, RF_PLC);
-    pn_launch_rate_plc(r->c->stream, rows.n, rows.d_ids, r->d_plc_lost, r->plc_tick, d_x48, r->d_plc_hist, r->d_plc_q, r->d_plc_meta,
-                       r->plc_report ? r->d_plc_report : NULL);
-  }
-  PN_HIP_CHECK(hipGetLastError());
+  if (rate_timed(r, RF_PLC, [&] { pn_launch_rate_plc(r->c->stream, rows.n, rows.d_ids, r->d_plc_lost, r->plc_tick, d_x48, stf(r, PN_RS_PLC_HIST), stf(r, PN_RS_PLC_Q),
+                                                     r->st[PN_RS_PLC_META], rate_report(r, RF_PLC)); })) return -1;
   return plc_drop_marks(r);
 }
 // the level control over the rows, in place; d_lost / tick: the concealer's stamps and the tick it used for this frame (NULL: nobody is concealed)
 static int rate_agc(pn_rate *r, float *d_y48, const RateRows &rows, const uint32_t *d_lost, uint32_t tick) {
-  {
-    RateScope sc(r, RF_AGC);
-    pn_launch_rate_agc(r->c->stream, rows.n, rows.d_ids, r->d_agc_targets, d_lost, tick, r->agc_params, d_y48, r->d_agc_state,
-                       r->agc_report ? r->d_agc_report : NULL);
-  }
-  PN_HIP_CHECK(hipGetLastError());
-  return 0;
+  return rate_timed(r, RF_AGC, [&] { pn_launch_rate_agc(r->c->stream, rows.n, rows.d_ids, r->d_agc_targets, d_lost, tick, r->agc_params, d_y48, r->st[PN_RS_AGC], rate_report(r, RF_AGC)); });
 }
 // the output limiter over the rows, in place on the rows the down-conversion reads next
 static int rate_lim(pn_rate *r, float *d_o48, const RateRows &rows) {
-  {
-    RateScope sc(r, RF_LIM);
-    pn_launch_rate_lim(r->c->stream, rows.n, rows.d_ids, r->d_lim_ceilings, r->lim_params, d_o48, r->d_lim_state, r->lim_report ? r->d_lim_report : NULL);
-  }
-  PN_HIP_CHECK(hipGetLastError());
-  return 0;
+  return rate_timed(r, RF_LIM, [&] { pn_launch_rate_lim(r->c->stream, rows.n, rows.d_ids, r->d_lim_ceilings, r->lim_params, d_o48, r->st[PN_RS_LIM], rate_report(r, RF_LIM)); });
 }
-// the DTMF detector over the rows, which it only reads; d_lost / tick as for the level control
+// the DTMF detector over the rows, which it only reads; d_lost / tick as for the level control.  Its report rows are written for the
+// user, or for the removal stage while that is on for somebody
 static int rate_dtmf(pn_rate *r, const float *d_x48, const RateRows &rows, const uint32_t *d_lost, uint32_t tick) {
-  {
-    RateScope sc(r, RF_DTMF);
-    pn_launch_rate_dtmf(r->c->stream, rows.n, rows.d_ids, r->d_dtmf_on, d_lost, tick, r->dtmf_params, pn_dtmf_tables_ref().rot, r->d_dtmf_tab, d_x48,
-                        r->d_dtmf_state, r->dtmf_report || r->clamp_on > 0 ? r->d_dtmf_report : NULL);
-  }
-  PN_HIP_CHECK(hipGetLastError());
-  return 0;
+  return rate_timed(r, RF_DTMF, [&] { pn_launch_rate_dtmf(r->c->stream, rows.n, rows.d_ids, r->d_dtmf_on, d_lost, tick, r->dtmf_params, pn_dtmf_tables_ref().rot, r->d_dtmf_tab, d_x48,
+                                                          r->st[PN_RS_DTMF], r->report[RF_DTMF] || r->clamp_on > 0 ? r->d_report[RF_DTMF] : NULL); });
 }
 // DTMF removal over the rows, in place on y48; det: the detector ran in this frame (or the caller vouches for its report rows), otherwise
 // every stream counts as "detection off"
 static int rate_clamp(pn_rate *r, float *d_y48, const RateRows &rows, bool det) {
-  {
-    RateScope sc(r, RF_CLAMP);
-    pn_launch_rate_dtmf_clamp(r->c->stream, rows.n, rows.d_ids, r->d_clamp_on, r->clamp_params, det ? r->d_dtmf_report : NULL, d_y48, r->d_clamp_state,
-                              r->clamp_report ? r->d_clamp_report : NULL);
-  }
-  PN_HIP_CHECK(hipGetLastError());
-  return 0;
+  return rate_timed(r, RF_CLAMP, [&] { pn_launch_rate_dtmf_clamp(r->c->stream, rows.n, rows.d_ids, r->d_clamp_on, r->clamp_params, det ? r->d_report[RF_DTMF] : NULL, d_y48,
+                                                                 r->st[PN_RS_CLAMP], rate_report(r, RF_CLAMP)); });
 }
-static int rate_up_call(pn_rate *r, const void *d_in, int fmt, float *d_out48, const int32_t *ids, int n) {
+// The stand-alone stage calls.  Their prologue: the converter, `off` (the stage's switch is off: its message), the rows' alignment —
+// then RATE_STAGE_ROWS: the context's device for the rest of the call, and the rows
+static int rate_stage_check(const pn_rate *r, const void *a, const void *b, const char *off = NULL) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
-  if (rate_aligned(d_in, d_out48)) return -1;
-  PN_ON_DEVICE(r->c);
-  RateRows rows;
-  if (rate_rows(r, ids, n, &rows)) return -1;
+  if (off) { pn_set_error("%s", off); return -1; }
+  return rate_aligned(a, b);
+}
+#define RATE_STAGE_ROWS(r, ids, n) PN_ON_DEVICE((r)->c); RateRows rows; if (rate_rows(r, ids, n, &rows)) return -1
+static int rate_up_call(pn_rate *r, const void *d_in, int fmt, float *d_out48, const int32_t *ids, int n) {
+  if (rate_stage_check(r, d_in, d_out48)) return -1;
+  RATE_STAGE_ROWS(r, ids, n);
   return rate_up(r, d_in, fmt, d_out48, rows);
 }
 static int rate_down_call(pn_rate *r, const float *d_in48, void *d_out, int fmt, const int32_t *ids, int n) {
-  if (!r) { pn_set_error("NULL argument"); return -1; }
-  if (rate_aligned(d_in48, d_out)) return -1;
-  PN_ON_DEVICE(r->c);
-  RateRows rows;
-  if (rate_rows(r, ids, n, &rows)) return -1;
+  if (rate_stage_check(r, d_in48, d_out)) return -1;
+  RATE_STAGE_ROWS(r, ids, n);
   return rate_down(r, d_in48, d_out, fmt, rows);
 }
 extern "C" int pn_rate_up_f32(pn_rate *r, const float *d_in, float *d_out48, const int32_t *ids, int n_ids) { return rate_up_call(r, d_in, PN_FMT_F32, d_out48, ids, n_ids); }
@@ -1040,60 +836,37 @@ extern "C" int pn_rate_down_f32(pn_rate *r, const float *d_in48, float *d_out, c
 extern "C" int pn_rate_down_i16(pn_rate *r, const float *d_in48, int16_t *d_out, const int32_t *ids, int n_ids) { return rate_down_call(r, d_in48, d_out, PN_FMT_I16, ids, n_ids); }
 extern "C" int pn_rate_down_g711(pn_rate *r, const float *d_in48, uint8_t *d_out, const int32_t *ids, int n_ids) { return rate_down_call(r, d_in48, d_out, PN_FMT_G711, ids, n_ids); }
 extern "C" int pn_rate_mix_f32(pn_rate *r, const float *d_in48, float *d_out48, const int32_t *ids, int n_ids) {
-  if (!r) { pn_set_error("NULL argument"); return -1; }
-  if (rate_aligned(d_in48, d_out48)) return -1;
+  if (rate_stage_check(r, d_in48, d_out48)) return -1;
   const uintptr_t a = (uintptr_t)d_in48, b = (uintptr_t)d_out48, span = (uintptr_t)r->c->B * PN_FRAME * 4;
   if (a < b + span && b < a + span) { pn_set_error("the mix reads every member's row for every listener: its input and output rows must not overlap"); return -1; }
-  PN_ON_DEVICE(r->c);
-  RateRows rows;
-  if (rate_rows(r, ids, n_ids, &rows)) return -1;
+  RATE_STAGE_ROWS(r, ids, n_ids);
   return rate_mix(r, d_in48, d_out48, rows);
 }
 extern "C" int pn_rate_plc_f32(pn_rate *r, float *d_x48, const int32_t *ids, int n_ids) {
-  if (!r) { pn_set_error("NULL argument"); return -1; }
-  if (!r->plc) { pn_set_error("packet-loss concealment is off (pn_rate_set_plc)"); return -1; }
-  if (rate_aligned(d_x48, d_x48)) return -1;
-  PN_ON_DEVICE(r->c);
-  RateRows rows;
-  if (rate_rows(r, ids, n_ids, &rows)) return -1;
+  if (rate_stage_check(r, d_x48, d_x48, r && !r->plc ? "packet-loss concealment is off (pn_rate_set_plc)" : NULL)) return -1;
+  RATE_STAGE_ROWS(r, ids, n_ids);
   return rate_plc(r, d_x48, rows);
 }
 extern "C" int pn_rate_agc_f32(pn_rate *r, float *d_y48, const int32_t *ids, int n_ids) {
-  if (!r) { pn_set_error("NULL argument"); return -1; }
-  if (!r->agc) { pn_set_error("automatic level control is off (pn_rate_set_agc)"); return -1; }
-  if (rate_aligned(d_y48, d_y48)) return -1;
-  PN_ON_DEVICE(r->c);
-  RateRows rows;
-  if (rate_rows(r, ids, n_ids, &rows)) return -1;
+  if (rate_stage_check(r, d_y48, d_y48, r && !r->agc ? "automatic level control is off (pn_rate_set_agc)" : NULL)) return -1;
+  RATE_STAGE_ROWS(r, ids, n_ids);
   return rate_agc(r, d_y48, rows, NULL, 0);
 }
+// (the next three: where the stage was never used every stream is off, and its device side exists from here on)
 extern "C" int pn_rate_lim_f32(pn_rate *r, float *d_o48, const int32_t *ids, int n_ids) {
-  if (!r) { pn_set_error("NULL argument"); return -1; }
-  if (rate_aligned(d_o48, d_o48)) return -1;
-  PN_ON_DEVICE(r->c);
-  RateRows rows;
-  if (rate_rows(r, ids, n_ids, &rows)) return -1;
-  if (lim_buffers(r)) return -1;                     // (no ceiling was ever set: every stream is off, the state exists from here on)
-  return rate_lim(r, d_o48, rows);
+  if (rate_stage_check(r, d_o48, d_o48)) return -1;
+  RATE_STAGE_ROWS(r, ids, n_ids);
+  return lim_buffers(r) ? -1 : rate_lim(r, d_o48, rows);
 }
 extern "C" int pn_rate_dtmf_f32(pn_rate *r, const float *d_x48, const int32_t *ids, int n_ids) {
-  if (!r) { pn_set_error("NULL argument"); return -1; }
-  if (rate_aligned(d_x48, d_x48)) return -1;
-  PN_ON_DEVICE(r->c);
-  RateRows rows;
-  if (rate_rows(r, ids, n_ids, &rows)) return -1;
-  if (dtmf_buffers(r)) return -1;                    // (no stream was ever enabled: every stream is off, the state exists from here on)
-  return rate_dtmf(r, d_x48, rows, NULL, 0);
+  if (rate_stage_check(r, d_x48, d_x48)) return -1;
+  RATE_STAGE_ROWS(r, ids, n_ids);
+  return dtmf_buffers(r) ? -1 : rate_dtmf(r, d_x48, rows, NULL, 0);
 }
-
 extern "C" int pn_rate_dtmf_clamp_f32(pn_rate *r, float *d_y48, const int32_t *ids, int n_ids) {
-  if (!r) { pn_set_error("NULL argument"); return -1; }
-  if (rate_aligned(d_y48, d_y48)) return -1;
-  PN_ON_DEVICE(r->c);
-  RateRows rows;
-  if (rate_rows(r, ids, n_ids, &rows)) return -1;
-  if (clamp_buffers(r)) return -1;                   // (no stream was ever enabled: every stream is off, the state exists from here on)
-  return rate_clamp(r, d_y48, rows, true);
+  if (rate_stage_check(r, d_y48, d_y48)) return -1;
+  RATE_STAGE_ROWS(r, ids, n_ids);
+  return clamp_buffers(r) ? -1 : rate_clamp(r, d_y48, rows, true);
 }
 
 // ---- one whole frame -----------------------------------------------------------------------------------------------------------
@@ -1193,12 +966,11 @@ extern "C" int pn_rate_process_host_g711(pn_rate *r, const uint8_t *h_in, uint8_
 // serialises the frames.  Whole rows travel both ways; on a mixed converter that is 480 samples per stream, of which the
 // kernels read and write each stream's own n_s, with no landing buffer and no host copy.
 static int rate_pipe_prepare(pn_rate *r) {           // (the caller is on the context's device)
-  pn_ctx *c = r->c;
-  const size_t bytes = (size_t)c->B * r->n * 4;
+  const size_t bytes = (size_t)r->c->B * r->n * 4;
   // (a mixed converter's rows are zeroed like slot 0's, so that the part of an output row no kernel writes is never stale memory)
-  if (!r->io_in1 && dev_alloc_into(r->allocs, r->bytes, c->stream, &r->io_in1, bytes, r->mixed)) return -1;
-  if (!r->io_out1 && dev_alloc_into(r->allocs, r->bytes, c->stream, &r->io_out1, bytes, r->mixed)) return -1;
-  return pn_host_pipeline_prepare(c);
+  if (!r->io_in1 && rate_alloc(r, r->io_in1, bytes, r->mixed)) return -1;
+  if (!r->io_out1 && rate_alloc(r, r->io_out1, bytes, r->mixed)) return -1;
+  return pn_host_pipeline_prepare(r->c);
 }
 extern "C" int pn_rate_host_pipeline_prepare(pn_rate *r) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
@@ -1242,7 +1014,7 @@ extern "C" int pn_rate_kernel_time(pn_rate *r, const char *name, double *total_m
   PN_ON_DEVICE(r->c);
   if (rate_flush_events(r)) return -1;
   for (int i = 0; i < RF_COUNT; i++)
-    if (!strcmp(name, kRateFamily[i])) { if (total_ms) *total_ms = r->fam_ms[i]; if (launches) *launches = r->fam_n[i]; return 0; }
+    if (!strcmp(name, kRateStage[i].family)) { if (total_ms) *total_ms = r->fam_ms[i]; if (launches) *launches = r->fam_n[i]; return 0; }
   pn_set_error("unknown converter kernel '%s' (rate_up, rate_down, rate_mix, rate_plc, rate_agc, rate_lim, rate_dtmf, rate_clamp)", name);
   return -1;
 }
@@ -1255,38 +1027,40 @@ extern "C" int pn_rate_reset_profile(pn_rate *r) {
 }
 
 // ---- state records -----------------------------------------------------------------------------------------------------------
+// What the four host record calls ask of their arguments: -1 refused, 1 nothing to do (n == 0), 0 go on
+static int host_records_args(const pn_rate *r, const int32_t *ids, int n, const void *h_records, bool distinct) {
+  if (!r || n < 0 || (n > 0 && (!ids || !h_records))) { pn_set_error("bad argument"); return -1; }
+  if (n == 0) return 1;
+  return pn_ids_check(r->c->B, ids, n, distinct) ? -1 : 0;
+}
+// ... and the four device ones, ahead of their list check
+static int dev_records_args(const pn_rate *r, bool import, const int32_t *ids, int n, const void *d_records, const int32_t *d_status) {
+  if (!r || n < 0 || (n > 0 && (!ids || !d_records || (import && !d_status)))) { pn_set_error("bad argument"); return -1; }
+  if (n == 0) return 1;
+  if ((uintptr_t)d_records & 15) { pn_set_error("records must be 16-byte aligned"); return -1; }
+  return 0;
+}
 // Host forms only: synchronous, through the context's host form of a record transfer (host_records_sync).
-// rate: the records' rate — the converter's, or on a mixed one the rate the listed streams share (record_rate)
-static int rate_records_host(pn_rate *r, int rate, bool import, const int32_t *ids, int n, void *h_records) {
+// rate: the records' rate — the converter's, or on a mixed one the rate the listed streams share (record_rate).
+// An imported slot is now another stream: behind the scatter, what the state table clears on PN_RE_IMPORT starts fresh
+static int rate_records_host(pn_rate *r, bool import, const int32_t *ids, int n, void *h_records) {
+  if (int rc = host_records_args(r, ids, n, h_records, import)) return rc < 0 ? -1 : 0;
   pn_ctx *c = r->c;
+  const int rate = r->mixed ? pn_rate_mixed_record_rate(r->rates.data(), ids, n) : r->rate;
+  if (rate < 0) return -1;
   const int f = pn_rate_factor(rate);
+  if (import && pn_records_check(h_records, n, 4 * pn_rate_record_words(f), [&](const void *rec, size_t b) { return pn_rate_record_check(rec, b, rate); })) return -1;
   return host_records_sync(c, import, h_records, (size_t)n * 4 * pn_rate_record_words(f), [&](void *d) {
     const int *d_ids = stage_ids(c, ids, n);
     if (!d_ids) return -1;
-    pn_launch_rate_records(c->stream, f, rate, d_ids, n, r->tail_up, r->tail_down, r->td, d, import ? 1 : 0);
-    if (import) { plc_zero_rows(r, d_ids, n); agc_zero_rows(r, d_ids, n); lim_zero_rows(r, d_ids, n); dtmf_zero_rows(r, d_ids, n); }   // the slot is now another stream: it starts with an empty history and fresh gains
+    pn_launch_rate_records(c->stream, f, rate, d_ids, n, stf(r, PN_RS_TAIL_UP), stf(r, PN_RS_TAIL_DOWN), r->td, d, import ? 1 : 0);
+    if (import) state_clear_rows(r, PN_RE_IMPORT, d_ids, n);
     if (hipGetLastError() != hipSuccess) { pn_set_error(import ? "record scatter launch failed" : "record gather launch failed"); return -1; }
     return 0;
   });
 }
-static int record_rate(const pn_rate *r, const int32_t *ids, int n) { return r->mixed ? pn_rate_mixed_record_rate(r->rates.data(), ids, n) : r->rate; }
-extern "C" int pn_rate_export_streams_host(pn_rate *r, const int32_t *ids, int n, void *h_records) {
-  if (!r || n < 0 || (n > 0 && (!ids || !h_records))) { pn_set_error("bad argument"); return -1; }
-  if (n == 0) return 0;
-  if (pn_ids_check(r->c->B, ids, n, false)) return -1;
-  const int rate = record_rate(r, ids, n);
-  if (rate < 0) return -1;
-  return rate_records_host(r, rate, false, ids, n, h_records);
-}
-extern "C" int pn_rate_import_streams_host(pn_rate *r, const int32_t *ids, int n, const void *h_records) {
-  if (!r || n < 0 || (n > 0 && (!ids || !h_records))) { pn_set_error("bad argument"); return -1; }
-  if (n == 0) return 0;
-  if (pn_ids_check(r->c->B, ids, n, true)) return -1;
-  const int rate = record_rate(r, ids, n);
-  if (rate < 0) return -1;
-  if (pn_records_check(h_records, n, 4 * pn_rate_record_words(pn_rate_factor(rate)), [&](const void *rec, size_t b) { return pn_rate_record_check(rec, b, rate); })) return -1;
-  return rate_records_host(r, rate, true, ids, n, const_cast<void *>(h_records));
-}
+extern "C" int pn_rate_export_streams_host(pn_rate *r, const int32_t *ids, int n, void *h_records) { return rate_records_host(r, false, ids, n, h_records); }
+extern "C" int pn_rate_import_streams_host(pn_rate *r, const int32_t *ids, int n, const void *h_records) { return rate_records_host(r, true, ids, n, const_cast<void *>(h_records)); }
 
 // Device forms: asynchronous on the context's stream and ordered like pn_ctx_export_streams / pn_ctx_import_streams.  Records are
 // pn_rate_record_stride(r) apart — on a mixed converter the largest record's size, which is what lets one call move streams of
@@ -1300,17 +1074,15 @@ extern "C" size_t pn_rate_record_stride(const pn_rate *r) {
   return r->mixed ? (size_t)PN_RATE_STATE_MAX_BYTES : 4 * pn_rate_record_words(r->f);
 }
 static int rate_records_dev(pn_rate *r, bool import, const int32_t *ids, int n, void *d_records, int32_t *d_status) {
-  if (!r || n < 0 || (n > 0 && (!ids || !d_records || (import && !d_status)))) { pn_set_error("bad argument"); return -1; }
-  if (n == 0) return 0;
-  if ((uintptr_t)d_records & 15) { pn_set_error("records must be 16-byte aligned"); return -1; }
+  if (int rc = dev_records_args(r, import, ids, n, d_records, d_status)) return rc < 0 ? -1 : 0;
   pn_ctx *c = r->c;
   if (pn_rate_records_list_check(c->B, r->mixed ? r->rates.data() : NULL, ids, n, import)) return -1;
   PN_ON_DEVICE(c);
   const int *d = stage_ids(c, ids, n);
   if (!d) return -1;
-  pn_launch_rate_records_dev(c->stream, d, n, r->mixed ? r->factors : NULL, r->f, r->tail_up, r->tail_down, r->td, d_records,
+  pn_launch_rate_records_dev(c->stream, d, n, r->mixed ? r->factors : NULL, r->f, stf(r, PN_RS_TAIL_UP), stf(r, PN_RS_TAIL_DOWN), r->td, d_records,
                              (int)(pn_rate_record_stride(r) / 4), d_status, import ? 1 : 0);
-  if (import) { plc_zero_rows(r, d, n); agc_zero_rows(r, d, n); lim_zero_rows(r, d, n); dtmf_zero_rows(r, d, n); }   // the slot is now another stream: it starts with an empty history and fresh gains, whatever its record's status
+  if (import) state_clear_rows(r, PN_RE_IMPORT, d, n);   // (whatever the record's status: the slot is another stream's now)
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -1320,10 +1092,13 @@ extern "C" int pn_rate_import_streams(pn_rate *r, const int32_t *ids, int n, con
 }
 
 // ---- call-state records (include/percepnet_hip.h; layout and verdict pn_call_rules.h; the kernel pn_rate_call.hip) ----------------
-// The second record of a stream: the PLC, AGC, limiter and level state, whatever its rate.  Nothing here allocates state: a section
-// the converter does not hold is zero on export and dropped on import.
+// The second record of a stream: the PLC, AGC, limiter and level state, whatever its rate — the entries of the state table that have a
+// section.  Nothing here allocates state: a section the converter does not hold is zero on export and dropped on import.  A section
+// is held while its buffers exist; the concealer's, while the concealer is ON
 static uint32_t call_held(const pn_rate *r) {
-  return (r->plc ? PN_CALL_PLC : 0u) | (r->d_agc_state ? PN_CALL_AGC : 0u) | (r->d_lim_state ? PN_CALL_LIM : 0u) | (r->d_level ? PN_CALL_MIX : 0u);
+  uint32_t held = 0;
+  for (int e = 0; e < PN_RS_COUNT; e++) if (r->st[e]) held |= pn_kRateState[e].call_bit;
+  return r->plc ? held : held & ~(uint32_t)PN_CALL_PLC;
 }
 extern "C" size_t pn_rate_call_state_bytes(void) { return PN_RATE_CALL_STATE_BYTES; }
 extern "C" int pn_rate_call_state_check(const void *record, size_t bytes) { return pn_call_record_check(record, bytes); }
@@ -1332,15 +1107,13 @@ extern "C" int pn_rate_call_state_sections(const pn_rate *r) { if (!r) { pn_set_
 static int call_state_launch(pn_rate *r, bool import, const int32_t *ids, int n, void *d_records, int32_t *d_status) {
   const int *d = stage_ids(r->c, ids, n);
   if (!d) return -1;
-  pn_launch_rate_call_state(r->c->stream, d, n, call_held(r), r->d_plc_hist, r->d_plc_q, r->d_plc_meta, r->d_agc_state, r->d_lim_state, r->d_level, d_records,
-                            d_status, import ? 1 : 0);
+  pn_launch_rate_call_state(r->c->stream, d, n, call_held(r), stf(r, PN_RS_PLC_HIST), stf(r, PN_RS_PLC_Q), r->st[PN_RS_PLC_META], r->st[PN_RS_AGC], r->st[PN_RS_LIM],
+                            stf(r, PN_RS_LEVEL), d_records, d_status, import ? 1 : 0);
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
 static int call_state_dev(pn_rate *r, bool import, const int32_t *ids, int n, void *d_records, int32_t *d_status) {
-  if (!r || n < 0 || (n > 0 && (!ids || !d_records || (import && !d_status)))) { pn_set_error("bad argument"); return -1; }
-  if (n == 0) return 0;
-  if ((uintptr_t)d_records & 15) { pn_set_error("records must be 16-byte aligned"); return -1; }
+  if (int rc = dev_records_args(r, import, ids, n, d_records, d_status)) return rc < 0 ? -1 : 0;
   if (pn_ids_check(r->c->B, ids, n, import)) return -1;
   PN_ON_DEVICE(r->c);
   return call_state_launch(r, import, ids, n, d_records, d_status);
@@ -1352,15 +1125,11 @@ extern "C" int pn_rate_import_call_state(pn_rate *r, const int32_t *ids, int n, 
 // Host forms: synchronous through host_records_sync, like the tails records'.  The import judges every record with the kernel's own
 // verdict before anything is launched; the statuses the kernel then writes come back with the transfer and must all be PN_SS_OK.
 extern "C" int pn_rate_export_call_state_host(pn_rate *r, const int32_t *ids, int n, void *h_records) {
-  if (!r || n < 0 || (n > 0 && (!ids || !h_records))) { pn_set_error("bad argument"); return -1; }
-  if (n == 0) return 0;
-  if (pn_ids_check(r->c->B, ids, n, false)) return -1;
+  if (int rc = host_records_args(r, ids, n, h_records, false)) return rc < 0 ? -1 : 0;
   return host_records_sync(r->c, false, h_records, (size_t)n * PN_RATE_CALL_STATE_BYTES, [&](void *d) { return call_state_launch(r, false, ids, n, d, NULL); });
 }
 extern "C" int pn_rate_import_call_state_host(pn_rate *r, const int32_t *ids, int n, const void *h_records) {
-  if (!r || n < 0 || (n > 0 && (!ids || !h_records))) { pn_set_error("bad argument"); return -1; }
-  if (n == 0) return 0;
-  if (pn_ids_check(r->c->B, ids, n, true)) return -1;
+  if (int rc = host_records_args(r, ids, n, h_records, true)) return rc < 0 ? -1 : 0;
   if (pn_records_check(h_records, n, PN_RATE_CALL_STATE_BYTES, [&](const void *rec, size_t b) { return pn_call_record_check(rec, b); })) return -1;
   const size_t bytes = (size_t)n * PN_RATE_CALL_STATE_BYTES;
   std::vector<int32_t> status(n, 0);

@@ -153,3 +153,19 @@ def test_design_and_record_check_under_sanitizers(tmp_path):
     assert r.returncode == 0, r.stderr[-3000:]
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-500:], r.stderr[-3000:])
+
+
+def test_state_table_under_sanitizers(tmp_path):
+    """tests/c/rate_layout_sanitize.cpp = pn_rate_layout.h (+ pn_model.cpp for the error string) built WITHOUT HIP by plain g++ with
+    -fsanitize=address,undefined: which event clears which of the converter's ten per-stream state buffers against the matrix
+    written out there, the call-state sections against pn_call_rules.h, every width against its stage's constant."""
+    if not shutil.which("g++"):
+        pytest.skip("g++ not available")
+    exe = tmp_path / "rate_layout_sanitize"
+    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-DPN_NO_HIP", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                        os.path.join(ROOT, "tests", "c", "rate_layout_sanitize.cpp"), "-o", str(exe)], capture_output=True, text=True)
+    if r.returncode and "sanitize" in r.stderr and "cannot find" in r.stderr:
+        pytest.skip("sanitizer runtimes not installed")
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-500:], r.stderr[-3000:])
