@@ -632,7 +632,7 @@ int pn_rate_get_stream_rates(const pn_rate *r, int32_t *h_rates);
    the context's pipeline and may be interleaved with the other pn_rate_submit_host_* calls and with pn_submit_host_*;
    pn_host_next_report works unchanged.
    NOT provided: linear and companded rows in one call; G.711 on pn_process_* without a converter (a mixed converter whose slots
-   run at 48000 covers it); G.711 Appendix II comfort noise (packet-loss concealment: its own section below).  How well the model, trained on
+   run at 48000 covers it).  (Packet-loss concealment and comfort noise: their own sections below.)  How well the model, trained on
    full-band linear speech, cleans companded narrowband input is not measured. */
 #define PN_G711_ULAW 0
 #define PN_G711_ALAW 1
@@ -838,7 +838,7 @@ int pn_rate_read_mix_report_dev(pn_rate *r, void *d_report);
    stream; the call-state record ("call-state records", below), imported behind them, brings the moved stream's own history.
    Host only, needing no GPU: pn_plc_pitch (hist[1920] -> P), pn_plc_period (hist, P in [240, 720] -> q[0..P); -1 otherwise),
    pn_plc_gain (m -> g(m)).
-   NOT provided: Appendix I's lengthening of the repeated segment to two and three periods on long losses; Appendix II comfort noise;
+   NOT provided: Appendix I's lengthening of the repeated segment to two and three periods on long losses (comfort noise for DTX streams: the next section);
    concealment on pn_process_* without a converter; lost marks set for the next frame in any record (a mover sets them again).  How
    the model's output quality fares on concealed frames is not measured. */
 #define PN_PLC_HIST 1920
@@ -857,6 +857,85 @@ int pn_rate_plc_f32(pn_rate *r, float *d_x48, const int32_t *ids, int n_ids);
 int pn_rate_set_plc_report(pn_rate *r, int enable);
 int pn_rate_read_plc_report(pn_rate *r, void *h_report);
 int pn_rate_read_plc_report_dev(pn_rate *r, void *d_report);
+
+/* ---- comfort noise: DTX streams filled on the GPU --------------------------------------------------------------------------------- */
+/* An endpoint with silence suppression (DTX) stops sending in a pause and sends only a silence descriptor (SID, RFC 3389 / G.711
+   Appendix II): a noise level and a spectral shape.  Such a stream is neither left off the id list (the talker stops hearing the
+   conference), nor marked lost (the concealer repeats speech and fades to digital silence), nor fed zeros (the noise floor the engine
+   leaves under speech drops out in every pause and pumps): the row of a SILENT stream is filled with the noise its SID describes, IN
+   FRONT of the engine, so the noise of a pause passes the same suppressor as the noise under speech.  One kernel (csrc/pn_rate_cng.hip)
+   writes the row AT THE STREAM'S OWN RATE — the SID's spectrum is defined there — into a converter-owned buffer, and the stream's own,
+   unchanged up-conversion (float) takes it to 48 kHz: the noise is band-limited like the stream's speech, and the filter tail runs
+   continuously across speech, noise and speech.  Everything behind sees an ordinary row: the concealer (a received row of its
+   history), the detector, the engine, level control, the mix, the reports.  A silent frame is bit for bit the frame of a float
+   converter whose caller had supplied the same noise row.  OFF by default: a converter that never enables it, or enables it and marks
+   nobody, launches exactly what it launches without this section and gives the same bits.
+
+   The rule, with every rounding, is csrc/pn_cng_rules.h (HIP-free); tests/cng_model.py restates it in numpy integers and float32 and
+   the kernel matches both bit for bit.  Samples are in the float convention (int16 / 32768).
+   SID of a stream: PN_CNG_SID_BYTES = 14 bytes, FIXED: byte 0 = M, the number of reflection coefficients, 0..12; byte 1 = L, the level in
+     -dBov, 0..127; bytes 2..13 = N_1..N_12, 0..254 each, of which the first M count (the rest is not looked at and reads back as 0).
+     That is the RFC 3389 payload behind a count byte.  Refused: M > 12, L > 127, N_i = 255 for an i <= M.  A stream nobody gave a SID
+     has the DEFAULT: level only, M = 0, L = PN_CNG_DEFAULT_LEVEL = 60 (-60 dBov).
+   Decode (host, double, rounded once to fp32): k_i = 258 (N_i - 127) / 32768 — this formula is the contract; it is RFC 3389 section 3.2
+     as remembered, no copy of the RFC was at hand —, rms = 10^(-L/20) from a table of 128 fp32 literals, g = rms sqrt(prod (1 - k_i^2)),
+     so shaped noise of any spectrum has the level the SID names.
+   Excitation: h = mix(mix(c) ^ key), c the stream's sample counter, key = seed ^ slot * 0x9e3779b1, mix the 32-bit murmur3 finaliser;
+     u = (h & 0xffff) + (h >> 16) - 65535, triangular; e = (float)u * (1 / sqrt((2^32 - 1) / 6)).  Gaussian it is not.
+   Synthesis: f = gain(n) e; for i = M..1: f = f - k_i b[i-1], and where i < M: b[i] = b[i-1] + k_i f; b[0] = f; the sample is f.
+   Gain: g on the first row of a run; on a row that continues a run, prev + ((n+1) / n_s) (g - prev), prev the g of the row before: an
+     unchanged SID gives g exactly, a changed one ramps across one row.  A row CONTINUES a run when the stream's row was generated in the
+     converter's previous frame too; a frame in which it was received, concealed or did not advance ends the run.
+   State per stream, 16 words, allocated by the first enable: b[12], the sample counter (+ n_s per generated row, wrapping), prev, the
+     run, the generated rows since the state was cleared.  The end of a run leaves b and the counter: the next pause continues the
+     sequence.  Every finite SID gives finite rows.  The state is zeroed by pn_rate_reset, for the listed streams by
+     pn_rate_reset_streams, pn_rate_set_stream_rates, pn_rate_import_streams[_host], and by "on again"; it travels in NO record.
+
+   pn_rate_set_cng(r, enable): the first enable allocates the state, the decoded SIDs and the rows, and makes room in the id ring, so no
+     frame allocates.  Enabling again after a disable zeroes every stream's state.  Disabling drops the marks.
+   pn_rate_set_cng_seed / pn_rate_get_cng_seed: the converter's seed, default PN_CNG_DEFAULT_SEED; an argument of every launch.
+   pn_rate_set_stream_sid(r, ids, n, sids, stride): SID i, at sids + i * stride (stride >= 14), becomes stream ids[i]'s.  A setting,
+     asynchronous and ordered like pn_rate_set_stream_laws, on the pipelined path too; valid with the switch off or never on (the
+     first enable decodes what was set).  All or nothing: a bad or duplicate id or a refused SID changes nothing; every refusal
+     stands in front of the first launch.  A list goes to the device in pieces of 1024 SIDs; should the device itself fail at a later
+     piece (-1, a HIP error), the pieces before it are written on the device and pn_rate_get_stream_sid still gives the SIDs of before.
+     pn_rate_get_stream_sid(r, h_sids): [n_streams][14] bytes as last set.
+   pn_rate_set_silent(r, ids, n): the listed streams are silent in the NEXT frame submitted on this converter, and only in that one,
+     with the lifetime of pn_rate_set_lost's marks; calls before one frame add up.  Refused while the switch is off.  A silent stream's
+     INPUT row is never read.  A stream marked lost AND silent is concealed (lost wins); its silent mark is consumed all the same.  A
+     marked stream that does not advance keeps all its state; its mark is dropped.
+   pn_rate_cng_f32(r, d_x48, ids, n_ids): the stage on its own: the row of every LISTED stream (NULL: all), marked or not, is generated
+     and up-converted into its row of d_x48 [n_streams][480]; other rows are not touched.  It counts as a frame: marks are dropped.
+   pn_rate_kernel_time takes "rate_cng"; the second up-conversion launch counts under "rate_up".  (With the two launches a frame can
+     now have ten timed scopes, so pn_rate_set_profiling creates 1280 events up front where it created 1024, on every converter.)
+   CNG report (pn_rate_set_cng_report, pn_rate_read_cng_report[_dev]; -1 while off): PN_CNG_REPORT_WORDS = 4 words per stream, written
+     when the stream's row is generated (other streams' records keep what they had):
+     word 0  run     consecutive generated rows including this one      word 2  g     the gain in use, float bits
+     word 1  total   generated rows since the state was cleared         word 3  ctr   the sample counter behind the row
+   Host only, needing no GPU: pn_cng_sid_decode (14 bytes -> g, k[12], M; -1 for a refused SID), pn_cng_level (L -> the table's rms),
+     pn_cng_frame (one row of one stream: the twin of the kernel, as pn_agc_frame is; cont: the row continues a run).
+   NOT provided: the send side (VAD, the DTX decision, SID generation for outgoing streams); noise state in any record (a moved call's
+   noise restarts under the new slot's key); comfort noise without a converter, or in the gap behind DTMF removal; Gaussian excitation;
+   any measurement of how the model treats synthetic noise, or of perceived quality. */
+#define PN_CNG_MAX_ORDER 12
+#define PN_CNG_SID_BYTES 14
+#define PN_CNG_DEFAULT_LEVEL 60
+#define PN_CNG_DEFAULT_SEED 0x434e4731u
+#define PN_CNG_REPORT_WORDS 4
+int pn_cng_sid_decode(const uint8_t *sid14, float *g, float *k12, int32_t *M);
+float pn_cng_level(int level);
+int pn_cng_frame(const uint8_t *sid14, uint32_t *state16, uint32_t seed, int slot, int cont, int n, float *row, uint32_t *report4);
+int pn_rate_set_cng(pn_rate *r, int enable);
+int pn_rate_set_cng_seed(pn_rate *r, uint32_t seed);
+int pn_rate_get_cng_seed(const pn_rate *r, uint32_t *seed);
+int pn_rate_set_stream_sid(pn_rate *r, const int32_t *ids, int n, const uint8_t *sids, int stride);
+int pn_rate_get_stream_sid(const pn_rate *r, uint8_t *h_sids);
+int pn_rate_set_silent(pn_rate *r, const int32_t *ids, int n);
+int pn_rate_cng_f32(pn_rate *r, float *d_x48, const int32_t *ids, int n_ids);
+int pn_rate_set_cng_report(pn_rate *r, int enable);
+int pn_rate_read_cng_report(pn_rate *r, void *h_report);
+int pn_rate_read_cng_report_dev(pn_rate *r, void *d_report);
+int pn_rate_debug_cng_state(pn_rate *r, void *h_state);                /* tests: [n_streams][16] words, synchronising */
 
 /* ---- automatic level control: talkers levelled on the GPU ------------------------------------------------------------------------ */
 /* A quiet phone caller and a hot headset otherwise enter a conference at whatever level they arrive: loudest-N ranks raw frame

@@ -35,6 +35,10 @@ PLC_HIST, PLC_P_MIN, PLC_P_MAX = 1920, 240, 720
 PLC_REPORT_WORDS = 4
 PLC_CONCEALED, PLC_CROSSFADE, PLC_SILENT = 1, 2, 4                  # its flags
 PLC_REPORT_DTYPE = np.dtype([("flags", "<u4"), ("period", "<u4"), ("run", "<u4"), ("lost", "<u4")])
+# comfort noise (include/percepnet_hip.h "comfort noise"): PN_CNG_*
+CNG_MAX_ORDER, CNG_SID_BYTES, CNG_DEFAULT_LEVEL, CNG_DEFAULT_SEED = 12, 14, 60, 0x434e4731
+CNG_REPORT_WORDS = 4
+CNG_REPORT_DTYPE = np.dtype([("run", "<u4"), ("total", "<u4"), ("gain", "<f4"), ("counter", "<u4")])
 # automatic level control (include/percepnet_hip.h "automatic level control"): PN_AGC_*
 AGC_N_PARAMS = 8
 AGC_MAX_GAIN, AGC_MIN_GAIN, AGC_GATE_RMS, AGC_ATTACK, AGC_RELEASE, AGC_STEP_UP, AGC_STEP_DOWN, AGC_CEILING = range(8)   # parameter indices
@@ -248,6 +252,19 @@ def load_library():
         L.pn_rate_set_lost.argtypes = [_vp, _vp, ctypes.c_int]
         L.pn_rate_plc_f32.argtypes = [_vp, _vp, _vp, ctypes.c_int]
         for name in ("pn_rate_read_plc_report", "pn_rate_read_plc_report_dev"):
+            getattr(L, name).argtypes = [_vp, _vp]
+    if hasattr(L, "pn_rate_set_cng"):
+        L.pn_cng_sid_decode.argtypes = [_vp, _vp, _vp, _vp]
+        L.pn_cng_level.restype = ctypes.c_float
+        L.pn_cng_level.argtypes = [ctypes.c_int]
+        L.pn_cng_frame.argtypes = [_vp, _vp, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp]
+        for name in ("pn_rate_set_cng", "pn_rate_set_cng_report"):
+            getattr(L, name).argtypes = [_vp, ctypes.c_int]
+        L.pn_rate_set_cng_seed.argtypes = [_vp, ctypes.c_uint32]
+        L.pn_rate_set_stream_sid.argtypes = [_vp, _vp, ctypes.c_int, _vp, ctypes.c_int]
+        L.pn_rate_set_silent.argtypes = [_vp, _vp, ctypes.c_int]
+        L.pn_rate_cng_f32.argtypes = [_vp, _vp, _vp, ctypes.c_int]
+        for name in ("pn_rate_get_cng_seed", "pn_rate_get_stream_sid", "pn_rate_read_cng_report", "pn_rate_read_cng_report_dev", "pn_rate_debug_cng_state"):
             getattr(L, name).argtypes = [_vp, _vp]
     if hasattr(L, "pn_rate_set_agc"):
         for name in ("pn_agc_default_params", "pn_agc_params_check"):
@@ -765,6 +782,50 @@ def plc_gain(m):
     return np.float32(load_library().pn_plc_gain(int(m)))
 
 
+def cng_sid(level, coeffs=()):
+    """A SID of CNG_SID_BYTES bytes from a level L (-dBov) and up to 12 quantised reflection coefficients N_i -> uint8 [14].  Nothing is
+    checked here: the library refuses what the rule excludes."""
+    n = list(coeffs)
+    sid = np.zeros(CNG_SID_BYTES, np.uint8)
+    sid[0], sid[1] = min(len(n), 255), int(level) & 0xff
+    sid[2:2 + min(len(n), CNG_MAX_ORDER)] = n[:CNG_MAX_ORDER]
+    return sid
+
+
+def _cng_sid(sid):
+    a = np.ascontiguousarray(sid, dtype=np.uint8).ravel()
+    if a.size != CNG_SID_BYTES:
+        raise PercepNetError(f"a SID of {a.size} bytes: the converter's has {CNG_SID_BYTES} (M, L, N_1..N_12)")
+    return a
+
+
+def cng_sid_decode(sid):
+    """(g, k[12], M) of a SID (pn_cng_sid_decode, host only); raises PercepNetError for byte values the rule excludes."""
+    L = load_library()
+    a, g, k, M = _cng_sid(sid), ctypes.c_float(0), np.zeros(CNG_MAX_ORDER, np.float32), ctypes.c_int32(0)
+    if L.pn_cng_sid_decode(a.ctypes.data, ctypes.byref(g), k.ctypes.data, ctypes.byref(M)) != 0:
+        raise PercepNetError(_err(L))
+    return np.float32(g.value), k, int(M.value)
+
+
+def cng_level(level):
+    """The rms of level L in -dBov, the rule's table entry (pn_cng_level, host only) -> numpy float32 scalar; NaN outside [0, 127]."""
+    return np.float32(load_library().pn_cng_level(int(level)))
+
+
+def cng_frame(sid, state, seed, slot, cont, n):
+    """One comfort-noise row of n samples of the stream in `slot` (pn_cng_frame, host only).  state: uint32 [16], updated in place
+    -> (row float32 [n], report uint32 [4])."""
+    L = load_library()
+    a = _cng_sid(sid)
+    if not (isinstance(state, np.ndarray) and state.dtype == np.uint32 and state.size == 16 and state.flags.c_contiguous):
+        raise PercepNetError("state: a contiguous uint32 array of 16 words")
+    row, rep = np.empty(max(int(n), 1), np.float32), np.zeros(4, np.uint32)
+    if L.pn_cng_frame(a.ctypes.data, state.ctypes.data, int(seed) & 0xffffffff, int(slot), 1 if cont else 0, int(n), row.ctypes.data, rep.ctypes.data) != 0:
+        raise PercepNetError(_err(L))
+    return row[:int(n)], rep
+
+
 def agc_default_params():
     """-> float32 [AGC_N_PARAMS]: the level control's default parameters (pn_agc_default_params, host only)."""
     p = np.empty(AGC_N_PARAMS, np.float32)
@@ -1155,6 +1216,66 @@ class RateConverter:
         """The same into device memory [n_streams][4] words, asynchronous on the context's stream (pn_rate_read_plc_report_dev)."""
         self._chk(self.L.pn_rate_read_plc_report_dev(self.h, d_report))
 
+    # comfort noise: a silent (DTX) stream's row is filled with the noise its SID describes, at its own rate, in front of the up-conversion
+    def set_cng(self, on):
+        """Comfort noise on or off (pn_rate_set_cng); the first enable allocates the per-stream state, the decoded SIDs and the rows."""
+        self._chk(self.L.pn_rate_set_cng(self.h, 1 if on else 0))
+
+    def set_cng_seed(self, seed):
+        """The converter's excitation seed from the next frame on (pn_rate_set_cng_seed); CNG_DEFAULT_SEED on a new converter."""
+        self._chk(self.L.pn_rate_set_cng_seed(self.h, int(seed) & 0xffffffff))
+
+    def cng_seed(self):
+        v = ctypes.c_uint32(0)
+        self._chk(self.L.pn_rate_get_cng_seed(self.h, ctypes.byref(v)))
+        return int(v.value)
+
+    def set_stream_sid(self, ids, sids):
+        """The SIDs of streams `ids`: uint8 [n][CNG_SID_BYTES] rows of (M, L, N_1..N_12) (pn_rate_set_stream_sid); a setting ordered
+        like set_stream_laws, valid with comfort noise off.  All or nothing."""
+        a, n = self._ids(ids)
+        w = np.ascontiguousarray(np.asarray(sids, dtype=np.uint8).reshape(-1, CNG_SID_BYTES))
+        if w.shape[0] != n:
+            raise PercepNetError(f"{w.shape[0]} SIDs for {n} streams")
+        self._chk(self.L.pn_rate_set_stream_sid(self.h, a.ctypes.data if a is not None else None, n, w.ctypes.data, CNG_SID_BYTES))
+
+    def stream_sids(self):
+        """-> uint8 [n_streams][CNG_SID_BYTES]: the SIDs as last set (pn_rate_get_stream_sid); the default everywhere on a new converter."""
+        w = np.empty((self.n_streams, CNG_SID_BYTES), np.uint8)
+        self._chk(self.L.pn_rate_get_stream_sid(self.h, w.ctypes.data))
+        return w
+
+    def set_silent(self, ids):
+        """Streams `ids` are silent in the NEXT frame submitted on this converter, and only in that one (pn_rate_set_silent): their rows
+        are comfort noise, their input rows are not read; calls before one frame add up.  Refused while comfort noise is off."""
+        a, n = self._ids(ids)
+        self._chk(self.L.pn_rate_set_silent(self.h, a.ctypes.data if a is not None else None, n))
+
+    def cng_f32_dev(self, d_x48, ids=None):
+        """Comfort noise on its own: the listed streams' rows generated and up-converted into device rows [n_streams][480] float
+        (pn_rate_cng_f32); other rows are not touched."""
+        a, n = self._ids(ids)
+        self._chk(self.L.pn_rate_cng_f32(self.h, d_x48, a.ctypes.data if a is not None else None, n))
+
+    def set_cng_report(self, on):
+        self._chk(self.L.pn_rate_set_cng_report(self.h, 1 if on else 0))
+
+    def read_cng_report(self):
+        """-> CNG_REPORT_DTYPE [n_streams]: a stream's record is of its last generated row (pn_rate_read_cng_report, synchronising)."""
+        rep = np.empty(self.n_streams, CNG_REPORT_DTYPE)
+        self._chk(self.L.pn_rate_read_cng_report(self.h, rep.ctypes.data))
+        return rep
+
+    def read_cng_report_dev(self, d_report):
+        """The same into device memory [n_streams][4] words, asynchronous on the context's stream (pn_rate_read_cng_report_dev)."""
+        self._chk(self.L.pn_rate_read_cng_report_dev(self.h, d_report))
+
+    def debug_cng_state(self):
+        """-> uint32 [n_streams][16]: b[12], counter, prev, run, total (tests; synchronising)."""
+        st = np.empty((self.n_streams, 16), np.uint32)
+        self._chk(self.L.pn_rate_debug_cng_state(self.h, st.ctypes.data))
+        return st
+
     # automatic level control: a levelled stream's enhanced 48 kHz row is brought towards its target RMS, between the engine and the mix
     def set_agc(self, on):
         """Automatic level control on or off (pn_rate_set_agc); the first enable allocates the per-stream state and targets."""
@@ -1493,7 +1614,7 @@ class RateConverter:
     def kernel_times(self, names=("rate_up", "rate_down")):
         """-> {"rate_up": (total_ms, launches), "rate_down": (...)}; names: which kernels ("rate_mix" is the conference mix,
         "rate_plc" the packet-loss concealer, "rate_agc" the level control, "rate_lim" the output limiter, "rate_dtmf" the DTMF detector,
-        "rate_clamp" DTMF removal)"""
+        "rate_clamp" DTMF removal, "rate_cng" comfort noise)"""
         out = {}
         for name in names:
             ms = ctypes.c_double()

@@ -5,7 +5,7 @@
 // dropped, main.cpp:32-33); with a single pair ./feature_test.raw gets 68 floats per frame.
 //
 //   percepnet_run [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N]
-//                 [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--plc [--lose P:F0-F1,P:F,..]] [--agc RMS [--agc-max-gain G]] [--limiter CEIL [--limiter-hold H]] [--dtmf [--dtmf-on-frames N]] [--dtmf-clamp [--dtmf-guard PRE,POST]] [--migrate-at F] [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
+//                 [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--plc [--lose P:F0-F1,P:F,..]] [--dtx P:F0-F1,P:F,.. [--sid L[:N1:..:NM]]] [--agc RMS [--agc-max-gain G]] [--limiter CEIL [--limiter-hold H]] [--dtmf [--dtmf-on-frames N]] [--dtmf-clamp [--dtmf-guard PRE,POST]] [--migrate-at F] [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
 //                 in0.pcm out0.pcm [in1.pcm out1.pcm ...]
 //
 // --rate R: the files are raw int16 at R Hz instead of 48 kHz, in frames of n = 480 * R / 48000 samples (80 | 160 | 240 | 320): a rate
@@ -46,6 +46,12 @@
 // converter of all 48000, as --conference does.  --lose P:F0-F1,P:F,..: pair P (counted over the whole command line, from 0) loses its
 // frames F0..F1 (or the one frame F; a pair's frames count from 0): the frame is still READ from the pair's input and discarded, so the
 // files stay aligned, and pn_rate_set_lost marks the pair's slot in front of that frame's submit.  --lose without --plc is refused.
+// --dtx P:F0-F1,P:F,..: comfort noise on the converter (pn_rate_set_cng), with the syntax of --lose: pair P is SILENT on its frames F0..F1 — the
+// frame is still read from the pair's input and discarded, pn_rate_set_silent marks the pair's slot in front of that frame's submit, and the
+// row the engine sees is the noise of the pair's silence descriptor.  --sid L[:N1:..:NM]: that descriptor for every pair, the level L in
+// -dBov (0..127) and up to 12 quantised reflection coefficients (0..254) (pn_rate_set_stream_sid; default: level only, 60); it needs --dtx.
+// With --rate or --rates it uses their converter, alone it makes a mixed converter of all 48000, as --plc does; with --plc a frame that is
+// both lost and silent is concealed; with --migrate-at the noise starts again behind the move: no record carries its state.
 // --agc RMS: automatic level control on the converter (pn_rate_set_agc): every pair's enhanced signal is levelled towards the linear RMS
 // target RMS in (0, 1] (parsed with strtof; pn_rate_set_stream_agc_targets for every slot, once: a slot reset starts the slot's level
 // again and keeps its target), in front of the mix where there is one.  With --rate or --rates it uses their converter, alone it makes a
@@ -147,6 +153,9 @@ static std::vector<float> g_mix_gains;                // --mix-gains: one send g
 static bool g_plc = false;                            // --plc: packet-loss concealment on the converter
 struct LoseRange { long pair, f0, f1; };
 static std::vector<LoseRange> g_lose;                 // --lose: pair, first and last lost frame of the pair
+static std::vector<LoseRange> g_dtx;                  // --dtx: pair, first and last silent frame of the pair; not empty: comfort noise is on
+static uint8_t g_sid[PN_CNG_SID_BYTES];               // --sid: every pair's silence descriptor
+static bool g_sid_given = false;
 static float g_agc = 0.0f, g_agc_max_gain = 0.0f;     // --agc: every pair's target RMS (0: not given); --agc-max-gain (0: not given)
 static bool g_dtmf = false;                            // --dtmf: detection on every pair
 static float g_dtmf_on_frames = 0.0f;                  // --dtmf-on-frames (0: not given)
@@ -205,6 +214,13 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
         return bad(std::string("pn_rate_set_stream_mix_gains: ") + pn_last_error());
     }
     if (g_plc && pn_rate_set_plc(rt, 1)) return bad(std::string("pn_rate_set_plc: ") + pn_last_error());
+    if (!g_dtx.empty()) {                                 // comfort noise, and every slot's SID, once (a setting: slot resets and rate changes keep it)
+      if (pn_rate_set_cng(rt, 1)) return bad(std::string("pn_rate_set_cng: ") + pn_last_error());
+      std::vector<int32_t> all(B);
+      std::vector<uint8_t> sids((size_t)B * PN_CNG_SID_BYTES);
+      for (int s = 0; s < B; s++) { all[s] = s; memcpy(&sids[(size_t)s * PN_CNG_SID_BYTES], g_sid, PN_CNG_SID_BYTES); }
+      if (g_sid_given && pn_rate_set_stream_sid(rt, all.data(), B, sids.data(), PN_CNG_SID_BYTES)) return bad(std::string("pn_rate_set_stream_sid: ") + pn_last_error());
+    }
     if (g_agc > 0.0f) {                                   // every slot's target, once (a setting: slot resets and rate changes keep it)
       std::vector<int32_t> all(B);
       std::vector<float> targets(B, g_agc);
@@ -347,11 +363,12 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
   };
   std::vector<int32_t> restart, restart_rates, live;   // live (--conference): the slots whose pair still has input, this frame's id list
   std::vector<int32_t> lost;                           // --lose: the slots whose pair loses this frame
+  std::vector<int32_t> silent;                         // --dtx: the slots whose pair is silent this frame
   int n_alive = B;
   long t = 0;
   for (;; t++) {
     Slot &sl = slot[t % 3];
-    restart.clear(); restart_rates.clear(); live.clear(); lost.clear();
+    restart.clear(); restart_rates.clear(); live.clear(); lost.clear(); silent.clear();
     for (int s = 0; s < B; s++) {
       char *x = sl.in + (size_t)s * FS * SW;
       sl.file[s] = NULL; sl.skip[s] = 0; sl.last[s] = 0;
@@ -378,6 +395,8 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
       if (fin[s]) {                                    // the frame was read, so the files stay aligned; lost: its samples never reach the device's kernels
         for (const LoseRange &lr : g_lose)
           if (lr.pair == sh->first + cur_pair[s] && pair_frame[s] >= lr.f0 && pair_frame[s] <= lr.f1) { lost.push_back(s); break; }
+        for (const LoseRange &lr : g_dtx)              // silent: likewise read and discarded; its row is comfort noise
+          if (lr.pair == sh->first + cur_pair[s] && pair_frame[s] >= lr.f0 && pair_frame[s] <= lr.f1) { silent.push_back(s); break; }
         pair_frame[s]++;
       }
     }
@@ -390,6 +409,7 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
                                            : pn_rate_reset_streams(rt, restart.data(), (int)restart.size()))) ||
                              set_limit(cx, restart.data(), (int)restart.size()))) return fail(5, pn_last_error());
     if (!lost.empty() && pn_rate_set_lost(rt, lost.data(), (int)lost.size())) return fail(5, pn_last_error());
+    if (!silent.empty() && pn_rate_set_silent(rt, silent.data(), (int)silent.size())) return fail(5, pn_last_error());
     if (g_report && pn_host_next_report(cx, sl.rep)) return fail(5, pn_last_error());
     // --rate, --rates: the converter's frame through the same pipeline
     // --conference: only the pairs that still have input advance, so an ended one is no member of this frame's mix
@@ -422,7 +442,7 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
 
 // the usage text, for a command line without pairs and for a rate no converter takes.  Returns the exit status, 1.
 static int usage(const char *argv0) {
-  fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N] [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--plc [--lose P:F0-F1,P:F,..]] [--agc RMS [--agc-max-gain G]] [--limiter CEIL [--limiter-hold H]] [--dtmf [--dtmf-on-frames N]] [--dtmf-clamp [--dtmf-guard PRE,POST]] [--migrate-at F] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv0);
+  fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N] [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--plc [--lose P:F0-F1,P:F,..]] [--dtx P:F0-F1,P:F,.. [--sid L[:N1:..:NM]]] [--agc RMS [--agc-max-gain G]] [--limiter CEIL [--limiter-hold H]] [--dtmf [--dtmf-on-frames N]] [--dtmf-clamp [--dtmf-guard PRE,POST]] [--migrate-at F] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv0);
   return 1;
 }
 
@@ -495,8 +515,9 @@ int main(int argc, char **argv) {
       }
     }
     else if (!strcmp(argv[ai], "--plc")) g_plc = true;               // packet-loss concealment on the converter (pn_rate_set_plc)
-    else if (!strcmp(argv[ai], "--lose") && ai + 1 < argc) {        // pair:frame or pair:first-last, lost frames (pn_rate_set_lost)
-      const char *v = argv[++ai];
+    else if ((!strcmp(argv[ai], "--lose") || !strcmp(argv[ai], "--dtx")) && ai + 1 < argc) {   // pair:frame or pair:first-last: lost frames (pn_rate_set_lost), silent frames (pn_rate_set_silent)
+      const char *opt = argv[ai], *v = argv[++ai];
+      std::vector<LoseRange> &list = !strcmp(opt, "--lose") ? g_lose : g_dtx;
       for (const char *q = v; ; ) {
         char *end = NULL;
         LoseRange lr;
@@ -504,11 +525,30 @@ int main(int argc, char **argv) {
         bool ok = end != q && *end == ':' && lr.pair >= 0;
         if (ok) { q = end + 1; lr.f0 = lr.f1 = strtol(q, &end, 10); ok = end != q && lr.f0 >= 0; }
         if (ok && *end == '-') { q = end + 1; lr.f1 = strtol(q, &end, 10); ok = end != q && lr.f1 >= lr.f0; }
-        if (!ok || (*end && *end != ',')) { fprintf(stderr, "--lose: expected a comma-separated list of pair:frame or pair:first-last, got '%s'\n", v); return 1; }
-        g_lose.push_back(lr);
+        if (!ok || (*end && *end != ',')) { fprintf(stderr, "%s: expected a comma-separated list of pair:frame or pair:first-last, got '%s'\n", opt, v); return 1; }
+        list.push_back(lr);
         if (!*end) break;
         q = end + 1;
       }
+    }
+    else if (!strcmp(argv[ai], "--sid") && ai + 1 < argc) {         // L[:N1:..:NM]: every pair's silence descriptor (pn_rate_set_stream_sid)
+      const char *v = argv[++ai];
+      std::vector<long> f;
+      for (const char *q = v; ; ) {
+        char *end = NULL;
+        const long x = strtol(q, &end, 10);
+        if (end == q || (*end && *end != ':') || x < 0 || x > 255) { fprintf(stderr, "--sid: expected L[:N1:..:NM], whole numbers in [0, 255], got '%s'\n", v); return 1; }
+        f.push_back(x);
+        if (!*end) break;
+        q = end + 1;
+      }
+      if (f.size() > 1 + PN_CNG_MAX_ORDER) { fprintf(stderr, "--sid: %d reflection coefficients, at most %d\n", (int)f.size() - 1, PN_CNG_MAX_ORDER); return 1; }
+      memset(g_sid, 0, sizeof g_sid);
+      g_sid[0] = (uint8_t)(f.size() - 1);
+      for (size_t i = 0; i < f.size(); i++) g_sid[1 + i] = (uint8_t)f[i];
+      float g, k[PN_CNG_MAX_ORDER]; int32_t M;
+      if (pn_cng_sid_decode(g_sid, &g, k, &M)) { fprintf(stderr, "--sid: %s\n", pn_last_error()); return 1; }
+      g_sid_given = true;
     }
     else if (!strcmp(argv[ai], "--agc") && ai + 1 < argc) {         // every pair's target RMS, linear (pn_rate_set_stream_agc_targets)
       const char *v = argv[++ai];
@@ -607,6 +647,9 @@ int main(int argc, char **argv) {
   if (!g_lose.empty() && !g_plc) { fprintf(stderr, "--lose needs --plc: a lost frame is filled by the packet-loss concealment\n"); return 1; }
   for (const LoseRange &lr : g_lose)
     if (lr.pair >= B) { fprintf(stderr, "--lose: pair %ld of %d pairs (pairs count from 0)\n", lr.pair, B); return 1; }
+  if (g_sid_given && g_dtx.empty()) { fprintf(stderr, "--sid needs --dtx: it describes the comfort noise of the silent frames\n"); return 1; }
+  for (const LoseRange &lr : g_dtx)
+    if (lr.pair >= B) { fprintf(stderr, "--dtx: pair %ld of %d pairs (pairs count from 0)\n", lr.pair, B); return 1; }
   if (g_agc_max_gain > 0.0f && !(g_agc > 0.0f)) { fprintf(stderr, "--agc-max-gain needs --agc: it is a parameter of the level control\n"); return 1; }
   if (g_limiter_hold >= 0.0f && !(g_limiter > 0.0f)) { fprintf(stderr, "--limiter-hold needs --limiter: it is a parameter of the output limiter\n"); return 1; }
   if (g_dtmf_on_frames > 0.0f && !g_dtmf) { fprintf(stderr, "--dtmf-on-frames needs --dtmf: it is a parameter of the DTMF detector\n"); return 1; }
@@ -620,7 +663,7 @@ int main(int argc, char **argv) {
     if (g_dtmf_guard[0] >= 0) { cp[PN_DTMF_CLAMP_PRE] = g_dtmf_guard[0]; cp[PN_DTMF_CLAMP_POST] = g_dtmf_guard[1]; }
     if (pn_dtmf_clamp_params_check(cp, dp)) { fprintf(stderr, "--dtmf-clamp: %s\n", pn_last_error()); return 1; }
   }
-  if ((g_plc || g_agc > 0.0f || g_limiter > 0.0f || g_dtmf) && !g_rate && g_rates.empty()) g_rates.assign(B, 48000);        // on its own: a mixed converter of all 48000
+  if ((g_plc || !g_dtx.empty() || g_agc > 0.0f || g_limiter > 0.0f || g_dtmf) && !g_rate && g_rates.empty()) g_rates.assign(B, 48000);        // on its own: a mixed converter of all 48000
   if (g_migrate_at >= 0) {
     if (devices.size() > 1) { fprintf(stderr, "--migrate-at takes one device: the slots move between two contexts of one device\n"); return 1; }
     if (!g_rate && g_rates.empty()) { fprintf(stderr, "--migrate-at needs a converter (--rate or --rates): it moves the converter's records with the engine's\n"); return 1; }

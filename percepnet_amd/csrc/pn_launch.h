@@ -116,6 +116,13 @@ void pn_launch_rate_conf_rows(hipStream_t st, const int *d_touched, const int *d
 // [n_streams][1920], q [n_streams][720], meta [n_streams][4] words; d_report [n_streams][4] words or NULL
 void pn_launch_rate_plc(hipStream_t st, int n_rows, const int *d_ids, const uint32_t *d_lost, uint32_t tick, float *x48, float *hist, float *q,
                         void *meta, void *d_report);
+// comfort noise (pn_rate_cng.hip; the rule pn_cng_rules.h): the rows of the DISTINCT streams d_ids[0..n_rows), never NULL, each of its
+// stream's own n_s samples (d_factors [n_streams], or NULL and ns for everybody), into out [n_streams][stride], stride >= n_s.  d_cont
+// [n_rows] words: != 0 = the row continues a run.  d_sid [n_streams][16] words: the decoded SIDs (k[12], g, M, 0, 0).  State
+// [n_streams][16] words; d_report [n_streams][4] words or NULL.  cng_sids: row i of d_rows [n][16] becomes the SID of stream d_ids[i]
+void pn_launch_rate_cng(hipStream_t st, int n_rows, const int *d_ids, const int *d_cont, const int *d_factors, int ns, uint32_t seed, const void *d_sid, void *state,
+                        float *out, int stride, void *d_report);
+void pn_launch_rate_cng_sids(hipStream_t st, const int *d_ids, const int *d_rows, int n, void *d_sid);
 // automatic level control (pn_rate_agc.hip; the rule pn_agc_rules.h): rows d_ids[0..n_rows) or, with d_ids == NULL, streams 0..n_rows of
 // y48 [.][480], in place.  d_targets [n_streams]: +0.0 = the stream is not levelled; a stream whose d_lost word equals tick was concealed
 // this frame (d_lost == NULL: nobody); params: the converter's PN_AGC_N_PARAMS floats on the HOST, passed by value.  State [n_streams][4]

@@ -19,7 +19,7 @@
 #include <vector>
 
 // the stages: the timed kernels (pn_rate_kernel_time) and their reports
-enum { RF_UP, RF_DOWN, RF_MIX, RF_PLC, RF_AGC, RF_LIM, RF_DTMF, RF_CLAMP, RF_COUNT };
+enum { RF_UP, RF_DOWN, RF_MIX, RF_PLC, RF_AGC, RF_LIM, RF_DTMF, RF_CLAMP, RF_CNG, RF_COUNT };
 struct RateStage { const char *family; int report_words; const char *report_off; };   // report_words per stream, 0: the stage has no report
 static const RateStage kRateStage[RF_COUNT] = {
     {"rate_up", 0, NULL},
@@ -30,6 +30,7 @@ static const RateStage kRateStage[RF_COUNT] = {
     {"rate_lim", PN_LIM_REPORT_WORDS, "the limiter report is off (pn_rate_set_limiter_report)"},
     {"rate_dtmf", PN_DTMF_REPORT_WORDS, "the DTMF report is off (pn_rate_set_dtmf_report)"},
     {"rate_clamp", PN_DTMF_CLAMP_REPORT_WORDS, "the DTMF removal report is off (pn_rate_set_dtmf_clamp_report)"},
+    {"rate_cng", PN_CNG_REPORT_WORDS, "the comfort-noise report is off (pn_rate_set_cng_report)"},
 };
 enum { RATE_PIECE = 16384 };    // ids a setting stages through the id ring at a time
 
@@ -39,6 +40,7 @@ struct pn_rate {
   size_t bytes;
   float *taps_up, *taps_down;   // [2D + 1] h, g.  Mixed: the tables of L = 6, 3, 2 one behind the other, and behind them the g of 32000
   void *st[PN_RS_COUNT] = {};   // the per-stream state, [B][pn_rate_state_words] each (pn_rate_layout.h): NULL until the owning stage is first used
+  void *st2[PN_RS2_COUNT] = {}; // ... and that of the second table: the stages in front of the up-conversion
   void *d_report[RF_COUNT] = {};   // [B][kRateStage[].report_words] words: allocated by the first enabling of the report
   bool report[RF_COUNT] = {};      // the report switches
   float *x48, *y48;             // [B][480]: the engine's input and output rows of a whole frame
@@ -113,6 +115,20 @@ struct pn_rate {
   std::vector<uint8_t> clamp_sw;                      // [B], 0
   int clamp_on = 0;                                   // streams whose switch is on
   int *d_clamp_on = NULL;                             // [B] words
+  // comfort noise (pn_rate_set_cng; the rule pn_cng_rules.h): SETTINGS — the switch, the seed (an argument of every launch), a SID per
+  // stream as last set (host, PN_CNG_SID_BYTES each, from creation on) and decoded on the device, written in stream order through the id
+  // ring — the state, 16 words per stream (st2[PN_RS2_CNG]), and the rows the kernel writes at the streams' own rates, strided like an
+  // input row.  The device side exists from the first enable on.  Marks (pn_rate_set_silent) live on the HOST alone: a frame compacts
+  // them into the list the kernel runs over, and consumes them.  cng_last: the tick of the frame that last generated a stream's row, 0:
+  // none — a row CONTINUES a run when that is the tick before this frame's.  Nobody marked: a frame launches nothing of it
+  bool cng = false;
+  uint32_t cng_seed = PN_CNG_DEFAULT_SEED, cng_tick = 1;
+  std::vector<uint8_t> sids;                          // [B][PN_CNG_SID_BYTES]
+  uint32_t *d_cng_sid = NULL;                         // [B][PN_CNG_PARAM_WORDS]
+  float *cng_rows = NULL;                             // [B][n]
+  std::vector<uint8_t> silent_mark;                   // [B]
+  std::vector<int32_t> silent_ids, gen_ids, gen_cont; // the marked streams; a frame's generated streams and their "continues" words
+  std::vector<uint32_t> cng_last;                     // [B]
   std::vector<void *> allocs;
   // timing of the kernels (pn_rate_set_profiling): HIP events around their launches, like the context's families but owned
   // here; while it is off no event exists and none is recorded
@@ -198,6 +214,20 @@ extern "C" uint32_t pn_dtmf_event_payload(int digit, int end, int volume, uint32
   return pn_dtmf_event_payload_hd((uint32_t)digit, end != 0, (uint32_t)volume, dur, (uint32_t)ts_per_frame);
 }
 extern "C" int pn_rate_limiter_ceilings_check(const float *ceilings, int n) { return pn_lim_ceilings_list_check(ceilings, n); }
+extern "C" int pn_cng_sid_decode(const uint8_t *sid14, float *g, float *k12, int32_t *M) {
+  PnCngSid d;
+  if (!g || !k12 || !M) { pn_set_error("NULL argument"); return -1; }
+  if (pn_cng_sid_decode_host(sid14, &d)) return -1;
+  *g = d.g; *M = d.M; memcpy(k12, d.k, sizeof d.k);
+  return 0;
+}
+extern "C" float pn_cng_level(int L) { if (L < 0 || L > 127) { pn_set_error("SID level %d: a level in [0, 127] -dBov", L); return NAN; } return pn_kCngLevel[L]; }
+extern "C" int pn_cng_frame(const uint8_t *sid14, uint32_t *state16, uint32_t seed, int slot, int cont, int n, float *row, uint32_t *report4) {
+  PnCngSid d;
+  if (slot < 0) { pn_set_error("stream slot %d", slot); return -1; }
+  if (pn_cng_sid_decode_host(sid14, &d)) return -1;
+  return pn_cng_frame_host(&d, state16, pn_cng_key(seed, (uint32_t)slot), cont, n, row, report4);
+}
 
 // ---- the shared routines: allocation, the state table's walks, reports, per-stream settings ----------------------------------------
 // (callers are on the context's device.)  Device memory of the converter; p is written on success only, which is what lets a stage
@@ -220,10 +250,19 @@ static int state_alloc(pn_rate *r, int stage, void *p[PN_RS_COUNT]) {
 static void state_commit(pn_rate *r, int stage, void *const p[PN_RS_COUNT]) {
   for (int e = 0; e < PN_RS_COUNT; e++) if (pn_kRateState[e].stage == stage) r->st[e] = p[e];
 }
+// the host's side of a cleared comfort-noise state: the streams (ids == NULL: all) have generated no row, so their next one starts a run
+static void cng_forget(pn_rate *r, const int32_t *ids, int n) {
+  if (r->cng_last.empty()) return;
+  if (!ids) std::fill(r->cng_last.begin(), r->cng_last.end(), 0u);
+  else for (int i = 0; i < n; i++) r->cng_last[ids[i]] = 0u;
+}
 // The two zeroing rules.  What `event` (of `stage`, where it is a stage's event) clears goes to zero for every stream ...
 static int state_clear_all(pn_rate *r, unsigned event, int stage = -1) {
   for (int e = 0; e < PN_RS_COUNT; e++)
     if (pn_rate_state_cleared(e, event, stage) && r->st[e]) PN_HIP_CHECK(hipMemsetAsync(r->st[e], 0, state_bytes(r, e), r->c->stream));
+  for (int e = 0; e < PN_RS2_COUNT; e++)
+    if (pn_rate_state2_cleared(e, event, stage) && r->st2[e]) PN_HIP_CHECK(hipMemsetAsync(r->st2[e], 0, (size_t)r->c->B * pn_kRateState2[e].words * 4, r->c->stream));
+  if (pn_rate_state2_cleared(PN_RS2_CNG, event, stage)) cng_forget(r, NULL, 0);
   return 0;
 }
 // ... or for the staged streams d[0..n) (nothing where the buffer does not exist: pn_launch_zero_rows)
@@ -231,6 +270,10 @@ static void state_clear_rows(pn_rate *r, unsigned event, const int *d, int n, in
   for (int e = 0; e < PN_RS_COUNT; e++) {
     const int w = pn_rate_state_words(e, r->td);
     if (pn_rate_state_cleared(e, event, stage)) pn_launch_zero_rows(r->c->stream, r->st[e], w, w, 1, 0, d, n);
+  }
+  for (int e = 0; e < PN_RS2_COUNT; e++) {
+    const int w = pn_kRateState2[e].words;
+    if (pn_rate_state2_cleared(e, event, stage)) pn_launch_zero_rows(r->c->stream, r->st2[e], w, w, 1, 0, d, n);
   }
 }
 // a stage switched on for streams that were off: they start from the fresh state.  Staged in pieces, in front of the switch write
@@ -355,6 +398,8 @@ static pn_rate *rate_create(pn_ctx *c, int rate_hz, int f, const int32_t *rates_
   r->lim_ceilings.assign(B, 0.0f); pn_lim_default_params_host(r->lim_params);
   r->dtmf_sw.assign(B, 0); pn_dtmf_default_params_host(r->dtmf_params);
   r->clamp_sw.assign(B, 0); pn_dtmf_clamp_default_params_host(r->clamp_params);
+  r->sids.assign(B * PN_CNG_SID_BYTES, 0);
+  for (size_t s = 0; s < B; s++) pn_cng_default_sid(&r->sids[s * PN_CNG_SID_BYTES]);
   static const int kF[4] = {6, 3, 2, PN_RATE_F_3_2};   // (the order of pn_rate.hip rt_taps_offset; the h of 32000 is the table of 3 and is not staged twice)
   std::vector<float> h[2];
   std::vector<int> fs(B);
@@ -409,7 +454,7 @@ extern "C" int pn_rate_set_stream_rates(pn_rate *r, const int32_t *ids, int n, c
   const int *d = stage_ids(r->c, ids, n, f.data(), n);
   if (!d) return -1;
   pn_launch_rate_set_factors(r->c->stream, d, d + ((n + 3) & ~3), n, r->factors);
-  state_clear_rows(r, PN_RE_RATE, d, n);
+  state_clear_rows(r, PN_RE_RATE, d, n); cng_forget(r, ids, n);
   PN_HIP_CHECK(hipGetLastError());
   for (int i = 0; i < n; i++) r->rates[ids[i]] = rates_hz[i];
   return 0;
@@ -571,6 +616,109 @@ extern "C" int pn_rate_set_plc_report(pn_rate *r, int enable) { return rate_set_
 extern "C" int pn_rate_read_plc_report(pn_rate *r, void *h_report) { return rate_report_copy(r, RF_PLC, h_report, hipMemcpyDeviceToHost); }
 extern "C" int pn_rate_read_plc_report_dev(pn_rate *r, void *d_report) { return rate_report_copy(r, RF_PLC, d_report, hipMemcpyDeviceToDevice); }
 
+// ---- comfort noise (include/percepnet_hip.h; the rule pn_cng_rules.h; the kernel pn_rate_cng.hip) ----------------------------------
+static void cng_drop_marks(pn_rate *r) {
+  for (int32_t s : r->silent_ids) r->silent_mark[s] = 0;
+  r->silent_ids.clear();
+  if (++r->cng_tick == 0) { cng_forget(r, NULL, 0); r->cng_tick = 1; }   // (2^32 frames on: no stale tick may meet the new one; every run starts again)
+}
+static void cng_param_row(const PnCngSid &d, uint32_t *row) {   // a decoded SID as the kernel reads it
+  memset(row, 0, PN_CNG_PARAM_WORDS * 4);
+  memcpy(row, d.k, sizeof d.k); memcpy(row + PN_CNG_P_G, &d.g, 4); row[PN_CNG_P_M] = (uint32_t)d.M;
+}
+extern "C" int pn_rate_set_cng(pn_rate *r, int enable) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  PN_ON_DEVICE(r->c);
+  if (enable && !r->d_cng_sid) {
+    pn_ctx *c = r->c;
+    const size_t B = (size_t)c->B;
+    void *st = NULL; uint32_t *sid = NULL; float *rows = NULL;
+    if (rate_alloc(r, st, B * PN_CNG_STATE_WORDS * 4, true) || rate_alloc(r, sid, B * PN_CNG_PARAM_WORDS * 4, false) || rate_alloc(r, rows, B * r->n * 4, true)) return -1;
+    // the SIDs as set so far (the defaults, or what pn_rate_set_stream_sid has kept on the host), decoded; a synchronous copy: the source is a local
+    std::vector<uint32_t> tab(B * PN_CNG_PARAM_WORDS);
+    for (size_t s = 0; s < B; s++) {
+      PnCngSid d;
+      if (pn_cng_sid_decode_host(&r->sids[s * PN_CNG_SID_BYTES], &d)) return -1;
+      cng_param_row(d, &tab[s * PN_CNG_PARAM_WORDS]);
+    }
+    PN_HIP_CHECK(hipMemcpyAsync(sid, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
+    PN_HIP_CHECK(hipStreamSynchronize(c->stream));
+    // room in the id ring for the longest lists a frame stages — "every stream but the silent ones", and every stream with its
+    // "continues" word — so that no frame grows the ring: the identity list goes through it once, read by nobody
+    r->gen_ids.resize(B); r->gen_cont.assign(B, 0);
+    for (size_t s = 0; s < B; s++) r->gen_ids[s] = (int32_t)s;
+    if (!stage_ids(c, r->gen_ids.data(), (int)B, r->gen_cont.data(), (int)B)) return -1;
+    r->gen_ids.clear(); r->gen_cont.clear(); r->up_ids.reserve(B);
+    r->silent_mark.assign(B, 0); r->silent_ids.reserve(B); r->cng_last.assign(B, 0u);
+    r->st2[PN_RS2_CNG] = st; r->cng_rows = rows; r->cng_tick = 1; r->d_cng_sid = sid;
+  } else if (enable && !r->cng) {
+    // on again after a pause: every stream's noise starts again, counts included, like pn_rate_reset
+    if (state_clear_all(r, PN_RE_AGAIN, PN_RST_CNG)) return -1;
+  }
+  if (!enable && r->cng) cng_drop_marks(r);
+  r->cng = enable != 0;
+  return 0;
+}
+// the seed travels as an argument of every launch, so a change is ordered like one
+extern "C" int pn_rate_set_cng_seed(pn_rate *r, uint32_t seed) { if (!r) { pn_set_error("NULL argument"); return -1; } r->cng_seed = seed; return 0; }
+extern "C" int pn_rate_get_cng_seed(const pn_rate *r, uint32_t *seed) { if (!r || !seed) { pn_set_error("NULL argument"); return -1; } *seed = r->cng_seed; return 0; }
+// The SIDs of the listed streams, a per-stream setting ordered like the law: decoded on the host, the ids and the decoded rows go through
+// the context's id ring in bounded pieces, each followed by the launch that reads it.  While the device side does not exist the host's
+// copy is all there is; the first enable decodes it.  No state is touched: a run goes on under the new SID, its gain ramping to the new g
+extern "C" int pn_rate_set_stream_sid(pn_rate *r, const int32_t *ids, int n, const uint8_t *sids, int stride) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (pn_cng_sids_set_check(r->c->B, ids, n, sids, stride)) return -1;
+  if (n == 0) return 0;
+  if (r->d_cng_sid) {
+    PN_ON_DEVICE(r->c);
+    enum { PIECE = RATE_PIECE / PN_CNG_PARAM_WORDS };
+    std::vector<uint32_t> rows((size_t)(n < PIECE ? n : PIECE) * PN_CNG_PARAM_WORDS);
+    for (int at = 0; at < n; at += PIECE) {
+      const int m = n - at < PIECE ? n - at : PIECE;
+      for (int i = 0; i < m; i++) {
+        PnCngSid d;
+        if (pn_cng_sid_decode_host(sids + (size_t)(at + i) * stride, &d)) return -1;
+        cng_param_row(d, &rows[(size_t)i * PN_CNG_PARAM_WORDS]);
+      }
+      const int *d = stage_ids(r->c, ids + at, m, rows.data(), m * PN_CNG_PARAM_WORDS);
+      if (!d) return -1;
+      pn_launch_rate_cng_sids(r->c->stream, d, d + ((m + 3) & ~3), m, r->d_cng_sid);
+      PN_HIP_CHECK(hipGetLastError());
+    }
+  }
+  // the host's copy behind the last piece.  Every refusal stands in front of the first, so only a failure of the device itself gets
+  // between two pieces: the call then returns -1 with the earlier pieces written on the device and the host's copy as it was
+  for (int i = 0; i < n; i++) pn_cng_sid_store(sids + (size_t)i * stride, &r->sids[(size_t)ids[i] * PN_CNG_SID_BYTES]);
+  return 0;
+}
+extern "C" int pn_rate_get_stream_sid(const pn_rate *r, uint8_t *h_sids) {
+  if (!r || !h_sids) { pn_set_error("NULL argument"); return -1; }
+  memcpy(h_sids, r->sids.data(), r->sids.size());
+  return 0;
+}
+// Marks for the next frame, with the lifetime of pn_rate_set_lost's.  They live on the host alone — a frame compacts them into the list
+// its kernel runs over — so the call launches nothing and is ordered, like every call, by where it stands between two submits
+extern "C" int pn_rate_set_silent(pn_rate *r, const int32_t *ids, int n) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (!r->cng) { pn_set_error("comfort noise is off (pn_rate_set_cng)"); return -1; }
+  if (pn_ids_check(r->c->B, ids, n, true)) return -1;
+  for (int i = 0; i < n; i++)
+    if (!r->silent_mark[ids[i]]) { r->silent_mark[ids[i]] = 1; r->silent_ids.push_back(ids[i]); }
+  return 0;
+}
+extern "C" int pn_rate_set_cng_report(pn_rate *r, int enable) { return rate_set_report(r, RF_CNG, enable); }
+extern "C" int pn_rate_read_cng_report(pn_rate *r, void *h_report) { return rate_report_copy(r, RF_CNG, h_report, hipMemcpyDeviceToHost); }
+extern "C" int pn_rate_read_cng_report_dev(pn_rate *r, void *d_report) { return rate_report_copy(r, RF_CNG, d_report, hipMemcpyDeviceToDevice); }
+extern "C" int pn_rate_debug_cng_state(pn_rate *r, void *h_state) {
+  if (!r || !h_state) { pn_set_error("NULL argument"); return -1; }
+  const size_t bytes = (size_t)r->c->B * PN_CNG_STATE_WORDS * 4;
+  if (!r->st2[PN_RS2_CNG]) { memset(h_state, 0, bytes); return 0; }
+  PN_ON_DEVICE(r->c);
+  PN_HIP_CHECK(hipMemcpyAsync(h_state, r->st2[PN_RS2_CNG], bytes, hipMemcpyDeviceToHost, r->c->stream));
+  PN_HIP_CHECK(hipStreamSynchronize(r->c->stream));
+  return 0;
+}
+
 // ---- automatic level control (include/percepnet_hip.h; the rule pn_agc_rules.h; the kernel pn_rate_agc.hip) -----------------------
 extern "C" int pn_rate_set_agc(pn_rate *r, int enable) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
@@ -727,7 +875,7 @@ extern "C" int pn_rate_reset_streams(pn_rate *r, const int32_t *ids, int n) {
   PN_ON_DEVICE(r->c);
   const int *d = stage_ids(r->c, ids, n);
   if (!d) return -1;
-  state_clear_rows(r, PN_RE_RESET_STREAMS, d, n);
+  state_clear_rows(r, PN_RE_RESET_STREAMS, d, n); cng_forget(r, ids, n);
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -811,6 +959,23 @@ static int rate_clamp(pn_rate *r, float *d_y48, const RateRows &rows, bool det) 
   return rate_timed(r, RF_CLAMP, [&] { pn_launch_rate_dtmf_clamp(r->c->stream, rows.n, rows.d_ids, r->d_clamp_on, r->clamp_params, det ? r->d_report[RF_DTMF] : NULL, d_y48,
                                                                  r->st[PN_RS_CLAMP], rate_report(r, RF_CLAMP)); });
 }
+// comfort noise for the streams gen (host, distinct): their rows at their own rates into cng_rows, then the unchanged up-conversion, float,
+// from there into d_x48 — both over ONE staged list, which carries every stream's "continues" word behind the ids
+static int rate_cng(pn_rate *r, float *d_x48, const std::vector<int32_t> &gen) {
+  const int n = (int)gen.size();
+  r->gen_cont.resize(n);
+  for (int i = 0; i < n; i++) {
+    uint32_t &last = r->cng_last[gen[i]];
+    r->gen_cont[i] = last != 0u && last == r->cng_tick - 1u;
+    last = r->cng_tick;
+  }
+  const int *d = stage_ids(r->c, gen.data(), n, r->gen_cont.data(), n);
+  if (!d) return -1;
+  if (rate_timed(r, RF_CNG, [&] { pn_launch_rate_cng(r->c->stream, n, d, d + ((n + 3) & ~3), r->mixed ? r->factors : NULL, r->n, r->cng_seed, r->d_cng_sid, r->st2[PN_RS2_CNG],
+                                                     r->cng_rows, r->n, rate_report(r, RF_CNG)); })) return -1;
+  const RateRows rows = {d, n};
+  return rate_up(r, r->cng_rows, PN_FMT_F32, d_x48, rows);
+}
 // The stand-alone stage calls.  Their prologue: the converter, `off` (the stage's switch is off: its message), the rows' alignment —
 // then RATE_STAGE_ROWS: the context's device for the rest of the call, and the rows
 static int rate_stage_check(const pn_rate *r, const void *a, const void *b, const char *off = NULL) {
@@ -868,9 +1033,21 @@ extern "C" int pn_rate_dtmf_clamp_f32(pn_rate *r, float *d_y48, const int32_t *i
   RATE_STAGE_ROWS(r, ids, n_ids);
   return clamp_buffers(r) ? -1 : rate_clamp(r, d_y48, rows, true);
 }
+// comfort noise on its own: every listed stream's row is generated and up-converted into d_x48, marked or not; like a frame it moves the
+// tick on and drops the marks
+extern "C" int pn_rate_cng_f32(pn_rate *r, float *d_x48, const int32_t *ids, int n_ids) {
+  if (rate_stage_check(r, d_x48, d_x48, r && !r->cng ? "comfort noise is off (pn_rate_set_cng)" : NULL)) return -1;
+  PN_ON_DEVICE(r->c);
+  if (ids && pn_ids_check(r->c->B, ids, n_ids, true)) return -1;
+  r->gen_ids.clear();
+  if (ids) r->gen_ids.assign(ids, ids + n_ids); else for (int s = 0; s < r->c->B; s++) r->gen_ids.push_back(s);
+  const int rc = r->gen_ids.empty() ? 0 : rate_cng(r, d_x48, r->gen_ids);
+  cng_drop_marks(r);
+  return rc;
+}
 
 // ---- one whole frame -----------------------------------------------------------------------------------------------------------
-// up into x48, while packet-loss concealment is on the concealer in place on x48, the engine's float frame from x48 into y48 (all streams, or the listed ones through the context's own active
+// up into x48 — for the streams marked silent while comfort noise is on, from the rows its kernel writes —, while packet-loss concealment is on the concealer in place on x48, the engine's float frame from x48 into y48 (all streams, or the listed ones through the context's own active
 // set), while automatic level control is on and a stream has a target the level control in place on y48, down from y48 — or, while a stream is in a conference, the mix from y48 into o48 and down from o48 — and in front of the down-conversion, while a stream has a ceiling, the output limiter in place on the rows it reads.  A frame the engine refuses returns -1 with its error kept; the up kernel has then advanced its tails
 // and the down kernel has not, which is why the header asks for a reset of both objects before reuse.
 // rate_frame: the launches alone — the caller is on the context's device and has checked the rows and, when active, the list
@@ -878,21 +1055,30 @@ extern "C" int pn_rate_dtmf_clamp_f32(pn_rate *r, float *d_y48, const int32_t *i
 static int rate_frame(pn_rate *r, const void *d_in, void *d_out, float *d_gr, int fmt, bool active, const int32_t *ids, int n) {
   pn_ctx *c = r->c;
   RateRows rows = {NULL, c->B};
-  // marked streams: the up-conversion runs over "advancing minus lost" — its own staged list, in front of the frame's — so a lost
-  // stream's input row is never read and its tail stays.  Nobody marked, or no marked stream advancing: the launch of always
+  // marked streams: the up-conversion runs over "advancing minus lost minus silent" — its own staged list, in front of the frame's — so a
+  // lost or silent stream's input row is never read, and a lost stream's tail stays.  The advancing silent streams that are not lost
+  // (lost wins) get their rows from the comfort-noise kernel and their own up-conversion, float, behind the others'.  Nobody marked, or
+  // no marked stream advancing: the launch of always
   bool up_done = false;
-  if (r->plc && !r->lost_ids.empty()) {
-    r->up_ids.clear();
-    if (active) { for (int i = 0; i < n; i++) if (!r->lost_mark[ids[i]]) r->up_ids.push_back(ids[i]); }
-    else for (int s = 0; s < c->B; s++) if (!r->lost_mark[s]) r->up_ids.push_back(s);
+  const bool any_lost = r->plc && !r->lost_ids.empty(), any_silent = r->cng && !r->silent_ids.empty();
+  if (any_lost || any_silent) {
+    r->up_ids.clear(); r->gen_ids.clear();
+    auto sort = [&](int32_t s) {
+      if (any_lost && r->lost_mark[s]) return;
+      if (any_silent && r->silent_mark[s]) r->gen_ids.push_back(s); else r->up_ids.push_back(s);
+    };
+    if (active) for (int i = 0; i < n; i++) sort(ids[i]);
+    else for (int s = 0; s < c->B; s++) sort(s);
     const int nu = (int)r->up_ids.size();
     if (nu != (active ? n : c->B)) {
       RateRows up = {NULL, nu};
       if (nu > 0 && !(up.d_ids = stage_ids(c, r->up_ids.data(), nu))) return -1;
       if (nu > 0 && rate_up(r, d_in, fmt, r->x48, up)) return -1;
+      if (!r->gen_ids.empty() && rate_cng(r, r->x48, r->gen_ids)) return -1;
       up_done = true;
     }
   }
+  if (r->cng) cng_drop_marks(r);                      // the frame consumes the silent marks: the tick moves on
   if (active) {                                      // (an empty list is legal, as for pn_process_*_active: nobody advances)
     rows.n = n;
     if (n > 0 && !(rows.d_ids = stage_ids(c, ids, n))) return -1;
@@ -1002,9 +1188,9 @@ extern "C" int pn_rate_submit_host_g711_active(pn_rate *r, const uint8_t *h_in, 
 // ---- timing the kernels --------------------------------------------------------------------------------------------------------
 extern "C" int pn_rate_set_profiling(pn_rate *r, int enable) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
-  if (enable && r->event_pool.size() < 1024) {        // up to eight scopes a frame (up, plc, dtmf, clamp, agc, mix, lim, down): enough for 64 frames between two reads; created outside any timed region
+  if (enable && r->event_pool.size() < 1280) {        // up to ten scopes a frame (up, cng, up, plc, dtmf, clamp, agc, mix, lim, down): enough for 64 frames between two reads; created outside any timed region
     PN_ON_DEVICE(r->c);
-    while (r->event_pool.size() < 1024) { hipEvent_t e; PN_HIP_CHECK(hipEventCreate(&e)); r->event_pool.push_back(e); }
+    while (r->event_pool.size() < 1280) { hipEvent_t e; PN_HIP_CHECK(hipEventCreate(&e)); r->event_pool.push_back(e); }
   }
   r->profiling = enable != 0;
   return 0;
@@ -1015,7 +1201,7 @@ extern "C" int pn_rate_kernel_time(pn_rate *r, const char *name, double *total_m
   if (rate_flush_events(r)) return -1;
   for (int i = 0; i < RF_COUNT; i++)
     if (!strcmp(name, kRateStage[i].family)) { if (total_ms) *total_ms = r->fam_ms[i]; if (launches) *launches = r->fam_n[i]; return 0; }
-  pn_set_error("unknown converter kernel '%s' (rate_up, rate_down, rate_mix, rate_plc, rate_agc, rate_lim, rate_dtmf, rate_clamp)", name);
+  pn_set_error("unknown converter kernel '%s' (rate_up, rate_down, rate_mix, rate_plc, rate_agc, rate_lim, rate_dtmf, rate_clamp, rate_cng)", name);
   return -1;
 }
 extern "C" int pn_rate_reset_profile(pn_rate *r) {
@@ -1054,7 +1240,7 @@ static int rate_records_host(pn_rate *r, bool import, const int32_t *ids, int n,
     const int *d_ids = stage_ids(c, ids, n);
     if (!d_ids) return -1;
     pn_launch_rate_records(c->stream, f, rate, d_ids, n, stf(r, PN_RS_TAIL_UP), stf(r, PN_RS_TAIL_DOWN), r->td, d, import ? 1 : 0);
-    if (import) state_clear_rows(r, PN_RE_IMPORT, d_ids, n);
+    if (import) { state_clear_rows(r, PN_RE_IMPORT, d_ids, n); cng_forget(r, ids, n); }
     if (hipGetLastError() != hipSuccess) { pn_set_error(import ? "record scatter launch failed" : "record gather launch failed"); return -1; }
     return 0;
   });
@@ -1082,7 +1268,7 @@ static int rate_records_dev(pn_rate *r, bool import, const int32_t *ids, int n, 
   if (!d) return -1;
   pn_launch_rate_records_dev(c->stream, d, n, r->mixed ? r->factors : NULL, r->f, stf(r, PN_RS_TAIL_UP), stf(r, PN_RS_TAIL_DOWN), r->td, d_records,
                              (int)(pn_rate_record_stride(r) / 4), d_status, import ? 1 : 0);
-  if (import) state_clear_rows(r, PN_RE_IMPORT, d, n);   // (whatever the record's status: the slot is another stream's now)
+  if (import) { state_clear_rows(r, PN_RE_IMPORT, d, n); cng_forget(r, ids, n); }   // (whatever the record's status: the slot is another stream's now)
   PN_HIP_CHECK(hipGetLastError());
   return 0;
 }
