@@ -534,7 +534,7 @@ int pn_rate_export_streams(pn_rate *r, const int32_t *ids, int n, void *d_record
 int pn_rate_import_streams(pn_rate *r, const int32_t *ids, int n, const void *d_records, int32_t *d_status);
 /* Timing of the converter's two kernels inside a frame: HIP events around their launches, like pn_ctx_set_profiling but owned by
    the converter (the context's family list does not change).  Off by default; off, no event is created or recorded.  name:
-   "rate_up" | "rate_down" | "rate_mix" (the conference mix, below) | "rate_plc" (packet-loss concealment, below) | "rate_agc" (automatic level control, below) | "rate_lim" (the output limiter, below) | "rate_dtmf" (DTMF detection, below) | "rate_clamp" (DTMF removal, below).  pn_rate_kernel_time synchronises the context's stream. */
+   "rate_up" | "rate_down" | "rate_mix" (the conference mix, below) | "rate_plc" (packet-loss concealment, below) | "rate_agc" (automatic level control, below) | "rate_lim" (the output limiter, below) | "rate_dtmf" (DTMF detection, below) | "rate_clamp" (DTMF removal, below) | "rate_cng" (comfort noise, below) | "rate_dtx" (the DTX send side, below).  pn_rate_kernel_time synchronises the context's stream. */
 int pn_rate_set_profiling(pn_rate *r, int enable);
 int pn_rate_kernel_time(pn_rate *r, const char *name, double *total_ms, int64_t *launches);
 int pn_rate_reset_profile(pn_rate *r);
@@ -907,14 +907,15 @@ int pn_rate_read_plc_report_dev(pn_rate *r, void *d_report);
    pn_rate_cng_f32(r, d_x48, ids, n_ids): the stage on its own: the row of every LISTED stream (NULL: all), marked or not, is generated
      and up-converted into its row of d_x48 [n_streams][480]; other rows are not touched.  It counts as a frame: marks are dropped.
    pn_rate_kernel_time takes "rate_cng"; the second up-conversion launch counts under "rate_up".  (With the two launches a frame can
-     now have ten timed scopes, so pn_rate_set_profiling creates 1280 events up front where it created 1024, on every converter.)
+     have ten timed scopes, eleven with the DTX send side below: pn_rate_set_profiling creates 1408 events up front, on every converter.)
    CNG report (pn_rate_set_cng_report, pn_rate_read_cng_report[_dev]; -1 while off): PN_CNG_REPORT_WORDS = 4 words per stream, written
      when the stream's row is generated (other streams' records keep what they had):
      word 0  run     consecutive generated rows including this one      word 2  g     the gain in use, float bits
      word 1  total   generated rows since the state was cleared         word 3  ctr   the sample counter behind the row
    Host only, needing no GPU: pn_cng_sid_decode (14 bytes -> g, k[12], M; -1 for a refused SID), pn_cng_level (L -> the table's rms),
      pn_cng_frame (one row of one stream: the twin of the kernel, as pn_agc_frame is; cont: the row continues a run).
-   NOT provided: the send side (VAD, the DTX decision, SID generation for outgoing streams); noise state in any record (a moved call's
+   The send side (VAD, the DTX decision, SID generation for outgoing streams) is the next section, "DTX send side".
+   NOT provided: noise state in any record (a moved call's
    noise restarts under the new slot's key); comfort noise without a converter, or in the gap behind DTMF removal; Gaussian excitation;
    any measurement of how the model treats synthetic noise, or of perceived quality. */
 #define PN_CNG_MAX_ORDER 12
@@ -936,6 +937,109 @@ int pn_rate_set_cng_report(pn_rate *r, int enable);
 int pn_rate_read_cng_report(pn_rate *r, void *h_report);
 int pn_rate_read_cng_report_dev(pn_rate *r, void *d_report);
 int pn_rate_debug_cng_state(pn_rate *r, void *h_state);                /* tests: [n_streams][16] words, synchronising */
+
+/* ---- DTX send side: VAD, the DTX decision and SIDs for outgoing streams, on the GPU ------------------------------------------------ */
+/* The section above lets a bridge HEAR an endpoint that suppresses silence; this one lets it SEND that way.  Most legs of a conference
+   listen to a pause most of the time, and without this every leg is sent all 100 packets a second — or every output row goes to the
+   host for a detector there, the per-stream CPU loop this library exists to replace.  With the stage ON for a stream, one kernel
+   (csrc/pn_rate_dtx.hip) reads the stream's OUTPUT row BEHIND the down-conversion — behind the suppressor, the mix and the limiter,
+   at the stream's own rate, in the format of the call — and leaves a decision per frame in a report row: send the frame, send this
+   SID instead, or send nothing.  It WRITES NO AUDIO: a converter with streams switched on gives bit for bit the audio of one without.
+   OFF by default, a switch per stream like DTMF detection: a converter on which nobody was ever switched on launches exactly what it
+   launches without this section.  The SID is the 14 bytes of the section above (M, L, N_1..N_12), always one pn_rate_set_stream_sid of
+   another converter accepts: the send side is the inverse of csrc/pn_cng_rules.h.
+
+   The rule, with every rounding and summation order, is csrc/pn_dtx_rules.h (HIP-free); tests/dtx_model.py restates it in numpy float32
+   and integers; the kernel, pn_dtx_frame and the model agree bit for bit.  Every fp32 operation is singly rounded.
+   Samples: the output row, n_s = 80, 160, 240, 320 or 480, float as it is, int16 times 2^-15, G.711 decoded with the stream's law.
+   Autocorrelation of the row alone, r[j] = sum_{n >= j} x[n] x[n-j], j = 0..12, 64 lanes' partial sums folded by the xor butterfly (the
+     order of the mix level).  No history from the row before: the sequence is positive semi-definite.
+   Energy e = r[0] / n_s.  A non-finite e (NaN or inf in a float row) makes the frame ACTIVE with PN_DTX_NONFINITE and changes nothing
+     but the hangover and the mode.
+   Floor N: the first analysed frame after a clear sets N = e and counts as ACTIVE (a stream starts by sending).  Then
+     active = e > THR max(N, FLOOR_MIN), and N = e where e < N, else N += FLOOR_UP (e - N) where not active, else
+     N = max(N, FLOOR_MIN) FLOOR_DRIFT.  Digital silence: rows with e == 0 in front of a stream's first other row (the zeros of the
+     converter's delay) are sent and not analysed; a row of zeros later in a call takes the floor to 0, from where it climbs back at
+     the drift's pace — about 40 s from FLOOR_MIN to a floor of -60 dBov at the defaults, during which the stream sends every frame.
+   Hangover: an active frame sets hang = HANGOVER; a frame is sent while active or hang > 0; a frame that is not active takes one off
+     hang: exactly HANGOVER frames are sent behind the last active one.
+   Noise statistics R[0..12], on every frame that is not active (hangover frames included): R[j] += SMOOTH (r[j] / n_s - R[j]); the first
+     such frame after a clear sets them.
+   Decision: sent -> PN_DTX_FRAME, mode VOICE.  Else from VOICE -> PN_DTX_SID, mode SILENT.  Else, L being the level of R[0]:
+     |L - L_sent| >= UPDATE_DB, or MAX_INTERVAL > 0 and MAX_INTERVAL frames since the last SID -> PN_DTX_SID; otherwise PN_DTX_NONE.
+   Level L, -dBov: the number of i in 0..126 with R[0] < 10^(-(i + 0.5) / 10), from 127 fp32 literals; no logarithm.  R[0] = 0: 127.
+   SID, on a frame that emits one: Levinson-Durbin in fp32 on R[0..ORDER] in the sign convention of the comfort-noise lattice, each k_i
+     quantised inside the loop (N_i = (int)(k_i 32768/258 + 127.5)) and the recursion continued with the quantised value; it stops early
+     (a smaller M) where |k_i| < 1 or the residual > 0 fails, and with M = 0 unless R[0] > 0 and finite.
+   A stream that is switched off: decision FRAME, eight zero report words, no state touched.  A stream off the id list keeps both.
+   Parameters, one set per converter, PN_DTX_N_PARAMS = 9 floats.  THE DEFAULTS ARE THE AUTHOR'S AND ARE NOT TUNED ON SPEECH:
+     0 PN_DTX_THR 4.0 (finite, > 1)   1 PN_DTX_FLOOR_UP 0.1 ((0, 1])   2 PN_DTX_FLOOR_DRIFT 1.0023 ([1, 2))   3 PN_DTX_FLOOR_MIN 1e-10
+     (finite, > 0)   4 PN_DTX_HANGOVER 20 (whole, 0..255)   5 PN_DTX_SMOOTH 0.1 ((0, 1])   6 PN_DTX_UPDATE_DB 2 (whole, 1..127)
+     7 PN_DTX_MAX_INTERVAL 0 (whole, 0..65535; 0: never)   8 PN_DTX_ORDER 10 (whole, 0..12).  They travel as an argument of every launch.
+   State per stream, 24 words, allocated by the first enabling, never inside a frame: R[13], N, hang, the mode, the frames since the
+     last SID, the analysed frames, the last emitted SID with its count.  Zeroed by pn_rate_reset, for the listed streams by
+     pn_rate_reset_streams, pn_rate_set_stream_rates, pn_rate_import_streams[_host], and for a stream that is switched on from off; a
+     conference or hold change leaves it.  It travels in NO record.
+
+   pn_rate_set_stream_dtx(r, ids, n, on) / pn_rate_get_stream_dtx: the switch, a setting ordered like pn_rate_set_stream_dtmf.
+   pn_rate_set_dtx_params / pn_rate_get_dtx_params: the converter's nine parameters; refused like pn_dtx_params_check.
+   A frame (pn_rate_process_*, pn_rate_submit_host_*), while somebody is switched on: one launch behind the down-conversion over the
+     frame's rows, on the caller's output rows in the frame's format.
+   pn_rate_dtx_f32 / _i16 / _g711(r, d_out_rows, ids, n_ids): the stage on its own over caller-supplied OUTPUT rows [n_streams][n] (a
+     mixed converter: [n_streams][480]) at a 16-byte aligned device address, ids as for pn_rate_down_*.
+   DTX report (pn_rate_set_dtx_report, pn_rate_read_dtx_report synchronising, pn_rate_read_dtx_report_dev asynchronous on the context's
+     stream; -1 while off): PN_DTX_REPORT_WORDS = 8 little-endian 32-bit words per stream, written for every stream on a launch's list:
+     word 0  the decision: PN_DTX_FRAME 0, PN_DTX_SID 1, PN_DTX_NONE 2
+     word 1  PN_DTX_ON | PN_DTX_ACTIVE | PN_DTX_HANGOVER_FRAME | PN_DTX_NONFINITE in the low byte; L in bits 8..14 (the level of this frame's
+             R[0] where the decision is SID or NONE, 0 on a FRAME); hang in bits 16..31
+     word 2  the bits of e          word 3  the bits of N
+     words 4..7  the last emitted SID's 14 bytes, then a 16-bit count of the SIDs emitted since the clear (it wraps): a caller that
+             reads less often than every frame tells a new SID from the old one
+   pn_rate_kernel_time takes "rate_dtx".  (A frame can now have eleven timed scopes, so pn_rate_set_profiling creates 1408 events up
+     front where it created 1280, on every converter.)
+   Host only, needing no GPU: pn_dtx_default_params, pn_dtx_params_check, pn_dtx_frame (one float row of one enabled stream, the twin of
+     the kernel: -> the decision, -1 for a refused argument; state24 read and written, report8 may be NULL), pn_dtx_sid_from_acorr (the
+     Levinson step alone on R[0..12]: -> M, the SID's level byte being that of R[0]), pn_dtx_level (a mean square -> L).
+   Known limit.  The detector is an energy detector behind a suppressor.  On the comfort-noise model's most strongly shaped noise (all
+     twelve coefficients large) at 80-sample rows the frame energy fluctuates enough that THR = 4 fires on about 2 % of pure-noise
+     frames (12 of 535 on the numpy model); at 160 samples, or on white noise, on none.
+   NOT provided: the report on pn_host_next_report; DTX state in any record (a moved call starts in VOICE and relearns its floor); a
+   model-based or spectral VAD; packetisation and RTP; the send side without a converter; any measurement of detection quality on speech
+   or of perceived quality. */
+#define PN_DTX_N_PARAMS 9
+#define PN_DTX_THR 0
+#define PN_DTX_FLOOR_UP 1
+#define PN_DTX_FLOOR_DRIFT 2
+#define PN_DTX_FLOOR_MIN 3
+#define PN_DTX_HANGOVER 4
+#define PN_DTX_SMOOTH 5
+#define PN_DTX_UPDATE_DB 6
+#define PN_DTX_MAX_INTERVAL 7
+#define PN_DTX_ORDER 8
+#define PN_DTX_REPORT_WORDS 8
+#define PN_DTX_FRAME 0
+#define PN_DTX_SID 1
+#define PN_DTX_NONE 2
+#define PN_DTX_ON 1
+#define PN_DTX_ACTIVE 2
+#define PN_DTX_HANGOVER_FRAME 4
+#define PN_DTX_NONFINITE 8
+int pn_dtx_default_params(float *params9);                /* host only */
+int pn_dtx_params_check(const float *params9);            /* host only */
+int pn_dtx_frame(const float *params9, uint32_t *state24, const float *row, int n, uint32_t *report8);   /* host only */
+int pn_dtx_sid_from_acorr(const float *R13, int order, uint8_t *sid14);                                  /* host only */
+int pn_dtx_level(float mean_square);                      /* host only */
+int pn_rate_set_stream_dtx(pn_rate *r, const int32_t *ids, int n, const uint8_t *on);
+int pn_rate_get_stream_dtx(const pn_rate *r, uint8_t *h_on);
+int pn_rate_set_dtx_params(pn_rate *r, const float *params9);
+int pn_rate_get_dtx_params(const pn_rate *r, float *params9);
+int pn_rate_dtx_f32(pn_rate *r, const float *d_out_rows, const int32_t *ids, int n_ids);
+int pn_rate_dtx_i16(pn_rate *r, const int16_t *d_out_rows, const int32_t *ids, int n_ids);
+int pn_rate_dtx_g711(pn_rate *r, const uint8_t *d_out_rows, const int32_t *ids, int n_ids);
+int pn_rate_set_dtx_report(pn_rate *r, int enable);
+int pn_rate_read_dtx_report(pn_rate *r, void *h_report);
+int pn_rate_read_dtx_report_dev(pn_rate *r, void *d_report);
+int pn_rate_debug_dtx_state(pn_rate *r, void *h_state);                /* tests: [n_streams][24] words, synchronising; zeros while no stream was ever enabled */
 
 /* ---- automatic level control: talkers levelled on the GPU ------------------------------------------------------------------------ */
 /* A quiet phone caller and a hot headset otherwise enter a conference at whatever level they arrive: loudest-N ranks raw frame

@@ -39,6 +39,14 @@ PLC_REPORT_DTYPE = np.dtype([("flags", "<u4"), ("period", "<u4"), ("run", "<u4")
 CNG_MAX_ORDER, CNG_SID_BYTES, CNG_DEFAULT_LEVEL, CNG_DEFAULT_SEED = 12, 14, 60, 0x434e4731
 CNG_REPORT_WORDS = 4
 CNG_REPORT_DTYPE = np.dtype([("run", "<u4"), ("total", "<u4"), ("gain", "<f4"), ("counter", "<u4")])
+# the DTX send side (include/percepnet_hip.h "DTX send side"): PN_DTX_*
+DTX_N_PARAMS = 9
+DTX_THR, DTX_FLOOR_UP, DTX_FLOOR_DRIFT, DTX_FLOOR_MIN, DTX_HANGOVER, DTX_SMOOTH, DTX_UPDATE_DB, DTX_MAX_INTERVAL, DTX_ORDER = range(9)   # parameter indices
+DTX_REPORT_WORDS, DTX_STATE_WORDS = 8, 24
+DTX_FRAME, DTX_SID, DTX_NONE = 0, 1, 2                                             # the decision, report word 0
+DTX_ON, DTX_ACTIVE, DTX_HANGOVER_FRAME, DTX_NONFINITE = 1, 2, 4, 8                 # its flags, the low byte of report word 1
+# word1: flags | L << 8 | hang << 16; sid: the last emitted SID; count: the SIDs emitted since the clear, mod 2^16
+DTX_REPORT_DTYPE = np.dtype([("decision", "<u4"), ("word1", "<u4"), ("energy", "<f4"), ("floor", "<f4"), ("sid", "u1", (14,)), ("count", "<u2")])
 # automatic level control (include/percepnet_hip.h "automatic level control"): PN_AGC_*
 AGC_N_PARAMS = 8
 AGC_MAX_GAIN, AGC_MIN_GAIN, AGC_GATE_RMS, AGC_ATTACK, AGC_RELEASE, AGC_STEP_UP, AGC_STEP_DOWN, AGC_CEILING = range(8)   # parameter indices
@@ -320,6 +328,19 @@ def load_library():
             getattr(L, name).argtypes = [_vp, _vp]
         L.pn_rate_set_stream_dtmf_clamp.argtypes = [_vp, _vp, ctypes.c_int, _vp]
         L.pn_rate_dtmf_clamp_f32.argtypes = [_vp, _vp, _vp, ctypes.c_int]
+    if hasattr(L, "pn_rate_set_stream_dtx"):
+        for name in ("pn_dtx_default_params", "pn_dtx_params_check"):
+            getattr(L, name).argtypes = [_vp]
+        L.pn_dtx_frame.argtypes = [_vp, _vp, _vp, ctypes.c_int, _vp]
+        L.pn_dtx_sid_from_acorr.argtypes = [_vp, ctypes.c_int, _vp]
+        L.pn_dtx_level.argtypes = [ctypes.c_float]
+        L.pn_rate_set_dtx_report.argtypes = [_vp, ctypes.c_int]
+        for name in ("pn_rate_set_dtx_params", "pn_rate_get_dtx_params", "pn_rate_get_stream_dtx", "pn_rate_read_dtx_report",
+                     "pn_rate_read_dtx_report_dev", "pn_rate_debug_dtx_state"):
+            getattr(L, name).argtypes = [_vp, _vp]
+        L.pn_rate_set_stream_dtx.argtypes = [_vp, _vp, ctypes.c_int, _vp]
+        for name in ("pn_rate_dtx_f32", "pn_rate_dtx_i16", "pn_rate_dtx_g711"):
+            getattr(L, name).argtypes = [_vp, _vp, _vp, ctypes.c_int]
     if hasattr(L, "pn_host_pipeline_prepare"):
         L.pn_host_pipeline_prepare.argtypes = [_vp]
     L.pn_ctx_debug_copy.restype = ctypes.c_longlong
@@ -900,6 +921,60 @@ def lim_frame(params, ceiling, state, row, want_report=False):
     if flags < 0:
         raise PercepNetError(_err(L))
     return (out, int(flags), rep) if want_report else (out, int(flags))
+
+
+def dtx_default_params():
+    """-> float32 [DTX_N_PARAMS]: the DTX send side's default parameters (pn_dtx_default_params, host only).  Not tuned on speech."""
+    p = np.empty(DTX_N_PARAMS, np.float32)
+    load_library().pn_dtx_default_params(p.ctypes.data)
+    return p
+
+
+def _dtx_params(params):
+    p = np.ascontiguousarray(params, dtype=np.float32).ravel()
+    if p.size != DTX_N_PARAMS:
+        raise PercepNetError(f"{p.size} DTX parameters: a set has {DTX_N_PARAMS}")
+    return p
+
+
+def dtx_params_check(params):
+    """Raises PercepNetError naming the first parameter that is NaN, outside its range or no whole number where one is asked
+    (pn_dtx_params_check, host only)."""
+    L = load_library()
+    if L.pn_dtx_params_check(_dtx_params(params).ctypes.data) != 0:
+        raise PercepNetError(_err(L))
+
+
+def dtx_frame(params, state, row):
+    """One frame of the DTX send side on one float row (80, 160, 240, 320 or 480 samples) of an enabled stream (pn_dtx_frame, host
+    only).  state: uint32 [DTX_STATE_WORDS] (zeros are fresh), updated IN PLACE -> (the decision, the DTX_REPORT_DTYPE row)."""
+    L = load_library()
+    x = np.ascontiguousarray(row, dtype=np.float32).ravel()
+    if not isinstance(state, np.ndarray) or state.dtype != np.uint32 or state.size != DTX_STATE_WORDS or not state.flags.c_contiguous or not state.flags.writeable:
+        raise PercepNetError(f"state: {DTX_STATE_WORDS} writable contiguous uint32 words")
+    rep = np.zeros((), DTX_REPORT_DTYPE)
+    decision = L.pn_dtx_frame(_dtx_params(params).ctypes.data, state.ctypes.data, x.ctypes.data, int(x.size), rep.ctypes.data)
+    if decision < 0:
+        raise PercepNetError(_err(L))
+    return int(decision), rep
+
+
+def dtx_sid_from_acorr(R, order):
+    """The SID of the noise statistics R[0..12] at the given order (pn_dtx_sid_from_acorr, host only): the Levinson step alone ->
+    uint8 [14]: M, the level of R[0], N_1..N_M, zeros."""
+    L = load_library()
+    r = np.ascontiguousarray(R, dtype=np.float32).ravel()
+    if r.size != 13:
+        raise PercepNetError(f"{r.size} autocorrelation lags: the step takes 13, R[0..12]")
+    sid = np.zeros(CNG_SID_BYTES, np.uint8)
+    if L.pn_dtx_sid_from_acorr(r.ctypes.data, int(order), sid.ctypes.data) < 0:
+        raise PercepNetError(_err(L))
+    return sid
+
+
+def dtx_level(mean_square):
+    """L in -dBov of a mean square: how many of the rule's 127 edges lie above it (pn_dtx_level, host only)."""
+    return int(load_library().pn_dtx_level(ctypes.c_float(float(np.float32(mean_square)))))
 
 
 def dtmf_default_params():
@@ -1502,6 +1577,62 @@ class RateConverter:
         """The same into device memory [n_streams][4] words, asynchronous on the context's stream (pn_rate_read_dtmf_report_dev)."""
         self._chk(self.L.pn_rate_read_dtmf_report_dev(self.h, d_report))
 
+    # the DTX send side: an enabled stream's OUTPUT row is read behind the down-conversion; the audio is untouched
+    def set_stream_dtx(self, ids, on):
+        """The DTX send side on or off for the streams `ids` from the next frame on (pn_rate_set_stream_dtx): asynchronous, ordered like
+        set_stream_dtmf.  `on`: one value for all of them or one per id.  A stream that was off starts from the fresh state."""
+        a, n = self._ids(ids)
+        w = np.asarray(on).astype(bool).astype(np.uint8).ravel()
+        if w.size == 1:
+            w = np.repeat(w, n)
+        if w.size != n:
+            raise PercepNetError(f"{w.size} switches for {n} streams")
+        w = np.ascontiguousarray(w)
+        self._chk(self.L.pn_rate_set_stream_dtx(self.h, a.ctypes.data, n, w.ctypes.data))
+
+    def stream_dtx(self):
+        """-> uint8 [n_streams]: the switches as last set (pn_rate_get_stream_dtx); 0 everywhere on a new converter."""
+        w = np.empty(self.n_streams, np.uint8)
+        self._chk(self.L.pn_rate_get_stream_dtx(self.h, w.ctypes.data))
+        return w
+
+    def set_dtx_params(self, params):
+        """The converter's DTX_N_PARAMS parameters from the next frame on (pn_rate_set_dtx_params); refused as a whole, naming the
+        first bad one."""
+        self._chk(self.L.pn_rate_set_dtx_params(self.h, _dtx_params(params).ctypes.data))
+
+    def dtx_params(self):
+        """-> float32 [DTX_N_PARAMS] as last set (pn_rate_get_dtx_params); dtx_default_params() on a new converter."""
+        p = np.empty(DTX_N_PARAMS, np.float32)
+        self._chk(self.L.pn_rate_get_dtx_params(self.h, p.ctypes.data))
+        return p
+
+    def dtx_dev(self, d_out_rows, fmt="f32", ids=None):
+        """The stage on its own over device OUTPUT rows [n_streams][row_samples] of format "f32", "i16" or "g711", which it only reads
+        (pn_rate_dtx_f32 / _i16 / _g711)."""
+        a, n = self._ids(ids)
+        self._chk(getattr(self.L, "pn_rate_dtx_" + fmt)(self.h, d_out_rows, a.ctypes.data if a is not None else None, n))
+
+    def set_dtx_report(self, on):
+        self._chk(self.L.pn_rate_set_dtx_report(self.h, 1 if on else 0))
+
+    def read_dtx_report(self):
+        """-> DTX_REPORT_DTYPE [n_streams]: a stream's record is of the last launch that had it on its list (pn_rate_read_dtx_report,
+        synchronising)."""
+        rep = np.empty(self.n_streams, DTX_REPORT_DTYPE)
+        self._chk(self.L.pn_rate_read_dtx_report(self.h, rep.ctypes.data))
+        return rep
+
+    def read_dtx_report_dev(self, d_report):
+        """The same into device memory [n_streams][8] words, asynchronous on the context's stream (pn_rate_read_dtx_report_dev)."""
+        self._chk(self.L.pn_rate_read_dtx_report_dev(self.h, d_report))
+
+    def dtx_state(self):
+        """-> uint32 [n_streams, DTX_STATE_WORDS]: the stage's state words (pn_rate_debug_dtx_state, synchronising): for tests."""
+        st = np.empty((self.n_streams, DTX_STATE_WORDS), np.uint32)
+        self._chk(self.L.pn_rate_debug_dtx_state(self.h, st.ctypes.data))
+        return st
+
     # DTMF removal: a detected digit is muted in the stream's enhanced 48 kHz row, behind the engine and in front of the level control
     def set_stream_dtmf_clamp(self, ids, on):
         """Removal on or off for the streams `ids` from the next frame on (pn_rate_set_stream_dtmf_clamp): asynchronous, ordered like
@@ -1614,7 +1745,7 @@ class RateConverter:
     def kernel_times(self, names=("rate_up", "rate_down")):
         """-> {"rate_up": (total_ms, launches), "rate_down": (...)}; names: which kernels ("rate_mix" is the conference mix,
         "rate_plc" the packet-loss concealer, "rate_agc" the level control, "rate_lim" the output limiter, "rate_dtmf" the DTMF detector,
-        "rate_clamp" DTMF removal, "rate_cng" comfort noise)"""
+        "rate_clamp" DTMF removal, "rate_cng" comfort noise, "rate_dtx" the DTX send side)"""
         out = {}
         for name in names:
             ms = ctypes.c_double()

@@ -19,7 +19,7 @@ LIB = os.path.join(LIBDIR, "libpercepnet_hip.so")
 RUN = os.path.join(LIBDIR, "percepnet_run")
 EXPORT_MAP = os.path.join(CSRC, "libpercepnet_hip.map")    # ld version script: the export list (everything else is local)
 SOURCES = ["pn_tables.cpp", "pn_model.cpp", "pn_pack.cpp", "pn_dsp_fe.hip", "pn_dsp_fe_g2.hip", "pn_dsp_fe_split_s.hip", "pn_dsp_fe_split_p.hip", "pn_dsp.hip", "pn_outstage.hip", "pn_nn.hip", "pn_nn_small.hip", "pn_nn_x3.hip", "pn_nn_d.hip", "pn_nn_n48.hip", "pn_targets.hip", "pn_state.hip", "pn_active.hip", "pn_stream_state.hip", "pn_context.cpp", "pn_selftest.cpp", "pn_host_pipe.cpp", "pn_stream_state.cpp", "pn_network.cpp",
-           "pn_featgen.cpp", "pn_rate.hip", "pn_rate_mix.hip", "pn_rate_plc.hip", "pn_rate_agc.hip", "pn_rate_lim.hip", "pn_rate_call.hip", "pn_rate_dtmf.hip", "pn_rate_dtmf_clamp.hip", "pn_rate_cng.hip", "pn_rate.cpp", "rnnoise_compat.cpp"]
+           "pn_featgen.cpp", "pn_rate.hip", "pn_rate_mix.hip", "pn_rate_plc.hip", "pn_rate_agc.hip", "pn_rate_lim.hip", "pn_rate_call.hip", "pn_rate_dtmf.hip", "pn_rate_dtmf_clamp.hip", "pn_rate_cng.hip", "pn_rate_dtx.hip", "pn_rate.cpp", "rnnoise_compat.cpp"]
 # percepnet_run.cpp / percepnet_featgen.cpp (the CLIs) are linked separately against the library
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden",
          "-Wall", "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unused-value", "-Wno-unused-result"]
@@ -64,7 +64,7 @@ RESOURCE_LIMITS = {"pn_fe_spec_in_kernel": (0, 0), "pn_fe_spec_out_kernel": (0, 
                    # a thread's 64 twiddles in registers across the rows of its block; DTMF removal (pn_rate_dtmf_clamp.hip) decides a row
                    # per thread in a handful of registers and uses neither LDS nor scratch
                    "pn_rate_": (0, 0)}
-RESOURCE_SOURCES = ("pn_dsp_fe_split_s.hip", "pn_dsp_fe_split_p.hip", "pn_dsp.hip", "pn_nn_x3.hip", "pn_nn_d.hip", "pn_rate.hip", "pn_rate_mix.hip", "pn_rate_plc.hip", "pn_rate_agc.hip", "pn_rate_lim.hip", "pn_rate_call.hip", "pn_rate_dtmf.hip", "pn_rate_dtmf_clamp.hip", "pn_rate_cng.hip")
+RESOURCE_SOURCES = ("pn_dsp_fe_split_s.hip", "pn_dsp_fe_split_p.hip", "pn_dsp.hip", "pn_nn_x3.hip", "pn_nn_d.hip", "pn_rate.hip", "pn_rate_mix.hip", "pn_rate_plc.hip", "pn_rate_agc.hip", "pn_rate_lim.hip", "pn_rate_call.hip", "pn_rate_dtmf.hip", "pn_rate_dtmf_clamp.hip", "pn_rate_cng.hip", "pn_rate_dtx.hip")
 
 
 def parse_resource_remarks(text):

@@ -5,7 +5,7 @@
 // dropped, main.cpp:32-33); with a single pair ./feature_test.raw gets 68 floats per frame.
 //
 //   percepnet_run [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N]
-//                 [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--plc [--lose P:F0-F1,P:F,..]] [--dtx P:F0-F1,P:F,.. [--sid L[:N1:..:NM]]] [--agc RMS [--agc-max-gain G]] [--limiter CEIL [--limiter-hold H]] [--dtmf [--dtmf-on-frames N]] [--dtmf-clamp [--dtmf-guard PRE,POST]] [--migrate-at F] [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
+//                 [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--plc [--lose P:F0-F1,P:F,..]] [--dtx P:F0-F1,P:F,.. [--sid L[:N1:..:NM]]] [--agc RMS [--agc-max-gain G]] [--limiter CEIL [--limiter-hold H]] [--dtmf [--dtmf-on-frames N]] [--dtmf-clamp [--dtmf-guard PRE,POST]] [--dtx-send [--dtx-send-hangover H]] [--migrate-at F] [--device N | --devices 0,1,..|all] [--no-numa] [--verbose]
 //                 in0.pcm out0.pcm [in1.pcm out1.pcm ...]
 //
 // --rate R: the files are raw int16 at R Hz instead of 48 kHz, in frames of n = 480 * R / 48000 samples (80 | 160 | 240 | 320): a rate
@@ -76,6 +76,15 @@
 // units of an 8 kHz RTP clock), read behind every submit like the digits.  F is the frame of the INPUT: the audio it describes leaves six
 // frames later.  --dtmf-guard PRE,POST: the rows removed in front of and behind a digit's marked rows, whole numbers in [0, 4] and
 // [0, 8] (parameters PN_DTMF_CLAMP_PRE and PN_DTMF_CLAMP_POST; default 1,0); it needs --dtmf-clamp, and on_frames + PRE must be <= 5.
+// --dtx-send: the DTX send side on the converter (pn_rate_set_stream_dtx for every slot, once: a slot reset starts the slot's detector
+// again and keeps its switch): behind the run one line "dtx-send: pair P frame F sid S none N last-sid M:L:N1:..:NM" on stdout for every
+// pair — how many of its frames the stage decided to send, to replace by a SID, to leave out, and the last SID it emitted ("-": none).
+// The audio is untouched and every frame is still written to the output file: the decisions are what a sender would act on.  Like the
+// DTMF report, the DTX report is not part of the pipelined path's report, so the run reads it (pn_rate_read_dtx_report, synchronising)
+// behind every submit: with --dtx-send a frame's GPU work no longer overlaps the next frame's file reads.  With --rate or --rates it
+// uses their converter, alone it makes a mixed converter of all 48000, as --agc does.  --dtx-send-hangover H: the frames sent behind the
+// last active one, a whole number in [0, 255] (parameter PN_DTX_HANGOVER; default 20); it needs --dtx-send.  With --migrate-at every
+// pair starts again in VOICE on the target and relearns its floor: no record carries the stage's state.
 // --migrate-at F (needs a converter — --rate, --rates or an option that makes one — and one device): when frame F (the shard's frames
 // count from 0) has been delivered, the run builds a SECOND context and converter with the same settings, moves every slot there with
 // all three record kinds in the mover's order of include/percepnet_hip.h "call-state records" (the engine's, the converter's tails,
@@ -159,6 +168,8 @@ static bool g_sid_given = false;
 static float g_agc = 0.0f, g_agc_max_gain = 0.0f;     // --agc: every pair's target RMS (0: not given); --agc-max-gain (0: not given)
 static bool g_dtmf = false;                            // --dtmf: detection on every pair
 static float g_dtmf_on_frames = 0.0f;                  // --dtmf-on-frames (0: not given)
+static bool g_dtx_send = false;                        // --dtx-send: the DTX send side on every pair
+static float g_dtx_hangover = -1.0f;                   // --dtx-send-hangover (-1: not given)
 static bool g_dtmf_clamp = false;                      // --dtmf-clamp: removal on every pair
 static int g_dtmf_guard[2] = {-1, -1};                 // --dtmf-guard PRE,POST (-1: not given)
 static float g_limiter = 0.0f, g_limiter_hold = -1.0f; // --limiter: every pair's ceiling (0: not given); --limiter-hold (-1: not given)
@@ -261,6 +272,16 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
       if (pn_rate_set_dtmf_clamp_params(rt, params) || pn_rate_set_stream_dtmf_clamp(rt, all.data(), B, on.data()) || pn_rate_set_dtmf_clamp_report(rt, 1))
         return bad(std::string("--dtmf-clamp: ") + pn_last_error());
     }
+    if (g_dtx_send) {                                     // every slot's switch, once (a setting: slot resets and rate changes keep it)
+      std::vector<int32_t> all(B);
+      std::vector<uint8_t> on(B, 1);
+      float params[PN_DTX_N_PARAMS];
+      for (int s = 0; s < B; s++) all[s] = s;
+      pn_dtx_default_params(params);
+      if (g_dtx_hangover >= 0.0f) params[PN_DTX_HANGOVER] = g_dtx_hangover;
+      if (pn_rate_set_dtx_params(rt, params) || pn_rate_set_stream_dtx(rt, all.data(), B, on.data()) || pn_rate_set_dtx_report(rt, 1))
+        return bad(std::string("--dtx-send: ") + pn_last_error());
+    }
     if (postfilter) pn_ctx_set_postfilter(cx, 1);
     if ((g_saturate && pn_ctx_set_output_saturate(cx, 1)) || (g_report && pn_ctx_set_report(cx, 1))) return bad(pn_last_error());
     {
@@ -280,6 +301,9 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
   std::vector<long> pair_frame(B, 0);                   // --lose: the frames the pair playing in a slot has supplied so far
   std::vector<PairStat> stat(g_report ? P : 0);
   std::vector<uint32_t> dtmf_rep(g_dtmf ? (size_t)B * PN_DTMF_REPORT_WORDS : 0), clamp_rep(g_dtmf_clamp ? (size_t)B * PN_DTMF_CLAMP_REPORT_WORDS : 0);
+  std::vector<uint32_t> dtx_rep(g_dtx_send ? (size_t)B * PN_DTX_REPORT_WORDS : 0);
+  struct DtxStat { long n[3] = {0, 0, 0}; uint32_t sid[4] = {0, 0, 0, 0}; bool any = false; };
+  std::vector<DtxStat> dtx_stat(g_dtx_send ? P : 0);  // --dtx-send: the decisions of every pair of the shard
   auto open_pair = [&](int s) -> bool {                 // the next waiting pair starts playing in slot s
     const char *pi = paths[2 * (sh->first + next_pair)], *po = paths[2 * (sh->first + next_pair) + 1];
     cur_pair[s] = next_pair++; pair_frame[s] = 0;
@@ -433,16 +457,36 @@ static void run_shard(Shard *sh, const pn_model *m, char **paths, int nn_mode, i
           printf("dtmf-event: pair %d frame %ld event %u end %u duration %u\n", sh->first + cur_pair[s], pair_frame[s] - 1, w[2] >> 24, (w[2] >> 23) & 1u, w[2] & 0xffffu);
       }
     }
+    if (g_dtx_send) {                                  // this frame's decisions: the read waits for the frame just submitted
+      if (pn_rate_read_dtx_report(rt, dtx_rep.data())) return fail(5, pn_last_error());
+      for (int s = 0; s < B; s++) {
+        const uint32_t *w = &dtx_rep[(size_t)s * PN_DTX_REPORT_WORDS];
+        if (!sl.file[s] || w[0] > PN_DTX_NONE) continue;
+        DtxStat &ds = dtx_stat[cur_pair[s]];
+        ds.n[w[0]]++;
+        if (w[0] == PN_DTX_SID) { memcpy(ds.sid, w + 4, sizeof ds.sid); ds.any = true; }
+      }
+    }
     if (t >= 2) flush(slot[(t - 2) % 3]);
   }
   if (pn_host_wait(cx)) return fail(5, pn_last_error());
   for (long u = (t >= 2 ? t - 2 : 0); u < t; u++) flush(slot[u % 3]);     // the last two frames in flight
   for (int s = 0; s < B; s++) fout[s] = NULL;        // every output file was closed with its last frame
+  for (size_t q = 0; q < dtx_stat.size(); q++) {      // --dtx-send: one line a pair
+    const DtxStat &ds = dtx_stat[q];
+    std::string sid = "-";
+    if (ds.any) {
+      const int M = (int)(ds.sid[0] & 0xffu);
+      sid = std::to_string(M);
+      for (int b = 1; b < 2 + M && b < PN_CNG_SID_BYTES; b++) sid += ":" + std::to_string((ds.sid[b >> 2] >> (8 * (b & 3))) & 0xffu);
+    }
+    printf("dtx-send: pair %d frame %ld sid %ld none %ld last-sid %s\n", sh->first + (int)q, ds.n[PN_DTX_FRAME], ds.n[PN_DTX_SID], ds.n[PN_DTX_NONE], sid.c_str());
+  }
 }
 
 // the usage text, for a command line without pairs and for a rate no converter takes.  Returns the exit status, 1.
 static int usage(const char *argv0) {
-  fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N] [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--plc [--lose P:F0-F1,P:F,..]] [--dtx P:F0-F1,P:F,.. [--sid L[:N1:..:NM]]] [--agc RMS [--agc-max-gain G]] [--limiter CEIL [--limiter-hold H]] [--dtmf [--dtmf-on-frames N]] [--dtmf-clamp [--dtmf-guard PRE,POST]] [--migrate-at F] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv0);
+  fprintf(stderr, "usage: %s [--model model.pnw] [--strict | --x3] [--postfilter] [--atten-lim DB] [--saturate] [--report] [--slots N] [--rate 8000|16000|24000|32000 | --rates R0,R1,..] [--g711 ulaw|alaw] [--conference C0,C1,.. [--conf-speakers N] [--mix-gains G0,G1,..]] [--plc [--lose P:F0-F1,P:F,..]] [--dtx P:F0-F1,P:F,.. [--sid L[:N1:..:NM]]] [--agc RMS [--agc-max-gain G]] [--limiter CEIL [--limiter-hold H]] [--dtmf [--dtmf-on-frames N]] [--dtmf-clamp [--dtmf-guard PRE,POST]] [--dtx-send [--dtx-send-hangover H]] [--migrate-at F] [--device N | --devices 0,1,..|all] <noisy speech> <output denoised> [...more pairs]\n", argv0);
   return 1;
 }
 
@@ -587,6 +631,16 @@ int main(int argc, char **argv) {
       params[PN_DTMF_ON_FRAMES] = g_dtmf_on_frames;
       if (end == v || *end || pn_dtmf_params_check(params)) { fprintf(stderr, "--dtmf-on-frames: expected a whole number of frames in [1, 100], got '%s'\n", v); return 1; }
     }
+    else if (!strcmp(argv[ai], "--dtx-send")) g_dtx_send = true;    // the DTX send side on every pair (pn_rate_set_stream_dtx)
+    else if (!strcmp(argv[ai], "--dtx-send-hangover") && ai + 1 < argc) {   // the frames sent behind the last active one (PN_DTX_HANGOVER)
+      const char *v = argv[++ai];
+      char *end = NULL;
+      g_dtx_hangover = strtof(v, &end);
+      float params[PN_DTX_N_PARAMS];
+      pn_dtx_default_params(params);
+      params[PN_DTX_HANGOVER] = g_dtx_hangover;
+      if (end == v || *end || pn_dtx_params_check(params)) { fprintf(stderr, "--dtx-send-hangover: expected a whole number of frames in [0, 255], got '%s'\n", v); return 1; }
+    }
     else if (!strcmp(argv[ai], "--dtmf-clamp")) g_dtmf_clamp = true;   // DTMF removal on every pair (pn_rate_set_stream_dtmf_clamp)
     else if (!strcmp(argv[ai], "--dtmf-guard") && ai + 1 < argc) {    // rows removed in front of and behind a digit (PN_DTMF_CLAMP_PRE, PN_DTMF_CLAMP_POST)
       const char *v = argv[++ai];
@@ -653,6 +707,7 @@ int main(int argc, char **argv) {
   if (g_agc_max_gain > 0.0f && !(g_agc > 0.0f)) { fprintf(stderr, "--agc-max-gain needs --agc: it is a parameter of the level control\n"); return 1; }
   if (g_limiter_hold >= 0.0f && !(g_limiter > 0.0f)) { fprintf(stderr, "--limiter-hold needs --limiter: it is a parameter of the output limiter\n"); return 1; }
   if (g_dtmf_on_frames > 0.0f && !g_dtmf) { fprintf(stderr, "--dtmf-on-frames needs --dtmf: it is a parameter of the DTMF detector\n"); return 1; }
+  if (g_dtx_hangover >= 0.0f && !g_dtx_send) { fprintf(stderr, "--dtx-send-hangover needs --dtx-send: it is a parameter of the DTX send side\n"); return 1; }
   if (g_dtmf_clamp && !g_dtmf) { fprintf(stderr, "--dtmf-clamp needs --dtmf: a digit is removed where the detector finds it\n"); return 1; }
   if (g_dtmf_guard[0] >= 0 && !g_dtmf_clamp) { fprintf(stderr, "--dtmf-guard needs --dtmf-clamp: it is a parameter of DTMF removal\n"); return 1; }
   if (g_dtmf_clamp) {                                  // the guard in front must be in time for the detector's on_frames
@@ -663,7 +718,7 @@ int main(int argc, char **argv) {
     if (g_dtmf_guard[0] >= 0) { cp[PN_DTMF_CLAMP_PRE] = g_dtmf_guard[0]; cp[PN_DTMF_CLAMP_POST] = g_dtmf_guard[1]; }
     if (pn_dtmf_clamp_params_check(cp, dp)) { fprintf(stderr, "--dtmf-clamp: %s\n", pn_last_error()); return 1; }
   }
-  if ((g_plc || !g_dtx.empty() || g_agc > 0.0f || g_limiter > 0.0f || g_dtmf) && !g_rate && g_rates.empty()) g_rates.assign(B, 48000);        // on its own: a mixed converter of all 48000
+  if ((g_plc || !g_dtx.empty() || g_agc > 0.0f || g_limiter > 0.0f || g_dtmf || g_dtx_send) && !g_rate && g_rates.empty()) g_rates.assign(B, 48000);        // on its own: a mixed converter of all 48000
   if (g_migrate_at >= 0) {
     if (devices.size() > 1) { fprintf(stderr, "--migrate-at takes one device: the slots move between two contexts of one device\n"); return 1; }
     if (!g_rate && g_rates.empty()) { fprintf(stderr, "--migrate-at needs a converter (--rate or --rates): it moves the converter's records with the engine's\n"); return 1; }

@@ -147,6 +147,14 @@ void pn_launch_rate_dtmf(hipStream_t st, int n_rows, const int *d_ids, const int
 // off for everybody.  State [n_streams][4] words; d_report [n_streams][4] words or NULL
 void pn_launch_rate_dtmf_clamp(hipStream_t st, int n_rows, const int *d_ids, const int *d_on, const int32_t *params, const void *d_det_report, float *y48,
                                void *state, void *d_report);
+// the DTX send side (pn_rate_dtx.hip; the rule pn_dtx_rules.h): rows d_ids[0..n_rows) or, with d_ids == NULL, streams 0..n_rows of the
+// OUTPUT rows [n_streams][stride] samples of format fmt (PN_FMT_*), which it only reads, each of its stream's own n_s samples (d_factors
+// [n_streams], or NULL and ns for everybody; stride >= n_s, a multiple of 16).  d_on [n_streams] words: 0 = the stage is off for the
+// stream; d_laws [n_streams]: the G.711 laws (read for PN_FMT_G711 only); params: the converter's PN_DTX_N_PARAMS floats on the HOST,
+// passed by value.  State [n_streams][24] words; d_report [n_streams][8] words or NULL.  -1 (pn_set_error) without launching for a
+// format or geometry it has no kernel for
+int pn_launch_rate_dtx(hipStream_t st, int fmt, int n_rows, const int *d_ids, const int *d_on, const int *d_factors, int ns, const int *d_laws, const float *params,
+                       const void *rows, int stride, void *state, void *d_report);
 // call-state records (pn_rate_call.hip; layout and verdict pn_call_rules.h): record i of rec [n][PN_RATE_CALL_STATE_BYTES] (16-byte aligned)
 // <-> the PLC, AGC, limiter and level state of stream d_ids[i].  held: the PN_CALL_* states the converter holds — a state's pointers
 // are read only under its bit and may be NULL otherwise.  scatter: d_status[i] receives record i's verdict, a refused record moves nothing

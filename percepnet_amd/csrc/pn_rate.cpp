@@ -11,7 +11,7 @@
 // rate_set_report / rate_report_copy.  A per-stream SETTING goes through rate_set_words and comes back through rate_get.
 #include "pn_context.h"      // the context it borrows, the launchers, dev_alloc_into, stage_ids, the id rule, host_records_sync
 #include "pn_rate_layout.h"  // the per-stream state, and through it every stage's rules: pn_rate_design.h, pn_call_rules.h (pn_plc_rules.h,
-                             // pn_agc_rules.h, pn_lim_rules.h, pn_mix_rules.h), pn_dtmf_rules.h, pn_dtmf_clamp_rules.h
+                             // pn_agc_rules.h, pn_lim_rules.h, pn_mix_rules.h), pn_dtmf_rules.h, pn_dtmf_clamp_rules.h, pn_cng_rules.h, pn_dtx_rules.h
 #include "pn_rate_mixed.h"   // the mixed converter's host rules: the five rates, a rate change, one rate per record call
 #include "pn_g711.h"         // the 8-bit sample format: the companding and what a list of laws must be
 #include "pn_conf.h"         // conferences: what an id must be, the table after a change, the members in ascending order
@@ -19,7 +19,7 @@
 #include <vector>
 
 // the stages: the timed kernels (pn_rate_kernel_time) and their reports
-enum { RF_UP, RF_DOWN, RF_MIX, RF_PLC, RF_AGC, RF_LIM, RF_DTMF, RF_CLAMP, RF_CNG, RF_COUNT };
+enum { RF_UP, RF_DOWN, RF_MIX, RF_PLC, RF_AGC, RF_LIM, RF_DTMF, RF_CLAMP, RF_CNG, RF_DTX, RF_COUNT };
 struct RateStage { const char *family; int report_words; const char *report_off; };   // report_words per stream, 0: the stage has no report
 static const RateStage kRateStage[RF_COUNT] = {
     {"rate_up", 0, NULL},
@@ -31,6 +31,7 @@ static const RateStage kRateStage[RF_COUNT] = {
     {"rate_dtmf", PN_DTMF_REPORT_WORDS, "the DTMF report is off (pn_rate_set_dtmf_report)"},
     {"rate_clamp", PN_DTMF_CLAMP_REPORT_WORDS, "the DTMF removal report is off (pn_rate_set_dtmf_clamp_report)"},
     {"rate_cng", PN_CNG_REPORT_WORDS, "the comfort-noise report is off (pn_rate_set_cng_report)"},
+    {"rate_dtx", PN_DTX_REPORT_WORDS, "the DTX report is off (pn_rate_set_dtx_report)"},
 };
 enum { RATE_PIECE = 16384 };    // ids a setting stages through the id ring at a time
 
@@ -40,7 +41,7 @@ struct pn_rate {
   size_t bytes;
   float *taps_up, *taps_down;   // [2D + 1] h, g.  Mixed: the tables of L = 6, 3, 2 one behind the other, and behind them the g of 32000
   void *st[PN_RS_COUNT] = {};   // the per-stream state, [B][pn_rate_state_words] each (pn_rate_layout.h): NULL until the owning stage is first used
-  void *st2[PN_RS2_COUNT] = {}; // ... and that of the second table: the stages in front of the up-conversion
+  void *st2[PN_RS2_COUNT] = {}; // ... and that of the second table: the stages at the edges, at the streams' own rates
   void *d_report[RF_COUNT] = {};   // [B][kRateStage[].report_words] words: allocated by the first enabling of the report
   bool report[RF_COUNT] = {};      // the report switches
   float *x48, *y48;             // [B][480]: the engine's input and output rows of a whole frame
@@ -129,6 +130,13 @@ struct pn_rate {
   std::vector<uint8_t> silent_mark;                   // [B]
   std::vector<int32_t> silent_ids, gen_ids, gen_cont; // the marked streams; a frame's generated streams and their "continues" words
   std::vector<uint32_t> cng_last;                     // [B]
+  // the DTX send side (pn_rate_set_stream_dtx; the rule pn_dtx_rules.h): SETTINGS — the converter's parameters, a switch per stream as last
+  // set (host) and as a word on the device, written in stream order through the id ring like the detector's — and the state, 24 words per
+  // stream (st2[PN_RS2_DTX]).  The device side exists from the first enabling on.  dtx_on == 0: a frame launches nothing of it
+  float dtx_params[PN_DTX_N_PARAMS];
+  std::vector<uint8_t> dtx_sw;                        // [B], 0
+  int dtx_on = 0;                                     // streams whose switch is on
+  int *d_dtx_on = NULL;                               // [B] words
   std::vector<void *> allocs;
   // timing of the kernels (pn_rate_set_profiling): HIP events around their launches, like the context's families but owned
   // here; while it is off no event exists and none is recorded
@@ -222,6 +230,11 @@ extern "C" int pn_cng_sid_decode(const uint8_t *sid14, float *g, float *k12, int
   return 0;
 }
 extern "C" float pn_cng_level(int L) { if (L < 0 || L > 127) { pn_set_error("SID level %d: a level in [0, 127] -dBov", L); return NAN; } return pn_kCngLevel[L]; }
+extern "C" int pn_dtx_default_params(float *params9) { if (!params9) { pn_set_error("NULL argument"); return -1; } pn_dtx_default_params_host(params9); return 0; }
+extern "C" int pn_dtx_params_check(const float *params9) { return pn_dtx_params_check_host(params9); }
+extern "C" int pn_dtx_frame(const float *params9, uint32_t *state24, const float *row, int n, uint32_t *report8) { return pn_dtx_frame_host(params9, state24, row, n, report8); }
+extern "C" int pn_dtx_sid_from_acorr(const float *R13, int order, uint8_t *sid14) { return pn_dtx_sid_from_acorr_host(R13, order, sid14); }
+extern "C" int pn_dtx_level(float mean_square) { return pn_dtx_level_hd(mean_square); }
 extern "C" int pn_cng_frame(const uint8_t *sid14, uint32_t *state16, uint32_t seed, int slot, int cont, int n, float *row, uint32_t *report4) {
   PnCngSid d;
   if (slot < 0) { pn_set_error("stream slot %d", slot); return -1; }
@@ -398,6 +411,7 @@ static pn_rate *rate_create(pn_ctx *c, int rate_hz, int f, const int32_t *rates_
   r->lim_ceilings.assign(B, 0.0f); pn_lim_default_params_host(r->lim_params);
   r->dtmf_sw.assign(B, 0); pn_dtmf_default_params_host(r->dtmf_params);
   r->clamp_sw.assign(B, 0); pn_dtmf_clamp_default_params_host(r->clamp_params);
+  r->dtx_sw.assign(B, 0); pn_dtx_default_params_host(r->dtx_params);
   r->sids.assign(B * PN_CNG_SID_BYTES, 0);
   for (size_t s = 0; s < B; s++) pn_cng_default_sid(&r->sids[s * PN_CNG_SID_BYTES]);
   static const int kF[4] = {6, 3, 2, PN_RATE_F_3_2};   // (the order of pn_rate.hip rt_taps_offset; the h of 32000 is the table of 3 and is not staged twice)
@@ -862,6 +876,43 @@ extern "C" int pn_rate_debug_set_dtmf_report(pn_rate *r, const void *h_report) {
   return 0;
 }
 
+// ---- the DTX send side (include/percepnet_hip.h; the rule pn_dtx_rules.h; the kernel pn_rate_dtx.hip) ------------------------------------
+static int dtx_buffers(pn_rate *r) {                 // (the caller is on the context's device)
+  if (r->d_dtx_on) return 0;
+  int *on = NULL; void *st = NULL;
+  if (rate_alloc(r, on, (size_t)r->c->B * 4, true) || rate_alloc(r, st, (size_t)r->c->B * PN_DTX_STATE_WORDS * 4, true)) return -1;
+  r->st2[PN_RS2_DTX] = st; r->d_dtx_on = on;
+  return 0;
+}
+extern "C" int pn_rate_set_stream_dtx(pn_rate *r, const int32_t *ids, int n, const uint8_t *on) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (pn_dtx_on_set_check(r->c->B, ids, n, on)) return -1;
+  std::vector<int32_t> v, fresh;
+  switch_words(r->dtx_sw, ids, n, on, v, fresh);
+  return rate_set_words(r, ids, n, v.data(), (int32_t)0, r->d_dtx_on, dtx_buffers, r->dtx_sw, r->dtx_on, [&] { return state_switch_on(r, PN_RST_DTX, fresh); });
+}
+extern "C" int pn_rate_get_stream_dtx(const pn_rate *r, uint8_t *h_on) { return rate_get(r, &pn_rate::dtx_sw, h_on); }
+// the parameters travel as an argument of every launch, so a change is ordered like one
+extern "C" int pn_rate_set_dtx_params(pn_rate *r, const float *params9) {
+  if (!r) { pn_set_error("NULL argument"); return -1; }
+  if (pn_dtx_params_check_host(params9)) return -1;
+  memcpy(r->dtx_params, params9, sizeof(r->dtx_params));
+  return 0;
+}
+extern "C" int pn_rate_get_dtx_params(const pn_rate *r, float *params9) { return rate_get_params(r, &pn_rate::dtx_params, params9); }
+extern "C" int pn_rate_set_dtx_report(pn_rate *r, int enable) { return rate_set_report(r, RF_DTX, enable); }
+extern "C" int pn_rate_read_dtx_report(pn_rate *r, void *h_report) { return rate_report_copy(r, RF_DTX, h_report, hipMemcpyDeviceToHost); }
+extern "C" int pn_rate_read_dtx_report_dev(pn_rate *r, void *d_report) { return rate_report_copy(r, RF_DTX, d_report, hipMemcpyDeviceToDevice); }
+extern "C" int pn_rate_debug_dtx_state(pn_rate *r, void *h_state) {
+  if (!r || !h_state) { pn_set_error("NULL argument"); return -1; }
+  const size_t bytes = (size_t)r->c->B * PN_DTX_STATE_WORDS * 4;
+  if (!r->st2[PN_RS2_DTX]) { memset(h_state, 0, bytes); return 0; }
+  PN_ON_DEVICE(r->c);
+  PN_HIP_CHECK(hipMemcpyAsync(h_state, r->st2[PN_RS2_DTX], bytes, hipMemcpyDeviceToHost, r->c->stream));
+  PN_HIP_CHECK(hipStreamSynchronize(r->c->stream));
+  return 0;
+}
+
 // ---- the two resets: what they clear is the state table's ------------------------------------------------------------------------
 extern "C" int pn_rate_reset(pn_rate *r) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
@@ -976,6 +1027,14 @@ static int rate_cng(pn_rate *r, float *d_x48, const std::vector<int32_t> &gen) {
   const RateRows rows = {d, n};
   return rate_up(r, r->cng_rows, PN_FMT_F32, d_x48, rows);
 }
+// the DTX send side over the OUTPUT rows (fmt: their format), which it only reads: rows strided like an output row
+static int rate_dtx(pn_rate *r, const void *d_out, int fmt, const RateRows &rows) {
+  if (rows.n <= 0) return 0;                         // (an empty list: nothing to launch, nothing to time)
+  int rc = 0;
+  if (rate_timed(r, RF_DTX, [&] { rc = pn_launch_rate_dtx(r->c->stream, fmt, rows.n, rows.d_ids, r->d_dtx_on, r->mixed ? r->factors : NULL, r->n, r->d_laws, r->dtx_params, d_out, r->n,
+                                                         r->st2[PN_RS2_DTX], rate_report(r, RF_DTX)); })) return -1;
+  return rc;
+}
 // The stand-alone stage calls.  Their prologue: the converter, `off` (the stage's switch is off: its message), the rows' alignment —
 // then RATE_STAGE_ROWS: the context's device for the rest of the call, and the rows
 static int rate_stage_check(const pn_rate *r, const void *a, const void *b, const char *off = NULL) {
@@ -1033,6 +1092,15 @@ extern "C" int pn_rate_dtmf_clamp_f32(pn_rate *r, float *d_y48, const int32_t *i
   RATE_STAGE_ROWS(r, ids, n_ids);
   return clamp_buffers(r) ? -1 : rate_clamp(r, d_y48, rows, true);
 }
+// (where the stage was never used every stream is off, and its device side exists from here on)
+static int rate_dtx_call(pn_rate *r, const void *d_out, int fmt, const int32_t *ids, int n) {
+  if (rate_stage_check(r, d_out, d_out)) return -1;
+  RATE_STAGE_ROWS(r, ids, n);
+  return dtx_buffers(r) ? -1 : rate_dtx(r, d_out, fmt, rows);
+}
+extern "C" int pn_rate_dtx_f32(pn_rate *r, const float *d_out_rows, const int32_t *ids, int n_ids) { return rate_dtx_call(r, d_out_rows, PN_FMT_F32, ids, n_ids); }
+extern "C" int pn_rate_dtx_i16(pn_rate *r, const int16_t *d_out_rows, const int32_t *ids, int n_ids) { return rate_dtx_call(r, d_out_rows, PN_FMT_I16, ids, n_ids); }
+extern "C" int pn_rate_dtx_g711(pn_rate *r, const uint8_t *d_out_rows, const int32_t *ids, int n_ids) { return rate_dtx_call(r, d_out_rows, PN_FMT_G711, ids, n_ids); }
 // comfort noise on its own: every listed stream's row is generated and up-converted into d_x48, marked or not; like a frame it moves the
 // tick on and drops the marks
 extern "C" int pn_rate_cng_f32(pn_rate *r, float *d_x48, const int32_t *ids, int n_ids) {
@@ -1048,7 +1116,7 @@ extern "C" int pn_rate_cng_f32(pn_rate *r, float *d_x48, const int32_t *ids, int
 
 // ---- one whole frame -----------------------------------------------------------------------------------------------------------
 // up into x48 — for the streams marked silent while comfort noise is on, from the rows its kernel writes —, while packet-loss concealment is on the concealer in place on x48, the engine's float frame from x48 into y48 (all streams, or the listed ones through the context's own active
-// set), while automatic level control is on and a stream has a target the level control in place on y48, down from y48 — or, while a stream is in a conference, the mix from y48 into o48 and down from o48 — and in front of the down-conversion, while a stream has a ceiling, the output limiter in place on the rows it reads.  A frame the engine refuses returns -1 with its error kept; the up kernel has then advanced its tails
+// set), while automatic level control is on and a stream has a target the level control in place on y48, down from y48 — or, while a stream is in a conference, the mix from y48 into o48 and down from o48 — and in front of the down-conversion, while a stream has a ceiling, the output limiter in place on the rows it reads; behind it, while a stream has the DTX send side on, that stage reading the output rows.  A frame the engine refuses returns -1 with its error kept; the up kernel has then advanced its tails
 // and the down kernel has not, which is why the header asks for a reset of both objects before reuse.
 // rate_frame: the launches alone — the caller is on the context's device and has checked the rows and, when active, the list
 // (pn_ids_check, distinct), which is what lets the pipelined path refuse a list BEFORE the frame takes a pipeline slot.
@@ -1103,6 +1171,8 @@ static int rate_frame(pn_rate *r, const void *d_in, void *d_out, float *d_gr, in
   // the output limiter, while somebody has a ceiling: in place on the rows the down-conversion reads — mix rows, or the streams' own
   if (r->lim_on > 0 && rate_lim(r, o, rows)) return -1;
   if (rate_down(r, o, d_out, fmt, rows)) return -1;
+  // the DTX send side, while somebody is switched on: behind the down-conversion, reading the rows the caller is about to send
+  if (r->dtx_on > 0 && rate_dtx(r, d_out, fmt, rows)) return -1;
   if (r->events.size() >= 4096 && rate_flush_events(r)) return -1;   // profiling left on: bound the pending events
   return 0;
 }
@@ -1188,9 +1258,9 @@ extern "C" int pn_rate_submit_host_g711_active(pn_rate *r, const uint8_t *h_in, 
 // ---- timing the kernels --------------------------------------------------------------------------------------------------------
 extern "C" int pn_rate_set_profiling(pn_rate *r, int enable) {
   if (!r) { pn_set_error("NULL argument"); return -1; }
-  if (enable && r->event_pool.size() < 1280) {        // up to ten scopes a frame (up, cng, up, plc, dtmf, clamp, agc, mix, lim, down): enough for 64 frames between two reads; created outside any timed region
+  if (enable && r->event_pool.size() < 1408) {        // up to eleven scopes a frame (up, cng, up, plc, dtmf, clamp, agc, mix, lim, down, dtx): enough for 64 frames between two reads; created outside any timed region
     PN_ON_DEVICE(r->c);
-    while (r->event_pool.size() < 1280) { hipEvent_t e; PN_HIP_CHECK(hipEventCreate(&e)); r->event_pool.push_back(e); }
+    while (r->event_pool.size() < 1408) { hipEvent_t e; PN_HIP_CHECK(hipEventCreate(&e)); r->event_pool.push_back(e); }
   }
   r->profiling = enable != 0;
   return 0;
@@ -1201,7 +1271,7 @@ extern "C" int pn_rate_kernel_time(pn_rate *r, const char *name, double *total_m
   if (rate_flush_events(r)) return -1;
   for (int i = 0; i < RF_COUNT; i++)
     if (!strcmp(name, kRateStage[i].family)) { if (total_ms) *total_ms = r->fam_ms[i]; if (launches) *launches = r->fam_n[i]; return 0; }
-  pn_set_error("unknown converter kernel '%s' (rate_up, rate_down, rate_mix, rate_plc, rate_agc, rate_lim, rate_dtmf, rate_clamp, rate_cng)", name);
+  pn_set_error("unknown converter kernel '%s' (rate_up, rate_down, rate_mix, rate_plc, rate_agc, rate_lim, rate_dtmf, rate_clamp, rate_cng, rate_dtx)", name);
   return -1;
 }
 extern "C" int pn_rate_reset_profile(pn_rate *r) {

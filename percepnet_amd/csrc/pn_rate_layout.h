@@ -20,6 +20,7 @@
 #include "pn_dtmf_clamp_rules.h"   // DTMF removal
 #include "pn_dtmf_rules.h"         // DTMF detection
 #include "pn_cng_rules.h"          // comfort noise
+#include "pn_dtx_rules.h"          // the DTX send side
 
 enum { PN_RS_TAIL_UP, PN_RS_TAIL_DOWN, PN_RS_LEVEL, PN_RS_PLC_HIST, PN_RS_PLC_Q, PN_RS_PLC_META, PN_RS_AGC, PN_RS_LIM, PN_RS_DTMF, PN_RS_CLAMP, PN_RS_COUNT };
 enum { PN_RST_CORE, PN_RST_MIX, PN_RST_PLC, PN_RST_AGC, PN_RST_LIM, PN_RST_DTMF, PN_RST_CLAMP, PN_RST_COUNT };      // the owning stage
@@ -55,15 +56,18 @@ static constexpr PnRateStateEntry pn_kRateState[PN_RS_COUNT] = {
     {PN_DTMF_CLAMP_STATE_WORDS, PN_RST_CLAMP, PN_RE_ANY_RESET | PN_RE_IMPORT | PN_RE_SWITCH_ON,   0,           -1,              0},                        // clamp
 };
 
-// The SECOND table: state of stages IN FRONT of the up-conversion, entries of the same type, held as pn_rate::st2[entry] and walked by
-// the same two walks behind the first.  It stands apart because the first is pinned at its ten entries and seven stages
-// (tests/c/rate_layout_sanitize.cpp), so its stages count on from PN_RST_COUNT.  Comfort noise (pn_cng_rules.h): cleared by the whole
-// reset, the per-stream reset, a rate change (the lattice ran at the old rate), the tails-record import (the slot is another stream's)
-// and "on again"; a conference, hold or switch change leaves it.  It travels in no record.
-enum { PN_RS2_CNG, PN_RS2_COUNT };
-enum { PN_RST_CNG = PN_RST_COUNT };
+// The SECOND table: state of the stages at the converter's EDGES, at the streams' own rates — in front of the up-conversion and behind
+// the down-conversion —, entries of the same type, held as pn_rate::st2[entry] and walked by the same two walks behind the first.  It
+// stands apart because the first is pinned at its ten entries and seven stages (tests/c/rate_layout_sanitize.cpp), so its stages count
+// on from PN_RST_COUNT.  Comfort noise (pn_cng_rules.h): cleared by the whole reset, the per-stream reset, a rate change (the lattice
+// ran at the old rate), the tails-record import (the slot is another stream's) and "on again"; a conference, hold or switch change
+// leaves it.  The DTX send side (pn_dtx_rules.h): cleared by the same resets, the rate change (the statistics are of the old rate's
+// rows), the import, and for a stream that is switched on from off; a conference or hold change leaves it.  Neither travels in a record.
+enum { PN_RS2_CNG, PN_RS2_DTX, PN_RS2_COUNT };
+enum { PN_RST_CNG = PN_RST_COUNT, PN_RST_DTX };
 static constexpr PnRateStateEntry pn_kRateState2[PN_RS2_COUNT] = {
     {PN_CNG_STATE_WORDS,        PN_RST_CNG,   PN_RE_ANY_RESET | PN_RE_IMPORT | PN_RE_AGAIN,       0,           -1,              0},                        // cng
+    {PN_DTX_STATE_WORDS,        PN_RST_DTX,   PN_RE_ANY_RESET | PN_RE_IMPORT | PN_RE_SWITCH_ON,   0,           -1,              0},                        // dtx
 };
 constexpr bool pn_rate_state2_cleared(int e, unsigned event, int stage = -1) {
   return (pn_kRateState2[e].clears & event) != 0 && (stage < 0 || pn_kRateState2[e].stage == stage);
